@@ -6,10 +6,13 @@ arena after backward. For N > 1 either a launcher starts the ranks (`python -m t
 bench.py --gpus N ...`: WORLD_SIZE is set and must equal N) or, run bare, bench.py starts that launcher itself as a
 child process before anything touches the GPU and relays rank 0's line (launch_ranks below); fewer than N visible
 GPUs is an error, never a smaller run under the asked-for label.
-Rank 0 prints ONE JSON line: whole-job throughput, the roofline of the dominant kernel class (durations
-measured live with HIP events on the launch stream, inside the timed region: every 4th timed step carries the
-per-class event timers -- `profiled_steps` in the output -- because ~200 event records per step cost 4 % of a
-ResNet step; BENCH_PROFILE_EVERY=1 times every step) and a CPU baseline (the unmodified reference,
+Rank 0 prints ONE JSON line. A plain run does only what its headline needs: set-up, warm-up, exactly K timed steps,
+the outputs of the last timed step if --dump-outputs DIR is given, and the line with the whole-job throughput
+(`value`, images/s) and `ms_per_step`. --full adds everything else, as before: the roofline of the dominant kernel
+class (durations measured live with HIP events on the launch stream, inside the timed region: every 4th timed step
+carries the per-class event timers -- `profiled_steps` in the output -- because ~200 event records per step cost 4 % of
+a ResNet step; BENCH_PROFILE_EVERY=1 times every step), the per-class tables (also from an untimed leg with every kernel
+on one stream), the side workloads of the default single-GPU run and a CPU baseline (the unmodified reference,
 oracle/_ref, timed on this host on a bounded sample; single-GPU runs only).
 Data-parallel runs overlap the gradient all-reduce with backward (bcnn_amd/dp.py); --no-overlap disables it.
 
@@ -139,8 +142,32 @@ def cpu_baseline(workload, sample_n):
     return out
 
 
-# (tests that compare parameter checksums between two runs need the same number of steps in both: no stretching there)
+# (tests that compare parameter checksums between two runs need the same number of steps in both: no stretching there;
+# the same holds for --dump-outputs, see main)
 MIN_WARM_S = 0.0 if os.environ.get("BENCH_TEST_CHECKSUM") == "1" else float(os.environ.get("BENCH_MIN_WARM_S", "0.08"))
+
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: all files of one run together
+
+
+def dump_outputs(dirname, outputs):
+    """Write the arrays of `outputs` (name -> (device tensor, at most this many elements)) as DIR/<name>.npy, float32.
+    A tensor larger than its allowance is written as a fixed sample: sorted indices drawn by a RandomState seeded with 0
+    from the flattened tensor, so two runs with the same arguments sample the same elements."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, (t, limit) in outputs.items():
+        flat = t.detach().reshape(-1)
+        if flat.numel() > limit:
+            idx = np.sort(np.random.RandomState(0).randint(0, flat.numel(), size=limit, dtype=np.int64))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+            arr = flat.float().cpu().numpy()
+        else:
+            arr = flat.float().cpu().numpy().reshape(tuple(t.shape))
+        total += arr.nbytes
+        assert total <= DUMP_LIMIT_BYTES, "bench.py: --dump-outputs would write more than %d bytes" % DUMP_LIMIT_BYTES
+        np.save(os.path.join(dirname, name + ".npy"), arr)
 
 
 def read_profile(L):
@@ -332,6 +359,18 @@ class Workload:
                         torch.cuda.synchronize()
                 net.update()
             self.step = step
+
+            def outputs():
+                """what a caller of the training step receives: the network's output (softmax) of the step's forward and
+                the parameters after its update; the gradient arena (the momentum carry after the update) as a sample"""
+                prob = net.tensor(net.index("prob"))
+                pptr, psize = net.parameter_arena()
+                gptr, gsize = net.gradient_arena()
+                return {"prob": (torch.as_tensor(capi.DeviceArray(prob.data_gpu, prob.n * prob.c * prob.h * prob.w),
+                                                 device=dev).view(prob.n, prob.c * prob.h * prob.w), 1 << 20),
+                        "params": (torch.as_tensor(capi.DeviceArray(pptr, psize), device=dev), 12 << 20),
+                        "grad_arena": (torch.as_tensor(capi.DeviceArray(gptr, gsize), device=dev), 2 << 20)}
+            self.outputs = outputs
             if name == "resnet18":
                 self.desc = ("ResNet-18 224x224 (BASELINE configs[2]), N=%d per GPU, fwd+bwd+SGD through bcnn_net C API; "
                              "CIFAR-example topology + ImageNet stem, fc-1000" % n)
@@ -376,17 +415,21 @@ class Workload:
                     dist.all_reduce(grads)
                     torch.cuda.synchronize()
             self.step = step
+            # what forward + backward hand their caller: the output, the weight and bias gradients (and dX)
+            self.outputs = lambda: dict({"y": (y, 8 << 20), "dw": (dw, 1 << 20), "db": (db, 1 << 20)},
+                                        **({"dx": (dxg, 4 << 20)} if input_grad else {}))
             self.desc = ("conv3x3 s1 p1, N=%d x 3 x 224 x 224 -> 64 (BASELINE configs[1]), fwd + bwd(dW, dbias%s)"
                          % (n, ", dX: variant with a gradient-carrying source" if input_grad else
                             "); no dX: the layer's source is the net input"))
             self.sample_n = 16
             self.default_n = 128
 
-    def run(self, steps, warmup):
+    def run(self, steps, warmup, profile=False, min_warm_s=MIN_WARM_S):
         """W untimed steps, then exactly K timed steps between barrier + synchronize; returns (seconds, per-class
-        profile, profiled steps). The per-class HIP-event timers cost ~3.5 us of GPU pipeline per event (~200 events
-        per ResNet step = 4 % of the step), so inside the timed region they sample every PROFILE_EVERY-th step
-        instead of all of them; the averages they give are per profiled launch, the throughput is over all steps."""
+        profile, profiled steps). With `profile` (--full) the per-class HIP-event timers run inside the timed region;
+        they cost ~3.5 us of GPU pipeline per event (~200 events per ResNet step = 4 % of the step), so they sample
+        every PROFILE_EVERY-th step instead of all of them; the averages they give are per profiled launch, the
+        throughput is over all steps. Without `profile` no timer runs and the profile is empty."""
         import torch
         import torch.distributed as dist
         L = self.L
@@ -406,14 +449,14 @@ class Workload:
             spent = torch.tensor([time.perf_counter() - tw], dtype=torch.float64, device=self.dev if dist.get_backend() == "nccl" else "cpu")
             dist.all_reduce(spent, op=dist.ReduceOp.MAX)
             spent = float(spent.item())
-            per_step = spent / warmup if warmup > 0 else MIN_WARM_S / 4
-            extra = int(max(0.0, MIN_WARM_S - spent) / max(per_step, 1e-6) + 0.999)
+            per_step = spent / warmup if warmup > 0 else min_warm_s / 4
+            extra = int(max(0.0, min_warm_s - spent) / max(per_step, 1e-6) + 0.999)
             for _ in range(min(extra, 1000)):
                 self.step()
                 self.warmup_extra += 1
             L.bcnn_hip_sync()
         else:
-            while time.perf_counter() - tw < MIN_WARM_S:
+            while time.perf_counter() - tw < min_warm_s:
                 self.step()
                 L.bcnn_hip_sync()
                 self.warmup_extra += 1
@@ -425,7 +468,7 @@ class Workload:
             dist.barrier()
         t0 = time.perf_counter()
         for it in range(steps):
-            prof_on = (it % profile_every) == 0
+            prof_on = profile and (it % profile_every) == 0
             L.bcnn_hip_profile_enable(1 if prof_on else 0)
             profiled += 1 if prof_on else 0
             self.step()
@@ -435,11 +478,15 @@ class Workload:
             dist.barrier()
         dt = time.perf_counter() - t0
         L.bcnn_hip_profile_enable(0)
-        prof = read_profile(L)
-        # `alone` leg, OUTSIDE the timed region: a few more steps with the weight gradients on the caller's stream
-        # (bcnn_set_weight_gradient_stream(net, 0)), every launch timed -- what each kernel class takes when it has the chip to
-        # itself. Inside the timed region the weight gradients run next to the sweeps and data gradients of the layers in
-        # front, and a class's events span the time it shares the chip.
+        prof = read_profile(L) if profile else {}
+        return dt, prof, profiled
+
+    def time_alone(self):
+        """--full only, after run(): the `alone` leg, OUTSIDE the timed region: a few more steps with the weight gradients
+        on the caller's stream (bcnn_set_weight_gradient_stream(net, 0)), every launch timed -- what each kernel class
+        takes when it has the chip to itself. Inside the timed region the weight gradients run next to the sweeps and
+        data gradients of the layers in front, and a class's events span the time it shares the chip."""
+        L = self.L
         self.prof_alone = None
         if self.net is not None and self.world == 1 and os.environ.get("BENCH_NO_ALONE_LEG") != "1":
             capi_lib = self.net.L
@@ -453,7 +500,6 @@ class Workload:
             L.bcnn_hip_profile_enable(0)
             self.prof_alone = (read_profile(L), 3)
             capi_lib.bcnn_set_weight_gradient_stream(self.net.net, 1)
-        return dt, prof, profiled
 
     def close(self):
         self.L.bcnn_hip_sync()
@@ -522,10 +568,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="resnet18", choices=["resnet18", "conv3x3", "mobilenet"])
     ap.add_argument("--batch", type=int, default=None, help="images per GPU (default 128; 256 for mobilenet)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also report what the headline does not need: per-class timers inside the timed region, roofline, "
+                         "per-class tables (also from an untimed one-stream leg), the side workloads and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB, larger arrays "
+                         "as a fixed sample); the warm-up then runs exactly --warmup steps (no stretch by wall time), so "
+                         "that the same arguments give the same outputs in every run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--no-side-workloads", action="store_true",
-                    help="single-GPU default run only: skip the short conv3x3 (configs[1]) and mobilenet (configs[4]) "
-                         "timings reported under `workloads`")
+                    help="--full, single-GPU default run only: skip the short conv3x3 (configs[1]) and mobilenet "
+                         "(configs[4]) timings reported under `workloads`")
     ap.add_argument("--input-grad", action="store_true",
                     help="conv3x3 only: give the source a gradient so that backward also runs dX (SURVEY.md 8d, config #2 variant)")
     ap.add_argument("--comm", default="torch", choices=["torch", "inlib"],
@@ -588,7 +641,13 @@ def main():
 
     overlap = not args.no_overlap and os.environ.get("BENCH_NO_OVERLAP") != "1"
     wl = Workload(args.workload, n, rank, world, dev, L, stream, input_grad=args.input_grad, overlap=overlap, comm=args.comm)
-    dt, prof, profiled_steps = wl.run(args.steps, args.warmup)
+    # --dump-outputs: the state the last timed step starts from must not depend on the wall clock (MIN_WARM_S above)
+    dt, prof, profiled_steps = wl.run(args.steps, args.warmup, profile=args.full,
+                                      min_warm_s=0.0 if args.dump_outputs else MIN_WARM_S)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, wl.outputs())
+    if args.full:
+        wl.time_alone()
 
     def with_alone(roof, w, workload):
         """the dominant class once more from the untimed `alone` leg (weight gradients on the caller's stream)"""
@@ -618,17 +677,20 @@ def main():
                        "comm": ("none (one rank)" if world == 1 and os.environ.get("BENCH_FORCE_DP") != "1" else
                                 "in-library RCCL (csrc/comm.hip, bcnn_set_data_parallel_comm)" if args.comm == "inlib" else
                                 "torch.distributed (%s)" % dist.get_backend())},
-            "roofline": with_alone(roofline_of(prof, args.workload, default_shape), wl, args.workload),
-            "profiled_steps": profiled_steps,
-            "kernel_classes": class_table(prof, profiled_steps),
-            "kernel_classes_alone": class_table(*wl.prof_alone) if getattr(wl, "prof_alone", None) else None,
-            # bcnn_backward queues the weight-gradient kernels on a second HIP stream of the library (include/bcnn_hip.h:
-            # bcnn_hip_conv_side_stream_mode), where they run next to the batch-norm / pooling sweeps and the data gradients
-            # of the layers in front. Each class is timed with HIP events on the stream its kernels are launched on, so the
-            # *_dw classes overlap the others in time: the classes' sum exceeds ms_per_step, and a class's rate is what it
-            # reaches while it shares the chip.
-            "streams": "weight gradients on a second stream: per-class times overlap (sum > ms_per_step)",
         }
+        if args.full:
+            out.update({
+                "roofline": with_alone(roofline_of(prof, args.workload, default_shape), wl, args.workload),
+                "profiled_steps": profiled_steps,
+                "kernel_classes": class_table(prof, profiled_steps),
+                "kernel_classes_alone": class_table(*wl.prof_alone) if getattr(wl, "prof_alone", None) else None,
+                # bcnn_backward queues the weight-gradient kernels on a second HIP stream of the library (include/bcnn_hip.h:
+                # bcnn_hip_conv_side_stream_mode), where they run next to the batch-norm / pooling sweeps and the data
+                # gradients of the layers in front. Each class is timed with HIP events on the stream its kernels are
+                # launched on, so the *_dw classes overlap the others in time: the classes' sum exceeds ms_per_step, and a
+                # class's rate is what it reaches while it shares the chip.
+                "streams": "weight gradients on a second stream: per-class times overlap (sum > ms_per_step)",
+            })
         if os.environ.get("BENCH_TEST_CHECKSUM") == "1" and wl.net is not None:
             pptr, psize = wl.net.parameter_arena()
             params = torch.as_tensor(capi.DeviceArray(pptr, psize), device=dev)
@@ -640,13 +702,14 @@ def main():
     # The other single-GPU configurations of BASELINE.json, timed briefly by the same process so that the driver's
     # clock covers them too: configs[1] (the 3x3 conv `north_star` quotes its >= 50 % MFMA target on) and configs[4]
     # (MobileNet-v1, the HBM-bound config). Same step definition and timers as above; `value` stays the headline's.
-    if rank == 0 and world == 1 and args.workload == "resnet18" and args.batch is None and not args.no_side_workloads \
-            and os.environ.get("BENCH_FORCE_DP") != "1":
+    if args.full and rank == 0 and world == 1 and args.workload == "resnet18" and args.batch is None \
+            and not args.no_side_workloads and os.environ.get("BENCH_FORCE_DP") != "1":
         side = {}
         for name, sn, ssteps, swarm in (("conv3x3", 128, 40, 3), ("mobilenet", 256, 6, 2)):
             torch.cuda.empty_cache()
             w2 = Workload(name, sn, 0, 1, dev, L, stream)
-            sdt, sprof, sprofiled = w2.run(ssteps, swarm)
+            sdt, sprof, sprofiled = w2.run(ssteps, swarm, profile=True)
+            w2.time_alone()
             side[name] = {"config": w2.desc, "images_per_s": round(ssteps * sn / sdt, 2),
                           "ms_per_step": round(sdt / ssteps * 1e3, 4), "steps": ssteps, "warmup": swarm,
                           "warmup_extra": w2.warmup_extra,
@@ -660,7 +723,7 @@ def main():
                 side[name]["cpu_baseline"] = cpu_baseline(name, side_sample)
         out["workloads"] = side
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:  # reported by the single-GPU run only
+        if args.full and not args.no_cpu_baseline and world == 1:  # reported by the single-GPU run only
             out["cpu_baseline"] = cpu_baseline(args.workload, sample_n)
         line = json.dumps(out)
     if dist.is_initialized():

@@ -1,11 +1,13 @@
 """bench.py prints ONE JSON line with the fields the driver reads (metric / value / unit / n_gpus / steps / warmup /
-ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload) plus the `roofline` and
-`cpu_baseline` objects; checked here on a short run so that a broken bench shows up in the GPU suite."""
+ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload); with --full also the `roofline`
+and `cpu_baseline` objects. A plain run writes the outputs of its last timed step with --dump-outputs. Checked here on
+short runs so that a broken bench shows up in the GPU suite."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.parametrize("workload", ["resnet18", "conv3x3", "mobilenet"])
 def test_bench_prints_the_contract_line(workload):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--workload", workload], cwd=ROOT, capture_output=True, text=True, timeout=900)
+                        "--workload", workload, "--full"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -43,3 +45,36 @@ def test_bench_prints_the_contract_line(workload):
     assert cpu["host_cores"] == os.cpu_count()
     if "winograd" in roof["kernel"]:
         assert 0 < roof["frac_unpadded"] <= roof["frac"]
+
+
+def _plain_run(workload, dump_dir):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--workload", workload, "--dump-outputs", str(dump_dir)], cwd=ROOT, capture_output=True, text=True,
+                       timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("workload,names", [("resnet18", {"prob", "params", "grad_arena"}), ("conv3x3", {"y", "dw", "db"})])
+def test_plain_run_is_lean_and_dumps_the_same_outputs_every_time(tmp_path, workload, names):
+    """without --full: the headline fields only (no profiling, side workloads or CPU baseline); --dump-outputs writes the
+    last timed step's arrays as float .npy files, at most 64 MB in all, identical in two runs with the same arguments"""
+    a = _plain_run(workload, tmp_path / "a")
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup"):
+        assert key in a, key
+    assert a["steps"] == 3 and a["warmup"] == 1 and a["warmup_extra"] == 0 and a["value"] > 0 and a["ms_per_step"] > 0
+    assert a["metric"] == "images/sec fwd+bwd" and a["unit"] == "images/s" and a["higher_is_better"] is True
+    assert abs(a["value"] - 3 * a["config"]["batch_per_gpu"] / (a["ms_per_step"] * 3e-3)) < 1e-2 * a["value"]
+    for key in ("roofline", "kernel_classes", "kernel_classes_alone", "cpu_baseline", "workloads"):
+        assert key not in a, key
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert {f[:-4] for f in files} == names and all(f.endswith(".npy") for f in files)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    _plain_run(workload, tmp_path / "b")
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and x.size > 0 and np.isfinite(x).all(), f
+        assert x.shape == y.shape and np.array_equal(x, y), f

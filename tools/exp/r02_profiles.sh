@@ -10,9 +10,10 @@ NAME=resnet18 bash tools/exp/bench_trace.sh | head -3
 NAME=conv3x3 BENCH_ARGS="--workload conv3x3" bash tools/exp/bench_trace.sh | head -3
 NAME=mobilenet BENCH_ARGS="--workload mobilenet" bash tools/exp/bench_trace.sh | head -3
 cd $GRAFT_REPO_ROOT
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"   # where the bench lines below go
 for wl in resnet18 conv3x3 mobilenet; do
-  python3 bench.py --workload $wl --steps 20 --warmup 5 --no-side-workloads > gpurun_out/r02_bench_$wl.json 2> gpurun_out/r02_bench_$wl.err
-  tail -c 200 gpurun_out/r02_bench_$wl.json; echo
+  python3 bench.py --full --workload $wl --steps 20 --warmup 5 --no-side-workloads > $OUT/r02_bench_$wl.json 2> $OUT/r02_bench_$wl.err
+  tail -c 200 $OUT/r02_bench_$wl.json; echo
 done
-python3 bench.py > gpurun_out/r02_bench_default_line.json 2> gpurun_out/r02_bench_default_line.err
-tail -c 200 gpurun_out/r02_bench_default_line.json; echo
+python3 bench.py --full > $OUT/r02_bench_default_line.json 2> $OUT/r02_bench_default_line.err
+tail -c 200 $OUT/r02_bench_default_line.json; echo

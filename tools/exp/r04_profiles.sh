@@ -11,12 +11,13 @@ ROUND=r04 NAME=resnet18 bash tools/exp/bench_trace.sh | head -3
 ROUND=r04 NAME=conv3x3 BENCH_ARGS="--workload conv3x3" bash tools/exp/bench_trace.sh | head -3
 ROUND=r04 NAME=mobilenet BENCH_ARGS="--workload mobilenet" bash tools/exp/bench_trace.sh | head -3
 cd $GRAFT_REPO_ROOT
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"   # where the bench lines below go
 for wl in resnet18 conv3x3 mobilenet; do
-  python3 bench.py --workload $wl --steps 20 --warmup 5 --no-side-workloads > gpurun_out/r04_bench_$wl.json 2> gpurun_out/r04_bench_$wl.err
-  tail -c 200 gpurun_out/r04_bench_$wl.json; echo
+  python3 bench.py --full --workload $wl --steps 20 --warmup 5 --no-side-workloads > $OUT/r04_bench_$wl.json 2> $OUT/r04_bench_$wl.err
+  tail -c 200 $OUT/r04_bench_$wl.json; echo
 done
-python3 bench.py > gpurun_out/r04_bench_default_line.json 2> gpurun_out/r04_bench_default_line.err
-tail -c 200 gpurun_out/r04_bench_default_line.json; echo
+python3 bench.py --full > $OUT/r04_bench_default_line.json 2> $OUT/r04_bench_default_line.err
+tail -c 200 $OUT/r04_bench_default_line.json; echo
 # SQ counters: every kernel of a ResNet-18 / MobileNet step, and the depthwise kernels stand-alone before (LDS-staged kernels,
 # experiment library with BCNN_HIP_NO_DW_MARCH=1) and after (marching kernels)
 cd $GRAFT_REPO_ROOT

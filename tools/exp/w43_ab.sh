@@ -10,7 +10,7 @@ for rep in 1 2; do
       PROF_BN=1 python tools/prof_layer.py $shape 3 1 1 40 2>&1 | grep -E "wino43|conv_fwd|conv_bwd_data" | head -4
     done
     echo "== $v rep $rep resnet18"
-    python bench.py --workload resnet18 --steps 12 --warmup 3 --no-cpu-baseline --no-side-workloads 2>/dev/null | tail -1 \
+    python bench.py --full --workload resnet18 --steps 12 --warmup 3 --no-cpu-baseline --no-side-workloads 2>/dev/null | tail -1 \
       | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'])"
   done
 done
