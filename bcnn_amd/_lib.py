@@ -112,6 +112,11 @@ SIGNATURES = {
     "bcnn_hip_axpy_strided": (None, [i, f, vp, vp] + [i] * 11),
     "bcnn_hip_add_rowvec": (None, [vp, vp, i, i]),
     "bcnn_hip_softmax_forward": (None, [vp, vp, i, i, i]),
+    "bcnn_hip_concat_forward": (None, [i, vp, vp, vp, i, i]),
+    "bcnn_hip_concat_backward": (None, [i, vp, vp, vp, i, i]),
+    "bcnn_hip_upsample_forward": (None, [vp, vp, i, i, i, i, i]),
+    "bcnn_hip_upsample_backward": (None, [vp, vp, i, i, i, i, i]),
+    "bcnn_hip_yolo_activate": (None, [vp, vp, i, i, i, i, i]),
     "bcnn_hip_comm_init": (None, [i, i, C.c_char_p]),
     "bcnn_hip_comm_destroy": (None, []),
     "bcnn_hip_comm_retain": (None, []),

@@ -26,6 +26,32 @@ class Tensor(C.Structure):
                 ("data_gpu", C.c_void_p), ("grad_data_gpu", C.c_void_p)]
 
 
+class Detection(C.Structure):
+    """struct bcnn_output_detection (include/bcnn/bcnn.h); prob / mask / the array itself come from calloc."""
+    _fields_ = [("num_classes", C.c_int), ("x", C.c_float), ("y", C.c_float), ("w", C.c_float), ("h", C.c_float),
+                ("prob", C.POINTER(C.c_float)), ("mask", C.POINTER(C.c_float)), ("objectness", C.c_float)]
+
+
+_libc = C.CDLL(None)
+_libc.free.argtypes, _libc.free.restype = [C.c_void_p], None
+
+
+def detections_to_list(dets, count):
+    """copies a bcnn_yolo_get_detections result into dicts (x, y, w, h, objectness, prob) and frees it as a C caller
+    would: free(prob), free(mask), free(array)"""
+    out = []
+    if not dets:
+        return out
+    for k in range(count):
+        d = dets[k]
+        out.append(dict(x=d.x, y=d.y, w=d.w, h=d.h, objectness=d.objectness,
+                        prob=np.array(d.prob[:d.num_classes], np.float32)))
+        _libc.free(C.cast(d.prob, C.c_void_p))
+        _libc.free(C.cast(d.mask, C.c_void_p))
+    _libc.free(C.cast(dets, C.c_void_p))
+    return out
+
+
 _lib = None
 
 
@@ -70,6 +96,9 @@ def lib():
         "bcnn_get_node_tensor": (i, [vp, i, i, i]), "bcnn_get_node_state": (vp, [vp, i, i]),
         "bcnn_forward_node": (i, [vp, i]), "bcnn_backward_node": (i, [vp, i]),
         "bcnn_load_net": (i, [vp, cp, cp]), "bcnn_save_weights": (i, [vp, cp]), "bcnn_load_weights": (i, [vp, cp]),
+        "bcnn_add_concat_layer": (i, [vp, i, C.POINTER(cp), cp]), "bcnn_add_upsample_layer": (i, [vp, i, cp, cp]),
+        "bcnn_add_yolo_layer": (i, [vp, i, i, i, i, C.POINTER(i), C.POINTER(f), cp, cp]),
+        "bcnn_yolo_get_detections": (C.POINTER(Detection), [vp, i, i, i, i, i, f, i, C.POINTER(i)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -136,6 +165,46 @@ class Net:
 
     def cost(self, src, label="label", dst="cost", scale=1.0):
         return self._added(self.L.bcnn_add_cost_layer(self.net, 0, 0, scale, src.encode(), label.encode(), dst.encode()))
+
+    def concat(self, srcs, dst):
+        """bcnn_add_concat_layer: srcs (tensor names) stacked along the channels"""
+        arr = (C.c_char_p * len(srcs))(*[x.encode() for x in srcs])
+        return self._added(self.L.bcnn_add_concat_layer(self.net, len(srcs), arr, dst.encode()))
+
+    def upsample(self, size, src, dst):
+        return self._added(self.L.bcnn_add_upsample_layer(self.net, size, src.encode(), dst.encode()))
+
+    def yolo(self, num, classes, mask, anchors, src, dst, coords=4):
+        """bcnn_add_yolo_layer: `mask` (num anchor indices), `anchors` (2 * total extents) or None (all 0.5 x total)"""
+        m = (C.c_int * len(mask))(*mask) if mask is not None else None
+        total = len(anchors) // 2 if anchors is not None else num
+        a = (C.c_float * len(anchors))(*anchors) if anchors is not None else None
+        return self._added(self.L.bcnn_add_yolo_layer(self.net, num, classes, coords, total, m, a, src.encode(),
+                                                       dst.encode()))
+
+    def get_detections(self, batch, w, h, netw, neth, thresh, relative):
+        """bcnn_yolo_get_detections, as a list of dicts (count includes the boxes NMS suppressed: objectness 0)"""
+        n = C.c_int(0)
+        dets = self.L.bcnn_yolo_get_detections(self.net, batch, w, h, netw, neth, thresh, relative, C.byref(n))
+        return detections_to_list(dets, n.value)
+
+    @classmethod
+    def load_net(cls, config_path, model_path=None, mode=MODE_PREDICT, silent=True):
+        """bcnn_load_net (bcnn or Darknet config dialect; a *.weights model selects Darknet); raises on failure"""
+        net = cls.__new__(cls)
+        net.L, net.net, net._node_io = lib(), C.c_void_p(), []
+        assert net.L.bcnn_init_net(C.byref(net.net), mode) == 0
+        if silent:
+            net.L.bcnn_set_log_context(net.net, None, LOG_SILENT)
+        st = net.L.bcnn_load_net(net.net, config_path.encode(), model_path.encode() if model_path else None)
+        if st != 0:
+            net.close()
+            raise RuntimeError("bcnn_load_net(%s) failed with status %d" % (config_path, st))
+        net.num_nodes = net.L.bcnn_get_num_nodes(net.net)
+        return net
+
+    def set_mode(self, mode):
+        return self.L.bcnn_set_mode(self.net, mode)
 
     def compile(self):
         assert self.L.bcnn_compile_net(self.net) == 0

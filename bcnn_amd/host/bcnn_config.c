@@ -172,13 +172,18 @@ typedef struct {
     int num_srcs;
     char *src_id[MAX_SRCS];
     char *dst_id;
+    int boxes_per_cell, num_anchors, num_classes, num_coords, num_anchor_vals; /* [yolo] */
+    int *anchors_mask;
+    float *anchors;
 } layer_param;
 
 static void lp_reset(layer_param *lp) {
     for (int i = 0; i < lp->num_srcs; ++i) free(lp->src_id[i]);
     free(lp->dst_id);
+    free(lp->anchors_mask);
+    free(lp->anchors);
     memset(lp, 0, sizeof(*lp));
-    lp->stride = 1; lp->n_filts = 1; lp->size = 3; lp->num_groups = 1; lp->rate = 1.0f;
+    lp->stride = 1; lp->n_filts = 1; lp->size = 3; lp->num_groups = 1; lp->rate = 1.0f; lp->num_coords = 4;
     lp->padding_type = BCNN_PADDING_SAME; lp->a = BCNN_ACT_NONE; lp->init = BCNN_FILLER_XAVIER;
     lp->cost = BCNN_METRIC_SSE; lp->loss = BCNN_LOSS_EUCLIDEAN;
 }
@@ -199,6 +204,21 @@ static void lp_set_srcs(layer_param *lp, const char *list) {
         if (!e) break;
         p = e + 1;
     }
+}
+
+/* comma-separated list -> number of entries; *out (calloc) gets each entry through atof (reference: bh_strsplit + atof/atoi) */
+static int split_floats(const char *list, float **out) {
+    int n = 1;
+    for (const char *p = list; *p; ++p) n += *p == ',';
+    *out = (float *)calloc((size_t)n, sizeof(float));
+    const char *p = list;
+    for (int i = 0; i < n; ++i) {
+        (*out)[i] = (float)atof(p);
+        const char *e = strchr(p, ',');
+        if (!e) break;
+        p = e + 1;
+    }
+    return n;
 }
 
 static void lp_set_lid(char **dst, int id) {
@@ -283,15 +303,28 @@ static void lp_set(bcnn_net *net, int section_idx, layer_param *lp, const char *
         lp_set_srcs(lp, "a,b");
         lp_set_lid(&lp->src_id[0], section_idx - 1);
         lp_set_lid(&lp->src_id[1], l >= 0 ? l + 1 : section_idx + l);
+    } else if (!strcmp(name, "boxes_per_cell")) lp->boxes_per_cell = atoi(val); /* the YOLO head: reference :792-818 */
+    else if (!strcmp(name, "num_anchors") || !strcmp(name, "num")) lp->num_anchors = atoi(val);
+    else if (!strcmp(name, "num_classes") || !strcmp(name, "classes")) lp->num_classes = atoi(val);
+    else if (!strcmp(name, "num_coords")) lp->num_coords = atoi(val);
+    else if (!strcmp(name, "anchors")) {
+        free(lp->anchors);
+        lp->num_anchor_vals = split_floats(val, &lp->anchors);
+    } else if (!strcmp(name, "anchors_mask") || !strcmp(name, "mask")) {
+        float *m = NULL;
+        lp->boxes_per_cell = split_floats(val, &m);
+        free(lp->anchors_mask);
+        lp->anchors_mask = (int *)calloc((size_t)lp->boxes_per_cell, sizeof(int));
+        for (int i = 0; i < lp->boxes_per_cell; ++i) lp->anchors_mask[i] = (int)m[i];
+        free(m);
     }
-    /* anchors / masks / classes of the YOLO head: that layer is not built here, the keys are ignored */
 }
 
 static int is_any(const char *name, const char *a, const char *b, const char *c, const char *d) {
     return !strcmp(name, a) || (b && !strcmp(name, b)) || (c && !strcmp(name, c)) || (d && !strcmp(name, d));
 }
 
-static bcnn_status add_layer(bcnn_net *net, const char *name, const layer_param *lp) {
+static bcnn_status add_layer(bcnn_net *net, const char *name, layer_param *lp) {
     if (net->num_nodes == 0) {
         BCNN_CHECK_AND_LOG(net->log_ctx, net->tensors[0].w > 0 && net->tensors[0].h > 0 && net->tensors[0].c > 0,
                            BCNN_INVALID_PARAMETER, "Input's width, height and channels must be > 0\n");
@@ -329,7 +362,18 @@ static bcnn_status add_layer(bcnn_net *net, const char *name, const layer_param 
                            "Eltwise layer needs two sources (src=a,b)\n");
         return bcnn_add_eltwise_layer(net, lp->a, lp->src_id[0], lp->src_id[1], dst);
     }
-    if (!strcmp(name, "[yolo]")) return bcnn_add_yolo_layer(net, 0, 0, 4, 0, NULL, NULL, src, dst);
+    if (!strcmp(name, "[yolo]")) {
+        /* the builder copies 2 * num values (the reference reads past a shorter list); pad a short one with zeros */
+        if (lp->anchors && lp->num_anchor_vals < 2 * lp->num_anchors) {
+            float *a = (float *)calloc((size_t)2 * lp->num_anchors, sizeof(float));
+            memcpy(a, lp->anchors, (size_t)lp->num_anchor_vals * sizeof(float));
+            free(lp->anchors);
+            lp->anchors = a;
+            lp->num_anchor_vals = 2 * lp->num_anchors;
+        }
+        return bcnn_add_yolo_layer(net, lp->boxes_per_cell, lp->num_classes, lp->num_coords, lp->num_anchors,
+                                   lp->anchors_mask, lp->anchors, src, dst);
+    }
     if (!strcmp(name, "[cost]")) return bcnn_add_cost_layer(net, lp->loss, lp->cost, 1.0f, src, "label", dst);
     bcnn_log(net->log_ctx, BCNN_LOG_ERROR, "Unknown Layer %s\n", name);
     return BCNN_INVALID_PARAMETER;

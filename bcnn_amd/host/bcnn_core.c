@@ -501,6 +501,14 @@ static bcnn_status resize_private_f32(float **buf, size_t old_elems, size_t new_
 
 bcnn_status bcnn_resize_net(bcnn_net *net, int w, int h, int c, int need_realloc) {
     if (!net || w <= 0 || h <= 0 || c <= 0) return BCNN_INVALID_PARAMETER;
+    /* The reference gives every node type other than convolution and max-pooling its source's shape, which is wrong for
+     * upsample (scaled extent) and concat (summed depth). Such graphs are refused before any shape changes. */
+    for (int i = 0; i < net->num_nodes; ++i) {
+        const bcnn_layer_type t = net->nodes[i].type;
+        BCNN_CHECK_AND_LOG(net->log_ctx, t != BCNN_LAYER_CONCAT && t != BCNN_LAYER_UPSAMPLE && t != BCNN_LAYER_YOLOV3,
+                           BCNN_INVALID_PARAMETER,
+                           "bcnn_resize_net: node %d is a concat / upsample / YOLO node, whose resize is not supported\n", i);
+    }
     bcnn_set_input_shape(net, w, h, c, 1);
     for (int i = 0; i < net->num_nodes; ++i) {
         bcnn_node *nd = &net->nodes[i];
@@ -549,6 +557,10 @@ bcnn_status bcnn_resize_net(bcnn_net *net, int w, int h, int c, int need_realloc
 
 bcnn_status bcnn_set_mode(bcnn_net *net, bcnn_mode mode) {
     if (net->mode == mode) return BCNN_SUCCESS;
+    if (mode == BCNN_MODE_TRAIN) /* the YOLO head's training loss is not built: it would train on a zero gradient */
+        for (int i = 0; i < net->num_nodes; ++i)
+            BCNN_CHECK_AND_LOG(net->log_ctx, net->nodes[i].type != BCNN_LAYER_YOLOV3, BCNN_INVALID_PARAMETER,
+                               "bcnn_set_mode: the net holds a YOLO node, whose TRAIN-mode loss is not built\n");
     net->mode = mode;
     /* TRAIN reads the train streams, VALID / PREDICT the (rewound) test streams: reference bcnn_net.c:490-504 */
     if (net->data_loader) bcnn_switch_data_handles(net, net->data_loader);

@@ -194,6 +194,8 @@ bcnn_status bcnn_net_add_node(bcnn_net *net, bcnn_node node);
 bcnn_status bcnn_net_add_tensor(bcnn_net *net, bcnn_tensor tensor);
 bcnn_status bcnn_node_add_input(bcnn_net *net, bcnn_node *node, int index);
 bcnn_status bcnn_node_add_output(bcnn_net *net, bcnn_node *node, int index);
+/* new n x c x h x w tensor `dst_id` (with gradient, allocated for the net's mode) as the node's next output */
+bcnn_status bcnn_node_new_output(bcnn_net *net, bcnn_node *node, int n, int c, int h, int w, const char *dst_id);
 
 typedef struct tensor_filler {
     int range;
@@ -367,11 +369,15 @@ typedef struct bcnn_cost_param {
     bcnn_loss_metric loss_metric;
 } bcnn_cost_param;
 
-/* only `classes` is read by consumers (src/cli/bcnn_cl.c:199); the YOLO head itself is out of scope */
+typedef struct bcnn_upsample_param {
+    int size;
+} bcnn_upsample_param;
+
+/* the YOLOv3 head (reference src/layers/bcnn_yolo.h); consumers read `classes` (src/cli/bcnn_cl.c:199) */
 typedef struct bcnn_yolo_param {
     int num, classes, coords, total;
-    int *mask;
-    float *biases;
+    int *mask;      /* num anchor indices of this head */
+    float *biases;  /* host: total * 2 anchor extents (w, h) in input pixels */
     float *cost;
 } bcnn_yolo_param;
 
@@ -405,6 +411,13 @@ void bcnn_forward_softmax_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_softmax_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_forward_cost_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_cost_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_forward_concat_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_backward_concat_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_forward_upsample_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_backward_upsample_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_forward_yolo_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_backward_yolo_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_release_param_yolo_layer(bcnn_node *node);
 
 /* SGD step on one node's parameters (bcnn_learner.c:67-104 in the reference) */
 void bcnn_link_depthwise_batchnorm(bcnn_net *net); /* bcnn_layers_hot.c; called by bcnn_compile_net */

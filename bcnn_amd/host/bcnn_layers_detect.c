@@ -1,0 +1,324 @@
+/*
+ * bcnn_layers_detect.c -- the nodes a Darknet detector graph (yolov3-tiny) needs besides the hot path: concat
+ * ([route]), nearest-neighbour upsample, the YOLOv3 head, and bcnn_yolo_get_detections.
+ *
+ * Reference behaviour: bcnn_concat_layer.c:33-146, bcnn_upsample_layer.c:28-147, bcnn_yolo.c:15-107, 207-215, 417-468,
+ * 470-639. Deliberate deviations:
+ *   - the YOLO head runs in PREDICT / VALID nets only: its training loss (and the detection-list loader it needs) is not
+ *     built, so bcnn_add_yolo_layer on a TRAIN net and bcnn_set_mode(TRAIN) on a net holding a head are refused;
+ *   - bcnn_yolo_get_detections prints nothing per box and sizes `prob` from the classes of the YOLO nodes (the
+ *     reference reads them from the LAST node of the net, right only when that node is a head);
+ *   - a head whose mask names an anchor outside [0, total) is refused (the reference reads past its anchor table).
+ */
+#include <math.h>
+#include <string.h>
+
+#include "bcnn_internal.h"
+#include "../../include/bcnn_hip.h"
+
+/* ================================================================================================
+ * concat: dst = [src_0 | src_1 | ...] along the channels, image by image. A single source is a copy (Darknet
+ * `[route] layers=-4`). Backward src_grad += slice of dst_grad for every source with a gradient; the sources'
+ * gradient fills stay live (mark_dead_grad_fills: a concat consumer is never a sole writer).
+ * ============================================================================================== */
+bcnn_status bcnn_add_concat_layer(bcnn_net *net, int num_src, char *const *src_ids, const char *dst_id) {
+    BCNN_CHECK_AND_LOG(net->log_ctx, net->num_nodes >= 1, BCNN_INVALID_PARAMETER,
+                       "Concat layer can't be the first layer of the network\n");
+    BCNN_CHECK_AND_LOG(net->log_ctx, num_src >= 1 && src_ids && dst_id, BCNN_INVALID_PARAMETER,
+                       "Concat layer: needs at least one source and a destination\n");
+    bcnn_node node = {0};
+    int out_c = 0;
+    for (int i = 0; i < num_src; ++i) {
+        const int idx = bcnn_get_tensor_index_by_name(net, src_ids[i]);
+        if (idx < 0) {
+            free(node.src);
+            BCNN_ERROR(net->log_ctx, BCNN_INVALID_PARAMETER, "Concat layer: invalid input node name %s\n", src_ids[i]);
+        }
+        bcnn_node_add_input(net, &node, idx);
+        const bcnn_tensor *s0 = &net->tensors[node.src[0]], *si = &net->tensors[idx];
+        if (si->w != s0->w || si->h != s0->h) {
+            free(node.src);
+            BCNN_ERROR(net->log_ctx, BCNN_INVALID_PARAMETER,
+                       "Concat layer: inconsistent spatial sizes between node %s (%dx%d) and node %s (%dx%d)\n",
+                       src_ids[0], s0->w, s0->h, src_ids[i], si->w, si->h);
+        }
+        out_c += si->c;
+    }
+    const bcnn_tensor s = net->tensors[node.src[0]];
+    node.type = BCNN_LAYER_CONCAT;
+    node.forward = bcnn_forward_concat_layer;
+    node.backward = bcnn_backward_concat_layer;
+    BCNN_CHECK_STATUS(bcnn_node_new_output(net, &node, s.n, out_c, s.h, s.w, dst_id));
+    BCNN_CHECK_STATUS(bcnn_net_add_node(net, node));
+    BCNN_INFO(net->log_ctx, "[Concat] %d sources -> %-8s (%4d x%4d x%4d)\n", num_src, dst_id, s.w, s.h, out_c);
+    return BCNN_SUCCESS;
+}
+
+void bcnn_forward_concat_layer(bcnn_net *net, bcnn_node *node) {
+    bcnn_tensor *y = &net->tensors[node->dst[0]];
+    const float **src = (const float **)malloc((size_t)node->num_src * sizeof(*src));
+    int *size = (int *)malloc((size_t)node->num_src * sizeof(int));
+    for (int i = 0; i < node->num_src; ++i) {
+        const bcnn_tensor *x = &net->tensors[node->src[i]];
+        src[i] = x->data_gpu;
+        size[i] = bcnn_tensor_size3d(x);
+    }
+    bcnn_hip_concat_forward(node->num_src, src, size, y->data_gpu, bcnn_tensor_size3d(y), y->n);
+    free(src);
+    free(size);
+}
+
+void bcnn_backward_concat_layer(bcnn_net *net, bcnn_node *node) {
+    bcnn_tensor *y = &net->tensors[node->dst[0]];
+    if (!y->grad_data_gpu) return;
+    float **grad = (float **)malloc((size_t)node->num_src * sizeof(*grad));
+    int *size = (int *)malloc((size_t)node->num_src * sizeof(int));
+    for (int i = 0; i < node->num_src; ++i) {
+        const bcnn_tensor *x = &net->tensors[node->src[i]];
+        grad[i] = x->grad_data_gpu; /* NULL (the net input, PREDICT nets): skipped */
+        size[i] = bcnn_tensor_size3d(x);
+    }
+    bcnn_hip_concat_backward(node->num_src, grad, size, y->grad_data_gpu, bcnn_tensor_size3d(y), y->n);
+    free(grad);
+    free(size);
+}
+
+/* ================================================================================================
+ * upsample: nearest neighbour by an integer factor
+ * ============================================================================================== */
+bcnn_status bcnn_add_upsample_layer(bcnn_net *net, int size, const char *src_id, const char *dst_id) {
+    BCNN_CHECK_AND_LOG(net->log_ctx, size >= 1, BCNN_INVALID_PARAMETER, "Upsample layer: invalid factor %d\n", size);
+    bcnn_node node = {0};
+    if (net->num_nodes > 0) {
+        const int idx = bcnn_net_find_tensor(net, src_id);
+        BCNN_CHECK_AND_LOG(net->log_ctx, idx >= 0, BCNN_INVALID_PARAMETER, "Upsample layer: invalid input node name %s\n",
+                           src_id);
+        bcnn_node_add_input(net, &node, idx);
+    } else {
+        bcnn_node_add_input(net, &node, 0);
+    }
+    const bcnn_tensor s = net->tensors[node.src[0]];
+    node.type = BCNN_LAYER_UPSAMPLE;
+    node.param_size = sizeof(bcnn_upsample_param);
+    bcnn_upsample_param *param = (bcnn_upsample_param *)calloc(1, node.param_size);
+    node.param = param;
+    param->size = size;
+    node.forward = bcnn_forward_upsample_layer;
+    node.backward = bcnn_backward_upsample_layer;
+    BCNN_CHECK_STATUS(bcnn_node_new_output(net, &node, s.n, s.c, s.h * size, s.w * size, dst_id));
+    BCNN_CHECK_STATUS(bcnn_net_add_node(net, node));
+    BCNN_INFO(net->log_ctx, "[Upsample] %-8s (%4d x%4d x%4d) -> %-8s (%4d x%4d x%4d)\n", s.name, s.w, s.h, s.c, dst_id,
+              s.w * size, s.h * size, s.c);
+    return BCNN_SUCCESS;
+}
+
+void bcnn_forward_upsample_layer(bcnn_net *net, bcnn_node *node) {
+    const bcnn_upsample_param *p = (const bcnn_upsample_param *)node->param;
+    bcnn_tensor *x = &net->tensors[node->src[0]], *y = &net->tensors[node->dst[0]];
+    bcnn_hip_upsample_forward(x->data_gpu, y->data_gpu, x->n, x->c, x->h, x->w, p->size);
+}
+
+void bcnn_backward_upsample_layer(bcnn_net *net, bcnn_node *node) {
+    const bcnn_upsample_param *p = (const bcnn_upsample_param *)node->param;
+    bcnn_tensor *x = &net->tensors[node->src[0]], *y = &net->tensors[node->dst[0]];
+    if (x->grad_data_gpu && y->grad_data_gpu)
+        bcnn_hip_upsample_backward(x->grad_data_gpu, y->grad_data_gpu, x->n, x->c, x->h, x->w, p->size);
+}
+
+/* ================================================================================================
+ * YOLOv3 head (inference): dst = src with the logistic on x, y, objectness and the class scores
+ * ============================================================================================== */
+bcnn_status bcnn_add_yolo_layer(bcnn_net *net, int num_boxes_per_cell, int classes, int coords, int total, int *mask,
+                                float *anchors, const char *src_id, const char *dst_id) {
+    BCNN_CHECK_AND_LOG(net->log_ctx, net->num_nodes >= 1, BCNN_INVALID_PARAMETER,
+                       "Yolo layer can't be the first layer of the network\n");
+    BCNN_CHECK_AND_LOG(net->log_ctx, net->mode != BCNN_MODE_TRAIN, BCNN_INVALID_PARAMETER,
+                       "Yolo layer: the TRAIN-mode loss of the YOLO head is not built (PREDICT / VALID nets only)\n");
+    const int idx = bcnn_net_find_tensor(net, src_id);
+    BCNN_CHECK_AND_LOG(net->log_ctx, idx >= 0, BCNN_INVALID_PARAMETER, "Yolo layer: invalid input node name %s\n", src_id);
+    const bcnn_tensor s = net->tensors[idx];
+    BCNN_CHECK_AND_LOG(net->log_ctx, num_boxes_per_cell * (classes + coords + 1) == s.c, BCNN_INVALID_PARAMETER,
+                       "Yolo layer: inconsistent number of channels %d\n", num_boxes_per_cell * (classes + coords + 1));
+    for (int i = 0; mask && i < num_boxes_per_cell; ++i)
+        BCNN_CHECK_AND_LOG(net->log_ctx, mask[i] >= 0 && mask[i] < total, BCNN_INVALID_PARAMETER,
+                           "Yolo layer: mask entry %d names anchor %d of %d\n", i, mask[i], total);
+    bcnn_node node = {0};
+    bcnn_node_add_input(net, &node, idx);
+    node.type = BCNN_LAYER_YOLOV3;
+    node.param_size = sizeof(bcnn_yolo_param);
+    bcnn_yolo_param *param = (bcnn_yolo_param *)calloc(1, node.param_size);
+    node.param = param;
+    param->num = num_boxes_per_cell;
+    param->classes = classes;
+    param->coords = coords;
+    param->total = total;
+    param->mask = (int *)calloc((size_t)(num_boxes_per_cell > 0 ? num_boxes_per_cell : 1), sizeof(int));
+    for (int i = 0; i < num_boxes_per_cell; ++i) param->mask[i] = mask ? mask[i] : i;
+    param->biases = (float *)malloc((size_t)(total > 0 ? 2 * total : 1) * sizeof(float));
+    for (int i = 0; i < 2 * total; ++i) param->biases[i] = 0.5f;
+    if (anchors) memcpy(param->biases, anchors, (size_t)(2 * total) * sizeof(float));
+    param->cost = (float *)calloc(1, sizeof(float));
+    node.forward = bcnn_forward_yolo_layer;
+    node.backward = bcnn_backward_yolo_layer;
+    node.release_param = bcnn_release_param_yolo_layer;
+    BCNN_CHECK_STATUS(bcnn_node_new_output(net, &node, s.n, s.c, s.h, s.w, dst_id));
+    BCNN_CHECK_STATUS(bcnn_net_add_node(net, node));
+    BCNN_INFO(net->log_ctx, "[Yolo] %-8s (%4d x%4d x%4d) -> %-8s %5d classes\n", src_id, s.w, s.h, s.c, dst_id, classes);
+    return BCNN_SUCCESS;
+}
+
+void bcnn_forward_yolo_layer(bcnn_net *net, bcnn_node *node) {
+    const bcnn_yolo_param *p = (const bcnn_yolo_param *)node->param;
+    bcnn_tensor *x = &net->tensors[node->src[0]], *y = &net->tensors[node->dst[0]];
+    bcnn_hip_yolo_activate(x->data_gpu, y->data_gpu, y->n, p->num, p->coords, p->classes, y->h * y->w);
+}
+
+void bcnn_backward_yolo_layer(bcnn_net *net, bcnn_node *node) { /* reference bcnn_yolo.c:441-447 */
+    bcnn_tensor *x = &net->tensors[node->src[0]], *y = &net->tensors[node->dst[0]];
+    if (x->grad_data_gpu && y->grad_data_gpu)
+        bcnn_hip_axpy((size_t)bcnn_tensor_size(x), 1.0f, y->grad_data_gpu, x->grad_data_gpu);
+}
+
+void bcnn_release_param_yolo_layer(bcnn_node *node) {
+    bcnn_yolo_param *p = (bcnn_yolo_param *)node->param;
+    free(p->mask);
+    free(p->biases);
+    free(p->cost);
+}
+
+/* ================================================================================================
+ * detections (host; a few thousand candidate boxes at most), reference bcnn_yolo.c:99-145, 470-639
+ * ============================================================================================== */
+typedef struct {
+    float x, y, w, h;
+} yolo_box;
+
+static float overlap(float x1, float w1, float x2, float w2) {
+    const float l1 = x1 - w1 / 2, l2 = x2 - w2 / 2;
+    const float left = l1 > l2 ? l1 : l2;
+    const float r1 = x1 + w1 / 2, r2 = x2 + w2 / 2;
+    const float right = r1 < r2 ? r1 : r2;
+    return right - left;
+}
+
+static float box_iou(yolo_box a, yolo_box b) {
+    const float w = overlap(a.x, a.w, b.x, b.w), h = overlap(a.y, a.h, b.y, b.h);
+    const float inter = (w < 0 || h < 0) ? 0 : w * h;
+    return inter / (a.w * a.h + b.w * b.h - inter);
+}
+
+static int entry_index(const bcnn_yolo_param *p, const bcnn_tensor *t, int batch, int location, int entry) {
+    const int n = location / (t->w * t->h), loc = location % (t->w * t->h);
+    return batch * bcnn_tensor_size3d(t) + n * t->w * t->h * (p->coords + p->classes + 1) + entry * t->w * t->h + loc;
+}
+
+static void correct_region_boxes(bcnn_output_detection *dets, int n, int w, int h, int netw, int neth, int relative) {
+    int new_w, new_h;
+    if (((float)netw / w) < ((float)neth / h)) {
+        new_w = netw;
+        new_h = (h * netw) / w;
+    } else {
+        new_h = neth;
+        new_w = (w * neth) / h;
+    }
+    for (int i = 0; i < n; ++i) {
+        dets[i].x = (dets[i].x - (netw - new_w) / 2. / netw) / ((float)new_w / netw);
+        dets[i].y = (dets[i].y - (neth - new_h) / 2. / neth) / ((float)new_h / neth);
+        dets[i].w *= (float)netw / new_w;
+        dets[i].h *= (float)neth / new_h;
+        if (!relative) {
+            dets[i].x *= w;
+            dets[i].w *= w;
+            dets[i].y *= h;
+            dets[i].h *= h;
+        }
+    }
+}
+
+static int by_objectness_desc(const void *pa, const void *pb) {
+    const float diff = ((const bcnn_output_detection *)pa)->objectness - ((const bcnn_output_detection *)pb)->objectness;
+    return diff < 0 ? 1 : (diff > 0 ? -1 : 0);
+}
+
+static void do_nms_obj(bcnn_output_detection *dets, int num_dets, float thresh) {
+    int k = num_dets - 1;
+    for (int i = 0; i <= k; ++i) { /* zero-objectness boxes to the end, outside the sort */
+        if (dets[i].objectness == 0) {
+            const bcnn_output_detection swap = dets[i];
+            dets[i] = dets[k];
+            dets[k] = swap;
+            --k;
+            --i;
+        }
+    }
+    num_dets = k + 1;
+    qsort(dets, (size_t)num_dets, sizeof(bcnn_output_detection), by_objectness_desc);
+    for (int i = 0; i < num_dets; ++i) {
+        if (dets[i].objectness == 0) continue;
+        const yolo_box a = {dets[i].x, dets[i].y, dets[i].w, dets[i].h};
+        for (int j = i + 1; j < num_dets; ++j) {
+            if (dets[j].objectness == 0) continue;
+            const yolo_box b = {dets[j].x, dets[j].y, dets[j].w, dets[j].h};
+            if (box_iou(a, b) > thresh) {
+                dets[j].objectness = 0;
+                for (int c = 0; c < dets[j].num_classes; ++c) dets[j].prob[c] = 0;
+            }
+        }
+    }
+}
+
+bcnn_output_detection *bcnn_yolo_get_detections(bcnn_net *net, int batch, int w, int h, int netw, int neth,
+                                                float thresh, int relative, int *num_dets) {
+    int count = 0;
+    if (num_dets) *num_dets = 0;
+    for (int k = 0; k < net->num_nodes; ++k) { /* one read-back per head, then count the candidates */
+        if (net->nodes[k].type != BCNN_LAYER_YOLOV3) continue;
+        bcnn_download_tensor(net, net->nodes[k].dst[0], 0);
+    }
+    bcnn_synchronize(net);
+    for (int k = 0; k < net->num_nodes; ++k) {
+        if (net->nodes[k].type != BCNN_LAYER_YOLOV3) continue;
+        const bcnn_yolo_param *p = (const bcnn_yolo_param *)net->nodes[k].param;
+        const bcnn_tensor *dst = &net->tensors[net->nodes[k].dst[0]];
+        if (batch < 0 || batch >= dst->n || !dst->data) return NULL;
+        for (int i = 0; i < dst->w * dst->h; ++i)
+            for (int n = 0; n < p->num; ++n)
+                count += dst->data[entry_index(p, dst, batch, n * dst->w * dst->h + i, p->coords)] > thresh;
+    }
+    if (count == 0) return NULL;
+    bcnn_output_detection *dets = (bcnn_output_detection *)calloc((size_t)count, sizeof(bcnn_output_detection));
+    count = 0;
+    for (int k = 0; k < net->num_nodes; ++k) {
+        if (net->nodes[k].type != BCNN_LAYER_YOLOV3) continue;
+        const bcnn_yolo_param *p = (const bcnn_yolo_param *)net->nodes[k].param;
+        const bcnn_tensor *dst = &net->tensors[net->nodes[k].dst[0]];
+        const int hw = dst->w * dst->h;
+        for (int i = 0; i < hw; ++i) {
+            const int row = i / dst->w, col = i % dst->w;
+            for (int n = 0; n < p->num; ++n) {
+                const float objectness = dst->data[entry_index(p, dst, batch, n * hw + i, p->coords)];
+                if (objectness <= thresh) continue;
+                const float *x = dst->data + entry_index(p, dst, batch, n * hw + i, 0);
+                const float *anchor = p->biases + 2 * p->mask[n];
+                bcnn_output_detection *d = &dets[count++];
+                /* get_yolo_box, reference bcnn_yolo.c:137-145 */
+                d->x = (col + x[0]) / dst->w;
+                d->y = (row + x[hw]) / dst->h;
+                d->w = expf(x[2 * hw]) * anchor[0] / net->tensors[0].w;
+                d->h = expf(x[3 * hw]) * anchor[1] / net->tensors[0].h;
+                d->objectness = objectness;
+                d->num_classes = p->classes;
+                d->prob = (float *)calloc((size_t)(p->classes > 0 ? p->classes : 1), sizeof(float));
+                if (p->coords > 4) d->mask = (float *)calloc((size_t)(p->coords - 4), sizeof(float));
+                for (int j = 0; j < p->classes; ++j) {
+                    const float prob = objectness * x[(p->coords + 1 + j) * hw];
+                    d->prob[j] = (prob > thresh) ? prob : 0;
+                }
+            }
+        }
+    }
+    correct_region_boxes(dets, count, w, h, netw, neth, relative);
+    do_nms_obj(dets, count, 0.45f);
+    if (num_dets) *num_dets = count;
+    return dets;
+}

@@ -16,7 +16,7 @@
 static int imin(int a, int b) { return a < b ? a : b; }
 static int imax(int a, int b) { return a > b ? a : b; }
 
-static bcnn_status new_output(bcnn_net *net, bcnn_node *node, int n, int c, int h, int w, const char *dst_id) {
+bcnn_status bcnn_node_new_output(bcnn_net *net, bcnn_node *node, int n, int c, int h, int w, const char *dst_id) {
     bcnn_tensor t = {0};
     bcnn_tensor_set_shape(&t, n, c, h, w, 1);
     BCNN_CHECK_STATUS(bcnn_tensor_allocate(&t, net->mode));
@@ -61,7 +61,7 @@ bcnn_status bcnn_add_eltwise_layer(bcnn_net *net, bcnn_activation activation, co
     param->stride[0] = imax(1, st0); param->stride[1] = imax(1, st1);
     node.forward = bcnn_forward_eltwise_layer;
     node.backward = bcnn_backward_eltwise_layer;
-    BCNN_CHECK_STATUS(new_output(net, &node, a.n, a.c, a.h, a.w, dst_id));
+    BCNN_CHECK_STATUS(bcnn_node_new_output(net, &node, a.n, a.c, a.h, a.w, dst_id));
     BCNN_CHECK_STATUS(bcnn_net_add_node(net, node));
     BCNN_INFO(net->log_ctx, "[EltWiseAdd] %-8s , %-8s -> %-8s (%4d x%4d x%4d)\n", a.name, b.name, dst_id, a.w, a.h, a.c);
     return BCNN_SUCCESS;
@@ -142,7 +142,7 @@ bcnn_status bcnn_add_fullc_layer(bcnn_net *net, int output_size, bcnn_filler_typ
     BCNN_CHECK_STATUS(bcnn_net_add_tensor(net, biases));
     BCNN_CHECK_STATUS(bcnn_node_add_input(net, &node, net->num_tensors - 1));
     bcnn_net_register_param(net, net->num_tensors - 1);
-    BCNN_CHECK_STATUS(new_output(net, &node, s.n, output_size, 1, 1, dst_id));
+    BCNN_CHECK_STATUS(bcnn_node_new_output(net, &node, s.n, output_size, 1, 1, dst_id));
     node.type = BCNN_LAYER_FULL_CONNECTED;
     node.param_size = sizeof(bcnn_fullc_param);
     bcnn_fullc_param *param = (bcnn_fullc_param *)calloc(1, node.param_size);
@@ -203,7 +203,7 @@ bcnn_status bcnn_add_softmax_layer(bcnn_net *net, const char *src_id, const char
         bcnn_node_add_input(net, &node, 0);
     }
     const bcnn_tensor s = net->tensors[node.src[0]];
-    BCNN_CHECK_STATUS(new_output(net, &node, s.n, s.c, s.h, s.w, dst_id));
+    BCNN_CHECK_STATUS(bcnn_node_new_output(net, &node, s.n, s.c, s.h, s.w, dst_id));
     node.type = BCNN_LAYER_SOFTMAX;
     node.forward = bcnn_forward_softmax_layer;
     node.backward = bcnn_backward_softmax_layer;
@@ -248,7 +248,7 @@ bcnn_status bcnn_add_cost_layer(bcnn_net *net, bcnn_loss loss, bcnn_loss_metric 
     bcnn_tensor_set_shape(&net->tensors[1], s.n, s.c, s.h, s.w, 0);
     BCNN_CHECK_STATUS(bcnn_tensor_allocate(&net->tensors[1], net->mode));
     bcnn_node_add_input(net, &node, 1);
-    BCNN_CHECK_STATUS(new_output(net, &node, s.n, s.c, s.h, s.w, dst_id));
+    BCNN_CHECK_STATUS(bcnn_node_new_output(net, &node, s.n, s.c, s.h, s.w, dst_id));
     return bcnn_net_add_node(net, node);
 }
 

@@ -1,6 +1,7 @@
 /*
  * bcnn_unsupported.c -- entry points of the public API that lie outside the hot path (SURVEY.md
- * section 8: control plane, detection head, rarely used layers; the dataset readers are in bcnn_data.c). They exist so
+ * section 8: control plane, rarely used layers; the dataset readers are in bcnn_data.c, the detector nodes in
+ * bcnn_layers_detect.c). They exist so
  * that every consumer of the reference links; each returns BCNN_INVALID_PARAMETER (or does nothing)
  * and says so in the log. INTEGRATION.md lists them.
  */
@@ -44,13 +45,6 @@ void bcnn_draw_color_box(unsigned char *img, int w_img, int h_img, float cx, flo
     (void)img; (void)w_img; (void)h_img; (void)cx; (void)cy; (void)w; (void)h; (void)color;
 }
 
-bcnn_output_detection *bcnn_yolo_get_detections(bcnn_net *net, int batch, int width, int height, int netw, int neth,
-                                                float thresh, int relative, int *num_dets) {
-    (void)net; (void)batch; (void)width; (void)height; (void)netw; (void)neth; (void)thresh; (void)relative;
-    if (num_dets) *num_dets = 0;
-    return NULL;
-}
-
 bcnn_status bcnn_add_deconvolutional_layer(bcnn_net *net, int n, int size, int stride, int pad, bcnn_filler_type init,
                                            bcnn_activation act, const char *s, const char *d) {
     (void)n; (void)size; (void)stride; (void)pad; (void)init; (void)act; (void)s; (void)d;
@@ -60,17 +54,4 @@ bcnn_status bcnn_add_lrn_layer(bcnn_net *net, int ls, float a, float b, float k,
     (void)ls; (void)a; (void)b; (void)k; (void)s; (void)d;
     NOT_BUILT(net, "LRN layer");
 }
-bcnn_status bcnn_add_concat_layer(bcnn_net *net, int n, char *const *ids, const char *d) {
-    (void)n; (void)ids; (void)d;
-    NOT_BUILT(net, "concat layer");
-}
 bcnn_status bcnn_add_dropout_layer(bcnn_net *net, float rate, const char *id) { (void)rate; (void)id; NOT_BUILT(net, "dropout layer"); }
-bcnn_status bcnn_add_upsample_layer(bcnn_net *net, int size, const char *s, const char *d) {
-    (void)size; (void)s; (void)d;
-    NOT_BUILT(net, "upsample layer");
-}
-bcnn_status bcnn_add_yolo_layer(bcnn_net *net, int nb, int nc, int coords, int total, int *mask, float *anchors,
-                                const char *s, const char *d) {
-    (void)nb; (void)nc; (void)coords; (void)total; (void)mask; (void)anchors; (void)s; (void)d;
-    NOT_BUILT(net, "YOLOv3 head");
-}

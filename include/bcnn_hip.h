@@ -523,6 +523,30 @@ void bcnn_hip_add_rowvec(float *y_d, const float *v_d, int rows, int cols);
 void bcnn_hip_softmax_forward(const float *x_d, float *y_d, int n, int c, int hw);
 
 /* ---------------------------------------------------------------------------------------------
+ * Detector graph nodes (yolov3-tiny: [route], [upsample], [yolo]).  Replace the reference's
+ * bcnn_forward/backward_concat_layer_gpu (bcnn_concat_layer.c:113-146: num_src x n copies / axpys),
+ * bcnn_forward/backward_upsample_layer_gpu (bcnn_upsample_layer.cu) and the activation part of
+ * bcnn_forward_yolo_layer (bcnn_yolo.c:417-440, done on the host there).
+ *   concat_forward  : for every image j < n and source i, dst[j*dst_size3d + off_i ..] = src_i[j*size_i ..],
+ *                     off_i = sum of the sizes before i. One launch for the node.
+ *   concat_backward : src_grad_i[j*size_i ..] += dst_grad[j*dst_size3d + off_i ..] (one float add per element,
+ *                     bit-exact with the reference's axpy); NULL entries of src_grad_d are skipped.
+ *                     src_d / src_grad_d / src_size3d are HOST arrays of num_src entries.
+ *   upsample_forward  : nearest neighbour by the integer `size`: y[n][c][h*size][w*size] from x[n][c][h][w].
+ *   upsample_backward : dx[e] += the size x size block of dy over e, added row by row, left to right, onto the
+ *                       current dx (the reference CPU order: bit-exact, no atomics).
+ *   yolo_activate   : y = x with the logistic of bcnn_activation_layer.c applied to entries 0, 1 and
+ *                     coords .. coords+classes of each of the `num` boxes; x is [n][num*(coords+classes+1)][hw].
+ * ------------------------------------------------------------------------------------------- */
+void bcnn_hip_concat_forward(int num_src, const float *const *src_d, const int *src_size3d, float *dst_d,
+                             int dst_size3d, int n);
+void bcnn_hip_concat_backward(int num_src, float *const *src_grad_d, const int *src_size3d, const float *dst_grad_d,
+                              int dst_size3d, int n);
+void bcnn_hip_upsample_forward(const float *x_d, float *y_d, int n, int c, int h, int w, int size);
+void bcnn_hip_upsample_backward(float *dx_d, const float *dy_d, int n, int c, int h, int w, int size);
+void bcnn_hip_yolo_activate(const float *x_d, float *y_d, int n, int num, int coords, int classes, int hw);
+
+/* ---------------------------------------------------------------------------------------------
  * Data-parallel exchange (RCCL over xGMI).  No reference counterpart (the reference is single-device); process
  * model = the reference's one device per process (bcnn_cuda_set_device once in main, src/cli/bcnn_cl.c:281-285,
  * src/bcnn_utils.c:201): N processes, each after bcnn_hip_set_device(local rank), form one communicator.
