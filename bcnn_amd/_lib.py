@@ -117,6 +117,9 @@ SIGNATURES = {
     "bcnn_hip_upsample_forward": (None, [vp, vp, i, i, i, i, i]),
     "bcnn_hip_upsample_backward": (None, [vp, vp, i, i, i, i, i]),
     "bcnn_hip_yolo_activate": (None, [vp, vp, i, i, i, i, i]),
+    "bcnn_hip_deconv_workspace_size": (sz, [i] * 8),
+    "bcnn_hip_deconv_forward": (None, [vp, vp, vp, vp] + [i] * 9),
+    "bcnn_hip_deconv_backward": (None, [vp] * 7 + [i] * 9 + [vp, sz]),
     "bcnn_hip_comm_init": (None, [i, i, C.c_char_p]),
     "bcnn_hip_comm_destroy": (None, []),
     "bcnn_hip_comm_retain": (None, []),

@@ -83,6 +83,7 @@ def lib():
         "bcnn_get_batch_size": (i, [vp]),
         "bcnn_add_convolutional_layer": (i, [vp, i, i, i, i, i, i, i, i, i, cp, cp]),
         "bcnn_add_depthwise_conv_layer": (i, [vp, i, i, i, i, i, i, cp, cp]),
+        "bcnn_add_deconvolutional_layer": (i, [vp, i, i, i, i, i, i, cp, cp]),
         "bcnn_add_batchnorm_layer": (i, [vp, cp, cp]), "bcnn_add_maxpool_layer": (i, [vp, i, i, i, cp, cp]),
         "bcnn_add_avgpool_layer": (i, [vp, cp, cp]), "bcnn_add_activation_layer": (i, [vp, i, cp]),
         "bcnn_add_eltwise_layer": (i, [vp, i, cp, cp, cp]), "bcnn_add_fullc_layer": (i, [vp, i, i, i, i, cp, cp]),
@@ -137,6 +138,11 @@ class Net:
     def conv(self, f, k, s, p, g=1, bn=0, act=ACT_NONE, src="input", dst="conv", init=FILLER_XAVIER):
         return self._added(self.L.bcnn_add_convolutional_layer(self.net, f, k, s, p, g, bn, init, act, 0,
                                                                 src.encode(), dst.encode()))
+
+    def deconv(self, f, k, s, p, act=ACT_NONE, src="input", dst="deconv", init=FILLER_XAVIER):
+        """bcnn_add_deconvolutional_layer: f output channels, k x k kernel, stride s, pad p"""
+        return self._added(self.L.bcnn_add_deconvolutional_layer(self.net, f, k, s, p, init, act, src.encode(),
+                                                                  dst.encode()))
 
     def depthwise(self, k, s, p, act=ACT_NONE, src="input", dst="dw"):
         return self._added(self.L.bcnn_add_depthwise_conv_layer(self.net, k, s, p, 0, FILLER_XAVIER, act,

@@ -502,12 +502,15 @@ static bcnn_status resize_private_f32(float **buf, size_t old_elems, size_t new_
 bcnn_status bcnn_resize_net(bcnn_net *net, int w, int h, int c, int need_realloc) {
     if (!net || w <= 0 || h <= 0 || c <= 0) return BCNN_INVALID_PARAMETER;
     /* The reference gives every node type other than convolution and max-pooling its source's shape, which is wrong for
-     * upsample (scaled extent) and concat (summed depth). Such graphs are refused before any shape changes. */
+     * upsample (scaled extent), concat (summed depth) and deconvolution (scaled extent, own depth). Such graphs are
+     * refused before any shape changes. */
     for (int i = 0; i < net->num_nodes; ++i) {
         const bcnn_layer_type t = net->nodes[i].type;
-        BCNN_CHECK_AND_LOG(net->log_ctx, t != BCNN_LAYER_CONCAT && t != BCNN_LAYER_UPSAMPLE && t != BCNN_LAYER_YOLOV3,
+        BCNN_CHECK_AND_LOG(net->log_ctx, t != BCNN_LAYER_CONCAT && t != BCNN_LAYER_UPSAMPLE && t != BCNN_LAYER_YOLOV3 &&
+                                             t != BCNN_LAYER_TRANSPOSE_CONV2D,
                            BCNN_INVALID_PARAMETER,
-                           "bcnn_resize_net: node %d is a concat / upsample / YOLO node, whose resize is not supported\n", i);
+                           "bcnn_resize_net: node %d is a concat / upsample / YOLO / deconvolution node, whose resize is "
+                           "not supported\n", i);
     }
     bcnn_set_input_shape(net, w, h, c, 1);
     for (int i = 0; i < net->num_nodes; ++i) {
@@ -739,7 +742,7 @@ static void sgd_table_add(bcnn_hip_context *hc, float *w, float *g, size_t n, in
 /* update workers whose whole effect is bcnn_node_sgd_step on their own tensors: safe to replay from the table */
 static int update_is_tabled(const bcnn_node *nd) {
     return nd->update == bcnn_update_conv_layer || nd->update == bcnn_update_depthwise_conv_layer ||
-           nd->update == bcnn_update_fullc_layer;
+           nd->update == bcnn_update_fullc_layer || nd->update == bcnn_update_deconv_layer;
 }
 
 void bcnn_update(bcnn_net *net) {

@@ -373,6 +373,19 @@ typedef struct bcnn_upsample_param {
     int size;
 } bcnn_upsample_param;
 
+/* transposed convolution (reference src/layers/bcnn_deconv_layer.h); weights [c_in][num][size][size] */
+typedef struct bcnn_deconv_param {
+    int num, size, stride, pad;
+    bcnn_activation activation;
+    float *conv_workspace;      /* unused on the device path (no materialised col2im / im2col) */
+    float *adam_m, *adam_v;
+#ifdef BCNN_USE_HIP
+    float *conv_workspace_gpu;  /* the node's own dW split partials (bcnn_hip_deconv_workspace_size), first backward */
+    size_t workspace_size;
+    float *adam_m_gpu, *adam_v_gpu; /* weight moments, allocated by the first Adam step */
+#endif
+} bcnn_deconv_param;
+
 /* the YOLOv3 head (reference src/layers/bcnn_yolo.h); consumers read `classes` (src/cli/bcnn_cl.c:199) */
 typedef struct bcnn_yolo_param {
     int num, classes, coords, total;
@@ -418,6 +431,10 @@ void bcnn_backward_upsample_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_forward_yolo_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_yolo_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_yolo_layer(bcnn_node *node);
+void bcnn_forward_deconv_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_backward_deconv_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_update_deconv_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_release_param_deconv_layer(bcnn_node *node);
 
 /* SGD step on one node's parameters (bcnn_learner.c:67-104 in the reference) */
 void bcnn_link_depthwise_batchnorm(bcnn_net *net); /* bcnn_layers_hot.c; called by bcnn_compile_net */

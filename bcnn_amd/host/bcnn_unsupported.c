@@ -1,7 +1,7 @@
 /*
  * bcnn_unsupported.c -- entry points of the public API that lie outside the hot path (SURVEY.md
  * section 8: control plane, rarely used layers; the dataset readers are in bcnn_data.c, the detector nodes in
- * bcnn_layers_detect.c). They exist so
+ * bcnn_layers_detect.c, the deconvolution node in bcnn_layers_deconv.c). They exist so
  * that every consumer of the reference links; each returns BCNN_INVALID_PARAMETER (or does nothing)
  * and says so in the log. INTEGRATION.md lists them.
  */
@@ -45,11 +45,6 @@ void bcnn_draw_color_box(unsigned char *img, int w_img, int h_img, float cx, flo
     (void)img; (void)w_img; (void)h_img; (void)cx; (void)cy; (void)w; (void)h; (void)color;
 }
 
-bcnn_status bcnn_add_deconvolutional_layer(bcnn_net *net, int n, int size, int stride, int pad, bcnn_filler_type init,
-                                           bcnn_activation act, const char *s, const char *d) {
-    (void)n; (void)size; (void)stride; (void)pad; (void)init; (void)act; (void)s; (void)d;
-    NOT_BUILT(net, "deconvolution layer");
-}
 bcnn_status bcnn_add_lrn_layer(bcnn_net *net, int ls, float a, float b, float k, const char *s, const char *d) {
     (void)ls; (void)a; (void)b; (void)k; (void)s; (void)d;
     NOT_BUILT(net, "LRN layer");

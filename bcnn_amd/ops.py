@@ -63,6 +63,35 @@ def conv_backward(x, wt, y, dy, dx, dw, dbias, k, stride, pad, groups, act, work
                              workspace.numel() if workspace is not None else 0)
 
 
+def deconv_out_hw(h, w, k, s, p):
+    """bcnn_deconv_layer.c:96-101"""
+    return s * (h - 1) + k - 2 * p, s * (w - 1) + k - 2 * p
+
+
+def deconv_workspace_size(n, c, h, w, f, k, s, p):
+    return int(_lib.load().bcnn_hip_deconv_workspace_size(n, c, h, w, f, k, s, p))
+
+
+def deconv_forward(x, wt, bias, y, k, stride, pad, act=0):
+    """bcnn_forward_deconv_layer (bcnn_deconv_layer.c:150-193). wt: [c_in][f][k][k] (any shape of that size), y is
+    overwritten with act(transposed convolution + bias)."""
+    n, c, h, w = x.shape
+    f = y.shape[1]
+    assert wt.numel() == c * f * k * k
+    _lib.load().bcnn_hip_deconv_forward(_f32(x), _f32(wt), _f32(bias), _f32(y), n, c, h, w, f, k, stride, pad, act)
+
+
+def deconv_backward(x, wt, y, dy, dx, dw, dbias, k, stride, pad, act, workspace):
+    """bcnn_backward_deconv_layer (bcnn_deconv_layer.c:195-246). dy is updated in place (dy * act'(y)), dbias and
+    dw accumulate (dw += (1/n) x dyᵀ), dx (may be None) is overwritten."""
+    n, c, h, w = x.shape
+    f = y.shape[1]
+    assert wt.numel() == c * f * k * k
+    _lib.load().bcnn_hip_deconv_backward(_f32(x), _f32(wt), _f32(y), _f32(dy), _f32(dx), _f32(dw), _f32(dbias), n, c,
+                                         h, w, f, k, stride, pad, act, _f32(workspace),
+                                         workspace.numel() if workspace is not None else 0)
+
+
 def batchnorm_forward(x, y, run_mean, run_var, scales, bias, saved_mean, saved_var, workspace, mode,
                       x_norm=None, act=0):
     """bcnn_forward_batchnorm_cpu (bcnn_batchnorm_layer.c:196-242)"""

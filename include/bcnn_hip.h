@@ -547,6 +547,29 @@ void bcnn_hip_upsample_backward(float *dx_d, const float *dy_d, int n, int c, in
 void bcnn_hip_yolo_activate(const float *x_d, float *y_d, int n, int num, int coords, int classes, int hw);
 
 /* ---------------------------------------------------------------------------------------------
+ * Transposed convolution (deconvolution), implicit GEMMs on fp32 MFMA with no col2im / im2col buffer.
+ * Replaces bcnn_forward_deconv_layer_gpu / bcnn_backward_deconv_layer_gpu (bcnn_deconv_layer.c:249-320) with the
+ * semantics of the CPU workers (:150-193, :195-246):
+ *   - x [n][c][h][w], weights [c][f][k][k] (c_in major, as the reference's Wᵀ GEMM reads them), bias [f],
+ *     y [n][f][s (h - 1) + k - 2 pad][s (w - 1) + k - 2 pad];
+ *   - forward: y = act(transposed conv + bias), OVERWRITTEN; the bias is skipped for channels whose bias is exactly
+ *     0.0f or 1.0f, as bcnn_hip_add_bias does; PReLU is not supported (the reference passes NULL slopes);
+ *   - backward: dy_d <- dy_d * act'(y_d) in place; dbias += sum dy; dw += (1/n) sum x dy (beta = 1; the factor
+ *     1/n of the reference's GEMM alpha, :209, is kept); dx_d (if non-NULL) is OVERWRITTEN (beta = 0); dw_d may be
+ *     NULL (no weight gradient).
+ * pad > 0: the reference's GPU and CPU paths read the col2im / im2col workspace with the wrong extent; here pad crops
+ * the full s (h - 1) + k result by pad on each side (torch.nn.functional.conv_transpose2d(padding=pad)).
+ * workspace_d: at least bcnn_hip_deconv_workspace_size(...) floats (the K-split partials of dw; a smaller one of at
+ * least c f k k floats splits less). The weight gradient is bit-identical from run to run (fixed split, no atomics).
+ * ------------------------------------------------------------------------------------------- */
+size_t bcnn_hip_deconv_workspace_size(int n, int c, int h, int w, int f, int k, int stride, int pad);
+void bcnn_hip_deconv_forward(const float *x_d, const float *w_d, const float *bias_d, float *y_d, int n, int c, int h,
+                             int w, int f, int k, int stride, int pad, int act);
+void bcnn_hip_deconv_backward(const float *x_d, const float *w_d, const float *y_d, float *dy_d, float *dx_d,
+                              float *dw_d, float *dbias_d, int n, int c, int h, int w, int f, int k, int stride, int pad,
+                              int act, float *workspace_d, size_t workspace_elems);
+
+/* ---------------------------------------------------------------------------------------------
  * Data-parallel exchange (RCCL over xGMI).  No reference counterpart (the reference is single-device); process
  * model = the reference's one device per process (bcnn_cuda_set_device once in main, src/cli/bcnn_cl.c:281-285,
  * src/bcnn_utils.c:201): N processes, each after bcnn_hip_set_device(local rank), form one communicator.
