@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BCNN_HIP_LIB", os.path.join(_HERE, "lib", "libbcnn_hip.so"))  # override: kernel experiments
 CSRC = os.path.join(_HERE, "csrc")
 
-vp, i, f, sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
+vp, i, f, sz, u64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_uint64
 
 # name -> (restype, [argtypes]); mirrors include/bcnn_hip.h one to one
 SIGNATURES = {
@@ -120,6 +120,10 @@ SIGNATURES = {
     "bcnn_hip_deconv_workspace_size": (sz, [i] * 8),
     "bcnn_hip_deconv_forward": (None, [vp, vp, vp, vp] + [i] * 9),
     "bcnn_hip_deconv_backward": (None, [vp] * 7 + [i] * 9 + [vp, sz]),
+    "bcnn_hip_lrn_forward": (None, [vp, vp] + [i] * 5 + [f] * 3),
+    "bcnn_hip_lrn_backward": (None, [vp, vp, vp] + [i] * 5 + [f] * 3 + [i]),
+    "bcnn_hip_dropout_forward": (None, [vp, sz, f, u64, u64]),
+    "bcnn_hip_dropout_backward": (None, [vp, sz, f, u64, u64]),
     "bcnn_hip_comm_init": (None, [i, i, C.c_char_p]),
     "bcnn_hip_comm_destroy": (None, []),
     "bcnn_hip_comm_retain": (None, []),

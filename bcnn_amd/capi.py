@@ -84,6 +84,8 @@ def lib():
         "bcnn_add_convolutional_layer": (i, [vp, i, i, i, i, i, i, i, i, i, cp, cp]),
         "bcnn_add_depthwise_conv_layer": (i, [vp, i, i, i, i, i, i, cp, cp]),
         "bcnn_add_deconvolutional_layer": (i, [vp, i, i, i, i, i, i, cp, cp]),
+        "bcnn_add_lrn_layer": (i, [vp, i, f, f, f, cp, cp]), "bcnn_add_dropout_layer": (i, [vp, f, cp]),
+        "bcnn_set_dropout_seed": (None, [vp, C.c_uint64]),
         "bcnn_add_batchnorm_layer": (i, [vp, cp, cp]), "bcnn_add_maxpool_layer": (i, [vp, i, i, i, cp, cp]),
         "bcnn_add_avgpool_layer": (i, [vp, cp, cp]), "bcnn_add_activation_layer": (i, [vp, i, cp]),
         "bcnn_add_eltwise_layer": (i, [vp, i, cp, cp, cp]), "bcnn_add_fullc_layer": (i, [vp, i, i, i, i, cp, cp]),
@@ -143,6 +145,14 @@ class Net:
         """bcnn_add_deconvolutional_layer: f output channels, k x k kernel, stride s, pad p"""
         return self._added(self.L.bcnn_add_deconvolutional_layer(self.net, f, k, s, p, init, act, src.encode(),
                                                                   dst.encode()))
+
+    def lrn(self, local_size, alpha, beta, k=1.0, src="input", dst="lrn"):
+        """bcnn_add_lrn_layer: local response normalisation across channels"""
+        return self._added(self.L.bcnn_add_lrn_layer(self.net, local_size, alpha, beta, k, src.encode(), dst.encode()))
+
+    def dropout(self, rate, src):
+        """bcnn_add_dropout_layer: in place on tensor `src`"""
+        return self._added(self.L.bcnn_add_dropout_layer(self.net, rate, src.encode()))
 
     def depthwise(self, k, s, p, act=ACT_NONE, src="input", dst="dw"):
         return self._added(self.L.bcnn_add_depthwise_conv_layer(self.net, k, s, p, 0, FILLER_XAVIER, act,

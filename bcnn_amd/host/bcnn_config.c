@@ -8,7 +8,8 @@
  *     to the command-line tool: data sources, output_model, ...);
  *   - every further section is one layer; `src` may list several tensors separated by ',';
  *   - when the model file is a Darknet *.weights file, sections may omit src/dst (implicit "lid<i-1>" ->
- *     "lid<i>" chaining), `pad=1` means size/2 and `layers=` / `from=` name earlier sections.
+ *     "lid<i>" chaining; an in-place [dropout] / [activation] section stands for its source), `pad=1` means size/2 and
+ *     `layers=` / `from=` name earlier sections.
  * One deliberate difference: the reference discards the status of the layer builders; here a builder that
  * fails (an out-of-scope layer of this build, a bad tensor name) aborts the load with its status instead of
  * leaving a half-built graph. */
@@ -186,6 +187,7 @@ static void lp_reset(layer_param *lp) {
     lp->stride = 1; lp->n_filts = 1; lp->size = 3; lp->num_groups = 1; lp->rate = 1.0f; lp->num_coords = 4;
     lp->padding_type = BCNN_PADDING_SAME; lp->a = BCNN_ACT_NONE; lp->init = BCNN_FILLER_XAVIER;
     lp->cost = BCNN_METRIC_SSE; lp->loss = BCNN_LOSS_EUCLIDEAN;
+    lp->k = 1.0f; /* [lrn] without a k key: the Caffe / torch default */
 }
 
 static void lp_set_srcs(layer_param *lp, const char *list) {
@@ -229,7 +231,8 @@ static void lp_set_lid(char **dst, int id) {
 }
 
 static void lp_set(bcnn_net *net, int section_idx, layer_param *lp, const char *name, const char *val, int format) {
-    if (!strcmp(name, "dropout_rate") || !strcmp(name, "rate")) lp->rate = (float)atof(val);
+    if (!strcmp(name, "dropout_rate") || !strcmp(name, "rate") || !strcmp(name, "probability")) /* Darknet: probability */
+        lp->rate = (float)atof(val);
     else if (!strcmp(name, "filters")) lp->n_filts = atoi(val);
     else if (!strcmp(name, "size")) lp->size = atoi(val);
     else if (!strcmp(name, "stride")) lp->stride = atoi(val);
@@ -239,9 +242,10 @@ static void lp_set(bcnn_net *net, int section_idx, layer_param *lp, const char *
         if (format == 0) lp->pad = atoi(val);
         else lp->pad = atoi(val) ? lp->size / 2 : 0; /* Darknet: boolean, needs `size` to come first */
     } else if (!strcmp(name, "num_groups") || !strcmp(name, "groups")) lp->num_groups = atoi(val);
-    else if (!strcmp(name, "alpha")) lp->alpha = (float)atoi(val); /* atoi: as the reference parses these three */
-    else if (!strcmp(name, "beta")) lp->beta = (float)atoi(val);
-    else if (!strcmp(name, "k")) lp->k = (float)atoi(val);
+    /* only [lrn] reads these three; atof, where the reference's atoi loads a Caffe LRN (alpha=0.0001) as the identity */
+    else if (!strcmp(name, "alpha")) lp->alpha = (float)atof(val);
+    else if (!strcmp(name, "beta")) lp->beta = (float)atof(val);
+    else if (!strcmp(name, "k")) lp->k = (float)atof(val);
     else if (!strcmp(name, "w")) lp->in_w = atoi(val);
     else if (!strcmp(name, "h")) lp->in_h = atoi(val);
     else if (!strcmp(name, "c")) lp->in_c = atoi(val);
@@ -410,6 +414,9 @@ bcnn_status bcnn_load_net(bcnn_net *net, const char *config_path, const char *mo
         layer_param lp;
         memset(&lp, 0, sizeof(lp));
         lp_reset(&lp);
+        /* Darknet: the tensor each section stands for. An in-place section ([dropout], [activation]) creates no tensor
+         * "lid<i>": it stands for its source, so the next section and `layers=` / `from=` offsets read that tensor */
+        char **stands_for = (char **)calloc((size_t)cfg.num_sections, sizeof(char *));
         for (int i = 1; st == BCNN_SUCCESS && i < cfg.num_sections; ++i) {
             for (int j = 0; j < cfg.sections[i].num_keys; ++j)
                 lp_set(net, i, &lp, cfg.sections[i].keys[j].name, cfg.sections[i].keys[j].val, format);
@@ -419,10 +426,22 @@ bcnn_status bcnn_load_net(bcnn_net *net, const char *config_path, const char *mo
                     lp_set_lid(&lp.src_id[0], i - 1);
                 }
                 if (lp.dst_id == NULL) lp_set_lid(&lp.dst_id, i);
+                for (int k = 0; k < lp.num_srcs; ++k) {
+                    char *end = NULL;
+                    const long j = strncmp(lp.src_id[k], "lid", 3) ? -1 : strtol(lp.src_id[k] + 3, &end, 10);
+                    if (j > 0 && j < i && end && *end == '\0' && stands_for[j]) {
+                        free(lp.src_id[k]);
+                        lp.src_id[k] = dup_str(stands_for[j]);
+                    }
+                }
+                const int in_place = is_any(cfg.sections[i].name, "[activation]", "[nl]", "[dropout]", NULL);
+                stands_for[i] = dup_str(in_place && lp.num_srcs > 0 ? lp.src_id[0] : lp.dst_id);
             }
             st = add_layer(net, cfg.sections[i].name, &lp);
             lp_reset(&lp);
         }
+        for (int i = 0; i < cfg.num_sections; ++i) free(stands_for[i]);
+        free(stands_for);
         lp_reset(&lp);
     }
     ini_free(&cfg);

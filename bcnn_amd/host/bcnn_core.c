@@ -393,9 +393,10 @@ static void mark_dead_grad_fills(bcnn_net *net) {
          * gather; the full-size operand of a same-shape eltwise add) needs no fill either if that writer assigns
          * `0 + sum` instead of accumulating: mark 2, the node's backward asks bcnn_grad_sole_writer(). Holds for
          * the forward -> backward order every caller of the reference uses (bcnn_train_on_batch). */
-        if (uses == 1 && (nd->type == BCNN_LAYER_MAXPOOL || nd->type == BCNN_LAYER_DEPTHWISE_CONV2D)) {
-            /* max-pooling's gather and the depthwise data gradient (a gather too: one thread owns a dx element,
-             * bcnn_depthwise_conv_layer.c:432-547 accumulates onto the zero fill) */
+        if (uses == 1 && (nd->type == BCNN_LAYER_MAXPOOL || nd->type == BCNN_LAYER_DEPTHWISE_CONV2D ||
+                          nd->type == BCNN_LAYER_LRN)) {
+            /* max-pooling's gather, the depthwise data gradient (a gather too: one thread owns a dx element,
+             * bcnn_depthwise_conv_layer.c:432-547 accumulates onto the zero fill) and LRN's (one lane per column) */
             hc->grad_fill_dead[t] = 2;
             continue;
         }
@@ -467,6 +468,18 @@ bcnn_status bcnn_compile_net(bcnn_net *net) {
 static void relink_graph(bcnn_net *net) {
     bcnn_hip_context *hc = hctx(net);
     mark_dead_grad_fills(net);
+    /* An in-place node behind a convolution (dropout) rewrites its output between forward and backward; the reference's
+     * backward then reads the rewritten values (act'(y) of logistic / tanh differs), so the convolution must read them
+     * too instead of recomputing its output from the pre-normalisation workspace. The fusion links below all require
+     * a single writer of the tensor and so never fire across such a node. */
+    for (int i = 0; i < net->num_nodes; ++i) {
+        if (net->nodes[i].type != BCNN_LAYER_CONV2D) continue;
+        const int t = net->nodes[i].dst[0];
+        int rewritten = 0;
+        for (int j = 0; j < net->num_nodes; ++j)
+            rewritten |= net->nodes[j].type == BCNN_LAYER_DROPOUT && net->nodes[j].dst[0] == t;
+        ((bcnn_conv_param *)net->nodes[i].param)->out_rewritten = rewritten;
+    }
     bcnn_link_depthwise_batchnorm(net);
     bcnn_link_conv_eltwise(net);
     bcnn_link_conv_maxpool(net);
@@ -516,6 +529,7 @@ bcnn_status bcnn_resize_net(bcnn_net *net, int w, int h, int c, int need_realloc
     for (int i = 0; i < net->num_nodes; ++i) {
         bcnn_node *nd = &net->nodes[i];
         if (nd->num_src < 1 || nd->num_dst < 1) continue;
+        if (nd->type == BCNN_LAYER_DROPOUT) continue; /* in place: its tensor was re-shaped by its producer */
         const bcnn_tensor *s = &net->tensors[nd->src[0]];
         bcnn_tensor *d = &net->tensors[nd->dst[0]];
         const size_t old_elems = (size_t)bcnn_tensor_size(d);

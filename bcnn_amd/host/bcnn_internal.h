@@ -166,6 +166,7 @@ typedef struct bcnn_hip_context {
      * (bcnn_forward_node / bcnn_backward_node run one worker alone: 0) */
     int in_pass;
     int no_side_stream; /* bcnn_set_weight_gradient_stream(net, 0) */
+    uint64_t dropout_seed; /* bcnn_set_dropout_seed; 0 until set */
 } bcnn_hip_context;
 
 /* ---- net ------------------------------------------------------------------------------------------ */
@@ -277,6 +278,8 @@ typedef struct bcnn_conv_param {
     int insums_splits;   /* > 0: insums_gpu holds them (partials per channel) */
     int data_pending;  /* the last forward pass did not write this node's output tensor (nobody inside a pass reads it):
                         * bcnn_materialize_data produces it from bn_workspace_gpu on demand */
+    int out_rewritten; /* another node rewrites this node's output in place (dropout; set by bcnn_compile_net): the
+                        * backward reads the output tensor instead of recomputing it from bn_workspace_gpu */
 #endif
 } bcnn_conv_param;
 
@@ -386,6 +389,26 @@ typedef struct bcnn_deconv_param {
 #endif
 } bcnn_deconv_param;
 
+/* local response normalisation across channels (reference src/layers/bcnn_lrn_layer.h); no buffers: the backward
+ * recomputes the scale from the input */
+typedef struct bcnn_lrn_param {
+    int local_size;
+    float alpha;
+    float beta;
+    float k;
+} bcnn_lrn_param;
+
+/* in-place dropout (reference src/layers/bcnn_dropout_layer.h); the mask is regenerated from (key, step) of the last
+ * TRAIN forward instead of being stored (include/bcnn_hip.h) */
+typedef struct bcnn_dropout_param {
+    float dropout_rate;
+    float scale;
+    uint64_t step;      /* TRAIN forwards run so far */
+    uint64_t last_key;  /* key and step of the last TRAIN forward, for the backward */
+    uint64_t last_step;
+    int has_mask;       /* a TRAIN forward has run since the node was built */
+} bcnn_dropout_param;
+
 /* the YOLOv3 head (reference src/layers/bcnn_yolo.h); consumers read `classes` (src/cli/bcnn_cl.c:199) */
 typedef struct bcnn_yolo_param {
     int num, classes, coords, total;
@@ -435,6 +458,13 @@ void bcnn_forward_deconv_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_deconv_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_update_deconv_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_deconv_layer(bcnn_node *node);
+void bcnn_forward_lrn_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_backward_lrn_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_release_param_lrn_layer(bcnn_node *node);
+void bcnn_forward_dropout_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_backward_dropout_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_release_param_dropout_layer(bcnn_node *node);
+uint64_t bcnn_dropout_key(uint64_t seed, int node, int rank);
 
 /* SGD step on one node's parameters (bcnn_learner.c:67-104 in the reference) */
 void bcnn_link_depthwise_batchnorm(bcnn_net *net); /* bcnn_layers_hot.c; called by bcnn_compile_net */

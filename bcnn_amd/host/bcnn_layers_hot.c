@@ -268,7 +268,7 @@ void bcnn_backward_conv_layer(bcnn_net *net, bcnn_node *node) {
         bcnn_node *bn = to_bn ? &net->nodes[p->bnsums_node] : NULL;
         bcnn_batchnorm_param *bp = bn ? (bcnn_batchnorm_param *)bn->param : NULL;
         const int splits = bcnn_hip_conv_backward_presummed(
-            xin, io.w->data_gpu, io.b->data_gpu, io.y->data_gpu, io.y->grad_data_gpu, io.x->grad_data_gpu,
+            xin, io.w->data_gpu, p->out_rewritten ? NULL : io.b->data_gpu, io.y->data_gpu, io.y->grad_data_gpu, io.x->grad_data_gpu,
             io.w->grad_data_gpu, io.b->grad_data_gpu, io.x->n, io.x->c, io.x->h, io.x->w, p->num, p->size, p->stride, p->pad,
             p->num_groups, (int)p->activation, io.slopes ? io.slopes->data_gpu : NULL,
             io.slopes ? io.slopes->grad_data_gpu : NULL, p->batch_norm, io.scales ? io.scales->data_gpu : NULL,
@@ -280,7 +280,8 @@ void bcnn_backward_conv_layer(bcnn_net *net, bcnn_node *node) {
         if (bp) bp->bsums_splits = splits;
         return;
     }
-    bcnn_hip_conv_backward(xin, io.w->data_gpu, io.b->data_gpu, io.y->data_gpu, io.y->grad_data_gpu,
+    bcnn_hip_conv_backward(xin, io.w->data_gpu, p->out_rewritten ? NULL : io.b->data_gpu /* NULL: read y */,
+                           io.y->data_gpu, io.y->grad_data_gpu,
                            io.x->grad_data_gpu /* NULL for the net input: no dX */, io.w->grad_data_gpu,
                            io.b->grad_data_gpu, io.x->n, io.x->c, io.x->h, io.x->w, p->num, p->size, p->stride,
                            p->pad, p->num_groups, (int)p->activation, io.slopes ? io.slopes->data_gpu : NULL,

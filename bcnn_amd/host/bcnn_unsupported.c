@@ -1,7 +1,8 @@
 /*
  * bcnn_unsupported.c -- entry points of the public API that lie outside the hot path (SURVEY.md
  * section 8: control plane, rarely used layers; the dataset readers are in bcnn_data.c, the detector nodes in
- * bcnn_layers_detect.c, the deconvolution node in bcnn_layers_deconv.c). They exist so
+ * bcnn_layers_detect.c, the deconvolution node in bcnn_layers_deconv.c, LRN and dropout in bcnn_layers_lrn_dropout.c).
+ * They exist so
  * that every consumer of the reference links; each returns BCNN_INVALID_PARAMETER (or does nothing)
  * and says so in the log. INTEGRATION.md lists them.
  */
@@ -9,12 +10,6 @@
 
 #include "bcnn_internal.h"
 
-#define NOT_BUILT(net, what)                                                                                  \
-    do {                                                                                                      \
-        bcnn_log((net)->log_ctx, BCNN_LOG_ERROR, "%s is outside the MI355X hot-path build (see INTEGRATION.md)\n", \
-                 (what));                                                                                     \
-        return BCNN_INVALID_PARAMETER;                                                                        \
-    } while (0)
 
 /* uint8 HWC image -> float CHW, reference bcnn_data.c:70-100 */
 void bcnn_convert_img_to_float(const uint8_t *src, int w, int h, int c, float norm_coeff, int swap_to_bgr,
@@ -44,9 +39,3 @@ void bcnn_draw_color_box(unsigned char *img, int w_img, int h_img, float cx, flo
                          unsigned char color[3]) {
     (void)img; (void)w_img; (void)h_img; (void)cx; (void)cy; (void)w; (void)h; (void)color;
 }
-
-bcnn_status bcnn_add_lrn_layer(bcnn_net *net, int ls, float a, float b, float k, const char *s, const char *d) {
-    (void)ls; (void)a; (void)b; (void)k; (void)s; (void)d;
-    NOT_BUILT(net, "LRN layer");
-}
-bcnn_status bcnn_add_dropout_layer(bcnn_net *net, float rate, const char *id) { (void)rate; (void)id; NOT_BUILT(net, "dropout layer"); }

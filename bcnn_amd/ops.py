@@ -92,6 +92,29 @@ def deconv_backward(x, wt, y, dy, dx, dw, dbias, k, stride, pad, act, workspace)
                                          workspace.numel() if workspace is not None else 0)
 
 
+def lrn_forward(x, y, local_size, alpha, beta, k):
+    """LRN across channels (include/bcnn_hip.h; the reference's bcnn_lrn_layer.c:106-149 with its deviations fixed):
+    y = x * (k + alpha/n sum_window x^2)^-beta, overwritten."""
+    n, c, h, w = x.shape
+    _lib.load().bcnn_hip_lrn_forward(_f32(x), _f32(y), n, c, h, w, local_size, alpha, beta, k)
+
+
+def lrn_backward(x, dy, dx, local_size, alpha, beta, k, overwrite=0):
+    """LRN data gradient from x and dy (s and y recomputed); dx += (overwrite 0) or = (overwrite 1)."""
+    n, c, h, w = x.shape
+    _lib.load().bcnn_hip_lrn_backward(_f32(x), _f32(dy), _f32(dx), n, c, h, w, local_size, alpha, beta, k, overwrite)
+
+
+def dropout_forward(x, rate, key, step):
+    """In-place dropout of x with the Philox mask of (key, step) (include/bcnn_hip.h; bcnn_dropout_layer.c:66-82)."""
+    _lib.load().bcnn_hip_dropout_forward(_f32(x), x.numel(), rate, key, step)
+
+
+def dropout_backward(dx, rate, key, step):
+    """The same mask and scale applied to the gradient in place (bcnn_dropout_layer.c:93-111)."""
+    _lib.load().bcnn_hip_dropout_backward(_f32(dx), dx.numel(), rate, key, step)
+
+
 def batchnorm_forward(x, y, run_mean, run_var, scales, bias, saved_mean, saved_var, workspace, mode,
                       x_norm=None, act=0):
     """bcnn_forward_batchnorm_cpu (bcnn_batchnorm_layer.c:196-242)"""

@@ -238,6 +238,10 @@ BCNN_API int bcnn_get_node_tensor(bcnn_net *net, int node, int is_dst, int slot)
  * from (the reference's param->workspace: a fused-BN convolution's raw output / a batch-norm node's kept input);
  * returns a DEVICE pointer or NULL */
 BCNN_API void *bcnn_get_node_state(bcnn_net *net, int node, int which);
+/* Seed of the dropout masks (default 0). Node i of data-parallel rank r draws its mask from a Philox4x32-10 keyed by
+ * (seed, i, r), counted by its TRAIN forwards (include/bcnn_hip.h): the same seed gives the same masks run after run.
+ * Takes effect at the next TRAIN forward. */
+BCNN_API void bcnn_set_dropout_seed(bcnn_net *net, uint64_t seed);
 /* Run ONE node's forward / backward worker on whatever its tensors currently hold (no executor bookkeeping:
  * no zero fill of the dst gradients, no dead-fill elision -- a sole-writer gradient is accumulated like in the
  * reference). Used by the teacher-forced parity walk, which feeds every node the REFERENCE's inputs. */

@@ -18,6 +18,7 @@
 #define BCNN_HIP_H
 
 #include <stddef.h>
+#include <stdint.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -568,6 +569,36 @@ void bcnn_hip_deconv_forward(const float *x_d, const float *w_d, const float *bi
 void bcnn_hip_deconv_backward(const float *x_d, const float *w_d, const float *y_d, float *dy_d, float *dx_d,
                               float *dw_d, float *dbias_d, int n, int c, int h, int w, int f, int k, int stride, int pad,
                               int act, float *workspace_d, size_t workspace_elems);
+
+/* ---------------------------------------------------------------------------------------------
+ * Local response normalisation across channels (Caffe / torch.nn.functional.local_response_norm). The reference's
+ * device workers are empty (bcnn_lrn_layer.c:207-225); its CPU workers (:106-201) are wrong for every local_size
+ * (INTEGRATION.md). NCHW, channel stride h*w; with n_w = local_size:
+ *   s_c = k + (alpha / n_w) * sum_{c' in W(c)} x_{c'}^2,   W(c) = [c - (n_w - 1)/2, c + n_w/2] clipped to [0, c),
+ *   forward : y_c = x_c * s_c^-beta, OVERWRITTEN;
+ *   backward: dx_j (=, overwrite != 0 / +=, overwrite == 0) dy_j s_j^-beta
+ *                      - (2 alpha beta / n_w) x_j sum_{c in [j - n_w/2, j + (n_w - 1)/2]} dy_c y_c / s_c,
+ *             s and y recomputed from x (no saved scale tensor).
+ * Each s_c is the window sum in ascending channel order, whatever the launch shape (bit-identical results).
+ * ------------------------------------------------------------------------------------------- */
+void bcnn_hip_lrn_forward(const float *x_d, float *y_d, int n, int c, int h, int w, int local_size, float alpha,
+                          float beta, float k);
+void bcnn_hip_lrn_backward(const float *x_d, const float *dy_d, float *dx_d, int n, int c, int h, int w,
+                           int local_size, float alpha, float beta, float k, int overwrite);
+
+/* ---------------------------------------------------------------------------------------------
+ * Dropout, in place (reference bcnn_dropout_layer.c:32-126 with a reproducible mask instead of the reference's
+ * time-seeded cuRAND one). The mask of element i (0 <= i < size) is defined as:
+ *   (w0, w1, w2, w3) = Philox4x32-10(counter = (q lo32, q hi32, step lo32, step hi32), key = (key lo32, key hi32)),
+ *   q = i / 4; multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85 (Salmon et al., SC11);
+ *   u_i = (w_{i % 4} >> 8) * 2^-24;  dropped <=> u_i < rate.
+ * forward: x_i <- dropped ? 0 : x_i * scale, scale = 1.0f / (1.0f - rate) (as the reference's param->scale);
+ * backward: the same map on the gradient, with the (key, step) of the forward. rate 0 leaves the tensor unchanged.
+ * The net gives node i of rank r the key bcnn_dropout_key(seed, i, r) (host/bcnn_layers_lrn_dropout.c) and counts
+ * its TRAIN forwards in `step`.
+ * ------------------------------------------------------------------------------------------- */
+void bcnn_hip_dropout_forward(float *x_d, size_t size, float rate, uint64_t key, uint64_t step);
+void bcnn_hip_dropout_backward(float *dx_d, size_t size, float rate, uint64_t key, uint64_t step);
 
 /* ---------------------------------------------------------------------------------------------
  * Data-parallel exchange (RCCL over xGMI).  No reference counterpart (the reference is single-device); process
