@@ -124,6 +124,9 @@ SIGNATURES = {
     "bcnn_hip_lrn_backward": (None, [vp, vp, vp] + [i] * 5 + [f] * 3 + [i]),
     "bcnn_hip_dropout_forward": (None, [vp, sz, f, u64, u64]),
     "bcnn_hip_dropout_backward": (None, [vp, sz, f, u64, u64]),
+    "bcnn_hip_lifted_struct_workspace_size": (sz, [i, i]),
+    "bcnn_hip_lifted_struct_forward": (None, [vp, vp, vp, i, i, f, i, vp, vp]),
+    "bcnn_hip_lifted_struct_backward": (None, [vp, i, i, f, vp]),
     "bcnn_hip_comm_init": (None, [i, i, C.c_char_p]),
     "bcnn_hip_comm_destroy": (None, []),
     "bcnn_hip_comm_retain": (None, []),

@@ -16,6 +16,7 @@ MODE_PREDICT, MODE_TRAIN, MODE_VALID = 0, 1, 2
  ACT_LOGISTIC) = range(10)
 PADDING_SAME, PADDING_VALID, PADDING_CAFFE = 0, 1, 2
 FILLER_FIXED, FILLER_XAVIER, FILLER_MSRA = 0, 1, 2
+LOSS_EUCLIDEAN, LOSS_LIFTED_STRUCT = 0, 1
 LOG_SILENT = 3
 
 
@@ -86,6 +87,7 @@ def lib():
         "bcnn_add_deconvolutional_layer": (i, [vp, i, i, i, i, i, i, cp, cp]),
         "bcnn_add_lrn_layer": (i, [vp, i, f, f, f, cp, cp]), "bcnn_add_dropout_layer": (i, [vp, f, cp]),
         "bcnn_set_dropout_seed": (None, [vp, C.c_uint64]),
+        "bcnn_get_lifted_struct_loss": (i, [vp, C.POINTER(f), C.POINTER(i)]),
         "bcnn_add_batchnorm_layer": (i, [vp, cp, cp]), "bcnn_add_maxpool_layer": (i, [vp, i, i, i, cp, cp]),
         "bcnn_add_avgpool_layer": (i, [vp, cp, cp]), "bcnn_add_activation_layer": (i, [vp, i, cp]),
         "bcnn_add_eltwise_layer": (i, [vp, i, cp, cp, cp]), "bcnn_add_fullc_layer": (i, [vp, i, i, i, i, cp, cp]),
@@ -179,8 +181,17 @@ class Net:
     def softmax(self, src, dst):
         return self._added(self.L.bcnn_add_softmax_layer(self.net, src.encode(), dst.encode()))
 
-    def cost(self, src, label="label", dst="cost", scale=1.0):
-        return self._added(self.L.bcnn_add_cost_layer(self.net, 0, 0, scale, src.encode(), label.encode(), dst.encode()))
+    def cost(self, src, label="label", dst="cost", scale=1.0, loss=LOSS_EUCLIDEAN, metric=0):
+        return self._added(self.L.bcnn_add_cost_layer(self.net, loss, metric, scale, src.encode(), label.encode(),
+                                                      dst.encode()))
+
+    def lifted_struct_loss(self):
+        """(loss, positive pairs) of the latest forward of the net's last lifted-structure cost node"""
+        loss, pairs = C.c_float(), C.c_int()
+        st = self.L.bcnn_get_lifted_struct_loss(self.net, C.byref(loss), C.byref(pairs))
+        if st != 0:
+            raise ValueError("the net has no lifted-structure cost node (status %d)" % st)
+        return loss.value, pairs.value
 
     def concat(self, srcs, dst):
         """bcnn_add_concat_layer: srcs (tensor names) stacked along the channels"""

@@ -387,6 +387,13 @@ static void mark_dead_grad_fills(bcnn_net *net) {
                     ++uses;
                 }
         if (first < 0) continue;
+        /* The lifted-structure loss adds its gradient onto the fill of its SOURCE tensor in forward
+         * (bcnn_forward_cost_layer), the one writer outside a backward pass: that fill is read whoever else consumes it. */
+        int lifted_src = 0;
+        for (int i = 0; i < net->num_nodes; ++i)
+            lifted_src |= net->nodes[i].type == BCNN_LAYER_COST && net->nodes[i].src[0] == t &&
+                          ((const bcnn_cost_param *)net->nodes[i].param)->loss == BCNN_LOSS_LIFTED_STRUCT;
+        if (lifted_src) continue;
         const bcnn_node *nd = &net->nodes[first];
         if (nd->src[0] != t) continue;
         /* A gradient with exactly ONE writer that touches every element once per backward pass (max-pooling's
@@ -524,6 +531,12 @@ bcnn_status bcnn_resize_net(bcnn_net *net, int w, int h, int c, int need_realloc
                            BCNN_INVALID_PARAMETER,
                            "bcnn_resize_net: node %d is a concat / upsample / YOLO / deconvolution node, whose resize is "
                            "not supported\n", i);
+        /* every node but convolution and max-pooling takes its source's shape below, so the [n][c][1][1] embedding the
+         * lifted-structure loss was built on (and its label) would not survive the call */
+        BCNN_CHECK_AND_LOG(net->log_ctx,
+                           t != BCNN_LAYER_COST || ((const bcnn_cost_param *)net->nodes[i].param)->loss != BCNN_LOSS_LIFTED_STRUCT,
+                           BCNN_INVALID_PARAMETER,
+                           "bcnn_resize_net: node %d is a lifted-structure cost node, whose resize is not supported\n", i);
     }
     bcnn_set_input_shape(net, w, h, c, 1);
     for (int i = 0; i < net->num_nodes; ++i) {

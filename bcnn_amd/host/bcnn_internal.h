@@ -370,6 +370,13 @@ typedef struct bcnn_cost_param {
     float scale;
     bcnn_loss loss;
     bcnn_loss_metric loss_metric;
+    float num_constraints;           /* lifted-structure loss: positive pairs of the batch bcnn_get_lifted_struct_loss
+                                        last read (the reference's field, bcnn_cost_layer.h:34) */
+#ifdef BCNN_USE_HIP
+    float *lifted_workspace_gpu;     /* bcnn_hip_lifted_struct_workspace_size(n, c) floats, the node's own */
+    size_t lifted_workspace_size;
+    void *lifted_record_gpu;         /* bcnn_hip_lifted_struct_record {loss, P}: backward scales by scale / P from it */
+#endif
 } bcnn_cost_param;
 
 typedef struct bcnn_upsample_param {
@@ -447,6 +454,7 @@ void bcnn_forward_softmax_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_softmax_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_forward_cost_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_cost_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_release_param_cost_layer(bcnn_node *node);
 void bcnn_forward_concat_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_concat_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_forward_upsample_layer(bcnn_net *net, bcnn_node *node);

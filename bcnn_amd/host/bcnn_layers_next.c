@@ -232,10 +232,17 @@ bcnn_status bcnn_add_cost_layer(bcnn_net *net, bcnn_loss loss, bcnn_loss_metric 
     bcnn_node node = {0};
     BCNN_CHECK_AND_LOG(net->log_ctx, net->num_nodes >= 1, BCNN_INVALID_PARAMETER,
                        "Cost layer can't be the first layer of the network\n");
-    BCNN_CHECK_AND_LOG(net->log_ctx, loss == BCNN_LOSS_EUCLIDEAN, BCNN_INVALID_PARAMETER,
-                       "Cost layer: only the euclidean loss is built in the MI355X hot-path build\n");
+    BCNN_CHECK_AND_LOG(net->log_ctx, loss == BCNN_LOSS_EUCLIDEAN || loss == BCNN_LOSS_LIFTED_STRUCT, BCNN_INVALID_PARAMETER,
+                       "Cost layer: unknown loss %d\n", (int)loss);
     const int idx = bcnn_net_find_tensor(net, src_id);
     BCNN_CHECK_AND_LOG(net->log_ctx, idx >= 0, BCNN_INVALID_PARAMETER, "Cost layer: invalid input node name %s\n", src_id);
+    /* The reference takes K = c but strides the rows by c as well, so with h w > 1 it reads the wrong elements
+     * (bcnn_lifted_structure_loss.c:31-33, :57-60): refused here. */
+    BCNN_CHECK_AND_LOG(net->log_ctx,
+                       loss != BCNN_LOSS_LIFTED_STRUCT || (net->tensors[idx].h == 1 && net->tensors[idx].w == 1),
+                       BCNN_INVALID_PARAMETER,
+                       "Cost layer: the lifted-structure loss needs a [n][c][1][1] embedding, %s is %d x %d x %d\n", src_id,
+                       net->tensors[idx].w, net->tensors[idx].h, net->tensors[idx].c);
     bcnn_node_add_input(net, &node, idx);
     node.type = BCNN_LAYER_COST;
     node.param_size = sizeof(bcnn_cost_param);
@@ -244,6 +251,7 @@ bcnn_status bcnn_add_cost_layer(bcnn_net *net, bcnn_loss loss, bcnn_loss_metric 
     param->scale = scale; param->loss = loss; param->loss_metric = loss_metric;
     node.forward = bcnn_forward_cost_layer;
     node.backward = bcnn_backward_cost_layer;
+    node.release_param = bcnn_release_param_cost_layer;
     const bcnn_tensor s = net->tensors[idx];
     bcnn_tensor_set_shape(&net->tensors[1], s.n, s.c, s.h, s.w, 0);
     BCNN_CHECK_STATUS(bcnn_tensor_allocate(&net->tensors[1], net->mode));
@@ -298,7 +306,25 @@ void bcnn_forward_cost_layer(bcnn_net *net, bcnn_node *node) {
     bcnn_tensor *pred = &net->tensors[node->src[0]], *label = &net->tensors[1], *dst = &net->tensors[node->dst[0]];
     if (!label->data) return;
     const size_t sz = (size_t)bcnn_tensor_size(pred);
-    if (dst->grad_data_gpu) {
+    if (p->loss == BCNN_LOSS_LIFTED_STRUCT) {
+        /* The reference's host loop (bcnn_lifted_structure_loss.c:16-298) adds the unscaled gradient onto the zero fill
+         * of the SOURCE gradient in forward and leaves the node's own dst gradient alone; so does this. PREDICT nets
+         * have no gradient to write. Nothing is copied to the host: {loss, P} stay in a device record that the backward
+         * scales from and bcnn_get_lifted_struct_loss reads. */
+        if (pred->grad_data_gpu && label->data_gpu && net->mode != BCNN_MODE_PREDICT) {
+            const size_t need = bcnn_hip_lifted_struct_workspace_size(pred->n, pred->c);
+            if (p->lifted_workspace_size < need) { /* first forward, or the batch grew since (a new input shape) */
+                bcnn_hip_sync();
+                bcnn_hip_free(p->lifted_workspace_gpu);
+                p->lifted_workspace_gpu = bcnn_hip_malloc_f32(need);
+                p->lifted_workspace_size = need;
+            }
+            if (!p->lifted_record_gpu) p->lifted_record_gpu = bcnn_hip_malloc_f32(2);
+            bcnn_hip_lifted_struct_forward(pred->data_gpu, label->data_gpu, pred->grad_data_gpu, pred->n, pred->c, 1.0f, 1,
+                                           (bcnn_hip_lifted_struct_record *)p->lifted_record_gpu,
+                                           p->lifted_workspace_gpu);
+        }
+    } else if (dst->grad_data_gpu) {
         bcnn_hip_copy_f32(sz, pred->data_gpu, dst->grad_data_gpu);
         bcnn_hip_axpy(sz, -1.0f, label->data_gpu, dst->grad_data_gpu);
     }
@@ -324,6 +350,36 @@ void bcnn_forward_cost_layer(bcnn_net *net, bcnn_node *node) {
 void bcnn_backward_cost_layer(bcnn_net *net, bcnn_node *node) {
     bcnn_cost_param *p = (bcnn_cost_param *)node->param;
     bcnn_tensor *pred = &net->tensors[node->src[0]], *dst = &net->tensors[node->dst[0]];
+    if (p->loss == BCNN_LOSS_LIFTED_STRUCT) { /* bcnn_lifted_structure_loss.c:300-320: gradient *= scale / P */
+        if (pred->grad_data_gpu && p->lifted_record_gpu)
+            bcnn_hip_lifted_struct_backward(pred->grad_data_gpu, pred->n, pred->c, p->scale,
+                                            (const bcnn_hip_lifted_struct_record *)p->lifted_record_gpu);
+        return;
+    }
     if (pred->grad_data_gpu)
         bcnn_hip_axpy((size_t)bcnn_tensor_size(pred), p->scale, dst->grad_data_gpu, pred->grad_data_gpu);
+}
+
+void bcnn_release_param_cost_layer(bcnn_node *node) {
+    bcnn_cost_param *p = (bcnn_cost_param *)node->param;
+    bcnn_hip_free(p->lifted_workspace_gpu);
+    bcnn_hip_free(p->lifted_record_gpu);
+}
+
+/* The lifted-structure loss value is not visible otherwise: dst->data[0] holds the metric (bcnn_cost_layer.c:263-265).
+ * Reads the 8-byte device record of the LAST cost node with this loss, as its latest forward left it. */
+bcnn_status bcnn_get_lifted_struct_loss(bcnn_net *net, float *loss, int *num_constraints) {
+    if (!net) return BCNN_INVALID_PARAMETER;
+    for (int i = net->num_nodes - 1; i >= 0; --i) {
+        if (net->nodes[i].type != BCNN_LAYER_COST) continue;
+        bcnn_cost_param *p = (bcnn_cost_param *)net->nodes[i].param;
+        if (p->loss != BCNN_LOSS_LIFTED_STRUCT) continue;
+        bcnn_hip_lifted_struct_record rec = {0.f, 0};
+        if (p->lifted_record_gpu) bcnn_hip_memcpy_d2h(&rec, p->lifted_record_gpu, sizeof(rec));
+        p->num_constraints = (float)rec.num_constraints;
+        if (loss) *loss = rec.loss;
+        if (num_constraints) *num_constraints = rec.num_constraints;
+        return BCNN_SUCCESS;
+    }
+    return BCNN_INVALID_PARAMETER;
 }

@@ -105,6 +105,27 @@ def lrn_backward(x, dy, dx, local_size, alpha, beta, k, overwrite=0):
     _lib.load().bcnn_hip_lrn_backward(_f32(x), _f32(dy), _f32(dx), n, c, h, w, local_size, alpha, beta, k, overwrite)
 
 
+def lifted_struct_workspace_size(batch, k):
+    return int(_lib.load().bcnn_hip_lifted_struct_workspace_size(batch, k))
+
+
+def lifted_struct_forward(x, label, g, record, workspace, margin=1.0, accumulate=False):
+    """Lifted-structure loss of a [B][K] embedding with a one-hot [B][K] label (include/bcnn_hip.h): g = (or +=) the
+    unscaled gradient the reference's forward leaves (bcnn_lifted_structure_loss.c:16-298), record = 2 x 4 bytes on the
+    device, {float loss, int32 P}; workspace holds at least lifted_struct_workspace_size(B, K) floats."""
+    b, k = x.shape[0], x.numel() // x.shape[0]
+    assert label.numel() == x.numel() and g.numel() == x.numel() and record.numel() * record.element_size() >= 8
+    assert workspace.numel() >= lifted_struct_workspace_size(b, k)
+    _lib.load().bcnn_hip_lifted_struct_forward(_f32(x), _f32(label), _f32(g), b, k, margin, 1 if accumulate else 0,
+                                               record.data_ptr(), _f32(workspace))
+
+
+def lifted_struct_backward(g, record, scale):
+    """g *= scale / P with P read from the record on the device (P == 0: g *= 0), bcnn_lifted_structure_loss.c:300-320"""
+    b, k = g.shape[0], g.numel() // g.shape[0]
+    _lib.load().bcnn_hip_lifted_struct_backward(_f32(g), b, k, scale, record.data_ptr())
+
+
 def dropout_forward(x, rate, key, step):
     """In-place dropout of x with the Philox mask of (key, step) (include/bcnn_hip.h; bcnn_dropout_layer.c:66-82)."""
     _lib.load().bcnn_hip_dropout_forward(_f32(x), x.numel(), rate, key, step)

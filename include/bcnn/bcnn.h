@@ -242,6 +242,11 @@ BCNN_API void *bcnn_get_node_state(bcnn_net *net, int node, int which);
  * (seed, i, r), counted by its TRAIN forwards (include/bcnn_hip.h): the same seed gives the same masks run after run.
  * Takes effect at the next TRAIN forward. */
 BCNN_API void bcnn_set_dropout_seed(bcnn_net *net, uint64_t seed);
+/* Loss value and number of positive pairs P of the latest forward of the LAST cost node with
+ * BCNN_LOSS_LIFTED_STRUCT (the node's output holds the metric, as in the reference, so the loss is not visible
+ * otherwise). An 8-byte read-back; either pointer may be NULL. BCNN_INVALID_PARAMETER if the net has no such node.
+ * A batch without a positive pair gives loss 0 and P 0. */
+BCNN_API bcnn_status bcnn_get_lifted_struct_loss(bcnn_net *net, float *loss, int *num_constraints);
 /* Run ONE node's forward / backward worker on whatever its tensors currently hold (no executor bookkeeping:
  * no zero fill of the dst gradients, no dead-fill elision -- a sole-writer gradient is accumulated like in the
  * reference). Used by the teacher-forced parity walk, which feeds every node the REFERENCE's inputs. */

@@ -601,6 +601,38 @@ void bcnn_hip_dropout_forward(float *x_d, size_t size, float rate, uint64_t key,
 void bcnn_hip_dropout_backward(float *dx_d, size_t size, float rate, uint64_t key, uint64_t step);
 
 /* ---------------------------------------------------------------------------------------------
+ * Lifted-structure loss of the cost node (Song et al., "Deep Metric Learning via Lifted Structured Feature
+ * Embedding"). The reference computes it on the host, in its CUDA build too (bcnn_lifted_structure_loss.c:16-298):
+ * every positive pair walks every negative of both anchors, O(P B K). Here, with x [B][K] the embedding,
+ * cls[i] the index of the first entry > 0 in row i of the [B][K] label (-1 if none) and m = margin:
+ *   D_ij  = |x_i - x_j|                                   (Gram form on fp32 MFMA for K >= 32, differences below)
+ *   neg(i,k) = cls[i] != cls[k]        pos(i,j) = cls[i] == cls[j] and i != j
+ *   E_ik  = exp(m - D_ik) if neg(i,k) else 0              S_i = sum_k E_ik
+ *   L_ij  = max(0, log(S_i + S_j) + D_ij) for pos(i,j)    (0 when S_i + S_j == 0)
+ *   P     = number of unordered positive pairs            loss = sum_{i<j, pos} L_ij^2 / P
+ *   Wp_ij = 2 L_ij / (D_ij + 1e-10) for pos(i,j), else 0
+ *   T_i   = sum_{j: pos(i,j)} 2 L_ij / (S_i + S_j)        (term 0 when S_i + S_j == 0)
+ *   Wn_ik = -T_i E_ik / D_ik for neg(i,k), else 0         A = Wp + Wn + Wn^T
+ *   g     = diag(rowsum(A)) x - A x                       ([B][K]; what the reference's forward leaves in the gradient)
+ * forward : g_d = g (accumulate == 0) or g_d += g (accumulate != 0, the reference's add onto the zero fill);
+ *           record_d = {loss, P}; no positive pair: loss 0, P 0, g = 0 (the reference divides 0 by 0).
+ * backward: g_d *= scale / P with P read from record_d on the device (P == 0: g_d *= 0).
+ * workspace_d: at least bcnn_hip_lifted_struct_workspace_size(batch, k) floats, about batch^2; it needs no
+ * initialisation and its contents afterwards are unspecified. No atomics and a summation order that depends on
+ * (batch, k) only: two calls on the same input give the same bits. Two samples of different classes with identical
+ * embeddings divide by D = 0, as in the reference.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct bcnn_hip_lifted_struct_record {
+    float loss;
+    int num_constraints;
+} bcnn_hip_lifted_struct_record;
+size_t bcnn_hip_lifted_struct_workspace_size(int batch, int k);
+void bcnn_hip_lifted_struct_forward(const float *x_d, const float *label_d, float *g_d, int batch, int k, float margin,
+                                    int accumulate, bcnn_hip_lifted_struct_record *record_d, float *workspace_d);
+void bcnn_hip_lifted_struct_backward(float *g_d, int batch, int k, float scale,
+                                     const bcnn_hip_lifted_struct_record *record_d);
+
+/* ---------------------------------------------------------------------------------------------
  * Data-parallel exchange (RCCL over xGMI).  No reference counterpart (the reference is single-device); process
  * model = the reference's one device per process (bcnn_cuda_set_device once in main, src/cli/bcnn_cl.c:281-285,
  * src/bcnn_utils.c:201): N processes, each after bcnn_hip_set_device(local rank), form one communicator.
