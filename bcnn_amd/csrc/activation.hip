@@ -96,7 +96,7 @@ void bcnn_hip_activation_backward(const float* x, float* dx, size_t size, int ac
     if (dslopes) {
         const long long M = (long long)n * spatial;
         const int splits = chan_splits(channels, M);
-        float* part = reduce_scratch((size_t)channels * splits);
+        float* part = scratch(SCRATCH_REDUCE, (size_t)channels * splits);
         launch_chan_reduce<1>(PreluGradF{x, dx}, channels, spatial, M, splits, part);
         accumulate_kernel<<<ceil_div(channels, 256), 256, 0, current_stream()>>>(part, channels, splits, dslopes);
         KERNEL_CHECK();

@@ -29,32 +29,11 @@ namespace bcnn_hip {
 // table (same operations, same roundings: bit-identical results), and the bodies load three float4 per call.
 //   forward  [2c]   = {mean, rs6, 1 / rs6, scale}   [2c + 1] = {bias, -, -, -}                  rs6 = sqrt(var + 1e-6)
 //   backward [3c]   = {mean, scale, rs5, 1 / rs5}   [3c + 1] = {rs6, 1 / rs6, fwd bias, dmean / M}   [3c + 2] = {dvar, -, -, -}
-struct ConstScratch {
-    float4* p = nullptr;
-    size_t cap = 0;
-    int dev = -1;
-};
-// One table per host thread AND device (a thread that alternates devices keeps each device's table). A thread drives
-// one stream at a time (runtime.hip: the current stream is per thread), and finalize -> apply run back to back on it: two nets
-// on different streams need two host threads, like every per-thread scratch of this library.
-constexpr int kMaxDevices = 64;
-static thread_local ConstScratch g_bn_consts[kMaxDevices];
-float4* bn_consts_scratch(int channels, bool required);
-float4* bn_consts_scratch(int channels, bool required) {  // grow-only: finalize -> apply only
-    if (!required && BCNN_EXP_ENV("BCNN_HIP_BN_NO_CONSTS")) return nullptr;  // A/B switch (experiment build): constants evaluated in the bodies
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= kMaxDevices) { fprintf(stderr, "[bcnn_hip] device ordinal %d out of range\n", dev); exit(1); }
-    ConstScratch& sc = g_bn_consts[dev];
-    const size_t need = (size_t)channels * 3;
-    if (sc.p == nullptr || sc.cap < need) {
-        if (sc.p) HIP_CHECK(hipFree(sc.p));  // hipFree syncs the device
-        const size_t cap = need < 4096 ? 4096 : need * 2;
-        HIP_CHECK(hipMalloc((void**)&sc.p, cap * sizeof(float4)));
-        sc.cap = cap;
-        sc.dev = dev;
-    }
-    return sc.p;
+// The table is the SCRATCH_BN_CONSTS slot (common.h), written and read on the current stream: finalize -> apply run back to back
+// on it, so two nets on different streams need two host threads, like every library scratch.
+static float4* bn_consts_scratch(int channels) {
+    if (BCNN_EXP_ENV("BCNN_HIP_BN_NO_CONSTS")) return nullptr;  // A/B switch (experiment build): constants evaluated in the bodies
+    return scratch_f4(SCRATCH_BN_CONSTS, (size_t)channels * 3);
 }
 __device__ __forceinline__ void bn_fwd_consts_store(float4* consts, int c, float mean, float var, const float* scale,
                                                     const float* bias) {
@@ -464,7 +443,7 @@ void batchnorm_forward_impl(const float* x, float* y, float* run_mean, float* ru
     a.predict = (mode == BCNN_HIP_MODE_PREDICT);
     a.mean = run_mean; a.var = run_var;
     a.consts = nullptr;
-    float4* consts = (mode == BCNN_HIP_MODE_TRAIN && !stats_only) ? bn_consts_scratch(c, false) : nullptr;
+    float4* consts = (mode == BCNN_HIP_MODE_TRAIN && !stats_only) ? bn_consts_scratch(c) : nullptr;
     if (mode == BCNN_HIP_MODE_PREDICT) a.ws = nullptr;  // the reference keeps no copy in PREDICT mode
     if (mode == BCNN_HIP_MODE_VALID) a.xn = nullptr;    // x_norm is only written in TRAIN mode (:230)
     if (have_pre) {
@@ -474,7 +453,7 @@ void batchnorm_forward_impl(const float* x, float* y, float* run_mean, float* ru
         a.mean = saved_mean; a.var = saved_var; a.consts = consts;
     } else if (mode == BCNN_HIP_MODE_TRAIN) {
         const int splits = chan_splits(c, M);
-        float* part = reduce_scratch((size_t)c * splits * 2);
+        float* part = scratch(SCRATCH_REDUCE, (size_t)c * splits * 2);
         launch_chan_reduce<2>(StatsF{x}, c, hw, M, splits, part);
         bn_stats_finalize_kernel<<<ceil_div(c, 256), 256, 0, current_stream()>>>(
             part, c, splits, (int)M, saved_mean, saved_var, run_mean, run_var, consts, scales, bias, mean_shift);
@@ -538,7 +517,7 @@ void batchnorm_backward_sums(const float* dy, const float* y, int act, const flo
                              float consts_fM = 0.f /* divisor of dmean in the table; 0: N * hw */) {
     const long long M = (long long)n * hw;
     const int splits = chan_splits(c, M);
-    float* part = reduce_scratch((size_t)c * splits * 2);
+    float* part = scratch(SCRATCH_REDUCE, (size_t)c * splits * 2);
     BwdSumsF f;
     f.dy = dy; f.y = y; f.x = workspace; f.mean = saved_mean; f.act = act; f.C = c; f.HW = hw;
     f.fwd_bias = fwd_bias; f.var = saved_var; f.scale = scales; f.res = res; f.res_count = res_count;
@@ -593,7 +572,7 @@ void batchnorm_backward_impl(float* dy, float* dx, const float* y, int act, cons
         bcnn_hip_activation_backward(y, dy, (size_t)total, act, nullptr, nullptr, hw, c);
         act = BCNN_HIP_ACT_NONE;
     }
-    float4* consts = bn_consts_scratch(c, false);
+    float4* consts = bn_consts_scratch(c);
     batchnorm_backward_sums(dy, y, act, scales, dscales, dbias, saved_mean, saved_var, dmean, dvar, workspace, n, c, hw,
                             fwd_bias, nullptr, 0, consts);
     batchnorm_backward_apply(dy, dx, y, act, scales, saved_mean, saved_var, dmean, dvar, workspace, n, c, hw, fwd_bias, 0,
@@ -609,7 +588,7 @@ void batchnorm_backward_presummed(float* dy, const float* y, int act, const floa
     if (!total) return;
     if (act == BCNN_HIP_ACT_NONE) fwd_bias = nullptr;
     KTimer kt(K_BN_BWD, 0.0, 4.0 * ((act != BCNN_HIP_ACT_NONE && !fwd_bias) ? 4.0 : 3.0) * (double)total);
-    float4* consts = bn_consts_scratch(c, false);
+    float4* consts = bn_consts_scratch(c);
     bn_bwd_finalize_wide_kernel<<<c, 1024, 0, current_stream()>>>(sums, c, splits, scales, saved_var, dbias, dscales, dmean,
                                                                   dvar, consts, saved_mean, fwd_bias, (float)M);
     KERNEL_CHECK();
@@ -640,7 +619,7 @@ void batchnorm_backward_residual(const float* dout, const float* out, int act_re
         bn_residual_grad_kernel<<<stream_grid(cnt, 256), 256, 0, current_stream()>>>(out, dout, dres, cnt, act_res);
         KERNEL_CHECK();
     }
-    float4* consts = bn_consts_scratch(c, false);
+    float4* consts = bn_consts_scratch(c);
     batchnorm_backward_sums(dout, out, act_res, scales, dscales, dbias, saved_mean, saved_var, dmean, dvar, workspace, n, c,
                             hw, fwd_bias, res, cnt, consts);
     batchnorm_backward_apply(const_cast<float*>(dout), dx, out, act_res, scales, saved_mean, saved_var, dmean, dvar,

@@ -5,29 +5,6 @@
 
 namespace bcnn_hip {
 
-// ---- per-thread reduction scratch ---------------------------------------------------------------
-struct Scratch {
-    float* p = nullptr;
-    size_t cap = 0;
-    int dev = -1;
-};
-static thread_local Scratch g_scratch[64];  // per host thread and device
-
-float* reduce_scratch(size_t floats) {
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) { fprintf(stderr, "[bcnn_hip] device ordinal %d out of range\n", dev); exit(1); }
-    Scratch& sc = g_scratch[dev];
-    if (sc.p == nullptr || sc.cap < floats) {
-        if (sc.p) HIP_CHECK(hipFree(sc.p));  // hipFree syncs the device
-        size_t cap = floats < (1u << 16) ? (1u << 16) : floats * 2;
-        HIP_CHECK(hipMalloc((void**)&sc.p, cap * sizeof(float)));
-        sc.cap = cap;
-        sc.dev = dev;
-    }
-    return sc.p;
-}
-
 // ---- elementwise -------------------------------------------------------------------------------
 template <class Op>
 __global__ __launch_bounds__(256) void map2_kernel(const float* __restrict__ x, float* __restrict__ y,
@@ -234,7 +211,7 @@ void bcnn_hip_grad_bias(float* dbias, const float* g, int n, int c, int hw) {
     const long long M = (long long)n * hw;
     if (!M || !c) return;
     const int splits = chan_splits(c, M);
-    float* part = reduce_scratch((size_t)c * splits);
+    float* part = scratch(SCRATCH_REDUCE, (size_t)c * splits);
     launch_chan_reduce<1>(SumF{g}, c, hw, M, splits, part);
     chan_accumulate_kernel<<<ceil_div(c, 256), 256, 0, current_stream()>>>(part, c, splits, dbias);
     KERNEL_CHECK();
@@ -255,7 +232,7 @@ void activation_backward_grad_bias(const float* y, float* dy, float* dbias, int 
         return;
     }
     const int splits = chan_splits(c, M);
-    float* part = reduce_scratch((size_t)c * splits);
+    float* part = scratch(SCRATCH_REDUCE, (size_t)c * splits);
     launch_chan_reduce<1>(ActBwdSumF{y, dy, act}, c, hw, M, splits, part);
     chan_accumulate_kernel<<<ceil_div(c, 256), 256, 0, current_stream()>>>(part, c, splits, dbias);
     KERNEL_CHECK();
@@ -268,7 +245,7 @@ void bcnn_hip_grad_scales(const float* x_norm, const float* g, int n, int c, int
     const long long M = (long long)n * hw;
     if (!M || !c) return;
     const int splits = chan_splits(c, M);
-    float* part = reduce_scratch((size_t)c * splits);
+    float* part = scratch(SCRATCH_REDUCE, (size_t)c * splits);
     launch_chan_reduce<1>(DotF{g, x_norm}, c, hw, M, splits, part);
     chan_accumulate_kernel<<<ceil_div(c, 256), 256, 0, current_stream()>>>(part, c, splits, dscales);
     KERNEL_CHECK();

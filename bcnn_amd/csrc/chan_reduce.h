@@ -187,7 +187,4 @@ inline void launch_chan_map(const Body& body, int N, int C, int HW) {
 }
 #endif
 
-// Small per-stream scratch for reduction partials (grow-only, freed at process exit).
-float* reduce_scratch(size_t floats);  // blas1.hip
-
 }  // namespace bcnn_hip

@@ -34,6 +34,36 @@ namespace bcnn_hip {
 hipStream_t current_stream();
 void set_current_stream(hipStream_t st);  // runtime.hip
 
+// The calling thread's device ordinal, checked against the bound of the per-device tables (exits outside it). runtime.hip
+constexpr int kMaxDevices = 64;
+int current_device();
+
+// ---- library-private device scratch (runtime.hip) -----------------------------------------------------------------------------
+// Grow-only blocks, one per host thread, device and slot; not zero-filled. A thread drives at most two streams at a time: the
+// current stream and, inside a backward pass, the weight-gradient side stream (conv.hip). No slot is used on both. A block that
+// must grow is freed after hipDeviceSynchronize (queued readers may be on either stream); each slot's growth rule (minimum,
+// headroom) is its row of the policy table in runtime.hip.
+enum ScratchSlot {
+    SCRATCH_REDUCE,        // current stream: split partials of the channel / GEMM reductions (blas1.hip and its callers)
+    SCRATCH_BN_CONSTS,     // current stream: batch-norm per-channel constants, finalize -> apply (float4: scratch_f4)
+    SCRATCH_FOLD_ROWCONST, // current stream: row constants of a batch-norm folded into a 1x1 convolution (conv.hip, forward)
+    SCRATCH_COL,           // current stream: col buffer of the few-channel data gradient (conv_igemm.hip)
+    SCRATCH_DMA,           // current stream: LDS-DMA weight packs, padded input of the few-channel forward (conv_igemm_dma.hip)
+    SCRATCH_DMA_DW,        // side stream: padded input of the few-channel weight gradient (conv_igemm_dma.hip)
+    SCRATCH_WINO,          // current stream: V, M, U of the three-kernel F(2x2,3x3) forward / data gradient (conv_winograd.hip)
+    SCRATCH_WINO_DW,       // side stream: V, M, U of the three-kernel F(2x2,3x3) weight gradient (conv_winograd.hip)
+    SCRATCH_WINO43_U,      // current stream: packed U of the F(4x4,3x3) forward / data gradient (conv_winograd43b.hip)
+    SCRATCH_WINO43_TAIL,   // current stream: piece outputs of its K-split tail (U is still being read)
+    SCRATCH_WFUSED_U,      // current stream: packed U of the fused F(2x2,3x3) forward / data gradient (conv_winograd_fused.hip)
+    SCRATCH_WFUSED_TAIL,   // current stream: piece outputs of its K-split tail
+    SCRATCH_W43FF_U,       // current stream: packed U of the first-form F(4x4,3x3) (experiment build, wino43_first_form_exp.h)
+    SCRATCH_W43FF_TAIL,    // current stream: piece outputs of its K-split tail (experiment build)
+    SCRATCH_SLOTS
+};
+// A block of at least `floats` floats for `slot` on the calling thread's device; valid until that slot's next call.
+float* scratch(ScratchSlot slot, size_t floats);
+inline float4* scratch_f4(ScratchSlot slot, size_t n) { return reinterpret_cast<float4*>(scratch(slot, n * 4)); }
+
 // Optional per-kernel-class timing with HIP events on the launch stream (off by default; bench.py turns it
 // on to report the roofline of the dominant kernel from inside the timed region). runtime.hip.
 enum KClass { K_CONV_FWD = 0, K_CONV_DW, K_CONV_DX, K_BN_FWD, K_BN_BWD, K_POOL, K_ELTWISE_ACT, K_GEMM, K_SGD,

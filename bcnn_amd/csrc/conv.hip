@@ -23,7 +23,6 @@ void batchnorm_backward_presummed(float* dy, const float* y, int act, const floa
                                   const float* saved_mean, const float* saved_var, float* dmean, float* dvar,
                                   const float* workspace, int n, int c, int hw, const float* fwd_bias, const float* sums,
                                   int splits);  // batchnorm.hip
-float* reduce_scratch(size_t floats);                                                        // blas1.hip
 size_t conv_dw_workspace_floats(const ConvShape& s);
 bool conv_backward_weights(const float* x, const float* dy, float* dw, float* dbias, const ConvShape& s,
                            float* workspace, size_t workspace_floats, bool want_bias);
@@ -116,48 +115,35 @@ __global__ __launch_bounds__(256) void bnfold_rowconst_kernel(const float* __res
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
     if (lane == 0) rowc[f] = (float)acc;
 }
-struct FoldScratch { float* p = nullptr; size_t cap = 0; };
-static thread_local FoldScratch g_fold_scratch[64];
 static float* fold_rowconst(const BnFold& fold, const float* w, int C, int F) {
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) { fprintf(stderr, "[bcnn_hip] device ordinal %d out of range\n", dev); exit(1); }
-    FoldScratch& sc = g_fold_scratch[dev];
-    if (!sc.p || sc.cap < (size_t)F) {
-        if (sc.p) { HIP_CHECK(hipStreamSynchronize(current_stream())); HIP_CHECK(hipFree(sc.p)); }
-        sc.cap = F < 8192 ? 8192 : (size_t)F * 2;
-        HIP_CHECK(hipMalloc((void**)&sc.p, sc.cap * sizeof(float)));
-    }
-    bnfold_rowconst_kernel<<<ceil_div(F, 4), 256, 0, current_stream()>>>(w, fold, F, C, sc.p);
+    float* rowc = scratch(SCRATCH_FOLD_ROWCONST, (size_t)F);
+    bnfold_rowconst_kernel<<<ceil_div(F, 4), 256, 0, current_stream()>>>(w, fold, F, C, rowc);
     KERNEL_CHECK();
-    return sc.p;
+    return rowc;
 }
 
 
-// per-thread side stream for the weight-gradient GEMM of bcnn_hip_conv_backward
+// side stream for the weight-gradient GEMM of bcnn_hip_conv_backward: one per host thread and device, created on first use
 struct SideStream {
     hipStream_t stream = nullptr;
     hipEvent_t ready = nullptr, done = nullptr;
-    int dev = -1;
     bool pending = false;  // deferred mode: work queued whose completion the caller's stream has not been ordered behind yet
 };
+static thread_local SideStream g_side[kMaxDevices];
 // 0: weight gradients on the caller's stream (default); 1: on the side stream, joined before the call returns (the round-1
 // experiment); 2: on the side stream, joined when the caller says so (bcnn_hip_conv_side_join) -- bcnn_backward's mode: the
 // weight gradient of a layer then runs next to the batch-norm / pooling sweeps and the data gradients of the layers in front
 static thread_local int g_side_mode = 0;
 bool conv_side_stream_deferred() { return g_side_mode == 2; }
 static SideStream* side_stream() {
-    static thread_local SideStream ss;
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    if (ss.stream == nullptr || ss.dev != dev) {
+    SideStream& ss = g_side[current_device()];
+    if (ss.stream == nullptr) {
         // lowest priority: when a CU frees up, the caller's stream (the pass's critical chain: data gradients, sweeps) gets it first
         int prio_lo = 0, prio_hi = 0;
         HIP_CHECK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
         HIP_CHECK(hipStreamCreateWithPriority(&ss.stream, hipStreamNonBlocking, BCNN_EXP_ENV("BCNN_HIP_SIDE_PRIO_SAME") ? prio_hi : prio_lo));
         HIP_CHECK(hipEventCreateWithFlags(&ss.ready, hipEventDisableTiming));
         HIP_CHECK(hipEventCreateWithFlags(&ss.done, hipEventDisableTiming));
-        ss.dev = dev;
     }
     return &ss;
 }
@@ -378,7 +364,7 @@ static void conv_forward_impl(const float* x, const float* w, const float* bias,
         const long long tiles = (long long)n * ((s.OH + 1) / 2) * ((s.OW + 1) / 2);
         const long long slots_gemm = ceil_div(s.total_q, 64), slots_wino = 2 * ceil_div(tiles, 64);
         st.capacity = (size_t)f * (size_t)(slots_gemm > slots_wino ? slots_gemm : slots_wino) * 2;
-        st.partials = reduce_scratch(st.capacity);
+        st.partials = scratch(SCRATCH_REDUCE, st.capacity);
     }
     const float* mean_shift = nullptr;
     if (fold.mean) {
@@ -572,10 +558,10 @@ int bcnn_hip_conv_side_stream_mode(int mode) {
 }
 
 void bcnn_hip_conv_side_join(void) {
-    SideStream* ss = side_stream();
-    if (!ss->pending) return;
-    ss->pending = false;
-    HIP_CHECK(hipStreamWaitEvent(current_stream(), ss->done, 0));  // `done` was recorded behind the last weight-gradient launch
+    SideStream& ss = g_side[current_device()];  // no side stream on this device yet: nothing pending
+    if (!ss.pending) return;
+    ss.pending = false;
+    HIP_CHECK(hipStreamWaitEvent(current_stream(), ss.done, 0));  // `done` was recorded behind the last weight-gradient launch
 }
 
 void bcnn_hip_conv_backward(const float* x, const float* w, const float* bias, const float* y, float* dy, float* dx,

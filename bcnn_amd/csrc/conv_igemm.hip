@@ -392,25 +392,6 @@ __global__ __launch_bounds__(256) void col2im_batch_kernel(const float* __restri
     }
 }
 
-struct ColScratch {
-    float* p = nullptr;
-    size_t cap = 0;
-    int dev = -1;
-};
-static thread_local ColScratch g_col_scratch;
-
-static float* col_scratch(size_t floats) {
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    ColScratch& sc = g_col_scratch;
-    if (sc.p == nullptr || sc.cap < floats || sc.dev != dev) {
-        if (sc.p && sc.dev == dev) HIP_CHECK(hipFree(sc.p));  // hipFree synchronises the device
-        HIP_CHECK(hipMalloc((void**)&sc.p, floats * sizeof(float)));
-        sc.cap = floats; sc.dev = dev;
-    }
-    return sc.p;
-}
-
 static bool conv_backward_data_small_c(const float* w, const float* dy, float* dx, const ConvShape& s) {
     static const bool off = BCNN_EXP_ENV("BCNN_HIP_NO_SMALLC_DX") != nullptr;
     if (off || s.pointwise || s.groups != 1 || s.K > 32 || s.Mg < 32) return false;
@@ -419,8 +400,8 @@ static bool conv_backward_data_small_c(const float* w, const float* dy, float* d
     int chunk = (int)(((size_t)96 << 20) / (per_image * sizeof(float)));  // <= 96 MB of col in flight
     if (chunk < 1) chunk = 1;
     if (chunk > s.N) chunk = s.N;
-    float* scratch = col_scratch((size_t)chunk * per_image + (size_t)s.K * s.Mg);
-    float* wt = scratch + (size_t)chunk * per_image;
+    float* col = scratch(SCRATCH_COL, (size_t)chunk * per_image + (size_t)s.K * s.Mg);
+    float* wt = col + (size_t)chunk * per_image;
     transpose_weights_kernel<<<ceil_div(s.Mg * s.K, 256), 256, 0, current_stream()>>>(w, wt, s.Mg, s.K);
     KERNEL_CHECK();
     for (int n0 = 0; n0 < s.N; n0 += chunk) {
@@ -428,14 +409,14 @@ static bool conv_backward_data_small_c(const float* w, const float* dy, float* d
         // col = Wt * dy as a bare 1x1 "forward" over the chunk: source dy [nb][F][OH*OW], K output rows
         const ConvShape g = make_conv_shape(nb, s.F, s.OH, s.OW, s.K, 1, 1, 0, 1);
         IgemmArgs a;
-        a.a_base = wt; a.b_base = dy + (size_t)n0 * s.F * s.OHOW; a.out = scratch; a.bias = nullptr; a.slopes = nullptr;
+        a.a_base = wt; a.b_base = dy + (size_t)n0 * s.F * s.OHOW; a.out = col; a.bias = nullptr; a.slopes = nullptr;
         a.s = g; a.mode = 0; a.act = BCNN_HIP_ACT_NONE; a.add_bias = 0;
         a.M = g.Mg; a.KR = g.K; a.a_row_stride = g.K; a.a_group_stride = (long long)g.Mg * g.K;
         a.ntaps = 1; a.ntaps_magic = magic_of(1); a.ksz_magic = magic_of(1); a.nclass = 1;
         dispatch_igemm(a, g.total_q);
         const long long total = (long long)nb * s.C * s.HW;
         col2im_batch_kernel<<<stream_grid((size_t)total, 256), 256, 0, current_stream()>>>(
-            scratch, dx + (size_t)n0 * s.C * s.HW, s.C, s.H, s.W, s.ksz, s.pad, s.stride, s.OH, s.OW, (unsigned)total);
+            col, dx + (size_t)n0 * s.C * s.HW, s.C, s.H, s.W, s.ksz, s.pad, s.stride, s.OH, s.OW, (unsigned)total);
         KERNEL_CHECK();
     }
     return true;

@@ -523,29 +523,6 @@ __global__ __launch_bounds__(256) void conv_pack_weights_multi_kernel(const Igem
 // ---- host side ------------------------------------------------------------------------------------------
 static int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
-struct DmaScratch {
-    float* p = nullptr;
-    size_t cap = 0;
-    int dev = -1;
-};
-// two blocks: [0] forward / data gradient (weight packs, the padded input of the few-channel forward), [1] the padded input of
-// the few-channel WEIGHT gradient, which may run on a side stream next to another layer's data gradient
-static thread_local DmaScratch g_dma_scratch[2];
-
-static float* dma_scratch(size_t floats, int which = 0) {
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    DmaScratch& sc = g_dma_scratch[which];
-    if (sc.p == nullptr || sc.cap < floats || sc.dev != dev) {
-        if (sc.p && sc.dev == dev) HIP_CHECK(hipFree(sc.p));  // hipFree synchronises the device
-        const size_t cap = floats < (1u << 20) ? (1u << 20) : floats + floats / 2;
-        HIP_CHECK(hipMalloc((void**)&sc.p, cap * sizeof(float)));
-        sc.cap = cap;
-        sc.dev = dev;
-    }
-    return sc.p;
-}
-
 // Shapes the DMA kernel takes; everything else stays on conv_igemm.hip.
 static bool dma_supported(const ConvShape& s, int M, int J, size_t b_elems) {
     if (s.ksz > 7 && !s.pointwise) return false;
@@ -684,7 +661,7 @@ bool conv_forward_dma(const float* x, const float* w, const float* bias, const f
     const size_t at_floats = (size_t)s.groups * kk2 * a.Jpad * a.Mpad;
     float* at = prepack_take(w, PREPACK_IGEMM, 0, at_floats);  // packed ahead by bcnn_hip_conv_prepack?
     const bool packed = at != nullptr && fold == nullptr;   // a scaled pack depends on this batch's statistics: made here
-    if (!packed) at = dma_scratch(at_floats);
+    if (!packed) at = scratch(SCRATCH_DMA, at_floats);
     a.at = at; a.at_bytes = (unsigned)(at_floats * 4);
     a.b_bytes = (unsigned)((size_t)s.N * s.C * s.HW * 4);
     a.b_major_stride = s.pointwise ? s.OHOW : s.HW;
@@ -730,7 +707,7 @@ bool conv_small_c_applicable(const ConvShape& s) {
 float* conv_small_c_padded_input(const float* x, const ConvShape& s, size_t extra_floats, float** extra, int for_dw) {
     const int Hp = s.H + 2 * s.pad, Wp = s.W + 2 * s.pad;
     const size_t xp_floats = (size_t)s.N * s.C * Hp * Wp;
-    float* base = dma_scratch(xp_floats + extra_floats + 64, for_dw ? 1 : 0);
+    float* base = scratch(for_dw ? SCRATCH_DMA_DW : SCRATCH_DMA, xp_floats + extra_floats + 64);
     float* xp = base;
     if (extra) *extra = base + ((xp_floats + 63) & ~(size_t)63);
     conv_pad_input_kernel<<<stream_grid(xp_floats / 4 + 1, 256), 256, 0, current_stream()>>>(x, xp, s.H, s.W, Hp, Wp, s.pad,
@@ -788,7 +765,7 @@ bool conv_backward_data_dma(const float* w, const float* dy, float* dx, const Co
     const size_t at_floats = (size_t)s.groups * kk2 * a.Jpad * a.Mpad;
     float* at = prepack_take(w, PREPACK_IGEMM, 1, at_floats);  // packed ahead by bcnn_hip_conv_prepack?
     const bool packed = at != nullptr;
-    if (!packed) at = dma_scratch(at_floats);
+    if (!packed) at = scratch(SCRATCH_DMA, at_floats);
     a.at = at; a.at_bytes = (unsigned)(at_floats * 4);
     a.b_bytes = (unsigned)((size_t)s.N * s.F * s.OHOW * 4);
     a.b_major_stride = s.OHOW;

@@ -262,32 +262,8 @@ __global__ __launch_bounds__(256) void wino_dw_finish_kernel(const float* __rest
     }
 }
 
-// ---- scratch: V, M and U of the layer in flight (grow-only; sized by the first step, Infinity-Cache resident
-// for the shapes wino_profitable admits) ----------------------------------------------------------------------
-struct WinoScratch {
-    float* p = nullptr;
-    size_t cap = 0;
-    int dev = -1;
-};
-// two blocks: [0] forward / data gradient, [1] weight gradient -- the weight gradient may run on a side stream next to
-// another layer's data gradient (bcnn_hip_conv_side_stream_mode)
-static thread_local WinoScratch g_wino_scratch[2];
-
-static float* wino_scratch(size_t floats, int which = 0) {
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    WinoScratch& sc = g_wino_scratch[which];
-    if (sc.p == nullptr || sc.cap < floats || sc.dev != dev) {
-        if (sc.p && sc.dev == dev) {
-            HIP_CHECK(hipStreamSynchronize(current_stream()));  // launches still reading the old block
-            HIP_CHECK(hipFree(sc.p));
-        }
-        HIP_CHECK(hipMalloc((void**)&sc.p, floats * sizeof(float)));
-        sc.cap = floats;
-        sc.dev = dev;
-    }
-    return sc.p;
-}
+// V, M and U of the layer in flight live in the SCRATCH_WINO / SCRATCH_WINO_DW slots (common.h; sized by the first step,
+// Infinity-Cache resident for the shapes wino_profitable admits).
 
 // Shapes the path takes at all (the algorithm needs 3x3 / s1 / p1 / one group).
 static bool wino_applicable(const ConvShape& s) {
@@ -322,7 +298,7 @@ static void wino_run(const float* src, const float* w, float* dst, const ConvSha
     g.TH = (s.H + 1) / 2; g.TW = (s.W + 1) / 2;
     g.T = (unsigned)((long long)s.N * g.TH * g.TW);
     const size_t v_floats = (size_t)16 * J * g.T, m_floats = (size_t)16 * M * g.T, u_floats = (size_t)16 * M * J;
-    float* V = wino_scratch(v_floats + m_floats + u_floats);
+    float* V = scratch(SCRATCH_WINO, v_floats + m_floats + u_floats);
     float* Mm = V + v_floats;
     float* U = Mm + m_floats;
     wino_weight_transform_kernel<<<ceil_div((long long)M * J, 256), 256, 0, current_stream()>>>(w, U, s.F, s.C, dx_mode);
@@ -412,7 +388,7 @@ bool conv_backward_weights_winograd(const float* x, const float* dy, float* dw, 
     g.TH = (s.H + 1) / 2; g.TW = (s.W + 1) / 2;
     g.T = (unsigned)((long long)s.N * g.TH * g.TW);
     const size_t v_floats = (size_t)16 * s.C * g.T, m_floats = (size_t)16 * s.F * g.T, u_floats = (size_t)16 * s.F * s.C;
-    float* V = wino_scratch(v_floats + m_floats + u_floats, 1);
+    float* V = scratch(SCRATCH_WINO_DW, v_floats + m_floats + u_floats);
     float* dM = V + v_floats;
     float* dU = dM + m_floats;
     dim3 gi((unsigned)ceil_div(g.T, 256), (unsigned)s.C);

@@ -410,29 +410,6 @@ __global__ __launch_bounds__(256) void wino43b_pack_weights_kernel(const float* 
 }
 
 // ---- host side ------------------------------------------------------------------------------------------
-struct WbScratch {
-    float* p = nullptr;
-    size_t cap = 0;
-};
-static float* wb_grow(WbScratch (&tab)[64], size_t floats, size_t min_floats) {
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) { fprintf(stderr, "[bcnn_hip] device ordinal %d out of range\n", dev); exit(1); }
-    WbScratch& sc = tab[dev];
-    if (sc.p == nullptr || sc.cap < floats) {
-        if (sc.p) {
-            HIP_CHECK(hipStreamSynchronize(current_stream()));
-            HIP_CHECK(hipFree(sc.p));
-        }
-        const size_t cap = floats < min_floats ? min_floats : floats;
-        HIP_CHECK(hipMalloc((void**)&sc.p, cap * sizeof(float)));
-        sc.cap = cap;
-    }
-    return sc.p;
-}
-static thread_local WbScratch g_wb_u_scratch[64];
-static thread_local WbScratch g_wb_tail_scratch[64];  // separate from the U scratch, which the running kernel reads
-
 int wino43b_stats_slots(const ConvShape& s) {  // per channel, for a caller's statistics buffer
     const long long T = (long long)s.N * (s.H / 4) * (s.W / 4);
     return 2 * (int)ceil_div(T, WB_BT);
@@ -464,7 +441,7 @@ void wino43b_run(const float* src, const float* w, float* dst, const ConvShape& 
     a.upk_bytes = (unsigned)(u_floats * 4);
     float* U = prepack_take(w, PREPACK_WINO, dx_mode, u_floats);  // transformed ahead by bcnn_hip_conv_prepack?
     if (!U) {
-        U = wb_grow(g_wb_u_scratch, u_floats, (size_t)1 << 20);
+        U = scratch(SCRATCH_WINO43_U, u_floats);
         wino43b_pack_weights_kernel<<<ceil_div((long long)Jpad * Mpad, 256), 256, 0, current_stream()>>>(w, U, s.F, s.C, dx_mode, Jpad,
                                                                                                            Mpad);
         KERNEL_CHECK();
@@ -486,7 +463,7 @@ void wino43b_run(const float* src, const float* w, float* dst, const ConvShape& 
             a.tail_units = rem;
             a.tail_q = q;
             const size_t scr_floats = (size_t)2 * grid * WB_BF * WB_BT * 16;
-            a.tail_scr = wb_grow(g_wb_tail_scratch, scr_floats, scr_floats);
+            a.tail_scr = scratch(SCRATCH_WINO43_TAIL, scr_floats);
             a.tail_scr_bytes = (unsigned)(scr_floats * sizeof(float));
         }
     }

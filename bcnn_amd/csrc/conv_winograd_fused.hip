@@ -513,48 +513,6 @@ __global__ __launch_bounds__(256) void wino_pack_weights_multi_kernel(const Wino
 }
 
 // ---- host side ------------------------------------------------------------------------------------------
-struct WfScratch {
-    float* p = nullptr;
-    size_t cap = 0;
-    int dev = -1;
-};
-static thread_local WfScratch g_wf_scratch;
-static float* wf_scratch(size_t floats) {
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    WfScratch& sc = g_wf_scratch;
-    if (sc.p == nullptr || sc.cap < floats || sc.dev != dev) {
-        if (sc.p && sc.dev == dev) {
-            HIP_CHECK(hipStreamSynchronize(current_stream()));
-            HIP_CHECK(hipFree(sc.p));
-        }
-        const size_t cap = floats < (1u << 20) ? (1u << 20) : floats;
-        HIP_CHECK(hipMalloc((void**)&sc.p, cap * sizeof(float)));
-        sc.cap = cap;
-        sc.dev = dev;
-    }
-    return sc.p;
-}
-
-// the piece outputs of a K-split tail (33.5 MB: two slots of 64 x 64 x 4 floats per CU); separate from the U scratch, which
-// the running kernel reads
-static thread_local WfScratch g_wf_tail_scratch;
-static float* wf_tail_scratch(size_t floats) {
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    WfScratch& sc = g_wf_tail_scratch;
-    if (sc.p == nullptr || sc.cap < floats || sc.dev != dev) {
-        if (sc.p && sc.dev == dev) {
-            HIP_CHECK(hipStreamSynchronize(current_stream()));
-            HIP_CHECK(hipFree(sc.p));
-        }
-        HIP_CHECK(hipMalloc((void**)&sc.p, floats * sizeof(float)));
-        sc.cap = floats;
-        sc.dev = dev;
-    }
-    return sc.p;
-}
-
 #ifdef BCNN_HIP_EXPERIMENT
 }  // namespace bcnn_hip
 #include "wino_bf16_exp.h"  // the split-bf16 experiment (kernels + launch): not part of the product library
@@ -601,7 +559,7 @@ static void wino_fused_run(const float* src, const float* w, float* dst, const C
         a.upk_bytes = (unsigned)(u_floats * 4);
         float* U = prepack_take(w, PREPACK_WINO, dx_mode, u_floats);  // transformed ahead by bcnn_hip_conv_prepack?
         if (!U) {
-            U = wf_scratch(u_floats);
+            U = scratch(SCRATCH_WFUSED_U, u_floats);
             wino_pack_weights_kernel<<<ceil_div((long long)a.Jpad * a.Mpad, 256), 256, 0, current_stream()>>>(w, U, s.F, s.C, dx_mode,
                                                                                                             a.Jpad, a.Mpad);
             KERNEL_CHECK();
@@ -632,7 +590,7 @@ static void wino_fused_run(const float* src, const float* w, float* dst, const C
             a.tail_units = rem;
             a.tail_q = q;
             const size_t scr_floats = (size_t)2 * grid * 64 * 64 * 4;
-            a.tail_scr = wf_tail_scratch(scr_floats);
+            a.tail_scr = scratch(SCRATCH_WFUSED_TAIL, scr_floats);
             a.tail_scr_bytes = (unsigned)(scr_floats * sizeof(float));
         }
     }

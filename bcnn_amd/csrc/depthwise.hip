@@ -714,7 +714,7 @@ void bcnn_hip_depthwise_backward(const float* x, const float* w, const float* y,
     const int NT = k * k;
     const long long M = (long long)n * ohow;
     const int splits = chan_splits(c, M);
-    float* part = reduce_scratch((size_t)c * splits * NT);
+    float* part = scratch(SCRATCH_REDUCE, (size_t)c * splits * NT);
     dim3 grid((unsigned)c, (unsigned)splits);
     const unsigned gpr = (unsigned)ceil_div(s.OW, 4);
     constexpr int VR = DW_VR;

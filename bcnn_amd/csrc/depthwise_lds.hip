@@ -999,7 +999,7 @@ bool depthwise_backward_lds(const float* x, const float* w, const float* y, floa
     a.rfM = 1.0f / a.fM;  // host division: IEEE, round to nearest
     if (bn) a.bn = *bn;
     else a.bn = DwBnBwd{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    a.partials = reduce_scratch((size_t)s.C * a.splits * kPart);
+    a.partials = scratch(SCRATCH_REDUCE, (size_t)s.C * a.splits * kPart);
     a.in_sums = nullptr;
     if (want_sums) {
         a.in_sums = in_sums->partials;

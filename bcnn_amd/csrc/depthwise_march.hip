@@ -36,7 +36,6 @@
 namespace bcnn_hip {
 
 void dwl_finalize_launch(const float* partials, int splits, int C, float* dw, float* dbias, hipStream_t st);  // depthwise_lds.hip
-float* reduce_scratch(size_t floats);                                                                          // blas1.hip
 
 namespace {
 
@@ -837,7 +836,7 @@ bool depthwise_backward_march(const float* x, const float* w, const float* y, fl
     a.bn = bn ? *bn : DwBnBwd{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     a.in = in ? *in : DwBnIn{nullptr, nullptr, nullptr, nullptr, 0};
     const int splits = dwm_splits(s, a.g);
-    a.partials = reduce_scratch((size_t)s.C * splits * kDwmPart);
+    a.partials = scratch(SCRATCH_REDUCE, (size_t)s.C * splits * kDwmPart);
     a.in_sums = nullptr;
     // the sums of the producer's batch-norm backward are of the COMPLETE gradient: only when this kernel is its sole writer,
     // and for producer activations whose derivative is 0 or 1

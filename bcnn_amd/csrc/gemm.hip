@@ -185,7 +185,7 @@ void bcnn_hip_gemm(int ta, int tb, int m, int n, int k, float alpha, const float
     }
     a.tiles_per_split = ceil_div(ktiles, splits);
     splits = ceil_div(ktiles, a.tiles_per_split);
-    a.partials = splits > 1 ? reduce_scratch((size_t)splits * m * n) : nullptr;
+    a.partials = splits > 1 ? scratch(SCRATCH_REDUCE, (size_t)splits * m * n) : nullptr;
     dim3 grid((unsigned)ceil_div(n, 64), (unsigned)ceil_div(m, 64), (unsigned)splits);
     gemm_kernel<<<grid, 256, 0, current_stream()>>>(a);
     KERNEL_CHECK();

@@ -258,7 +258,7 @@ void bcnn_hip_cost_metric(int metric, const float* pred, const float* label, con
     int blocks = (int)((sz + 8191) / 8192);  // >= 8 values per thread before a second workgroup pays
     if (blocks > 64) blocks = 64;
     if (blocks < 1) blocks = 1;
-    double* partials = reinterpret_cast<double*>(reduce_scratch(2 * 64));
+    double* partials = reinterpret_cast<double*>(scratch(SCRATCH_REDUCE, 2 * 64));
     cost_metric_kernel<<<blocks, 1024, 0, current_stream()>>>(metric, pred, label, grad, batch, per, partials);
     KERNEL_CHECK();
     cost_metric_final_kernel<<<1, 1, 0, current_stream()>>>(metric, partials, blocks, per, out);

@@ -1,6 +1,6 @@
 // runtime.hip -- device, memory, stream and event entry points of the C-ABI (include/bcnn_hip.h).
 // Replaces the bcnn_cuda_* helper family (reference src/bcnn_utils.c:101-201). No process-global
-// library handles: the only state is one current stream per host thread.
+// library handles: the state is per host thread -- one current stream, and the table of library-private device scratch.
 #include "common.h"
 
 #include <cstring>
@@ -10,6 +10,50 @@ namespace bcnn_hip {
 static thread_local hipStream_t g_stream = nullptr;  // nullptr = null stream (PyTorch-ROCm default)
 hipStream_t current_stream() { return g_stream; }
 void set_current_stream(hipStream_t st) { g_stream = st; }  // internal: side-stream sections (conv.hip)
+
+int current_device() {
+    int dev = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    if (dev < 0 || dev >= kMaxDevices) { fprintf(stderr, "[bcnn_hip] device ordinal %d out of range\n", dev); exit(1); }
+    return dev;
+}
+
+// ---- library-private device scratch (common.h: ScratchSlot) ------------------------------------------------------------------
+// Growth: a request below `min_floats` gets min_floats, a larger one `need * grow_num / grow_den` (1/1: exactly what was asked).
+struct ScratchPolicy { size_t min_floats; unsigned grow_num, grow_den; };
+static constexpr ScratchPolicy kScratchPolicy[] = {  // in ScratchSlot order
+    /* REDUCE        */ {1u << 16, 2, 1},
+    /* BN_CONSTS     */ {4096 * 4, 2, 1},  // 4,096 float4
+    /* FOLD_ROWCONST */ {8192, 2, 1},
+    /* COL           */ {0, 1, 1},
+    /* DMA           */ {1u << 20, 3, 2},
+    /* DMA_DW        */ {1u << 20, 3, 2},
+    /* WINO          */ {0, 1, 1},
+    /* WINO_DW       */ {0, 1, 1},
+    /* WINO43_U      */ {1u << 20, 1, 1},
+    /* WINO43_TAIL   */ {0, 1, 1},
+    /* WFUSED_U      */ {1u << 20, 1, 1},
+    /* WFUSED_TAIL   */ {0, 1, 1},
+    /* W43FF_U       */ {1u << 20, 1, 1},
+    /* W43FF_TAIL    */ {0, 1, 1},
+};
+static_assert(sizeof(kScratchPolicy) / sizeof(kScratchPolicy[0]) == SCRATCH_SLOTS, "one policy row per ScratchSlot");
+struct ScratchBlock { float* p = nullptr; size_t cap = 0; };
+static thread_local ScratchBlock g_scratch[kMaxDevices][SCRATCH_SLOTS];
+
+float* scratch(ScratchSlot slot, size_t floats) {
+    ScratchBlock& b = g_scratch[current_device()][slot];
+    if (b.p == nullptr || b.cap < floats) {
+        const ScratchPolicy& pol = kScratchPolicy[slot];
+        if (b.p) {
+            HIP_CHECK(hipDeviceSynchronize());  // launches still reading the old block, on the current or the side stream
+            HIP_CHECK(hipFree(b.p));
+        }
+        b.cap = floats < pol.min_floats ? pol.min_floats : floats * pol.grow_num / pol.grow_den;
+        HIP_CHECK(hipMalloc((void**)&b.p, b.cap * sizeof(float)));
+    }
+    return b.p;
+}
 
 // ---- per-kernel-class event timing ---------------------------------------------------------------
 struct KRecord { int cls; hipEvent_t a, b; double flops, bytes, useful; };

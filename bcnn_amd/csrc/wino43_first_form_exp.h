@@ -443,46 +443,6 @@ __global__ __launch_bounds__(256) void wino43_pack_weights_kernel(const float* _
 }
 
 // ---- host side ------------------------------------------------------------------------------------------
-struct W43Scratch {
-    float* p = nullptr;
-    size_t cap = 0;
-};
-static thread_local W43Scratch g_w43_scratch[64];
-static float* w43_scratch(size_t floats) {
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) { fprintf(stderr, "[bcnn_hip] device ordinal %d out of range\n", dev); exit(1); }
-    W43Scratch& sc = g_w43_scratch[dev];
-    if (sc.p == nullptr || sc.cap < floats) {
-        if (sc.p) {
-            HIP_CHECK(hipStreamSynchronize(current_stream()));
-            HIP_CHECK(hipFree(sc.p));
-        }
-        const size_t cap = floats < (1u << 20) ? (1u << 20) : floats;
-        HIP_CHECK(hipMalloc((void**)&sc.p, cap * sizeof(float)));
-        sc.cap = cap;
-    }
-    return sc.p;
-}
-
-static thread_local W43Scratch g_w43_tail_scratch[64];  // separate from the U scratch, which the running kernel reads
-static float* w43_tail_scratch(size_t floats) {
-    int dev = 0;
-    HIP_CHECK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) { fprintf(stderr, "[bcnn_hip] device ordinal %d out of range\n", dev); exit(1); }
-    W43Scratch& sc = g_w43_tail_scratch[dev];
-    if (sc.p == nullptr || sc.cap < floats) {
-        if (sc.p) {
-            HIP_CHECK(hipStreamSynchronize(current_stream()));
-            HIP_CHECK(hipFree(sc.p));
-        }
-        HIP_CHECK(hipMalloc((void**)&sc.p, floats * sizeof(float)));
-        sc.cap = floats;
-    }
-    return sc.p;
-}
-
-
 static void wino43_run(const float* src, const float* w, float* dst, const ConvShape& s, int dx_mode, ConvStats* stats) {
     Wino43Args a;
     a.src = src; a.dst = dst;
@@ -502,7 +462,7 @@ static void wino43_run(const float* src, const float* w, float* dst, const ConvS
     a.upk_bytes = (unsigned)(u_floats * 4);
     float* U = prepack_take(w, PREPACK_WINO, dx_mode, u_floats);  // transformed ahead by bcnn_hip_conv_prepack?
     if (!U) {
-        U = w43_scratch(u_floats);
+        U = scratch(SCRATCH_W43FF_U, u_floats);
         wino43_pack_weights_kernel<<<ceil_div((long long)a.Jpad * a.Mpad, 256), 256, 0, current_stream()>>>(w, U, s.F, s.C, dx_mode,
                                                                                                           a.Jpad, a.Mpad);
         KERNEL_CHECK();
@@ -524,7 +484,7 @@ static void wino43_run(const float* src, const float* w, float* dst, const ConvS
             a.tail_units = rem;
             a.tail_q = q;
             const size_t scr_floats = (size_t)2 * grid * 32 * 32 * 16;
-            a.tail_scr = w43_tail_scratch(scr_floats);
+            a.tail_scr = scratch(SCRATCH_W43FF_TAIL, scr_floats);
             a.tail_scr_bytes = (unsigned)(scr_floats * sizeof(float));
         }
     }

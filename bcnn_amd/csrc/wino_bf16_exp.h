@@ -392,7 +392,7 @@ template <int NP>
 static void wino_bf16_launch(WinoFusedArgs& a, const float* w, const ConvShape& s, int dx_mode, unsigned grid, bool plain) {
     const size_t u_elems = (size_t)NP * 16 * a.Jpad * a.Mpad;  // bf16
     a.upk_bytes = (unsigned)(u_elems * 2);
-    float* U = wf_scratch((u_elems + 1) / 2);
+    float* U = scratch(SCRATCH_WFUSED_U, (u_elems + 1) / 2);
     a.upk = U;
     wino_pack_bf16_kernel<NP><<<ceil_div((long long)a.Jpad * a.Mpad, 256), 256, 0, current_stream()>>>(
         w, reinterpret_cast<__bf16*>(U), s.F, s.C, dx_mode, a.Jpad, a.Mpad);

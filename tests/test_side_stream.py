@@ -115,6 +115,39 @@ def test_gradients_do_not_depend_on_the_stream_of_the_weight_gradients(ch, n, hw
     net.close()
 
 
+def test_one_thread_alternating_two_devices_reproduces_the_gradients_of_device_0():
+    """one host thread, the same graph and parameters built once on device 0 and once on device 1, forward + backward on the
+    two alternately with the side stream on: the library's scratch blocks and side stream belong to a (thread, device) pair,
+    so no block or pending join of one device may reach a pass on the other -- every pass equals the first one on device 0"""
+    from bcnn_amd import _lib
+    L = _lib.load()
+    if L.bcnn_hip_device_count() < 2:
+        pytest.skip("needs two visible GPUs")
+    nets = []
+    try:
+        for dev in (0, 1):
+            L.bcnn_hip_set_device(dev)
+            ctypes.CDLL(None).srand(5)  # the builders draw the initial parameters from rand()
+            nets.append(_make(64, 16, 32, seed=5))
+        first = None
+        for _ in range(3):
+            for dev, net in enumerate(nets):
+                L.bcnn_hip_set_device(dev)
+                got = _pass(net, 1)
+                if first is None:
+                    first = got
+                    assert len(first) > 20
+                    continue
+                assert got.keys() == first.keys()
+                for i in first:
+                    assert np.array_equal(got[i], first[i]), "tensor %d on device %d differs from the first pass" % (i, dev)
+    finally:
+        for dev, net in enumerate(nets):
+            L.bcnn_hip_set_device(dev)
+            net.close()
+        L.bcnn_hip_set_device(0)
+
+
 def test_gradient_ready_callback_reads_complete_ranges_on_the_callers_stream():
     """inside the callback a copy of the reported range is queued on the CALLER's stream -- no host synchronisation -- and
     has to hold the final gradients, although the weight gradients of that range came from the library's second stream"""
