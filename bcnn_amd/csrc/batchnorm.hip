@@ -8,7 +8,7 @@
 // with the activation fused); backward = 1 pass of reads (sums) + 1 read/write pass (apply). The
 // reference CPU path makes ~10 forward sweeps (two copies, x_norm, scale and bias passes).
 #include "chan_reduce.h"
-#include "conv_common.h"
+#include "batchnorm.h"
 #include "bn_math.h"
 
 namespace bcnn_hip {
@@ -513,8 +513,8 @@ namespace bcnn_hip {
 void batchnorm_backward_sums(const float* dy, const float* y, int act, const float* scales, float* dscales,
                              float* dbias, const float* saved_mean, const float* saved_var, float* dmean,
                              float* dvar, const float* workspace, int n, int c, int hw, const float* fwd_bias,
-                             const float* res = nullptr, unsigned res_count = 0, float4* consts = nullptr,
-                             float consts_fM = 0.f /* divisor of dmean in the table; 0: N * hw */) {
+                             const float* res, unsigned res_count, float4* consts,
+                             float consts_fM /* divisor of dmean in the table; 0: N * hw */) {
     const long long M = (long long)n * hw;
     const int splits = chan_splits(c, M);
     float* part = scratch(SCRATCH_REDUCE, (size_t)c * splits * 2);

@@ -64,6 +64,9 @@ enum ScratchSlot {
 float* scratch(ScratchSlot slot, size_t floats);
 inline float4* scratch_f4(ScratchSlot slot, size_t n) { return reinterpret_cast<float4*>(scratch(slot, n * 4)); }
 
+// dy *= act'(y) in place and dbias += the per-channel sums of the result (depthwise.hip's backward). blas1.hip
+void activation_backward_grad_bias(const float* y, float* dy, float* dbias, int n, int c, int hw, int act);
+
 // Optional per-kernel-class timing with HIP events on the launch stream (off by default; bench.py turns it
 // on to report the roofline of the dominant kernel from inside the timed region). runtime.hip.
 enum KClass { K_CONV_FWD = 0, K_CONV_DW, K_CONV_DX, K_BN_FWD, K_BN_BWD, K_POOL, K_ELTWISE_ACT, K_GEMM, K_SGD,

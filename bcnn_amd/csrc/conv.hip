@@ -1,90 +1,13 @@
 // conv.hip -- C-ABI entry points of the convolution node (include/bcnn_hip.h), composing the
 // implicit-GEMM kernels (conv_fwd.hip, conv_bwd.hip) with the batch-norm / activation kernels the way
 // bcnn_forward_conv_layer_cpu / bcnn_backward_conv_layer_cpu do (reference bcnn_conv_layer.c:367-587).
-#include "conv_common.h"
+#include "batchnorm.h"
+#include "conv_paths.h"
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
 namespace bcnn_hip {
-void conv_forward_dispatch(const float* x, const float* w, const float* bias, const float* slopes, float* y,
-                           const ConvShape& s, int act, int raw, ConvStats* stats);
-void batchnorm_forward_impl(const float* x, float* y, float* run_mean, float* run_var, const float* scales,
-                            const float* bias, float* saved_mean, float* saved_var, float* x_norm, float* workspace,
-                            int n, int c, int hw, int mode, int act, const ConvStats* pre,
-                            const BnResidual* res, bool stats_only, const float* mean_shift = nullptr);  // batchnorm.hip
-void batchnorm_backward_residual(const float* dout, const float* out, int act_res, const float* res, float* dres,
-                                 size_t res_count, float* dx, const float* scales, float* dscales, float* dbias,
-                                 const float* fwd_bias, const float* saved_mean, const float* saved_var, float* dmean,
-                                 float* dvar, const float* workspace, int n, int c, int hw);  // batchnorm.hip
-void batchnorm_backward_impl(float* dy, float* dx, const float* y, int act, const float* scales, float* dscales,
-                             float* dbias, const float* saved_mean, const float* saved_var, float* dmean,
-                             float* dvar, const float* workspace, int n, int c, int hw, const float* fwd_bias);
-void batchnorm_backward_presummed(float* dy, const float* y, int act, const float* scales, float* dscales, float* dbias,
-                                  const float* saved_mean, const float* saved_var, float* dmean, float* dvar,
-                                  const float* workspace, int n, int c, int hw, const float* fwd_bias, const float* sums,
-                                  int splits);  // batchnorm.hip
-size_t conv_dw_workspace_floats(const ConvShape& s);
-bool conv_backward_weights(const float* x, const float* dy, float* dw, float* dbias, const ConvShape& s,
-                           float* workspace, size_t workspace_floats, bool want_bias);
-void conv_backward_data(const float* w, const float* dy, float* dx, const ConvShape& s, DxBnSums* bs = nullptr);
-// conv_dw_dma.hip: per-tap GEMM with LDS-DMA staging (the general fast path)
-size_t conv_dw_dma_workspace_floats(const ConvShape& s);
-bool conv_backward_weights_dma(const float* x, const float* dy, float* dw, const ConvShape& s, float* workspace,
-                               size_t workspace_floats, const BnFold* fold = nullptr);
-bool conv_forward_dma(const float* x, const float* w, const float* bias, const float* slopes, float* y,
-                      const ConvShape& s, int act, int raw, ConvStats* stats, const BnFold* fold = nullptr);  // conv_igemm_dma.hip
-bool conv_forward_dma_supported(const ConvShape& s);
-// conv_direct.hip: LDS-free kernels for small reduction lengths (K <= 32)
-bool conv_forward_direct(const float* x, const float* w, const float* bias, const float* slopes, float* y,
-                         const ConvShape& s, int act, int raw);
-size_t conv_dw_direct_workspace_floats(const ConvShape& s);
-bool conv_backward_weights_direct(const float* x, const float* dy, float* dw, float* dbias, const ConvShape& s,
-                                  float* workspace, size_t workspace_floats);
-// conv_window.hip: window-in-LDS kernels for 3x3 / s1 layers with K <= 27 (configs[1])
-bool conv_forward_window(const float* x, const float* w, const float* bias, const float* slopes, float* y, const ConvShape& s,
-                         int act, int raw);
-bool conv_forward_stem(const float* x, const float* w, const float* bias, const float* slopes, float* y, const ConvShape& s,
-                       int act, int raw, ConvStats* stats);
-size_t conv_dw_window_workspace_floats(const ConvShape& s);
-size_t conv_dw_stem_workspace_floats(const ConvShape& s);
-bool conv_backward_weights_stem(const float* x, const float* dy, float* dw, float* dbias, const ConvShape& s, float* workspace,
-                                size_t workspace_floats);
-bool conv_backward_weights_window(const float* x, const float* dy, float* dw, float* dbias, const ConvShape& s,
-                                  float* workspace, size_t workspace_floats);
-// conv_winograd.hip: F(2x2, 3x3) for the deep 3x3 / s1 layers (false: the layer stays on the direct kernels)
-bool conv_forward_winograd(const float* x, const float* w, const float* bias, const float* slopes, float* y,
-                           const ConvShape& s, int act, int raw, ConvStats* stats);
-bool conv_backward_data_winograd(const float* w, const float* dy, float* dx, const ConvShape& s);
-// conv_winograd_fused.hip: the same algorithm in one kernel for the wide-and-shallow layers
-bool conv_forward_winograd_fused(const float* x, const float* w, const float* bias, const float* slopes, float* y,
-                                 const ConvShape& s, int act, int raw, ConvStats* stats);
-bool conv_backward_data_winograd_fused(const float* w, const float* dy, float* dx, const ConvShape& s);
-// conv_winograd43.hip: F(4x4, 3x3) for planes of whole 4 x 4 tiles, raw output only
-bool conv_forward_winograd43(const float* x, const float* w, float* y, const ConvShape& s, int raw, ConvStats* stats);
-bool conv_backward_data_winograd43(const float* w, const float* dy, float* dx, const ConvShape& s);
-// few input channels (the RGB stem): padded-plane GEMM over all (c, kr, kc) rows (conv_dw_dma.hip)
-size_t conv_dw_small_c_workspace_floats(const ConvShape& s);
-bool conv_backward_weights_small_c(const float* x, const float* dy, float* dw, const ConvShape& s, float* workspace,
-                                   size_t workspace_floats);
-size_t conv_dw_winograd_fused_workspace_floats(const ConvShape& s);
-// conv_winograd43_dw.hip: F(4x4, 3x3) in its transposed form for planes of whole 4 x 4 tiles
-size_t conv_dw_winograd43_workspace_floats(const ConvShape& s);
-bool conv_backward_weights_winograd43(const float* x, const float* dy, float* dw, const ConvShape& s, float* workspace,
-                                      size_t workspace_floats);
-bool conv_backward_weights_winograd_fused(const float* x, const float* dy, float* dw, const ConvShape& s, float* workspace,
-                                          size_t workspace_floats);
-size_t conv_dw_winograd_workspace_floats(const ConvShape& s);
-bool conv_backward_weights_winograd(const float* x, const float* dy, float* dw, const ConvShape& s, float* workspace,
-                                    size_t workspace_floats);
-
-static bool conv_backward_weights_dma_timed(const float* x, const float* dy, float* dw, const ConvShape& s,
-                                            float* workspace, size_t workspace_floats, const BnFold* fold = nullptr) {
-    if (conv_dw_dma_workspace_floats(s) == 0) return false;
-    KTimer kt(K_CONV_DW, 2.0 * (double)s.total_q * s.Mg * s.K * s.groups,
-              4.0 * ((double)s.N * s.C * s.HW + (double)s.F * s.K + (double)s.N * s.F * s.OHOW));
-    return conv_backward_weights_dma(x, dy, dw, s, workspace, workspace_floats, fold);
-}
-
 // ---- a stand-alone batch-norm node in front of a 1x1 convolution, folded into it (BnFold, conv_common.h) -------------
 // The host announces the fold right before the forward / backward call it applies to (same thread): the call takes it.
 static thread_local BnFold g_fold_pending = {nullptr, nullptr, nullptr, nullptr};
@@ -146,19 +69,6 @@ static SideStream* side_stream() {
         HIP_CHECK(hipEventCreateWithFlags(&ss.done, hipEventDisableTiming));
     }
     return &ss;
-}
-
-static void conv_fwd_any(const float* x, const float* w, const float* bias, const float* slopes, float* y,
-                         const ConvShape& s, int act, int raw, ConvStats* stats = nullptr) {
-    if (stats) stats->splits = 0;
-    static const int window_on = BCNN_EXP_ENV("BCNN_HIP_NO_WINDOW") ? 0 : 1;  // A/B switch: the LDS-free kernels instead
-    if (window_on && conv_forward_window(x, w, bias, slopes, y, s, act, raw)) return;
-    if (window_on && conv_forward_stem(x, w, bias, slopes, y, s, act, raw, stats)) return;
-    if (conv_forward_direct(x, w, bias, slopes, y, s, act, raw)) return;
-    if (raw && conv_forward_winograd43(x, w, y, s, raw, stats)) return;
-    if (conv_forward_winograd_fused(x, w, bias, slopes, y, s, act, raw, stats)) return;
-    if (conv_forward_winograd(x, w, bias, slopes, y, s, act, raw, stats)) return;
-    conv_forward_dispatch(x, w, bias, slopes, y, s, act, raw, stats);
 }
 
 // ---- weight packs made ahead of their use (bcnn_hip_conv_prepack) -------------------------------------------------
@@ -240,6 +150,56 @@ static const void* prepack_table(PrepackStore& st, int kind, int mode, const voi
     host.assign((const char*)jobs, (const char*)jobs + bytes);
     return st.table_dev[kind][mode];
 }
+
+// ---- which kernel takes a layer --------------------------------------------------------------------------------------
+// Every family is tried in a fixed order and says for itself whether the shape, and the alignment of what it is handed, is
+// its own (conv_paths.h):
+//   forward          window, stem, direct, winograd43 (raw only), winograd_fused, winograd; then, inside
+//                    conv_forward_dispatch, dma, small_c, the register-staged kernel
+//   data gradient    winograd43, winograd_fused, winograd; then, inside conv_backward_data, small_c, dma, register-staged
+//   weight gradient  the rows of kDwFamilies
+// bcnn_hip_conv_prepack below walks the first two for the families that read packed weights (the fused Winograd kernels and
+// dma); the others read the weights as they are or, the three-kernel Winograd, transform them in a kernel of their own.
+// A new family is a line or a row here and its declaration in conv_paths.h.
+static void conv_fwd_any(const float* x, const float* w, const float* bias, const float* slopes, float* y,
+                         const ConvShape& s, int act, int raw, ConvStats* stats = nullptr) {
+    if (stats) stats->splits = 0;
+    static const int window_on = BCNN_EXP_ENV("BCNN_HIP_NO_WINDOW") ? 0 : 1;  // A/B switch: the LDS-free kernels instead
+    if (window_on && conv_forward_window(x, w, bias, slopes, y, s, act, raw)) return;
+    if (window_on && conv_forward_stem(x, w, bias, slopes, y, s, act, raw, stats)) return;
+    if (conv_forward_direct(x, w, bias, slopes, y, s, act, raw)) return;
+    if (raw && conv_forward_winograd43(x, w, y, s, raw, stats)) return;
+    if (conv_forward_winograd_fused(x, w, bias, slopes, y, s, act, raw, stats)) return;
+    if (conv_forward_winograd(x, w, bias, slopes, y, s, act, raw, stats)) return;
+    conv_forward_dispatch(x, w, bias, slopes, y, s, act, raw, stats);
+}
+
+static void conv_dx_any(const float* w, const float* dy, float* dx, const ConvShape& s, DxBnSums* bs) {
+    if (conv_backward_data_winograd43(w, dy, dx, s)) return;
+    if (conv_backward_data_winograd_fused(w, dy, dx, s)) return;
+    if (conv_backward_data_winograd(w, dy, dx, s)) return;
+    conv_backward_data(w, dy, dx, s, bs);
+}
+
+// A/B switches of the experiment build that take a family out: BCNN_HIP_NO_WINDOW, BCNN_HIP_NO_DMA
+enum DwGate { GATE_NONE, GATE_WINDOW, GATE_DMA, GATE_COUNT };
+struct DwFamily {
+    size_t (*workspace_floats)(const ConvShape& s);  // of split partials in the caller's workspace; 0: not its shape
+    bool (*run)(const float* x, const float* dy, float* dw, float* dbias, const ConvShape& s, float* workspace,
+                size_t workspace_floats, bool* bias_done);
+    DwGate gate;
+};
+static const DwFamily kDwFamilies[] = {
+    {conv_dw_window_workspace_floats, conv_backward_weights_window, GATE_WINDOW},
+    {conv_dw_stem_workspace_floats, conv_backward_weights_stem, GATE_WINDOW},
+    {conv_dw_direct_workspace_floats, conv_backward_weights_direct, GATE_NONE},
+    {conv_dw_winograd43_workspace_floats, conv_backward_weights_winograd43, GATE_NONE},
+    {conv_dw_winograd_fused_workspace_floats, conv_backward_weights_winograd_fused, GATE_NONE},
+    {conv_dw_winograd_workspace_floats, conv_backward_weights_winograd, GATE_NONE},
+    {conv_dw_dma_workspace_floats, conv_backward_weights_dma_timed, GATE_DMA},
+    {conv_dw_small_c_workspace_floats, conv_backward_weights_small_c, GATE_DMA},
+    {conv_dw_workspace_floats, conv_backward_weights, GATE_NONE},  // takes every shape
+};
 }  // namespace bcnn_hip
 
 using namespace bcnn_hip;
@@ -265,8 +225,6 @@ void bcnn_hip_conv_prepack(const bcnn_hip_conv_desc* layers, int count, int data
         if (!d.w_d || d.groups <= 0 || d.n <= 0) continue;
         const ConvShape s = make_conv_shape(d.n, d.c, d.h, d.w, d.f, d.k, d.stride, d.pad, d.groups);
         if (s.total_q <= 0 || s.Mg == 0 || s.Cg == 0) continue;
-        // the order bcnn_hip_conv_forward / _backward try their kernels in (conv_fwd_any, conv_backward_impl): the kernels
-        // for few input channels (window, stem, direct, small-C dX) read the weights as they are
         WinoPackJob w1;
         IgemmPackJob i1;
         memset(&w1, 0, sizeof(w1));  // padding bytes too: the tables are compared bytewise against the uploaded ones
@@ -279,8 +237,8 @@ void bcnn_hip_conv_prepack(const bcnn_hip_conv_desc* layers, int count, int data
             wj.push_back(w1);
         } else if (conv_winograd_unfused_takes(s)) {
             continue;  // transforms its weights inside its own first kernel
-        } else if (mode == 1 && !s.pointwise && s.groups == 1 && s.K <= 32 && s.Mg >= 32) {
-            continue;  // conv_backward_data_small_c
+        } else if (mode == 1 && conv_dx_small_c_takes(s)) {
+            continue;
         } else if (dma_pack_plan(s, mode, &i1, &floats)) {
             PrepackEntry* e = prepack_entry(st, d.w_d, PREPACK_IGEMM, mode, floats);
             i1.w = d.w_d; i1.at = e->buf;
@@ -310,22 +268,8 @@ void bcnn_hip_conv_prepack_reset(void) {
 
 size_t bcnn_hip_conv_workspace_size(int n, int c, int h, int w, int f, int k, int stride, int pad, int groups) {
     const ConvShape s = make_conv_shape(n, c, h, w, f, k, stride, pad, groups);
-    size_t m = conv_dw_workspace_floats(s);
-    size_t b = conv_dw_direct_workspace_floats(s);
-    const size_t d = conv_dw_dma_workspace_floats(s), bw = conv_dw_window_workspace_floats(s);
-    const size_t bs = conv_dw_stem_workspace_floats(s);
-    if (bw > b) b = bw;
-    if (bs > b) b = bs;
-    size_t wg = conv_dw_winograd_workspace_floats(s);
-    const size_t wgf = conv_dw_winograd_fused_workspace_floats(s);
-    if (wgf > wg) wg = wgf;
-    const size_t wg43 = conv_dw_winograd43_workspace_floats(s);
-    if (wg43 > wg) wg = wg43;
-    const size_t sc = conv_dw_small_c_workspace_floats(s);
-    if (sc > wg) wg = sc;
-    if (b > m) m = b;
-    if (d > m) m = d;
-    if (wg > m) m = wg;
+    size_t m = 0;
+    for (const DwFamily& fam : kDwFamilies) m = std::max(m, fam.workspace_floats(s));
     return m;
 }
 
@@ -374,8 +318,7 @@ static void conv_forward_impl(const float* x, const float* w, const float* bias,
         // is added where it is visible: the running mean.
         trace_kernel("bnfold:fwd");
         mean_shift = fold_rowconst(fold, w, c, f);
-        KTimer kt(K_CONV_FWD, 2.0 * (double)s.total_q * s.Mg * s.K * s.groups,
-                  4.0 * ((double)s.N * s.C * s.HW + (double)s.F * s.K + (double)s.N * s.F * s.OHOW));
+        KTimer kt(K_CONV_FWD, conv_gemm_flops(s), conv_gemm_bytes(s));
         ConvStats* stp = st.partials ? &st : nullptr;
         if (!conv_forward_dma(x, w, nullptr, nullptr, raw, s, BCNN_HIP_ACT_NONE, /*raw=*/1, stp, &fold)) {
             fprintf(stderr, "[bcnn_hip] conv forward: the LDS-DMA GEMM refused a folded layer\n");
@@ -501,50 +444,31 @@ static void conv_backward_impl(const float* x, const float* w, const float* bias
         HIP_CHECK(hipStreamWaitEvent(side->stream, side->ready, 0));
         set_current_stream(side->stream);
     }
-    bool bias_done;
-    static const int dma_on = BCNN_EXP_ENV("BCNN_HIP_NO_DMA") ? 0 : 1;  // A/B switch for profiling
-    static const int window_on = BCNN_EXP_ENV("BCNN_HIP_NO_WINDOW") ? 0 : 1;
+    bool bias_done = false;
     if (fold.mean) {
         // (the term b (x) sum_q dy of the exact derivative is left out: dy here is the gradient of a batch-norm's input, whose
         // sum over the batch is zero up to rounding -- in the reference too, where it multiplies the same b)
         trace_kernel("bnfold:dw");
-        if (!conv_backward_weights_dma_timed(x, dy, dw, s, workspace, workspace_elems, &fold)) {
+        KTimer kt(K_CONV_DW, conv_gemm_flops(s), conv_gemm_bytes(s));
+        if (!conv_backward_weights_dma(x, dy, dw, s, workspace, workspace_elems, &fold)) {
             fprintf(stderr, "[bcnn_hip] conv backward: the LDS-DMA weight-gradient kernel refused a folded layer\n");
             exit(1);
         }
-        bias_done = false;
-    } else if (window_on && conv_backward_weights_window(x, dy, dw, batch_norm ? nullptr : dbias, s, workspace, workspace_elems))
-        bias_done = true;
-    else if (window_on && conv_backward_weights_stem(x, dy, dw, batch_norm ? nullptr : dbias, s, workspace, workspace_elems))
-        bias_done = true;
-    else if (conv_backward_weights_direct(x, dy, dw, batch_norm ? nullptr : dbias, s, workspace, workspace_elems))
-        bias_done = true;
-    else if (conv_backward_weights_winograd43(x, dy, dw, s, workspace, workspace_elems))
-        bias_done = false;
-    else if (conv_backward_weights_winograd_fused(x, dy, dw, s, workspace, workspace_elems))
-        bias_done = false;
-    else if (conv_backward_weights_winograd(x, dy, dw, s, workspace, workspace_elems))
-        bias_done = false;
-    else if (dma_on && conv_backward_weights_dma_timed(x, dy, dw, s, workspace, workspace_elems))
-        bias_done = false;
-    else if (dma_on && conv_dw_small_c_workspace_floats(s) > 0) {
-        KTimer kt(K_CONV_DW, 2.0 * (double)s.total_q * s.Mg * s.K * s.groups,
-                  4.0 * ((double)s.N * s.C * s.HW + (double)s.F * s.K + (double)s.N * s.F * s.OHOW));
-        conv_backward_weights_small_c(x, dy, dw, s, workspace, workspace_elems);
-        bias_done = false;
+    } else {
+        static const bool gated_off[GATE_COUNT] = {false, BCNN_EXP_ENV("BCNN_HIP_NO_WINDOW") != nullptr,
+                                                   BCNN_EXP_ENV("BCNN_HIP_NO_DMA") != nullptr};
+        for (const DwFamily& fam : kDwFamilies)
+            if (!gated_off[fam.gate] &&
+                fam.run(x, dy, dw, batch_norm ? nullptr : dbias, s, workspace, workspace_elems, &bias_done))
+                break;
     }
-    else
-        bias_done = conv_backward_weights(x, dy, dw, dbias, s, workspace, workspace_elems,
-                                          /*want_bias=*/!batch_norm);
     if (side) {
         HIP_CHECK(hipEventRecord(side->done, side->stream));
         set_current_stream(main_stream);
     }
     if (!batch_norm && !bias_done) bcnn_hip_grad_bias(dbias, dy, n, f, s.OHOW);  // uses the shared reduce scratch
     if (bs) bs->splits = 0;
-    if (dx && !conv_backward_data_winograd43(w, dy, dx, s) && !conv_backward_data_winograd_fused(w, dy, dx, s) &&
-        !conv_backward_data_winograd(w, dy, dx, s))
-        conv_backward_data(w, dy, dx, s, bs);
+    if (dx) conv_dx_any(w, dy, dx, s, bs);
     if (side) {
         if (side_mode == 2) side->pending = true;
         else HIP_CHECK(hipStreamWaitEvent(main_stream, side->done, 0));

@@ -13,7 +13,7 @@
 //       keeps the `+=` onto the momentum carry). One extra all-ones im2col column yields the bias
 //       gradient for free when the padded K tile has room (saves a full re-read of dy).
 //   dX lives in conv_igemm.hip (it is the same gather-GEMM as the forward pass).
-#include "conv_common.h"
+#include "conv_paths.h"
 
 namespace bcnn_hip {
 
@@ -221,18 +221,13 @@ static DwPlan plan_dw(const ConvShape& s, bool want_bias_col) {
 
 size_t conv_dw_workspace_floats(const ConvShape& s) { return plan_dw(s, true).partial_floats; }
 
-// returns true when the bias gradient was produced by the all-ones column
+// the bias gradient comes from an all-ones column when the padded k tile has a free slot for it
 bool conv_backward_weights(const float* x, const float* dy, float* dw, float* dbias, const ConvShape& s,
-                           float* workspace, size_t workspace_floats, bool want_bias) {
-    if (s.total_q == 0 || s.Mg == 0 || s.K == 0) return false;
-    const DwPlan p = plan_dw(s, want_bias && dbias != nullptr);
-    if (workspace == nullptr || workspace_floats < p.partial_floats) {
-        fprintf(stderr, "[bcnn_hip] conv backward: workspace too small (%zu floats given, %zu needed)\n",
-                workspace_floats, p.partial_floats);
-        exit(1);
-    }
-    KTimer kt(K_CONV_DW, 2.0 * (double)s.total_q * s.Mg * s.K * s.groups,
-              4.0 * ((double)s.N * s.C * s.HW + (double)s.F * s.K + (double)s.N * s.F * s.OHOW));
+                           float* workspace, size_t workspace_floats, bool* bias_done) {
+    if (s.total_q == 0 || s.Mg == 0 || s.K == 0) return true;
+    const DwPlan p = plan_dw(s, dbias != nullptr);
+    conv_require_workspace(workspace, workspace_floats, p.partial_floats);
+    KTimer kt(K_CONV_DW, conv_gemm_flops(s), conv_gemm_bytes(s));
     ConvDwArgs a;
     a.x = x; a.dy = dy; a.partials = workspace; a.s = s;
     a.mtiles = p.mtiles; a.ntiles = p.ntiles; a.qsplits = p.qsplits; a.q_per_split = p.q_per_split;
@@ -251,7 +246,8 @@ bool conv_backward_weights(const float* x, const float* dy, float* dw, float* db
         conv_dw_finalize_kernel<16><<<(unsigned)((total + 15) / 16), 256, 0, current_stream()>>>(
             workspace, p.qsplits * 4, s.groups, s.Mg, s.K, p.mtiles * p.TM * 32, p.ntiles * p.TN * 32, p.bias_col, dw, dbias);
     KERNEL_CHECK();
-    return p.bias_col != 0;
+    *bias_done = p.bias_col != 0;
+    return true;
 }
 
 }  // namespace bcnn_hip

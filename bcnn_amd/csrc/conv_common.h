@@ -28,6 +28,20 @@ inline ConvShape make_conv_shape(int n, int c, int h, int w, int f, int k, int s
     return s;
 }
 
+// what the profile (KTimer, common.h) charges a layer that runs as the plain GEMM: its multiply-adds, and every tensor once
+inline double conv_gemm_flops(const ConvShape& s) { return 2.0 * (double)s.total_q * s.Mg * s.K * s.groups; }
+inline double conv_gemm_bytes(const ConvShape& s) {
+    return 4.0 * ((double)s.N * s.C * s.HW + (double)s.F * s.K + (double)s.N * s.F * s.OHOW);
+}
+// a weight-gradient kernel's split partials go to the caller's workspace (bcnn_hip_conv_workspace_size floats)
+inline void conv_require_workspace(const float* workspace, size_t given, size_t need) {
+    if (workspace != nullptr && given >= need) return;
+    fprintf(stderr, "[bcnn_hip] conv backward: workspace too small (%zu floats given, %zu needed)\n", given, need);
+    exit(1);
+}
+// ceil(2^32 / d), the multiplier of the kernels' multiply-high divisions by d (0 for d <= 1); every caller's d is >= 0
+inline unsigned magic_of(int d) { return d > 1 ? (unsigned)((0x100000000ULL + (unsigned)d - 1) / (unsigned)d) : 0u; }
+
 // Batch-norm statistics produced by a convolution kernel's epilogue (conv_igemm_dma.hip):
 // partials[(channel * splits + i) * 2 + {sum, sum of squares}], the layout bn_stats_finalize consumes.
 struct ConvStats {

@@ -15,7 +15,7 @@
 //             are then 32 CONTIGUOUS bytes => two 16-byte loads per operand per 16 output pixels.
 //             A 29th all-ones im2col column yields the bias gradient in the same pass.
 // Reference semantics as in conv_fwd.hip / conv_bwd.hip (bcnn_conv_layer.c:367-587).
-#include "conv_common.h"
+#include "conv_paths.h"
 
 // Cache policy of the result stores: 2 = nt (non-temporal). The output of a small-K layer is a stream far larger
 // than L2 + Infinity Cache; written "nt" it does not displace the input taps there (configs[1]: forward -3 %, and the
@@ -320,8 +320,7 @@ bool conv_forward_direct(const float* x, const float* w, const float* bias, cons
     dim3 grid((unsigned)blocks, (unsigned)s.groups);
     const int ks = (s.K + 1) / 2;
     const int tm = (s.Mg <= 32) ? 1 : 2;
-    KTimer kt(K_CONV_FWD, 2.0 * (double)s.total_q * s.Mg * s.K * s.groups,
-              4.0 * ((double)s.N * s.C * s.HW + (double)s.F * s.K + (double)s.N * s.F * s.OHOW));
+    KTimer kt(K_CONV_FWD, conv_gemm_flops(s), conv_gemm_bytes(s));
     conv_prefetch_input(x, s, y);
     const int actm = (a.act == BCNN_HIP_ACT_NONE) ? 0 : (a.act == BCNN_HIP_ACT_RELU ? 1 : 2);
 #define LAUNCH(TMv, KSv, KZ)                                                                            \
@@ -539,23 +538,16 @@ size_t conv_dw_direct_workspace_floats(const ConvShape& s) {
     return (size_t)blocks * s.groups * tm * 32 * 32;
 }
 
-// returns false when the shape is not covered (caller falls back to the LDS-tiled kernel);
-// when it returns true the bias gradient has been accumulated too (if dbias != NULL).
 bool conv_backward_weights_direct(const float* x, const float* dy, float* dw, float* dbias, const ConvShape& s,
-                                  float* workspace, size_t workspace_floats) {
+                                  float* workspace, size_t workspace_floats, bool* bias_done) {
     if (!dw_direct_ok(s)) return false;
     if ((reinterpret_cast<uintptr_t>(dy) & 15) != 0) return false;
     int nwin, wpb, blocks;
     dw_direct_plan(s, &nwin, &wpb, &blocks);
     const int tm = (s.Mg <= 32) ? 1 : 2;
     const size_t need = (size_t)blocks * s.groups * tm * 32 * 32;
-    if (workspace == nullptr || workspace_floats < need) {
-        fprintf(stderr, "[bcnn_hip] conv backward: workspace too small (%zu floats given, %zu needed)\n",
-                workspace_floats, need);
-        exit(1);
-    }
-    KTimer kt(K_CONV_DW, 2.0 * (double)s.total_q * s.Mg * s.K * s.groups,
-              4.0 * ((double)s.N * s.C * s.HW + (double)s.F * s.K + (double)s.N * s.F * s.OHOW));
+    conv_require_workspace(workspace, workspace_floats, need);
+    KTimer kt(K_CONV_DW, conv_gemm_flops(s), conv_gemm_bytes(s));
     ConvDirectDwArgs a;
     a.x = x; a.dy = dy; a.partials = workspace; a.s = s; a.nwin = nwin; a.win_per_block = wpb;
     a.bias_col = dbias ? 1 : 0;
@@ -564,6 +556,7 @@ bool conv_backward_weights_direct(const float* x, const float* dy, float* dw, fl
     else conv_dw_direct_kernel<2><<<grid, 256, 0, current_stream()>>>(a);
     KERNEL_CHECK();
     conv_dw_direct_finalize(workspace, blocks, s.groups, s.Mg, s.K, tm * 32, a.bias_col, dw, dbias);
+    *bias_done = dbias != nullptr;
     return true;
 }
 

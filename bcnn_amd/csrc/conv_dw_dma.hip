@@ -18,7 +18,7 @@
 // compiler pairs them into ds_read2_b64, which is 2-way conflicted on its 32-bank view; LDS is ~20 % busy so
 // that is harmless, and the alternative -- interleaving the two rows lane by lane so that ds_read2_b32 is
 // conflict-free -- measured 6 % SLOWER because the global side of the DMA then gathers 8-byte pieces).
-#include "conv_common.h"
+#include "conv_paths.h"
 #include "lds_dma.h"
 
 namespace bcnn_hip {
@@ -360,19 +360,13 @@ static DwDmaPlan plan_dw_dma(const ConvShape& s) {
 
 size_t conv_dw_dma_workspace_floats(const ConvShape& s) { return plan_dw_dma(s).partial_floats; }
 
-static unsigned magic_of_u(int d) { return d > 1 ? (unsigned)((0x100000000ULL + (unsigned)d - 1) / (unsigned)d) : 0u; }
 
-// Returns false when the shape is not covered (caller falls back to conv_bwd.hip's kernel).
 // fold: the layer ran on W diag(a) (BnFold, conv_common.h): the weight gradient's columns take the same factors
 bool conv_backward_weights_dma(const float* x, const float* dy, float* dw, const ConvShape& s, float* workspace,
                                size_t workspace_floats, const BnFold* fold) {
     const DwDmaPlan p = plan_dw_dma(s);
     if (!p.ok) return false;
-    if (workspace == nullptr || workspace_floats < p.partial_floats) {
-        fprintf(stderr, "[bcnn_hip] conv backward: workspace too small (%zu floats given, %zu needed)\n",
-                workspace_floats, p.partial_floats);
-        exit(1);
-    }
+    conv_require_workspace(workspace, workspace_floats, p.partial_floats);
     DwDmaArgs a;
     a.rowmode = 0; a.nrows = 0;
     a.x = x; a.dy = dy; a.partials = workspace; a.s = s;
@@ -380,7 +374,7 @@ bool conv_backward_weights_dma(const float* x, const float* dy, float* dw, const
     a.Mpad = p.Mpad; a.Npad = p.Npad; a.kk2 = p.kk2;
     a.x_bytes = (unsigned)((size_t)s.N * s.C * s.HW * 4);
     a.dy_bytes = (unsigned)((size_t)s.N * s.F * s.OHOW * 4);
-    a.ow_magic = magic_of_u(s.OW);
+    a.ow_magic = magic_of(s.OW);
     a.b_row_stride = s.pointwise ? s.OHOW : s.HW;
     dim3 grid((unsigned)(p.mtiles * p.ntiles * p.kk2 * p.qsplits), (unsigned)s.groups);
     const unsigned threads = (unsigned)kDwTiles[p.cfg].threads;
@@ -410,9 +404,14 @@ bool conv_backward_weights_dma(const float* x, const float* dy, float* dw, const
     return true;
 }
 
+bool conv_backward_weights_dma_timed(const float* x, const float* dy, float* dw, float*, const ConvShape& s, float* workspace,
+                                     size_t workspace_floats, bool*) {
+    if (!plan_dw_dma(s).ok) return false;
+    KTimer kt(K_CONV_DW, conv_gemm_flops(s), conv_gemm_bytes(s));
+    return conv_backward_weights_dma(x, dy, dw, s, workspace, workspace_floats, nullptr);
+}
+
 // ---- few input channels (the RGB stem): dW[f][(c, kr, kc)] as ONE GEMM over the zero-padded input ----------
-bool conv_small_c_applicable(const ConvShape& s);                                                    // conv_igemm_dma.hip
-float* conv_small_c_padded_input(const float* x, const ConvShape& s, size_t extra_floats, float** extra, int for_dw);
 
 static DwDmaPlan plan_dw_small_c(const ConvShape& s) {
     DwDmaPlan p;
@@ -439,15 +438,12 @@ static DwDmaPlan plan_dw_small_c(const ConvShape& s) {
 
 size_t conv_dw_small_c_workspace_floats(const ConvShape& s) { return plan_dw_small_c(s).partial_floats; }
 
-bool conv_backward_weights_small_c(const float* x, const float* dy, float* dw, const ConvShape& s, float* workspace,
-                                   size_t workspace_floats) {
+bool conv_backward_weights_small_c(const float* x, const float* dy, float* dw, float*, const ConvShape& s, float* workspace,
+                                   size_t workspace_floats, bool*) {
     const DwDmaPlan p = plan_dw_small_c(s);
     if (!p.ok) return false;
-    if (workspace == nullptr || workspace_floats < p.partial_floats) {
-        fprintf(stderr, "[bcnn_hip] conv backward: workspace too small (%zu floats given, %zu needed)\n", workspace_floats,
-                p.partial_floats);
-        exit(1);
-    }
+    conv_require_workspace(workspace, workspace_floats, p.partial_floats);
+    KTimer kt(K_CONV_DW, conv_gemm_flops(s), conv_gemm_bytes(s));
     const int Hp = s.H + 2 * s.pad, Wp = s.W + 2 * s.pad;
     float* xp = conv_small_c_padded_input(x, s, 0, nullptr, /*for_dw=*/1);
     const ConvShape sp = make_conv_shape(s.N, s.C, Hp, Wp, s.F, s.ksz, s.stride, 0, 1);
@@ -457,10 +453,10 @@ bool conv_backward_weights_small_c(const float* x, const float* dy, float* dw, c
     a.Mpad = p.Mpad; a.Npad = p.Npad; a.kk2 = 1;
     a.x_bytes = (unsigned)((size_t)s.N * s.C * Hp * Wp * 4);
     a.dy_bytes = (unsigned)((size_t)s.N * s.F * s.OHOW * 4);
-    a.ow_magic = magic_of_u(sp.OW);
+    a.ow_magic = magic_of(sp.OW);
     a.b_row_stride = 0;
     a.rowmode = 1; a.nrows = s.K; a.row_kk = s.ksz * s.ksz; a.row_ks = s.ksz; a.row_plane = Hp * Wp; a.row_pitch = Wp;
-    a.row_kk_magic = magic_of_u(a.row_kk); a.row_ks_magic = magic_of_u(a.row_ks);
+    a.row_kk_magic = magic_of(a.row_kk); a.row_ks_magic = magic_of(a.row_ks);
     dim3 grid((unsigned)(p.mtiles * p.ntiles * p.qsplits), 1u);
     conv_dw_dma_kernel<2, 2, 1, 1><<<grid, (unsigned)kDwTiles[0].threads, 0, current_stream()>>>(a);
     KERNEL_CHECK();

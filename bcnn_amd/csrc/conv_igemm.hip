@@ -22,7 +22,7 @@
 //     so a gathered element costs: table read, bit test, add, clamp -- and an UNCONDITIONAL load;
 //   * table entries {A offset, B offset, tap index} are produced with multiply-high "magic" division;
 //   * all offsets are 32-bit against wave-uniform bases.
-#include "conv_common.h"
+#include "conv_paths.h"
 
 namespace bcnn_hip {
 
@@ -291,7 +291,6 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const IgemmArgs a) {
 }
 
 // ---- host side ------------------------------------------------------------------------------------------
-static unsigned magic_of(int d) { return d > 1 ? (unsigned)((0x100000000ULL + (unsigned)d - 1) / (unsigned)d) : 0u; }
 
 template <int WM, int WN, int TM, int TN, int BK>
 static void launch_igemm(IgemmArgs& a, long long max_cols) {
@@ -310,12 +309,6 @@ static void dispatch_igemm(IgemmArgs& a, long long max_cols) {
     else launch_igemm<2, 2, 2, 2, 16>(a, max_cols);                  // 128 x 128
 }
 
-bool conv_forward_dma(const float* x, const float* w, const float* bias, const float* slopes, float* y,
-                      const ConvShape& s, int act, int raw, ConvStats* stats, const BnFold* fold = nullptr);        // conv_igemm_dma.hip
-bool conv_backward_data_dma(const float* w, const float* dy, float* dx, const ConvShape& s, DxBnSums* bs);
-bool conv_forward_small_c(const float* x, const float* w, const float* bias, const float* slopes, float* y,
-                          const ConvShape& s, int act, int raw, ConvStats* stats);   // conv_igemm_dma.hip
-
 static bool dma_enabled() {
     static const int on = BCNN_EXP_ENV("BCNN_HIP_NO_DMA") ? 0 : 1;  // A/B switch for profiling
     return on != 0;
@@ -330,8 +323,7 @@ void conv_forward_dispatch(const float* x, const float* w, const float* bias, co
         fprintf(stderr, "[bcnn_hip] conv forward: kernel size %d > 7 is not supported\n", s.ksz);
         exit(1);
     }
-    KTimer kt(K_CONV_FWD, 2.0 * (double)s.total_q * s.Mg * s.K * s.groups,
-              4.0 * ((double)s.N * s.C * s.HW + (double)s.F * s.K + (double)s.N * s.F * s.OHOW));
+    KTimer kt(K_CONV_FWD, conv_gemm_flops(s), conv_gemm_bytes(s));
     if (dma_enabled() && conv_forward_dma(x, w, bias, slopes, y, s, act, raw, stats)) return;
     if (dma_enabled() && conv_forward_small_c(x, w, bias, slopes, y, s, act, raw, stats)) return;
     IgemmArgs a;
@@ -392,10 +384,13 @@ __global__ __launch_bounds__(256) void col2im_batch_kernel(const float* __restri
     }
 }
 
-static bool conv_backward_data_small_c(const float* w, const float* dy, float* dx, const ConvShape& s) {
+bool conv_dx_small_c_takes(const ConvShape& s) {
     static const bool off = BCNN_EXP_ENV("BCNN_HIP_NO_SMALLC_DX") != nullptr;
-    if (off || s.pointwise || s.groups != 1 || s.K > 32 || s.Mg < 32) return false;
-    if ((long long)s.N * s.C * s.HW >= (1LL << 31)) return false;
+    return !off && !s.pointwise && s.groups == 1 && s.K <= 32 && s.Mg >= 32 && (long long)s.N * s.C * s.HW < (1LL << 31);
+}
+
+static bool conv_backward_data_small_c(const float* w, const float* dy, float* dx, const ConvShape& s) {
+    if (!conv_dx_small_c_takes(s)) return false;
     const size_t per_image = (size_t)s.K * s.OHOW;                      // col floats per image
     int chunk = (int)(((size_t)96 << 20) / (per_image * sizeof(float)));  // <= 96 MB of col in flight
     if (chunk < 1) chunk = 1;
@@ -429,8 +424,7 @@ void conv_backward_data(const float* w, const float* dy, float* dx, const ConvSh
         fprintf(stderr, "[bcnn_hip] conv backward: kernel size %d > 7 is not supported\n", s.ksz);
         exit(1);
     }
-    KTimer kt(K_CONV_DX, 2.0 * (double)s.total_q * s.Mg * s.K * s.groups,
-              4.0 * ((double)s.N * s.C * s.HW + (double)s.F * s.K + (double)s.N * s.F * s.OHOW));
+    KTimer kt(K_CONV_DX, conv_gemm_flops(s), conv_gemm_bytes(s));
     if (conv_backward_data_small_c(w, dy, dx, s)) return;
     if (dma_enabled() && conv_backward_data_dma(w, dy, dx, s, bs)) return;
     IgemmArgs a;

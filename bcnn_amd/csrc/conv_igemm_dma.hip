@@ -20,7 +20,7 @@
 // padding, so ragged M / J need no predicates (a zero A row cancels whatever finite B row was fetched).
 #include <type_traits>
 
-#include "conv_common.h"
+#include "conv_paths.h"
 #include "lds_dma.h"
 
 // ---- compile-time tuning knobs (defaults = what is measured best; tools/exp/build_variant.sh DEFS=-D... builds
@@ -693,7 +693,6 @@ __global__ __launch_bounds__(256) void conv_pad_input_kernel(const float* __rest
     }
 }
 
-static unsigned magic_u32(int d) { return d > 1 ? (unsigned)((0x100000000ULL + (unsigned)d - 1) / (unsigned)d) : 0u; }
 
 bool conv_small_c_applicable(const ConvShape& s) {
     if (s.groups != 1 || s.pointwise || s.ksz > 7 || s.Cg >= 8 || s.Mg <= 32) return false;
@@ -735,7 +734,7 @@ bool conv_forward_small_c(const float* x, const float* w, const float* bias, con
     a.b_bytes = (unsigned)((size_t)s.N * s.C * Hp * Wp * 4);
     a.b_major_stride = 0;
     a.rowmode = 1; a.row_kk = s.ksz * s.ksz; a.row_ks = s.ksz; a.row_plane = Hp * Wp; a.row_pitch = Wp;
-    a.row_kk_magic = magic_u32(a.row_kk); a.row_ks_magic = magic_u32(a.row_ks);
+    a.row_kk_magic = magic_of(a.row_kk); a.row_ks_magic = magic_of(a.row_ks);
     a.nclass = 1;
     DmaClass& ci = a.cls[0];
     ci.ih0 = 0; ci.iw0 = 0; ci.Hc = sp.OH; ci.Wc = sp.OW; ci.ntaps = 1; ci.tap0 = 0; ci.nkx = 1; ci.sgn = 1;

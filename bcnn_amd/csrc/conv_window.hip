@@ -16,7 +16,7 @@
 //      dW: see the second half of the file -- dy reaches LDS by LDS-DMA, one filter-plane row per instruction.
 // The weights live in MFMA A-operand registers (forward) for the life of the workgroup. Reference semantics:
 // bcnn_forward_conv_layer_cpu / bcnn_backward_conv_layer_cpu, bcnn_conv_layer.c:367-587 (im2col + gemm, add_bias quirk).
-#include "conv_common.h"
+#include "conv_paths.h"
 #include "lds_dma.h"
 
 #include <mutex>
@@ -83,8 +83,6 @@ struct WinSteps {
         if (CG & 1) st[n++] = WinStep{CG - 1, 2, 2, WD_NONE, 0};                        // the odd one out
     }
 };
-
-void conv_prefetch_input(const float* x, const ConvShape& s, float* sink);  // conv_direct.hip
 
 struct ConvWindowFwdArgs {
     const float* x;
@@ -389,8 +387,7 @@ bool conv_forward_window(const float* x, const float* w, const float* bias, cons
     const int tm = (s.Mg <= 32) ? 1 : 2;
     const int actm = (a.act == BCNN_HIP_ACT_NONE) ? 0 : (a.act == BCNN_HIP_ACT_RELU ? 1 : 2);
     const int pitch = window_pitch(s);
-    KTimer kt(K_CONV_FWD, 2.0 * (double)s.total_q * s.Mg * s.K * s.groups,
-              4.0 * ((double)s.N * s.C * s.HW + (double)s.F * s.K + (double)s.N * s.F * s.OHOW));
+    KTimer kt(K_CONV_FWD, conv_gemm_flops(s), conv_gemm_bytes(s));
     // One workgroup per CU (fewer when there are fewer strips); strips beyond the first round are handed out by a device counter.
     const int nunits = s.N * a.strips;
     a.sched = window_sched_slot(s.groups);
@@ -679,8 +676,7 @@ bool conv_forward_stem(const float* x, const float* w, const float* bias, const 
     a.stats = want_stats ? stats->partials : nullptr;
     const dim3 grid((unsigned)(s.N * a.strips), (unsigned)s.groups);
     const int actm = (a.act == BCNN_HIP_ACT_NONE) ? 0 : (a.act == BCNN_HIP_ACT_RELU ? 1 : 2);
-    KTimer kt(K_CONV_FWD, 2.0 * (double)s.total_q * s.Mg * s.K * s.groups,
-              4.0 * ((double)s.N * s.C * s.HW + (double)s.F * s.K + (double)s.N * s.F * s.OHOW));
+    KTimer kt(K_CONV_FWD, conv_gemm_flops(s), conv_gemm_bytes(s));
 #define SLAUNCH3(CGv, Av, STv) conv_fwd_stem_kernel<CGv, R, 232, Av, STv><<<grid, 256, 0, current_stream()>>>(a)
 #define SLAUNCH2(CGv) do { if (want_stats) SLAUNCH3(CGv, 0, true); else if (actm == 0) SLAUNCH3(CGv, 0, false); \
                            else if (actm == 1) SLAUNCH3(CGv, 1, false); else SLAUNCH3(CGv, 2, false); } while (0)
@@ -1064,21 +1060,15 @@ size_t conv_dw_stem_workspace_floats(const ConvShape& s) {
     return (size_t)blocks * s.groups * 64 * kStemTapCols;
 }
 
-// false: shape not covered. true: dW accumulated, and the bias gradient too when dbias != NULL.
 bool conv_backward_weights_stem(const float* x, const float* dy, float* dw, float* dbias, const ConvShape& s, float* workspace,
-                                size_t workspace_floats) {
+                                size_t workspace_floats, bool* bias_done) {
     if (!dw_stem_ok(s)) return false;
     ConvStemDwArgs a;
     int blocks;
     dw_stem_plan(s, &a.rows_per_block, &blocks);
     const size_t need = (size_t)blocks * s.groups * 64 * kStemTapCols;
-    if (workspace == nullptr || workspace_floats < need) {
-        fprintf(stderr, "[bcnn_hip] conv backward: workspace too small (%zu floats given, %zu needed)\n", workspace_floats,
-                need);
-        exit(1);
-    }
-    KTimer kt(K_CONV_DW, 2.0 * (double)s.total_q * s.Mg * s.K * s.groups,
-              4.0 * ((double)s.N * s.C * s.HW + (double)s.F * s.K + (double)s.N * s.F * s.OHOW));
+    conv_require_workspace(workspace, workspace_floats, need);
+    KTimer kt(K_CONV_DW, conv_gemm_flops(s), conv_gemm_bytes(s));
     a.x = x; a.dy = dy; a.partials = workspace; a.s = s;
     a.total_rows = s.N * s.OH;
     a.bias_col = dbias ? 1 : 0;
@@ -1092,12 +1082,9 @@ bool conv_backward_weights_stem(const float* x, const float* dy, float* dw, floa
     conv_dw_stem_finalize_kernel<<<ceil_div(total, 16), 256, 0, current_stream()>>>(workspace, blocks, s.groups, s.Mg, s.K,
                                                                                     a.bias_col, dw, dbias);
     KERNEL_CHECK();
+    *bias_done = dbias != nullptr;
     return true;
 }
-
-// conv_direct.hip
-void conv_dw_direct_finalize(const float* partials, int nparts, int groups, int Mg, int K, int MP, int bias_col, float* dw,
-                             float* dbias);
 
 static bool dw_window_ok(const ConvShape& s) { return window_ok(s) && (s.OW % 8) == 0; }
 
@@ -1125,22 +1112,16 @@ size_t conv_dw_window_workspace_floats(const ConvShape& s) {
     return (size_t)blocks * s.groups * tm * 32 * 32;
 }
 
-// false: shape not covered. true: dW accumulated, and the bias gradient too when dbias != NULL.
 bool conv_backward_weights_window(const float* x, const float* dy, float* dw, float* dbias, const ConvShape& s,
-                                  float* workspace, size_t workspace_floats) {
+                                  float* workspace, size_t workspace_floats, bool* bias_done) {
     if (!dw_window_ok(s)) return false;
     ConvRowsDwArgs ra;
     int rblocks;
     dw_rows_plan(s, &ra.rows_per_block, &rblocks);
     const int tm = (s.Mg <= 32) ? 1 : 2;
     const size_t need = (size_t)rblocks * s.groups * tm * 32 * 32;
-    if (workspace == nullptr || workspace_floats < need) {
-        fprintf(stderr, "[bcnn_hip] conv backward: workspace too small (%zu floats given, %zu needed)\n", workspace_floats,
-                need);
-        exit(1);
-    }
-    KTimer kt(K_CONV_DW, 2.0 * (double)s.total_q * s.Mg * s.K * s.groups,
-              4.0 * ((double)s.N * s.C * s.HW + (double)s.F * s.K + (double)s.N * s.F * s.OHOW));
+    conv_require_workspace(workspace, workspace_floats, need);
+    KTimer kt(K_CONV_DW, conv_gemm_flops(s), conv_gemm_bytes(s));
     ra.x = x; ra.dy = dy; ra.partials = workspace; ra.s = s;
     ra.total_rows = s.N * s.OH;
     ra.bias_col = dbias ? 1 : 0;
@@ -1163,6 +1144,7 @@ bool conv_backward_weights_window(const float* x, const float* dy, float* dw, fl
 #undef RLAUNCH2
     KERNEL_CHECK();
     conv_dw_direct_finalize(workspace, rblocks, s.groups, s.Mg, s.K, tm * 32, ra.bias_col, dw, dbias);
+    *bias_done = dbias != nullptr;
     return true;
 }
 

@@ -14,7 +14,7 @@
 //
 // Reference: bcnn_forward_conv_layer_cpu's Winograd branch (bcnn_conv_layer.c:388-436; F(2x2,3x3) on bcnn_mat.c:1403-2138)
 // is the precedent for computing these layers in a transformed domain; the transform matrices are Lavin & Gray's F(4x4,3x3).
-#include "conv_common.h"
+#include "conv_paths.h"
 #include "lds_dma.h"
 #include "wino43_math.h"
 #include "wino43_pack.h"
@@ -33,12 +33,8 @@ constexpr int W4_STAGE = 2 * W4_OP;        // U then V: 73,728 bytes
 #include "wino43_first_form_exp.h"  // the round-5 kernel: planes that are not whole tiles, A/B partner
 #endif
 
-// conv_winograd43b.hip: the second form of the kernel (16 x 16 MFMA tiles, output transform in registers), whole-tile planes
-void wino43b_run(const float* src, const float* w, float* dst, const ConvShape& s, int dx_mode, ConvStats* stats);
-int wino43b_stats_slots(const ConvShape& s);
-void wino43b_pack_dims(int J, int M, int* Jpad, int* Mpad);
-// which form takes a wanted layer: the second one wherever the planes are whole tiles (experiment build: BCNN_HIP_W43_FORM=1
-// keeps everything on the first form)
+// which form takes a wanted layer: the second one (conv_winograd43b.hip: 16 x 16 MFMA tiles, output transform in registers)
+// wherever the planes are whole tiles (experiment build: BCNN_HIP_W43_FORM=1 keeps everything on the first form)
 static bool wino43_second_form(const ConvShape& s) {
     static const int forced_first = BCNN_EXP_ENV("BCNN_HIP_W43_FORM") ? (BCNN_EXP_ENV("BCNN_HIP_W43_FORM")[0] == '1') : 0;
     return !forced_first && (s.H & 3) == 0 && (s.W & 3) == 0;
@@ -109,14 +105,11 @@ bool wino43_pack_plan(const ConvShape& s, int dx_mode, WinoPackJob* job, size_t*
 static double w43_flops(const ConvShape& s) { return 2.0 * 36.0 * ((double)s.N * ((s.H + 3) / 4) * ((s.W + 3) / 4)) * s.C * s.F; }
 // the same without the tiles' overhang on planes that are not whole tiles (7 x 7: four tiles cover 8 x 8)
 static double w43_useful_flops(const ConvShape& s) { return 2.0 * 36.0 * ((double)s.N * s.H * s.W / 16.0) * s.C * s.F; }
-static double w43_bytes(const ConvShape& s) {
-    return 4.0 * ((double)s.N * s.C * s.HW + (double)s.F * s.K + (double)s.N * s.F * s.OHOW);
-}
 
 // raw output only (a fused batch-norm behind it, or a caller that adds nothing): the other forms stay on F(2x2, 3x3)
 bool conv_forward_winograd43(const float* x, const float* w, float* y, const ConvShape& s, int raw, ConvStats* stats) {
     if (!raw || !wino43_wanted(s, s.C, s.F) || !wino43_usable(x, y, s, 0, stats)) return false;
-    KTimer kt(K_CONV_FWD_WINO43, w43_flops(s), w43_bytes(s), w43_useful_flops(s));
+    KTimer kt(K_CONV_FWD_WINO43, w43_flops(s), conv_gemm_bytes(s), w43_useful_flops(s));
     if (wino43_second_form(s)) wino43b_run(x, w, y, s, 0, stats);
 #ifdef BCNN_HIP_EXPERIMENT
     else wino43_run(x, w, y, s, 0, stats);
@@ -126,7 +119,7 @@ bool conv_forward_winograd43(const float* x, const float* w, float* y, const Con
 
 bool conv_backward_data_winograd43(const float* w, const float* dy, float* dx, const ConvShape& s) {
     if (!wino43_wanted(s, s.F, s.C) || !wino43_usable(dy, dx, s, 1, nullptr)) return false;
-    KTimer kt(K_CONV_DX_WINO43, w43_flops(s), w43_bytes(s), w43_useful_flops(s));
+    KTimer kt(K_CONV_DX_WINO43, w43_flops(s), conv_gemm_bytes(s), w43_useful_flops(s));
     if (wino43_second_form(s)) wino43b_run(dy, w, dx, s, 1, nullptr);
 #ifdef BCNN_HIP_EXPERIMENT
     else wino43_run(dy, w, dx, s, 1, nullptr);

@@ -26,7 +26,7 @@
 // fragment reads conflict-free (a ds_read_b128 group holds rows k and k + 1 of a pair: they must share their rotation).
 // The partial dU of a workgroup leaves as G^T dU G (9 instead of 36 values per channel pair); wino43_dw_finalize_kernel adds
 // the splits in a fixed order onto dw (beta = 1: the momentum carry of the reference, bcnn_conv_layer.c:533-560).
-#include "conv_common.h"
+#include "conv_paths.h"
 #include "lds_dma.h"
 #include "wino43_math.h"
 #include "wino43b_mma.h"
@@ -349,19 +349,13 @@ static Wino43DwPlan wino43_dw_plan(const ConvShape& s, int cus = kCUs) {
 
 size_t conv_dw_winograd43_workspace_floats(const ConvShape& s) { return wino43_dw_plan(s).partial_floats; }
 
-static unsigned magic_of(unsigned d) { return d <= 1 ? 0u : (unsigned)((0x100000000ull + d - 1) / d); }
-
-bool conv_backward_weights_winograd43(const float* x, const float* dy, float* dw, const ConvShape& s, float* workspace,
-                                      size_t workspace_floats) {
+bool conv_backward_weights_winograd43(const float* x, const float* dy, float* dw, float*, const ConvShape& s, float* workspace,
+                                      size_t workspace_floats, bool*) {
     const bool yield_cus = conv_side_stream_deferred() && wino43_dw_plan(s).ok;  // (the workspace was sized for the full plan)
     const Wino43DwPlan p = wino43_dw_plan(s, yield_cus ? kCUs * 3 / 4 : kCUs);
     if (!p.ok) return false;
     if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) return false;  // 16-byte rows
-    if (workspace == nullptr || workspace_floats < p.partial_floats) {
-        fprintf(stderr, "[bcnn_hip] conv backward: workspace too small (%zu floats given, %zu needed)\n", workspace_floats,
-                p.partial_floats);
-        exit(1);
-    }
+    conv_require_workspace(workspace, workspace_floats, p.partial_floats);
     const double tiles = (double)s.N * (s.H / 4) * (s.W / 4);
     KTimer kt(K_CONV_DW_WINO43, 2.0 * 36.0 * tiles * s.C * s.F, 4.0 * ((double)s.N * s.HW * (s.C + s.F) + 9.0 * s.C * s.F));
     Wino43DwArgs a;
@@ -371,8 +365,8 @@ bool conv_backward_weights_winograd43(const float* x, const float* dy, float* dw
     a.fblocks = p.fblocks; a.cblocks = p.cblocks; a.splits = p.splits;
     a.x_bytes = (unsigned)((size_t)s.N * s.C * s.HW * 4);
     a.dy_bytes = (unsigned)((size_t)s.N * s.F * s.HW * 4);
-    a.magic_img = magic_of((unsigned)(a.TH * a.TW));
-    a.magic_tw = magic_of((unsigned)a.TW);
+    a.magic_img = magic_of(a.TH * a.TW);
+    a.magic_tw = magic_of(a.TW);
     const int nob = p.fblocks * p.cblocks;
     trace_kernel("wino43_dw_kernel");
     wino43_dw_kernel<<<(unsigned)(p.splits * nob), 64 * WB_NW, 0, current_stream()>>>(a);

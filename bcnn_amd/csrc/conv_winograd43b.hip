@@ -32,7 +32,7 @@
 //
 // Reference: bcnn_forward_conv_layer_cpu / bcnn_backward_conv_layer_cpu (bcnn_conv_layer.c:438-481, 533-581) are what is
 // computed; the reference's own transformed-domain path (bcnn_conv_layer.c:388-436 on bcnn_mat.c:1403-2138) is the precedent.
-#include "conv_common.h"
+#include "conv_paths.h"
 #include "lds_dma.h"
 #include "wino43_math.h"
 #include "wino43_pack.h"

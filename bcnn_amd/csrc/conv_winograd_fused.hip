@@ -21,7 +21,7 @@
 //
 // Reference: bcnn_forward_conv_layer_cpu's Winograd branch (bcnn_conv_layer.c:388-436) on bcnn_mat.c:1403-2138
 // (PREDICT mode there; here also TRAIN forward / dX, inside the 1e-4 parity bar).
-#include "conv_common.h"
+#include "conv_paths.h"
 #include "lds_dma.h"
 #include "wino43_pack.h"
 
@@ -654,14 +654,11 @@ static double wf_flops(const ConvShape& s) {
 }
 // the same without the tiles' overhang on odd-sized planes (7 x 7: 16 tiles cover 8 x 8)
 static double wf_useful_flops(const ConvShape& s) { return 2.0 * 16.0 * ((double)s.N * s.H * s.W / 4.0) * s.C * s.F; }
-static double wf_bytes(const ConvShape& s) {
-    return 4.0 * ((double)s.N * s.C * s.HW + (double)s.F * s.K + (double)s.N * s.F * s.OHOW);
-}
 
 bool conv_forward_winograd_fused(const float* x, const float* w, const float* bias, const float* slopes, float* y,
                                  const ConvShape& s, int act, int raw, ConvStats* stats) {
     if (!wino_fused_wanted(s, s.C, s.F)) return false;
-    KTimer kt(K_CONV_FWD_WINO, wf_flops(s), wf_bytes(s), wf_useful_flops(s));
+    KTimer kt(K_CONV_FWD_WINO, wf_flops(s), conv_gemm_bytes(s), wf_useful_flops(s));
     if (stats && !raw) stats->splits = 0;
     wino_fused_run(x, w, y, s, 0, bias, slopes, raw ? BCNN_HIP_ACT_NONE : act, raw ? 0 : (bias != nullptr), raw ? stats : nullptr);
     return true;
@@ -669,7 +666,7 @@ bool conv_forward_winograd_fused(const float* x, const float* w, const float* bi
 
 bool conv_backward_data_winograd_fused(const float* w, const float* dy, float* dx, const ConvShape& s) {
     if (!wino_fused_wanted(s, s.F, s.C)) return false;
-    KTimer kt(K_CONV_DX_WINO, wf_flops(s), wf_bytes(s), wf_useful_flops(s));
+    KTimer kt(K_CONV_DX_WINO, wf_flops(s), conv_gemm_bytes(s), wf_useful_flops(s));
     wino_fused_run(dy, w, dx, s, 1, nullptr, nullptr, BCNN_HIP_ACT_NONE, 0, nullptr);
     return true;
 }
@@ -1036,8 +1033,8 @@ static WinoDwPlan wino_dw_fused_plan(const ConvShape& s, int cus = kCUs) {
 
 size_t conv_dw_winograd_fused_workspace_floats(const ConvShape& s) { return wino_dw_fused_plan(s).partial_floats; }
 
-bool conv_backward_weights_winograd_fused(const float* x, const float* dy, float* dw, const ConvShape& s, float* workspace,
-                                          size_t workspace_floats) {
+bool conv_backward_weights_winograd_fused(const float* x, const float* dy, float* dw, float*, const ConvShape& s,
+                                          float* workspace, size_t workspace_floats, bool*) {
     // (the workspace was sized for the full plan.) Only on planes from 28 x 28 up: there the chain's sweeps are long enough to need
     // the CUs; with the 56 x 56 / 28 x 28 layers on conv_winograd43_dw.hip what is left here in ResNet-18 are the 14 x 14 / 7 x 7
     // layers, which do better on the whole chip (-0.05 ms per step)
@@ -1045,12 +1042,8 @@ bool conv_backward_weights_winograd_fused(const float* x, const float* dy, float
     const WinoDwPlan p = wino_dw_fused_plan(s, yield_cus ? kCUs * 3 / 4 : kCUs);
     if (!p.ok) return false;
     if (reinterpret_cast<uintptr_t>(workspace) & 15) return false;  // the finalize kernel reads the slabs 16 bytes at a time
-    if (workspace == nullptr || workspace_floats < p.partial_floats) {
-        fprintf(stderr, "[bcnn_hip] conv backward: workspace too small (%zu floats given, %zu needed)\n", workspace_floats,
-                p.partial_floats);
-        exit(1);
-    }
-    KTimer kt(K_CONV_DW_WINO, wf_flops(s), wf_bytes(s), wf_useful_flops(s));
+    conv_require_workspace(workspace, workspace_floats, p.partial_floats);
+    KTimer kt(K_CONV_DW_WINO, wf_flops(s), conv_gemm_bytes(s), wf_useful_flops(s));
     WinoDwArgs a;
     a.x = x; a.dy = dy; a.partials = workspace;
     a.N = s.N; a.C = s.C; a.F = s.F; a.H = s.H; a.W = s.W; a.TH = (s.H + 1) / 2; a.TW = (s.W + 1) / 2;

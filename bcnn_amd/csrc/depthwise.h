@@ -35,6 +35,8 @@ struct DwBnIn {
 bool depthwise_lds_ok(const DwShape& s);
 size_t depthwise_lds_stats_floats(const DwShape& s);    // capacity a ConvStats needs for depthwise_forward_lds
 size_t depthwise_lds_partial_floats(const DwShape& s);  // scratch of depthwise_backward_lds
+// dw, dbias += the `splits` partials of a backward kernel (depthwise_march.hip writes the same layout)
+void dwl_finalize_launch(const float* partials, int splits, int C, float* dw, float* dbias, hipStream_t st);
 // y = act(dwconv(x) + bias); with `stats` also the per-channel sum / sum of squares partials of y
 bool depthwise_forward_lds(const float* x, const float* w, const float* bias, float* y, const DwShape& s, int act,
                            ConvStats* stats, const DwBnIn* in = nullptr);

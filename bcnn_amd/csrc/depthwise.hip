@@ -11,8 +11,6 @@
 
 namespace bcnn_hip {
 
-void activation_backward_grad_bias(const float* y, float* dy, float* dbias, int n, int c, int hw, int act);  // blas1.hip
-
 
 __global__ __launch_bounds__(256) void dw_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                      const float* __restrict__ bias, float* __restrict__ y,

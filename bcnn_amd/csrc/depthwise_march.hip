@@ -35,8 +35,6 @@
 
 namespace bcnn_hip {
 
-void dwl_finalize_launch(const float* partials, int splits, int C, float* dw, float* dbias, hipStream_t st);  // depthwise_lds.hip
-
 namespace {
 
 #ifndef DWM_BWD_WAVES

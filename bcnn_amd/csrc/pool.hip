@@ -4,8 +4,8 @@
 // src/layers/bcnn_avgpool_layer.c:82-99, 109-125.
 #include <cfloat>
 
+#include "batchnorm.h"
 #include "bn_math.h"
-#include "common.h"
 
 namespace bcnn_hip {
 
@@ -408,12 +408,6 @@ __global__ __launch_bounds__(256) void avgpool_bwd_kernel(const float* __restric
         dx[i] += dy[p] / (float)HW;  // dst.grad / (h*w), int divisor promoted (bcnn_avgpool_layer.c:118-120)
     }
 }
-
-// batchnorm.hip: sums + finalize of a batch-norm backward over (dy, x) with the forward output recomputed from x
-void batchnorm_backward_sums(const float* dy, const float* y, int act, const float* scales, float* dscales, float* dbias,
-                             const float* saved_mean, const float* saved_var, float* dmean, float* dvar,
-                             const float* workspace, int n, int c, int hw, const float* fwd_bias, const float* res,
-                             unsigned res_count, float4* consts = nullptr, float consts_fM = 0.f);
 
 }  // namespace bcnn_hip
 
