@@ -1,5 +1,6 @@
-// depthwise.h -- shapes and entry points shared by the depthwise-convolution kernels (depthwise.hip: register-window
-// kernels for any shape; depthwise_lds.hip: the LDS-staged 3x3 kernels).
+// depthwise.h -- shapes, call descriptions and kernel families of the depthwise convolution. depthwise.hip holds the C-ABI, the
+// two ordered family tables and the kernels for any shape; depthwise_march.hip and depthwise_lds.hip hold one fused 3x3
+// family each and know nothing of each other.
 #pragma once
 #include "conv_common.h"
 
@@ -8,6 +9,10 @@ namespace bcnn_hip {
 struct DwShape {
     int N, C, H, W, OH, OW, ksz, stride, pad;
 };
+inline DwShape dw_shape(int n, int c, int h, int w, int k, int stride, int pad) {
+    const int st = stride < 1 ? 1 : stride;  // a size query may carry anything; no family takes such a shape
+    return DwShape{n, c, h, w, (h + 2 * pad - k) / st + 1, (w + 2 * pad - k) / st + 1, k, stride, pad};
+}
 
 // Batch-norm coefficients of the stand-alone batch-norm node that consumes a depthwise layer's output, for the backward
 // kernel that applies bcnn_batchnorm_layer.c:292-296 to the incoming gradient on the fly (device pointers, [C] each).
@@ -30,35 +35,85 @@ struct DwBnIn {
     const float* bias;
     int act;
 };
+// what a kernel that normalises its input on load can apply
+inline bool dw_in_ok(const DwBnIn* in) {
+    return !in || (in->mean && act_is_cheap(in->act) && in->act != BCNN_HIP_ACT_PRELU);
+}
 
-// depthwise_lds.hip. All return false (and launch nothing) when the shape is not theirs.
-bool depthwise_lds_ok(const DwShape& s);
-size_t depthwise_lds_stats_floats(const DwShape& s);    // capacity a ConvStats needs for depthwise_forward_lds
-size_t depthwise_lds_partial_floats(const DwShape& s);  // scratch of depthwise_backward_lds
-// dw, dbias += the `splits` partials of a backward kernel (depthwise_march.hip writes the same layout)
-void dwl_finalize_launch(const float* partials, int splits, int C, float* dw, float* dbias, hipStream_t st);
-// y = act(dwconv(x) + bias); with `stats` also the per-channel sum / sum of squares partials of y
-bool depthwise_forward_lds(const float* x, const float* w, const float* bias, float* y, const DwShape& s, int act,
-                           ConvStats* stats, const DwBnIn* in = nullptr);
+// y = act(dwconv(x) + bias); with `stats` also the per-channel sum / sum of squares partials of y (stats->splits: the slots
+// per channel written, 0: not emitted); with `in`, x is normalised on load
+struct DwFwdCall {
+    const float *x, *w, *bias;
+    float* y;
+    DwShape s;
+    int act;
+    ConvStats* stats;
+    const DwBnIn* in;
+};
 // g = dy * act'(y) (written back over dy when `write_back`), or with `bn` g = BNbackward(bn->dz) * act'(y) and dy is not
 // touched; dbias += sum g; dw += sum x * g; dx = (overwrite ? 0 : dx) + w * g
 // in_sums (with `in`, overwrite): the kernel also emits the backward sums of the producer's batch-norm over the dx it
 // writes -- partials[(channel * splits + i) * 2 + {S1, S2}], the layout bn_bwd_finalize consumes; out: splits (0: not emitted)
-size_t depthwise_lds_in_sums_floats(const DwShape& s);
-bool depthwise_backward_lds(const float* x, const float* w, const float* y, float* dy, float* dx, float* dw, float* dbias,
-                            const DwShape& s, int act, int overwrite, int write_back, const DwBnBwd* bn,
-                            const DwBnIn* in = nullptr, ConvStats* in_sums = nullptr);
+struct DwBwdCall {
+    const float *x, *w, *y;
+    float *dy, *dx, *dw, *dbias;
+    DwShape s;
+    int act, overwrite, write_back;
+    const DwBnBwd* bn;
+    const DwBnIn* in;
+    ConvStats* in_sums;
+    float* partials;  // fused families: C * (most slots of any of them) * kDwPartFloats floats of scratch, from the ladder
+};
+constexpr int kDwPartFloats = 12;  // a fused backward kernel's partial per slot and channel: nine taps, bias sum, two unused
 
-// depthwise_march.hip: the same contracts for rows of at most 64 column groups of 4 / 2 / 1 floats, tried first by the two
-// entry points above; slots per channel of their statistics / sums / partials (0: not their shape)
-bool depthwise_march_ok(const DwShape& s);
+// what the kernel timer is told: forward and fused backward, one sweep; the unfused backward, the sweeps of its sequence
+struct DwWork {
+    double flops, bytes;
+};
+inline DwWork dw_fwd_work(const DwShape& s) {
+    const double in = (double)s.N * s.C * s.H * s.W, out = (double)s.N * s.C * s.OH * s.OW;
+    return DwWork{2.0 * out * s.ksz * s.ksz, 4.0 * (in + out)};
+}
+inline DwWork dw_bwd_work(const DwBwdCall& c) {
+    const DwShape& s = c.s;
+    const double in = (double)s.N * s.C * s.H * s.W, out = (double)s.N * s.C * s.OH * s.OW;
+    double bytes;
+    if (c.bn || c.in)  // dz (or dy read and written), y, x read; dx written (read too when it accumulates)
+        bytes = (c.bn ? 2.0 : 3.0) * out + (c.overwrite ? 2.0 : 3.0) * in;
+    else  // activation backward (y, dy r/w), bias gradient (dy), dW (x, dy), dX (dy, dx r/w)
+        bytes = ((c.act != BCNN_HIP_ACT_NONE) ? 3.0 : 0.0) * out + out +
+                (c.dx ? (in + out) + (out + (c.overwrite ? 1.0 : 2.0) * in) : 0.0);
+    return DwWork{4.0 * out * s.ksz * s.ksz, 4.0 * bytes};
+}
+
+// the caller's buffer when it holds `splits` slots of two floats per channel (st->splits then says so), else NULL
+inline float* dw_stats_slots(ConvStats* st, int C, int splits) {
+    if (!st || !st->partials || st->capacity < (size_t)C * splits * 2) return nullptr;
+    st->splits = splits;
+    return st->partials;
+}
+// the sums of the producer's batch-norm backward are of the COMPLETE gradient: only when the kernel is dx's sole writer, and
+// for producer activations whose derivative is 0 or 1
+inline bool dw_in_sums_wanted(const DwBwdCall& c) {
+    return c.in && c.in_sums && c.overwrite && (c.in->act == BCNN_HIP_ACT_NONE || c.in->act == BCNN_HIP_ACT_RELU);
+}
+
+// A fused family (depthwise_march.hip, depthwise_lds.hip) is asked only for 3x3 / pad 1 / stride 1 or 2 layers whose
+// activations its kernels can apply (dw_fused_fwd_ok / dw_fused_bwd_ok of depthwise.hip). `takes` decides everything else that
+// can refuse the layer -- plane geometry, alignment, LDS -- and touches nothing; `run` then launches. `slots`: partials per
+// channel of its statistics / sums / weight-gradient partials, 0 when the shape is not the family's.
 size_t depthwise_march_splits(const DwShape& s);
-bool depthwise_forward_march(const float* x, const float* w, const float* bias, float* y, const DwShape& s, int act,
-                             ConvStats* stats, const DwBnIn* in);
-bool depthwise_backward_march_takes(const float* x, const float* y, const float* dy, const float* dx, const DwShape& s, int act,
-                                    const DwBnBwd* bn, const DwBnIn* in);  // false: depthwise_backward_march would launch nothing
-bool depthwise_backward_march(const float* x, const float* w, const float* y, float* dy, float* dx, float* dw, float* dbias,
-                              const DwShape& s, int act, int overwrite, int write_back, const DwBnBwd* bn, const DwBnIn* in,
-                              ConvStats* in_sums);
+bool depthwise_march_fwd_takes(const DwFwdCall& c);
+void depthwise_march_forward(const DwFwdCall& c);
+bool depthwise_march_bwd_takes(const DwBwdCall& c);
+void depthwise_march_backward(const DwBwdCall& c);
+
+size_t depthwise_lds_slots(const DwShape& s);
+bool depthwise_lds_fwd_takes(const DwFwdCall& c);
+void depthwise_lds_forward(const DwFwdCall& c);
+bool depthwise_lds_bwd_takes(const DwBwdCall& c);
+void depthwise_lds_backward(const DwBwdCall& c);
+// dw, dbias += the `splits` partials of a fused backward kernel (depthwise_lds.hip; both families write its layout)
+void dwl_finalize_launch(const float* partials, int splits, int C, float* dw, float* dbias, hipStream_t st);
 
 }  // namespace bcnn_hip

@@ -9,8 +9,9 @@
 #include "chan_reduce.h"
 #include "depthwise.h"
 
-namespace bcnn_hip {
+#include <algorithm>
 
+namespace bcnn_hip {
 
 __global__ __launch_bounds__(256) void dw_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                      const float* __restrict__ bias, float* __restrict__ y,
@@ -510,129 +511,290 @@ __global__ __launch_bounds__(256) void dw3_bwd_data_s1_kernel(const float* __res
 
 static unsigned dw_magic(unsigned d) { return d > 1 ? (unsigned)((0x100000000ULL + d - 1) / d) : 0u; }
 
+// item space of the 3x3 register-window forward (planes = N * C) / weight-gradient (planes = N) kernels; false: not their shape
+static bool dw3_args(const DwShape& s, long long planes, Dw3Args* a) {
+    if (s.ksz != 3 || (s.stride != 1 && s.stride != 2)) return false;
+    const unsigned gpr = (unsigned)ceil_div(s.OW, 4), rgs = (unsigned)ceil_div(s.OH, DW_VR);
+    const long long groups = planes * rgs * gpr;
+    if (groups >= 0x7fffffffLL) return false;
+    a->s = s; a->groups_per_row = gpr; a->row_groups = rgs; a->gpr_magic = dw_magic(gpr); a->oh_magic = dw_magic(rgs);
+    a->total_groups = (unsigned)groups;
+    return true;
+}
+
+static bool dw_window3_fwd_takes(const DwFwdCall& c) {
+    Dw3Args a;
+    return dw3_args(c.s, (long long)c.s.N * c.s.C, &a);
+}
+static void dw_window3_forward(const DwFwdCall& c) {
+    Dw3Args a;
+    dw3_args(c.s, (long long)c.s.N * c.s.C, &a);
+    unsigned blocks = (a.total_groups + 255) / 256;
+#ifdef DW_PERSIST
+    if (blocks > (unsigned)(kCUs * DW_PERSIST)) blocks = (unsigned)(kCUs * DW_PERSIST);
+#endif
+    if (c.s.stride == 1) dw3_fwd_kernel<1, DW_VR><<<blocks, 256, 0, current_stream()>>>(c.x, c.w, c.bias, c.y, a, c.act);
+    else dw3_fwd_kernel<2, DW_VR><<<blocks, 256, 0, current_stream()>>>(c.x, c.w, c.bias, c.y, a, c.act);
+    KERNEL_CHECK();
+}
+
+static void dw_generic_forward(const DwFwdCall& c) {
+    const size_t total = (size_t)c.s.N * c.s.C * c.s.OH * c.s.OW;
+    dw_fwd_kernel<<<stream_grid(total, 256), 256, 0, current_stream()>>>(c.x, c.w, c.bias, c.y, c.s, c.act, (unsigned)total);
+    KERNEL_CHECK();
+}
+
+// three sweeps: dy *= act'(y) with dbias += sum; dw += the split partials of sum x * dy; dx (+)= w * dy
+static void dw_unfused_backward(const DwBwdCall& c) {
+    const DwShape& s = c.s;
+    const int n = s.N, ch = s.C, k = s.ksz, ohow = s.OH * s.OW;
+    activation_backward_grad_bias(c.y, c.dy, c.dbias, n, ch, ohow, c.act);
+    if (!c.dx) return;  // reference: dW and dX are both skipped when the source has no gradient (:318, :432)
+    const int NT = k * k;
+    const int splits = chan_splits(ch, (long long)n * ohow);
+    float* part = scratch(SCRATCH_REDUCE, (size_t)ch * splits * NT);
+    dim3 grid((unsigned)ch, (unsigned)splits);
+    Dw3Args a3;
+    if (ch <= 65535 && dw3_args(s, n, &a3)) {
+        dim3 g2((unsigned)splits, (unsigned)ch);
+        if (s.stride == 1) dw3_bwd_weight_kernel<1, DW_VR><<<g2, 256, 0, current_stream()>>>(c.x, c.dy, a3, splits, part);
+        else dw3_bwd_weight_kernel<2, DW_VR><<<g2, 256, 0, current_stream()>>>(c.x, c.dy, a3, splits, part);
+    } else if (k == 3) dw_bwd_weight_kernel<3><<<grid, 256, 0, current_stream()>>>(c.x, c.dy, s, splits, part);
+    else if (k == 5) dw_bwd_weight_kernel<5><<<grid, 256, 0, current_stream()>>>(c.x, c.dy, s, splits, part);
+    else {
+        dim3 g3((unsigned)ch, (unsigned)splits, (unsigned)NT);
+        dw_bwd_weight_tap_kernel<<<g3, 256, 0, current_stream()>>>(c.x, c.dy, s, splits, part);
+    }
+    KERNEL_CHECK();
+    dw_weight_accumulate_kernel<<<ceil_div(ch * NT, 256), 256, 0, current_stream()>>>(part, ch, NT, splits, c.dw);
+    KERNEL_CHECK();
+    const long long total_i = (long long)n * ch * s.H * s.W;
+    const unsigned gpr_i = (unsigned)ceil_div(s.W, 4);
+    const unsigned rgs_i = s.stride == 1 ? (unsigned)ceil_div(s.H, DW_VR) : (unsigned)s.H;
+    const long long groups_i = (long long)n * ch * rgs_i * gpr_i;
+    if (k == 3 && groups_i < 0x7fffffffLL) {
+        Dw3DxArgs a;
+        a.s = s; a.groups_per_row = gpr_i; a.row_groups = rgs_i; a.gpr_magic = dw_magic(gpr_i); a.h_magic = dw_magic(rgs_i);
+        a.total_groups = (unsigned)groups_i;
+        a.overwrite = c.overwrite;
+        const unsigned blocks = (unsigned)((groups_i + 255) / 256);
+        if (s.stride == 1) dw3_bwd_data_s1_kernel<DW_VR><<<blocks, 256, 0, current_stream()>>>(c.dy, c.w, c.dx, a);
+        else if (s.stride == 2) dw3_bwd_data_kernel<2><<<blocks, 256, 0, current_stream()>>>(c.dy, c.w, c.dx, a);
+        else dw3_bwd_data_kernel<0><<<blocks, 256, 0, current_stream()>>>(c.dy, c.w, c.dx, a);
+    } else {
+        dw_bwd_data_kernel<<<stream_grid((size_t)total_i, 256), 256, 0, current_stream()>>>(c.dy, c.w, c.dx, s,
+                                                                                         (unsigned)total_i, c.overwrite);
+    }
+    KERNEL_CHECK();
+}
+
+// ---- which family takes a layer ------------------------------------------------------------------------------------------------------
+// Every family is tried in a fixed order and says for itself whether the layer is its own (depthwise.h):
+//   forward   marching windows, LDS-staged, register-window 3x3, generic
+//   backward  marching windows, LDS-staged, then the unfused sequence (activation_backward_grad_bias, the weight-gradient
+//             kernel with its accumulate, the data-gradient kernel)
+// The first two of each are the FUSED families, asked only behind dw_fused_shape and the activation rules below; only they can
+// serve `stats` / `in` / `bn` / `in_sums`. The size queries and the backward scratch are the maximum of `slots` over the rows.
+// A new family is a row here and its declarations in depthwise.h.
+template <class Call>
+struct DwFamily {
+    bool fused;
+    bool (*takes)(const Call& c);  // decides everything that can refuse the layer, touches nothing
+    void (*run)(const Call& c);    // cannot refuse
+    size_t (*slots)(const DwShape& s);
+};
+static size_t dw_no_slots(const DwShape&) { return 0; }
+static const DwFamily<DwFwdCall> kDwFwdFamilies[] = {
+    {true, depthwise_march_fwd_takes, depthwise_march_forward, depthwise_march_splits},
+    {true, depthwise_lds_fwd_takes, depthwise_lds_forward, depthwise_lds_slots},
+    {false, dw_window3_fwd_takes, dw_window3_forward, dw_no_slots},
+    {false, [](const DwFwdCall&) { return true; }, dw_generic_forward, dw_no_slots},
+};
+static const DwFamily<DwBwdCall> kDwBwdFamilies[] = {
+    {true, depthwise_march_bwd_takes, depthwise_march_backward, depthwise_march_splits},
+    {true, depthwise_lds_bwd_takes, depthwise_lds_backward, depthwise_lds_slots},
+    {false, [](const DwBwdCall&) { return true; }, dw_unfused_backward, dw_no_slots},
+};
+
+// the fused families' shape gate. Experiment build: BCNN_HIP_NO_DW_LDS turns both off, BCNN_HIP_NO_DW_MARCH the marching one
+static bool dw_fused_shape(const DwShape& s) {
+    static const int on = BCNN_EXP_ENV("BCNN_HIP_NO_DW_LDS") ? 0 : 1;
+    if (!on || s.ksz != 3 || s.pad != 1 || (s.stride != 1 && s.stride != 2)) return false;
+    return s.N >= 1 && s.C >= 1 && s.H >= 1 && s.W >= 1 && s.OH >= 1 && s.OW >= 1;
+}
+static bool dw_fused_fwd_ok(const DwFwdCall& c) {
+    return dw_fused_shape(c.s) && act_is_cheap(c.act) && c.act != BCNN_HIP_ACT_PRELU && dw_in_ok(c.in);
+}
+static bool dw_fused_bwd_ok(const DwBwdCall& c) {
+    return c.dx && dw_fused_shape(c.s) && act_bwd_is_cheap(c.act) && c.act != BCNN_HIP_ACT_PRELU && dw_in_ok(c.in);
+}
+// A fused family gets dy with the derivative already applied, and ACT_NONE, when the derivative is expensive (softplus needs
+// exp()), or when the kernel would write g = dy * act'(y) back over dy and the factor is not 0 or 1: the band that owns a row
+// writes it while the neighbouring band reads it as its halo -- a race unless applying the derivative twice changes nothing
+// (leaky ReLU: 0.01 instead of 0.1 on a band's edge row). With `bn` there is no dy to prepare; PReLU is never fused.
+static bool dw_bwd_prepass(const DwBwdCall& c) {
+    if (c.bn || c.act == BCNN_HIP_ACT_PRELU) return false;
+    return !act_bwd_is_cheap(c.act) ||
+           (c.write_back && c.act != BCNN_HIP_ACT_NONE && c.act != BCNN_HIP_ACT_RELU && c.act != BCNN_HIP_ACT_CLAMP);
+}
+
+template <class Call, size_t R>
+static size_t dw_slots(const DwFamily<Call> (&rows)[R], const DwShape& s) {
+    size_t m = 0;
+    if (dw_fused_shape(s))
+        for (const DwFamily<Call>& fam : rows) m = std::max(m, fam.slots(s));
+    return m;
+}
+
+// false: no family takes the layer (one with `in` that the fused families refuse); nothing has been launched
+static bool dw_forward(DwFwdCall c) {
+    const DwShape& s = c.s;
+    const long long total = (long long)s.N * s.C * s.OH * s.OW;
+    if (c.stats) c.stats->splits = 0;
+    if (total <= 0) return true;
+    KTimer kt(K_DEPTHWISE_FWD, dw_fwd_work(s).flops, dw_fwd_work(s).bytes);
+    const int act = c.act;
+    if (!act_is_cheap(act)) {  // applied to y in a pass of its own; the statistics are those of the STORED output: none then
+        if (c.in) return false;
+        c.act = BCNN_HIP_ACT_NONE;
+        c.stats = nullptr;
+    }
+    for (const DwFamily<DwFwdCall>& fam : kDwFwdFamilies) {
+        if ((fam.fused ? !dw_fused_fwd_ok(c) : c.in != nullptr) || !fam.takes(c)) continue;
+        fam.run(c);
+        if (c.act != act) bcnn_hip_activation_forward(c.y, (size_t)total, act, nullptr, s.OH * s.OW, s.C);
+        return true;
+    }
+    return false;
+}
+
+// false: no family takes the layer (one with `bn` or `in` that the fused families refuse); dy is as it was handed over
+static bool dw_backward(const DwBwdCall& call) {
+    const DwShape& s = call.s;
+    const long long total_o = (long long)s.N * s.C * s.OH * s.OW;
+    if (call.in_sums) call.in_sums->splits = 0;
+    if (total_o <= 0) return true;
+    KTimer kt(K_DEPTHWISE_BWD, dw_bwd_work(call).flops, dw_bwd_work(call).bytes);
+    DwBwdCall fused = call;  // what a fused family sees
+    const bool prepass = dw_bwd_prepass(call);
+    if (prepass) fused.act = BCNN_HIP_ACT_NONE;
+    const bool fused_ok = dw_fused_bwd_ok(fused);
+    for (const DwFamily<DwBwdCall>& fam : kDwBwdFamilies) {
+        const DwBwdCall& c = fam.fused ? fused : call;
+        if ((fam.fused ? !fused_ok : (c.bn || c.in)) || !fam.takes(c)) continue;
+        if (fam.fused && prepass)
+            bcnn_hip_activation_backward(c.y, c.dy, (size_t)total_o, call.act, nullptr, nullptr, s.OH * s.OW, s.C);
+        if (fam.fused) fused.partials = scratch(SCRATCH_REDUCE, (size_t)s.C * dw_slots(kDwBwdFamilies, s) * kDwPartFloats);
+        fam.run(c);
+        return true;
+    }
+    return false;
+}
+
+// the entry points that have nothing to fall back to
+static void dw_refused(const char* who, bool bnin) {
+    fprintf(stderr, "[bcnn_hip] %s: %s not fusable (ask bcnn_hip_depthwise_%s_fusable)\n", who,
+            bnin ? "shape / activation" : "shape", bnin ? "bnin" : "bn");
+    exit(1);
+}
+
 }  // namespace bcnn_hip
 
 using namespace bcnn_hip;
 
 extern "C" {
 
+int bcnn_hip_depthwise_forward_stats(const float* x, const float* w, const float* bias, float* y, int n, int c, int h,
+                                     int wd, int k, int stride, int pad, int act, float* stats, size_t stats_floats) {
+    ConvStats st{stats, 0, stats_floats};
+    dw_forward(DwFwdCall{x, w, bias, y, dw_shape(n, c, h, wd, k, stride, pad), act, &st, nullptr});
+    return st.splits;
+}
+
 void bcnn_hip_depthwise_forward(const float* x, const float* w, const float* bias, float* y, int n, int c,
                                 int h, int wd, int k, int stride, int pad, int act) {
-    DwShape s{n, c, h, wd, (h + 2 * pad - k) / stride + 1, (wd + 2 * pad - k) / stride + 1, k, stride, pad};
-    const long long total = (long long)n * c * s.OH * s.OW;
-    if (total <= 0) return;
-    KTimer kt(K_DEPTHWISE_FWD, 2.0 * (double)total * k * k, 4.0 * ((double)n * c * h * wd + (double)total));
-    const int fused = act_is_cheap(act) ? act : BCNN_HIP_ACT_NONE;
-    if (depthwise_forward_lds(x, w, bias, y, s, fused, nullptr)) {
-        if (fused != act) bcnn_hip_activation_forward(y, (size_t)total, act, nullptr, s.OH * s.OW, c);
-        return;
-    }
-    const unsigned gpr = (unsigned)ceil_div(s.OW, 4);
-    constexpr int VR = DW_VR;
-    const unsigned rgs = (unsigned)ceil_div(s.OH, VR);
-    const long long groups = (long long)n * c * rgs * gpr;
-    if (k == 3 && (stride == 1 || stride == 2) && groups < 0x7fffffffLL) {
-        Dw3Args a;
-        a.s = s; a.groups_per_row = gpr; a.row_groups = rgs; a.gpr_magic = dw_magic(gpr); a.oh_magic = dw_magic(rgs);
-        a.total_groups = (unsigned)groups;
-        unsigned blocks = (unsigned)((groups + 255) / 256);
-#ifdef DW_PERSIST
-        if (blocks > (unsigned)(kCUs * DW_PERSIST)) blocks = (unsigned)(kCUs * DW_PERSIST);
-#endif
-        if (stride == 1) dw3_fwd_kernel<1, VR><<<blocks, 256, 0, current_stream()>>>(x, w, bias, y, a, fused);
-        else dw3_fwd_kernel<2, VR><<<blocks, 256, 0, current_stream()>>>(x, w, bias, y, a, fused);
-    } else {
-        dw_fwd_kernel<<<stream_grid((size_t)total, 256), 256, 0, current_stream()>>>(x, w, bias, y, s, fused,
-                                                                                   (unsigned)total);
-    }
-    KERNEL_CHECK();
-    if (fused != act) bcnn_hip_activation_forward(y, (size_t)total, act, nullptr, s.OH * s.OW, c);
+    bcnn_hip_depthwise_forward_stats(x, w, bias, y, n, c, h, wd, k, stride, pad, act, nullptr, 0);
+}
+
+// ---- the same with the producing convolution node's batch-norm applied to the input on the fly -------------------------------------
+int bcnn_hip_depthwise_forward_bnin(const float* x_raw, const float* w, const float* bias, float* y, int n, int c, int h,
+                                    int wd, int k, int stride, int pad, int act, float* stats, size_t stats_floats,
+                                    const float* in_mean, const float* in_var, const float* in_scale, const float* in_bias,
+                                    int in_act) {
+    ConvStats st{stats, 0, stats_floats};
+    const DwBnIn in{in_mean, in_var, in_scale, in_bias, in_act};
+    if (!dw_forward(DwFwdCall{x_raw, w, bias, y, dw_shape(n, c, h, wd, k, stride, pad), act, &st, &in}))
+        dw_refused("bcnn_hip_depthwise_forward_bnin", true);
+    return st.splits;
 }
 
 size_t bcnn_hip_depthwise_stats_size(int n, int c, int h, int wd, int k, int stride, int pad) {
-    if (stride < 1 || k < 1) return 0;
-    DwShape s{n, c, h, wd, (h + 2 * pad - k) / stride + 1, (wd + 2 * pad - k) / stride + 1, k, stride, pad};
-    return depthwise_lds_stats_floats(s);
+    return (size_t)c * dw_slots(kDwFwdFamilies, dw_shape(n, c, h, wd, k, stride, pad)) * 2;
 }
 
-int bcnn_hip_depthwise_forward_stats(const float* x, const float* w, const float* bias, float* y, int n, int c, int h,
-                                     int wd, int k, int stride, int pad, int act, float* stats, size_t stats_floats) {
-    DwShape s{n, c, h, wd, (h + 2 * pad - k) / stride + 1, (wd + 2 * pad - k) / stride + 1, k, stride, pad};
-    const long long total = (long long)n * c * s.OH * s.OW;
-    if (total > 0 && stats && act_is_cheap(act)) {
-        // the statistics are those of the STORED output, so the activation has to be fused in the kernel
-        KTimer kt(K_DEPTHWISE_FWD, 2.0 * (double)total * k * k, 4.0 * ((double)n * c * h * wd + (double)total));
-        ConvStats st;
-        st.partials = stats; st.capacity = stats_floats; st.splits = 0;
-        if (depthwise_forward_lds(x, w, bias, y, s, act, &st)) return st.splits;
-    }
-    bcnn_hip_depthwise_forward(x, w, bias, y, n, c, h, wd, k, stride, pad, act);
-    return 0;
+size_t bcnn_hip_depthwise_insums_size(int n, int c, int h, int wd, int k, int stride, int pad) {
+    return (size_t)c * dw_slots(kDwBwdFamilies, dw_shape(n, c, h, wd, k, stride, pad)) * 2;
 }
 
 int bcnn_hip_depthwise_bn_fusable(int n, int c, int h, int wd, int k, int stride, int pad, int act) {
-    if (stride < 1 || k < 1) return 0;
-    DwShape s{n, c, h, wd, (h + 2 * pad - k) / stride + 1, (wd + 2 * pad - k) / stride + 1, k, stride, pad};
-    return depthwise_lds_ok(s) && act_bwd_is_cheap(act) && act != BCNN_HIP_ACT_PRELU;
+    return dw_slots(kDwBwdFamilies, dw_shape(n, c, h, wd, k, stride, pad)) && act_bwd_is_cheap(act) && act != BCNN_HIP_ACT_PRELU;
+}
+
+int bcnn_hip_depthwise_bnin_fusable(int n, int c, int h, int wd, int k, int stride, int pad, int act, int in_act) {
+    return bcnn_hip_depthwise_bn_fusable(n, c, h, wd, k, stride, pad, act) && act_is_cheap(act) && act_is_cheap(in_act) &&
+           in_act != BCNN_HIP_ACT_PRELU;
+}
+
+void bcnn_hip_depthwise_backward(const float* x, const float* w, const float* y, float* dy, float* dx,
+                                 float* dw, float* dbias, int n, int c, int h, int wd, int k, int stride,
+                                 int pad, int act, int overwrite) {
+    dw_backward(DwBwdCall{x, w, y, dy, dx, dw, dbias, dw_shape(n, c, h, wd, k, stride, pad), act, overwrite, /*write_back=*/1,
+                          nullptr, nullptr, nullptr, nullptr});
 }
 
 void bcnn_hip_depthwise_backward_bn(const float* x, const float* w, const float* y, const float* dz, float* dx, float* dw,
                                     float* dbias, int n, int c, int h, int wd, int k, int stride, int pad, int act,
                                     int overwrite, const float* bn_mean, const float* bn_var, const float* bn_scales,
                                     const float* bn_dmean, const float* bn_dvar) {
-    DwShape s{n, c, h, wd, (h + 2 * pad - k) / stride + 1, (wd + 2 * pad - k) / stride + 1, k, stride, pad};
-    const long long total_o = (long long)n * c * s.OH * s.OW;
-    if (total_o <= 0) return;
-    // algorithmic bytes: dz, y, x read; dx written (read too when it accumulates)
-    KTimer kt(K_DEPTHWISE_BWD, 4.0 * (double)total_o * k * k,
-              4.0 * (2.0 * (double)total_o + (overwrite ? 2.0 : 3.0) * (double)n * c * h * wd));
-    DwBnBwd bn{dz, bn_mean, bn_var, bn_scales, bn_dmean, bn_dvar};
-    if (!dx || !depthwise_backward_lds(x, w, y, nullptr, dx, dw, dbias, s, act, overwrite, 0, &bn)) {
-        fprintf(stderr, "[bcnn_hip] bcnn_hip_depthwise_backward_bn: shape not fusable (ask bcnn_hip_depthwise_bn_fusable)\n");
-        exit(1);
-    }
+    const DwBnBwd bn{dz, bn_mean, bn_var, bn_scales, bn_dmean, bn_dvar};
+    if (!dw_backward(DwBwdCall{x, w, y, nullptr, dx, dw, dbias, dw_shape(n, c, h, wd, k, stride, pad), act, overwrite,
+                               /*write_back=*/0, &bn, nullptr, nullptr, nullptr}))
+        dw_refused("bcnn_hip_depthwise_backward_bn", false);
 }
 
-// ---- the same three with the producing convolution node's batch-norm applied to the input on the fly ----------------
-int bcnn_hip_depthwise_bnin_fusable(int n, int c, int h, int wd, int k, int stride, int pad, int act, int in_act) {
-    if (stride < 1 || k < 1) return 0;
-    DwShape s{n, c, h, wd, (h + 2 * pad - k) / stride + 1, (wd + 2 * pad - k) / stride + 1, k, stride, pad};
-    return depthwise_lds_ok(s) && act_is_cheap(act) && act_bwd_is_cheap(act) && act != BCNN_HIP_ACT_PRELU &&
-           act_is_cheap(in_act) && in_act != BCNN_HIP_ACT_PRELU;
-}
-
-static void dw_bnin_refused(const char* who) {
-    fprintf(stderr, "[bcnn_hip] %s: shape / activation not fusable (ask bcnn_hip_depthwise_bnin_fusable)\n", who);
-    exit(1);
-}
-
-int bcnn_hip_depthwise_forward_bnin(const float* x_raw, const float* w, const float* bias, float* y, int n, int c, int h,
-                                    int wd, int k, int stride, int pad, int act, float* stats, size_t stats_floats,
-                                    const float* in_mean, const float* in_var, const float* in_scale, const float* in_bias,
-                                    int in_act) {
-    DwShape s{n, c, h, wd, (h + 2 * pad - k) / stride + 1, (wd + 2 * pad - k) / stride + 1, k, stride, pad};
-    const long long total = (long long)n * c * s.OH * s.OW;
-    if (total <= 0) return 0;
-    KTimer kt(K_DEPTHWISE_FWD, 2.0 * (double)total * k * k, 4.0 * ((double)n * c * h * wd + (double)total));
-    ConvStats st;
-    st.partials = stats; st.capacity = stats_floats; st.splits = 0;
-    DwBnIn in{in_mean, in_var, in_scale, in_bias, in_act};
-    if (!depthwise_forward_lds(x_raw, w, bias, y, s, act, stats ? &st : nullptr, &in)) dw_bnin_refused("bcnn_hip_depthwise_forward_bnin");
+// The backward of a layer whose input is normalised on load: with bn_mean the following batch-norm's backward is applied to dy
+// (which is then that node's dz and is not written), without it g is written back over dy. in_sums: the kernel also leaves the
+// backward sums of the PRODUCER's batch-norm there; returns the partials per channel (0: not emitted -- dx accumulates, or the
+// buffer is too small)
+static int dw_backward_bnin(const char* who, const float* x_raw, const float* w, const float* y, float* dy, float* dx, float* dw,
+                            float* dbias, const DwShape& s, int act, int overwrite, const DwBnBwd& bn, const DwBnIn& in,
+                            float* in_sums, size_t in_sums_floats) {
+    ConvStats st{in_sums, 0, in_sums_floats};
+    if (!dw_backward(DwBwdCall{x_raw, w, y, bn.mean ? nullptr : dy, dx, dw, dbias, s, act, overwrite, /*write_back=*/bn.mean ? 0 : 1,
+                               bn.mean ? &bn : nullptr, &in, &st, nullptr}))
+        dw_refused(who, true);
     return st.splits;
+}
+
+int bcnn_hip_depthwise_backward_bnin_sums(const float* x_raw, const float* w, const float* y, float* dy, float* dx, float* dw,
+                                          float* dbias, int n, int c, int h, int wd, int k, int stride, int pad, int act,
+                                          int overwrite, const float* bn_mean, const float* bn_var, const float* bn_scales,
+                                          const float* bn_dmean, const float* bn_dvar, const float* in_mean,
+                                          const float* in_var, const float* in_scale, const float* in_bias, int in_act,
+                                          float* in_sums, size_t in_sums_floats) {
+    return dw_backward_bnin("bcnn_hip_depthwise_backward_bnin_sums", x_raw, w, y, dy, dx, dw, dbias,
+                            dw_shape(n, c, h, wd, k, stride, pad), act, overwrite,
+                            DwBnBwd{dy, bn_mean, bn_var, bn_scales, bn_dmean, bn_dvar},
+                            DwBnIn{in_mean, in_var, in_scale, in_bias, in_act}, in_sums, in_sums_floats);
 }
 
 void bcnn_hip_depthwise_backward_bnin(const float* x_raw, const float* w, const float* y, float* dy, float* dx, float* dw,
                                       float* dbias, int n, int c, int h, int wd, int k, int stride, int pad, int act,
                                       int overwrite, const float* in_mean, const float* in_var, const float* in_scale,
                                       const float* in_bias, int in_act) {
-    DwShape s{n, c, h, wd, (h + 2 * pad - k) / stride + 1, (wd + 2 * pad - k) / stride + 1, k, stride, pad};
-    const long long total_o = (long long)n * c * s.OH * s.OW;
-    if (total_o <= 0) return;
-    KTimer kt(K_DEPTHWISE_BWD, 4.0 * (double)total_o * k * k,
-              4.0 * (3.0 * (double)total_o + (overwrite ? 2.0 : 3.0) * (double)n * c * h * wd));
-    DwBnIn in{in_mean, in_var, in_scale, in_bias, in_act};
-    if (!dx || !depthwise_backward_lds(x_raw, w, y, dy, dx, dw, dbias, s, act, overwrite, /*write_back=*/1, nullptr, &in))
-        dw_bnin_refused("bcnn_hip_depthwise_backward_bnin");
+    dw_backward_bnin("bcnn_hip_depthwise_backward_bnin", x_raw, w, y, dy, dx, dw, dbias, dw_shape(n, c, h, wd, k, stride, pad),
+                     act, overwrite, DwBnBwd{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
+                     DwBnIn{in_mean, in_var, in_scale, in_bias, in_act}, nullptr, 0);
 }
 
 void bcnn_hip_depthwise_backward_bn_bnin(const float* x_raw, const float* w, const float* y, const float* dz, float* dx,
@@ -641,117 +803,9 @@ void bcnn_hip_depthwise_backward_bn_bnin(const float* x_raw, const float* w, con
                                          const float* bn_scales, const float* bn_dmean, const float* bn_dvar,
                                          const float* in_mean, const float* in_var, const float* in_scale,
                                          const float* in_bias, int in_act) {
-    DwShape s{n, c, h, wd, (h + 2 * pad - k) / stride + 1, (wd + 2 * pad - k) / stride + 1, k, stride, pad};
-    const long long total_o = (long long)n * c * s.OH * s.OW;
-    if (total_o <= 0) return;
-    KTimer kt(K_DEPTHWISE_BWD, 4.0 * (double)total_o * k * k,
-              4.0 * (2.0 * (double)total_o + (overwrite ? 2.0 : 3.0) * (double)n * c * h * wd));
-    DwBnBwd bn{dz, bn_mean, bn_var, bn_scales, bn_dmean, bn_dvar};
-    DwBnIn in{in_mean, in_var, in_scale, in_bias, in_act};
-    if (!dx || !depthwise_backward_lds(x_raw, w, y, nullptr, dx, dw, dbias, s, act, overwrite, 0, &bn, &in))
-        dw_bnin_refused("bcnn_hip_depthwise_backward_bn_bnin");
-}
-
-size_t bcnn_hip_depthwise_insums_size(int n, int c, int h, int wd, int k, int stride, int pad) {
-    if (stride < 1 || k < 1) return 0;
-    DwShape s{n, c, h, wd, (h + 2 * pad - k) / stride + 1, (wd + 2 * pad - k) / stride + 1, k, stride, pad};
-    return depthwise_lds_in_sums_floats(s);
-}
-
-// bcnn_hip_depthwise_backward_bnin (bn_mean == NULL) / _bn_bnin whose kernel also leaves the backward sums of the PRODUCER's
-// batch-norm in in_sums; returns the partials per channel (0: not emitted -- dx accumulates, or the buffer is too small)
-int bcnn_hip_depthwise_backward_bnin_sums(const float* x_raw, const float* w, const float* y, float* dy, float* dx, float* dw,
-                                          float* dbias, int n, int c, int h, int wd, int k, int stride, int pad, int act,
-                                          int overwrite, const float* bn_mean, const float* bn_var, const float* bn_scales,
-                                          const float* bn_dmean, const float* bn_dvar, const float* in_mean,
-                                          const float* in_var, const float* in_scale, const float* in_bias, int in_act,
-                                          float* in_sums, size_t in_sums_floats) {
-    DwShape s{n, c, h, wd, (h + 2 * pad - k) / stride + 1, (wd + 2 * pad - k) / stride + 1, k, stride, pad};
-    const long long total_o = (long long)n * c * s.OH * s.OW;
-    if (total_o <= 0) return 0;
-    KTimer kt(K_DEPTHWISE_BWD, 4.0 * (double)total_o * k * k,
-              4.0 * ((bn_mean ? 2.0 : 3.0) * (double)total_o + (overwrite ? 2.0 : 3.0) * (double)n * c * h * wd));
-    DwBnBwd bn{dy, bn_mean, bn_var, bn_scales, bn_dmean, bn_dvar};
-    DwBnIn in{in_mean, in_var, in_scale, in_bias, in_act};
-    ConvStats st;
-    st.partials = in_sums; st.capacity = in_sums_floats; st.splits = 0;
-    if (!dx || !depthwise_backward_lds(x_raw, w, y, bn_mean ? nullptr : dy, dx, dw, dbias, s, act, overwrite,
-                                       /*write_back=*/bn_mean ? 0 : 1, bn_mean ? &bn : nullptr, &in, in_sums ? &st : nullptr))
-        dw_bnin_refused("bcnn_hip_depthwise_backward_bnin_sums");
-    return st.splits;
-}
-
-void bcnn_hip_depthwise_backward(const float* x, const float* w, const float* y, float* dy, float* dx,
-                                 float* dw, float* dbias, int n, int c, int h, int wd, int k, int stride,
-                                 int pad, int act, int overwrite) {
-    DwShape s{n, c, h, wd, (h + 2 * pad - k) / stride + 1, (wd + 2 * pad - k) / stride + 1, k, stride, pad};
-    const int ohow = s.OH * s.OW;
-    const long long total_o = (long long)n * c * ohow;
-    if (total_o <= 0) return;
-    // algorithmic bytes: activation backward (y, dy r/w), bias gradient (dy), dW (x, dy), dX (dy, dx r/w)
-    KTimer kt(K_DEPTHWISE_BWD, 4.0 * (double)total_o * k * k,
-              4.0 * (((act != BCNN_HIP_ACT_NONE) ? 3.0 : 0.0) * (double)total_o + (double)total_o +
-                     (dx ? ((double)n * c * h * wd + (double)total_o) + ((double)total_o + (overwrite ? 1.0 : 2.0) * (double)n * c * h * wd)
-                         : 0.0)));
-    if (dx && depthwise_lds_ok(s) && act != BCNN_HIP_ACT_PRELU) {
-        // one pass: dy *= act'(y) written back, dbias, dW, dX (softplus: its derivative needs exp() -> own pass first)
-        int a = act;
-        if (!act_bwd_is_cheap(act)) {
-            bcnn_hip_activation_backward(y, dy, (size_t)total_o, act, nullptr, nullptr, ohow, c);
-            a = BCNN_HIP_ACT_NONE;
-        }
-        // a refusal (an LDS image above 64 KB on a shape the marching kernels do not take either) leaves dy as it was handed
-        // over: depthwise_backward_lds decides before it prepares anything
-        if (depthwise_backward_lds(x, w, y, dy, dx, dw, dbias, s, a, overwrite, /*write_back=*/1, nullptr)) return;
-        if (a != act) {  // the expensive derivative has been applied above: the generic path continues without it
-            act = BCNN_HIP_ACT_NONE;
-        }
-    }
-    activation_backward_grad_bias(y, dy, dbias, n, c, ohow, act);  // one sweep: dy *= act'(y), dbias += sum
-    if (!dx) return;  // reference: dW and dX are both skipped when the source has no gradient (:318, :432)
-    const int NT = k * k;
-    const long long M = (long long)n * ohow;
-    const int splits = chan_splits(c, M);
-    float* part = scratch(SCRATCH_REDUCE, (size_t)c * splits * NT);
-    dim3 grid((unsigned)c, (unsigned)splits);
-    const unsigned gpr = (unsigned)ceil_div(s.OW, 4);
-    constexpr int VR = DW_VR;
-    const unsigned rgs = (unsigned)ceil_div(s.OH, VR);
-    if (k == 3 && (stride == 1 || stride == 2) && (long long)n * rgs * gpr < 0x7fffffffLL && c <= 65535) {
-        Dw3Args a;
-        a.s = s; a.groups_per_row = gpr; a.row_groups = rgs; a.gpr_magic = dw_magic(gpr); a.oh_magic = dw_magic(rgs);
-        a.total_groups = 0;
-        dim3 g2((unsigned)splits, (unsigned)c);
-        if (stride == 1) dw3_bwd_weight_kernel<1, VR><<<g2, 256, 0, current_stream()>>>(x, dy, a, splits, part);
-        else dw3_bwd_weight_kernel<2, VR><<<g2, 256, 0, current_stream()>>>(x, dy, a, splits, part);
-    } else if (k == 3) dw_bwd_weight_kernel<3><<<grid, 256, 0, current_stream()>>>(x, dy, s, splits, part);
-    else if (k == 5) dw_bwd_weight_kernel<5><<<grid, 256, 0, current_stream()>>>(x, dy, s, splits, part);
-    else {
-        dim3 g3((unsigned)c, (unsigned)splits, (unsigned)NT);
-        dw_bwd_weight_tap_kernel<<<g3, 256, 0, current_stream()>>>(x, dy, s, splits, part);
-    }
-    KERNEL_CHECK();
-    dw_weight_accumulate_kernel<<<ceil_div(c * NT, 256), 256, 0, current_stream()>>>(part, c, NT, splits, dw);
-    KERNEL_CHECK();
-    const long long total_i = (long long)n * c * h * wd;
-    const unsigned gpr_i = (unsigned)ceil_div(wd, 4);
-    constexpr int VRX = DW_VR;
-    const unsigned rgs_i = stride == 1 ? (unsigned)ceil_div(h, VRX) : (unsigned)h;
-    const long long groups_i = (long long)n * c * rgs_i * gpr_i;
-    if (k == 3 && groups_i < 0x7fffffffLL) {
-        Dw3DxArgs a;
-        a.s = s; a.groups_per_row = gpr_i; a.row_groups = rgs_i; a.gpr_magic = dw_magic(gpr_i); a.h_magic = dw_magic(rgs_i);
-        a.total_groups = (unsigned)groups_i;
-        a.overwrite = overwrite;
-        const unsigned blocks = (unsigned)((groups_i + 255) / 256);
-        if (stride == 1) dw3_bwd_data_s1_kernel<VRX><<<blocks, 256, 0, current_stream()>>>(dy, w, dx, a);
-        else if (stride == 2) dw3_bwd_data_kernel<2><<<blocks, 256, 0, current_stream()>>>(dy, w, dx, a);
-        else dw3_bwd_data_kernel<0><<<blocks, 256, 0, current_stream()>>>(dy, w, dx, a);
-    } else {
-        dw_bwd_data_kernel<<<stream_grid((size_t)total_i, 256), 256, 0, current_stream()>>>(dy, w, dx, s,
-                                                                                         (unsigned)total_i, overwrite);
-    }
-    KERNEL_CHECK();
+    dw_backward_bnin("bcnn_hip_depthwise_backward_bn_bnin", x_raw, w, y, nullptr, dx, dw, dbias,
+                     dw_shape(n, c, h, wd, k, stride, pad), act, overwrite, DwBnBwd{dz, bn_mean, bn_var, bn_scales, bn_dmean, bn_dvar},
+                     DwBnIn{in_mean, in_var, in_scale, in_bias, in_act}, nullptr, 0);
 }
 
 }  // extern "C"

@@ -23,8 +23,6 @@
 #include "depthwise.h"
 #include "lds_dma.h"
 
-#include <algorithm>
-
 namespace bcnn_hip {
 
 namespace {
@@ -415,7 +413,7 @@ struct DwlBwdArgs {
     int x_floats, g_floats;
 };
 
-constexpr int kPart = 12;
+constexpr int kPart = kDwPartFloats;
 
 template <int S, int VR, bool BN, bool BNIN>
 __global__ __launch_bounds__(256) void dwl_bwd_kernel(const DwlBwdArgs a) {
@@ -872,86 +870,58 @@ void dwl_finalize_launch(const float* partials, int splits, int C, float* dw, fl
     KERNEL_CHECK();
 }
 
-bool depthwise_lds_ok(const DwShape& s) {
-    static const int on = BCNN_EXP_ENV("BCNN_HIP_NO_DW_LDS") ? 0 : 1;  // A/B switch (experiment build only)
-    if (!on) return false;
-    if (s.ksz != 3 || s.pad != 1 || (s.stride != 1 && s.stride != 2)) return false;
-    if (s.N < 1 || s.C < 1 || s.H < 1 || s.W < 1 || s.OH < 1 || s.OW < 1) return false;
-    if (s.W > kTileFloats / 8) return false;  // a band needs at least 3 + stride input rows of <= kTileFloats floats
+// what the tiling adds to the fused-shape gate of depthwise.hip; slots per channel: one per image and band
+size_t depthwise_lds_slots(const DwShape& s) {
+    if (s.W > kTileFloats / 8) return 0;  // a band needs at least 3 + stride input rows of <= kTileFloats floats
     const DwlGeom g = dwl_plan(s);
     const long long tiles = (long long)ceil_div((long long)s.N * s.C, g.P) * g.NB;
-    return tiles < 0x7fffffffLL && (long long)s.N * s.C * s.H * s.W < 0x7fffffffLL * 2;
+    if (tiles >= 0x7fffffffLL || (long long)s.N * s.C * s.H * s.W >= 0x7fffffffLL * 2) return 0;
+    return (size_t)s.N * g.NB;
 }
 
-size_t depthwise_lds_stats_floats(const DwShape& s) {
-    if (!depthwise_lds_ok(s)) return 0;
-    const DwlGeom g = dwl_plan(s);
-    const size_t march = (size_t)s.C * depthwise_march_splits(s) * 2;  // the marching kernels' slots, where they take the shape
-    return std::max((size_t)s.C * s.N * g.NB * 2, march);
+// the geometry part of the kernel arguments; returns the LDS bytes of a workgroup
+static size_t dwl_fwd_plan(const DwShape& s, DwlFwdArgs* a) {
+    a->g = dwl_plan(s);
+    a->C = s.C; a->H = s.H; a->W = s.W; a->OH = s.OH; a->OW = s.OW; a->planes = s.N * s.C;
+    a->splits = s.N * a->g.NB;
+    a->RG = ceil_div(a->g.BR, s.stride == 1 ? kVR1 : kVR2);
+    a->g.stage_floats = (a->g.P * a->g.BR * s.OW + 3) & ~3;
+    a->x_floats = (a->g.rows_x * a->g.PWX + 3) & ~3;
+    a->w_magic = dwl_magic((unsigned)s.W); a->h_magic = dwl_magic((unsigned)s.H);
+    a->ow_magic = dwl_magic((unsigned)s.OW); a->rg_magic = dwl_magic((unsigned)a->RG);
+    return (size_t)(a->x_floats + a->g.stage_floats + a->g.P * kConst) * sizeof(float);
 }
 
-size_t depthwise_lds_partial_floats(const DwShape& s) {
-    if (!depthwise_lds_ok(s)) return 0;
-    const DwlGeom g = dwl_plan(s);
-    return std::max((size_t)s.C * s.N * g.NB * kPart, (size_t)s.C * depthwise_march_splits(s) * kPart);
-}
-
-bool depthwise_forward_lds(const float* x, const float* w, const float* bias, float* y, const DwShape& s, int act,
-                           ConvStats* stats, const DwBnIn* in) {
-    if (!depthwise_lds_ok(s) || !act_is_cheap(act) || act == BCNN_HIP_ACT_PRELU) return false;
-    if (in && (!in->mean || !act_is_cheap(in->act) || in->act == BCNN_HIP_ACT_PRELU)) return false;
-    if (depthwise_forward_march(x, w, bias, y, s, act, stats, in)) return true;  // rows of whole 16-byte groups
+bool depthwise_lds_fwd_takes(const DwFwdCall& c) {
     DwlFwdArgs a;
-    a.g = dwl_plan(s);
-    const int VR = s.stride == 1 ? kVR1 : kVR2;
-    a.x = x; a.w = w; a.bias = bias; a.y = y; a.stats = nullptr;
-    a.C = s.C; a.H = s.H; a.W = s.W; a.OH = s.OH; a.OW = s.OW; a.planes = s.N * s.C; a.act = act;
-    a.splits = s.N * a.g.NB;
-    a.RG = ceil_div(a.g.BR, VR);
-    a.g.stage_floats = (a.g.P * a.g.BR * s.OW + 3) & ~3;
-    a.x_floats = (a.g.rows_x * a.g.PWX + 3) & ~3;
-    a.w_magic = dwl_magic((unsigned)s.W); a.h_magic = dwl_magic((unsigned)s.H);
-    a.ow_magic = dwl_magic((unsigned)s.OW); a.rg_magic = dwl_magic((unsigned)a.RG);
-    if (stats) {
-        stats->splits = 0;
-        if (stats->partials && stats->capacity >= (size_t)s.C * a.splits * 2) {
-            a.stats = stats->partials;
-            stats->splits = a.splits;
-        }
-    }
-    const size_t lds = (size_t)(a.x_floats + a.g.stage_floats + a.g.P * kConst) * sizeof(float);
-    if (lds > 64 * 1024) return false;
+    return depthwise_lds_slots(c.s) && dwl_fwd_plan(c.s, &a) <= 64 * 1024;
+}
+
+void depthwise_lds_forward(const DwFwdCall& c) {
+    const DwShape& s = c.s;
+    DwlFwdArgs a;
+    const size_t lds = dwl_fwd_plan(s, &a);
+    a.x = c.x; a.w = c.w; a.bias = c.bias; a.y = c.y; a.act = c.act;
+    a.stats = dw_stats_slots(c.stats, s.C, a.splits);
+    a.in = c.in ? *c.in : DwBnIn{nullptr, nullptr, nullptr, nullptr, 0};
     const unsigned tiles = (unsigned)ceil_div((long long)a.planes, a.g.P) * (unsigned)a.g.NB;
-    if (in) {
-        a.in = *in;
+    if (c.in) {
         if (s.stride == 1) dwl_fwd_kernel<1, kVR1, true><<<tiles, 256, lds, current_stream()>>>(a);
         else dwl_fwd_kernel<2, kVR2, true><<<tiles, 256, lds, current_stream()>>>(a);
     } else {
-        a.in = DwBnIn{nullptr, nullptr, nullptr, nullptr, 0};
         if (s.stride == 1) dwl_fwd_kernel<1, kVR1, false><<<tiles, 256, lds, current_stream()>>>(a);
         else dwl_fwd_kernel<2, kVR2, false><<<tiles, 256, lds, current_stream()>>>(a);
     }
     KERNEL_CHECK();
-    return true;
 }
 
-size_t depthwise_lds_in_sums_floats(const DwShape& s) {
-    if (!depthwise_lds_ok(s)) return 0;
-    const DwlGeom g = dwl_plan(s);
-    return std::max((size_t)s.C * s.N * g.NB * 2, (size_t)s.C * depthwise_march_splits(s) * 2);
-}
-
-bool depthwise_backward_lds(const float* x, const float* w, const float* y, float* dy, float* dx, float* dw, float* dbias,
-                            const DwShape& s, int act, int overwrite, int write_back, const DwBnBwd* bn,
-                            const DwBnIn* in, ConvStats* in_sums) {
-    if (in_sums) in_sums->splits = 0;
-    if (!depthwise_lds_ok(s) || !act_bwd_is_cheap(act) || act == BCNN_HIP_ACT_PRELU || !dx) return false;
-    if (in && (!in->mean || !act_is_cheap(in->act) || in->act == BCNN_HIP_ACT_PRELU)) return false;
-    // Everything that can still refuse the layer is decided BEFORE dy is touched (a pre-pass followed by a refusal
-    // left the caller to apply the derivative a second time).
-    DwlBwdArgs a;
+// the geometry part of the kernel arguments and whether the kernel emits c.in_sums; returns the LDS bytes of a workgroup
+static size_t dwl_bwd_plan(const DwBwdCall& c, DwlBwdArgs* ap, bool* sums) {
+    const DwShape& s = c.s;
+    DwlBwdArgs& a = *ap;
     a.g = dwl_plan(s);
     const int S = s.stride, VR = S == 1 ? kVR1 : kVR2;
+    a.C = s.C; a.H = s.H; a.W = s.W; a.OH = s.OH; a.OW = s.OW; a.planes = s.N * s.C;
     a.splits = s.N * a.g.NB;
     a.RG = ceil_div(a.g.BR, VR);
     a.RGX = ceil_div(a.g.BR, 4);  // stride 1: a tile owns as many input rows as output rows
@@ -960,54 +930,44 @@ bool depthwise_backward_lds(const float* x, const float* w, const float* y, floa
     a.x_floats = (a.g.rows_x * a.g.PWX + 3) & ~3;
     if (a.x_floats < a.g.stage_floats) a.x_floats = a.g.stage_floats;  // the dx rows reuse the x image's space
     a.g_floats = (a.g.rows_g * a.g.PWG + 3) & ~3;
-    // the sums of the producer's batch-norm backward are of the COMPLETE gradient: only when this kernel is its sole writer;
-    // for producer activations whose derivative is 0 or 1 (noted as one bit per element while staging); tiles of several
-    // planes form g and g * (raw - mean) in LDS -- the dx piece and the g image's space, which then must hold a dx piece
-    bool want_sums = in && in_sums && in_sums->partials && overwrite &&
-                     (in->act == BCNN_HIP_ACT_NONE || in->act == BCNN_HIP_ACT_RELU) &&
-                     in_sums->capacity >= (size_t)s.C * a.splits * 2;
-    if (want_sums && a.g.P > 1 && a.g_floats < a.g.stage_floats) {  // stride 2
-        if ((size_t)(a.x_floats + a.g.stage_floats + a.g.P * kConst) * sizeof(float) <= 64 * 1024) a.g_floats = a.g.stage_floats;
-        else want_sums = false;
-    }
-    const size_t lds = (size_t)(a.x_floats + a.g_floats + a.g.P * kConst) * sizeof(float);
-    const bool lds_takes = lds <= 64 * 1024;
-    const bool march_takes = depthwise_backward_march_takes(x, y, dy, dx, s, act, bn, in);
-    if (!lds_takes && !march_takes) return false;
-    if (!bn && write_back && act != BCNN_HIP_ACT_NONE && act != BCNN_HIP_ACT_RELU && act != BCNN_HIP_ACT_CLAMP) {
-        // g = dy * act'(y) is written back over dy by the band that owns the row, while the neighbouring band reads the same
-        // row as its halo: harmless when applying the derivative twice changes nothing (a factor 0 or 1), a race otherwise
-        // (leaky ReLU: 0.01 instead of 0.1 on a band's edge row, whenever the owner happened to run first). Those
-        // activations get their own in-place pass first.
-        bcnn_hip_activation_backward(y, dy, (size_t)s.N * s.C * s.OH * s.OW, act, nullptr, nullptr, s.OH * s.OW, s.C);
-        act = BCNN_HIP_ACT_NONE;
-    }
-    if (march_takes) {
-        if (depthwise_backward_march(x, w, y, dy, dx, dw, dbias, s, act, overwrite, write_back, bn, in, in_sums)) return true;
-        fprintf(stderr, "[bcnn_hip] depthwise_backward_march refused a layer depthwise_backward_march_takes accepted\n");
-        exit(1);
-    }
-    a.x = x; a.w = w; a.y = y; a.dy = dy; a.dx = dx;
-    a.C = s.C; a.H = s.H; a.W = s.W; a.OH = s.OH; a.OW = s.OW; a.planes = s.N * s.C; a.act = act;
-    a.overwrite = overwrite; a.write_back = write_back;
     a.w_magic = dwl_magic((unsigned)s.W); a.h_magic = dwl_magic((unsigned)s.H);
     a.ow_magic = dwl_magic((unsigned)s.OW); a.oh_magic = dwl_magic((unsigned)s.OH);
     a.rg_magic = dwl_magic((unsigned)a.RG); a.rgx_magic = dwl_magic((unsigned)a.RGX);
     a.hw2_magic = dwl_magic((unsigned)((s.W + 1) >> 1));
     a.hw_magic = dwl_magic((unsigned)(s.H * s.W));
+    // in_sums: tiles of several planes form g and g * (raw - mean) in LDS -- the dx piece and the g image's space, which then must
+    // hold a dx piece (stride 2); where that does not fit the layer is still taken, without the sums
+    *sums = dw_in_sums_wanted(c) && c.in_sums->partials && c.in_sums->capacity >= (size_t)s.C * a.splits * 2;
+    if (*sums && a.g.P > 1 && a.g_floats < a.g.stage_floats) {
+        if ((size_t)(a.x_floats + a.g.stage_floats + a.g.P * kConst) * sizeof(float) <= 64 * 1024) a.g_floats = a.g.stage_floats;
+        else *sums = false;
+    }
+    return (size_t)(a.x_floats + a.g_floats + a.g.P * kConst) * sizeof(float);
+}
+
+bool depthwise_lds_bwd_takes(const DwBwdCall& c) {
+    DwlBwdArgs a;
+    bool sums;
+    return depthwise_lds_slots(c.s) && dwl_bwd_plan(c, &a, &sums) <= 64 * 1024;
+}
+
+void depthwise_lds_backward(const DwBwdCall& c) {
+    const DwShape& s = c.s;
+    const DwBnBwd* bn = c.bn;
+    const DwBnIn* in = c.in;
+    DwlBwdArgs a;
+    bool sums;
+    const size_t lds = dwl_bwd_plan(c, &a, &sums);
+    a.x = c.x; a.w = c.w; a.y = c.y; a.dy = c.dy; a.dx = c.dx; a.act = c.act;
+    a.overwrite = c.overwrite; a.write_back = c.write_back;
     a.fM = (float)((long long)s.N * s.OH * s.OW);
     a.rfM = 1.0f / a.fM;  // host division: IEEE, round to nearest
-    if (bn) a.bn = *bn;
-    else a.bn = DwBnBwd{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    a.partials = scratch(SCRATCH_REDUCE, (size_t)s.C * a.splits * kPart);
-    a.in_sums = nullptr;
-    if (want_sums) {
-        a.in_sums = in_sums->partials;
-        in_sums->splits = a.splits;
-    }
+    a.bn = bn ? *bn : DwBnBwd{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    a.in = in ? *in : DwBnIn{nullptr, nullptr, nullptr, nullptr, 0};
+    a.partials = c.partials;
+    a.in_sums = sums ? dw_stats_slots(c.in_sums, s.C, a.splits) : nullptr;
     const unsigned tiles = (unsigned)ceil_div((long long)a.planes, a.g.P) * (unsigned)a.g.NB;
     hipStream_t st = current_stream();
-    a.in = in ? *in : DwBnIn{nullptr, nullptr, nullptr, nullptr, 0};
 #define DWL_LAUNCH(SV, VRV)                                                                     \
     do {                                                                                        \
         if (bn && in) dwl_bwd_kernel<SV, VRV, true, true><<<tiles, 256, lds, st>>>(a);          \
@@ -1015,13 +975,11 @@ bool depthwise_backward_lds(const float* x, const float* w, const float* y, floa
         else if (in) dwl_bwd_kernel<SV, VRV, false, true><<<tiles, 256, lds, st>>>(a);          \
         else dwl_bwd_kernel<SV, VRV, false, false><<<tiles, 256, lds, st>>>(a);                 \
     } while (0)
-    if (S == 1) DWL_LAUNCH(1, kVR1);
+    if (s.stride == 1) DWL_LAUNCH(1, kVR1);
     else DWL_LAUNCH(2, kVR2);
 #undef DWL_LAUNCH
     KERNEL_CHECK();
-    dwl_finalize_kernel<<<s.C, 256, 0, st>>>(a.partials, a.splits, dw, dbias);
-    KERNEL_CHECK();
-    return true;
+    dwl_finalize_launch(a.partials, a.splits, s.C, c.dw, c.dbias, st);
 }
 
 }  // namespace bcnn_hip

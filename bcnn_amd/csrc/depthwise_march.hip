@@ -446,7 +446,7 @@ __global__ __launch_bounds__(256, DWM_FWD_WAVES) void dwm_fwd_kernel(const DwmFw
 // ================================================================================================
 // backward
 // ================================================================================================
-constexpr int kDwmPart = 12;  // partial layout of depthwise_lds.hip's finalize: nine taps, bias sum, two unused
+constexpr int kDwmPart = kDwPartFloats;  // partial layout of dwl_finalize_launch: nine taps, bias sum, two unused
 
 struct DwmBwdArgs {
     const float* x;
@@ -728,7 +728,7 @@ inline bool dwm_aligned(int V, std::initializer_list<const void*> ptrs) {
 
 }  // namespace
 
-bool depthwise_march_ok(const DwShape& s) {
+static bool dwm_ok(const DwShape& s) {
     static const int on = BCNN_EXP_ENV("BCNN_HIP_NO_DW_MARCH") ? 0 : 1;  // A/B switch (experiment build only)
     if (!on || !dwm_shape_ok(s)) return false;
     const DwmGeom g = dwm_plan(s);
@@ -737,29 +737,27 @@ bool depthwise_march_ok(const DwShape& s) {
 
 // slots per channel of the statistics / sums / weight-gradient partials (N * bands per plane)
 size_t depthwise_march_splits(const DwShape& s) {
-    if (!depthwise_march_ok(s)) return 0;
+    if (!dwm_ok(s)) return 0;
     const DwmGeom g = dwm_plan(s);
     return (size_t)dwm_splits(s, g);
 }
 
-bool depthwise_forward_march(const float* x, const float* w, const float* bias, float* y, const DwShape& s, int act,
-                             ConvStats* stats, const DwBnIn* in) {
-    if (!depthwise_march_ok(s) || !act_is_cheap(act) || act == BCNN_HIP_ACT_PRELU) return false;
-    if (in && (!in->mean || !act_is_cheap(in->act) || in->act == BCNN_HIP_ACT_PRELU)) return false;
+bool depthwise_march_fwd_takes(const DwFwdCall& c) {
+    if (!dwm_ok(c.s)) return false;
+    const DwmGeom g = dwm_plan(c.s);
+    return dwm_aligned(g.V, {c.x}) && dwm_aligned(c.s.stride == 1 ? g.V : g.V / 2, {c.y});
+}
+
+void depthwise_march_forward(const DwFwdCall& c) {
+    const DwShape& s = c.s;
+    const DwBnIn* in = c.in;
+    const int act = c.act;
     DwmFwdArgs a;
     a.g = dwm_plan(s);
-    if (!dwm_aligned(a.g.V, {x}) || !dwm_aligned(s.stride == 1 ? a.g.V : a.g.V / 2, {y})) return false;
-    a.x = x; a.w = w; a.bias = bias; a.y = y; a.stats = nullptr;
+    a.x = c.x; a.w = c.w; a.bias = c.bias; a.y = c.y;
     a.N = s.N; a.C = s.C; a.H = s.H; a.W = s.W; a.OH = s.OH; a.OW = s.OW; a.act = act;
     a.xbytes = (unsigned)((size_t)s.N * s.C * s.H * s.W * 4); a.ybytes = (unsigned)((size_t)s.N * s.C * s.OH * s.OW * 4);
-    const int splits = dwm_splits(s, a.g);
-    if (stats) {
-        stats->splits = 0;
-        if (stats->partials && stats->capacity >= (size_t)s.C * splits * 2) {
-            a.stats = stats->partials;
-            stats->splits = splits;
-        }
-    }
+    a.stats = dw_stats_slots(c.stats, s.C, dwm_splits(s, a.g));
     a.in = in ? *in : DwBnIn{nullptr, nullptr, nullptr, nullptr, 0};
     const unsigned waves = dwm_waves(a.g, (long long)s.N * s.C), blocks = (waves + 3) / 4;
     hipStream_t st = current_stream();
@@ -806,43 +804,33 @@ bool depthwise_forward_march(const float* x, const float* w, const float* bias, 
 #undef DWM_FWD
 #undef DWM_FWD_PF
     KERNEL_CHECK();
-    return true;
 }
 
-// every condition under which depthwise_backward_march launches nothing (a caller that has to prepare dy asks first)
-bool depthwise_backward_march_takes(const float* x, const float* y, const float* dy, const float* dx, const DwShape& s, int act,
-                                    const DwBnBwd* bn, const DwBnIn* in) {
-    if (!depthwise_march_ok(s) || !act_bwd_is_cheap(act) || act == BCNN_HIP_ACT_PRELU || !dx) return false;
-    if (in && (!in->mean || !act_is_cheap(in->act) || in->act == BCNN_HIP_ACT_PRELU)) return false;
-    const DwmGeom g = dwm_plan(s);
-    return dwm_aligned(g.V, {x, dx}) && dwm_aligned(s.stride == 1 ? g.V : g.V / 2, {y, dy, bn ? bn->dz : nullptr});
+bool depthwise_march_bwd_takes(const DwBwdCall& c) {
+    if (!dwm_ok(c.s)) return false;
+    const DwmGeom g = dwm_plan(c.s);
+    return dwm_aligned(g.V, {c.x, c.dx}) &&
+           dwm_aligned(c.s.stride == 1 ? g.V : g.V / 2, {c.y, c.dy, c.bn ? c.bn->dz : nullptr});
 }
 
-bool depthwise_backward_march(const float* x, const float* w, const float* y, float* dy, float* dx, float* dw, float* dbias,
-                              const DwShape& s, int act, int overwrite, int write_back, const DwBnBwd* bn, const DwBnIn* in,
-                              ConvStats* in_sums) {
-    if (in_sums) in_sums->splits = 0;
-    if (!depthwise_backward_march_takes(x, y, dy, dx, s, act, bn, in)) return false;
+void depthwise_march_backward(const DwBwdCall& c) {
+    const DwShape& s = c.s;
+    const DwBnBwd* bn = c.bn;
+    const DwBnIn* in = c.in;
+    const int act = c.act, overwrite = c.overwrite;
     DwmBwdArgs a;
     a.g = dwm_plan(s);
-    a.x = x; a.w = w; a.y = y; a.dy = dy; a.dx = dx;
+    a.x = c.x; a.w = c.w; a.y = c.y; a.dy = c.dy; a.dx = c.dx;
     a.N = s.N; a.C = s.C; a.H = s.H; a.W = s.W; a.OH = s.OH; a.OW = s.OW; a.act = act;
-    a.overwrite = overwrite; a.write_back = write_back;
+    a.overwrite = overwrite; a.write_back = c.write_back;
     a.xbytes = (unsigned)((size_t)s.N * s.C * s.H * s.W * 4); a.ybytes = (unsigned)((size_t)s.N * s.C * s.OH * s.OW * 4);
     a.fM = (float)((long long)s.N * s.OH * s.OW);
     a.rfM = 1.0f / a.fM;  // host division: IEEE, round to nearest
     a.bn = bn ? *bn : DwBnBwd{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     a.in = in ? *in : DwBnIn{nullptr, nullptr, nullptr, nullptr, 0};
     const int splits = dwm_splits(s, a.g);
-    a.partials = scratch(SCRATCH_REDUCE, (size_t)s.C * splits * kDwmPart);
-    a.in_sums = nullptr;
-    // the sums of the producer's batch-norm backward are of the COMPLETE gradient: only when this kernel is its sole writer,
-    // and for producer activations whose derivative is 0 or 1
-    if (in && in_sums && in_sums->partials && overwrite && (in->act == BCNN_HIP_ACT_NONE || in->act == BCNN_HIP_ACT_RELU) &&
-        in_sums->capacity >= (size_t)s.C * splits * 2) {
-        a.in_sums = in_sums->partials;
-        in_sums->splits = splits;
-    }
+    a.partials = c.partials;
+    a.in_sums = dw_in_sums_wanted(c) ? dw_stats_slots(c.in_sums, s.C, splits) : nullptr;
     const unsigned waves = dwm_waves(a.g, (long long)s.N * s.C), blocks = (waves + 3) / 4;
     hipStream_t st = current_stream();
     trace_kernel(bn && in ? "dwm_bwd_kernel:bn+bnin" : bn ? "dwm_bwd_kernel:bn" : in ? "dwm_bwd_kernel:bnin" : "dwm_bwd_kernel");
@@ -878,8 +866,7 @@ bool depthwise_backward_march(const float* x, const float* w, const float* y, fl
 #undef DWM_LAUNCH_R
 #undef DWM_LAUNCH_O
     KERNEL_CHECK();
-    dwl_finalize_launch(a.partials, splits, s.C, dw, dbias, st);
-    return true;
+    dwl_finalize_launch(a.partials, splits, s.C, c.dw, c.dbias, st);
 }
 
 }  // namespace bcnn_hip

@@ -117,3 +117,32 @@ def test_the_workspace_check_has_one_copy():
     for p in glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h")):
         n += open(p).read().count("workspace too small")
     assert n == 1
+
+
+def _identifiers(fn):
+    return set(re.findall(r"[A-Za-z_]\w*", _blank(_strip_comments(open(os.path.join(CSRC, fn)).read()))))
+
+
+def test_the_fused_depthwise_families_do_not_know_each_other():
+    """depthwise.hip's two tables order the families; of the other family's file only dwl_finalize_launch is called"""
+    lds, march = _identifiers("depthwise_lds.hip"), _identifiers("depthwise_march.hip")
+    assert not [i for i in lds if re.search(r"march", i, re.I)]
+    assert not [i for i in march if re.search(r"depthwise_\w*lds", i)]
+    defined = {f[0] for f in _functions(_strip_comments(open(os.path.join(CSRC, "depthwise_lds.hip")).read()))
+               if f[1] == "def" and not f[2] and not f[4]}
+    assert "dwl_finalize_launch" in defined and defined & march == {"dwl_finalize_launch"}
+
+
+def test_the_depthwise_shape_is_derived_once():
+    """the output-extent formula of a DwShape, and who may ask the marching family for its slots"""
+    n, splits = 0, set()
+    for p in glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.h")):
+        text = _strip_comments(open(p).read())
+        n += len(re.findall(r"DwShape\s*\w*\s*\{[^{};]*/\s*\w+\s*\+\s*1", text))
+        if re.search(r"\bdepthwise_march_splits\b", text):
+            splits.add(os.path.basename(p))
+    assert n == 1
+    assert splits == {"depthwise_march.hip", "depthwise.h", "depthwise.hip"}
+    table = _strip_comments(open(os.path.join(CSRC, "depthwise.hip")).read())
+    rows = re.findall(r"kDw(?:Fwd|Bwd)Families\[\]\s*=\s*\{(.*?)\n\};", table, re.S)
+    assert len(rows) == 2 and table.count("depthwise_march_splits") == sum(r.count("depthwise_march_splits") for r in rows) == 2
