@@ -154,9 +154,10 @@ static const void* prepack_table(PrepackStore& st, int kind, int mode, const voi
 // ---- which kernel takes a layer --------------------------------------------------------------------------------------
 // Every family is tried in a fixed order and says for itself whether the shape, and the alignment of what it is handed, is
 // its own (conv_paths.h):
-//   forward          window, stem, direct, winograd43 (raw only), winograd_fused, winograd; then, inside
-//                    conv_forward_dispatch, dma, small_c, the register-staged kernel
-//   data gradient    winograd43, winograd_fused, winograd; then, inside conv_backward_data, small_c, dma, register-staged
+//   forward          window, stem, direct, winograd43 (raw only), winograd_fused, winograd, large (kernels > 7x7); then,
+//                    inside conv_forward_dispatch, dma, small_c, the register-staged kernel
+//   data gradient    winograd43, winograd_fused, winograd, large; then, inside conv_backward_data, small_c, dma,
+//                    register-staged
 //   weight gradient  the rows of kDwFamilies
 // bcnn_hip_conv_prepack below walks the first two for the families that read packed weights (the fused Winograd kernels and
 // dma); the others read the weights as they are or, the three-kernel Winograd, transform them in a kernel of their own.
@@ -171,6 +172,7 @@ static void conv_fwd_any(const float* x, const float* w, const float* bias, cons
     if (raw && conv_forward_winograd43(x, w, y, s, raw, stats)) return;
     if (conv_forward_winograd_fused(x, w, bias, slopes, y, s, act, raw, stats)) return;
     if (conv_forward_winograd(x, w, bias, slopes, y, s, act, raw, stats)) return;
+    if (conv_forward_large(x, w, bias, slopes, y, s, act, raw, stats)) return;
     conv_forward_dispatch(x, w, bias, slopes, y, s, act, raw, stats);
 }
 
@@ -178,6 +180,7 @@ static void conv_dx_any(const float* w, const float* dy, float* dx, const ConvSh
     if (conv_backward_data_winograd43(w, dy, dx, s)) return;
     if (conv_backward_data_winograd_fused(w, dy, dx, s)) return;
     if (conv_backward_data_winograd(w, dy, dx, s)) return;
+    if (conv_backward_data_large(w, dy, dx, s)) return;
     conv_backward_data(w, dy, dx, s, bs);
 }
 
@@ -198,6 +201,7 @@ static const DwFamily kDwFamilies[] = {
     {conv_dw_winograd_workspace_floats, conv_backward_weights_winograd, GATE_NONE},
     {conv_dw_dma_workspace_floats, conv_backward_weights_dma_timed, GATE_DMA},
     {conv_dw_small_c_workspace_floats, conv_backward_weights_small_c, GATE_DMA},
+    {conv_dw_large_workspace_floats, conv_backward_weights_large, GATE_NONE},
     {conv_dw_workspace_floats, conv_backward_weights, GATE_NONE},  // takes every shape
 };
 }  // namespace bcnn_hip
@@ -237,6 +241,8 @@ void bcnn_hip_conv_prepack(const bcnn_hip_conv_desc* layers, int count, int data
             wj.push_back(w1);
         } else if (conv_winograd_unfused_takes(s)) {
             continue;  // transforms its weights inside its own first kernel
+        } else if (conv_large_takes(s)) {
+            continue;  // reads the weights as they are
         } else if (mode == 1 && conv_dx_small_c_takes(s)) {
             continue;
         } else if (dma_pack_plan(s, mode, &i1, &floats)) {

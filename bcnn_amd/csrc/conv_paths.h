@@ -24,6 +24,10 @@ bool conv_forward_winograd_fused(const float* x, const float* w, const float* bi
 // conv_winograd.hip: F(2x2, 3x3) as three kernels for the deep 3x3 / s1 layers
 bool conv_forward_winograd(const float* x, const float* w, const float* bias, const float* slopes, float* y, const ConvShape& s,
                            int act, int raw, ConvStats* stats);
+// conv_large.hip: every non-pointwise layer with a kernel larger than 7x7 (the three directions; reads w as it is)
+bool conv_large_takes(const ConvShape& s);
+bool conv_forward_large(const float* x, const float* w, const float* bias, const float* slopes, float* y, const ConvShape& s,
+                        int act, int raw, ConvStats* stats);
 // conv_igemm.hip: the LDS-DMA GEMM, the few-channel padded-plane GEMM, else the register-staged kernel (takes every shape)
 void conv_forward_dispatch(const float* x, const float* w, const float* bias, const float* slopes, float* y, const ConvShape& s,
                            int act, int raw, ConvStats* stats);
@@ -43,6 +47,7 @@ void conv_prefetch_input(const float* x, const ConvShape& s, float* sink);
 bool conv_backward_data_winograd43(const float* w, const float* dy, float* dx, const ConvShape& s);       // conv_winograd43.hip
 bool conv_backward_data_winograd_fused(const float* w, const float* dy, float* dx, const ConvShape& s);  // conv_winograd_fused.hip
 bool conv_backward_data_winograd(const float* w, const float* dy, float* dx, const ConvShape& s);        // conv_winograd.hip
+bool conv_backward_data_large(const float* w, const float* dy, float* dx, const ConvShape& s);           // conv_large.hip
 // conv_igemm.hip: the few-channel col2im form, the LDS-DMA GEMM, else the register-staged kernel (takes every shape).
 // bs (optional): the backward sums of a batch-norm node in front, emitted by the kernels that can (bs->splits > 0)
 void conv_backward_data(const float* w, const float* dy, float* dx, const ConvShape& s, DxBnSums* bs = nullptr);
@@ -51,7 +56,7 @@ bool conv_backward_data_dma(const float* w, const float* dy, float* dx, const Co
 
 // ---- weight gradient: dw += dy (x) x, one signature for every family (the rows of kDwFamilies, conv.hip). `workspace` takes
 // the split partials and is checked against the family's own *_workspace_floats(s) (0: not its shape); *bias_done is set when
-// the family accumulated dbias as well: the first three and the last can, and do for dbias != nullptr. Each times itself ------
+// the family accumulated dbias as well: the first three and the last two can, and do for dbias != nullptr. Each times itself ------
 size_t conv_dw_window_workspace_floats(const ConvShape& s);  // conv_window.hip: 3x3 / s1 layers with K <= 27
 bool conv_backward_weights_window(const float* x, const float* dy, float* dw, float* dbias, const ConvShape& s,
                                   float* workspace, size_t workspace_floats, bool* bias_done);
@@ -76,6 +81,9 @@ bool conv_backward_weights_dma_timed(const float* x, const float* dy, float* dw,
 size_t conv_dw_small_c_workspace_floats(const ConvShape& s);  // conv_dw_dma.hip: few input channels, one GEMM
 bool conv_backward_weights_small_c(const float* x, const float* dy, float* dw, float* dbias, const ConvShape& s,
                                    float* workspace, size_t workspace_floats, bool* bias_done);
+size_t conv_dw_large_workspace_floats(const ConvShape& s);  // conv_large.hip: kernels larger than 7x7
+bool conv_backward_weights_large(const float* x, const float* dy, float* dw, float* dbias, const ConvShape& s,
+                                 float* workspace, size_t workspace_floats, bool* bias_done);
 size_t conv_dw_workspace_floats(const ConvShape& s);  // conv_bwd.hip: register-staged, takes every shape
 bool conv_backward_weights(const float* x, const float* dy, float* dw, float* dbias, const ConvShape& s,
                            float* workspace, size_t workspace_floats, bool* bias_done);
