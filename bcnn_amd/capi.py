@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("BCNN_LIB", os.path.join(_HERE, "lib", "libbcnn.so"))  # override: experiment build
 
 MODE_PREDICT, MODE_TRAIN, MODE_VALID = 0, 1, 2
+PRECISION_FP32, PRECISION_BF16 = 0, 1
 (ACT_NONE, ACT_TANH, ACT_RELU, ACT_RAMP, ACT_SOFTPLUS, ACT_LRELU, ACT_ABS, ACT_CLAMP, ACT_PRELU,
  ACT_LOGISTIC) = range(10)
 PADDING_SAME, PADDING_VALID, PADDING_CAFFE = 0, 1, 2
@@ -95,6 +96,7 @@ def lib():
         "bcnn_upload_tensor": (i, [vp, i, i]), "bcnn_download_tensor": (i, [vp, i, i]),
         "bcnn_set_data_parallel": (i, [vp, i, i]), "bcnn_set_data_parallel_comm": (i, [vp, i, i, cp]),
         "bcnn_set_weight_gradient_stream": (None, [vp, i]),
+        "bcnn_set_inference_precision": (i, [vp, i]), "bcnn_get_inference_precision": (i, [vp]),
         "bcnn_set_gradient_ready_callback": (None, [vp, vp, vp]),
         "bcnn_get_gradient_arena": (vp, [vp, C.POINTER(sz)]), "bcnn_get_parameter_arena": (vp, [vp, C.POINTER(sz)]),
         "bcnn_synchronize": (None, [vp]), "bcnn_peek_tensor": (tp, [vp, i]), "bcnn_get_num_nodes": (i, [vp]),
@@ -232,6 +234,15 @@ class Net:
 
     def set_mode(self, mode):
         return self.L.bcnn_set_mode(self.net, mode)
+
+    def set_inference_precision(self, precision):
+        """bcnn_set_inference_precision: PRECISION_BF16 runs every convolution node of a PREDICT / VALID forward on the
+        bf16 matrix cores (fp32 accumulator; depthwise, deconvolution and full-connected nodes stay fp32); a TRAIN-mode
+        pass is never affected. Returns the bcnn_status (1 = BCNN_INVALID_PARAMETER for an unknown value)."""
+        return self.L.bcnn_set_inference_precision(self.net, precision)
+
+    def get_inference_precision(self):
+        return self.L.bcnn_get_inference_precision(self.net)
 
     def compile(self):
         assert self.L.bcnn_compile_net(self.net) == 0

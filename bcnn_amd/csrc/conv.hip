@@ -155,16 +155,22 @@ static const void* prepack_table(PrepackStore& st, int kind, int mode, const voi
 // Every family is tried in a fixed order and says for itself whether the shape, and the alignment of what it is handed, is
 // its own (conv_paths.h):
 //   forward          window, stem, direct, winograd43 (raw only), winograd_fused, winograd, large (kernels > 7x7); then,
-//                    inside conv_forward_dispatch, dma, small_c, the register-staged kernel
+//                    inside conv_forward_dispatch, dma, small_c, the register-staged kernel. The opt-in bf16 forward
+//                    (bcnn_hip_conv_forward_bf16) is one family for every shape: conv_forward_bf16
 //   data gradient    winograd43, winograd_fused, winograd, large; then, inside conv_backward_data, small_c, dma,
 //                    register-staged
 //   weight gradient  the rows of kDwFamilies
 // bcnn_hip_conv_prepack below walks the first two for the families that read packed weights (the fused Winograd kernels and
 // dma); the others read the weights as they are or, the three-kernel Winograd, transform them in a kernel of their own.
 // A new family is a line or a row here and its declaration in conv_paths.h.
+// bf16: the caller asked for the reduced-precision forward (bcnn_hip_conv_forward_bf16): one family takes every shape.
 static void conv_fwd_any(const float* x, const float* w, const float* bias, const float* slopes, float* y,
-                         const ConvShape& s, int act, int raw, ConvStats* stats = nullptr) {
+                         const ConvShape& s, int act, int raw, ConvStats* stats = nullptr, bool bf16 = false) {
     if (stats) stats->splits = 0;
+    if (bf16) {
+        conv_forward_bf16(x, w, bias, slopes, y, s, act, raw, stats);
+        return;
+    }
     static const int window_on = BCNN_EXP_ENV("BCNN_HIP_NO_WINDOW") ? 0 : 1;  // A/B switch: the LDS-free kernels instead
     if (window_on && conv_forward_window(x, w, bias, slopes, y, s, act, raw)) return;
     if (window_on && conv_forward_stem(x, w, bias, slopes, y, s, act, raw, stats)) return;
@@ -285,7 +291,7 @@ static void conv_forward_impl(const float* x, const float* w, const float* bias,
                               int wd, int f, int k, int stride, int pad, int groups, int act, const float* slopes,
                               int batch_norm, float* run_mean, float* run_var, const float* scales,
                               float* saved_mean, float* saved_var, float* x_norm, float* bn_workspace, int mode,
-                              const BnResidual* res, float* res_out, bool stats_only = false) {
+                              const BnResidual* res, float* res_out, bool stats_only = false, bool bf16 = false) {
     const ConvShape s = make_conv_shape(n, c, h, wd, f, k, stride, pad, groups);
     const BnFold fold = take_fold();  // announced by bcnn_hip_conv_set_input_bnfold: x then is the batch-norm's INPUT
     if (fold.mean && (!batch_norm || mode != BCNN_HIP_MODE_TRAIN || !bnfold_shape_ok(s))) {
@@ -295,9 +301,9 @@ static void conv_forward_impl(const float* x, const float* w, const float* bias,
     }
     if (!batch_norm) {
         if (act_is_cheap(act)) {
-            conv_fwd_any(x, w, bias, slopes, y, s, act, /*raw=*/0);
+            conv_fwd_any(x, w, bias, slopes, y, s, act, /*raw=*/0, nullptr, bf16);
         } else {  // tanh / softplus / logistic: bias in the epilogue, activation as a second in-place pass
-            conv_fwd_any(x, w, bias, slopes, y, s, BCNN_HIP_ACT_NONE, /*raw=*/0);
+            conv_fwd_any(x, w, bias, slopes, y, s, BCNN_HIP_ACT_NONE, /*raw=*/0, nullptr, bf16);
             bcnn_hip_activation_forward(y, (size_t)n * f * s.OHOW, act, slopes, s.OHOW, f);
         }
         return;
@@ -331,7 +337,7 @@ static void conv_forward_impl(const float* x, const float* w, const float* bias,
             exit(1);
         }
     } else {
-        conv_fwd_any(x, w, nullptr, nullptr, raw, s, BCNN_HIP_ACT_NONE, /*raw=*/1, st.partials ? &st : nullptr);
+        conv_fwd_any(x, w, nullptr, nullptr, raw, s, BCNN_HIP_ACT_NONE, /*raw=*/1, st.partials ? &st : nullptr, bf16);
     }
     const int fused_act = (act == BCNN_HIP_ACT_PRELU) ? BCNN_HIP_ACT_NONE : act;
     // x_norm is not materialised on this path: the backward pass recomputes it from the raw convolution
@@ -359,6 +365,19 @@ void bcnn_hip_conv_forward(const float* x, const float* w, const float* bias, fl
                            float* saved_mean, float* saved_var, float* x_norm, float* bn_workspace, int mode) {
     conv_forward_impl(x, w, bias, y, n, c, h, wd, f, k, stride, pad, groups, act, slopes, batch_norm, run_mean, run_var,
                       scales, saved_mean, saved_var, x_norm, bn_workspace, mode, nullptr, nullptr);
+}
+
+// bcnn_hip_conv_forward with the convolution itself on the bf16 matrix cores (conv_bf16.hip); everything behind the
+// accumulator -- bias, fused batch-norm apply, activation passes -- is conv_forward_impl's own code. Inference only.
+int bcnn_hip_conv_forward_bf16(const float* x, const float* w, const float* bias, float* y, int n, int c, int h,
+                               int wd, int f, int k, int stride, int pad, int groups, int act, const float* slopes,
+                               int batch_norm, float* run_mean, float* run_var, const float* scales,
+                               float* saved_mean, float* saved_var, float* x_norm, float* bn_workspace, int mode) {
+    if (mode != BCNN_HIP_MODE_PREDICT && mode != BCNN_HIP_MODE_VALID) return 0;
+    conv_forward_impl(x, w, bias, y, n, c, h, wd, f, k, stride, pad, groups, act, slopes, batch_norm, run_mean, run_var,
+                      scales, saved_mean, saved_var, x_norm, bn_workspace, mode, nullptr, nullptr, /*stats_only=*/false,
+                      /*bf16=*/true);
+    return 1;
 }
 
 // The convolution and the batch statistics (saved / running) of bcnn_hip_conv_forward, TRAIN mode, WITHOUT the apply sweep:

@@ -136,6 +136,18 @@ __device__ __forceinline__ f32x16 mfma32(float a, float b, f32x16 c) {
 __device__ __forceinline__ int mfma_row(int r, int lane) {
     return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
 }
+// What a forward GEMM kernel stores for accumulator v of output channel fc: the bias (bcnn_add_scalar of the AVX build
+// skips exactly 0 and 1: quirk 2), then a cheap activation. One copy for the fp32 kernels (conv_igemm.hip,
+// conv_large.hip) and the bf16 one (conv_bf16.hip): equal accumulators give equal bits.
+__device__ __forceinline__ float conv_store_value(float v, int fc, const float* bias, int add_bias, int act,
+                                                  const float* slopes) {
+    if (add_bias) {
+        const float b = bias[fc];
+        if (b != 0.0f && b != 1.0f) v += b;
+    }
+    if (act != BCNN_HIP_ACT_NONE) v = act_fwd_cheap(v, act, act == BCNN_HIP_ACT_PRELU ? slopes[fc] : 0.f);
+    return v;
+}
 #endif
 
 }  // namespace bcnn_hip

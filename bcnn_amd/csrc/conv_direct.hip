@@ -321,6 +321,7 @@ bool conv_forward_direct(const float* x, const float* w, const float* bias, cons
     const int ks = (s.K + 1) / 2;
     const int tm = (s.Mg <= 32) ? 1 : 2;
     KTimer kt(K_CONV_FWD, conv_gemm_flops(s), conv_gemm_bytes(s));
+    trace_kernel("conv_fwd_direct_kernel");
     conv_prefetch_input(x, s, y);
     const int actm = (a.act == BCNN_HIP_ACT_NONE) ? 0 : (a.act == BCNN_HIP_ACT_RELU ? 1 : 2);
 #define LAUNCH(TMv, KSv, KZ)                                                                            \

@@ -275,15 +275,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const IgemmArgs a) {
                 const int m = m0 + (wm * TM + i) * 32 + mfma_row(r, lane);
                 if (m >= a.M) continue;
                 float v = acc[i][j][r];
-                if (fwd) {
-                    const int fc = g * s.Mg + m;
-                    if (a.add_bias) {
-                        const float b = a.bias[fc];
-                        if (b != 0.0f && b != 1.0f) v += b;  // bcnn_add_scalar (AVX build) skips exactly 0 and 1
-                    }
-                    if (a.act != BCNN_HIP_ACT_NONE)
-                        v = act_fwd_cheap(v, a.act, a.act == BCNN_HIP_ACT_PRELU ? a.slopes[fc] : 0.f);
-                }
+                if (fwd) v = conv_store_value(v, g * s.Mg + m, a.bias, a.add_bias, a.act, a.slopes);
                 a.out[(size_t)ob + (size_t)m * o_row_stride] = v;
             }
         }
@@ -326,6 +318,7 @@ void conv_forward_dispatch(const float* x, const float* w, const float* bias, co
     KTimer kt(K_CONV_FWD, conv_gemm_flops(s), conv_gemm_bytes(s));
     if (dma_enabled() && conv_forward_dma(x, w, bias, slopes, y, s, act, raw, stats)) return;
     if (dma_enabled() && conv_forward_small_c(x, w, bias, slopes, y, s, act, raw, stats)) return;
+    trace_kernel("conv_igemm_kernel:fwd");
     IgemmArgs a;
     a.a_base = w; a.b_base = x; a.out = y; a.bias = bias; a.slopes = slopes; a.s = s;
     a.mode = 0;

@@ -247,15 +247,7 @@ __global__ __launch_bounds__(256) void conv_large_gemm_kernel(const LargeArgs a)
                 const int m = m0 + (wm * TM + i) * 32 + mfma_row(r, lane);
                 if (m >= a.M) continue;
                 float v = acc[i][j][r];
-                if (fwd) {
-                    const int fc = g * s.Mg + m;
-                    if (a.add_bias) {
-                        const float b = a.bias[fc];
-                        if (b != 0.0f && b != 1.0f) v += b;  // bcnn_add_scalar (AVX build) skips exactly 0 and 1
-                    }
-                    if (a.act != BCNN_HIP_ACT_NONE)
-                        v = act_fwd_cheap(v, a.act, a.act == BCNN_HIP_ACT_PRELU ? a.slopes[fc] : 0.f);
-                }
+                if (fwd) v = conv_store_value(v, g * s.Mg + m, a.bias, a.add_bias, a.act, a.slopes);
                 a.out[(size_t)ob + (size_t)m * o_row_stride] = v;
             }
         }

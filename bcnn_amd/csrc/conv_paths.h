@@ -28,6 +28,9 @@ bool conv_forward_winograd(const float* x, const float* w, const float* bias, co
 bool conv_large_takes(const ConvShape& s);
 bool conv_forward_large(const float* x, const float* w, const float* bias, const float* slopes, float* y, const ConvShape& s,
                         int act, int raw, ConvStats* stats);
+// conv_bf16.hip: the opt-in inference forward on the bf16 matrix cores, fp32 accumulator (takes every shape)
+bool conv_forward_bf16(const float* x, const float* w, const float* bias, const float* slopes, float* y, const ConvShape& s,
+                       int act, int raw, ConvStats* stats);
 // conv_igemm.hip: the LDS-DMA GEMM, the few-channel padded-plane GEMM, else the register-staged kernel (takes every shape)
 void conv_forward_dispatch(const float* x, const float* w, const float* bias, const float* slopes, float* y, const ConvShape& s,
                            int act, int raw, ConvStats* stats);

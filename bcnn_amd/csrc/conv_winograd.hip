@@ -334,6 +334,7 @@ bool conv_forward_winograd(const float* x, const float* w, const float* bias, co
                            const ConvShape& s, int act, int raw, ConvStats* stats) {
     if (!wino_applicable(s) || !wino_profitable(s)) return false;
     KTimer kt(K_CONV_FWD_WINO, wino_flops(s), conv_gemm_bytes(s), wino_useful_flops(s));
+    trace_kernel("wino_unfused:fwd");
     const bool plain = raw || (bias == nullptr && act == BCNN_HIP_ACT_NONE);
     // raw output for a fused batch-norm: the output transform also emits the per-channel statistics partials
     // (ceil(T / 256) <= ceil(N*OH*OW / 64) entries per channel: inside the buffer conv.hip sized)

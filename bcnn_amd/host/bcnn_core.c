@@ -696,6 +696,16 @@ void bcnn_backward(bcnn_net *net) {
 
 void bcnn_set_weight_gradient_stream(bcnn_net *net, int enable) { hctx(net)->no_side_stream = enable ? 0 : 1; }
 
+bcnn_status bcnn_set_inference_precision(bcnn_net *net, bcnn_precision p) {
+    if (!net || (p != BCNN_PRECISION_FP32 && p != BCNN_PRECISION_BF16)) return BCNN_INVALID_PARAMETER;
+    hctx(net)->inference_precision = (int)p;
+    return BCNN_SUCCESS;
+}
+
+bcnn_precision bcnn_get_inference_precision(const bcnn_net *net) {
+    return (bcnn_precision)((const bcnn_hip_context *)net->hip_ctx)->inference_precision;
+}
+
 void bcnn_set_gradient_ready_callback(bcnn_net *net, bcnn_gradient_ready_fn fn, void *user) {
     bcnn_hip_context *hc = hctx(net);
     hc->grad_ready_fn = fn;

@@ -167,6 +167,7 @@ typedef struct bcnn_hip_context {
     int in_pass;
     int no_side_stream; /* bcnn_set_weight_gradient_stream(net, 0) */
     uint64_t dropout_seed; /* bcnn_set_dropout_seed; 0 until set */
+    int inference_precision; /* bcnn_set_inference_precision (a bcnn_precision); read by the convolution node outside TRAIN mode */
 } bcnn_hip_context;
 
 /* ---- net ------------------------------------------------------------------------------------------ */

@@ -169,6 +169,11 @@ static const float *announce_bnfold(bcnn_net *net, const bcnn_conv_param *p) {
     return net->tensors[bn->src[0]].data_gpu; /* the batch-norm's INPUT: what the convolution multiplies */
 }
 
+/* bcnn_set_inference_precision(BCNN_PRECISION_BF16) is in force: only outside TRAIN mode */
+static int bcnn_bf16_inference(const bcnn_net *net) {
+    return net->mode != BCNN_MODE_TRAIN && ((const bcnn_hip_context *)net->hip_ctx)->inference_precision == BCNN_PRECISION_BF16;
+}
+
 void bcnn_forward_conv_layer(bcnn_net *net, bcnn_node *node) {
     bcnn_conv_param *p = (bcnn_conv_param *)node->param;
     conv_io io = conv_tensors(net, node);
@@ -208,6 +213,16 @@ void bcnn_forward_conv_layer(bcnn_net *net, bcnn_node *node) {
                                        (size_t)ep->min_dim[0] * out->h * out->w, (int)ep->activation, out->data_gpu);
         ep->done_forward = 1;
         p->data_pending = 1;
+        return;
+    }
+    if (bcnn_bf16_inference(net)) {
+        /* the opt-in reduced-precision inference forward: every convolution node, whatever its shape */
+        bcnn_hip_conv_forward_bf16(xin, io.w->data_gpu, io.b->data_gpu, io.y->data_gpu, io.x->n, io.x->c, io.x->h, io.x->w,
+                                   p->num, p->size, p->stride, p->pad, p->num_groups, (int)p->activation,
+                                   io.slopes ? io.slopes->data_gpu : NULL, p->batch_norm,
+                                   io.run_mean ? io.run_mean->data_gpu : NULL, io.run_var ? io.run_var->data_gpu : NULL,
+                                   io.scales ? io.scales->data_gpu : NULL, p->saved_mean.data_gpu,
+                                   p->saved_variance.data_gpu, p->x_norm_gpu, p->bn_workspace_gpu, (int)net->mode);
         return;
     }
     bcnn_hip_conv_forward(xin, io.w->data_gpu, io.b->data_gpu, io.y->data_gpu, io.x->n, io.x->c, io.x->h,
@@ -299,11 +314,13 @@ void bcnn_prepack_conv_weights(bcnn_net *net, int data_gradient) {
     int n = 0;
     if (BCNN_EXP_ENV("BCNN_NO_PREPACK")) return; /* A/B switch of the experiment build: every node packs for itself */
     if (net->num_nodes < 1) return;
+    /* the bf16 inference forward reads the weights as they are: no node has anything to pack (the call below still opens the pass) */
+    const int none = !data_gradient && bcnn_bf16_inference(net);
     bcnn_hip_conv_desc *d = (bcnn_hip_conv_desc *)malloc((size_t)net->num_nodes * sizeof(*d));
     if (!d) return; /* every node then packs for itself */
     for (int i = 0; i < net->num_nodes; ++i) {
         bcnn_node *node = &net->nodes[i];
-        if (node->type != BCNN_LAYER_CONV2D) continue;
+        if (node->type != BCNN_LAYER_CONV2D || none) continue;
         const bcnn_conv_param *p = (const bcnn_conv_param *)node->param;
         const bcnn_tensor *x = &net->tensors[node->src[0]], *w = &net->tensors[node->src[1]];
         if (!w->data_gpu || (data_gradient && !x->grad_data_gpu)) continue;

@@ -47,6 +47,19 @@ def conv_forward(x, wt, bias, y, k, stride, pad, groups=1, act=0, slopes=None, b
                             _f32(b.get("x_norm")), _f32(b.get("workspace")), mode)
 
 
+def conv_forward_bf16(x, wt, bias, y, k, stride, pad, groups=1, act=0, slopes=None, bn=None, mode=MODE_PREDICT):
+    """conv_forward for inference with the convolution on the bf16 matrix cores (bcnn_hip_conv_forward_bf16): fp32
+    tensors, operands rounded to bf16 inside the kernel, fp32 accumulator, the fp32 path's bias / batch-norm / activation.
+    mode is MODE_PREDICT or MODE_VALID; returns False, and launches and writes nothing, for MODE_TRAIN."""
+    n, c, h, w = x.shape
+    f = wt.shape[0]
+    b = bn or {}
+    return bool(_lib.load().bcnn_hip_conv_forward_bf16(
+        _f32(x), _f32(wt), _f32(bias), _f32(y), n, c, h, w, f, k, stride, pad, groups, act, _f32(slopes), 1 if bn else 0,
+        _f32(b.get("run_mean")), _f32(b.get("run_var")), _f32(b.get("scales")), _f32(b.get("saved_mean")),
+        _f32(b.get("saved_var")), _f32(b.get("x_norm")), _f32(b.get("workspace")), mode))
+
+
 def conv_backward(x, wt, y, dy, dx, dw, dbias, k, stride, pad, groups, act, workspace, slopes=None,
                   dslopes=None, bn=None, bias=None):
     """bcnn_backward_conv_layer (bcnn_conv_layer.c:487-587). dy is updated in place; dx may be None.

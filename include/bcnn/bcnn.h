@@ -247,6 +247,19 @@ BCNN_API void bcnn_set_dropout_seed(bcnn_net *net, uint64_t seed);
  * otherwise). An 8-byte read-back; either pointer may be NULL. BCNN_INVALID_PARAMETER if the net has no such node.
  * A batch without a positive pair gives loss 0 and P 0. */
 BCNN_API bcnn_status bcnn_get_lifted_struct_loss(bcnn_net *net, float *loss, int *num_constraints);
+/* Precision of the convolution nodes in an inference forward (default BCNN_PRECISION_FP32). With BCNN_PRECISION_BF16 every
+ * convolution node of a forward pass in BCNN_MODE_PREDICT or BCNN_MODE_VALID runs on the bf16 matrix cores: activations and
+ * weights stay fp32 in memory and are rounded to bf16 (round-to-nearest-even) inside the kernel, the accumulator is fp32,
+ * bias / fused batch-norm / activation are computed as before. The output of a node then differs from the fp32 one by at
+ * most about 2^-8 * sum |x| |w| per element, which is outside the 1e-4 parity the default path holds:
+ * hence opt-in. Every convolution node takes it, whatever its shape, so that the numerics of a net are predictable.
+ * Depthwise-convolution, deconvolution and full-connected nodes stay fp32. The value may be set in any mode and takes
+ * effect only while the net's mode is PREDICT or VALID: a BCNN_MODE_TRAIN pass never uses it (its backward needs the fp32
+ * forward). An unknown value returns BCNN_INVALID_PARAMETER and changes nothing. Config files: `inference_precision=bf16`
+ * (or `fp32`) in the [net] section. */
+typedef enum { BCNN_PRECISION_FP32 = 0, BCNN_PRECISION_BF16 = 1 } bcnn_precision;
+BCNN_API bcnn_status bcnn_set_inference_precision(bcnn_net *net, bcnn_precision p);
+BCNN_API bcnn_precision bcnn_get_inference_precision(const bcnn_net *net);
 /* Run ONE node's forward / backward worker on whatever its tensors currently hold (no executor bookkeeping:
  * no zero fill of the dst gradients, no dead-fill elision -- a sole-writer gradient is accumulated like in the
  * reference). Used by the teacher-forced parity walk, which feeds every node the REFERENCE's inputs. */

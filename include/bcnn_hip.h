@@ -191,6 +191,18 @@ void bcnn_hip_conv_backward(const float *x_d, const float *w_d, const float *bia
                             const float *saved_mean_d, const float *saved_var_d, float *dmean_d,
                             float *dvar_d, const float *x_norm_d, const float *bn_workspace_d,
                             float *workspace_d, size_t workspace_elems);
+/* bcnn_hip_conv_forward for inference with the convolution on the bf16 matrix cores: x_d and w_d stay fp32 in memory and
+ * are rounded to bf16 (round-to-nearest-even) on their way into the kernel, the accumulator is fp32, and bias, fused
+ * batch-norm and activation are the fp32 path's own code. Per output the result differs from bcnn_hip_conv_forward by at
+ * most about 2^-8 * sum |x| |w|: NOT the 1e-4 parity of the default path, hence opt-in. mode must be
+ * BCNN_HIP_MODE_PREDICT or _VALID (the training-only buffers may be NULL): returns 1 when it ran; 0 for _TRAIN, in
+ * which case nothing is launched and nothing is written (the backward pass needs the fp32 forward). No packed copy of
+ * the weights is kept between calls. */
+int bcnn_hip_conv_forward_bf16(const float *x_d, const float *w_d, const float *bias_d, float *y_d, int n, int c, int h,
+                               int w, int f, int k, int stride, int pad, int groups, int act, const float *slopes_d,
+                               int batch_norm, float *run_mean_d, float *run_var_d, const float *scales_d,
+                               float *saved_mean_d, float *saved_var_d, float *x_norm_d, float *bn_workspace_d,
+                               int mode);
 
 /* ---------------------------------------------------------------------------------------------
  * A convolution node with batch-norm (no activation) whose output is the first operand of the eltwise node that
