@@ -17,7 +17,7 @@ static BnFold take_fold() {
     return f;
 }
 static bool bnfold_shape_ok(const ConvShape& s) {
-    return s.ksz == 1 && s.stride == 1 && s.pad == 0 && s.groups == 1 && conv_forward_dma_supported(s) &&
+    return s.ksz == 1 && s.stride == 1 && s.pad == 0 && s.groups == 1 && conv_dma_fwd_wanted(s) &&
            conv_dw_dma_workspace_floats(s) > 0;
 }
 // rowc[f] = sum_c W[f][c] b[c], b[c] = bias - mean a[c] (a = scale / sqrt(var + 1e-6); the reference's bcnn_add_scalar adds
@@ -152,51 +152,92 @@ static const void* prepack_table(PrepackStore& st, int kind, int mode, const voi
 }
 
 // ---- which kernel takes a layer --------------------------------------------------------------------------------------
-// Every family is tried in a fixed order and says for itself whether the shape, and the alignment of what it is handed, is
-// its own (conv_paths.h):
-//   forward          window, stem, direct, winograd43 (raw only), winograd_fused, winograd, large (kernels > 7x7); then,
-//                    inside conv_forward_dispatch, dma, small_c, the register-staged kernel. The opt-in bf16 forward
-//                    (bcnn_hip_conv_forward_bf16) is one family for every shape: conv_forward_bf16
-//   data gradient    winograd43, winograd_fused, winograd, large; then, inside conv_backward_data, small_c, dma,
-//                    register-staged
-//   weight gradient  the rows of kDwFamilies
-// bcnn_hip_conv_prepack below walks the first two for the families that read packed weights (the fused Winograd kernels and
-// dma); the others read the weights as they are or, the three-kernel Winograd, transform them in a kernel of their own.
-// A new family is a line or a row here and its declaration in conv_paths.h.
-// bf16: the caller asked for the reduced-precision forward (bcnn_hip_conv_forward_bf16): one family takes every shape.
+// The three tables below are the order: a layer runs on the first row whose gate is open, whose shape rule holds and, where
+// pointers or buffers can still refuse it, whose `usable` agrees; the last row of each takes every shape. A new family is a
+// row here and its declarations in conv_paths.h. (The opt-in bf16 forward, bcnn_hip_conv_forward_bf16, is one family for
+// every shape: conv_forward_bf16. A folded batch-norm in front goes straight to the dma kernels: conv_forward_impl.)
+// A/B switches of the experiment build that take a family out: BCNN_HIP_NO_WINDOW, BCNN_HIP_NO_DMA, BCNN_HIP_NO_SMALLC_DX
+enum ConvGate { GATE_NONE, GATE_WINDOW, GATE_DMA, GATE_SMALLC_DX, GATE_COUNT };
+static bool gate_open(ConvGate g) {
+    static const bool off[GATE_COUNT] = {false, BCNN_EXP_ENV("BCNN_HIP_NO_WINDOW") != nullptr,
+                                         BCNN_EXP_ENV("BCNN_HIP_NO_DMA") != nullptr,
+                                         BCNN_EXP_ENV("BCNN_HIP_NO_SMALLC_DX") != nullptr};
+    return !off[g];
+}
+// what bcnn_hip_conv_prepack packs ahead for a layer a family wants (at most one is set): the family's plan function
+struct ConvPack {
+    bool (*wino)(const ConvShape& s, int dx_mode, WinoPackJob* job, size_t* floats);
+    bool (*igemm)(const ConvShape& s, int dx_mode, IgemmPackJob* job, size_t* floats);
+};
+constexpr ConvPack kNoPack = {nullptr, nullptr};  // the kernel reads w as it is, or transforms it in a kernel of its own
+template <class Call>
+struct ConvFamily {
+    bool (*wanted)(const ConvShape& s, int raw);  // the shape rule (raw: forward only)
+    bool (*usable)(const Call& c);                // nullptr: a wanted layer is never refused
+    void (*run)(const Call& c);                   // cannot refuse
+    ConvPack pack;
+    ConvGate gate;
+};
+static const ConvFamily<ConvFwdCall> kConvFwdFamilies[] = {
+    {conv_window_fwd_wanted, nullptr, conv_forward_window, kNoPack, GATE_WINDOW},
+    {conv_stem_fwd_wanted, nullptr, conv_forward_stem, kNoPack, GATE_WINDOW},
+    {conv_direct_fwd_wanted, nullptr, conv_forward_direct, kNoPack, GATE_NONE},
+    {conv_winograd43_fwd_wanted, conv_winograd43_fwd_usable, conv_forward_winograd43, {wino43_pack_plan, nullptr}, GATE_NONE},
+    {conv_winograd_fused_fwd_wanted, nullptr, conv_forward_winograd_fused, {wino_fused_pack_plan, nullptr}, GATE_NONE},
+    {conv_winograd_fwd_wanted, nullptr, conv_forward_winograd, kNoPack, GATE_NONE},
+    {conv_large_wanted, nullptr, conv_forward_large, kNoPack, GATE_NONE},
+    {conv_dma_fwd_wanted, nullptr, conv_forward_dma_timed, {nullptr, dma_pack_plan}, GATE_DMA},
+    {conv_small_c_fwd_wanted, nullptr, conv_forward_small_c, kNoPack, GATE_DMA},
+    {[](const ConvShape&, int) { return true; }, nullptr, conv_forward_igemm, kNoPack, GATE_NONE},
+};
+static const ConvFamily<ConvDxCall> kConvDxFamilies[] = {
+    {conv_winograd43_dx_wanted, conv_winograd43_dx_usable, conv_backward_data_winograd43, {wino43_pack_plan, nullptr}, GATE_NONE},
+    {conv_winograd_fused_dx_wanted, nullptr, conv_backward_data_winograd_fused, {wino_fused_pack_plan, nullptr}, GATE_NONE},
+    {conv_winograd_dx_wanted, nullptr, conv_backward_data_winograd, kNoPack, GATE_NONE},
+    {conv_large_wanted, nullptr, conv_backward_data_large, kNoPack, GATE_NONE},
+    {conv_small_c_dx_wanted, nullptr, conv_backward_data_small_c, kNoPack, GATE_SMALLC_DX},
+    {conv_dma_dx_wanted, nullptr, conv_backward_data_dma, {nullptr, dma_pack_plan}, GATE_DMA},
+    {[](const ConvShape&, int) { return true; }, nullptr, conv_backward_data_igemm, kNoPack, GATE_NONE},
+};
+
+template <class Call, size_t R>
+static void conv_run_first(const ConvFamily<Call> (&rows)[R], const Call& c, int raw) {
+    for (const ConvFamily<Call>& fam : rows)
+        if (gate_open(fam.gate) && fam.wanted(c.s, raw) && (!fam.usable || fam.usable(c))) {
+            fam.run(c);
+            return;
+        }
+}
+// The family bcnn_hip_conv_prepack plans for: the first wanted one in the raw form. The descriptor does not say whether a
+// batch-norm follows the layer; a forward layer without one then packs for itself where F(4x4,3x3) was planned, as does
+// every layer whose planned family turns out not to be usable.
+template <class Call, size_t R>
+static ConvPack conv_planned_pack(const ConvFamily<Call> (&rows)[R], const ConvShape& s) {
+    for (const ConvFamily<Call>& fam : rows)
+        if (gate_open(fam.gate) && fam.wanted(s, /*raw=*/1)) return fam.pack;
+    return kNoPack;
+}
+
+// bf16: the caller asked for the reduced-precision forward (bcnn_hip_conv_forward_bf16)
 static void conv_fwd_any(const float* x, const float* w, const float* bias, const float* slopes, float* y,
                          const ConvShape& s, int act, int raw, ConvStats* stats = nullptr, bool bf16 = false) {
     if (stats) stats->splits = 0;
-    if (bf16) {
-        conv_forward_bf16(x, w, bias, slopes, y, s, act, raw, stats);
-        return;
-    }
-    static const int window_on = BCNN_EXP_ENV("BCNN_HIP_NO_WINDOW") ? 0 : 1;  // A/B switch: the LDS-free kernels instead
-    if (window_on && conv_forward_window(x, w, bias, slopes, y, s, act, raw)) return;
-    if (window_on && conv_forward_stem(x, w, bias, slopes, y, s, act, raw, stats)) return;
-    if (conv_forward_direct(x, w, bias, slopes, y, s, act, raw)) return;
-    if (raw && conv_forward_winograd43(x, w, y, s, raw, stats)) return;
-    if (conv_forward_winograd_fused(x, w, bias, slopes, y, s, act, raw, stats)) return;
-    if (conv_forward_winograd(x, w, bias, slopes, y, s, act, raw, stats)) return;
-    if (conv_forward_large(x, w, bias, slopes, y, s, act, raw, stats)) return;
-    conv_forward_dispatch(x, w, bias, slopes, y, s, act, raw, stats);
+    if (s.total_q <= 0 || s.Mg == 0) return;
+    if (bf16) conv_forward_bf16(x, w, bias, slopes, y, s, act, raw, stats);
+    else conv_run_first(kConvFwdFamilies, ConvFwdCall{x, w, bias, slopes, y, s, act, raw, stats}, raw);
 }
 
 static void conv_dx_any(const float* w, const float* dy, float* dx, const ConvShape& s, DxBnSums* bs) {
-    if (conv_backward_data_winograd43(w, dy, dx, s)) return;
-    if (conv_backward_data_winograd_fused(w, dy, dx, s)) return;
-    if (conv_backward_data_winograd(w, dy, dx, s)) return;
-    if (conv_backward_data_large(w, dy, dx, s)) return;
-    conv_backward_data(w, dy, dx, s, bs);
+    if (bs) bs->splits = 0;
+    if (s.total_p == 0 || s.Cg == 0) return;
+    conv_run_first(kConvDxFamilies, ConvDxCall{w, dy, dx, s, bs}, 0);
 }
 
-// A/B switches of the experiment build that take a family out: BCNN_HIP_NO_WINDOW, BCNN_HIP_NO_DMA
-enum DwGate { GATE_NONE, GATE_WINDOW, GATE_DMA, GATE_COUNT };
 struct DwFamily {
     size_t (*workspace_floats)(const ConvShape& s);  // of split partials in the caller's workspace; 0: not its shape
     bool (*run)(const float* x, const float* dy, float* dw, float* dbias, const ConvShape& s, float* workspace,
                 size_t workspace_floats, bool* bias_done);
-    DwGate gate;
+    ConvGate gate;
 };
 static const DwFamily kDwFamilies[] = {
     {conv_dw_window_workspace_floats, conv_backward_weights_window, GATE_WINDOW},
@@ -235,23 +276,19 @@ void bcnn_hip_conv_prepack(const bcnn_hip_conv_desc* layers, int count, int data
         if (!d.w_d || d.groups <= 0 || d.n <= 0) continue;
         const ConvShape s = make_conv_shape(d.n, d.c, d.h, d.w, d.f, d.k, d.stride, d.pad, d.groups);
         if (s.total_q <= 0 || s.Mg == 0 || s.Cg == 0) continue;
+        const ConvPack pack = mode ? conv_planned_pack(kConvDxFamilies, s) : conv_planned_pack(kConvFwdFamilies, s);
         WinoPackJob w1;
         IgemmPackJob i1;
         memset(&w1, 0, sizeof(w1));  // padding bytes too: the tables are compared bytewise against the uploaded ones
         memset(&i1, 0, sizeof(i1));
         size_t floats = 0;
-        if (wino_fused_pack_plan(s, mode, &w1, &floats)) {
+        if (pack.wino && pack.wino(s, mode, &w1, &floats)) {
             PrepackEntry* e = prepack_entry(st, d.w_d, PREPACK_WINO, mode, floats);
             w1.w = d.w_d; w1.u = e->buf;
             if (w1.blocks > wmax) wmax = w1.blocks;
             wj.push_back(w1);
-        } else if (conv_winograd_unfused_takes(s)) {
-            continue;  // transforms its weights inside its own first kernel
-        } else if (conv_large_takes(s)) {
-            continue;  // reads the weights as they are
-        } else if (mode == 1 && conv_dx_small_c_takes(s)) {
-            continue;
-        } else if (dma_pack_plan(s, mode, &i1, &floats)) {
+        }
+        if (pack.igemm && pack.igemm(s, mode, &i1, &floats)) {
             PrepackEntry* e = prepack_entry(st, d.w_d, PREPACK_IGEMM, mode, floats);
             i1.w = d.w_d; i1.at = e->buf;
             const int blocks = i1.gx * i1.gy * i1.gz;
@@ -480,10 +517,8 @@ static void conv_backward_impl(const float* x, const float* w, const float* bias
             exit(1);
         }
     } else {
-        static const bool gated_off[GATE_COUNT] = {false, BCNN_EXP_ENV("BCNN_HIP_NO_WINDOW") != nullptr,
-                                                   BCNN_EXP_ENV("BCNN_HIP_NO_DMA") != nullptr};
         for (const DwFamily& fam : kDwFamilies)
-            if (!gated_off[fam.gate] &&
+            if (gate_open(fam.gate) &&
                 fam.run(x, dy, dw, batch_norm ? nullptr : dbias, s, workspace, workspace_elems, &bias_done))
                 break;
     }
@@ -492,8 +527,8 @@ static void conv_backward_impl(const float* x, const float* w, const float* bias
         set_current_stream(main_stream);
     }
     if (!batch_norm && !bias_done) bcnn_hip_grad_bias(dbias, dy, n, f, s.OHOW);  // uses the shared reduce scratch
-    if (bs) bs->splits = 0;
     if (dx) conv_dx_any(w, dy, dx, s, bs);
+    else if (bs) bs->splits = 0;
     if (side) {
         if (side_mode == 2) side->pending = true;
         else HIP_CHECK(hipStreamWaitEvent(main_stream, side->done, 0));

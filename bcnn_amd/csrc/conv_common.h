@@ -116,11 +116,11 @@ __device__ __forceinline__ float bnfold_a(const float* __restrict__ var, const f
 bool conv_side_stream_deferred();
 // the pack of (w, kind, mode) made by the current prepack batch and not yet used, or nullptr (conv.hip)
 float* prepack_take(const float* w, int kind, int mode, size_t floats);
-// what the kernel a layer will run on needs packed; false: nothing (another kernel takes the layer)
+// what a family's kernel needs packed for a layer its *_wanted rule holds for (conv_paths.h). One signature for the table's
+// hook; only wino_fused_pack_plan can still say false (experiment build: the split-bf16 kernels read no fp32 pack)
 bool wino_fused_pack_plan(const ConvShape& s, int dx_mode, WinoPackJob* job, size_t* floats);  // conv_winograd_fused.hip
 bool wino43_pack_plan(const ConvShape& s, int dx_mode, WinoPackJob* job, size_t* floats);      // conv_winograd43.hip
 bool dma_pack_plan(const ConvShape& s, int dx_mode, IgemmPackJob* job, size_t* floats);        // conv_igemm_dma.hip
-bool conv_winograd_unfused_takes(const ConvShape& s);                                          // conv_winograd.hip
 void wino_fused_pack_launch(const WinoPackJob* jobs_dev, int n, int max_blocks);
 void dma_pack_launch(const IgemmPackJob* jobs_dev, int n, int max_blocks);
 

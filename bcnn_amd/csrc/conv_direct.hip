@@ -302,15 +302,18 @@ void conv_prefetch_input(const float* x, const ConvShape& s, float* sink) {
         cache_prefetch_kernel<<<kCUs * 8, 256, 0, current_stream()>>>(reinterpret_cast<const float4*>(x), xb / 16, sink);
 }
 
-bool conv_forward_direct(const float* x, const float* w, const float* bias, const float* slopes, float* y,
-                         const ConvShape& s, int act, int raw) {
-    if (s.pointwise || s.K > 32 || s.Mg > 64 || s.total_q == 0) return false;
-    if ((long long)s.N * s.F * s.OHOW >= (1LL << 29) || (long long)s.N * s.C * s.HW >= (1LL << 28)) return false;
-    if (!((s.ksz == 3 && s.Cg <= 3) || (s.ksz == 5 && s.Cg == 1))) return false;
+// the (ksz, Cg) pairs the kernel is instantiated for: K = 9, 18, 27 and 25
+bool conv_direct_fwd_wanted(const ConvShape& s, int) {
+    if (!((s.ksz == 3 && s.Cg >= 1 && s.Cg <= 3) || (s.ksz == 5 && s.Cg == 1)) || s.Mg > 64) return false;
+    return (long long)s.N * s.F * s.OHOW < (1LL << 29) && (long long)s.N * s.C * s.HW < (1LL << 28);
+}
+
+void conv_forward_direct(const ConvFwdCall& c) {
+    const ConvShape& s = c.s;
     ConvDirectFwdArgs a;
-    a.x = x; a.w = w; a.bias = bias; a.slopes = slopes; a.y = y; a.s = s;
-    a.act = raw ? BCNN_HIP_ACT_NONE : act;
-    a.add_bias = raw ? 0 : 1;
+    a.x = c.x; a.w = c.w; a.bias = c.bias; a.slopes = c.slopes; a.y = c.y; a.s = s;
+    a.act = c.raw ? BCNN_HIP_ACT_NONE : c.act;
+    a.add_bias = c.raw ? 0 : 1;
     a.ntiles = ceil_div(s.total_q, 32);
     // persistent-ish: ~8 workgroups per CU, each walking a contiguous run of tiles (its 4 waves share rows)
     int blocks = kCUs * 8;
@@ -322,7 +325,7 @@ bool conv_forward_direct(const float* x, const float* w, const float* bias, cons
     const int tm = (s.Mg <= 32) ? 1 : 2;
     KTimer kt(K_CONV_FWD, conv_gemm_flops(s), conv_gemm_bytes(s));
     trace_kernel("conv_fwd_direct_kernel");
-    conv_prefetch_input(x, s, y);
+    conv_prefetch_input(c.x, s, c.y);
     const int actm = (a.act == BCNN_HIP_ACT_NONE) ? 0 : (a.act == BCNN_HIP_ACT_RELU ? 1 : 2);
 #define LAUNCH(TMv, KSv, KZ)                                                                            \
     do {                                                                                                \
@@ -334,10 +337,12 @@ bool conv_forward_direct(const float* x, const float* w, const float* bias, cons
     else if (s.ksz == 3 && ks == 9) { if (tm == 1) LAUNCH(1, 9, 3); else LAUNCH(2, 9, 3); }
     else if (s.ksz == 3 && ks == 5) { if (tm == 1) LAUNCH(1, 5, 3); else LAUNCH(2, 5, 3); }
     else if (s.ksz == 5 && ks == 13) { if (tm == 1) LAUNCH(1, 13, 5); else LAUNCH(2, 13, 5); }
-    else return false;
+    else {
+        fprintf(stderr, "[bcnn_hip] conv forward: no LDS-free kernel for kernel size %d with %d channels per group\n", s.ksz, s.Cg);
+        exit(1);
+    }
 #undef LAUNCH
     KERNEL_CHECK();
-    return true;
 }
 
 // ================================================================================================

@@ -416,7 +416,7 @@ bool conv_backward_weights_dma_timed(const float* x, const float* dy, float* dw,
 static DwDmaPlan plan_dw_small_c(const ConvShape& s) {
     DwDmaPlan p;
     p.ok = false; p.partial_floats = 0;
-    if (!conv_small_c_applicable(s) || (s.Mg & 1) || s.OHOW < DWQ || s.total_q < 4 * DWQ) return p;
+    if (!conv_small_c_fwd_wanted(s) || (s.Mg & 1) || s.OHOW < DWQ || s.total_q < 4 * DWQ) return p;
     p.kk2 = 1;
     p.cfg = 0;  // 64 x 64 tiles: 147 rows -> three column tiles
     const int BM = kDwTiles[p.cfg].bm, BN = kDwTiles[p.cfg].bn;

@@ -301,29 +301,17 @@ static void dispatch_igemm(IgemmArgs& a, long long max_cols) {
     else launch_igemm<2, 2, 2, 2, 16>(a, max_cols);                  // 128 x 128
 }
 
-static bool dma_enabled() {
-    static const int on = BCNN_EXP_ENV("BCNN_HIP_NO_DMA") ? 0 : 1;  // A/B switch for profiling
-    return on != 0;
-}
-
-// raw = 1: write the bare convolution (no bias, no activation) -- used by the fused-BN path.
-void conv_forward_dispatch(const float* x, const float* w, const float* bias, const float* slopes, float* y,
-                           const ConvShape& s, int act, int raw, ConvStats* stats) {
-    if (stats) stats->splits = 0;
-    if (s.total_q == 0 || s.Mg == 0) return;
-    if (s.ksz > 7 && !s.pointwise) {
-        fprintf(stderr, "[bcnn_hip] conv forward: kernel size %d > 7 is not supported\n", s.ksz);
-        exit(1);
-    }
+// the last row of the forward table (conv.hip): kernels of up to 7x7 (ClassInfo, ctaps), which is all that gets past the
+// large-kernel family. raw = 1: the bare convolution (no bias, no activation), no statistics
+void conv_forward_igemm(const ConvFwdCall& c) {
+    const ConvShape& s = c.s;
     KTimer kt(K_CONV_FWD, conv_gemm_flops(s), conv_gemm_bytes(s));
-    if (dma_enabled() && conv_forward_dma(x, w, bias, slopes, y, s, act, raw, stats)) return;
-    if (dma_enabled() && conv_forward_small_c(x, w, bias, slopes, y, s, act, raw, stats)) return;
     trace_kernel("conv_igemm_kernel:fwd");
     IgemmArgs a;
-    a.a_base = w; a.b_base = x; a.out = y; a.bias = bias; a.slopes = slopes; a.s = s;
+    a.a_base = c.w; a.b_base = c.x; a.out = c.y; a.bias = c.bias; a.slopes = c.slopes; a.s = s;
     a.mode = 0;
-    a.act = raw ? BCNN_HIP_ACT_NONE : act;
-    a.add_bias = raw ? 0 : 1;
+    a.act = c.raw ? BCNN_HIP_ACT_NONE : c.act;
+    a.add_bias = c.raw ? 0 : 1;
     a.M = s.Mg; a.KR = s.K; a.a_row_stride = s.K; a.a_group_stride = (long long)s.Mg * s.K;
     a.ntaps = s.pointwise ? 1 : s.ksz * s.ksz;
     a.ntaps_magic = magic_of(a.ntaps);
@@ -377,13 +365,16 @@ __global__ __launch_bounds__(256) void col2im_batch_kernel(const float* __restri
     }
 }
 
-bool conv_dx_small_c_takes(const ConvShape& s) {
-    static const bool off = BCNN_EXP_ENV("BCNN_HIP_NO_SMALLC_DX") != nullptr;
-    return !off && !s.pointwise && s.groups == 1 && s.K <= 32 && s.Mg >= 32 && (long long)s.N * s.C * s.HW < (1LL << 31);
+bool conv_small_c_dx_wanted(const ConvShape& s, int) {
+    return !s.pointwise && s.groups == 1 && s.K <= 32 && s.Mg >= 32 && (long long)s.N * s.C * s.HW < (1LL << 31);
 }
 
-static bool conv_backward_data_small_c(const float* w, const float* dy, float* dx, const ConvShape& s) {
-    if (!conv_dx_small_c_takes(s)) return false;
+void conv_backward_data_small_c(const ConvDxCall& c) {
+    const ConvShape& s = c.s;
+    const float *w = c.w, *dy = c.dy;
+    float* dx = c.dx;
+    KTimer kt(K_CONV_DX, conv_gemm_flops(s), conv_gemm_bytes(s));
+    trace_kernel("conv_small_c:dx");
     const size_t per_image = (size_t)s.K * s.OHOW;                      // col floats per image
     int chunk = (int)(((size_t)96 << 20) / (per_image * sizeof(float)));  // <= 96 MB of col in flight
     if (chunk < 1) chunk = 1;
@@ -407,21 +398,15 @@ static bool conv_backward_data_small_c(const float* w, const float* dy, float* d
             col, dx + (size_t)n0 * s.C * s.HW, s.C, s.H, s.W, s.ksz, s.pad, s.stride, s.OH, s.OW, (unsigned)total);
         KERNEL_CHECK();
     }
-    return true;
 }
 
-void conv_backward_data(const float* w, const float* dy, float* dx, const ConvShape& s, DxBnSums* bs) {
-    if (bs) bs->splits = 0;
-    if (s.total_p == 0 || s.Cg == 0) return;
-    if (s.ksz > 7 && !s.pointwise) {
-        fprintf(stderr, "[bcnn_hip] conv backward: kernel size %d > 7 is not supported\n", s.ksz);
-        exit(1);
-    }
+// the last row of the data-gradient table (conv.hip); emits no batch-norm sums
+void conv_backward_data_igemm(const ConvDxCall& c) {
+    const ConvShape& s = c.s;
     KTimer kt(K_CONV_DX, conv_gemm_flops(s), conv_gemm_bytes(s));
-    if (conv_backward_data_small_c(w, dy, dx, s)) return;
-    if (dma_enabled() && conv_backward_data_dma(w, dy, dx, s, bs)) return;
+    trace_kernel("conv_igemm_kernel:dx");
     IgemmArgs a;
-    a.a_base = w; a.b_base = dy; a.out = dx; a.bias = nullptr; a.slopes = nullptr; a.s = s;
+    a.a_base = c.w; a.b_base = c.dy; a.out = c.dx; a.bias = nullptr; a.slopes = nullptr; a.s = s;
     a.mode = 1; a.act = BCNN_HIP_ACT_NONE; a.add_bias = 0;
     a.M = s.Cg; a.a_group_stride = (long long)s.Mg * s.K;
     a.ksz_magic = magic_of(s.ksz);

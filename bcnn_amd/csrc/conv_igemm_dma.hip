@@ -623,10 +623,9 @@ static int dx_tap_order(const ConvShape& s, unsigned char* tapoff) {
     return n;
 }
 
-// bcnn_hip_conv_prepack: the A^T this layer's forward (dx_mode 0) / data-gradient (1) kernel will ask prepack_take for
+// bcnn_hip_conv_prepack: the A^T a wanted layer's forward (dx_mode 0) / data-gradient (1) kernel will ask prepack_take for
 bool dma_pack_plan(const ConvShape& s, int dx_mode, IgemmPackJob* job, size_t* floats) {
     const int M = dx_mode ? s.Cg : s.Mg, J = dx_mode ? s.Mg : s.Cg;
-    if (!dma_supported(s, M, J, dx_mode ? (size_t)s.N * s.F * s.OHOW : (size_t)s.N * s.C * s.HW)) return false;
     const int kk2 = s.pointwise ? 1 : s.ksz * s.ksz;
     const int Jpad = round_up(J, kDmaBK), Mpad = round_up(M, 128);
     unsigned char tapoff[kDmaMaxTaps];
@@ -645,7 +644,7 @@ void dma_pack_launch(const IgemmPackJob* jobs_dev, int n, int max_blocks) {
 // Returns false when the shape is not covered (caller falls back to the register-staged kernel).
 // stats (optional, raw mode only): in  -> partials buffer with room for F * ceil(N*OH*OW / 64) * 2 floats
 //                                   out -> splits = number of column tiles written per channel (0: none)
-bool conv_forward_dma_supported(const ConvShape& s) { return dma_supported(s, s.Mg, s.Cg, (size_t)s.N * s.C * s.HW); }
+bool conv_dma_fwd_wanted(const ConvShape& s, int) { return dma_supported(s, s.Mg, s.Cg, (size_t)s.N * s.C * s.HW); }
 
 // fold: the batch-norm in front of the layer whose per-channel factors go into the packed weights (BnFold)
 bool conv_forward_dma(const float* x, const float* w, const float* bias, const float* slopes, float* y,
@@ -671,12 +670,21 @@ bool conv_forward_dma(const float* x, const float* w, const float* bias, const f
     unsigned char tapoff[kDmaMaxTaps];
     ci.nkx = s.pointwise ? 1 : s.ksz; ci.sgn = 1;
     for (int t = 0; t < kk2; ++t) tapoff[t] = (unsigned char)t;
+    if (!packed && !fold) trace_kernel("pack:self");
     if (!packed) pack_weights(w, at, s, 0, a.M, a.J, a.Jpad, a.Mpad, kk2, tapoff, fold);
     a.stats = (stats && raw) ? stats->partials : nullptr;
     a.bs_out = nullptr; a.bs_y = nullptr; a.bs_mean = nullptr;
     launch_dma(a, (int)s.total_q);
     if (a.stats) stats->splits = a.stats_splits;
     return true;
+}
+
+void conv_forward_dma_timed(const ConvFwdCall& c) {
+    KTimer kt(K_CONV_FWD, conv_gemm_flops(c.s), conv_gemm_bytes(c.s));
+    if (!conv_forward_dma(c.x, c.w, c.bias, c.slopes, c.y, c.s, c.act, c.raw, c.stats, nullptr)) {
+        fprintf(stderr, "[bcnn_hip] conv forward: the LDS-DMA GEMM refused a layer its shape rule wants\n");
+        exit(1);
+    }
 }
 
 // ---- few input channels (the RGB stem): padded-plane GEMM over all (c, kr, kc) rows ---------------------------
@@ -694,7 +702,7 @@ __global__ __launch_bounds__(256) void conv_pad_input_kernel(const float* __rest
 }
 
 
-bool conv_small_c_applicable(const ConvShape& s) {
+bool conv_small_c_fwd_wanted(const ConvShape& s, int) {
     if (s.groups != 1 || s.pointwise || s.ksz > 7 || s.Cg >= 8 || s.Mg <= 32) return false;
     if (s.K < 64) return false;  // K <= 32 has the LDS-free kernels of conv_direct.hip
     const long long Hp = s.H + 2 * s.pad, Wp = s.W + 2 * s.pad;
@@ -715,21 +723,23 @@ float* conv_small_c_padded_input(const float* x, const ConvShape& s, size_t extr
     return xp;
 }
 
-bool conv_forward_small_c(const float* x, const float* w, const float* bias, const float* slopes, float* y,
-                          const ConvShape& s, int act, int raw, ConvStats* stats) {
-    if (stats) stats->splits = 0;
-    if (!conv_small_c_applicable(s)) return false;
+void conv_forward_small_c(const ConvFwdCall& c) {
+    const ConvShape& s = c.s;
+    ConvStats* stats = c.stats;
+    const int raw = c.raw;
+    KTimer kt(K_CONV_FWD, conv_gemm_flops(s), conv_gemm_bytes(s));
+    trace_kernel("conv_small_c:fwd");
     const int Hp = s.H + 2 * s.pad, Wp = s.W + 2 * s.pad;
     DmaArgs a;
     a.J = s.K; a.M = s.Mg; a.Jpad = round_up(a.J, kDmaBK); a.Mpad = round_up(a.M, 128); a.kk2 = 1;
     const size_t at_floats = (size_t)a.Jpad * a.Mpad;
     float* at = nullptr;
-    float* xp = conv_small_c_padded_input(x, s, at_floats, &at, /*for_dw=*/0);
+    float* xp = conv_small_c_padded_input(c.x, s, at_floats, &at, /*for_dw=*/0);
     // the problem as the kernel sees it: the padded tensor, no padding left, one tap
     const ConvShape sp = make_conv_shape(s.N, s.C, Hp, Wp, s.F, s.ksz, s.stride, 0, 1);
     a.s = sp;
-    a.b_base = xp; a.out = y; a.bias = bias; a.slopes = slopes;
-    a.mode = 0; a.act = raw ? BCNN_HIP_ACT_NONE : act; a.add_bias = raw ? 0 : 1;
+    a.b_base = xp; a.out = c.y; a.bias = c.bias; a.slopes = c.slopes;
+    a.mode = 0; a.act = raw ? BCNN_HIP_ACT_NONE : c.act; a.add_bias = raw ? 0 : 1;
     a.at = at; a.at_bytes = (unsigned)(at_floats * 4);
     a.b_bytes = (unsigned)((size_t)s.N * s.C * Hp * Wp * 4);
     a.b_major_stride = 0;
@@ -743,17 +753,21 @@ bool conv_forward_small_c(const float* x, const float* w, const float* bias, con
     ws.Cg = s.K; ws.Mg = s.Mg; ws.ksz = 1;
     unsigned char tapoff[kDmaMaxTaps];
     tapoff[0] = 0;
-    pack_weights(w, at, ws, 0, a.M, a.J, a.Jpad, a.Mpad, 1, tapoff);
+    pack_weights(c.w, at, ws, 0, a.M, a.J, a.Jpad, a.Mpad, 1, tapoff);
     a.stats = (stats && raw) ? stats->partials : nullptr;
     a.bs_out = nullptr; a.bs_y = nullptr; a.bs_mean = nullptr;
     launch_dma(a, (int)s.total_q);
     if (a.stats) stats->splits = a.stats_splits;
-    return true;
 }
 
-bool conv_backward_data_dma(const float* w, const float* dy, float* dx, const ConvShape& s, DxBnSums* bs) {
-    if (bs) bs->splits = 0;
-    if (!dma_supported(s, s.Cg, s.Mg, (size_t)s.N * s.F * s.OHOW)) return false;
+bool conv_dma_dx_wanted(const ConvShape& s, int) { return dma_supported(s, s.Cg, s.Mg, (size_t)s.N * s.F * s.OHOW); }
+
+void conv_backward_data_dma(const ConvDxCall& c) {
+    const ConvShape& s = c.s;
+    const float *w = c.w, *dy = c.dy;
+    float* dx = c.dx;
+    DxBnSums* bs = c.bs;
+    KTimer kt(K_CONV_DX, conv_gemm_flops(s), conv_gemm_bytes(s));
     const int kk2 = s.pointwise ? 1 : s.ksz * s.ksz;
     DmaArgs a;
     a.rowmode = 0;
@@ -764,6 +778,7 @@ bool conv_backward_data_dma(const float* w, const float* dy, float* dx, const Co
     const size_t at_floats = (size_t)s.groups * kk2 * a.Jpad * a.Mpad;
     float* at = prepack_take(w, PREPACK_IGEMM, 1, at_floats);  // packed ahead by bcnn_hip_conv_prepack?
     const bool packed = at != nullptr;
+    if (!packed) trace_kernel("pack:self");
     if (!packed) at = scratch(SCRATCH_DMA, at_floats);
     a.at = at; a.at_bytes = (unsigned)(at_floats * 4);
     a.b_bytes = (unsigned)((size_t)s.N * s.F * s.OHOW * 4);
@@ -784,7 +799,7 @@ bool conv_backward_data_dma(const float* w, const float* dy, float* dx, const Co
         }
         launch_dma(a, (int)s.total_q);
         if (a.bs_out) bs->splits = a.stats_splits;
-        return true;
+        return;
     }
     // stride-parity classes; the packed tap order is class-major
     const int st = s.stride;
@@ -817,7 +832,6 @@ bool conv_backward_data_dma(const float* w, const float* dy, float* dx, const Co
         a.nclass = nc;
         if (max_cols > 0) launch_dma(a, max_cols);
     }
-    return true;
 }
 
 }  // namespace bcnn_hip

@@ -22,7 +22,7 @@ namespace bcnn_hip {
 // n / d with magic = magic_of(d) (conv_common.h); exact while n * d < 2^32. The same function as conv_igemm.hip's.
 __device__ __forceinline__ unsigned fast_div(unsigned n, unsigned magic) { return magic ? __umulhi(n, magic) : n; }
 
-bool conv_large_takes(const ConvShape& s) { return s.ksz > 7 && !s.pointwise; }
+bool conv_large_wanted(const ConvShape& s, int) { return s.ksz > 7 && !s.pointwise; }
 
 // dX: stride-parity class (ra, rb) = the input pixels with (ih + pad) % s == ra, (iw + pad) % s == rb
 struct LargeClass {
@@ -311,11 +311,9 @@ static void large_check_reduction(const ConvShape& s, int rows) {
     }
 }
 
-bool conv_forward_large(const float* x, const float* w, const float* bias, const float* slopes, float* y, const ConvShape& s,
-                        int act, int raw, ConvStats* stats) {
-    if (!conv_large_takes(s)) return false;
-    if (stats) stats->splits = 0;  // the caller runs the stand-alone statistics sweep
-    if (s.total_q <= 0 || s.Mg == 0) return true;
+// (emits no statistics: the caller runs the stand-alone sweep)
+void conv_forward_large(const ConvFwdCall& c) {
+    const ConvShape& s = c.s;
     large_check_reduction(s, s.Cg);
     const int chunk = large_chunk_images(s);
     KTimer kt(K_CONV_FWD, conv_gemm_flops(s), conv_gemm_bytes(s));
@@ -324,21 +322,19 @@ bool conv_forward_large(const float* x, const float* w, const float* bias, const
         const int nb = s.N - n0 < chunk ? s.N - n0 : chunk;
         LargeArgs a;
         a.s = make_conv_shape(nb, s.C, s.H, s.W, s.F, s.ksz, s.stride, s.pad, s.groups);
-        a.a_base = w; a.b_base = x + (size_t)n0 * s.C * s.HW; a.out = y + (size_t)n0 * s.F * s.OHOW;
-        a.bias = bias; a.slopes = slopes;
+        a.a_base = c.w; a.b_base = c.x + (size_t)n0 * s.C * s.HW; a.out = c.y + (size_t)n0 * s.F * s.OHOW;
+        a.bias = c.bias; a.slopes = c.slopes;
         a.mode = 0;
-        a.act = raw ? BCNN_HIP_ACT_NONE : act;
-        a.add_bias = raw ? 0 : 1;
+        a.act = c.raw ? BCNN_HIP_ACT_NONE : c.act;
+        a.add_bias = c.raw ? 0 : 1;
         a.M = s.Mg; a.a_row_stride = s.K; a.a_group_stride = (long long)s.Mg * s.K;
         a.kk2_magic = magic_of(s.ksz * s.ksz); a.ksz_magic = magic_of(s.ksz);
         dispatch_large(a, a.s.total_q, 1);
     }
-    return true;
 }
 
-bool conv_backward_data_large(const float* w, const float* dy, float* dx, const ConvShape& s) {
-    if (!conv_large_takes(s)) return false;
-    if (s.total_p == 0 || s.Cg == 0) return true;
+void conv_backward_data_large(const ConvDxCall& c) {
+    const ConvShape& s = c.s;
     large_check_reduction(s, s.Mg);
     const int chunk = large_chunk_images(s);
     KTimer kt(K_CONV_DX, conv_gemm_flops(s), conv_gemm_bytes(s));
@@ -348,7 +344,7 @@ bool conv_backward_data_large(const float* w, const float* dy, float* dx, const 
         const int nb = s.N - n0 < chunk ? s.N - n0 : chunk;
         LargeArgs a;
         a.s = make_conv_shape(nb, s.C, s.H, s.W, s.F, s.ksz, s.stride, s.pad, s.groups);
-        a.a_base = w; a.b_base = dy + (size_t)n0 * s.F * s.OHOW; a.out = dx + (size_t)n0 * s.C * s.HW;
+        a.a_base = c.w; a.b_base = c.dy + (size_t)n0 * s.F * s.OHOW; a.out = c.dx + (size_t)n0 * s.C * s.HW;
         a.bias = nullptr; a.slopes = nullptr;
         a.mode = 1; a.act = BCNN_HIP_ACT_NONE; a.add_bias = 0;
         a.M = s.Cg; a.a_row_stride = s.ksz * s.ksz; a.a_group_stride = (long long)s.Mg * s.K;
@@ -363,7 +359,6 @@ bool conv_backward_data_large(const float* w, const float* dy, float* dx, const 
             }
         if (max_cols > 0) dispatch_large(a, max_cols, st * st);
     }
-    return true;
 }
 
 // ================================================================================================
@@ -561,7 +556,7 @@ static LargeDwPlan plan_large_dw(const ConvShape& s, bool want_bias_col) {
     return p;
 }
 
-static bool large_dw_runs(const ConvShape& s) { return conv_large_takes(s) && s.total_q > 0 && s.Mg > 0 && s.Cg > 0; }
+static bool large_dw_runs(const ConvShape& s) { return conv_large_wanted(s) && s.total_q > 0 && s.Mg > 0 && s.Cg > 0; }
 
 // the first chunk of images is the largest launch
 static ConvShape large_first_chunk(const ConvShape& s) {
@@ -575,7 +570,7 @@ size_t conv_dw_large_workspace_floats(const ConvShape& s) {
 
 bool conv_backward_weights_large(const float* x, const float* dy, float* dw, float* dbias, const ConvShape& s,
                                  float* workspace, size_t workspace_floats, bool* bias_done) {
-    if (!conv_large_takes(s)) return false;
+    if (!conv_large_wanted(s)) return false;
     if (!large_dw_runs(s)) return true;
     large_check_reduction(s, s.Cg);
     const int chunk = large_chunk_images(s);

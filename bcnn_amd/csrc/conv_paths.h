@@ -1,61 +1,87 @@
-// conv_paths.h -- the kernel families behind the convolution node: what one conv*.hip file defines and another one calls
-// (conv.hip tries them in order; the prepack helpers are in conv_common.h). A bool return is "took the layer": false means
-// the shape, or an alignment the kernel needs, is not covered, nothing was launched and the caller tries the next family.
+// conv_paths.h -- the kernel families behind the convolution node: what one conv*.hip file defines and another one calls.
+// conv.hip holds one ordered table per direction (kConvFwdFamilies, kConvDxFamilies, kDwFamilies); the tables are the order.
 #pragma once
 #include "conv_common.h"
 
 namespace bcnn_hip {
 
-// ---- forward: y = act(conv(x, w) + bias); raw = 1: the bare convolution (a batch-norm follows). stats (optional, raw only):
-// in -> a partials buffer, out -> splits = partials written per channel (0: none) -----------------------------------------
+// y = act(conv(x, w) + bias); raw = 1: the bare convolution (a batch-norm follows). stats (optional, raw only): in -> a
+// partials buffer, out -> splits = partials written per channel (the ladder has set it to 0: none)
+struct ConvFwdCall {
+    const float *x, *w, *bias, *slopes;
+    float* y;
+    ConvShape s;
+    int act, raw;
+    ConvStats* stats;
+};
+// dx = conv^T(dy, w). bs (optional): the backward sums of a batch-norm node in front, emitted by the kernels that can
+// (bs->splits > 0; the ladder has set it to 0)
+struct ConvDxCall {
+    const float *w, *dy;
+    float* dx;
+    ConvShape s;
+    DxBnSums* bs;
+};
+// A forward / data-gradient family is a row of conv.hip's tables made of:
+//   *_wanted(s, raw)  the pure shape rule, all that is known without pointers (what bcnn_hip_conv_prepack can know). The
+//                     layer has output (forward) / input (data gradient) pixels; the data gradient's rules ignore `raw`
+//   *_usable(call)    only where pointers or buffers can still refuse a wanted layer; touches nothing
+//   the run function  cannot refuse: opens its own KTimer, writes its trace name, launches
+//   *_pack_plan       only where the kernel reads re-arranged weights (conv_common.h), asked behind *_wanted
+
 // conv_window.hip: window-in-LDS kernels for 3x3 / s1 layers with K <= 27, and the 7x7 / s2 stem
-bool conv_forward_window(const float* x, const float* w, const float* bias, const float* slopes, float* y, const ConvShape& s,
-                         int act, int raw);
-bool conv_forward_stem(const float* x, const float* w, const float* bias, const float* slopes, float* y, const ConvShape& s,
-                       int act, int raw, ConvStats* stats);
-// conv_direct.hip: LDS-free kernels for small reduction lengths (K <= 32)
-bool conv_forward_direct(const float* x, const float* w, const float* bias, const float* slopes, float* y, const ConvShape& s,
-                         int act, int raw);
-// conv_winograd43.hip: F(4x4, 3x3) for planes of whole 4 x 4 tiles, raw output only
-bool conv_forward_winograd43(const float* x, const float* w, float* y, const ConvShape& s, int raw, ConvStats* stats);
+bool conv_window_fwd_wanted(const ConvShape& s, int raw);
+void conv_forward_window(const ConvFwdCall& c);
+bool conv_stem_fwd_wanted(const ConvShape& s, int raw);
+void conv_forward_stem(const ConvFwdCall& c);
+// conv_direct.hip: LDS-free kernels for 3x3 layers of up to three channels per group and 5x5 layers of one
+bool conv_direct_fwd_wanted(const ConvShape& s, int raw);
+void conv_forward_direct(const ConvFwdCall& c);
+// conv_winograd43.hip: F(4x4, 3x3) for planes of whole 4 x 4 tiles; the forward in the raw form only
+bool conv_winograd43_fwd_wanted(const ConvShape& s, int raw);
+bool conv_winograd43_fwd_usable(const ConvFwdCall& c);
+void conv_forward_winograd43(const ConvFwdCall& c);
+bool conv_winograd43_dx_wanted(const ConvShape& s, int);
+bool conv_winograd43_dx_usable(const ConvDxCall& c);
+void conv_backward_data_winograd43(const ConvDxCall& c);
 // conv_winograd_fused.hip: F(2x2, 3x3) in one kernel for the wide-and-shallow layers
-bool conv_forward_winograd_fused(const float* x, const float* w, const float* bias, const float* slopes, float* y,
-                                 const ConvShape& s, int act, int raw, ConvStats* stats);
-// conv_winograd.hip: F(2x2, 3x3) as three kernels for the deep 3x3 / s1 layers
-bool conv_forward_winograd(const float* x, const float* w, const float* bias, const float* slopes, float* y, const ConvShape& s,
-                           int act, int raw, ConvStats* stats);
+bool conv_winograd_fused_fwd_wanted(const ConvShape& s, int raw);
+void conv_forward_winograd_fused(const ConvFwdCall& c);
+bool conv_winograd_fused_dx_wanted(const ConvShape& s, int);
+void conv_backward_data_winograd_fused(const ConvDxCall& c);
+// conv_winograd.hip: F(2x2, 3x3) as three kernels for the deep 3x3 / s1 layers (transforms w in a kernel of its own)
+bool conv_winograd_fwd_wanted(const ConvShape& s, int raw);
+void conv_forward_winograd(const ConvFwdCall& c);
+bool conv_winograd_dx_wanted(const ConvShape& s, int);
+void conv_backward_data_winograd(const ConvDxCall& c);
 // conv_large.hip: every non-pointwise layer with a kernel larger than 7x7 (the three directions; reads w as it is)
-bool conv_large_takes(const ConvShape& s);
-bool conv_forward_large(const float* x, const float* w, const float* bias, const float* slopes, float* y, const ConvShape& s,
-                        int act, int raw, ConvStats* stats);
+bool conv_large_wanted(const ConvShape& s, int raw = 0);
+void conv_forward_large(const ConvFwdCall& c);
+void conv_backward_data_large(const ConvDxCall& c);
 // conv_bf16.hip: the opt-in inference forward on the bf16 matrix cores, fp32 accumulator (takes every shape)
 bool conv_forward_bf16(const float* x, const float* w, const float* bias, const float* slopes, float* y, const ConvShape& s,
                        int act, int raw, ConvStats* stats);
-// conv_igemm.hip: the LDS-DMA GEMM, the few-channel padded-plane GEMM, else the register-staged kernel (takes every shape)
-void conv_forward_dispatch(const float* x, const float* w, const float* bias, const float* slopes, float* y, const ConvShape& s,
-                           int act, int raw, ConvStats* stats);
-// conv_igemm_dma.hip. fold: the batch-norm in front of the layer whose per-channel factors go into the packed weights
-bool conv_forward_dma_supported(const ConvShape& s);
+// conv_igemm_dma.hip: the LDS-DMA GEMM. conv_forward_dma is the GEMM alone, untimed, false when the shape is not covered
+// (conv_winograd.hip runs its 16 grouped GEMMs on it, conv.hip a folded layer); fold: the batch-norm in front of the layer
+// whose per-channel factors go into the packed weights
+bool conv_dma_fwd_wanted(const ConvShape& s, int raw = 0);
 bool conv_forward_dma(const float* x, const float* w, const float* bias, const float* slopes, float* y, const ConvShape& s,
                       int act, int raw, ConvStats* stats, const BnFold* fold = nullptr);
-bool conv_forward_small_c(const float* x, const float* w, const float* bias, const float* slopes, float* y, const ConvShape& s,
-                          int act, int raw, ConvStats* stats);
-// conv_igemm_dma.hip: few input channels (the RGB stem); their zero-padded copy of x, which conv_dw_dma.hip reads too
-bool conv_small_c_applicable(const ConvShape& s);
+void conv_forward_dma_timed(const ConvFwdCall& c);
+bool conv_dma_dx_wanted(const ConvShape& s, int);
+void conv_backward_data_dma(const ConvDxCall& c);
+// conv_igemm_dma.hip: few input channels (the RGB stem) as a padded-plane GEMM; the zero-padded copy of x, which
+// conv_dw_dma.hip reads too
+bool conv_small_c_fwd_wanted(const ConvShape& s, int raw = 0);  // the weight gradient's few-channel family asks it too
+void conv_forward_small_c(const ConvFwdCall& c);
 float* conv_small_c_padded_input(const float* x, const ConvShape& s, size_t extra_floats, float** extra, int for_dw);
+// conv_igemm.hip: the register-staged kernel (takes every shape) and the few-channel col2im form of the data gradient
+void conv_forward_igemm(const ConvFwdCall& c);
+void conv_backward_data_igemm(const ConvDxCall& c);
+bool conv_small_c_dx_wanted(const ConvShape& s, int);
+void conv_backward_data_small_c(const ConvDxCall& c);
 // conv_direct.hip: pulls a small input into the Infinity Cache ahead of a kernel that streams a large output
 void conv_prefetch_input(const float* x, const ConvShape& s, float* sink);
-
-// ---- data gradient ---------------------------------------------------------------------------------------------------
-bool conv_backward_data_winograd43(const float* w, const float* dy, float* dx, const ConvShape& s);       // conv_winograd43.hip
-bool conv_backward_data_winograd_fused(const float* w, const float* dy, float* dx, const ConvShape& s);  // conv_winograd_fused.hip
-bool conv_backward_data_winograd(const float* w, const float* dy, float* dx, const ConvShape& s);        // conv_winograd.hip
-bool conv_backward_data_large(const float* w, const float* dy, float* dx, const ConvShape& s);           // conv_large.hip
-// conv_igemm.hip: the few-channel col2im form, the LDS-DMA GEMM, else the register-staged kernel (takes every shape).
-// bs (optional): the backward sums of a batch-norm node in front, emitted by the kernels that can (bs->splits > 0)
-void conv_backward_data(const float* w, const float* dy, float* dx, const ConvShape& s, DxBnSums* bs = nullptr);
-bool conv_dx_small_c_takes(const ConvShape& s);  // conv_igemm.hip: the few-channel form takes the layer (reads w as it is)
-bool conv_backward_data_dma(const float* w, const float* dy, float* dx, const ConvShape& s, DxBnSums* bs);  // conv_igemm_dma.hip
 
 // ---- weight gradient: dw += dy (x) x, one signature for every family (the rows of kDwFamilies, conv.hip). `workspace` takes
 // the split partials and is checked against the family's own *_workspace_floats(s) (0: not its shape); *bias_done is set when

@@ -375,14 +375,15 @@ static bool window_ok(const ConvShape& s) {
            (long long)s.N * s.F * s.OHOW < (1LL << 29) && (long long)s.N * s.C * s.HW < (1LL << 29) && s.OH >= 1 && s.OW >= 1;
 }
 
-bool conv_forward_window(const float* x, const float* w, const float* bias, const float* slopes, float* y, const ConvShape& s,
-                         int act, int raw) {
-    if (!window_ok(s)) return false;
+bool conv_window_fwd_wanted(const ConvShape& s, int) { return window_ok(s); }
+
+void conv_forward_window(const ConvFwdCall& c) {
+    const ConvShape& s = c.s;
     constexpr int R = WABL_FWD_R;
     ConvWindowFwdArgs a;
-    a.x = x; a.w = w; a.bias = bias; a.slopes = slopes; a.y = y; a.s = s;
-    a.act = raw ? BCNN_HIP_ACT_NONE : act;
-    a.add_bias = raw ? 0 : 1;
+    a.x = c.x; a.w = c.w; a.bias = c.bias; a.slopes = c.slopes; a.y = c.y; a.s = s;
+    a.act = c.raw ? BCNN_HIP_ACT_NONE : c.act;
+    a.add_bias = c.raw ? 0 : 1;
     a.strips = ceil_div(s.OH, R);
     const int tm = (s.Mg <= 32) ? 1 : 2;
     const int actm = (a.act == BCNN_HIP_ACT_NONE) ? 0 : (a.act == BCNN_HIP_ACT_RELU ? 1 : 2);
@@ -411,7 +412,6 @@ bool conv_forward_window(const float* x, const float* w, const float* bias, cons
 #undef LAUNCH3
 #undef LAUNCH4
     KERNEL_CHECK();
-    return true;
 }
 
 // ================================================================================================
@@ -661,14 +661,16 @@ static bool stem_ok(const ConvShape& s) {
 }
 
 // stats (optional, raw mode only): room for F * splits * 2 floats is checked against stats->capacity
-bool conv_forward_stem(const float* x, const float* w, const float* bias, const float* slopes, float* y, const ConvShape& s,
-                       int act, int raw, ConvStats* stats) {
-    if (stats) stats->splits = 0;
-    if (!stem_ok(s)) return false;
+bool conv_stem_fwd_wanted(const ConvShape& s, int) { return stem_ok(s); }
+
+void conv_forward_stem(const ConvFwdCall& c) {
+    const ConvShape& s = c.s;
+    ConvStats* stats = c.stats;
+    const int raw = c.raw;
     constexpr int R = STEM_R;
     ConvStemFwdArgs a;
-    a.x = x; a.w = w; a.bias = bias; a.slopes = slopes; a.y = y; a.s = s;
-    a.act = raw ? BCNN_HIP_ACT_NONE : act;
+    a.x = c.x; a.w = c.w; a.bias = c.bias; a.slopes = c.slopes; a.y = c.y; a.s = s;
+    a.act = raw ? BCNN_HIP_ACT_NONE : c.act;
     a.add_bias = raw ? 0 : 1;
     a.strips = ceil_div(s.OH, R);
     a.splits = s.N * a.strips * 2;
@@ -688,7 +690,6 @@ bool conv_forward_stem(const float* x, const float* w, const float* bias, const 
 #undef SLAUNCH3
     KERNEL_CHECK();
     if (want_stats) stats->splits = a.splits;
-    return true;
 }
 
 // ================================================================================================

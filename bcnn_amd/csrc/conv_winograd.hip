@@ -327,29 +327,30 @@ static double wino_flops(const ConvShape& s) {
 // the same without the tiles' overhang on odd-sized planes (7 x 7: 16 tiles cover 8 x 8)
 static double wino_useful_flops(const ConvShape& s) { return 2.0 * 16.0 * ((double)s.N * s.H * s.W / 4.0) * s.C * s.F; }
 
-// Returns false when the layer stays on the direct kernels.
-bool conv_winograd_unfused_takes(const ConvShape& s) { return wino_applicable(s) && wino_profitable(s); }
+// false: the layer stays on the direct kernels
+bool conv_winograd_fwd_wanted(const ConvShape& s, int) { return wino_applicable(s) && wino_profitable(s); }
 
-bool conv_forward_winograd(const float* x, const float* w, const float* bias, const float* slopes, float* y,
-                           const ConvShape& s, int act, int raw, ConvStats* stats) {
-    if (!wino_applicable(s) || !wino_profitable(s)) return false;
+void conv_forward_winograd(const ConvFwdCall& c) {
+    const ConvShape& s = c.s;
     KTimer kt(K_CONV_FWD_WINO, wino_flops(s), conv_gemm_bytes(s), wino_useful_flops(s));
     trace_kernel("wino_unfused:fwd");
-    const bool plain = raw || (bias == nullptr && act == BCNN_HIP_ACT_NONE);
+    const bool plain = c.raw || (c.bias == nullptr && c.act == BCNN_HIP_ACT_NONE);
     // raw output for a fused batch-norm: the output transform also emits the per-channel statistics partials
     // (ceil(T / 256) <= ceil(N*OH*OW / 64) entries per channel: inside the buffer conv.hip sized)
-    wino_run(x, w, y, s, /*dx_mode=*/0, bias, slopes, raw ? BCNN_HIP_ACT_NONE : act, plain, raw ? stats : nullptr);
-    if (stats && !raw) stats->splits = 0;
-    return true;
+    wino_run(c.x, c.w, c.y, s, /*dx_mode=*/0, c.bias, c.slopes, c.raw ? BCNN_HIP_ACT_NONE : c.act, plain,
+             c.raw ? c.stats : nullptr);
 }
 
-bool conv_backward_data_winograd(const float* w, const float* dy, float* dx, const ConvShape& s) {
-    if (!wino_applicable(s) || !wino_profitable(s)) return false;
-    // dX is itself a 3x3 / s1 / p1 convolution of dy [N][F][H][W] with F and C swapped
-    if (s.F < 16 || s.C < 64) return false;
+// dX is itself a 3x3 / s1 / p1 convolution of dy [N][F][H][W] with F and C swapped
+bool conv_winograd_dx_wanted(const ConvShape& s, int) {
+    return wino_applicable(s) && wino_profitable(s) && s.F >= 16 && s.C >= 64;
+}
+
+void conv_backward_data_winograd(const ConvDxCall& c) {
+    const ConvShape& s = c.s;
     KTimer kt(K_CONV_DX_WINO, wino_flops(s), conv_gemm_bytes(s), wino_useful_flops(s));
-    wino_run(dy, w, dx, s, /*dx_mode=*/1, nullptr, nullptr, BCNN_HIP_ACT_NONE, true);
-    return true;
+    trace_kernel("wino_unfused:dx");
+    wino_run(c.dy, c.w, c.dx, s, /*dx_mode=*/1, nullptr, nullptr, BCNN_HIP_ACT_NONE, true);
 }
 
 // ---- weight gradient -----------------------------------------------------------------------------------------

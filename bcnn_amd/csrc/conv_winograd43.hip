@@ -82,11 +82,10 @@ static bool wino43_usable(const float* src, const float* dst, const ConvShape& s
     return true;
 }
 
-// bcnn_hip_conv_prepack: the 36-position pack this layer's forward (dx_mode 0, raw form) / data-gradient (1) kernel will ask
-// prepack_take for; false when the layer does not run here
+// bcnn_hip_conv_prepack: the 36-position pack a wanted layer's forward (dx_mode 0, raw form) / data-gradient (1) kernel will
+// ask prepack_take for
 bool wino43_pack_plan(const ConvShape& s, int dx_mode, WinoPackJob* job, size_t* floats) {
     const int J = dx_mode ? s.F : s.C, M = dx_mode ? s.C : s.F;
-    if (!wino43_wanted(s, J, M)) return false;
     job->w = nullptr; job->u = nullptr;
     job->F = s.F; job->C = s.C; job->dx_mode = dx_mode;
     job->Jpad = (J + W4_KC - 1) / W4_KC * W4_KC;
@@ -107,24 +106,26 @@ static double w43_flops(const ConvShape& s) { return 2.0 * 36.0 * ((double)s.N *
 static double w43_useful_flops(const ConvShape& s) { return 2.0 * 36.0 * ((double)s.N * s.H * s.W / 16.0) * s.C * s.F; }
 
 // raw output only (a fused batch-norm behind it, or a caller that adds nothing): the other forms stay on F(2x2, 3x3)
-bool conv_forward_winograd43(const float* x, const float* w, float* y, const ConvShape& s, int raw, ConvStats* stats) {
-    if (!raw || !wino43_wanted(s, s.C, s.F) || !wino43_usable(x, y, s, 0, stats)) return false;
+bool conv_winograd43_fwd_wanted(const ConvShape& s, int raw) { return raw && wino43_wanted(s, s.C, s.F); }
+bool conv_winograd43_fwd_usable(const ConvFwdCall& c) { return wino43_usable(c.x, c.y, c.s, 0, c.stats); }
+void conv_forward_winograd43(const ConvFwdCall& c) {
+    const ConvShape& s = c.s;
     KTimer kt(K_CONV_FWD_WINO43, w43_flops(s), conv_gemm_bytes(s), w43_useful_flops(s));
-    if (wino43_second_form(s)) wino43b_run(x, w, y, s, 0, stats);
+    if (wino43_second_form(s)) wino43b_run(c.x, c.w, c.y, s, 0, c.stats);
 #ifdef BCNN_HIP_EXPERIMENT
-    else wino43_run(x, w, y, s, 0, stats);
+    else wino43_run(c.x, c.w, c.y, s, 0, c.stats);
 #endif
-    return true;
 }
 
-bool conv_backward_data_winograd43(const float* w, const float* dy, float* dx, const ConvShape& s) {
-    if (!wino43_wanted(s, s.F, s.C) || !wino43_usable(dy, dx, s, 1, nullptr)) return false;
+bool conv_winograd43_dx_wanted(const ConvShape& s, int) { return wino43_wanted(s, s.F, s.C); }
+bool conv_winograd43_dx_usable(const ConvDxCall& c) { return wino43_usable(c.dy, c.dx, c.s, 1, nullptr); }
+void conv_backward_data_winograd43(const ConvDxCall& c) {
+    const ConvShape& s = c.s;
     KTimer kt(K_CONV_DX_WINO43, w43_flops(s), conv_gemm_bytes(s), w43_useful_flops(s));
-    if (wino43_second_form(s)) wino43b_run(dy, w, dx, s, 1, nullptr);
+    if (wino43_second_form(s)) wino43b_run(c.dy, c.w, c.dx, s, 1, nullptr);
 #ifdef BCNN_HIP_EXPERIMENT
-    else wino43_run(dy, w, dx, s, 1, nullptr);
+    else wino43_run(c.dy, c.w, c.dx, s, 1, nullptr);
 #endif
-    return true;
 }
 
 }  // namespace bcnn_hip

@@ -441,6 +441,7 @@ void wino43b_run(const float* src, const float* w, float* dst, const ConvShape& 
     a.upk_bytes = (unsigned)(u_floats * 4);
     float* U = prepack_take(w, PREPACK_WINO, dx_mode, u_floats);  // transformed ahead by bcnn_hip_conv_prepack?
     if (!U) {
+        trace_kernel("pack:self");
         U = scratch(SCRATCH_WINO43_U, u_floats);
         wino43b_pack_weights_kernel<<<ceil_div((long long)Jpad * Mpad, 256), 256, 0, current_stream()>>>(w, U, s.F, s.C, dx_mode, Jpad,
                                                                                                            Mpad);

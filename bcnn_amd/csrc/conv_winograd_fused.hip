@@ -559,6 +559,7 @@ static void wino_fused_run(const float* src, const float* w, float* dst, const C
         a.upk_bytes = (unsigned)(u_floats * 4);
         float* U = prepack_take(w, PREPACK_WINO, dx_mode, u_floats);  // transformed ahead by bcnn_hip_conv_prepack?
         if (!U) {
+            trace_kernel("pack:self");
             U = scratch(SCRATCH_WFUSED_U, u_floats);
             wino_pack_weights_kernel<<<ceil_div((long long)a.Jpad * a.Mpad, 256), 256, 0, current_stream()>>>(w, U, s.F, s.C, dx_mode,
                                                                                                             a.Jpad, a.Mpad);
@@ -624,14 +625,11 @@ static void wino_fused_run(const float* src, const float* w, float* dst, const C
     if (stats) stats->splits = a.stats ? 2 * a.tblocks : 0;
 }
 
-// bcnn_hip_conv_prepack: the transformed weights this layer's forward (dx_mode 0) / data-gradient (1) kernel will ask
-// prepack_take for; false when the layer does not run on wino_fused_kernel
+// bcnn_hip_conv_prepack: the transformed weights a wanted layer's forward (dx_mode 0) / data-gradient (1) kernel will ask
+// prepack_take for; false when the split-bf16 experiment takes the layer, which reads no fp32 pack
 bool wino_fused_pack_plan(const ConvShape& s, int dx_mode, WinoPackJob* job, size_t* floats) {
     const int J = dx_mode ? s.F : s.C, M = dx_mode ? s.C : s.F;
-    // the F(4x4,3x3) kernel is asked first by both passes (its forward only in the raw form: a layer without a batch-norm
-    // behind it then packs for itself, like every layer whose planned kernel does not run)
-    if (wino43_pack_plan(s, dx_mode, job, floats)) return true;
-    if (!wino_fused_wanted(s, J, M) || wino_bf16_parts(J) != 0) return false;
+    if (wino_bf16_parts(J) != 0) return false;
     job->w = nullptr; job->u = nullptr;
     job->F = s.F; job->C = s.C; job->dx_mode = dx_mode;
     job->Jpad = (J + WF_KC - 1) / WF_KC * WF_KC;
@@ -655,20 +653,19 @@ static double wf_flops(const ConvShape& s) {
 // the same without the tiles' overhang on odd-sized planes (7 x 7: 16 tiles cover 8 x 8)
 static double wf_useful_flops(const ConvShape& s) { return 2.0 * 16.0 * ((double)s.N * s.H * s.W / 4.0) * s.C * s.F; }
 
-bool conv_forward_winograd_fused(const float* x, const float* w, const float* bias, const float* slopes, float* y,
-                                 const ConvShape& s, int act, int raw, ConvStats* stats) {
-    if (!wino_fused_wanted(s, s.C, s.F)) return false;
+bool conv_winograd_fused_fwd_wanted(const ConvShape& s, int) { return wino_fused_wanted(s, s.C, s.F); }
+void conv_forward_winograd_fused(const ConvFwdCall& c) {
+    const ConvShape& s = c.s;
     KTimer kt(K_CONV_FWD_WINO, wf_flops(s), conv_gemm_bytes(s), wf_useful_flops(s));
-    if (stats && !raw) stats->splits = 0;
-    wino_fused_run(x, w, y, s, 0, bias, slopes, raw ? BCNN_HIP_ACT_NONE : act, raw ? 0 : (bias != nullptr), raw ? stats : nullptr);
-    return true;
+    wino_fused_run(c.x, c.w, c.y, s, 0, c.bias, c.slopes, c.raw ? BCNN_HIP_ACT_NONE : c.act, c.raw ? 0 : (c.bias != nullptr),
+                   c.raw ? c.stats : nullptr);
 }
 
-bool conv_backward_data_winograd_fused(const float* w, const float* dy, float* dx, const ConvShape& s) {
-    if (!wino_fused_wanted(s, s.F, s.C)) return false;
+bool conv_winograd_fused_dx_wanted(const ConvShape& s, int) { return wino_fused_wanted(s, s.F, s.C); }
+void conv_backward_data_winograd_fused(const ConvDxCall& c) {
+    const ConvShape& s = c.s;
     KTimer kt(K_CONV_DX_WINO, wf_flops(s), conv_gemm_bytes(s), wf_useful_flops(s));
-    wino_fused_run(dy, w, dx, s, 1, nullptr, nullptr, BCNN_HIP_ACT_NONE, 0, nullptr);
-    return true;
+    wino_fused_run(c.dy, c.w, c.dx, s, 1, nullptr, nullptr, BCNN_HIP_ACT_NONE, 0, nullptr);
 }
 
 

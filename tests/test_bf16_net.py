@@ -12,7 +12,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 BF16_FAMILY = "conv_bf16_gemm_kernel"
-# what the fp32 forward families call themselves in the trace (conv_fwd_any and conv_forward_dispatch, conv.hip / conv_igemm.hip)
+# what the fp32 forward families call themselves in the trace (the rows of kConvFwdFamilies, conv.hip)
 FP32_FAMILIES = {"conv_fwd_window_kernel", "conv_fwd_stem_kernel", "conv_fwd_direct_kernel", "wino43b_kernel:fwd",
                  "wino_fused_kernel:fwd", "wino_unfused:fwd", "conv_large_gemm_kernel:fwd", "conv_igemm_dma_kernel:fwd",
                  "conv_igemm_kernel:fwd"}

@@ -88,8 +88,13 @@ def test_kernels_use_no_scratch(metadata, kernel, instances):
 
 def test_the_family_sits_in_front_of_the_catch_all_kernels():
     text = open(os.path.join(SRC, "conv.hip")).read()
-    assert text.index("conv_forward_large(") < text.index("conv_forward_dispatch(x, w, bias")
-    assert text.index("conv_backward_data_large(") < text.index("conv_backward_data(w, dy, dx, s, bs)")
+    for table, large, behind in (("kConvFwdFamilies", "conv_forward_large", ("conv_forward_dma_timed", "conv_forward_small_c",
+                                                                             "conv_forward_igemm")),
+                                 ("kConvDxFamilies", "conv_backward_data_large", ("conv_backward_data_small_c",
+                                                                                  "conv_backward_data_dma", "conv_backward_data_igemm"))):
+        rows = re.search(table + r"\[\]\s*=\s*\{(.*?)\n\};", text, re.S).group(1)
+        for name in behind:
+            assert rows.index(large) < rows.index(name), (table, name)
     rows = re.search(r"kDwFamilies\[\]\s*=\s*\{(.*?)\n\};", text, re.S).group(1)
     assert rows.index("conv_backward_weights_large") < rows.index("{conv_dw_workspace_floats")
     assert "conv_large.hip" in open(os.path.join(SRC, "Makefile")).read()
