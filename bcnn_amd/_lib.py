@@ -118,6 +118,9 @@ SIGNATURES = {
     "bcnn_hip_upsample_forward": (None, [vp, vp, i, i, i, i, i]),
     "bcnn_hip_upsample_backward": (None, [vp, vp, i, i, i, i, i]),
     "bcnn_hip_yolo_activate": (None, [vp, vp, i, i, i, i, i]),
+    "bcnn_hip_yolo_nms_capacity": (i, []),
+    "bcnn_hip_yolo_detect_result_words": (sz, [i, i, i]),
+    "bcnn_hip_yolo_detect_batch": (i, [vp, i, i, vp, i, i, i, i, f, i, f, i, i, vp]),
     "bcnn_hip_deconv_workspace_size": (sz, [i] * 8),
     "bcnn_hip_deconv_forward": (None, [vp, vp, vp, vp] + [i] * 9),
     "bcnn_hip_deconv_backward": (None, [vp] * 7 + [i] * 9 + [vp, sz]),

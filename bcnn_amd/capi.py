@@ -54,6 +54,18 @@ def detections_to_list(dets, count):
     return out
 
 
+def detections_batch_to_lists(L, dets, counts):
+    """copies a bcnn_yolo_get_detections_batch result (per-image arrays and counts) into one list of dicts per image and
+    frees every array through bcnn_free_detections"""
+    out = []
+    for b in range(len(counts)):
+        out.append([dict(x=d.x, y=d.y, w=d.w, h=d.h, objectness=d.objectness,
+                         prob=np.array(d.prob[:d.num_classes], np.float32))
+                    for d in (dets[b][k] for k in range(counts[b]))] if dets[b] else [])
+        L.bcnn_free_detections(dets[b], counts[b])
+    return out
+
+
 _lib = None
 
 
@@ -106,6 +118,9 @@ def lib():
         "bcnn_add_concat_layer": (i, [vp, i, C.POINTER(cp), cp]), "bcnn_add_upsample_layer": (i, [vp, i, cp, cp]),
         "bcnn_add_yolo_layer": (i, [vp, i, i, i, i, C.POINTER(i), C.POINTER(f), cp, cp]),
         "bcnn_yolo_get_detections": (C.POINTER(Detection), [vp, i, i, i, i, i, f, i, C.POINTER(i)]),
+        "bcnn_yolo_get_detections_batch": (i, [vp, C.POINTER(i), C.POINTER(i), i, i, f, i,
+                                               C.POINTER(C.POINTER(Detection)), C.POINTER(i)]),
+        "bcnn_free_detections": (None, [C.POINTER(Detection), i]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -216,6 +231,18 @@ class Net:
         n = C.c_int(0)
         dets = self.L.bcnn_yolo_get_detections(self.net, batch, w, h, netw, neth, thresh, relative, C.byref(n))
         return detections_to_list(dets, n.value)
+
+    def get_detections_batch(self, sizes, netw, neth, thresh, relative):
+        """bcnn_yolo_get_detections_batch: `sizes` holds the original (w, h) of every image of the batch; returns one
+        list of dicts per image, each like get_detections (equal objectness: by candidate index, see bcnn.h)"""
+        n = len(sizes)
+        assert n == self.L.bcnn_get_batch_size(self.net), "one (w, h) per image of the batch"
+        ws, hs = (C.c_int * n)(*[s[0] for s in sizes]), (C.c_int * n)(*[s[1] for s in sizes])
+        dets, counts = (C.POINTER(Detection) * n)(), (C.c_int * n)()
+        st = self.L.bcnn_yolo_get_detections_batch(self.net, ws, hs, netw, neth, thresh, relative, dets, counts)
+        if st != 0:
+            raise ValueError("bcnn_yolo_get_detections_batch failed with status %d" % st)
+        return detections_batch_to_lists(self.L, dets, counts)
 
     @classmethod
     def load_net(cls, config_path, model_path=None, mode=MODE_PREDICT, silent=True):

@@ -172,6 +172,193 @@ __global__ __launch_bounds__(256) void yolo_activate_kernel(const float* __restr
         y[k] = yolo_entry(x[k], (int)((k / hw) % channels), per_box, coords);
 }
 
+// ---- detections of a batch ------------------------------------------------------------------------------------------
+// Reference bcnn_yolo.c:470-639 (one image per call, on the host, after reading every head back). Here: one candidate
+// launch and one NMS launch for the whole batch; a few thousand lanes per image, launch-bound work.
+constexpr int kDetBlock = 1024;        // lanes per workgroup of both kernels (16 waves)
+constexpr int kDetWaves = kDetBlock / kWave;
+constexpr int kRecHead = BCNN_HIP_YOLO_RECORD_HEAD;  // x, y, w, h, objectness, candidate index; prob follows
+// Boxes per image the NMS kernel holds in LDS: 16 B box + 4 B key + 4 B slot + 1 B live flag = 25 B each, 50 KB.
+constexpr int kNmsCapacity = 2048;
+
+struct YoloTable {
+    bcnn_hip_yolo_head head[BCNN_HIP_YOLO_MAX_HEADS];
+    int first[BCNN_HIP_YOLO_MAX_HEADS + 1];  // candidate index of a head's (cell 0, anchor 0); [nheads] = candidates per image
+};
+
+// head of candidate g, and g's index inside it (cell * num + anchor)
+__device__ __forceinline__ int yolo_locate(const YoloTable& tab, int nheads, int g, int* local) {
+    int k = 0;
+    while (k + 1 < nheads && g >= tab.first[k + 1]) ++k;
+    *local = g - tab.first[k];
+    return k;
+}
+
+// entry_index of bcnn_yolo.c:207-215: image b, anchor a, entry e, cell
+__device__ __forceinline__ size_t yolo_entry_index(const bcnn_hip_yolo_head& hd, int b, int a, int e, int cell) {
+    const int hw = hd.h * hd.w;
+    return ((size_t)(b * hd.num + a) * (hd.coords + hd.classes + 1) + e) * hw + cell;
+}
+
+__device__ __forceinline__ float yolo_objectness(const YoloTable& tab, int nheads, int b, int g) {
+    int local;
+    const bcnn_hip_yolo_head& hd = tab.head[yolo_locate(tab, nheads, g, &local)];
+    return hd.out_d[yolo_entry_index(hd, b, local % hd.num, hd.coords, local / hd.num)];
+}
+
+// grid (chunks of kDetBlock candidates, images). A workgroup counts the survivors of the chunks in front of its own
+// (objectness only: at most a few reads per lane), then ranks its own survivors by wave ballot + wave offsets.
+__global__ __launch_bounds__(kDetBlock) void yolo_candidates_kernel(YoloTable tab, int nheads,
+                                                                     const int4* __restrict__ geom, int in_w, int in_h,
+                                                                     int netw, int neth, float thresh, int relative,
+                                                                     int cap, int stride, int* __restrict__ count,
+                                                                     float* __restrict__ records) {
+    __shared__ int wave_before[kDetWaves], wave_own[kDetWaves];
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid / kWave;
+    const int total = tab.first[nheads];
+    const int g0 = blockIdx.x * kDetBlock;  // < total by the launch shape
+
+    int before = 0;  // this wave's share of the survivors in [0, g0): wave-uniform
+    for (int g = tid; g < g0; g += kDetBlock)
+        before += __popcll(__ballot(yolo_objectness(tab, nheads, b, g) > thresh));
+
+    const int g = g0 + tid;
+    float objectness = 0.f;
+    if (g < total) objectness = yolo_objectness(tab, nheads, b, g);
+    const bool keep = g < total && objectness > thresh;
+    const unsigned long long vote = __ballot(keep);
+    if (lane == 0) {
+        wave_before[wid] = before;
+        wave_own[wid] = __popcll(vote);
+    }
+    __syncthreads();
+    int pos = 0, all = 0;
+    for (int w = 0; w < kDetWaves; ++w) {
+        pos += wave_before[w] + (w < wid ? wave_own[w] : 0);
+        all += wave_before[w] + wave_own[w];
+    }
+    pos += __popcll(vote & ((1ull << lane) - 1ull));
+    if (blockIdx.x == gridDim.x - 1 && tid == 0) count[b] = all;  // the true count, whatever cap is
+    if (!keep || pos >= cap) return;
+
+    int local;
+    const bcnn_hip_yolo_head& hd = tab.head[yolo_locate(tab, nheads, g, &local)];
+    const int a = local % hd.num, cell = local / hd.num, hw = hd.h * hd.w;
+    const int row = cell / hd.w, col = cell % hd.w;
+    const float* x = hd.out_d + yolo_entry_index(hd, b, a, 0, cell);
+    // get_yolo_box, bcnn_yolo.c:137-145
+    float bx = ((float)col + x[0]) / (float)hd.w;
+    float by = ((float)row + x[hw]) / (float)hd.h;
+    float bw = expf(x[2 * hw]) * hd.anchor_w[a] / (float)in_w;
+    float bh = expf(x[3 * hw]) * hd.anchor_h[a] / (float)in_h;
+    // correct_region_boxes, bcnn_yolo.c:99-128: the offsets are double there, the scales float
+    const int4 gm = geom[b];  // w, h, new_w, new_h
+    bx = (float)(((double)bx - (double)(netw - gm.z) / 2. / (double)netw) / (double)((float)gm.z / (float)netw));
+    by = (float)(((double)by - (double)(neth - gm.w) / 2. / (double)neth) / (double)((float)gm.w / (float)neth));
+    bw = bw * ((float)netw / (float)gm.z);
+    bh = bh * ((float)neth / (float)gm.w);
+    if (!relative) {
+        bx = bx * (float)gm.x;
+        bw = bw * (float)gm.x;
+        by = by * (float)gm.y;
+        bh = bh * (float)gm.y;
+    }
+    float* r = records + ((size_t)b * cap + pos) * stride;
+    r[0] = bx;
+    r[1] = by;
+    r[2] = bw;
+    r[3] = bh;
+    r[4] = objectness;
+    r[5] = __int_as_float(g);
+    const float* cls = x + (size_t)(hd.coords + 1) * hw;
+    for (int j = 0; j < hd.classes; ++j) {
+        const float p = objectness * cls[(size_t)j * hw];
+        r[kRecHead + j] = p > thresh ? p : 0.f;
+    }
+    for (int j = kRecHead + hd.classes; j < stride; ++j) r[j] = 0.f;
+}
+
+// overlap / box_iou of bcnn_yolo.c:15-53, operation for operation (contraction is off for this library)
+__device__ __forceinline__ float yolo_overlap(float x1, float w1, float x2, float w2) {
+    const float l1 = x1 - w1 / 2, l2 = x2 - w2 / 2;
+    const float left = l1 > l2 ? l1 : l2;
+    const float r1 = x1 + w1 / 2, r2 = x2 + w2 / 2;
+    const float right = r1 < r2 ? r1 : r2;
+    return right - left;
+}
+__device__ __forceinline__ float yolo_box_iou(float4 a, float4 b) {  // (x, y, z, w) = box (x, y, w, h)
+    const float w = yolo_overlap(a.x, a.z, b.x, b.z), h = yolo_overlap(a.y, a.w, b.y, b.w);
+    const float inter = (w < 0 || h < 0) ? 0 : w * h;
+    return inter / (a.z * a.w + b.z * b.w - inter);
+}
+
+// (objectness descending, slot ascending): the slot order is the candidate order
+__device__ __forceinline__ bool det_before(float ka, int ia, float kb, int ib) {
+    return ka > kb || (ka == kb && ia < ib);
+}
+
+// One workgroup per image. Bitonic sort of the keys on the power-of-two padding, then the greedy walk: one barrier per
+// box, the lanes behind a live box i test it against the boxes j > i.
+__global__ __launch_bounds__(kDetBlock) void yolo_nms_kernel(const int* __restrict__ count, int cap, int nms_cap,
+                                                              int stride, float nms_thresh, int* __restrict__ order,
+                                                              float* __restrict__ records) {
+    __shared__ float4 box[kNmsCapacity];
+    __shared__ float key[kNmsCapacity];
+    __shared__ int slot[kNmsCapacity];
+    __shared__ unsigned char live[kNmsCapacity];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int cnt = count[b];
+    if (cnt <= 0 || cnt > cap || cnt > nms_cap) return;  // nothing to do / the pass is run again / the caller's NMS
+    float* rec = records + (size_t)b * cap * stride;
+    int padded = 1;
+    while (padded < cnt) padded <<= 1;  // <= kNmsCapacity, a power of two: cnt <= nms_cap <= kNmsCapacity
+    for (int t = tid; t < padded; t += kDetBlock) {
+        key[t] = t < cnt ? rec[(size_t)t * stride + 4] : -INFINITY;
+        slot[t] = t < cnt ? t : 0x7fffffff;
+    }
+    __syncthreads();
+    for (int k = 2; k <= padded; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < padded; t += kDetBlock) {
+                const int u = t ^ j;
+                if (u > t) {
+                    const float kt = key[t], ku = key[u];
+                    const int it = slot[t], iu = slot[u];
+                    const bool swap = (t & k) == 0 ? det_before(ku, iu, kt, it) : det_before(kt, it, ku, iu);
+                    if (swap) {
+                        key[t] = ku; key[u] = kt;
+                        slot[t] = iu; slot[u] = it;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    for (int t = tid; t < cnt; t += kDetBlock) {
+        const float* r = rec + (size_t)slot[t] * stride;
+        box[t] = make_float4(r[0], r[1], r[2], r[3]);
+        live[t] = key[t] != 0.f;  // do_nms_obj: a box without objectness neither suppresses nor is suppressed
+    }
+    __syncthreads();
+    for (int i = 0; i < cnt; ++i) {
+        if (live[i]) {  // the same value in every lane: written before the barrier that ended step i - 1
+            const float4 a = box[i];
+            for (int j = i + 1 + tid; j < cnt; j += kDetBlock)
+                if (live[j] && yolo_box_iou(a, box[j]) > nms_thresh) live[j] = 0;
+        }
+        __syncthreads();
+    }
+    for (int t = tid; t < cnt; t += kDetBlock) {
+        const int s = slot[t];
+        if (!live[t]) {
+            float* r = rec + (size_t)s * stride;
+            r[4] = 0.f;
+            for (int j = kRecHead; j < stride; ++j) r[j] = 0.f;
+        }
+        order[(size_t)b * cap + t] = live[t] ? s : (int)(0x80000000u | (unsigned)s);
+    }
+}
+
 }  // namespace bcnn_hip
 
 using namespace bcnn_hip;
@@ -258,6 +445,58 @@ void bcnn_hip_yolo_activate(const float* x_d, float* y_d, int n, int num, int co
     yolo_activate_kernel<<<stream_grid(vec ? total / 4 + 1 : total, 256), 256, 0, current_stream()>>>(
         x_d, y_d, hw, num * per_box, per_box, coords, total, vec);
     KERNEL_CHECK();
+}
+
+int bcnn_hip_yolo_nms_capacity(void) { return kNmsCapacity; }
+
+size_t bcnn_hip_yolo_detect_result_words(int n, int record_cap, int max_classes) {
+    if (n <= 0 || record_cap <= 0 || max_classes < 0) return 0;
+    return (size_t)n + (size_t)n * record_cap * (1 + kRecHead + max_classes);
+}
+
+int bcnn_hip_yolo_detect_batch(const bcnn_hip_yolo_head* heads, int num_heads, int n, const int* image_geom, int in_w,
+                               int in_h, int netw, int neth, float thresh, int relative, float nms_thresh,
+                               int record_cap, int nms_cap, void* result_host) {
+    if (!heads || !image_geom || !result_host || num_heads < 1 || num_heads > BCNN_HIP_YOLO_MAX_HEADS || n < 1 || n > 65535 ||
+        record_cap < 1 || in_w < 1 || in_h < 1 || netw < 1 || neth < 1)
+        return 1;
+    YoloTable tab = {};
+    int max_classes = 0;
+    long long total = 0;
+    for (int k = 0; k < num_heads; ++k) {
+        const bcnn_hip_yolo_head& hd = heads[k];
+        if (!hd.out_d || hd.h < 1 || hd.w < 1 || hd.num < 1 || hd.num > BCNN_HIP_YOLO_MAX_ANCHORS || hd.coords < 4 ||
+            hd.classes < 0)
+            return 1;
+        tab.head[k] = hd;
+        tab.first[k] = (int)total;
+        total += (long long)hd.h * hd.w * hd.num;
+        if (total > (1ll << 30)) return 1;
+        if (hd.classes > max_classes) max_classes = hd.classes;
+    }
+    for (int k = num_heads; k <= BCNN_HIP_YOLO_MAX_HEADS; ++k) tab.first[k] = (int)total;
+    for (int b = 0; b < n; ++b)
+        if (image_geom[4 * b] < 1 || image_geom[4 * b + 1] < 1) return 1;
+    if (nms_cap <= 0 || nms_cap > kNmsCapacity) nms_cap = kNmsCapacity;
+    const int stride = kRecHead + max_classes;
+    const size_t result_words = bcnn_hip_yolo_detect_result_words(n, record_cap, max_classes);
+    if ((size_t)n * record_cap > (size_t)0x7fffffff) return 1;
+    // [geom n x 4][count n][order n x cap][records n x cap x stride]; the last three are the result, copied as one block
+    float* base = scratch(SCRATCH_DETECT, (size_t)4 * n + result_words);
+    int4* geom_d = reinterpret_cast<int4*>(base);
+    int* count_d = reinterpret_cast<int*>(base) + (size_t)4 * n;
+    int* order_d = count_d + n;
+    float* records_d = reinterpret_cast<float*>(order_d + (size_t)n * record_cap);
+    hipStream_t st = current_stream();
+    HIP_CHECK(hipMemcpyAsync(geom_d, image_geom, (size_t)4 * n * sizeof(int), hipMemcpyHostToDevice, st));
+    const dim3 grid(ceil_div(total, kDetBlock), n);
+    yolo_candidates_kernel<<<grid, kDetBlock, 0, st>>>(tab, num_heads, geom_d, in_w, in_h, netw, neth, thresh,
+                                                       relative, record_cap, stride, count_d, records_d);
+    KERNEL_CHECK();
+    yolo_nms_kernel<<<n, kDetBlock, 0, st>>>(count_d, record_cap, nms_cap, stride, nms_thresh, order_d, records_d);
+    KERNEL_CHECK();
+    HIP_CHECK(hipMemcpyAsync(result_host, count_d, result_words * sizeof(float), hipMemcpyDeviceToHost, st));
+    return 0;
 }
 
 }  // extern "C"

@@ -36,6 +36,7 @@ static constexpr ScratchPolicy kScratchPolicy[] = {  // in ScratchSlot order
     /* WFUSED_TAIL   */ {0, 1, 1},
     /* W43FF_U       */ {1u << 20, 1, 1},
     /* W43FF_TAIL    */ {0, 1, 1},
+    /* DETECT        */ {1u << 16, 1, 1},  // the caller's record capacity already carries the headroom
 };
 static_assert(sizeof(kScratchPolicy) / sizeof(kScratchPolicy[0]) == SCRATCH_SLOTS, "one policy row per ScratchSlot");
 struct ScratchBlock { float* p = nullptr; size_t cap = 0; };

@@ -168,6 +168,8 @@ typedef struct bcnn_hip_context {
     int no_side_stream; /* bcnn_set_weight_gradient_stream(net, 0) */
     uint64_t dropout_seed; /* bcnn_set_dropout_seed; 0 until set */
     int inference_precision; /* bcnn_set_inference_precision (a bcnn_precision); read by the convolution node outside TRAIN mode */
+    int detect_capacity; /* 1.25 x the most boxes an image of the latest bcnn_yolo_get_detections_batch had: the next call's record capacity
+                          * when above the default (0: never called) */
 } bcnn_hip_context;
 
 /* ---- net ------------------------------------------------------------------------------------------ */
@@ -463,6 +465,10 @@ void bcnn_backward_upsample_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_forward_yolo_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_yolo_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_yolo_layer(bcnn_node *node);
+/* bcnn_yolo_get_detections_batch with its capacities exposed (bcnn_layers_detect.c; exported for the tests) */
+bcnn_status bcnn_yolo_detections_batch_worker(bcnn_net *net, const int *widths, const int *heights, int netw, int neth,
+                                              float thresh, int relative, int record_cap, int nms_cap,
+                                              bcnn_output_detection **dets, int *num_dets, int *passes);
 void bcnn_forward_deconv_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_deconv_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_update_deconv_layer(bcnn_net *net, bcnn_node *node);

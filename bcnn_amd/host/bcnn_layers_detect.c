@@ -240,6 +240,8 @@ static int by_objectness_desc(const void *pa, const void *pb) {
     return diff < 0 ? 1 : (diff > 0 ? -1 : 0);
 }
 
+static void suppress_sorted(bcnn_output_detection *dets, int num_dets, float thresh);
+
 static void do_nms_obj(bcnn_output_detection *dets, int num_dets, float thresh) {
     int k = num_dets - 1;
     for (int i = 0; i <= k; ++i) { /* zero-objectness boxes to the end, outside the sort */
@@ -253,6 +255,11 @@ static void do_nms_obj(bcnn_output_detection *dets, int num_dets, float thresh) 
     }
     num_dets = k + 1;
     qsort(dets, (size_t)num_dets, sizeof(bcnn_output_detection), by_objectness_desc);
+    suppress_sorted(dets, num_dets, thresh);
+}
+
+/* the greedy walk of do_nms_obj over boxes already in their final order */
+static void suppress_sorted(bcnn_output_detection *dets, int num_dets, float thresh) {
     for (int i = 0; i < num_dets; ++i) {
         if (dets[i].objectness == 0) continue;
         const yolo_box a = {dets[i].x, dets[i].y, dets[i].w, dets[i].h};
@@ -321,4 +328,210 @@ bcnn_output_detection *bcnn_yolo_get_detections(bcnn_net *net, int batch, int w,
     do_nms_obj(dets, count, 0.45f);
     if (num_dets) *num_dets = count;
     return dets;
+}
+
+/* ================================================================================================
+ * detections of the whole batch, decoded / filtered / suppressed on the device (detect.hip: bcnn_hip_yolo_detect_batch).
+ * What comes back is one block -- the counts, the sort order and the compact box records -- whose size depends on the
+ * record capacity, not on the head tensors; the head tensors are never read back.
+ * ============================================================================================== */
+#define DETECT_RECORD_CAPACITY 256 /* boxes per image the first pass has room for, until a batch needed more */
+#define DETECT_NMS_THRESH 0.45f    /* reference bcnn_yolo.c:637 */
+
+typedef struct {
+    float objectness;
+    int index;
+} det_key;
+
+static int by_objectness_then_index(const void *pa, const void *pb) {
+    const det_key *a = (const det_key *)pa, *b = (const det_key *)pb;
+    if (a->objectness != b->objectness) return a->objectness < b->objectness ? 1 : -1;
+    return a->index < b->index ? -1 : (a->index > b->index ? 1 : 0);
+}
+
+/* one record -> one detection (prob and mask calloc'ed like bcnn_yolo_get_detections does); 0 on failure */
+static int detection_from_record(bcnn_output_detection *d, const float *rec, const bcnn_hip_yolo_head *heads,
+                                 int num_heads) {
+    int g, first = 0, k = 0;
+    memcpy(&g, &rec[5], sizeof(g));
+    for (; k < num_heads; ++k) {
+        const int cnt = heads[k].h * heads[k].w * heads[k].num;
+        if (g >= first && g < first + cnt) break;
+        first += cnt;
+    }
+    if (k == num_heads) return 0;
+    const int classes = heads[k].classes, coords = heads[k].coords;
+    d->x = rec[0];
+    d->y = rec[1];
+    d->w = rec[2];
+    d->h = rec[3];
+    d->objectness = rec[4];
+    d->num_classes = classes;
+    d->prob = (float *)calloc((size_t)(classes > 0 ? classes : 1), sizeof(float));
+    if (!d->prob) return 0;
+    memcpy(d->prob, rec + BCNN_HIP_YOLO_RECORD_HEAD, (size_t)classes * sizeof(float));
+    if (coords > 4) {
+        d->mask = (float *)calloc((size_t)(coords - 4), sizeof(float));
+        if (!d->mask) return 0;
+    }
+    return 1;
+}
+
+void bcnn_free_detections(bcnn_output_detection *dets, int num_dets) {
+    if (!dets) return;
+    for (int i = 0; i < num_dets; ++i) {
+        free(dets[i].prob);
+        free(dets[i].mask);
+    }
+    free(dets);
+}
+
+/* bcnn_yolo_get_detections_batch with its two capacities as arguments (<= 0: the defaults), so that a test can drive
+ * the grow-and-rerun path and the host-NMS path with a dozen boxes. record_cap: boxes per image the first pass has room
+ * for; nms_cap: boxes per image the device NMS takes (at most bcnn_hip_yolo_nms_capacity()). *passes (may be NULL)
+ * receives how many times the kernels ran (1, or 2 after a grow). */
+bcnn_status bcnn_yolo_detections_batch_worker(bcnn_net *net, const int *widths, const int *heights, int netw, int neth,
+                                              float thresh, int relative, int record_cap, int nms_cap,
+                                              bcnn_output_detection **dets, int *num_dets, int *passes) {
+    if (!net || !widths || !heights || !dets || !num_dets || netw <= 0 || neth <= 0) return BCNN_INVALID_PARAMETER;
+    bcnn_hip_context *hc = (bcnn_hip_context *)net->hip_ctx;
+    bcnn_hip_yolo_head heads[BCNN_HIP_YOLO_MAX_HEADS];
+    int num_heads = 0, n = 0, max_classes = 0;
+    memset(heads, 0, sizeof(heads));
+    for (int k = 0; k < net->num_nodes; ++k) {
+        if (net->nodes[k].type != BCNN_LAYER_YOLOV3) continue;
+        const bcnn_yolo_param *p = (const bcnn_yolo_param *)net->nodes[k].param;
+        BCNN_CHECK_AND_LOG(net->log_ctx, num_heads < BCNN_HIP_YOLO_MAX_HEADS && p->num <= BCNN_HIP_YOLO_MAX_ANCHORS,
+                           BCNN_INVALID_PARAMETER, "Batched detections: at most %d heads of %d anchors each\n",
+                           BCNN_HIP_YOLO_MAX_HEADS, BCNN_HIP_YOLO_MAX_ANCHORS);
+        bcnn_materialize_data(net, net->nodes[k].dst[0]);
+        const bcnn_tensor *dst = &net->tensors[net->nodes[k].dst[0]];
+        BCNN_CHECK_AND_LOG(net->log_ctx, dst->data_gpu && dst->n > 0 && (num_heads == 0 || dst->n == n),
+                           BCNN_INVALID_PARAMETER, "Batched detections: head %s has no device output\n", dst->name);
+        n = dst->n;
+        bcnn_hip_yolo_head *hd = &heads[num_heads++];
+        hd->out_d = dst->data_gpu;
+        hd->h = dst->h;
+        hd->w = dst->w;
+        hd->num = p->num;
+        hd->coords = p->coords;
+        hd->classes = p->classes;
+        for (int i = 0; i < p->num; ++i) {
+            hd->anchor_w[i] = p->biases[2 * p->mask[i]];
+            hd->anchor_h[i] = p->biases[2 * p->mask[i] + 1];
+        }
+        if (p->classes > max_classes) max_classes = p->classes;
+    }
+    if (num_heads == 0) return BCNN_INVALID_PARAMETER;
+    int *geom = (int *)malloc((size_t)n * 4 * sizeof(int));
+    if (!geom) return BCNN_FAILED_ALLOC;
+    for (int b = 0; b < n; ++b) { /* correct_region_boxes: the letter-boxed extent of image b */
+        const int w = widths[b], h = heights[b];
+        if (w <= 0 || h <= 0) {
+            free(geom);
+            return BCNN_INVALID_PARAMETER;
+        }
+        int new_w, new_h;
+        if (((float)netw / w) < ((float)neth / h)) {
+            new_w = netw;
+            new_h = (h * netw) / w;
+        } else {
+            new_h = neth;
+            new_w = (w * neth) / h;
+        }
+        geom[4 * b] = w;
+        geom[4 * b + 1] = h;
+        geom[4 * b + 2] = new_w;
+        geom[4 * b + 3] = new_h;
+    }
+    const int stride = BCNN_HIP_YOLO_RECORD_HEAD + max_classes;
+    const int nms_max = bcnn_hip_yolo_nms_capacity();
+    const int nms_eff = (nms_cap <= 0 || nms_cap > nms_max) ? nms_max : nms_cap;
+    int cap = record_cap > 0 ? record_cap
+                             : (hc->detect_capacity > DETECT_RECORD_CAPACITY ? hc->detect_capacity : DETECT_RECORD_CAPACITY);
+    int *result = NULL;
+    bcnn_status st = BCNN_SUCCESS;
+    int pass = 0, most = 0;
+    for (;;) { /* the counts are exact, so one grow is enough */
+        result = (int *)malloc(bcnn_hip_yolo_detect_result_words(n, cap, max_classes) * sizeof(int));
+        if (!result) {
+            st = BCNN_FAILED_ALLOC;
+            break;
+        }
+        ++pass;
+        if (bcnn_hip_yolo_detect_batch(heads, num_heads, n, geom, net->tensors[0].w, net->tensors[0].h, netw, neth, thresh,
+                                       relative, DETECT_NMS_THRESH, cap, nms_eff, result) != 0) {
+            st = BCNN_INVALID_PARAMETER;
+            break;
+        }
+        bcnn_hip_sync(); /* the one synchronisation of the call (two after a grow) */
+        most = 0;
+        for (int b = 0; b < n; ++b) most = result[b] > most ? result[b] : most;
+        if (most <= cap) break;
+        if (pass == 2) {
+            st = BCNN_INTERNAL_ERROR;
+            break;
+        }
+        free(result);
+        result = NULL;
+        cap = most + most / 4;
+    }
+    free(geom);
+    if (passes) *passes = pass;
+    if (st != BCNN_SUCCESS) {
+        free(result);
+        return st;
+    }
+    if (record_cap <= 0) hc->detect_capacity = most + most / 4; /* follows the latest batch: it shrinks again too */
+
+    const int *count = result, *order = result + n;
+    const float *records = (const float *)(result + n + (size_t)n * cap);
+    bcnn_output_detection **out = (bcnn_output_detection **)calloc((size_t)n, sizeof(*out));
+    if (!out) st = BCNN_FAILED_ALLOC;
+    for (int b = 0; st == BCNN_SUCCESS && b < n; ++b) {
+        const int cnt = count[b];
+        if (cnt <= 0) continue;
+        const float *rec = records + (size_t)b * cap * stride;
+        out[b] = (bcnn_output_detection *)calloc((size_t)cnt, sizeof(bcnn_output_detection));
+        det_key *keys = NULL;
+        if (cnt > nms_eff) { /* too many for the device NMS: the same order, then the host's greedy walk */
+            keys = (det_key *)malloc((size_t)cnt * sizeof(det_key));
+            for (int r = 0; keys && r < cnt; ++r) {
+                keys[r].objectness = rec[(size_t)r * stride + 4];
+                keys[r].index = r;
+            }
+            if (keys) qsort(keys, (size_t)cnt, sizeof(det_key), by_objectness_then_index);
+        }
+        if (!out[b] || (cnt > nms_eff && !keys)) {
+            st = BCNN_FAILED_ALLOC;
+            free(keys);
+            break;
+        }
+        for (int r = 0; r < cnt; ++r) {
+            const int slot = keys ? keys[r].index : (int)((unsigned)order[(size_t)b * cap + r] & 0x7fffffffu);
+            if (slot >= cnt || !detection_from_record(&out[b][r], rec + (size_t)slot * stride, heads, num_heads)) {
+                st = BCNN_INTERNAL_ERROR;
+                break;
+            }
+        }
+        if (keys && st == BCNN_SUCCESS) suppress_sorted(out[b], cnt, DETECT_NMS_THRESH);
+        free(keys);
+    }
+    if (st != BCNN_SUCCESS) {
+        for (int b = 0; out && b < n; ++b) bcnn_free_detections(out[b], out[b] ? count[b] : 0);
+    } else {
+        for (int b = 0; b < n; ++b) {
+            dets[b] = out[b];
+            num_dets[b] = count[b] > 0 ? count[b] : 0;
+        }
+    }
+    free(out);
+    free(result);
+    return st;
+}
+
+bcnn_status bcnn_yolo_get_detections_batch(bcnn_net *net, const int *widths, const int *heights, int netw, int neth,
+                                           float thresh, int relative, bcnn_output_detection **dets, int *num_dets) {
+    return bcnn_yolo_detections_batch_worker(net, widths, heights, netw, neth, thresh, relative, 0, 0, dets, num_dets,
+                                             NULL);
 }

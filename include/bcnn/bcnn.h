@@ -260,6 +260,26 @@ BCNN_API bcnn_status bcnn_get_lifted_struct_loss(bcnn_net *net, float *loss, int
 typedef enum { BCNN_PRECISION_FP32 = 0, BCNN_PRECISION_BF16 = 1 } bcnn_precision;
 BCNN_API bcnn_status bcnn_set_inference_precision(bcnn_net *net, bcnn_precision p);
 BCNN_API bcnn_precision bcnn_get_inference_precision(const bcnn_net *net);
+/* Detections of EVERY image of the batch from the latest forward, in one call. widths[b] / heights[b]: the original
+ * size of image b (what bcnn_yolo_get_detections takes as w, h). dets[b] receives a malloc'ed array of num_dets[b]
+ * boxes (NULL / 0 when image b has no candidate); per image, the result is what
+ * bcnn_yolo_get_detections(net, b, widths[b], heights[b], netw, neth, thresh, relative, &n) returns: num_dets[b]
+ * counts the boxes NMS suppressed too (objectness 0, prob zeroed), prob holds the classes of the head that produced the
+ * box, mask is a zeroed coords - 4 array when coords > 4, the NMS threshold is 0.45, and prob, mask and the array can
+ * each be released with free() (or all at once with bcnn_free_detections).
+ * The one allowed difference is the place of boxes with EQUAL objectness: the per-image call sorts with qsort, which
+ * leaves their order undefined; here boxes come by objectness, descending, and equal ones by candidate index,
+ * ascending -- heads in node order, then cell row * w + col, then anchor. A suppressed box keeps the place of its
+ * original objectness, as there.
+ * Threshold, box decode, compaction and NMS run in kernels queued on the net's stream. The call reads back one block
+ * (per-image counts, sort order and compact box records; its size follows the number of boxes kept, never the head
+ * tensors, which are not read back) and synchronises once; the block has room for 256 boxes per image, or for 1.25 x
+ * the most an image of the net's previous call had; a batch with more runs the kernels a second time with a larger block. Returns BCNN_INVALID_PARAMETER, writing nothing, when the net holds
+ * no YOLO node or a pointer argument is NULL. */
+BCNN_API bcnn_status bcnn_yolo_get_detections_batch(bcnn_net *net, const int *widths, const int *heights, int netw,
+                                                    int neth, float thresh, int relative,
+                                                    bcnn_output_detection **dets, int *num_dets);
+BCNN_API void bcnn_free_detections(bcnn_output_detection *dets, int num_dets); /* prob, mask and the array */
 /* Run ONE node's forward / backward worker on whatever its tensors currently hold (no executor bookkeeping:
  * no zero fill of the dst gradients, no dead-fill elision -- a sole-writer gradient is accumulated like in the
  * reference). Used by the teacher-forced parity walk, which feeds every node the REFERENCE's inputs. */

@@ -560,6 +560,51 @@ void bcnn_hip_upsample_backward(float *dx_d, const float *dy_d, int n, int c, in
 void bcnn_hip_yolo_activate(const float *x_d, float *y_d, int n, int num, int coords, int classes, int hw);
 
 /* ---------------------------------------------------------------------------------------------
+ * Detections of a whole batch on the device: threshold, box decode, ordered compaction and NMS of every YOLO head of
+ * a net (bcnn_yolo.c:99-145 get_yolo_box / correct_region_boxes, :470-639; bcnn_yolo_get_detections does the same on
+ * the host for one image per call after reading every head back). Two launches for the batch:
+ *   candidates : a lane per (image, head, cell, anchor). Reads the ACTIVATED objectness from the head's output tensor
+ *                (yolo_activate wrote it); where objectness > thresh it decodes the box with the host's expressions
+ *                (fp32, expf, the double sub-terms of correct_region_boxes), forms prob_j = objectness * p_j (0 when
+ *                <= thresh) and writes one record. The records of an image are compacted IN CANDIDATE ORDER -- heads
+ *                in table order, then cell row * w + col, then anchor -- by ballots and prefix sums, never through an
+ *                atomic counter, so the layout is the same from run to run. count[b] is always the true number of
+ *                candidates of image b; records past record_cap are dropped.
+ *   nms        : one workgroup per image with count <= min(record_cap, nms_cap). Sorts the records' (objectness
+ *                descending, record slot ascending) keys in LDS, then walks them in that order: a live box i clears
+ *                every later box j with box_iou(i, j) > nms_thresh (the host's expression). Writes order[b][r] = slot
+ *                of the r-th box (bit 31 set: cleared), and zeroes objectness and prob of the cleared records.
+ *                Images with more candidates are left to the caller (order[b] is not written).
+ * heads      : HOST table of num_heads <= BCNN_HIP_YOLO_MAX_HEADS entries; out_d is [n][num * (coords + classes + 1)]
+ *              [h * w], anchor_w / anchor_h the extents of the head's MASKED anchors (num <= BCNN_HIP_YOLO_MAX_ANCHORS).
+ * image_geom : HOST, n x 4 ints (w, h, new_w, new_h): the image's own size and its letter-boxed size inside netw x neth,
+ *              as correct_region_boxes computes it.
+ * in_w, in_h : extent of the net's input tensor (the divisor of the anchor extents).
+ * result_host: HOST buffer of bcnn_hip_yolo_detect_result_words(n, record_cap, max classes of the heads) 4-byte words:
+ *                int   count[n]
+ *                int   order[n][record_cap]
+ *                float record[n][record_cap][BCNN_HIP_YOLO_RECORD_HEAD + max classes]
+ *                      = x, y, w, h, objectness, candidate index (an int), prob[classes of its head], zero padding
+ *              filled by ONE device-to-host copy queued behind the two launches on the current stream; the caller
+ *              synchronises (bcnn_hip_sync) before reading it. The device side lives in the library's scratch table.
+ * nms_cap <= 0 or above bcnn_hip_yolo_nms_capacity() (what the LDS layout holds, a compile-time constant) means that
+ * capacity. Returns 0, or 1 when an argument is out of range (nothing is queued then).
+ * ------------------------------------------------------------------------------------------- */
+#define BCNN_HIP_YOLO_MAX_HEADS 8
+#define BCNN_HIP_YOLO_MAX_ANCHORS 16
+#define BCNN_HIP_YOLO_RECORD_HEAD 6
+typedef struct bcnn_hip_yolo_head {
+    const float *out_d;
+    int h, w, num, coords, classes;
+    float anchor_w[BCNN_HIP_YOLO_MAX_ANCHORS], anchor_h[BCNN_HIP_YOLO_MAX_ANCHORS];
+} bcnn_hip_yolo_head;
+int bcnn_hip_yolo_nms_capacity(void);
+size_t bcnn_hip_yolo_detect_result_words(int n, int record_cap, int max_classes);
+int bcnn_hip_yolo_detect_batch(const bcnn_hip_yolo_head *heads, int num_heads, int n, const int *image_geom, int in_w,
+                               int in_h, int netw, int neth, float thresh, int relative, float nms_thresh,
+                               int record_cap, int nms_cap, void *result_host);
+
+/* ---------------------------------------------------------------------------------------------
  * Transposed convolution (deconvolution), implicit GEMMs on fp32 MFMA with no col2im / im2col buffer.
  * Replaces bcnn_forward_deconv_layer_gpu / bcnn_backward_deconv_layer_gpu (bcnn_deconv_layer.c:249-320) with the
  * semantics of the CPU workers (:150-193, :195-246):

@@ -3,12 +3,18 @@
 the detector-graph kernels on large memory-bound cases: concat of two 64 x 128 x 104 x 104 sources and upsample
 64 x 128 x 52 x 52 -> 104 x 104, forward and backward. Device events on the library's stream, after warm-up.
     python tools/exp/yolo_tiny_time.py [--reps 20]
+--post: instead, the cost of getting a batch's boxes out after the N = 32 forward: 32 calls of bcnn_yolo_get_detections
+against one bcnn_yolo_get_detections_batch, wall clock around the calls (their synchronisation included), three
+alternating repeats; the raw record goes to --out (default profiles/detect_postprocess_n32.json).
+    python tools/exp/yolo_tiny_time.py --post [--candidates 300]
 Under rocprofv3:  rocprofv3 --kernel-trace --stats -d <dir> -- python tools/exp/yolo_tiny_time.py"""
 import argparse
 import json
 import os
 import sys
+import statistics
 import tempfile
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
@@ -85,11 +91,147 @@ def bandwidth(L, reps):
     return out
 
 
+class YoloHead(C.Structure):
+    """struct bcnn_hip_yolo_head (include/bcnn_hip.h)"""
+    _fields_ = [("out_d", C.c_void_p), ("h", C.c_int), ("w", C.c_int), ("num", C.c_int), ("coords", C.c_int),
+                ("classes", C.c_int), ("anchor_w", C.c_float * 16), ("anchor_h", C.c_float * 16)]
+
+
+def post(L, reps, tmp, n, want, out_path):
+    """after one forward of yolov3-tiny at N = n: (i) n calls of bcnn_yolo_get_detections, (ii) one
+    bcnn_yolo_get_detections_batch; `want` candidates per image on average set the threshold"""
+    cfg = os.path.join(tmp, "tiny%d.cfg" % n)
+    with open(cfg, "w") as fp:
+        fp.write(tiny_cfg(batch=n))
+    model = os.path.join(tmp, "tiny.weights")
+    if not os.path.exists(model):
+        write_tiny_weights(model)
+    net = capi.Net.load_net(cfg, model, capi.MODE_PREDICT)
+    net.compile()
+    net.data(0)[...] = np.random.RandomState(0).uniform(0, 1, net.shape(0)).astype(np.float32)
+    net.upload(0)
+    fwd_ms = timed(L, net.forward, reps)
+    net.forward()
+    net.sync()
+    _, _, neth, netw = net.shape(0)
+    # the heads: their activated objectness (read back once, outside every timed region) sets the threshold
+    heads, objectness, head_bytes = [], [], 0
+    for k in range(net.num_nodes):
+        y, src = net.node_dst(k), net.node_src(k, 0)
+        if y == src or net.shape(y)[1] != 255 or net.shape(src) != net.shape(y):
+            continue  # a head copies its 255-channel source (the convolution in front reads 512 / 256 channels)
+        net.download(y, with_grad=False)
+        nn, c, h, w = net.shape(y)
+        num = 3
+        per = c // num
+        objectness.append(net.data(y).reshape(nn, num, per, h * w)[:, :, 4].reshape(nn, -1).copy())
+        head_bytes += 4 * nn * c * h * w
+        heads.append((net.tensor(y).data_gpu, h, w, num, 4, per - 5))
+    assert len(heads) == 2, "yolov3-tiny has two heads"
+    obj = np.concatenate(objectness, 1)
+    thresh = float(np.sort(obj.reshape(-1))[::-1][min(obj.size - 1, want * n)])
+    counts = (obj > thresh).sum(1)
+    print("threshold %.6f: candidates per image %s" % (thresh, " ".join(str(int(v)) for v in counts)))
+    sizes = [(640 + 8 * (b % 5), 480 - 8 * (b % 3)) for b in range(n)]
+    ws, hs = (C.c_int * n)(*[s[0] for s in sizes]), (C.c_int * n)(*[s[1] for s in sizes])
+    NL = net.L
+
+    def per_image():
+        res = []
+        t0 = time.perf_counter()
+        for b in range(n):
+            cnt = C.c_int(0)
+            res.append((NL.bcnn_yolo_get_detections(net.net, b, sizes[b][0], sizes[b][1], netw, neth, thresh, 0,
+                                                    C.byref(cnt)), cnt))
+        dt = time.perf_counter() - t0
+        got = [c.value for _, c in res]
+        for d, c in res:
+            NL.bcnn_free_detections(d, c.value)
+        return dt * 1e3, got
+
+    def batch():
+        dets, cnts = (C.POINTER(capi.Detection) * n)(), (C.c_int * n)()
+        t0 = time.perf_counter()
+        st = NL.bcnn_yolo_get_detections_batch(net.net, ws, hs, netw, neth, thresh, 0, dets, cnts)
+        dt = time.perf_counter() - t0
+        assert st == 0, st
+        got = list(cnts)
+        for b in range(n):
+            NL.bcnn_free_detections(dets[b], cnts[b])
+        return dt * 1e3, got
+
+    for _ in range(3):  # warm-up (the batch call also settles its record capacity here)
+        per_image()
+        batch()
+    rec_i, rec_ii = [], []
+    for _ in range(3):
+        ms, got_i = per_image()
+        rec_i.append(ms)
+        ms, got_ii = batch()
+        rec_ii.append(ms)
+        assert got_i == got_ii == [int(v) for v in counts], (got_i, got_ii)
+    # device events around the C-ABI entry alone: the two kernels and the copy of the result block
+    anchors = [10, 14, 23, 27, 37, 58, 81, 82, 135, 169, 344, 319]
+    tab = (YoloHead * 2)()
+    for k, (ptr, h, w, num, coords, classes) in enumerate(heads):
+        mask = (3, 4, 5) if k == 0 else (0, 1, 2)
+        tab[k].out_d, tab[k].h, tab[k].w, tab[k].num, tab[k].coords, tab[k].classes = ptr, h, w, num, coords, classes
+        for a, m in enumerate(mask):
+            tab[k].anchor_w[a], tab[k].anchor_h[a] = anchors[2 * m], anchors[2 * m + 1]
+    # the record capacity the timed batch calls ran with (bcnn_layers_detect.c: 256, or 1.25 x the largest count of the
+    # net's previous call -- the warm-up calls, with these same counts)
+    cap = max(256, int(max(counts)) + int(max(counts)) // 4)
+    classes = heads[0][5]
+    words = L.bcnn_hip_yolo_detect_result_words(n, cap, classes)
+    result = (C.c_int * words)()
+    geom = (C.c_int * (4 * n))()
+    for b, (w, h) in enumerate(sizes):
+        new_w, new_h = (netw, (h * netw) // w) if netw / w < neth / h else ((w * neth) // h, neth)
+        geom[4 * b:4 * b + 4] = [w, h, new_w, new_h]
+    dev_ms = timed(L, lambda: L.bcnn_hip_yolo_detect_batch(tab, 2, n, geom, netw, neth, netw, neth, thresh, 0, 0.45, cap,
+                                                           0, result), reps)
+    assert list(result[:n]) == [int(v) for v in counts]
+    # what the copy of the result block alone costs: the same bytes, device to pageable host memory, synchronised
+    block = L.bcnn_hip_malloc_f32(words)
+    for _ in range(3):
+        L.bcnn_hip_memcpy_d2h(result, block, 4 * words)
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        L.bcnn_hip_memcpy_d2h(result, block, 4 * words)
+    copy_ms = (time.perf_counter() - t0) * 1e3 / reps
+    L.bcnn_hip_free(block)
+    net.close()
+    res = dict(device=torch.cuda.get_device_name(0), workload="yolov3-tiny 416x416 N=%d, random Darknet weights" % n,
+               threshold=thresh, candidates_per_image=[int(v) for v in counts], forward_ms=fwd_ms,
+               per_image_calls_ms=rec_i, batch_call_ms=rec_ii,
+               per_image_calls_median_ms=statistics.median(rec_i), batch_call_median_ms=statistics.median(rec_ii),
+               per_image_calls_spread_ms=max(rec_i) - min(rec_i), batch_call_spread_ms=max(rec_ii) - min(rec_ii),
+               kernels_and_copy_device_ms=dev_ms, result_copy_alone_wall_ms=copy_ms,
+               pcie_bytes_per_image_calls=n * head_bytes, pcie_bytes_batch_call=4 * (words + 4 * n),
+               record_capacity=cap)
+    print("forward %.3f ms | %d per-image calls: median %.3f ms (spread %.3f) | one batch call: median %.3f ms "
+          "(spread %.3f) | kernels + copy on the device %.3f ms | the copy alone %.3f ms wall" %
+          (fwd_ms, n, res["per_image_calls_median_ms"], res["per_image_calls_spread_ms"], res["batch_call_median_ms"],
+           res["batch_call_spread_ms"], dev_ms, copy_ms))
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fp:
+        json.dump(res, fp, indent=1)
+        fp.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--post", action="store_true", help="time the detection post-processing after the N = 32 forward")
+    ap.add_argument("--candidates", type=int, default=300, help="--post: candidates per image the threshold leaves")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "detect_postprocess_n32.json"))
     args = ap.parse_args()
     L = _lib.load()
+    if args.post:
+        with tempfile.TemporaryDirectory() as tmp:
+            post(L, args.reps, tmp, 32, args.candidates, args.out)
+        return
     res = {"device": torch.cuda.get_device_name(0)}
     with tempfile.TemporaryDirectory() as tmp:
         for n in (1, 32):
