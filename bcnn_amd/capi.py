@@ -19,6 +19,7 @@ PADDING_SAME, PADDING_VALID, PADDING_CAFFE = 0, 1, 2
 FILLER_FIXED, FILLER_XAVIER, FILLER_MSRA = 0, 1, 2
 LOSS_EUCLIDEAN, LOSS_LIFTED_STRUCT = 0, 1
 LOG_SILENT = 3
+IMAGE_FIT_STRETCH, IMAGE_FIT_LETTERBOX = 0, 1
 
 
 class Tensor(C.Structure):
@@ -121,6 +122,8 @@ def lib():
         "bcnn_yolo_get_detections_batch": (i, [vp, C.POINTER(i), C.POINTER(i), i, i, f, i,
                                                C.POINTER(C.POINTER(Detection)), C.POINTER(i)]),
         "bcnn_free_detections": (None, [C.POINTER(Detection), i]),
+        "bcnn_fill_tensor_with_images": (i, [vp, i, i, C.POINTER(vp), C.POINTER(i), C.POINTER(i), C.POINTER(i), i, i, f,
+                                             i, f, f, f]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -315,6 +318,34 @@ class Net:
 
     def download(self, idx, with_grad=True):
         assert self.L.bcnn_download_tensor(self.net, idx, 1 if with_grad else 0) == 0
+
+    def fill_images(self, images, fit=IMAGE_FIT_STRETCH, norm_coeff=1.0, swap_to_bgr=False, mean=(0.0, 0.0, 0.0),
+                    tensor=0):
+        """bcnn_fill_tensor_with_images: `images` is a list of H x W x C uint8 arrays (H x W for one channel), one per
+        batch entry from 0 on; each is resized (or letterboxed) to the tensor's extent and converted on the device.
+        Rows that are not contiguous go through `strides`; only an array whose pixels are not contiguous is copied.
+        Returns the bcnn_status (1 = BCNN_INVALID_PARAMETER: the tensor is untouched)."""
+        keep, ptrs, ws, hs, ss = [], [], [], [], []
+        c = None
+        for im in images:
+            a = np.asarray(im)
+            assert a.dtype == np.uint8 and a.ndim in (2, 3), "H x W x C uint8 arrays"
+            if a.ndim == 2:
+                a = a[:, :, None]
+            ch = a.shape[2]
+            if a.size and (a.strides[2] != 1 or a.strides[1] != ch or a.strides[0] < a.shape[1] * ch):
+                a = np.ascontiguousarray(a)
+            assert c is None or c == ch, "all images have the same number of channels"
+            c = ch
+            keep.append(a)
+            ptrs.append(a.ctypes.data if a.size else None)
+            hs.append(a.shape[0])
+            ws.append(a.shape[1])
+            ss.append(a.strides[0] if a.size else a.shape[1] * ch)
+        k = len(keep)
+        return self.L.bcnn_fill_tensor_with_images(self.net, tensor, k, (C.c_void_p * k)(*ptrs), (C.c_int * k)(*ws),
+                                                   (C.c_int * k)(*hs), (C.c_int * k)(*ss), c if c is not None else 0,
+                                                   fit, norm_coeff, 1 if swap_to_bgr else 0, mean[0], mean[1], mean[2])
 
     def forward(self):
         self.L.bcnn_forward(self.net)

@@ -59,6 +59,7 @@ enum ScratchSlot {
     SCRATCH_W43FF_U,       // current stream: packed U of the first-form F(4x4,3x3) (experiment build, wino43_first_form_exp.h)
     SCRATCH_W43FF_TAIL,    // current stream: piece outputs of its K-split tail (experiment build)
     SCRATCH_DETECT,        // current stream: image sizes, counts, sort order and box records of the batched YOLO decode (detect.hip)
+    SCRATCH_IMAGES,        // current stream: descriptors, tap tables and uint8 pixels of the batched input fill (image_fill.hip)
     SCRATCH_SLOTS
 };
 // A block of at least `floats` floats for `slot` on the calling thread's device; valid until that slot's next call.

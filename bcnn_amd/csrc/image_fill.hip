@@ -1,0 +1,241 @@
+// image_fill.hip -- the input tensor of a batch from raw uint8 images, on the device: bilinear resize (bip_resize_bilinear's
+// fixed-point rule), optional letterbox onto a grey canvas, uint8 -> float conversion with mean / scale / channel swap
+// (bcnn_convert_img_to_float), NCHW planes. One host-to-device copy of one staging block and one kernel launch per call.
+// The result is bit-identical to the host composition of those two functions: the sampling rule and the blend are the
+// host's own (../host/bip_resize_tap.h; the taps are tabulated on the host, the kernel only looks them up), the conversion
+// is one fp32 subtract and one fp32 multiply, uncontracted (-ffp-contract=off).
+#include "common.h"
+
+#include <cstdint>
+#include <cstring>
+
+#include "../host/bip_resize_tap.h"
+
+namespace bcnn_hip {
+namespace {
+
+// Per-image record at the head of the staging block. Offsets count from the block's first byte.
+struct ImageDesc {
+    uint32_t data_off;           // packed pixels: h rows of w * c bytes (the caller's row padding is dropped)
+    uint32_t tapx_off, tapy_off; // int2 (index, frac) per column of the resized image / per row
+    int w, h;                    // source extent
+    int new_w, new_h;            // extent of the resized image inside the W x H plane
+    int x_off, y_off;            // where it is pasted; everything outside is the canvas value 128
+};
+
+constexpr int kFillBlock = 256;
+constexpr int kRun = 8;          // destination pixels of one row per lane
+constexpr int kCanvas = 128;     // the letterbox canvas byte (yolo_example.cc:40-75)
+
+struct FillParams {
+    float mean[4];               // per OUTPUT channel: the mean of the source channel it reads
+    float norm;
+    int swap;                    // read channel 2 - k (c == 3 only)
+    int H, W;                    // destination plane
+    int runs_per_row, blocks_per_image;
+};
+
+// Stores a full run v[0 .. kRun) to d: HEAD scalar stores up to the first 16-byte boundary, 16-byte stores, scalar tail.
+// HEAD is a template argument so that every index into v is a compile-time constant (v stays in registers).
+template <int HEAD>
+__device__ __forceinline__ void store_full_run(float* __restrict__ d, const float (&v)[kRun]) {
+    static_assert(kRun == 8, "one 16-byte store after a head, two without");
+#pragma unroll
+    for (int j = 0; j < HEAD; ++j) d[j] = v[j];
+    *reinterpret_cast<float4*>(d + HEAD) = make_float4(v[HEAD], v[HEAD + 1], v[HEAD + 2], v[HEAD + 3]);
+    if (HEAD == 0) {
+        *reinterpret_cast<float4*>(d + 4) = make_float4(v[4], v[5], v[6], v[7]);
+    } else {
+#pragma unroll
+        for (int j = HEAD + 4; j < kRun; ++j) d[j] = v[j];
+    }
+}
+// Stores v[0 .. len) to d; a run cut short by the end of its row (len < kRun) goes out in scalar stores.
+__device__ __forceinline__ void store_run(float* __restrict__ d, const float (&v)[kRun], int len) {
+    if (len == kRun) {
+        switch ((4 - (int)((reinterpret_cast<uintptr_t>(d) >> 2) & 3)) & 3) {  // floats up to the 16-byte boundary
+            case 0: store_full_run<0>(d, v); break;
+            case 1: store_full_run<1>(d, v); break;
+            case 2: store_full_run<2>(d, v); break;
+            default: store_full_run<3>(d, v); break;
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < kRun - 1; ++j)
+            if (j < len) d[j] = v[j];
+    }
+}
+
+// A lane owns kRun consecutive destination pixels of one row of one image and writes them into all C planes.
+template <int C>
+__global__ __launch_bounds__(kFillBlock) void fill_images_kernel(const uint8_t* __restrict__ stage, float* __restrict__ dst,
+                                                                 FillParams p) {
+    const int b = blockIdx.x / p.blocks_per_image;
+    const int run = (blockIdx.x - b * p.blocks_per_image) * kFillBlock + threadIdx.x;
+    const int y = run / p.runs_per_row;
+    if (y >= p.H) return;
+    const int x0 = (run - y * p.runs_per_row) * kRun;
+    const int len = min(kRun, p.W - x0);
+    const ImageDesc d = reinterpret_cast<const ImageDesc*>(stage)[b];
+    const int2* __restrict__ tapx = reinterpret_cast<const int2*>(stage + d.tapx_off);
+    const int2* __restrict__ tapy = reinterpret_cast<const int2*>(stage + d.tapy_off);
+    const int row_bytes = d.w * C;
+    const int xstep = d.w > 1 ? C : 0, ystep = d.h > 1 ? row_bytes : 0;
+
+    float fill[C];
+#pragma unroll
+    for (int k = 0; k < C; ++k) fill[k] = ((float)kCanvas - p.mean[k]) * p.norm;
+    float v[C][kRun];
+    const int ty = y - d.y_off;
+    const bool row_inside = ty >= 0 && ty < d.new_h;
+    int2 ty_tap = make_int2(0, 0);
+    if (row_inside) ty_tap = tapy[ty];
+    const uint8_t* __restrict__ r0 = stage + d.data_off + (size_t)ty_tap.x * row_bytes;
+    const uint8_t* __restrict__ r1 = r0 + ystep;
+#pragma unroll
+    for (int j = 0; j < kRun; ++j) {
+        const int tx = x0 + j - d.x_off;
+        if (row_inside && j < len && tx >= 0 && tx < d.new_w) {
+            const int2 t = tapx[tx];
+#pragma unroll
+            for (int k = 0; k < C; ++k) {
+                const int o = t.x * C + ((C == 3 && p.swap) ? 2 - k : k);
+                const uint8_t s = bip_resize_blend(r0[o], r0[o + xstep], r1[o], r1[o + xstep], t.y, ty_tap.y);
+                v[k][j] = ((float)s - p.mean[k]) * p.norm;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < C; ++k) v[k][j] = fill[k];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < C; ++k)
+        store_run(dst + (((size_t)b * C + k) * p.H + y) * p.W + x0, v[k], len);
+}
+
+// Pinned host side of the staging block: grow-only, one per host thread and device. `copied` is recorded behind the
+// latest copy out of it; the next call waits for it before it overwrites (or frees) the block.
+struct HostStage { uint8_t* p = nullptr; size_t cap = 0; hipEvent_t copied = nullptr; bool in_flight = false; };
+thread_local HostStage g_stage[kMaxDevices];
+
+uint8_t* host_stage(size_t bytes) {
+    HostStage& s = g_stage[current_device()];
+    if (s.in_flight) {
+        HIP_CHECK(hipEventSynchronize(s.copied));
+        s.in_flight = false;
+    }
+    if (!s.copied) HIP_CHECK(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
+    if (s.p == nullptr || s.cap < bytes) {
+        if (s.p) HIP_CHECK(hipHostFree(s.p));
+        s.cap = bytes + bytes / 4;
+        HIP_CHECK(hipHostMalloc((void**)&s.p, s.cap, hipHostMallocDefault));
+    }
+    return s.p;
+}
+
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// Extent of image iw x ih inside the W x H plane: the plane itself (stretch), or the largest extent of the image's aspect
+// ratio that fits, by the reference example's integer rule (yolo_example.cc:40-75). False when an extent comes out 0.
+bool fitted_extent(int fit, int W, int H, int iw, int ih, int* new_w, int* new_h) {
+    *new_w = W;
+    *new_h = H;
+    if (fit == BCNN_HIP_IMAGE_FIT_LETTERBOX) {
+        if ((float)W / iw < (float)H / ih) {
+            *new_h = (int)(((long long)ih * W) / iw);
+        } else {
+            *new_w = (int)(((long long)iw * H) / ih);
+        }
+    }
+    return *new_w >= 1 && *new_h >= 1 && *new_w <= W && *new_h <= H;
+}
+
+}  // namespace
+}  // namespace bcnn_hip
+
+using namespace bcnn_hip;
+
+extern "C" {
+
+int bcnn_hip_fill_images(float* dst_d, int n, int c, int h, int w, int num_images, const uint8_t* const* images,
+                         const int* widths, const int* heights, const int* strides, int fit, float norm_coeff,
+                         int swap_to_bgr, float mean_r, float mean_g, float mean_b) {
+    if (!dst_d || !images || !widths || !heights || n < 1 || h < 1 || w < 1 || c < 1 || c > 4 || num_images < 1 ||
+        num_images > n || (fit != BCNN_HIP_IMAGE_FIT_STRETCH && fit != BCNN_HIP_IMAGE_FIT_LETTERBOX))
+        return 1;
+    // ---- every refusal comes before anything is staged or queued
+    size_t pixels = 0;
+    for (int b = 0; b < num_images; ++b) {
+        if (!images[b] || widths[b] < 1 || heights[b] < 1) return 1;
+        const long long row = (long long)widths[b] * c;
+        if (row > 0x7fffffff || (strides && strides[b] < row)) return 1;
+        int new_w, new_h;
+        if (!fitted_extent(fit, w, h, widths[b], heights[b], &new_w, &new_h)) return 1;
+        pixels += align_up((size_t)row * heights[b], 16);
+        if (pixels > (size_t)0x7fffffff) return 1;
+    }
+    // the staging block: [descriptors][tap tables, room for W + H taps per image][pixels]; its offsets are 32-bit
+    const size_t desc_bytes = align_up((size_t)num_images * sizeof(ImageDesc), 16);
+    const size_t taps = (size_t)num_images * ((size_t)w + h) * sizeof(int2);
+    const size_t total = desc_bytes + taps + pixels;
+    FillParams p;
+    p.runs_per_row = ceil_div(w, kRun);
+    p.blocks_per_image = ceil_div((long long)p.runs_per_row * h, kFillBlock);
+    const long long blocks = (long long)p.blocks_per_image * num_images;
+    if (total > (size_t)0x7fffffff || blocks > 0x7fffffff) return 1;
+
+    uint8_t* stage = host_stage(total);
+    ImageDesc* desc = reinterpret_cast<ImageDesc*>(stage);
+    size_t tap_at = desc_bytes, pix_at = desc_bytes + taps;
+    for (int b = 0; b < num_images; ++b) {
+        const int iw = widths[b], ih = heights[b];
+        ImageDesc& d = desc[b];
+        d.w = iw;
+        d.h = ih;
+        fitted_extent(fit, w, h, iw, ih, &d.new_w, &d.new_h);
+        d.x_off = (w - d.new_w) / 2;
+        d.y_off = (h - d.new_h) / 2;
+        d.tapx_off = (uint32_t)tap_at;
+        int2* tx = reinterpret_cast<int2*>(stage + tap_at);
+        const float xs = bip_resize_scale((size_t)iw, (size_t)d.new_w), ys = bip_resize_scale((size_t)ih, (size_t)d.new_h);
+        for (int x = 0; x < d.new_w; ++x) bip_resize_tap((size_t)x, xs, (size_t)iw, &tx[x].x, &tx[x].y);
+        tap_at += (size_t)d.new_w * sizeof(int2);
+        d.tapy_off = (uint32_t)tap_at;
+        int2* ty = reinterpret_cast<int2*>(stage + tap_at);
+        for (int y = 0; y < d.new_h; ++y) bip_resize_tap((size_t)y, ys, (size_t)ih, &ty[y].x, &ty[y].y);
+        tap_at += (size_t)d.new_h * sizeof(int2);
+        d.data_off = (uint32_t)pix_at;
+        const size_t row = (size_t)iw * c, stride = strides ? (size_t)strides[b] : row;
+        if (stride == row) {
+            memcpy(stage + pix_at, images[b], row * ih);
+        } else {
+            for (int y = 0; y < ih; ++y) memcpy(stage + pix_at + y * row, images[b] + y * stride, row);
+        }
+        pix_at += align_up(row * ih, 16);
+    }
+    // ---- one copy, one launch
+    uint8_t* stage_d = reinterpret_cast<uint8_t*>(scratch(SCRATCH_IMAGES, (total + 3) / 4));
+    hipStream_t st = current_stream();
+    HIP_CHECK(hipMemcpyAsync(stage_d, stage, total, hipMemcpyHostToDevice, st));
+    HostStage& hs = g_stage[current_device()];
+    HIP_CHECK(hipEventRecord(hs.copied, st));
+    hs.in_flight = true;
+
+    const float m[3] = {mean_r, mean_g, mean_b};
+    p.swap = (swap_to_bgr && c == 3) ? 1 : 0;
+    for (int k = 0; k < 4; ++k) p.mean[k] = (c == 3 && k < 3) ? m[p.swap ? 2 - k : k] : m[0];
+    p.norm = norm_coeff;
+    p.H = h;
+    p.W = w;
+    const dim3 grid((unsigned)blocks);
+    switch (c) {
+        case 1: fill_images_kernel<1><<<grid, kFillBlock, 0, st>>>(stage_d, dst_d, p); break;
+        case 2: fill_images_kernel<2><<<grid, kFillBlock, 0, st>>>(stage_d, dst_d, p); break;
+        case 3: fill_images_kernel<3><<<grid, kFillBlock, 0, st>>>(stage_d, dst_d, p); break;
+        default: fill_images_kernel<4><<<grid, kFillBlock, 0, st>>>(stage_d, dst_d, p); break;
+    }
+    KERNEL_CHECK();
+    return 0;
+}
+
+}  // extern "C"

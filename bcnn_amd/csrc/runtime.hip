@@ -37,6 +37,7 @@ static constexpr ScratchPolicy kScratchPolicy[] = {  // in ScratchSlot order
     /* W43FF_U       */ {1u << 20, 1, 1},
     /* W43FF_TAIL    */ {0, 1, 1},
     /* DETECT        */ {1u << 16, 1, 1},  // the caller's record capacity already carries the headroom
+    /* IMAGES        */ {1u << 18, 5, 4},  // 1 MiB to start with; frame sizes vary from batch to batch
 };
 static_assert(sizeof(kScratchPolicy) / sizeof(kScratchPolicy[0]) == SCRATCH_SLOTS, "one policy row per ScratchSlot");
 struct ScratchBlock { float* p = nullptr; size_t cap = 0; };

@@ -924,6 +924,45 @@ bcnn_status bcnn_upload_tensor(bcnn_net *net, int index, int with_grad) {
     return BCNN_SUCCESS;
 }
 
+/* Batch entries 0 .. num_images - 1 of a tensor from raw uint8 images, resized, letterboxed and converted on the device
+ * (bcnn_hip_fill_images: one staging copy and one kernel for the batch). The tensor's host data is not written. */
+bcnn_status bcnn_fill_tensor_with_images(bcnn_net *net, int tensor_index, int num_images, const uint8_t *const *images,
+                                         const int *widths, const int *heights, const int *strides, int c,
+                                         bcnn_image_fit fit, float norm_coeff, int swap_to_bgr, float mean_r,
+                                         float mean_g, float mean_b) {
+    BCNN_CHECK_AND_LOG(net->log_ctx, tensor_index >= 0 && tensor_index < net->num_tensors, BCNN_INVALID_PARAMETER,
+                       "Fill with images: invalid tensor index %d\n", tensor_index);
+    bcnn_tensor *t = &net->tensors[tensor_index];
+    BCNN_CHECK_AND_LOG(net->log_ctx, t->data_gpu != NULL, BCNN_INVALID_PARAMETER,
+                       "Fill with images: tensor %d has no device buffer\n", tensor_index);
+    BCNN_CHECK_AND_LOG(net->log_ctx, num_images >= 1 && num_images <= t->n, BCNN_INVALID_PARAMETER,
+                       "Fill with images: %d images for a batch of %d\n", num_images, t->n);
+    BCNN_CHECK_AND_LOG(net->log_ctx, c == t->c && c >= 1 && c <= 4, BCNN_INVALID_PARAMETER,
+                       "Fill with images: %d channels (tensor: %d; supported: 1 to 4)\n", c, t->c);
+    BCNN_CHECK_AND_LOG(net->log_ctx, images && widths && heights, BCNN_INVALID_PARAMETER,
+                       "Fill with images: NULL images, widths or heights\n");
+    BCNN_CHECK_AND_LOG(net->log_ctx, fit == BCNN_IMAGE_FIT_STRETCH || fit == BCNN_IMAGE_FIT_LETTERBOX,
+                       BCNN_INVALID_PARAMETER, "Fill with images: unknown fit %d\n", (int)fit);
+    for (int b = 0; b < num_images; ++b) {
+        BCNN_CHECK_AND_LOG(net->log_ctx, images[b] && widths[b] >= 1 && heights[b] >= 1, BCNN_INVALID_PARAMETER,
+                           "Fill with images: image %d is NULL or has an extent below 1\n", b);
+        BCNN_CHECK_AND_LOG(net->log_ctx, !strides || (long long)strides[b] >= (long long)widths[b] * c,
+                           BCNN_INVALID_PARAMETER, "Fill with images: image %d: stride %d below width * channels\n", b,
+                           strides[b]);
+    }
+    /* Values a fused forward left pending for this tensor go in first, as in bcnn_upload_tensor: produced later they would
+     * land on top of the images. That writes what the tensor already stands for, so a refusal below still leaves it as
+     * it was. The back-end repeats the checks above and adds its own (a letterbox extent of 0, the size of the staging
+     * block) before it queues anything. */
+    bcnn_materialize_data(net, tensor_index);
+    if (bcnn_hip_fill_images(t->data_gpu, t->n, t->c, t->h, t->w, num_images, images, widths, heights, strides, (int)fit,
+                             norm_coeff, swap_to_bgr, mean_r, mean_g, mean_b) != 0)
+        BCNN_ERROR(net->log_ctx, BCNN_INVALID_PARAMETER,
+                   "Fill with images: an image does not fit the %d x %d input (letterbox extent of 0, or more than 2 GiB "
+                   "to stage)\n", t->w, t->h);
+    return BCNN_SUCCESS;
+}
+
 bcnn_status bcnn_download_tensor(bcnn_net *net, int index, int with_grad) {
     if (index < 0 || index >= net->num_tensors) return BCNN_INVALID_PARAMETER;
     bcnn_tensor *t = &net->tensors[index];

@@ -138,6 +138,31 @@ BCNN_API void bcnn_augment_data_with_distortion(bcnn_net *net, float distortion)
 BCNN_API bcnn_status bcnn_fill_tensor_with_image(bcnn_net *net, const uint8_t *src, int w, int h, int c,
                                                  float norm_coeff, int swap_to_bgr, float mean_r, float mean_g,
                                                  float mean_b, int tensor_index, int batch_index);
+/* New, without a reference counterpart: batch entries 0 .. num_images - 1 of tensor `tensor_index` from raw images, in
+ * one call, prepared ON THE DEVICE (one host-to-device copy of the uint8 pixels and one kernel for the whole batch;
+ * bcnn_fill_tensor_with_image uploads the whole float tensor once per image). Entries num_images .. n - 1 keep their
+ * device content. images[b]: interleaved HWC uint8, widths[b] x heights[b] x c, rows strides[b] bytes apart (strides
+ * NULL: widths[b] * c). With W x H the tensor's extent, image b becomes, bit for bit,
+ *   STRETCH   : bip_resize_bilinear(images[b], widths[b], heights[b], strides[b], tmp, W, H, W * c, c), then
+ *               bcnn_convert_img_to_float(tmp, W, H, c, norm_coeff, swap_to_bgr, mean_r, mean_g, mean_b, entry b);
+ *               an image already W x H goes through the same arithmetic (the identity there);
+ *   LETTERBOX : the rule of the reference's examples/yolo: if (float)W / w < (float)H / h then new_w = W,
+ *               new_h = (h * W) / w, else new_h = H, new_w = (w * H) / h (integer divisions); resized to new_w x new_h,
+ *               pasted at ((W - new_w) / 2, (H - new_h) / 2) onto a canvas whose every byte is 128, and the canvas
+ *               converted. This is the geometry bcnn_yolo_get_detections[_batch] with netw = W, neth = H undoes.
+ * As in bcnn_convert_img_to_float, the channel swap applies only when c == 3 and mean_r serves every channel when c != 3.
+ * Returns BCNN_INVALID_PARAMETER with a log line, leaving the tensor as it was and queuing nothing, when tensor_index
+ * is out of range or the tensor has no device buffer; num_images < 1 or above the batch size; c differs from the
+ * tensor's or is outside 1..4; images, widths, heights or an images[b] is NULL; a width or height is below 1; a stride
+ * is below widths[b] * c; fit is unknown; a letterbox extent comes out 0; or the pixels of the batch exceed 2 GiB.
+ * The tensor's HOST data is not written: bcnn_download_tensor refreshes it, as for every tensor a kernel wrote. The work
+ * is queued on the calling thread's stream; the images are copied to a staging buffer before the call returns, so the
+ * caller may free or overwrite them at once. */
+typedef enum { BCNN_IMAGE_FIT_STRETCH = 0, BCNN_IMAGE_FIT_LETTERBOX = 1 } bcnn_image_fit;
+BCNN_API bcnn_status bcnn_fill_tensor_with_images(bcnn_net *net, int tensor_index, int num_images,
+                                                  const uint8_t *const *images, const int *widths, const int *heights,
+                                                  const int *strides, int c, bcnn_image_fit fit, float norm_coeff,
+                                                  int swap_to_bgr, float mean_r, float mean_g, float mean_b);
 
 /* ---- training set-up ---- */
 BCNN_API bcnn_status bcnn_set_mode(bcnn_net *net, bcnn_mode mode);

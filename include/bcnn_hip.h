@@ -605,6 +605,34 @@ int bcnn_hip_yolo_detect_batch(const bcnn_hip_yolo_head *heads, int num_heads, i
                                int record_cap, int nms_cap, void *result_host);
 
 /* ---------------------------------------------------------------------------------------------
+ * The input tensor of a batch from raw uint8 images (image_fill.hip): entries 0 .. num_images - 1 of the NCHW float
+ * tensor dst_d [n][c][h][w]; entries num_images .. n - 1 are not written. images / widths / heights / strides are HOST
+ * arrays of num_images entries: interleaved HWC uint8 pixels, extent in pixels, row pitch in bytes (strides NULL:
+ * widths[b] * c). Image b is resized with bip_resize_bilinear's fixed-point rule (half-pixel centres, fractions in 1/16,
+ * rounding + 128 >> 8; the taps come from the host's own function, bcnn_amd/host/bip_resize_tap.h) to
+ *   BCNN_HIP_IMAGE_FIT_STRETCH   : w x h;
+ *   BCNN_HIP_IMAGE_FIT_LETTERBOX : new_w x new_h with (float)w / iw < (float)h / ih ? (w, (ih * w) / iw)
+ *                                  : ((iw * h) / ih, h), pasted at ((w - new_w) / 2, (h - new_h) / 2) onto a canvas of
+ *                                  bytes 128,
+ * and converted like bcnn_convert_img_to_float (bcnn_data.c:70-100): plane k = ((float)byte[ks] - mean[ks]) * norm_coeff
+ * with ks = 2 - k when swap_to_bgr and c == 3, else k; mean = (mean_r, mean_g, mean_b) when c == 3, else mean_r. The
+ * result equals the host composition of the two functions bit for bit.
+ * The call packs per-image descriptors, tap tables and the pixels (row padding dropped) into one pinned host block,
+ * sends it with ONE copy on the current stream into the library's scratch table and queues ONE kernel for the batch:
+ * a lane computes 8 consecutive pixels of a row for all c planes (canvas pixels included, there is no fill pass) and
+ * stores them 16 bytes wide between a scalar head and tail. The images have been copied when the call returns. A later
+ * call waits for the earlier call's copy (not its kernel) before it reuses the pinned block.
+ * Returns 0, or 1 with nothing staged or queued: NULL dst_d / images / widths / heights / images[b]; n, h or w < 1;
+ * c outside 1..4; num_images outside 1..n; an extent < 1; a stride < widths[b] * c; unknown fit; a letterbox extent of
+ * 0; more than 2 GiB to stage.
+ * ------------------------------------------------------------------------------------------- */
+#define BCNN_HIP_IMAGE_FIT_STRETCH 0
+#define BCNN_HIP_IMAGE_FIT_LETTERBOX 1
+int bcnn_hip_fill_images(float *dst_d, int n, int c, int h, int w, int num_images, const uint8_t *const *images,
+                         const int *widths, const int *heights, const int *strides, int fit, float norm_coeff,
+                         int swap_to_bgr, float mean_r, float mean_g, float mean_b);
+
+/* ---------------------------------------------------------------------------------------------
  * Transposed convolution (deconvolution), implicit GEMMs on fp32 MFMA with no col2im / im2col buffer.
  * Replaces bcnn_forward_deconv_layer_gpu / bcnn_backward_deconv_layer_gpu (bcnn_deconv_layer.c:249-320) with the
  * semantics of the CPU workers (:150-193, :195-246):

@@ -7,6 +7,11 @@ the detector-graph kernels on large memory-bound cases: concat of two 64 x 128 x
 against one bcnn_yolo_get_detections_batch, wall clock around the calls (their synchronisation included), three
 alternating repeats; the raw record goes to --out (default profiles/detect_postprocess_n32.json).
     python tools/exp/yolo_tiny_time.py --post [--candidates 300]
+--pre: instead, the cost of getting a batch's frames in before the N = 32 forward: per image a host resize, a canvas paste
+and bcnn_fill_tensor_with_image (which uploads the whole tensor each time) against one bcnn_fill_tensor_with_images, both
+ended by bcnn_synchronize, wall clock, three alternating repeats; the raw record goes to --out (default
+profiles/input_fill_n32.json).
+    python tools/exp/yolo_tiny_time.py --pre
 Under rocprofv3:  rocprofv3 --kernel-trace --stats -d <dir> -- python tools/exp/yolo_tiny_time.py"""
 import argparse
 import json
@@ -220,14 +225,111 @@ def post(L, reps, tmp, n, want, out_path):
     print(json.dumps(res))
 
 
+def pre(L, reps, tmp, n, out_path, fw=640, fh=480):
+    """n random fw x fh x 3 frames into the input of yolov3-tiny at N = n, letterbox fit: (A) the host path, per image
+    bip_resize_bilinear, paste onto a canvas of 128, bcnn_fill_tensor_with_image; (B) one bcnn_fill_tensor_with_images"""
+    cfg = os.path.join(tmp, "tiny%d.cfg" % n)
+    with open(cfg, "w") as fp:
+        fp.write(tiny_cfg(batch=n))
+    model = os.path.join(tmp, "tiny.weights")
+    if not os.path.exists(model):
+        write_tiny_weights(model)
+    net = capi.Net.load_net(cfg, model, capi.MODE_PREDICT)
+    net.compile()
+    NL = net.L
+    _, c, H, W = net.shape(0)
+    u8p = C.POINTER(C.c_uint8)
+    bip = C.CDLL(os.path.join(os.path.dirname(capi.LIB_PATH), "libbip.so"))
+    bip.bip_resize_bilinear.argtypes = [u8p] + [C.c_size_t] * 3 + [u8p] + [C.c_size_t] * 4
+    NL.bcnn_fill_tensor_with_image.argtypes = [C.c_void_p, u8p] + [C.c_int] * 3 + [C.c_float, C.c_int] + [C.c_float] * 3 + \
+        [C.c_int] * 2
+    NL.bcnn_fill_tensor_with_image.restype = C.c_int
+    rs = np.random.RandomState(0)
+    frames = [rs.randint(0, 256, (fh, fw, c)).astype(np.uint8) for _ in range(n)]
+    new_w, new_h = (W, (fh * W) // fw) if np.float32(W) / np.float32(fw) < np.float32(H) / np.float32(fh) else \
+        ((fw * H) // fh, H)
+    xo, yo = (W - new_w) // 2, (H - new_h) // 2
+    norm = 1.0 / 255.0
+    ptrs = (C.c_void_p * n)(*[f.ctypes.data for f in frames])
+    ws, hs = (C.c_int * n)(*[fw] * n), (C.c_int * n)(*[fh] * n)
+
+    def host_path():
+        t0 = time.perf_counter()
+        for b in range(n):
+            small = np.empty((new_h, new_w, c), np.uint8)
+            bip.bip_resize_bilinear(frames[b].ctypes.data_as(u8p), fw, fh, fw * c, small.ctypes.data_as(u8p), new_w, new_h,
+                                    new_w * c, c)
+            canvas = np.full((H, W, c), 128, np.uint8)
+            canvas[yo:yo + new_h, xo:xo + new_w] = small
+            st = NL.bcnn_fill_tensor_with_image(net.net, canvas.ctypes.data_as(u8p), W, H, c, norm, 1, 0.0, 0.0, 0.0, 0, b)
+            assert st == 0, st
+        net.sync()
+        return (time.perf_counter() - t0) * 1e3
+
+    def device_path():
+        t0 = time.perf_counter()
+        st = NL.bcnn_fill_tensor_with_images(net.net, 0, n, ptrs, ws, hs, None, c, capi.IMAGE_FIT_LETTERBOX, norm, 1,
+                                             0.0, 0.0, 0.0)
+        net.sync()
+        dt = (time.perf_counter() - t0) * 1e3
+        assert st == 0, st
+        return dt
+
+    def device_tensor():
+        net.download(0, with_grad=False)
+        return net.data(0).copy()
+
+    for _ in range(3):  # warm-up: code objects, the pinned and the device staging blocks at their final size
+        host_path()
+        device_path()
+    rec_a, rec_b = [], []
+    for _ in range(3):
+        rec_a.append(host_path())
+        x_a = device_tensor()
+        rec_b.append(device_path())
+        x_b = device_tensor()
+        assert np.array_equal(x_a.view(np.uint32), x_b.view(np.uint32)), "the two legs fill the tensor differently"
+    # device events around the C-ABI entry alone: the staging copy and the kernel (the host packing overlaps neither)
+    x_d = net.tensor(0).data_gpu
+    dev_ms = timed(L, lambda: L.bcnn_hip_fill_images(x_d, n, c, H, W, n, ptrs, ws, hs, None, capi.IMAGE_FIT_LETTERBOX,
+                                                     norm, 1, 0.0, 0.0, 0.0), reps)
+    fwd_ms = timed(L, net.forward, reps)
+    net.close()
+    align = lambda v: (v + 15) // 16 * 16  # noqa: E731
+    staged = align(n * 36) + n * (W + H) * 8 + n * align(fw * fh * c)   # descriptors, tap tables, pixels (image_fill.hip)
+    res = dict(device=torch.cuda.get_device_name(0),
+               workload="yolov3-tiny %dx%d N=%d, random %dx%dx%d frames, letterbox" % (W, H, n, fw, fh, c),
+               forward_ms=fwd_ms, host_path_ms=rec_a, device_path_ms=rec_b,
+               host_path_median_ms=statistics.median(rec_a), device_path_median_ms=statistics.median(rec_b),
+               host_path_spread_ms=max(rec_a) - min(rec_a), device_path_spread_ms=max(rec_b) - min(rec_b),
+               copy_and_kernel_device_ms=dev_ms, pcie_bytes_host_path=n * n * c * H * W * 4, pcie_bytes_device_path=staged,
+               results_bit_identical=True)
+    print("forward %.3f ms | host path (%d fills): median %.3f ms (spread %.3f) | one device fill: median %.3f ms "
+          "(spread %.3f) | its copy + kernel on the device %.3f ms" %
+          (fwd_ms, n, res["host_path_median_ms"], res["host_path_spread_ms"], res["device_path_median_ms"],
+           res["device_path_spread_ms"], dev_ms))
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fp:
+        json.dump(res, fp, indent=1)
+        fp.write("\n")
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--post", action="store_true", help="time the detection post-processing after the N = 32 forward")
     ap.add_argument("--candidates", type=int, default=300, help="--post: candidates per image the threshold leaves")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "detect_postprocess_n32.json"))
+    ap.add_argument("--pre", action="store_true", help="time the input fill before the N = 32 forward")
+    ap.add_argument("--out", default=None, help="--post / --pre: where the raw record goes")
     args = ap.parse_args()
     L = _lib.load()
+    if args.pre:
+        with tempfile.TemporaryDirectory() as tmp:
+            pre(L, args.reps, tmp, 32, args.out or os.path.join(ROOT, "profiles", "input_fill_n32.json"))
+        return
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "detect_postprocess_n32.json")
     if args.post:
         with tempfile.TemporaryDirectory() as tmp:
             post(L, args.reps, tmp, 32, args.candidates, args.out)
