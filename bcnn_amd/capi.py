@@ -110,6 +110,7 @@ def lib():
         "bcnn_set_data_parallel": (i, [vp, i, i]), "bcnn_set_data_parallel_comm": (i, [vp, i, i, cp]),
         "bcnn_set_weight_gradient_stream": (None, [vp, i]),
         "bcnn_set_inference_precision": (i, [vp, i]), "bcnn_get_inference_precision": (i, [vp]),
+        "bcnn_set_loader_on_device": (i, [vp, i]), "bcnn_get_loader_on_device": (i, [vp]),
         "bcnn_set_gradient_ready_callback": (None, [vp, vp, vp]),
         "bcnn_get_gradient_arena": (vp, [vp, C.POINTER(sz)]), "bcnn_get_parameter_arena": (vp, [vp, C.POINTER(sz)]),
         "bcnn_synchronize": (None, [vp]), "bcnn_peek_tensor": (tp, [vp, i]), "bcnn_get_num_nodes": (i, [vp]),
@@ -273,6 +274,15 @@ class Net:
 
     def get_inference_precision(self):
         return self.L.bcnn_get_inference_precision(self.net)
+
+    def set_loader_on_device(self, on):
+        """bcnn_set_loader_on_device: bcnn_loader_next makes the input batch on the device from the raw uint8 samples
+        (augmentation, centre crop and conversion; bit-identical to the host path). The host copy of tensor 0 is then not
+        written: download(0) refreshes it. Returns the bcnn_status."""
+        return self.L.bcnn_set_loader_on_device(self.net, 1 if on else 0)
+
+    def get_loader_on_device(self):
+        return self.L.bcnn_get_loader_on_device(self.net)
 
     def compile(self):
         assert self.L.bcnn_compile_net(self.net) == 0

@@ -60,6 +60,7 @@ enum ScratchSlot {
     SCRATCH_W43FF_TAIL,    // current stream: piece outputs of its K-split tail (experiment build)
     SCRATCH_DETECT,        // current stream: image sizes, counts, sort order and box records of the batched YOLO decode (detect.hip)
     SCRATCH_IMAGES,        // current stream: descriptors, tap tables and uint8 pixels of the batched input fill (image_fill.hip)
+    SCRATCH_AUGMENT,       // current stream: records, channel sums, tap tables, raw and augmented uint8 samples of a training batch (augment.hip)
     SCRATCH_SLOTS
 };
 // A block of at least `floats` floats for `slot` on the calling thread's device; valid until that slot's next call.

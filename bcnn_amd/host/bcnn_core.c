@@ -290,6 +290,7 @@ void bcnn_end_net(bcnn_net **pnet) {
     for (int i = 0; i < net->num_tensors; ++i) bcnn_tensor_destroy(&net->tensors[i]);
     free(net->tensors);
     bcnn_hip_free(hc->workspace_gpu);
+    bcnn_free_loader_stage(net);
     free(hc->param_ids);
     free(hc);
     free(net->learner); free(net->data_aug); bcnn_destroy_data_loader(net); free(net->inputs);
@@ -704,6 +705,16 @@ bcnn_status bcnn_set_inference_precision(bcnn_net *net, bcnn_precision p) {
 
 bcnn_precision bcnn_get_inference_precision(const bcnn_net *net) {
     return (bcnn_precision)((const bcnn_hip_context *)net->hip_ctx)->inference_precision;
+}
+
+bcnn_status bcnn_set_loader_on_device(bcnn_net *net, int on) {
+    if (!net) return BCNN_INVALID_PARAMETER;
+    hctx(net)->loader_on_device = on ? 1 : 0;
+    return BCNN_SUCCESS;
+}
+
+int bcnn_get_loader_on_device(const bcnn_net *net) {
+    return net ? ((const bcnn_hip_context *)net->hip_ctx)->loader_on_device : 0;
 }
 
 void bcnn_set_gradient_ready_callback(bcnn_net *net, bcnn_gradient_ready_fn fn, void *user) {

@@ -5,6 +5,8 @@
  *   bcnn_set_data_loader      opens the train / test streams of one of the formats below and sizes the sample buffers
  *   bcnn_loader_next          fills one batch on the host, sample by sample, then uploads inputs (+ labels) to the device
  *                             (the reference's H2D hook, bcnn_data.c:413-425)
+ *                             with bcnn_set_loader_on_device the host only reads, decodes and draws; the raw samples and one
+ *                             record each go up in one copy and ../csrc/augment.hip makes the float batch (same bits)
  *   bcnn_augment_data_with_*  augmentation ranges; bcnn_apply_data_augmentation draws the parameters of one sample from
  *                             libc rand() in the reference's order (flip, shift, scale, rotation, contrast, brightness), so
  *                             that a run seeded like a reference run sees the same samples byte for byte
@@ -22,6 +24,7 @@
  * rand() call for call like the reference (parameters, the distortion's own seed, four values per spot), so that the other
  * augmentations stay aligned; the image is left untouched and a warning is printed once.
  */
+#include <math.h>
 #include <string.h>
 
 #include <bh/bh_string.h>
@@ -29,6 +32,7 @@
 #include <bip/bip.h>
 
 #include "bcnn_internal.h"
+#include "bip_resize_tap.h" /* the taps of the scale stage, tabulated here for the device path */
 
 /* ---- augmentation ranges (reference bcnn_data.c:144-209) ---------------------------------------------------------- */
 void bcnn_augment_data_with_shift(bcnn_net *net, int width_shift_range, int height_shift_range) {
@@ -72,54 +76,48 @@ static int rand_between(int lo, int hi) {
 static float rand_centred(float range) { return (float)(rand() - RAND_MAX / 2) / RAND_MAX * range; }
 static float rand_span(float a, float b) { return ((float)rand() / RAND_MAX) * (b - a) + a; }
 
-/* One sample, in place. `scratch` (same size as the image) is needed by flip / shift / rotation. */
-bcnn_status bcnn_apply_data_augmentation(unsigned char *img, int width, int height, int depth, bcnn_data_augmenter *p,
-                                         unsigned char *scratch) {
-    const size_t stride = (size_t)width * depth, bytes = stride * height;
-    int x_ul = 0, y_ul = 0;
-    if (p->random_fliph && p->apply_fliph) {
-        bip_fliph_image(img, width, height, depth, stride, scratch, stride);
-        memcpy(img, scratch, bytes);
-    }
+/* What the draws of one sample decide. The pixel work reads nothing else: augment_pixels below on the host, the kernels of
+ * ../csrc/augment.hip on the device (bcnn_set_loader_on_device). */
+typedef struct {
+    int flip, shift, scale, rotate, contrast, brighten; /* which stages run */
+    int x_ul, y_ul;                                     /* shift origin; (0, 0) without a shift */
+    float scale_factor, theta, contrast_factor;
+    int brightness;
+} aug_draw;
+
+/* Draws the parameters of one sample from rand() in the reference's order and number (shift x, shift y, scale, rotation,
+ * contrast, brightness, then the draws of the two effects that are not built), leaves them in `p` as the reference does,
+ * and touches no pixel. With use_precomputed the values already in `p` are taken instead. */
+static void draw_augmentation(bcnn_data_augmenter *p, aug_draw *d) {
+    memset(d, 0, sizeof(*d));
+    d->flip = p->random_fliph && p->apply_fliph;
     if (p->range_shift_x || p->range_shift_y) {
+        d->shift = 1;
         if (p->use_precomputed) {
-            x_ul = p->shift_x;
-            y_ul = p->shift_y;
+            d->x_ul = p->shift_x;
+            d->y_ul = p->shift_y;
         } else {
-            x_ul = p->shift_x = (int)rand_centred((float)p->range_shift_x);
-            y_ul = p->shift_y = (int)rand_centred((float)p->range_shift_y);
+            d->x_ul = p->shift_x = (int)rand_centred((float)p->range_shift_x);
+            d->y_ul = p->shift_y = (int)rand_centred((float)p->range_shift_y);
         }
-        memset(scratch, 128, bytes);
-        bip_crop_image(img, width, height, stride, x_ul, y_ul, scratch, width, height, stride, depth);
-        memcpy(img, scratch, bytes);
     }
     if (p->max_scale > 0.0f || p->min_scale > 0.0f) {
-        const float scale = p->use_precomputed ? p->scale : (p->scale = rand_span(p->min_scale, p->max_scale));
-        const int ws = (int)(width * scale), hs = (int)(height * scale);
-        unsigned char *scaled = (unsigned char *)calloc((size_t)ws * hs * depth, 1);
-        if (!scaled) return BCNN_FAILED_ALLOC;
-        bip_resize_bilinear(img, width, height, stride, scaled, ws, hs, (size_t)ws * depth, depth);
-        /* cropped back at the shift's origin, over the unscaled image */
-        bip_crop_image(scaled, ws, hs, (size_t)ws * depth, x_ul, y_ul, img, width, height, stride, depth);
-        free(scaled);
+        d->scale = 1;
+        d->scale_factor = p->use_precomputed ? p->scale : (p->scale = rand_span(p->min_scale, p->max_scale));
     }
     if (p->rotation_range > 0.0f) {
-        const float theta =
-            p->use_precomputed ? p->rotation : (p->rotation = bip_deg2rad(rand_centred(p->rotation_range)));
-        memset(scratch, 128, bytes);
-        bip_rotate_image(img, width, height, stride, scratch, width, height, stride, depth, theta, width / 2, height / 2,
-                         BILINEAR);
-        memcpy(img, scratch, bytes);
+        d->rotate = 1;
+        d->theta = p->use_precomputed ? p->rotation : (p->rotation = bip_deg2rad(rand_centred(p->rotation_range)));
     }
     if (p->min_contrast > 0.0f || p->max_contrast > 0.0f) {
-        const float c = p->use_precomputed ? p->contrast : (p->contrast = rand_span(p->min_contrast, p->max_contrast));
-        bip_contrast_stretch(img, stride, width, height, depth, img, stride, c);
+        d->contrast = 1;
+        d->contrast_factor = p->use_precomputed ? p->contrast : (p->contrast = rand_span(p->min_contrast, p->max_contrast));
     }
     if (p->min_brightness != 0 || p->max_brightness != 0) {
-        const int b = p->use_precomputed
-                          ? p->brightness
-                          : (p->brightness = (int)rand_span((float)p->min_brightness, (float)p->max_brightness));
-        bip_image_brightness(img, stride, width, height, depth, img, stride, b);
+        d->brighten = 1;
+        d->brightness = p->use_precomputed
+                            ? p->brightness
+                            : (p->brightness = (int)rand_span((float)p->min_brightness, (float)p->max_brightness));
     }
     /* Not built: Perlin distortion and random spotlights. Their draws are consumed exactly as the reference consumes them,
      * so that the samples behind this one see the generator in the reference's state: three parameters (when not
@@ -143,7 +141,47 @@ bcnn_status bcnn_apply_data_augmentation(unsigned char *img, int width, int heig
         fprintf(stderr, "[bcnn] max_distortion / max_spots: Perlin distortion and random spotlights are not built; samples keep "
                         "their pixels (the random stream stays aligned with the reference)\n");
     }
+}
+
+/* The drawn augmentation of one sample, in place. `scratch` (same size as the image) is needed by flip / shift / rotation. */
+static bcnn_status augment_pixels(unsigned char *img, int width, int height, int depth, const aug_draw *d,
+                                  unsigned char *scratch) {
+    const size_t stride = (size_t)width * depth, bytes = stride * height;
+    if (d->flip) {
+        bip_fliph_image(img, width, height, depth, stride, scratch, stride);
+        memcpy(img, scratch, bytes);
+    }
+    if (d->shift) {
+        memset(scratch, 128, bytes);
+        bip_crop_image(img, width, height, stride, d->x_ul, d->y_ul, scratch, width, height, stride, depth);
+        memcpy(img, scratch, bytes);
+    }
+    if (d->scale) {
+        const int ws = (int)(width * d->scale_factor), hs = (int)(height * d->scale_factor);
+        unsigned char *scaled = (unsigned char *)calloc((size_t)ws * hs * depth, 1);
+        if (!scaled) return BCNN_FAILED_ALLOC;
+        bip_resize_bilinear(img, width, height, stride, scaled, ws, hs, (size_t)ws * depth, depth);
+        /* cropped back at the shift's origin, over the unscaled image */
+        bip_crop_image(scaled, ws, hs, (size_t)ws * depth, d->x_ul, d->y_ul, img, width, height, stride, depth);
+        free(scaled);
+    }
+    if (d->rotate) {
+        memset(scratch, 128, bytes);
+        bip_rotate_image(img, width, height, stride, scratch, width, height, stride, depth, d->theta, width / 2, height / 2,
+                         BILINEAR);
+        memcpy(img, scratch, bytes);
+    }
+    if (d->contrast) bip_contrast_stretch(img, stride, width, height, depth, img, stride, d->contrast_factor);
+    if (d->brighten) bip_image_brightness(img, stride, width, height, depth, img, stride, d->brightness);
     return BCNN_SUCCESS;
+}
+
+/* One sample, in place: the draws, then the pixels. */
+bcnn_status bcnn_apply_data_augmentation(unsigned char *img, int width, int height, int depth, bcnn_data_augmenter *p,
+                                         unsigned char *scratch) {
+    aug_draw d;
+    draw_augmentation(p, &d);
+    return augment_pixels(img, width, height, depth, &d, scratch);
 }
 
 /* ---- streams ------------------------------------------------------------------------------------------------------ */
@@ -200,6 +238,146 @@ static void wrap_at_eof(FILE *f) {
     unsigned char probe;
     if (fread(&probe, 1, 1, f) == 0) rewind(f);
     else fseek(f, -1, SEEK_CUR);
+}
+
+/* ---- the batch on the device (bcnn_set_loader_on_device) ------------------------------------------------------------ */
+/* While a device-mode bcnn_loader_next runs, the readers below hand each raw sample and its draws to this block instead of
+ * augmenting and converting it; bcnn_hip_augment_batch then makes the float batch on the device. Grow-only, owned by the
+ * net's device context. */
+typedef struct {
+    uint8_t *pixels;                  /* batch x (w * h * c) raw samples */
+    bcnn_hip_augment_record *records; /* batch */
+    int32_t *taps;                    /* batch x (w + h) (index, fraction) pairs; written for samples that scale */
+    size_t cap_bytes, cap_records, cap_taps;
+    int w, h, c;                      /* the stored sample of the batch being gathered */
+    int active;                       /* inside a device-mode bcnn_loader_next */
+    /* List loaders: a file that fails to decode leaves the sample buffer as it was, and the reference then augments and
+     * converts that buffer again. On the host path the buffer holds the previous sample AUGMENTED; on the device path it
+     * holds it raw, and `owed` remembers the pixel work that makes the two equal should a decode fail next. */
+    int owed;
+    aug_draw owed_draw;
+} loader_stage;
+
+static loader_stage *stage_of(bcnn_net *net) { return (loader_stage *)((bcnn_hip_context *)net->hip_ctx)->loader_stage; }
+
+void bcnn_free_loader_stage(bcnn_net *net) {
+    loader_stage *ls = stage_of(net);
+    if (!ls) return;
+    free(ls->pixels); free(ls->records); free(ls->taps); free(ls);
+    ((bcnn_hip_context *)net->hip_ctx)->loader_stage = NULL;
+}
+
+static void settle_owed(bcnn_net *net, bcnn_loader *it) {
+    loader_stage *ls = stage_of(net);
+    if (!ls || !ls->owed) return;
+    ls->owed = 0;
+    bcnn_tensor *in = &net->tensors[0];
+    unsigned char *scratch = (unsigned char *)calloc((size_t)bcnn_tensor_size3d(in), 1);
+    if (scratch) augment_pixels(it->input_uchar, in->w, in->h, in->c, &ls->owed_draw, scratch);
+    free(scratch);
+}
+
+/* Sizes the block for one batch of w x h x c samples; NULL when this batch has to go the host way: no device input
+ * tensor, more than 4 channels (bip_resize_bilinear's limit, and the kernels'), or a stored sample that does not match
+ * the net input. */
+static loader_stage *stage_begin(bcnn_net *net, bcnn_loader *it) {
+    bcnn_hip_context *hc = (bcnn_hip_context *)net->hip_ctx;
+    bcnn_tensor *in = &net->tensors[0];
+    if (!hc->loader_on_device || !in->data_gpu || in->c < 1 || in->c > 4 || net->batch_size < 1 || in->n < net->batch_size)
+        return NULL;
+    const int stored = it->type == BCNN_LOAD_MNIST || it->type == BCNN_LOAD_CIFAR10;
+    if (stored && (it->input_depth != in->c || it->input_width < in->w || it->input_height < in->h)) return NULL;
+    if (!hc->loader_stage) hc->loader_stage = calloc(1, sizeof(loader_stage));
+    loader_stage *ls = (loader_stage *)hc->loader_stage;
+    if (!ls) return NULL;
+    ls->w = stored ? it->input_width : in->w;
+    ls->h = stored ? it->input_height : in->h;
+    ls->c = in->c;
+    const size_t n = (size_t)net->batch_size, bytes = n * ls->w * ls->h * ls->c, taps = n * ((size_t)ls->w + ls->h) * 2;
+    if (ls->cap_bytes < bytes) {
+        free(ls->pixels);
+        ls->pixels = (uint8_t *)calloc(bytes, 1);
+        ls->cap_bytes = ls->pixels ? bytes : 0;
+    }
+    if (ls->cap_records < n) {
+        free(ls->records);
+        ls->records = (bcnn_hip_augment_record *)calloc(n, sizeof(bcnn_hip_augment_record));
+        ls->cap_records = ls->records ? n : 0;
+    }
+    if (ls->cap_taps < taps) {
+        free(ls->taps);
+        ls->taps = (int32_t *)calloc(taps, sizeof(int32_t));
+        ls->cap_taps = ls->taps ? taps : 0;
+    }
+    if (!ls->pixels || !ls->records || !ls->taps) return NULL;
+    ls->active = 1;
+    return ls;
+}
+
+/* What the device needs of one sample's draws. Every float -> integer step is the host's own expression: ws / hs as
+ * bcnn_apply_data_augmentation forms them, the taps of bip_resize_bilinear, ca / sa of bip_rotate_image, the gain of
+ * bip_contrast_stretch. A scale draw that leaves ws < 1 or hs < 1 resizes to nothing on the host (calloc(0), then
+ * bip_resize_bilinear refuses the empty extent and the paste copies no byte): the stage is left out. */
+static void fill_record(bcnn_hip_augment_record *r, int32_t *taps, const aug_draw *d, int w, int h) {
+    memset(r, 0, sizeof(*r));
+    if (d->flip) r->flags |= BCNN_HIP_AUG_FLIP;
+    if (d->shift) {
+        r->flags |= BCNN_HIP_AUG_SHIFT;
+        r->x_ul = d->x_ul;
+        r->y_ul = d->y_ul;
+    }
+    if (d->scale) {
+        const int ws = (int)(w * d->scale_factor), hs = (int)(h * d->scale_factor);
+        if (ws >= 1 && hs >= 1) {
+            r->flags |= BCNN_HIP_AUG_SCALE;
+            /* the resized image is pasted back at (x_ul, y_ul): column x of the sample shows its column x + x_ul */
+            const float xs = bip_resize_scale((size_t)w, (size_t)ws), ys = bip_resize_scale((size_t)h, (size_t)hs);
+            for (int x = 0; x < w; ++x) {
+                const long long X = (long long)x + d->x_ul;
+                taps[2 * x] = -1;
+                taps[2 * x + 1] = 0;
+                if (X >= 0 && X < ws) bip_resize_tap((size_t)X, xs, (size_t)w, &taps[2 * x], &taps[2 * x + 1]);
+            }
+            int32_t *ty = taps + 2 * (size_t)w;
+            for (int y = 0; y < h; ++y) {
+                const long long Y = (long long)y + d->y_ul;
+                ty[2 * y] = -1;
+                ty[2 * y + 1] = 0;
+                if (Y >= 0 && Y < hs) bip_resize_tap((size_t)Y, ys, (size_t)h, &ty[2 * y], &ty[2 * y + 1]);
+            }
+        }
+    }
+    if (d->rotate) {
+        r->flags |= BCNN_HIP_AUG_ROTATE;
+        r->ca = (int32_t)(cos(d->theta) * 65536);
+        r->sa = (int32_t)(sin(d->theta) * 65536);
+    }
+    if (d->contrast) {
+        r->flags |= BCNN_HIP_AUG_CONTRAST;
+        r->gain = (int32_t)(d->contrast_factor * (1 << 12) + 0.5);
+    }
+    if (d->brighten) r->brightness = d->brightness;
+}
+
+/* The loader's sample buffer into slot idx of the block, with this sample's draws (TRAIN mode) or the identity record. */
+static bcnn_status stage_sample(bcnn_net *net, bcnn_loader *it, loader_stage *ls, int idx, int w, int h, int c,
+                                int list_loader) {
+    if (w != ls->w || h != ls->h || c != ls->c || idx < 0 || (size_t)idx >= ls->cap_records) return BCNN_INVALID_DATA;
+    const size_t bytes = (size_t)w * h * c;
+    memcpy(ls->pixels + (size_t)idx * bytes, it->input_uchar, bytes);
+    bcnn_hip_augment_record *r = &ls->records[idx];
+    memset(r, 0, sizeof(*r));
+    ls->owed = 0;
+    if (net->mode == BCNN_MODE_TRAIN && net->data_aug) {
+        aug_draw d;
+        draw_augmentation(net->data_aug, &d);
+        fill_record(r, ls->taps + (size_t)idx * ((size_t)w + h) * 2, &d, w, h);
+        if (list_loader) {
+            ls->owed = 1;
+            ls->owed_draw = d;
+        }
+    }
+    return BCNN_SUCCESS;
 }
 
 /* ---- sample -> tensors ---------------------------------------------------------------------------------------------- */
@@ -302,8 +480,13 @@ static bcnn_status mnist_next(bcnn_loader *it, bcnn_net *net, int idx) {
         bcnn_log(net->log_ctx, BCNN_LOG_ERROR, "Corrupted Mnist data\n");
         return BCNN_INVALID_DATA;
     }
-    BCNN_CHECK_STATUS(augment_if_training(net, it->input_uchar, it->input_width, it->input_height, it->input_depth, 0));
-    sample_to_input(net, it, idx);
+    loader_stage *ls = stage_of(net);
+    if (ls && ls->active) {
+        BCNN_CHECK_STATUS(stage_sample(net, it, ls, idx, it->input_width, it->input_height, it->input_depth, 0));
+    } else {
+        BCNN_CHECK_STATUS(augment_if_training(net, it->input_uchar, it->input_width, it->input_height, it->input_depth, 0));
+        sample_to_input(net, it, idx);
+    }
     if (net->mode != BCNN_MODE_PREDICT) {
         int n;
         float *y = label_slot(net, idx, &n);
@@ -333,8 +516,13 @@ static bcnn_status cifar10_next(bcnn_loader *it, bcnn_net *net, int idx) {
     }
     for (int k = 0; k < 3; ++k) /* planar -> interleaved */
         for (int p = 0; p < 1024; ++p) it->input_uchar[p * 3 + k] = rec[1 + k * 1024 + p];
-    BCNN_CHECK_STATUS(augment_if_training(net, it->input_uchar, 32, 32, 3, 0));
-    sample_to_input(net, it, idx);
+    loader_stage *ls = stage_of(net);
+    if (ls && ls->active) {
+        BCNN_CHECK_STATUS(stage_sample(net, it, ls, idx, 32, 32, 3, 0));
+    } else {
+        BCNN_CHECK_STATUS(augment_if_training(net, it->input_uchar, 32, 32, 3, 0));
+        sample_to_input(net, it, idx);
+    }
     if (net->mode != BCNN_MODE_PREDICT) {
         int n;
         float *y = label_slot(net, idx, &n);
@@ -391,8 +579,16 @@ static bcnn_status load_image(bcnn_net *net, char *path, int w, int h, int c, un
 /* reference bcnn_fill_input_tensor (bcnn_data.c:336-377): a sample that fails to decode leaves the buffer as it was */
 void bcnn_fill_input_tensor(bcnn_net *net, bcnn_loader *it, char *path_img, int idx) {
     bcnn_tensor *in = &net->tensors[0];
-    load_image(net, path_img, in->w, in->h, in->c, it->input_uchar, net->data_aug ? &net->data_aug->shift_x : NULL,
-               net->data_aug ? &net->data_aug->shift_y : NULL);
+    loader_stage *ls = stage_of(net);
+    if (load_image(net, path_img, in->w, in->h, in->c, it->input_uchar, net->data_aug ? &net->data_aug->shift_x : NULL,
+                   net->data_aug ? &net->data_aug->shift_y : NULL) != BCNN_SUCCESS)
+        settle_owed(net, it); /* the buffer as the host path would have left it */
+    else if (ls)
+        ls->owed = 0;
+    if (ls && ls->active) {
+        stage_sample(net, it, ls, idx, in->w, in->h, in->c, 1);
+        return;
+    }
     if (net->data_aug) augment_if_training(net, it->input_uchar, in->w, in->h, in->c, 1);
     bcnn_convert_img_to_float(it->input_uchar, in->w, in->h, in->c, 1 / 127.5f, net->data_aug ? net->data_aug->swap_to_bgr : 0,
                               127.5f, 127.5f, 127.5f, in->data + (size_t)idx * bcnn_tensor_size3d(in));
@@ -507,6 +703,7 @@ bcnn_status bcnn_set_data_loader(bcnn_net *net, bcnn_loader_type type, const cha
  * tensors itself and only the upload happens. */
 bcnn_status bcnn_loader_next(bcnn_net *net) {
     bcnn_loader *it = net->data_loader;
+    loader_stage *ls = it ? stage_begin(net, it) : NULL; /* non-NULL: the input batch is made on the device */
     if (it) {
         int failures = 0;
         for (int i = 0; i < net->batch_size; ++i) {
@@ -520,6 +717,7 @@ bcnn_status bcnn_loader_next(bcnn_net *net) {
             if (st != BCNN_SUCCESS) {
                 if (++failures >= 1000) {
                     bcnn_log(net->log_ctx, BCNN_LOG_ERROR, "bcnn_loader_next: 1000 samples in a row could not be read\n");
+                    if (ls) ls->active = 0;
                     return BCNN_INVALID_DATA;
                 }
                 --i;
@@ -528,7 +726,16 @@ bcnn_status bcnn_loader_next(bcnn_net *net) {
             failures = 0;
         }
     }
+    if (ls) { /* one copy of the raw samples and their records, two launches; tensors[0].data is not written */
+        bcnn_tensor *in = &net->tensors[0];
+        ls->active = 0;
+        const int list_loader = it->type != BCNN_LOAD_MNIST && it->type != BCNN_LOAD_CIFAR10;
+        if (bcnn_hip_augment_batch(in->data_gpu, in->n, in->c, in->h, in->w, net->batch_size, ls->w, ls->h, ls->pixels,
+                                   ls->records, ls->taps, list_loader && net->data_aug ? net->data_aug->swap_to_bgr : 0) != 0)
+            BCNN_ERROR(net->log_ctx, BCNN_INVALID_PARAMETER, "bcnn_loader_next: the batch does not fit the device loader path\n");
+    }
     for (int i = 0; i < net->num_inputs; ++i) {
+        if (ls && net->inputs[i] == 0) continue; /* the host copy is stale in this mode */
         bcnn_tensor *t = &net->tensors[net->inputs[i]];
         if (t->data && t->data_gpu) bcnn_hip_memcpy_h2d(t->data_gpu, t->data, (size_t)bcnn_tensor_size(t) * sizeof(float));
     }

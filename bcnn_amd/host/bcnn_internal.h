@@ -125,6 +125,7 @@ bcnn_status bcnn_open_dataset(bcnn_loader *iter, struct bcnn_net *net, const cha
 bcnn_status bcnn_switch_data_handles(struct bcnn_net *net, bcnn_loader *iter);
 void bcnn_fill_input_tensor(struct bcnn_net *net, bcnn_loader *iter, char *path_img, int idx);
 void bcnn_destroy_data_loader(struct bcnn_net *net);
+void bcnn_free_loader_stage(struct bcnn_net *net);
 
 /* ---- device context of a net (reference analogue: bcnn_cuda_context, src/bcnn_net.h:37-42) ------ */
 typedef struct bcnn_hip_context {
@@ -168,6 +169,8 @@ typedef struct bcnn_hip_context {
     int no_side_stream; /* bcnn_set_weight_gradient_stream(net, 0) */
     uint64_t dropout_seed; /* bcnn_set_dropout_seed; 0 until set */
     int inference_precision; /* bcnn_set_inference_precision (a bcnn_precision); read by the convolution node outside TRAIN mode */
+    int loader_on_device; /* bcnn_set_loader_on_device: bcnn_loader_next makes the input batch with bcnn_hip_augment_batch */
+    void *loader_stage;   /* its host-side gather block (bcnn_data.c: loader_stage); freed by bcnn_free_loader_stage */
     int detect_capacity; /* 1.25 x the most boxes an image of the latest bcnn_yolo_get_detections_batch had: the next call's record capacity
                           * when above the default (0: never called) */
 } bcnn_hip_context;

@@ -285,6 +285,22 @@ BCNN_API bcnn_status bcnn_get_lifted_struct_loss(bcnn_net *net, float *loss, int
 typedef enum { BCNN_PRECISION_FP32 = 0, BCNN_PRECISION_BF16 = 1 } bcnn_precision;
 BCNN_API bcnn_status bcnn_set_inference_precision(bcnn_net *net, bcnn_precision p);
 BCNN_API bcnn_precision bcnn_get_inference_precision(const bcnn_net *net);
+/* Where bcnn_loader_next makes the input batch (default 0: on the host, sample by sample, as the reference does). With
+ * on != 0 the host still reads and decodes every sample, crops a list image to the net input and draws the sample's
+ * augmentation parameters from rand() in the reference's order and number (net->data_aug holds the latest draws as
+ * before; the draws of max_distortion / max_spots are consumed too), but touches no pixel: the raw uint8 samples of the
+ * batch and one small record per sample go to the device in one copy, and two kernel launches (whatever the batch size)
+ * flip, shift, scale, rotate, adjust contrast and brightness, centre-crop and convert them into the float input tensor.
+ * The device tensor holds, bit for bit, what the host path writes for the same files, rand() seed and settings, in every
+ * mode (outside BCNN_MODE_TRAIN: centre crop and conversion only) and for every loader type. Labels, skipped samples,
+ * wrap-around and rewind are unchanged. tensors[0].data is NOT written and bcnn_loader_next does not upload it;
+ * bcnn_get_tensor_by_index / bcnn_download_tensor refresh it from the device as usual. A scale draw that leaves an
+ * extent below 1 pixel leaves the sample unscaled, as the host path does. A batch goes the host way regardless when the
+ * input tensor has more than 4 channels or no device buffer, or an MNIST / CIFAR-10 record does not match the input's
+ * channels. May be called before or after bcnn_set_data_loader / bcnn_compile_net and between batches; without a loader
+ * it has no effect. A NULL net returns BCNN_INVALID_PARAMETER. Config files: `loader_on_device=1` in the [net] section. */
+BCNN_API bcnn_status bcnn_set_loader_on_device(bcnn_net *net, int on);
+BCNN_API int bcnn_get_loader_on_device(const bcnn_net *net);
 /* Detections of EVERY image of the batch from the latest forward, in one call. widths[b] / heights[b]: the original
  * size of image b (what bcnn_yolo_get_detections takes as w, h). dets[b] receives a malloc'ed array of num_dets[b]
  * boxes (NULL / 0 when image b has no candidate); per image, the result is what

@@ -633,6 +633,56 @@ int bcnn_hip_fill_images(float *dst_d, int n, int c, int h, int w, int num_image
                          int swap_to_bgr, float mean_r, float mean_g, float mean_b);
 
 /* ---------------------------------------------------------------------------------------------
+ * The input tensor of a training batch from the loader's raw uint8 samples (augment.hip): online augmentation, centre
+ * crop and conversion on the device. Entries 0 .. num_samples - 1 of the NCHW float tensor dst_d [n][c][h][w] are
+ * written; the others are not. pixels (HOST) holds num_samples dense interleaved HWC samples of src_w x src_h x c bytes,
+ * records (HOST) one record per sample with what the host drew for it (bcnn_data.c draws from rand() in the reference's
+ * order and does every float -> integer step with its own arithmetic; the kernels only do integer and fp32 work whose
+ * result does not depend on the order of evaluation). With S0 the sample, per pixel (x, y) and channel:
+ *   FLIP     S1(x, y) = S0(src_w - 1 - x, y)
+ *   SHIFT    S2(x, y) = S1(x + x_ul, y + y_ul) inside the sample, else 128          (bip_crop_image onto a grey canvas)
+ *   SCALE    S3(x, y) = bip_resize_blend of the four S2 samples at (tapx[x], tapy[y]) where both taps have an index
+ *            >= 0, else S2(x, y). taps (HOST; may be NULL when no record has SCALE) holds per sample src_w (index,
+ *            fraction) int32 pairs for the columns followed by src_h pairs for the rows: the tap of the resized image's
+ *            column x + x_ul by bip_resize_tap (bcnn_amd/host/bip_resize_tap.h), or index -1 where the resized image
+ *            pasted back at the shift's origin does not cover the column
+ *   ROTATE   S4(x, y): 16.16 inverse map about (src_w / 2, src_h / 2) with ca = cos * 65536, sa = sin * 65536 and 32-bit
+ *            wrap-around; 0 unless 0 <= mx < src_w - 1 and 0 <= my < src_h - 1; the blend is four products of three
+ *            fp32 factors summed left to right, truncated                                             (bip_rotate_image)
+ *   CONTRAST S5 = clamp(((S4 - mean) * gain + 2048 >> 12) + mean), mean = per-channel sum of S4 / (src_w * src_h) in
+ *            unsigned 32-bit arithmetic, gain in 20.12                                            (bip_contrast_stretch)
+ *   always   S6 = clamp(S5 + brightness); plane k of entry b = ((float)S6(x + (src_w - w) / 2, y + (src_h - h) / 2)[ks]
+ *            - 127.5f) * (1 / 127.5f), ks = 2 - k when swap_to_bgr and c == 3, else k   (bcnn_convert_img_to_float)
+ * A stage whose flag is clear is the identity; a zeroed record is centre crop and conversion only. The result equals the
+ * host loader's (bcnn_apply_data_augmentation, bip_crop_image, bcnn_convert_img_to_float) bit for bit.
+ * One pinned staging block (records, zeroed channel sums, taps, pixels) goes up in ONE copy on the current stream; TWO
+ * kernels follow, whatever the batch size: the first writes S4 to a uint8 scratch of the library's table (a lane per
+ * pixel) and adds the per-channel sums of the samples with CONTRAST with one integer atomicAdd per wave (integer sums
+ * do not depend on the order: the result is the same from run to run); the second applies S5, S6, crop and conversion, a
+ * lane per 8 pixels of a row for all c planes, 16-byte stores between a scalar head and tail. The samples have been copied
+ * when the call returns; a later call waits for the earlier call's copy before it reuses the pinned block.
+ * Returns 0, or 1 with nothing staged or queued: a NULL dst_d / pixels / records; n, h or w < 1; c outside 1..4;
+ * num_samples outside 1..n; src_w < w or src_h < h; a record with SCALE and taps == NULL, or a tap index outside
+ * [-1, max(extent - 2, 0)]; more than 2 GiB to stage.
+ * ------------------------------------------------------------------------------------------- */
+#define BCNN_HIP_AUG_FLIP 1
+#define BCNN_HIP_AUG_SHIFT 2
+#define BCNN_HIP_AUG_SCALE 4
+#define BCNN_HIP_AUG_ROTATE 8
+#define BCNN_HIP_AUG_CONTRAST 16
+typedef struct bcnn_hip_augment_record {
+    int32_t flags;      /* BCNN_HIP_AUG_* */
+    int32_t x_ul, y_ul; /* SHIFT */
+    int32_t ca, sa;     /* ROTATE */
+    int32_t gain;       /* CONTRAST */
+    int32_t brightness; /* added last; 0 = none */
+    int32_t reserved;   /* 0 */
+} bcnn_hip_augment_record;
+int bcnn_hip_augment_batch(float *dst_d, int n, int c, int h, int w, int num_samples, int src_w, int src_h,
+                           const uint8_t *pixels, const bcnn_hip_augment_record *records, const int32_t *taps,
+                           int swap_to_bgr);
+
+/* ---------------------------------------------------------------------------------------------
  * Transposed convolution (deconvolution), implicit GEMMs on fp32 MFMA with no col2im / im2col buffer.
  * Replaces bcnn_forward_deconv_layer_gpu / bcnn_backward_deconv_layer_gpu (bcnn_deconv_layer.c:249-320) with the
  * semantics of the CPU workers (:150-193, :195-246):
