@@ -93,6 +93,8 @@ size_t bcnn_hip_trace_read(char *buf, size_t cap);
  * BLAS-1 / per-channel helpers.  Replaces bcnn_cuda_axpy/scal/copy (bcnn_mat.cu:44-100),
  * bcnn_cuda_add_bias / bcnn_cuda_grad_bias (bcnn_mat.cu:348-391), bcnn_scales_gpu /
  * bcnn_grad_scales_gpu (bcnn_mat.cu:393-438); CPU semantics bcnn_mat.c:52-115, 319-412, 761-811.
+ * Tensor pointers of the per-channel helpers must be 16-byte aligned: the reduction sweeps behind the gradient helpers take
+ * their float4 path on hw % 4 == 0 alone.
  * ------------------------------------------------------------------------------------------- */
 void bcnn_hip_axpy(size_t n, float a, const float *x_d, float *y_d);   /* y += a*x */
 void bcnn_hip_scal(size_t n, float a, float *x_d);                      /* x *= a (a==0 -> zero-fill) */
@@ -144,6 +146,8 @@ void bcnn_hip_activation_backward(const float *x_d, float *dx_d, size_t size, in
  *             x_norm_d may be NULL (recomputed from workspace_d, mean, var).
  * `act`/`y_d` in backward: optional fused activation-backward (conv+BN+act nodes): pass the
  * post-activation output and its activation, or act = NONE.
+ * Tensor pointers (x_d, y_d, dy_d, dx_d, workspace_d, x_norm_d) must be 16-byte aligned: the statistics and gradient-sum
+ * sweeps take their float4 path on hw % 4 == 0 alone (only the elementwise sweeps check the pointers and fall back).
  * ------------------------------------------------------------------------------------------- */
 void bcnn_hip_batchnorm_forward(const float *x_d, float *y_d, float *run_mean_d, float *run_var_d,
                                 const float *scales_d, const float *bias_d, float *saved_mean_d,

@@ -12,7 +12,10 @@ import pytest
 from oracle import orc_bind as ob
 from oracle import ref_bind as rb
 
-SHAPES = [(3, 5, 37), (2, 4, 1024), (2, 3, 4100), (4, 8, 49)]  # (n, c, hw)
+SHAPES = [(3, 5, 37), (2, 4, 1024), (2, 3, 4100), (4, 8, 49),  # (n, c, hw)
+          (5, 5, 3),          # a float4 group of the flat map straddles several planes
+          (186, 31, 729),     # 4 203 414 elements: three sweeps of the flat map, the carried (plane offset, channel) step twice
+          (23, 3, 196)]       # two reduction splits of 2256 elements: the second starts in the middle of an image
 
 
 def _case(n, c, hw, seed):
