@@ -1,34 +1,55 @@
-// batchnorm.h -- the batch-norm entry points of batchnorm.hip that the convolution and pooling nodes call (conv.hip, pool.hip).
+// batchnorm.h -- the batch-norm entry points of batchnorm.hip that the convolution and pooling nodes call (conv.hip, pool.hip),
+// and the call descriptions they take: filled by name at the call site, zero-initialised, what is absent stays zero.
 #pragma once
 #include "conv_common.h"
 
 namespace bcnn_hip {
 
-// pre: statistics partials the convolution epilogue left (pre->splits > 0); res: a following eltwise node folded into the
-// apply sweep; mean_shift [c]: added to the batch mean that goes into the running mean (BnFold)
-void batchnorm_forward_impl(const float* x, float* y, float* run_mean, float* run_var, const float* scales,
-                            const float* bias, float* saved_mean, float* saved_var, float* x_norm, float* workspace,
-                            int n, int c, int hw, int mode, int act, const ConvStats* pre, const BnResidual* res,
-                            bool stats_only, const float* mean_shift = nullptr);
-// fwd_bias (optional): the forward bias; with it the forward output is recomputed from `workspace` instead of read from y
-void batchnorm_backward_impl(float* dy, float* dx, const float* y, int act, const float* scales, float* dscales,
-                             float* dbias, const float* saved_mean, const float* saved_var, float* dmean,
-                             float* dvar, const float* workspace, int n, int c, int hw, const float* fwd_bias);
-// the same when whoever wrote dy left the sums as partials[(channel * splits + i) * 2 + {S1, S2}]: no read-only sweep
-void batchnorm_backward_presummed(float* dy, const float* y, int act, const float* scales, float* dscales, float* dbias,
-                                  const float* saved_mean, const float* saved_var, float* dmean, float* dvar,
-                                  const float* workspace, int n, int c, int hw, const float* fwd_bias, const float* sums,
-                                  int splits);
-// batch-norm backward of dout * act'(out) of a following eltwise node (out recomputed, dout not rewritten), result to dx
-void batchnorm_backward_residual(const float* dout, const float* out, int act_res, const float* res, float* dres,
-                                 size_t res_count, float* dx, const float* scales, float* dscales, float* dbias,
-                                 const float* fwd_bias, const float* saved_mean, const float* saved_var, float* dmean,
-                                 float* dvar, const float* workspace, int n, int c, int hw);
-// the first sweep alone: S1, S2 per channel -> dbias, dscales, dmean, dvar. consts_fM: divisor of dmean in `consts` (0: n * hw)
-void batchnorm_backward_sums(const float* dy, const float* y, int act, const float* scales, float* dscales, float* dbias,
-                             const float* saved_mean, const float* saved_var, float* dmean, float* dvar,
-                             const float* workspace, int n, int c, int hw, const float* fwd_bias,
-                             const float* res = nullptr, unsigned res_count = 0, float4* consts = nullptr,
-                             float consts_fM = 0.f);
+struct BnExtent { int n, c, hw; };                 // tensors are [n][c][hw], per-channel vectors [c]
+struct BnParams { const float *scales, *bias; };   // bias: the one the forward pass adds
+struct BnSaved { const float *mean, *var; };       // the batch statistics the forward pass saved, as the backward pass reads them
+struct BnRunning { float *run_mean, *run_var; };
+struct BnGrads { float *dscales, *dbias, *dmean, *dvar; };
+
+// workspace: copy of x kept for the backward pass (may be x itself); x_norm: the normalised values, which only
+// bcnn_hip_batchnorm_forward[_stats] can still ask for; saved_*: written in TRAIN mode; pre: statistics partials the convolution
+// epilogue left (pre->splits > 0); res: a following eltwise node folded into the apply sweep; stats_only: no apply sweep;
+// mean_shift [c]: added to the batch mean that goes into the running mean (BnFold)
+struct BnFwdCall {
+    const float* x;
+    float *y, *workspace, *x_norm, *saved_mean, *saved_var;
+    BnExtent e;
+    int mode, act;
+    BnParams p;
+    BnRunning run;
+    const ConvStats* pre;
+    const BnResidual* res;
+    bool stats_only;
+    const float* mean_shift;
+};
+void batchnorm_forward_impl(const BnFwdCall& f);
+
+// dy: the gradient of the output, overwritten with that of the input and copied to dx (optional) -- or dout in its place where
+// it must not be rewritten: the result then goes to dx alone. y: the forward output; workspace: the pre-normalisation input.
+// p.bias (optional): with it the forward output is recomputed from `workspace` instead of read from y.
+// sums (optional): whoever wrote dy left partials[(channel * splits + i) * 2 + {S1, S2}]: no read-only sweep.
+// dout with res, dres, res_count: the backward of dout * act'(y) of a following eltwise node folded into the forward pass (y its
+// output, act its activation), its second operand, that one's gradient (accumulated, may be NULL) and how much of it was added.
+// consts: the table the sums sweep leaves for the apply sweep, consts_fM its divisor of dmean (0: n * hw)
+struct BnBwdCall {
+    float *dy, *dx, *dres;
+    const float *dout, *y, *workspace, *sums, *res;
+    int act, splits;
+    size_t res_count;
+    BnExtent e;
+    BnParams p;
+    BnSaved s;
+    BnGrads g;
+    float4* consts;
+    float consts_fM;
+};
+void batchnorm_backward_impl(const BnBwdCall& b);
+// the first sweep alone: S1, S2 per channel -> dbias, dscales, dmean, dvar
+void batchnorm_backward_sums(const BnBwdCall& b);
 
 }  // namespace bcnn_hip

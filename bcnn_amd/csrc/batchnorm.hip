@@ -417,57 +417,53 @@ struct BnBwdApplyBody {
     }
 };
 
-
-// pre: statistics partials already produced by the convolution epilogue (pre->splits > 0), else NULL
-void batchnorm_forward_impl(const float* x, float* y, float* run_mean, float* run_var, const float* scales,
-                            const float* bias, float* saved_mean, float* saved_var, float* x_norm, float* workspace,
-                            int n, int c, int hw, int mode, int act, const ConvStats* pre, const BnResidual* res,
-                            bool stats_only, const float* mean_shift) {
+void batchnorm_forward_impl(const BnFwdCall& f) {
+    const int n = f.e.n, c = f.e.c, hw = f.e.hw, mode = f.mode;
     const long long M = (long long)n * hw, total = M * c;
     if (!total) return;
-    const bool have_pre = pre && pre->splits > 0 && mode == BCNN_HIP_MODE_TRAIN;
+    const bool have_pre = f.pre && f.pre->splits > 0 && mode == BCNN_HIP_MODE_TRAIN;
     // read x twice (statistics, apply) + write y; one read less with fused statistics
     // (stats_only: no apply sweep -- with fused statistics only the partials are read)
-    KTimer kt(K_BN_FWD, 0.0, 4.0 * ((have_pre ? 0.0 : 1.0) + (stats_only ? 0.0 : 2.0)) * (double)total);
-    const int want_act = act;
-    if (!act_is_cheap(act)) act = BCNN_HIP_ACT_NONE;  // tanh/softplus/logistic: separate pass below
+    KTimer kt(K_BN_FWD, 0.0, 4.0 * ((have_pre ? 0.0 : 1.0) + (f.stats_only ? 0.0 : 2.0)) * (double)total);
+    const int act = act_is_cheap(f.act) ? f.act : BCNN_HIP_ACT_NONE;  // tanh/softplus/logistic: separate pass below
     BnApplyArgs a;
-    a.x = x; a.y = y; a.ws = workspace; a.xn = x_norm; a.scale = scales; a.bias = bias;
+    a.x = f.x; a.y = f.y; a.ws = f.workspace; a.xn = f.x_norm; a.scale = f.p.scales; a.bias = f.p.bias;
     a.C = c; a.HW = hw; a.act = act; a.total = total;
     a.res = nullptr; a.res_count = 0; a.act2 = BCNN_HIP_ACT_NONE;
-    if (res) {  // the caller checked: both activations cheap, 16-byte aligned operand
-        a.res = res->res;
-        a.res_count = (unsigned)(res->count < (size_t)total ? res->count : (size_t)total);
-        a.act2 = res->act;
+    if (f.res) {  // the caller checked: both activations cheap, 16-byte aligned operand
+        a.res = f.res->res;
+        a.res_count = (unsigned)(f.res->count < (size_t)total ? f.res->count : (size_t)total);
+        a.act2 = f.res->act;
     }
     a.predict = (mode == BCNN_HIP_MODE_PREDICT);
-    a.mean = run_mean; a.var = run_var;
+    a.mean = f.run.run_mean; a.var = f.run.run_var;
     a.consts = nullptr;
-    float4* consts = (mode == BCNN_HIP_MODE_TRAIN && !stats_only) ? bn_consts_scratch(c) : nullptr;
+    float4* consts = (mode == BCNN_HIP_MODE_TRAIN && !f.stats_only) ? bn_consts_scratch(c) : nullptr;
     if (mode == BCNN_HIP_MODE_PREDICT) a.ws = nullptr;  // the reference keeps no copy in PREDICT mode
     if (mode == BCNN_HIP_MODE_VALID) a.xn = nullptr;    // x_norm is only written in TRAIN mode (:230)
-    if (have_pre) {
-        bn_stats_finalize_wide_kernel<<<c, kFinalizeThreads, 0, current_stream()>>>(
-            pre->partials, c, pre->splits, (int)M, saved_mean, saved_var, run_mean, run_var, consts, scales, bias, mean_shift);
+    if (mode == BCNN_HIP_MODE_TRAIN) {
+        if (have_pre) {
+            bn_stats_finalize_wide_kernel<<<c, kFinalizeThreads, 0, current_stream()>>>(
+                f.pre->partials, c, f.pre->splits, (int)M, f.saved_mean, f.saved_var, f.run.run_mean, f.run.run_var, consts,
+                f.p.scales, f.p.bias, f.mean_shift);
+        } else {
+            const int splits = chan_splits(c, M);
+            float* part = scratch(SCRATCH_REDUCE, (size_t)c * splits * 2);
+            launch_chan_reduce<2>(StatsF{f.x}, c, hw, M, splits, part);
+            bn_stats_finalize_kernel<<<ceil_div(c, 256), 256, 0, current_stream()>>>(
+                part, c, splits, (int)M, f.saved_mean, f.saved_var, f.run.run_mean, f.run.run_var, consts, f.p.scales, f.p.bias,
+                f.mean_shift);
+        }
         KERNEL_CHECK();
-        a.mean = saved_mean; a.var = saved_var; a.consts = consts;
-    } else if (mode == BCNN_HIP_MODE_TRAIN) {
-        const int splits = chan_splits(c, M);
-        float* part = scratch(SCRATCH_REDUCE, (size_t)c * splits * 2);
-        launch_chan_reduce<2>(StatsF{x}, c, hw, M, splits, part);
-        bn_stats_finalize_kernel<<<ceil_div(c, 256), 256, 0, current_stream()>>>(
-            part, c, splits, (int)M, saved_mean, saved_var, run_mean, run_var, consts, scales, bias, mean_shift);
-        KERNEL_CHECK();
-        a.mean = saved_mean; a.var = saved_var; a.consts = consts;
+        a.mean = f.saved_mean; a.var = f.saved_var; a.consts = consts;
     }
-    if (stats_only) return;  // the consumer normalises on the fly (bcnn_hip_maxpool_forward_bn)
-    auto al16 = [](const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    if (f.stats_only) return;  // the consumer normalises on the fly (bcnn_hip_maxpool_forward_bn)
 #ifdef BCNN_HIP_EXPERIMENT
     static const int skip_fw = getenv("BCNN_HIP_SKIP_SWEEPS") ? atoi(getenv("BCNN_HIP_SKIP_SWEEPS")) : 0;
     if (!(skip_fw & 4))
 #endif
-    launch_chan_map(BnApplyBody{a, al16(x) && al16(y) && al16(a.ws) && al16(a.xn) && al16(a.res)}, n, c, hw);
-    if (want_act != act) bcnn_hip_activation_forward(y, (size_t)total, want_act, nullptr, hw, c);
+    launch_chan_map(BnApplyBody{a, al16(f.x) && al16(f.y) && al16(a.ws) && al16(a.xn) && al16(a.res)}, n, c, hw);
+    if (f.act != act) bcnn_hip_activation_forward(f.y, (size_t)total, f.act, nullptr, hw, c);
 }
 
 }  // namespace bcnn_hip
@@ -476,22 +472,25 @@ using namespace bcnn_hip;
 
 extern "C" {
 
-void bcnn_hip_batchnorm_forward(const float* x, float* y, float* run_mean, float* run_var,
-                                const float* scales, const float* bias, float* saved_mean,
-                                float* saved_var, float* x_norm, float* workspace, int n, int c, int hw,
-                                int mode, int act) {
-    batchnorm_forward_impl(x, y, run_mean, run_var, scales, bias, saved_mean, saved_var, x_norm, workspace, n, c, hw,
-                           mode, act, nullptr, nullptr, false, nullptr);
-}
-
 void bcnn_hip_batchnorm_forward_stats(const float* x, float* y, float* run_mean, float* run_var, const float* scales,
                                       const float* bias, float* saved_mean, float* saved_var, float* x_norm,
                                       float* workspace, int n, int c, int hw, int mode, int act, const float* stats,
                                       int splits) {
     ConvStats st;
     st.partials = const_cast<float*>(stats); st.splits = stats ? splits : 0; st.capacity = 0;
-    batchnorm_forward_impl(x, y, run_mean, run_var, scales, bias, saved_mean, saved_var, x_norm, workspace, n, c, hw,
-                           mode, act, &st, nullptr, false, nullptr);
+    BnFwdCall f{};
+    f.x = x; f.y = y; f.workspace = workspace; f.x_norm = x_norm; f.mode = mode; f.act = act; f.pre = &st;
+    f.e.n = n; f.e.c = c; f.e.hw = hw; f.p.scales = scales; f.p.bias = bias;
+    f.saved_mean = saved_mean; f.saved_var = saved_var; f.run.run_mean = run_mean; f.run.run_var = run_var;
+    batchnorm_forward_impl(f);
+}
+
+void bcnn_hip_batchnorm_forward(const float* x, float* y, float* run_mean, float* run_var,
+                                const float* scales, const float* bias, float* saved_mean,
+                                float* saved_var, float* x_norm, float* workspace, int n, int c, int hw,
+                                int mode, int act) {
+    bcnn_hip_batchnorm_forward_stats(x, y, run_mean, run_var, scales, bias, saved_mean, saved_var, x_norm, workspace, n, c, hw,
+                                     mode, act, /*stats=*/nullptr, /*splits=*/0);
 }
 
 // TRAIN-mode batch statistics (saved and running) WITHOUT the apply sweep: the 1x1 convolution behind the node takes the
@@ -501,8 +500,11 @@ void bcnn_hip_batchnorm_forward_stats_only(const float* x, float* run_mean, floa
                                            const float* stats, int splits) {
     ConvStats st;
     st.partials = const_cast<float*>(stats); st.splits = stats ? splits : 0; st.capacity = 0;
-    batchnorm_forward_impl(x, nullptr, run_mean, run_var, scales, bias, saved_mean, saved_var, nullptr, nullptr, n, c, hw,
-                           BCNN_HIP_MODE_TRAIN, BCNN_HIP_ACT_NONE, &st, nullptr, true, nullptr);
+    BnFwdCall f{};
+    f.x = x; f.mode = BCNN_HIP_MODE_TRAIN; f.act = BCNN_HIP_ACT_NONE; f.pre = &st; f.stats_only = true;
+    f.e.n = n; f.e.c = c; f.e.hw = hw; f.p.scales = scales; f.p.bias = bias;
+    f.saved_mean = saved_mean; f.saved_var = saved_var; f.run.run_mean = run_mean; f.run.run_var = run_var;
+    batchnorm_forward_impl(f);
 }
 
 }  // extern "C"
@@ -510,91 +512,47 @@ void bcnn_hip_batchnorm_forward_stats_only(const float* x, float* run_mean, floa
 namespace bcnn_hip {
 // S1 = sum g', S2 = sum g' (x - mean) per channel -> dbias, dscales, dmean, dvar (the first sweep of the backward pass)
 // (also called by pool.hip: the stem's sums over the pooled tensors)
-void batchnorm_backward_sums(const float* dy, const float* y, int act, const float* scales, float* dscales,
-                             float* dbias, const float* saved_mean, const float* saved_var, float* dmean,
-                             float* dvar, const float* workspace, int n, int c, int hw, const float* fwd_bias,
-                             const float* res, unsigned res_count, float4* consts,
-                             float consts_fM /* divisor of dmean in the table; 0: N * hw */) {
-    const long long M = (long long)n * hw;
+void batchnorm_backward_sums(const BnBwdCall& b) {
+    const int c = b.e.c, hw = b.e.hw;
+    const long long M = (long long)b.e.n * hw;
     const int splits = chan_splits(c, M);
     float* part = scratch(SCRATCH_REDUCE, (size_t)c * splits * 2);
     BwdSumsF f;
-    f.dy = dy; f.y = y; f.x = workspace; f.mean = saved_mean; f.act = act; f.C = c; f.HW = hw;
-    f.fwd_bias = fwd_bias; f.var = saved_var; f.scale = scales; f.res = res; f.res_count = res_count;
+    f.dy = b.dout ? b.dout : b.dy; f.y = b.y; f.x = b.workspace; f.mean = b.s.mean; f.act = b.act; f.C = c; f.HW = hw;
+    f.fwd_bias = b.p.bias; f.var = b.s.var; f.scale = b.p.scales; f.res = b.res; f.res_count = (unsigned)b.res_count;
 #ifdef BCNN_HIP_EXPERIMENT
     // timing experiment (wrong results): what the step gains if the sums of the conv1 batch-norms of the 56 x 56 / 28 x 28 blocks
     // came from the data-gradient kernel behind them instead of this sweep
     static const int skip_exp = getenv("BCNN_HIP_SKIP_C1_SUMS") ? 1 : 0;
     static const int skip_all = getenv("BCNN_HIP_SKIP_SWEEPS") ? atoi(getenv("BCNN_HIP_SKIP_SWEEPS")) : 0;  // 1 sums, 2 bwd apply, 4 fwd apply
     if (!(skip_all & 1))
-    if (!(skip_exp && res == nullptr && act == BCNN_HIP_ACT_RELU && ((hw == 3136 && c == 64) || (hw == 784 && c == 128))))
+    if (!(skip_exp && b.res == nullptr && b.act == BCNN_HIP_ACT_RELU && ((hw == 3136 && c == 64) || (hw == 784 && c == 128))))
 #endif
     launch_chan_reduce<2>(f, c, hw, M, splits, part);
-    bn_bwd_finalize_kernel<<<ceil_div(c, 256), 256, 0, current_stream()>>>(part, c, splits, scales, saved_var,
-                                                                          dbias, dscales, dmean, dvar, consts, saved_mean,
-                                                                          fwd_bias, consts_fM > 0.f ? consts_fM : (float)M);
+    bn_bwd_finalize_kernel<<<ceil_div(c, 256), 256, 0, current_stream()>>>(part, c, splits, b.p.scales, b.s.var, b.g.dbias,
+                                                                          b.g.dscales, b.g.dmean, b.g.dvar, b.consts, b.s.mean,
+                                                                          b.p.bias, b.consts_fM > 0.f ? b.consts_fM : (float)M);
     KERNEL_CHECK();
 }
 
 // dy <- scale * g' / sqrt(var + 1e-5) + dvar * 2 (x - mean) / M + dmean / M, copied to dx (the second sweep)
-static void batchnorm_backward_apply(float* dy, float* dx, const float* y, int act, const float* scales,
-                                     const float* saved_mean, const float* saved_var, const float* dmean,
-                                     const float* dvar, const float* workspace, int n, int c, int hw,
-                                     const float* fwd_bias, int keep_dy = 0, const float* res = nullptr,
-                                     unsigned res_count = 0, const float4* consts = nullptr) {
-    const long long M = (long long)n * hw, total = M * c;
+static void batchnorm_backward_apply(const BnBwdCall& b) {
+    const long long M = (long long)b.e.n * b.e.hw, total = M * b.e.c;
     BnBwdApplyArgs a;
-    a.consts = consts;
+    a.consts = b.consts;
     a.rM = 1.0f / (float)M;  // IEEE, round to nearest: what __fdiv_rn(1.0f, M) gives on the device
-    a.dy = dy; a.dx = (dx && dx != dy) ? dx : nullptr; a.y = y; a.x = workspace;
-    a.mean = saved_mean; a.var = saved_var; a.scale = scales; a.dmean = dmean; a.dvar = dvar;
-    a.C = c; a.HW = hw; a.act = act; a.M = (int)M; a.total = total; a.fwd_bias = fwd_bias;
-    a.keep_dy = keep_dy; a.res = res; a.res_count = res_count;
-    auto al16 = [](const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+    a.dy = b.dout ? const_cast<float*>(b.dout) : b.dy;  // (only read then: keep_dy)
+    a.dx = (b.dx && b.dx != a.dy) ? b.dx : nullptr; a.y = b.y; a.x = b.workspace;
+    a.mean = b.s.mean; a.var = b.s.var; a.scale = b.p.scales; a.dmean = b.g.dmean; a.dvar = b.g.dvar;
+    a.C = b.e.c; a.HW = b.e.hw; a.act = b.act; a.M = (int)M; a.total = total; a.fwd_bias = b.p.bias;
+    a.keep_dy = b.dout != nullptr; a.res = b.res; a.res_count = (unsigned)b.res_count;
 #ifdef BCNN_HIP_EXPERIMENT
     static const int skip_bw = getenv("BCNN_HIP_SKIP_SWEEPS") ? atoi(getenv("BCNN_HIP_SKIP_SWEEPS")) : 0;
     if (skip_bw & 2) return;
 #endif
-    launch_chan_map(BnBwdApplyBody{a, al16(dy) && al16(a.dx) && al16(workspace) && al16(y)}, n, c, hw);
+    launch_chan_map(BnBwdApplyBody{a, al16(a.dy) && al16(a.dx) && al16(b.workspace) && al16(b.y)}, b.e.n, b.e.c, b.e.hw);
 }
 
-// fwd_bias (optional): the bias the forward pass added; with it the forward output is recomputed from the
-// workspace copy of the input instead of read from y (fused activation backward only).
-void batchnorm_backward_impl(float* dy, float* dx, const float* y, int act, const float* scales, float* dscales,
-                             float* dbias, const float* saved_mean, const float* saved_var, float* dmean,
-                             float* dvar, const float* workspace, int n, int c, int hw, const float* fwd_bias) {
-    const long long M = (long long)n * hw, total = M * c;
-    if (!total) return;
-    if (act == BCNN_HIP_ACT_NONE || !act_bwd_is_cheap(act)) fwd_bias = nullptr;
-    // 2 passes over (dy, x[, y]) + write dy
-    KTimer kt(K_BN_BWD, 0.0, 4.0 * ((act != BCNN_HIP_ACT_NONE && !fwd_bias) ? 7.0 : 5.0) * (double)total);
-    if (!act_bwd_is_cheap(act)) {  // softplus: its derivative needs exp() -> separate in-place pass first
-        bcnn_hip_activation_backward(y, dy, (size_t)total, act, nullptr, nullptr, hw, c);
-        act = BCNN_HIP_ACT_NONE;
-    }
-    float4* consts = bn_consts_scratch(c);
-    batchnorm_backward_sums(dy, y, act, scales, dscales, dbias, saved_mean, saved_var, dmean, dvar, workspace, n, c, hw,
-                            fwd_bias, nullptr, 0, consts);
-    batchnorm_backward_apply(dy, dx, y, act, scales, saved_mean, saved_var, dmean, dvar, workspace, n, c, hw, fwd_bias, 0,
-                             nullptr, 0, consts);
-}
-// batchnorm_backward_impl whose sums a producer of dy already left as partials[(channel * splits + i) * 2 + {S1, S2}]
-// (the depthwise kernel that wrote dy: depthwise_lds.hip): finalize + the apply sweep, no read-only sweep
-void batchnorm_backward_presummed(float* dy, const float* y, int act, const float* scales, float* dscales, float* dbias,
-                                  const float* saved_mean, const float* saved_var, float* dmean, float* dvar,
-                                  const float* workspace, int n, int c, int hw, const float* fwd_bias, const float* sums,
-                                  int splits) {
-    const long long M = (long long)n * hw, total = M * c;
-    if (!total) return;
-    if (act == BCNN_HIP_ACT_NONE) fwd_bias = nullptr;
-    KTimer kt(K_BN_BWD, 0.0, 4.0 * ((act != BCNN_HIP_ACT_NONE && !fwd_bias) ? 4.0 : 3.0) * (double)total);
-    float4* consts = bn_consts_scratch(c);
-    bn_bwd_finalize_wide_kernel<<<c, 1024, 0, current_stream()>>>(sums, c, splits, scales, saved_var, dbias, dscales, dmean,
-                                                                  dvar, consts, saved_mean, fwd_bias, (float)M);
-    KERNEL_CHECK();
-    batchnorm_backward_apply(dy, nullptr, y, act, scales, saved_mean, saved_var, dmean, dvar, workspace, n, c, hw, fwd_bias, 0,
-                             nullptr, 0, consts);
-}
 // d(res)[i] += dout[i] * act'(out[i]) for the first `count` elements (the partial operand of the folded eltwise node)
 __global__ __launch_bounds__(256) void bn_residual_grad_kernel(const float* __restrict__ out, const float* __restrict__ dout,
                                                                float* __restrict__ dres, unsigned count, int act) {
@@ -602,28 +560,42 @@ __global__ __launch_bounds__(256) void bn_residual_grad_kernel(const float* __re
         dres[i] += dout[i] * act_bwd_cheap(out[i], act, 0.f);  // `out` is read here only: one image's worth
 }
 
-// Backward of a batch-norm (no activation of its own) whose output went through a folded eltwise node: the incoming
-// gradient is dout * act'(out) (bcnn_eltwise_layer.c:124-127), read from the eltwise node's tensors and NOT rewritten; the
-// gradient w.r.t. the batch-norm input goes to dx. dres (optional) accumulates the partial operand's gradient.
-// The eltwise output needed by act' is RECOMPUTED from x, the forward bias and res (bn_recompute_y: the forward's own
-// operations, bit-identical) instead of read: the two sweeps read (dout, x) like a plain batch-norm backward.
-void batchnorm_backward_residual(const float* dout, const float* out, int act_res, const float* res, float* dres,
-                                 size_t res_count, float* dx, const float* scales, float* dscales, float* dbias,
-                                 const float* fwd_bias, const float* saved_mean, const float* saved_var, float* dmean,
-                                 float* dvar, const float* workspace, int n, int c, int hw) {
-    const long long total = (long long)n * hw * c;
+// The backward pass: the two sweeps (sums, apply) and what the optional members of the call ask for (batchnorm.h).
+// b.sums: the producer of dy left the sums (the depthwise kernel that wrote dy: depthwise_lds.hip; the caller has checked that
+// act' is cheap): finalize + the apply sweep, no read-only sweep.
+// b.dout: the batch-norm (no activation of its own) went through a folded eltwise node. The incoming gradient is dout * act'(out)
+// (bcnn_eltwise_layer.c:124-127), read from the eltwise node's tensors and NOT rewritten. The eltwise output needed by act' is
+// RECOMPUTED from x, the forward bias and res (bn_recompute_y: the forward's own operations, bit-identical) instead of read:
+// the two sweeps read (dout, x) like a plain batch-norm backward.
+void batchnorm_backward_impl(const BnBwdCall& call) {
+    BnBwdCall b = call;
+    const int c = b.e.c, hw = b.e.hw;
+    const long long M = (long long)b.e.n * hw, total = M * c;
     if (!total) return;
-    KTimer kt(K_BN_BWD, 0.0, 4.0 * 5.0 * (double)total);  // (dout, x) twice + dx
-    const unsigned cnt = (unsigned)(res_count < (size_t)total ? res_count : (size_t)total);
-    if (dres && cnt) {
-        bn_residual_grad_kernel<<<stream_grid(cnt, 256), 256, 0, current_stream()>>>(out, dout, dres, cnt, act_res);
-        KERNEL_CHECK();
+    if (!b.dout && (b.act == BCNN_HIP_ACT_NONE || !act_bwd_is_cheap(b.act))) b.p.bias = nullptr;
+    // passes over (dy, x[, y]) + the write of dy: two sweeps, or one behind given sums; folded eltwise: (dout, x) twice + dx
+    const bool reads_y = b.act != BCNN_HIP_ACT_NONE && !b.p.bias;
+    KTimer kt(K_BN_BWD, 0.0, 4.0 * (b.dout ? 5.0 : b.sums ? (reads_y ? 4.0 : 3.0) : (reads_y ? 7.0 : 5.0)) * (double)total);
+    if (b.dout) {
+        b.res_count = b.res_count < (size_t)total ? b.res_count : (size_t)total;
+        if (b.dres && b.res_count) {
+            bn_residual_grad_kernel<<<stream_grid(b.res_count, 256), 256, 0, current_stream()>>>(b.y, b.dout, b.dres,
+                                                                                                 (unsigned)b.res_count, b.act);
+            KERNEL_CHECK();
+        }
+    } else if (!act_bwd_is_cheap(b.act)) {  // softplus: its derivative needs exp() -> separate in-place pass first
+        bcnn_hip_activation_backward(b.y, b.dy, (size_t)total, b.act, nullptr, nullptr, hw, c);
+        b.act = BCNN_HIP_ACT_NONE;
     }
-    float4* consts = bn_consts_scratch(c);
-    batchnorm_backward_sums(dout, out, act_res, scales, dscales, dbias, saved_mean, saved_var, dmean, dvar, workspace, n, c,
-                            hw, fwd_bias, res, cnt, consts);
-    batchnorm_backward_apply(const_cast<float*>(dout), dx, out, act_res, scales, saved_mean, saved_var, dmean, dvar,
-                             workspace, n, c, hw, fwd_bias, /*keep_dy=*/1, res, cnt, consts);
+    b.consts = bn_consts_scratch(c);
+    if (b.sums) {
+        bn_bwd_finalize_wide_kernel<<<c, 1024, 0, current_stream()>>>(b.sums, c, b.splits, b.p.scales, b.s.var, b.g.dbias, b.g.dscales,
+                                                                      b.g.dmean, b.g.dvar, b.consts, b.s.mean, b.p.bias, (float)M);
+        KERNEL_CHECK();
+    } else {
+        batchnorm_backward_sums(b);
+    }
+    batchnorm_backward_apply(b);
 }
 
 }  // namespace bcnn_hip
@@ -638,7 +610,6 @@ void bcnn_hip_batchnorm_apply(const float* x, float* y, const float* scales, con
     a.x = x; a.y = y; a.ws = nullptr; a.xn = nullptr; a.scale = scales; a.bias = bias; a.mean = saved_mean; a.var = saved_var;
     a.C = c; a.HW = hw; a.act = act_is_cheap(act) ? act : BCNN_HIP_ACT_NONE; a.total = total; a.predict = 0;
     a.res = nullptr; a.res_count = 0; a.act2 = BCNN_HIP_ACT_NONE; a.consts = nullptr;
-    auto al16 = [](const void* p) { return p == nullptr || (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     launch_chan_map(BnApplyBody{a, al16(x) && al16(y)}, n, c, hw);
     if (a.act != act) bcnn_hip_activation_forward(y, (size_t)total, act, nullptr, hw, c);
 }
@@ -657,16 +628,22 @@ void bcnn_hip_batchnorm_backward_sums(const float* dy, const float* scales, floa
     const long long total = (long long)n * hw * c;
     if (!total) return;
     KTimer kt(K_BN_BWD, 0.0, 4.0 * 2.0 * (double)total);  // one pass over (dy, x)
-    batchnorm_backward_sums(dy, nullptr, BCNN_HIP_ACT_NONE, scales, dscales, dbias, saved_mean, saved_var, dmean, dvar, x,
-                            n, c, hw, nullptr);
+    BnBwdCall b{};
+    b.dout = dy; b.workspace = x; b.act = BCNN_HIP_ACT_NONE; b.e.n = n; b.e.c = c; b.e.hw = hw;
+    b.p.scales = scales; b.s.mean = saved_mean; b.s.var = saved_var;
+    b.g.dscales = dscales; b.g.dbias = dbias; b.g.dmean = dmean; b.g.dvar = dvar;
+    batchnorm_backward_sums(b);
 }
 
 void bcnn_hip_batchnorm_backward_apply(float* dy, float* dx, const float* scales, const float* saved_mean,
                                        const float* saved_var, const float* dmean, const float* dvar, const float* x,
                                        int n, int c, int hw) {
     if (!(long long)n * hw * c) return;
-    batchnorm_backward_apply(dy, dx, nullptr, BCNN_HIP_ACT_NONE, scales, saved_mean, saved_var, dmean, dvar, x, n, c, hw,
-                             nullptr);
+    BnBwdCall b{};
+    b.dy = dy; b.dx = dx; b.workspace = x; b.act = BCNN_HIP_ACT_NONE; b.e.n = n; b.e.c = c; b.e.hw = hw;
+    b.p.scales = scales; b.s.mean = saved_mean; b.s.var = saved_var;
+    b.g.dmean = const_cast<float*>(dmean); b.g.dvar = const_cast<float*>(dvar);  // only read by the apply sweep
+    batchnorm_backward_apply(b);
 }
 
 void bcnn_hip_batchnorm_backward(float* dy, float* dx, const float* y, int act, const float* scales,
@@ -674,8 +651,11 @@ void bcnn_hip_batchnorm_backward(float* dy, float* dx, const float* y, int act, 
                                  const float* saved_var, float* dmean, float* dvar, const float* x_norm,
                                  const float* workspace, int n, int c, int hw) {
     (void)x_norm;  // recomputed from workspace/mean/var: saves a full-tensor read (and its write in forward)
-    batchnorm_backward_impl(dy, dx, y, act, scales, dscales, dbias, saved_mean, saved_var, dmean, dvar, workspace, n,
-                            c, hw, nullptr);
+    BnBwdCall b{};
+    b.dy = dy; b.dx = dx; b.y = y; b.workspace = workspace; b.act = act; b.e.n = n; b.e.c = c; b.e.hw = hw;
+    b.p.scales = scales; b.s.mean = saved_mean; b.s.var = saved_var;
+    b.g.dscales = dscales; b.g.dbias = dbias; b.g.dmean = dmean; b.g.dvar = dvar;
+    batchnorm_backward_impl(b);
 }
 
 }  // extern "C"

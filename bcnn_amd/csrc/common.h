@@ -95,6 +95,8 @@ constexpr int kCUs = 256;      // MI355X
 constexpr int kXCDs = 8;
 
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
+// what a float4 access needs of a pointer; an absent (null) optional tensor passes
+inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 #ifndef STREAM_GRID_PER_CU
 #define STREAM_GRID_PER_CU 8

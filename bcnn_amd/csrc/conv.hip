@@ -1,6 +1,9 @@
 // conv.hip -- C-ABI entry points of the convolution node (include/bcnn_hip.h), composing the
 // implicit-GEMM kernels (conv_fwd.hip, conv_bwd.hip) with the batch-norm / activation kernels the way
 // bcnn_forward_conv_layer_cpu / bcnn_backward_conv_layer_cpu do (reference bcnn_conv_layer.c:367-587).
+// Each entry point writes what it was given into a ConvNodeFwd / ConvNodeBwd by name and hands it to conv_forward_impl /
+// conv_backward_impl. The calling thread's pending batch-norm fold and its side-stream mode enter there, at the ABI boundary,
+// and nothing below reads them again (conv_side_stream_deferred, which the weight-gradient kernels ask, apart).
 #include "batchnorm.h"
 #include "conv_paths.h"
 #include <algorithm>
@@ -219,12 +222,11 @@ static ConvPack conv_planned_pack(const ConvFamily<Call> (&rows)[R], const ConvS
 }
 
 // bf16: the caller asked for the reduced-precision forward (bcnn_hip_conv_forward_bf16)
-static void conv_fwd_any(const float* x, const float* w, const float* bias, const float* slopes, float* y,
-                         const ConvShape& s, int act, int raw, ConvStats* stats = nullptr, bool bf16 = false) {
-    if (stats) stats->splits = 0;
-    if (s.total_q <= 0 || s.Mg == 0) return;
-    if (bf16) conv_forward_bf16(x, w, bias, slopes, y, s, act, raw, stats);
-    else conv_run_first(kConvFwdFamilies, ConvFwdCall{x, w, bias, slopes, y, s, act, raw, stats}, raw);
+static void conv_fwd_any(const ConvFwdCall& c, bool bf16) {
+    if (c.stats) c.stats->splits = 0;
+    if (c.s.total_q <= 0 || c.s.Mg == 0) return;
+    if (bf16) conv_forward_bf16(c.x, c.w, c.bias, c.slopes, c.y, c.s, c.act, c.raw, c.stats);
+    else conv_run_first(kConvFwdFamilies, c, c.raw);
 }
 
 static void conv_dx_any(const float* w, const float* dy, float* dx, const ConvShape& s, DxBnSums* bs) {
@@ -251,6 +253,184 @@ static const DwFamily kDwFamilies[] = {
     {conv_dw_large_workspace_floats, conv_backward_weights_large, GATE_NONE},
     {conv_dw_workspace_floats, conv_backward_weights, GATE_NONE},  // takes every shape
 };
+
+// ---- the convolution node: convolution [+ batch-norm] + activation, with the fusions a caller can ask for ------------------
+// One description per direction. The entry points of the ABI (below) fill it by name, what is absent stays zero. The two pieces
+// of per-thread state that gate a fusion are read there, once per call, and travel in it: `fold` (take_fold) and `side_mode`.
+// p.bias / g.dbias are the node's: the convolution's own without batch_norm. bn_workspace: the pre-normalisation values.
+// res != NULL (batch_norm, TRAIN mode, cheap activations -- bcnn_hip_conv_residual_fusable): the following eltwise node
+// is folded into the batch-norm apply pass, whose result goes to res_out; y is not written
+// stats_only: stop behind the batch statistics; bf16: the convolution itself on the bf16 matrix cores (conv_bf16.hip)
+struct ConvNodeFwd {
+    const float *x, *w, *slopes;
+    float *y, *saved_mean, *saved_var, *bn_workspace, *res_out;
+    ConvShape s;
+    int act, batch_norm, mode;
+    BnParams p;
+    BnRunning run;
+    const BnResidual* res;
+    bool stats_only, bf16;
+    BnFold fold;  // announced by bcnn_hip_conv_set_input_bnfold: x then is the batch-norm's INPUT
+};
+struct ConvResidualBwd {
+    const float* out;   // the folded eltwise node's output
+    const float* dout;  // and its gradient (read only)
+    const float* res;   // the eltwise node's second operand
+    float* dres;        // and its gradient (accumulated), may be NULL
+    size_t res_count;
+    int act;
+};
+// workspace: split partials of the weight gradient (bcnn_hip_conv_workspace_size floats). rb: the eltwise node folded into the
+// forward pass; bs: the data-gradient kernel also emits the sums of the batch-norm node in front; own_sums: whoever wrote dy
+// left this node's batch-norm sums, own_splits per channel; bn_done: dy already is the gradient of the pre-normalisation output
+struct ConvNodeBwd {
+    const float *x, *w, *y, *slopes, *bn_workspace, *own_sums;
+    float *dy, *dx, *dw, *dslopes, *workspace;
+    size_t workspace_elems;
+    ConvShape s;
+    int act, batch_norm, own_splits, side_mode;  // side_mode: g_side_mode's values
+    BnParams p;  // p.bias lets the batch-norm backward recompute the forward output from bn_workspace (no read of y)
+    BnSaved saved;
+    BnGrads g;
+    const ConvResidualBwd* rb;
+    DxBnSums* bs;
+    bool bn_done;
+    BnFold fold;  // x then is the INPUT of the batch-norm in front: d/dW of W diag(a) is (dy x^T) diag(a)
+};
+
+static void conv_forward_impl(const ConvNodeFwd& nd) {
+    const ConvShape& s = nd.s;
+    const BnFold& fold = nd.fold;
+    const int n = s.N, f = s.F, act = nd.act, mode = nd.mode;
+    if (fold.mean && (!nd.batch_norm || mode != BCNN_HIP_MODE_TRAIN || !bnfold_shape_ok(s))) {
+        fprintf(stderr, "[bcnn_hip] conv forward: a batch-norm fold was announced for a layer that cannot take it (ask "
+                        "bcnn_hip_conv_bnfold_fusable)\n");
+        exit(1);
+    }
+    if (!nd.batch_norm) {
+        // tanh / softplus / logistic: bias in the epilogue, activation as a second in-place pass
+        const int fused_act = act_is_cheap(act) ? act : BCNN_HIP_ACT_NONE;
+        conv_fwd_any(ConvFwdCall{nd.x, nd.w, nd.p.bias, nd.slopes, nd.y, s, fused_act, /*raw=*/0, nullptr}, nd.bf16);
+        if (fused_act != act) bcnn_hip_activation_forward(nd.y, (size_t)n * f * s.OHOW, act, nd.slopes, s.OHOW, f);
+        return;
+    }
+    // conv -> (pre-normalisation values, kept for backward) -> statistics -> normalise+scale+bias+act
+    float* raw = (nd.bn_workspace && mode != BCNN_HIP_MODE_PREDICT) ? nd.bn_workspace : nd.y;
+    // TRAIN: the convolution epilogue also emits the per-channel sum / sum of squares of what it stores
+    ConvStats st;
+    st.partials = nullptr; st.splits = 0; st.capacity = 0;
+    static const int fuse_stats = BCNN_EXP_ENV("BCNN_HIP_NO_FUSED_STATS") ? 0 : 1;  // A/B switch for profiling
+    if (fuse_stats && mode == BCNN_HIP_MODE_TRAIN && s.total_q < 0x7fffffffLL) {
+        // slots per channel: one per 64 output pixels on the GEMM paths; the fused Winograd kernel writes two per block
+        // of 64 2x2 tiles, which is MORE than that when a tile covers fewer than two real pixels (H == 1 or W == 1)
+        const long long tiles = (long long)n * ((s.OH + 1) / 2) * ((s.OW + 1) / 2);
+        const long long slots_gemm = ceil_div(s.total_q, 64), slots_wino = 2 * ceil_div(tiles, 64);
+        st.capacity = (size_t)f * (size_t)(slots_gemm > slots_wino ? slots_gemm : slots_wino) * 2;
+        st.partials = scratch(SCRATCH_REDUCE, st.capacity);
+    }
+    BnFwdCall b{};
+    b.x = raw; b.y = nd.res ? nd.res_out : nd.y; b.workspace = raw; b.e.n = n; b.e.c = f; b.e.hw = s.OHOW; b.mode = mode;
+    b.act = (act == BCNN_HIP_ACT_PRELU) ? BCNN_HIP_ACT_NONE : act; b.pre = &st; b.res = nd.res; b.stats_only = nd.stats_only;
+    b.p = nd.p; b.saved_mean = nd.saved_mean; b.saved_var = nd.saved_var; b.run = nd.run;
+    ConvStats* stp = st.partials ? &st : nullptr;
+    if (fold.mean) {
+        // W z = (W diag(a)) y + W b: the GEMM reads y with column-scaled weights (packed here: a depends on this batch). The
+        // constant W b is left out of the stored pre-normalisation values -- the batch-norm behind subtracts the batch mean,
+        // so every later use (apply, backward, the consumers that normalise on the fly) sees raw - mean either way -- and
+        // is added where it is visible: the running mean.
+        trace_kernel("bnfold:fwd");
+        b.mean_shift = fold_rowconst(fold, nd.w, s.C, f);
+        KTimer kt(K_CONV_FWD, conv_gemm_flops(s), conv_gemm_bytes(s));
+        if (!conv_forward_dma(nd.x, nd.w, nullptr, nullptr, raw, s, BCNN_HIP_ACT_NONE, /*raw=*/1, stp, &fold)) {
+            fprintf(stderr, "[bcnn_hip] conv forward: the LDS-DMA GEMM refused a folded layer\n");
+            exit(1);
+        }
+    } else {
+        conv_fwd_any(ConvFwdCall{nd.x, nd.w, nullptr, nullptr, raw, s, BCNN_HIP_ACT_NONE, /*raw=*/1, stp}, nd.bf16);
+    }
+    batchnorm_forward_impl(b);
+    if (nd.stats_only) return;
+    if (act == BCNN_HIP_ACT_PRELU) bcnn_hip_activation_forward(nd.y, (size_t)n * f * s.OHOW, act, nd.slopes, s.OHOW, f);
+}
+
+static void conv_backward_impl(const ConvNodeBwd& nd) {
+    const ConvShape& s = nd.s;
+    const BnFold& fold = nd.fold;
+    const int n = s.N, f = s.F, act = nd.act, batch_norm = nd.batch_norm;
+    const size_t ysize = (size_t)n * f * s.OHOW;
+    if (fold.mean && (!batch_norm || !bnfold_shape_ok(s))) {
+        fprintf(stderr, "[bcnn_hip] conv backward: a batch-norm fold was announced for a layer that cannot take it\n");
+        exit(1);
+    }
+    BnBwdCall b{};
+    b.dy = nd.dy; b.y = nd.y; b.workspace = nd.bn_workspace; b.act = act; b.p = nd.p; b.s = nd.saved; b.g = nd.g;
+    b.e.n = n; b.e.c = f; b.e.hw = s.OHOW;
+    if (nd.rb) {
+        // dy <- batch-norm backward of dout * act'(out): the eltwise node's backward and this node's batch-norm backward
+        // in the two sweeps the latter takes alone
+        b.dy = nullptr; b.dout = nd.rb->dout; b.dx = nd.dy; b.y = nd.rb->out; b.act = nd.rb->act;
+        b.res = nd.rb->res; b.dres = nd.rb->dres; b.res_count = nd.rb->res_count;
+        batchnorm_backward_impl(b);
+    } else if (batch_norm && nd.bn_done) {
+        // dy already is the gradient of the pre-normalisation output (bcnn_hip_maxpool_bn_backward wrote it)
+    } else if (batch_norm) {
+        if (act == BCNN_HIP_ACT_PRELU) {
+            bcnn_hip_activation_backward(nd.y, nd.dy, ysize, act, nd.slopes, nd.dslopes, s.OHOW, f);
+            b.act = BCNN_HIP_ACT_NONE;
+        }
+        if (nd.own_sums && nd.own_splits > 0 && b.act == act && act_bwd_is_cheap(act)) {  // whoever wrote dy left the sums
+            b.sums = nd.own_sums; b.splits = nd.own_splits;
+        }
+        batchnorm_backward_impl(b);
+    } else {
+        bcnn_hip_activation_backward(nd.y, nd.dy, ysize, act, nd.slopes, nd.dslopes, s.OHOW, f);
+    }
+    // dW and dX only share their input dy, so the weight gradient CAN run on a private side stream to fill the
+    // CUs the other kernel leaves idle in its last round (the side stream joins the caller's stream before
+    // this function returns). Measured on ResNet-18 N=128 it is 1.7 % SLOWER than running them back to back
+    // (18.15 vs 17.86 ms/step): both GEMMs are MFMA-bound and evict each other's L2 working set. Kept as an
+    // opt-in experiment (BCNN_HIP_SIDE_STREAM=1), off by default.
+    // deferred mode: EVERY weight gradient (the per-net workspace of split partials then belongs to the side stream alone)
+    SideStream* side = (nd.side_mode == 2 || (nd.side_mode == 1 && nd.dx)) ? side_stream() : nullptr;
+    hipStream_t main_stream = current_stream();
+    if (side) {
+        HIP_CHECK(hipEventRecord(side->ready, main_stream));
+        HIP_CHECK(hipStreamWaitEvent(side->stream, side->ready, 0));
+        set_current_stream(side->stream);
+    }
+    bool bias_done = false;
+    if (fold.mean) {
+        // (the term b (x) sum_q dy of the exact derivative is left out: dy here is the gradient of a batch-norm's input, whose
+        // sum over the batch is zero up to rounding -- in the reference too, where it multiplies the same b)
+        trace_kernel("bnfold:dw");
+        KTimer kt(K_CONV_DW, conv_gemm_flops(s), conv_gemm_bytes(s));
+        if (!conv_backward_weights_dma(nd.x, nd.dy, nd.dw, s, nd.workspace, nd.workspace_elems, &fold)) {
+            fprintf(stderr, "[bcnn_hip] conv backward: the LDS-DMA weight-gradient kernel refused a folded layer\n");
+            exit(1);
+        }
+    } else {
+        for (const DwFamily& fam : kDwFamilies)
+            if (gate_open(fam.gate) && fam.run(nd.x, nd.dy, nd.dw, batch_norm ? nullptr : nd.g.dbias, s, nd.workspace,
+                                               nd.workspace_elems, &bias_done))
+                break;
+    }
+    if (side) {
+        HIP_CHECK(hipEventRecord(side->done, side->stream));
+        set_current_stream(main_stream);
+    }
+    if (!batch_norm && !bias_done) bcnn_hip_grad_bias(nd.g.dbias, nd.dy, n, f, s.OHOW);  // uses the shared reduce scratch
+    if (nd.dx) conv_dx_any(nd.w, nd.dy, nd.dx, s, nd.bs);
+    else if (nd.bs) nd.bs->splits = 0;
+    if (side) {
+        if (nd.side_mode == 2) side->pending = true;
+        else HIP_CHECK(hipStreamWaitEvent(main_stream, side->done, 0));
+    }
+}
+// the weight gradients' stream mode of a call: the calling thread's, or the experiment build's BCNN_HIP_SIDE_STREAM=1
+static int side_mode_now() {
+    static const int side_env = BCNN_EXP_ENV("BCNN_HIP_SIDE_STREAM") ? 1 : 0;
+    return g_side_mode ? g_side_mode : side_env;
+}
 }  // namespace bcnn_hip
 
 using namespace bcnn_hip;
@@ -322,71 +502,6 @@ size_t bcnn_hip_conv_workspace_size(int n, int c, int h, int w, int f, int k, in
     return m;
 }
 
-// res != NULL (batch_norm, TRAIN mode, cheap activations -- bcnn_hip_conv_residual_fusable): the following eltwise node
-// is folded into the batch-norm apply pass, whose result goes to res_out; y is not written
-static void conv_forward_impl(const float* x, const float* w, const float* bias, float* y, int n, int c, int h,
-                              int wd, int f, int k, int stride, int pad, int groups, int act, const float* slopes,
-                              int batch_norm, float* run_mean, float* run_var, const float* scales,
-                              float* saved_mean, float* saved_var, float* x_norm, float* bn_workspace, int mode,
-                              const BnResidual* res, float* res_out, bool stats_only = false, bool bf16 = false) {
-    const ConvShape s = make_conv_shape(n, c, h, wd, f, k, stride, pad, groups);
-    const BnFold fold = take_fold();  // announced by bcnn_hip_conv_set_input_bnfold: x then is the batch-norm's INPUT
-    if (fold.mean && (!batch_norm || mode != BCNN_HIP_MODE_TRAIN || !bnfold_shape_ok(s))) {
-        fprintf(stderr, "[bcnn_hip] conv forward: a batch-norm fold was announced for a layer that cannot take it (ask "
-                        "bcnn_hip_conv_bnfold_fusable)\n");
-        exit(1);
-    }
-    if (!batch_norm) {
-        if (act_is_cheap(act)) {
-            conv_fwd_any(x, w, bias, slopes, y, s, act, /*raw=*/0, nullptr, bf16);
-        } else {  // tanh / softplus / logistic: bias in the epilogue, activation as a second in-place pass
-            conv_fwd_any(x, w, bias, slopes, y, s, BCNN_HIP_ACT_NONE, /*raw=*/0, nullptr, bf16);
-            bcnn_hip_activation_forward(y, (size_t)n * f * s.OHOW, act, slopes, s.OHOW, f);
-        }
-        return;
-    }
-    // conv -> (pre-normalisation values, kept for backward) -> statistics -> normalise+scale+bias+act
-    float* raw = (bn_workspace && mode != BCNN_HIP_MODE_PREDICT) ? bn_workspace : y;
-    // TRAIN: the convolution epilogue also emits the per-channel sum / sum of squares of what it stores
-    ConvStats st;
-    st.partials = nullptr; st.splits = 0; st.capacity = 0;
-    static const int fuse_stats = BCNN_EXP_ENV("BCNN_HIP_NO_FUSED_STATS") ? 0 : 1;  // A/B switch for profiling
-    if (fuse_stats && mode == BCNN_HIP_MODE_TRAIN && s.total_q < 0x7fffffffLL) {
-        // slots per channel: one per 64 output pixels on the GEMM paths; the fused Winograd kernel writes two per block
-        // of 64 2x2 tiles, which is MORE than that when a tile covers fewer than two real pixels (H == 1 or W == 1)
-        const long long tiles = (long long)n * ((s.OH + 1) / 2) * ((s.OW + 1) / 2);
-        const long long slots_gemm = ceil_div(s.total_q, 64), slots_wino = 2 * ceil_div(tiles, 64);
-        st.capacity = (size_t)f * (size_t)(slots_gemm > slots_wino ? slots_gemm : slots_wino) * 2;
-        st.partials = scratch(SCRATCH_REDUCE, st.capacity);
-    }
-    const float* mean_shift = nullptr;
-    if (fold.mean) {
-        // W z = (W diag(a)) y + W b: the GEMM reads y with column-scaled weights (packed here: a depends on this batch). The
-        // constant W b is left out of the stored pre-normalisation values -- the batch-norm behind subtracts the batch mean,
-        // so every later use (apply, backward, the consumers that normalise on the fly) sees raw - mean either way -- and
-        // is added where it is visible: the running mean.
-        trace_kernel("bnfold:fwd");
-        mean_shift = fold_rowconst(fold, w, c, f);
-        KTimer kt(K_CONV_FWD, conv_gemm_flops(s), conv_gemm_bytes(s));
-        ConvStats* stp = st.partials ? &st : nullptr;
-        if (!conv_forward_dma(x, w, nullptr, nullptr, raw, s, BCNN_HIP_ACT_NONE, /*raw=*/1, stp, &fold)) {
-            fprintf(stderr, "[bcnn_hip] conv forward: the LDS-DMA GEMM refused a folded layer\n");
-            exit(1);
-        }
-    } else {
-        conv_fwd_any(x, w, nullptr, nullptr, raw, s, BCNN_HIP_ACT_NONE, /*raw=*/1, st.partials ? &st : nullptr, bf16);
-    }
-    const int fused_act = (act == BCNN_HIP_ACT_PRELU) ? BCNN_HIP_ACT_NONE : act;
-    // x_norm is not materialised on this path: the backward pass recomputes it from the raw convolution
-    // output kept in bn_workspace (a full-tensor write and read less per layer and step).
-    (void)x_norm;
-    batchnorm_forward_impl(raw, res ? res_out : y, run_mean, run_var, scales, bias, saved_mean, saved_var, nullptr, raw, n, f,
-                           s.OHOW, mode, fused_act, &st, res, stats_only, mean_shift);
-    if (stats_only) return;
-    if (act == BCNN_HIP_ACT_PRELU)
-        bcnn_hip_activation_forward(y, (size_t)n * f * s.OHOW, act, slopes, s.OHOW, f);
-}
-
 int bcnn_hip_conv_bnfold_fusable(int n, int c, int h, int wd, int f) {
     if (n <= 0 || c <= 0 || h <= 0 || wd <= 0 || f <= 0) return 0;
     return bnfold_shape_ok(make_conv_shape(n, c, h, wd, f, 1, 1, 0, 1)) ? 1 : 0;
@@ -396,12 +511,18 @@ void bcnn_hip_conv_set_input_bnfold(const float* mean, const float* var, const f
     g_fold_pending = BnFold{mean, var, scales, bias};
 }
 
+// (x_norm, here and in the backward entry points, is not materialised: the backward pass recomputes it from the raw convolution
+// output kept in bn_workspace -- a full-tensor write and read less per layer and step)
 void bcnn_hip_conv_forward(const float* x, const float* w, const float* bias, float* y, int n, int c, int h,
                            int wd, int f, int k, int stride, int pad, int groups, int act, const float* slopes,
                            int batch_norm, float* run_mean, float* run_var, const float* scales,
                            float* saved_mean, float* saved_var, float* x_norm, float* bn_workspace, int mode) {
-    conv_forward_impl(x, w, bias, y, n, c, h, wd, f, k, stride, pad, groups, act, slopes, batch_norm, run_mean, run_var,
-                      scales, saved_mean, saved_var, x_norm, bn_workspace, mode, nullptr, nullptr);
+    ConvNodeFwd nd{};
+    nd.s = make_conv_shape(n, c, h, wd, f, k, stride, pad, groups); nd.fold = take_fold();
+    nd.x = x; nd.w = w; nd.y = y; nd.act = act; nd.slopes = slopes; nd.batch_norm = batch_norm; nd.mode = mode;
+    nd.p.scales = scales; nd.p.bias = bias; nd.saved_mean = saved_mean; nd.saved_var = saved_var;
+    nd.run.run_mean = run_mean; nd.run.run_var = run_var; nd.bn_workspace = bn_workspace;
+    conv_forward_impl(nd);
 }
 
 // bcnn_hip_conv_forward with the convolution itself on the bf16 matrix cores (conv_bf16.hip); everything behind the
@@ -411,9 +532,12 @@ int bcnn_hip_conv_forward_bf16(const float* x, const float* w, const float* bias
                                int batch_norm, float* run_mean, float* run_var, const float* scales,
                                float* saved_mean, float* saved_var, float* x_norm, float* bn_workspace, int mode) {
     if (mode != BCNN_HIP_MODE_PREDICT && mode != BCNN_HIP_MODE_VALID) return 0;
-    conv_forward_impl(x, w, bias, y, n, c, h, wd, f, k, stride, pad, groups, act, slopes, batch_norm, run_mean, run_var,
-                      scales, saved_mean, saved_var, x_norm, bn_workspace, mode, nullptr, nullptr, /*stats_only=*/false,
-                      /*bf16=*/true);
+    ConvNodeFwd nd{};
+    nd.s = make_conv_shape(n, c, h, wd, f, k, stride, pad, groups); nd.fold = take_fold(); nd.bf16 = true;
+    nd.x = x; nd.w = w; nd.y = y; nd.act = act; nd.slopes = slopes; nd.batch_norm = batch_norm; nd.mode = mode;
+    nd.p.scales = scales; nd.p.bias = bias; nd.saved_mean = saved_mean; nd.saved_var = saved_var;
+    nd.run.run_mean = run_mean; nd.run.run_var = run_var; nd.bn_workspace = bn_workspace;
+    conv_forward_impl(nd);
     return 1;
 }
 
@@ -422,14 +546,16 @@ int bcnn_hip_conv_forward_bf16(const float* x, const float* w, const float* bias
 void bcnn_hip_conv_forward_stats_only(const float* x, const float* w, const float* bias, int n, int c, int h, int wd, int f,
                                       int k, int stride, int pad, int groups, float* run_mean, float* run_var,
                                       const float* scales, float* saved_mean, float* saved_var, float* bn_workspace) {
-    conv_forward_impl(x, w, bias, /*y=*/nullptr, n, c, h, wd, f, k, stride, pad, groups, BCNN_HIP_ACT_NONE, nullptr, 1,
-                      run_mean, run_var, scales, saved_mean, saved_var, nullptr, bn_workspace, BCNN_HIP_MODE_TRAIN, nullptr,
-                      nullptr, /*stats_only=*/true);
+    ConvNodeFwd nd{};
+    nd.s = make_conv_shape(n, c, h, wd, f, k, stride, pad, groups); nd.fold = take_fold(); nd.stats_only = true;
+    nd.x = x; nd.w = w; nd.act = BCNN_HIP_ACT_NONE; nd.batch_norm = 1; nd.mode = BCNN_HIP_MODE_TRAIN;
+    nd.p.scales = scales; nd.p.bias = bias; nd.saved_mean = saved_mean; nd.saved_var = saved_var;
+    nd.run.run_mean = run_mean; nd.run.run_var = run_var; nd.bn_workspace = bn_workspace;
+    conv_forward_impl(nd);
 }
 
 int bcnn_hip_conv_residual_fusable(int batch_norm, int act, int res_act, int mode, const float* bn_workspace,
                                    const float* res, const float* res_out) {
-    auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
     return batch_norm && mode == BCNN_HIP_MODE_TRAIN && bn_workspace && act == BCNN_HIP_ACT_NONE && act_is_cheap(res_act) &&
            act_bwd_is_cheap(res_act) && res_act != BCNN_HIP_ACT_PRELU && al16(res) && al16(res_out) && al16(bn_workspace);
 }
@@ -439,100 +565,12 @@ void bcnn_hip_conv_forward_residual(const float* x, const float* w, const float*
                                     const float* scales, float* saved_mean, float* saved_var, float* bn_workspace,
                                     const float* res, size_t res_count, int res_act, float* res_out) {
     BnResidual r{res, res_count, res_act};
-    conv_forward_impl(x, w, bias, /*y=*/nullptr, n, c, h, wd, f, k, stride, pad, groups, BCNN_HIP_ACT_NONE, nullptr, 1,
-                      run_mean, run_var, scales, saved_mean, saved_var, nullptr, bn_workspace, BCNN_HIP_MODE_TRAIN, &r,
-                      res_out);
-}
-
-struct ConvResidualBwd {
-    const float* out;   // the folded eltwise node's output
-    const float* dout;  // and its gradient (read only)
-    const float* res;   // the eltwise node's second operand
-    float* dres;        // and its gradient (accumulated), may be NULL
-    size_t res_count;
-    int act;
-};
-static void conv_backward_impl(const float* x, const float* w, const float* bias, const float* y, float* dy, float* dx,
-                               float* dw, float* dbias, int n, int c, int h, int wd, int f, int k, int stride, int pad,
-                               int groups, int act, const float* slopes, float* dslopes, int batch_norm,
-                               const float* scales, float* dscales, const float* saved_mean,
-                               const float* saved_var, float* dmean, float* dvar, const float* x_norm,
-                               const float* bn_workspace, float* workspace, size_t workspace_elems,
-                               const ConvResidualBwd* rb, DxBnSums* bs = nullptr, const float* own_sums = nullptr,
-                               int own_splits = 0, bool bn_done = false) {
-    const ConvShape s = make_conv_shape(n, c, h, wd, f, k, stride, pad, groups);
-    const size_t ysize = (size_t)n * f * s.OHOW;
-    const BnFold fold = take_fold();  // x then is the INPUT of the batch-norm in front: d/dW of W diag(a) is (dy x^T) diag(a)
-    if (fold.mean && (!batch_norm || !bnfold_shape_ok(s))) {
-        fprintf(stderr, "[bcnn_hip] conv backward: a batch-norm fold was announced for a layer that cannot take it\n");
-        exit(1);
-    }
-    if (rb) {
-        // dy <- batch-norm backward of dout * act'(out): the eltwise node's backward and this node's batch-norm backward
-        // in the two sweeps the latter takes alone
-        batchnorm_backward_residual(rb->dout, rb->out, rb->act, rb->res, rb->dres, rb->res_count, dy, scales, dscales, dbias,
-                                    bias, saved_mean, saved_var, dmean, dvar, bn_workspace, n, f, s.OHOW);
-    } else if (batch_norm && bn_done) {
-        // dy already is the gradient of the pre-normalisation output (bcnn_hip_maxpool_bn_backward wrote it)
-    } else if (batch_norm) {
-        int fused_act = act;
-        if (act == BCNN_HIP_ACT_PRELU) {
-            bcnn_hip_activation_backward(y, dy, ysize, act, slopes, dslopes, s.OHOW, f);
-            fused_act = BCNN_HIP_ACT_NONE;
-        }
-        // `bias` lets the batch-norm backward recompute the forward output from bn_workspace (no read of y)
-        (void)x_norm;
-        if (own_sums && own_splits > 0 && fused_act == act && act_bwd_is_cheap(act))  // whoever wrote dy left the sums
-            batchnorm_backward_presummed(dy, y, act, scales, dscales, dbias, saved_mean, saved_var, dmean, dvar, bn_workspace, n,
-                                         f, s.OHOW, bias, own_sums, own_splits);
-        else
-            batchnorm_backward_impl(dy, nullptr, y, fused_act, scales, dscales, dbias, saved_mean, saved_var, dmean, dvar,
-                                    bn_workspace, n, f, s.OHOW, bias);
-    } else {
-        bcnn_hip_activation_backward(y, dy, ysize, act, slopes, dslopes, s.OHOW, f);
-    }
-    // dW and dX only share their input dy, so the weight gradient CAN run on a private side stream to fill the
-    // CUs the other kernel leaves idle in its last round (the side stream joins the caller's stream before
-    // this function returns). Measured on ResNet-18 N=128 it is 1.7 % SLOWER than running them back to back
-    // (18.15 vs 17.86 ms/step): both GEMMs are MFMA-bound and evict each other's L2 working set. Kept as an
-    // opt-in experiment (BCNN_HIP_SIDE_STREAM=1), off by default.
-    static const int side_env = BCNN_EXP_ENV("BCNN_HIP_SIDE_STREAM") ? 1 : 0;
-    const int side_mode = g_side_mode ? g_side_mode : side_env;
-    // deferred mode: EVERY weight gradient (the per-net workspace of split partials then belongs to the side stream alone)
-    SideStream* side = (side_mode == 2 || (side_mode == 1 && dx)) ? side_stream() : nullptr;
-    hipStream_t main_stream = current_stream();
-    if (side) {
-        HIP_CHECK(hipEventRecord(side->ready, main_stream));
-        HIP_CHECK(hipStreamWaitEvent(side->stream, side->ready, 0));
-        set_current_stream(side->stream);
-    }
-    bool bias_done = false;
-    if (fold.mean) {
-        // (the term b (x) sum_q dy of the exact derivative is left out: dy here is the gradient of a batch-norm's input, whose
-        // sum over the batch is zero up to rounding -- in the reference too, where it multiplies the same b)
-        trace_kernel("bnfold:dw");
-        KTimer kt(K_CONV_DW, conv_gemm_flops(s), conv_gemm_bytes(s));
-        if (!conv_backward_weights_dma(x, dy, dw, s, workspace, workspace_elems, &fold)) {
-            fprintf(stderr, "[bcnn_hip] conv backward: the LDS-DMA weight-gradient kernel refused a folded layer\n");
-            exit(1);
-        }
-    } else {
-        for (const DwFamily& fam : kDwFamilies)
-            if (gate_open(fam.gate) &&
-                fam.run(x, dy, dw, batch_norm ? nullptr : dbias, s, workspace, workspace_elems, &bias_done))
-                break;
-    }
-    if (side) {
-        HIP_CHECK(hipEventRecord(side->done, side->stream));
-        set_current_stream(main_stream);
-    }
-    if (!batch_norm && !bias_done) bcnn_hip_grad_bias(dbias, dy, n, f, s.OHOW);  // uses the shared reduce scratch
-    if (dx) conv_dx_any(w, dy, dx, s, bs);
-    else if (bs) bs->splits = 0;
-    if (side) {
-        if (side_mode == 2) side->pending = true;
-        else HIP_CHECK(hipStreamWaitEvent(main_stream, side->done, 0));
-    }
+    ConvNodeFwd nd{};
+    nd.s = make_conv_shape(n, c, h, wd, f, k, stride, pad, groups); nd.fold = take_fold(); nd.res = &r; nd.res_out = res_out;
+    nd.x = x; nd.w = w; nd.act = BCNN_HIP_ACT_NONE; nd.batch_norm = 1; nd.mode = BCNN_HIP_MODE_TRAIN;
+    nd.p.scales = scales; nd.p.bias = bias; nd.saved_mean = saved_mean; nd.saved_var = saved_var;
+    nd.run.run_mean = run_mean; nd.run.run_var = run_var; nd.bn_workspace = bn_workspace;
+    conv_forward_impl(nd);
 }
 
 int bcnn_hip_conv_side_stream_mode(int mode) {
@@ -548,19 +586,29 @@ void bcnn_hip_conv_side_join(void) {
     HIP_CHECK(hipStreamWaitEvent(current_stream(), ss.done, 0));  // `done` was recorded behind the last weight-gradient launch
 }
 
-void bcnn_hip_conv_backward(const float* x, const float* w, const float* bias, const float* y, float* dy, float* dx,
-                            float* dw, float* dbias, int n, int c, int h, int wd, int f, int k, int stride, int pad,
-                            int groups, int act, const float* slopes, float* dslopes, int batch_norm,
-                            const float* scales, float* dscales, const float* saved_mean,
-                            const float* saved_var, float* dmean, float* dvar, const float* x_norm,
-                            const float* bn_workspace, float* workspace, size_t workspace_elems) {
-    conv_backward_impl(x, w, bias, y, dy, dx, dw, dbias, n, c, h, wd, f, k, stride, pad, groups, act, slopes, dslopes,
-                       batch_norm, scales, dscales, saved_mean, saved_var, dmean, dvar, x_norm, bn_workspace, workspace,
-                       workspace_elems, nullptr);
-}
-
 size_t bcnn_hip_conv_bnsums_size(int n, int c, int h, int wd) {
     return (size_t)c * (size_t)ceil_div((long long)n * h * wd, 64) * 2;
+}
+
+// bcnn_hip_conv_backward; own_sums: this node's batch-norm sums where whoever wrote dy left them; prev_*: the sums of the
+// batch-norm node in front, emitted by the data-gradient kernel (returns the partials per channel written, 0: none)
+int bcnn_hip_conv_backward_presummed(const float* x, const float* w, const float* bias, const float* y, float* dy, float* dx,
+                                     float* dw, float* dbias, int n, int c, int h, int wd, int f, int k, int stride, int pad,
+                                     int groups, int act, const float* slopes, float* dslopes, int batch_norm,
+                                     const float* scales, float* dscales, const float* saved_mean, const float* saved_var,
+                                     float* dmean, float* dvar, const float* x_norm, const float* bn_workspace,
+                                     float* workspace, size_t workspace_elems, const float* own_sums, int own_splits,
+                                     const float* prev_y, const float* prev_mean, float* prev_sums, size_t prev_sums_floats) {
+    DxBnSums bs{prev_y, prev_mean, prev_sums, prev_sums_floats, 0};
+    ConvNodeBwd nd{};
+    nd.s = make_conv_shape(n, c, h, wd, f, k, stride, pad, groups); nd.fold = take_fold(); nd.side_mode = side_mode_now();
+    nd.x = x; nd.w = w; nd.y = y; nd.dy = dy; nd.dx = dx; nd.dw = dw; nd.act = act; nd.slopes = slopes; nd.dslopes = dslopes;
+    nd.batch_norm = batch_norm; nd.p.scales = scales; nd.p.bias = bias; nd.saved.mean = saved_mean; nd.saved.var = saved_var;
+    nd.g.dscales = dscales; nd.g.dbias = dbias; nd.g.dmean = dmean; nd.g.dvar = dvar; nd.bn_workspace = bn_workspace;
+    nd.workspace = workspace; nd.workspace_elems = workspace_elems; nd.own_sums = own_sums; nd.own_splits = own_splits;
+    if (prev_sums && prev_y && prev_mean) nd.bs = &bs;
+    conv_backward_impl(nd);
+    return bs.splits;
 }
 
 int bcnn_hip_conv_backward_bnsums(const float* x, const float* w, const float* bias, const float* y, float* dy, float* dx,
@@ -571,31 +619,39 @@ int bcnn_hip_conv_backward_bnsums(const float* x, const float* w, const float* b
                                   float* workspace, size_t workspace_elems, const float* prev_y, const float* prev_mean,
                                   float* sums, size_t sums_floats) {
     DxBnSums bs{prev_y, prev_mean, sums, sums_floats, 0};
-    conv_backward_impl(x, w, bias, y, dy, dx, dw, dbias, n, c, h, wd, f, k, stride, pad, groups, act, slopes, dslopes,
-                       batch_norm, scales, dscales, saved_mean, saved_var, dmean, dvar, x_norm, bn_workspace, workspace,
-                       workspace_elems, nullptr, (sums && prev_y && prev_mean) ? &bs : nullptr);
+    ConvNodeBwd nd{};
+    nd.s = make_conv_shape(n, c, h, wd, f, k, stride, pad, groups); nd.fold = take_fold(); nd.side_mode = side_mode_now();
+    nd.x = x; nd.w = w; nd.y = y; nd.dy = dy; nd.dx = dx; nd.dw = dw; nd.act = act; nd.slopes = slopes; nd.dslopes = dslopes;
+    nd.batch_norm = batch_norm; nd.p.scales = scales; nd.p.bias = bias; nd.saved.mean = saved_mean; nd.saved.var = saved_var;
+    nd.g.dscales = dscales; nd.g.dbias = dbias; nd.g.dmean = dmean; nd.g.dvar = dvar; nd.bn_workspace = bn_workspace;
+    nd.workspace = workspace; nd.workspace_elems = workspace_elems;
+    if (sums && prev_y && prev_mean) nd.bs = &bs;
+    conv_backward_impl(nd);
     return bs.splits;
+}
+
+void bcnn_hip_conv_backward(const float* x, const float* w, const float* bias, const float* y, float* dy, float* dx,
+                            float* dw, float* dbias, int n, int c, int h, int wd, int f, int k, int stride, int pad,
+                            int groups, int act, const float* slopes, float* dslopes, int batch_norm,
+                            const float* scales, float* dscales, const float* saved_mean,
+                            const float* saved_var, float* dmean, float* dvar, const float* x_norm,
+                            const float* bn_workspace, float* workspace, size_t workspace_elems) {
+    ConvNodeBwd nd{};
+    nd.s = make_conv_shape(n, c, h, wd, f, k, stride, pad, groups); nd.fold = take_fold(); nd.side_mode = side_mode_now();
+    nd.x = x; nd.w = w; nd.y = y; nd.dy = dy; nd.dx = dx; nd.dw = dw; nd.act = act; nd.slopes = slopes; nd.dslopes = dslopes;
+    nd.batch_norm = batch_norm; nd.p.scales = scales; nd.p.bias = bias; nd.saved.mean = saved_mean; nd.saved.var = saved_var;
+    nd.g.dscales = dscales; nd.g.dbias = dbias; nd.g.dmean = dmean; nd.g.dvar = dvar; nd.bn_workspace = bn_workspace;
+    nd.workspace = workspace; nd.workspace_elems = workspace_elems;
+    conv_backward_impl(nd);
 }
 
 void bcnn_hip_conv_backward_bn_done(const float* x, const float* w, float* dy, float* dx, float* dw, int n, int c, int h, int wd,
                                     int f, int k, int stride, int pad, int groups, float* workspace, size_t workspace_elems) {
-    conv_backward_impl(x, w, nullptr, nullptr, dy, dx, dw, nullptr, n, c, h, wd, f, k, stride, pad, groups, BCNN_HIP_ACT_NONE,
-                       nullptr, nullptr, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, workspace,
-                       workspace_elems, nullptr, nullptr, nullptr, 0, /*bn_done=*/true);
-}
-
-int bcnn_hip_conv_backward_presummed(const float* x, const float* w, const float* bias, const float* y, float* dy, float* dx,
-                                     float* dw, float* dbias, int n, int c, int h, int wd, int f, int k, int stride, int pad,
-                                     int groups, int act, const float* slopes, float* dslopes, int batch_norm,
-                                     const float* scales, float* dscales, const float* saved_mean, const float* saved_var,
-                                     float* dmean, float* dvar, const float* x_norm, const float* bn_workspace,
-                                     float* workspace, size_t workspace_elems, const float* own_sums, int own_splits,
-                                     const float* prev_y, const float* prev_mean, float* prev_sums, size_t prev_sums_floats) {
-    DxBnSums bs{prev_y, prev_mean, prev_sums, prev_sums_floats, 0};
-    conv_backward_impl(x, w, bias, y, dy, dx, dw, dbias, n, c, h, wd, f, k, stride, pad, groups, act, slopes, dslopes,
-                       batch_norm, scales, dscales, saved_mean, saved_var, dmean, dvar, x_norm, bn_workspace, workspace,
-                       workspace_elems, nullptr, (prev_sums && prev_y && prev_mean) ? &bs : nullptr, own_sums, own_splits);
-    return bs.splits;
+    ConvNodeBwd nd{};
+    nd.s = make_conv_shape(n, c, h, wd, f, k, stride, pad, groups); nd.fold = take_fold(); nd.side_mode = side_mode_now();
+    nd.x = x; nd.w = w; nd.dy = dy; nd.dx = dx; nd.dw = dw; nd.act = BCNN_HIP_ACT_NONE; nd.batch_norm = 1; nd.bn_done = true;
+    nd.workspace = workspace; nd.workspace_elems = workspace_elems;
+    conv_backward_impl(nd);
 }
 
 void bcnn_hip_conv_backward_residual(const float* x, const float* w, const float* bias, float* dy, float* dx, float* dw,
@@ -605,9 +661,13 @@ void bcnn_hip_conv_backward_residual(const float* x, const float* w, const float
                                      float* workspace, size_t workspace_elems, const float* res_out,
                                      const float* dres_out, int res_act, const float* res, float* dres, size_t res_count) {
     ConvResidualBwd rb{res_out, dres_out, res, dres, res_count, res_act};
-    conv_backward_impl(x, w, bias, nullptr, dy, dx, dw, dbias, n, c, h, wd, f, k, stride, pad, groups, BCNN_HIP_ACT_NONE,
-                       nullptr, nullptr, 1, scales, dscales, saved_mean, saved_var, dmean, dvar, nullptr, bn_workspace,
-                       workspace, workspace_elems, &rb);
+    ConvNodeBwd nd{};
+    nd.s = make_conv_shape(n, c, h, wd, f, k, stride, pad, groups); nd.fold = take_fold(); nd.side_mode = side_mode_now();
+    nd.x = x; nd.w = w; nd.dy = dy; nd.dx = dx; nd.dw = dw; nd.act = BCNN_HIP_ACT_NONE; nd.batch_norm = 1; nd.rb = &rb;
+    nd.p.scales = scales; nd.p.bias = bias; nd.saved.mean = saved_mean; nd.saved.var = saved_var;
+    nd.g.dscales = dscales; nd.g.dbias = dbias; nd.g.dmean = dmean; nd.g.dvar = dvar; nd.bn_workspace = bn_workspace;
+    nd.workspace = workspace; nd.workspace_elems = workspace_elems;
+    conv_backward_impl(nd);
 }
 
 }  // extern "C"

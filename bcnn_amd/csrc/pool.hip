@@ -500,8 +500,11 @@ void bcnn_hip_maxpool_bn_backward(const float* dpool, const int* indexes, const 
     // the divisor of dmean / M and of the dvar term stays the un-pooled element count)
     {
         KTimer kt(K_BN_BWD, 0.0, 4.0 * 2.0 * (double)ptotal);
-        batchnorm_backward_sums(dpool, nullptr, act, scales, dscales, dbias, mean, var, dmean, dvar, raw_at_max, n, c,
-                                out_h * out_w, act != BCNN_HIP_ACT_NONE ? bias : nullptr, nullptr, 0u, consts, fM);
+        BnBwdCall b{};
+        b.dout = dpool; b.workspace = raw_at_max; b.act = act; b.e.n = n; b.e.c = c; b.e.hw = out_h * out_w;
+        b.p.scales = scales; b.p.bias = act != BCNN_HIP_ACT_NONE ? bias : nullptr; b.s.mean = mean; b.s.var = var;
+        b.g.dscales = dscales; b.g.dbias = dbias; b.g.dmean = dmean; b.g.dvar = dvar; b.consts = consts; b.consts_fM = fM;
+        batchnorm_backward_sums(b);
     }
     KTimer kt(K_POOL, 0.0, 4.0 * (2.0 * (double)total + 2.0 * (double)ptotal));
     dim3 grid((unsigned)ceil_div(h * (w / 4), 256), (unsigned)(n * c));

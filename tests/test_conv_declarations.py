@@ -146,3 +146,30 @@ def test_the_depthwise_shape_is_derived_once():
     table = _strip_comments(open(os.path.join(CSRC, "depthwise.hip")).read())
     rows = re.findall(r"kDw(?:Fwd|Bwd)Families\[\]\s*=\s*\{(.*?)\n\};", table, re.S)
     assert len(rows) == 2 and table.count("depthwise_march_splits") == sum(r.count("depthwise_march_splits") for r in rows) == 2
+
+
+def _parameter_count(params):
+    """top-level commas of a parameter list + 1; brackets of any kind (templates, function pointers, array bounds) nest"""
+    if params.strip() in ("", "void"):
+        return 0
+    depth = n = 0
+    for ch in params:
+        depth += {"(": 1, "[": 1, "{": 1, "<": 1, ")": -1, "]": -1, "}": -1, ">": -1}.get(ch, 0)
+        n += ch == "," and depth == 0
+    assert depth == 0, params
+    return n + 1
+
+
+def test_host_functions_behind_the_abi_take_at_most_13_parameters():
+    """what the C ABI spreads over dozens of positional arguments travels in named structs behind it (batchnorm.h: BnFwdCall,
+    BnBwdCall; conv.hip: ConvNodeFwd, ConvNodeBwd). 13 is lrn_run's count (lrn_dropout.hip), the largest there is."""
+    assert _parameter_count("const ConvFamily<A, B> (&rows)[R], int (*f)(int, int), float x = g(1, 2)") == 3
+    seen = 0
+    for pattern in ("*.hip", "*.h"):
+        for fn, fs in _parsed(pattern)[1].items():
+            for name, _, _, in_c, device, params in fs:
+                if in_c or device:
+                    continue
+                seen += 1
+                assert _parameter_count(params) <= 13, "%s: %s() takes %d parameters" % (fn, name, _parameter_count(params))
+    assert seen > 300, seen
