@@ -9,9 +9,11 @@ namespace bcnn_hip {
 struct DwShape {
     int N, C, H, W, OH, OW, ksz, stride, pad;
 };
+// a kernel larger than the padded plane has no output: (3 - 5) / 1 + 1 = -1 each way must not multiply to one pixel per plane
+inline int dw_extent(int e) { return e < 0 ? 0 : e; }
 inline DwShape dw_shape(int n, int c, int h, int w, int k, int stride, int pad) {
     const int st = stride < 1 ? 1 : stride;  // a size query may carry anything; no family takes such a shape
-    return DwShape{n, c, h, w, (h + 2 * pad - k) / st + 1, (w + 2 * pad - k) / st + 1, k, stride, pad};
+    return DwShape{n, c, h, w, dw_extent((h + 2 * pad - k) / st + 1), dw_extent((w + 2 * pad - k) / st + 1), k, stride, pad};
 }
 
 // Batch-norm coefficients of the stand-alone batch-norm node that consumes a depthwise layer's output, for the backward

@@ -533,6 +533,7 @@ static void dw_window3_forward(const DwFwdCall& c) {
 #ifdef DW_PERSIST
     if (blocks > (unsigned)(kCUs * DW_PERSIST)) blocks = (unsigned)(kCUs * DW_PERSIST);
 #endif
+    trace_kernel(c.s.stride == 1 ? "dw3_fwd_kernel<1>" : "dw3_fwd_kernel<2>");
     if (c.s.stride == 1) dw3_fwd_kernel<1, DW_VR><<<blocks, 256, 0, current_stream()>>>(c.x, c.w, c.bias, c.y, a, c.act);
     else dw3_fwd_kernel<2, DW_VR><<<blocks, 256, 0, current_stream()>>>(c.x, c.w, c.bias, c.y, a, c.act);
     KERNEL_CHECK();
@@ -540,6 +541,7 @@ static void dw_window3_forward(const DwFwdCall& c) {
 
 static void dw_generic_forward(const DwFwdCall& c) {
     const size_t total = (size_t)c.s.N * c.s.C * c.s.OH * c.s.OW;
+    trace_kernel("dw_fwd_kernel");
     dw_fwd_kernel<<<stream_grid(total, 256), 256, 0, current_stream()>>>(c.x, c.w, c.bias, c.y, c.s, c.act, (unsigned)total);
     KERNEL_CHECK();
 }
@@ -557,12 +559,18 @@ static void dw_unfused_backward(const DwBwdCall& c) {
     Dw3Args a3;
     if (ch <= 65535 && dw3_args(s, n, &a3)) {
         dim3 g2((unsigned)splits, (unsigned)ch);
+        trace_kernel(s.stride == 1 ? "dw3_bwd_weight_kernel<1>" : "dw3_bwd_weight_kernel<2>");
         if (s.stride == 1) dw3_bwd_weight_kernel<1, DW_VR><<<g2, 256, 0, current_stream()>>>(c.x, c.dy, a3, splits, part);
         else dw3_bwd_weight_kernel<2, DW_VR><<<g2, 256, 0, current_stream()>>>(c.x, c.dy, a3, splits, part);
-    } else if (k == 3) dw_bwd_weight_kernel<3><<<grid, 256, 0, current_stream()>>>(c.x, c.dy, s, splits, part);
-    else if (k == 5) dw_bwd_weight_kernel<5><<<grid, 256, 0, current_stream()>>>(c.x, c.dy, s, splits, part);
-    else {
+    } else if (k == 3) {
+        trace_kernel("dw_bwd_weight_kernel<3>");
+        dw_bwd_weight_kernel<3><<<grid, 256, 0, current_stream()>>>(c.x, c.dy, s, splits, part);
+    } else if (k == 5) {
+        trace_kernel("dw_bwd_weight_kernel<5>");
+        dw_bwd_weight_kernel<5><<<grid, 256, 0, current_stream()>>>(c.x, c.dy, s, splits, part);
+    } else {
         dim3 g3((unsigned)ch, (unsigned)splits, (unsigned)NT);
+        trace_kernel("dw_bwd_weight_tap_kernel");
         dw_bwd_weight_tap_kernel<<<g3, 256, 0, current_stream()>>>(c.x, c.dy, s, splits, part);
     }
     KERNEL_CHECK();
@@ -578,10 +586,12 @@ static void dw_unfused_backward(const DwBwdCall& c) {
         a.total_groups = (unsigned)groups_i;
         a.overwrite = c.overwrite;
         const unsigned blocks = (unsigned)((groups_i + 255) / 256);
+        trace_kernel(s.stride == 1 ? "dw3_bwd_data_s1_kernel" : s.stride == 2 ? "dw3_bwd_data_kernel<2>" : "dw3_bwd_data_kernel<0>");
         if (s.stride == 1) dw3_bwd_data_s1_kernel<DW_VR><<<blocks, 256, 0, current_stream()>>>(c.dy, c.w, c.dx, a);
         else if (s.stride == 2) dw3_bwd_data_kernel<2><<<blocks, 256, 0, current_stream()>>>(c.dy, c.w, c.dx, a);
         else dw3_bwd_data_kernel<0><<<blocks, 256, 0, current_stream()>>>(c.dy, c.w, c.dx, a);
     } else {
+        trace_kernel("dw_bwd_data_kernel");
         dw_bwd_data_kernel<<<stream_grid((size_t)total_i, 256), 256, 0, current_stream()>>>(c.dy, c.w, c.dx, s,
                                                                                          (unsigned)total_i, c.overwrite);
     }

@@ -905,6 +905,7 @@ void depthwise_lds_forward(const DwFwdCall& c) {
     a.stats = dw_stats_slots(c.stats, s.C, a.splits);
     a.in = c.in ? *c.in : DwBnIn{nullptr, nullptr, nullptr, nullptr, 0};
     const unsigned tiles = (unsigned)ceil_div((long long)a.planes, a.g.P) * (unsigned)a.g.NB;
+    trace_kernel(c.in ? "dwl_fwd_kernel:bnin" : "dwl_fwd_kernel");
     if (c.in) {
         if (s.stride == 1) dwl_fwd_kernel<1, kVR1, true><<<tiles, 256, lds, current_stream()>>>(a);
         else dwl_fwd_kernel<2, kVR2, true><<<tiles, 256, lds, current_stream()>>>(a);
@@ -968,6 +969,7 @@ void depthwise_lds_backward(const DwBwdCall& c) {
     a.in_sums = sums ? dw_stats_slots(c.in_sums, s.C, a.splits) : nullptr;
     const unsigned tiles = (unsigned)ceil_div((long long)a.planes, a.g.P) * (unsigned)a.g.NB;
     hipStream_t st = current_stream();
+    trace_kernel(bn && in ? "dwl_bwd_kernel:bn+bnin" : bn ? "dwl_bwd_kernel:bn" : in ? "dwl_bwd_kernel:bnin" : "dwl_bwd_kernel");
 #define DWL_LAUNCH(SV, VRV)                                                                     \
     do {                                                                                        \
         if (bn && in) dwl_bwd_kernel<SV, VRV, true, true><<<tiles, 256, lds, st>>>(a);          \

@@ -424,11 +424,13 @@ void bcnn_hip_maxpool_forward(const float* x, float* y, int* indexes, int n, int
         (long long)n * c * h * w < 0x7fffffffLL && (reinterpret_cast<uintptr_t>(x) & 15) == 0) {
         const long long pairs = (long long)n * c * out_h * ((out_w + 1) / 2);
         const unsigned blocks = (unsigned)((pairs + 255) / 256);
+        trace_kernel(size == 2 ? "maxpool_fwd_s2_kernel<2>" : "maxpool_fwd_s2_kernel<3>");
         if (size == 2) maxpool_fwd_s2_kernel<2><<<blocks, 256, 0, current_stream()>>>(x, y, indexes, h, w, out_h, out_w, (unsigned)pairs);
         else maxpool_fwd_s2_kernel<3><<<blocks, 256, 0, current_stream()>>>(x, y, indexes, h, w, out_h, out_w, (unsigned)pairs);
         KERNEL_CHECK();
         return;
     }
+    trace_kernel("maxpool_fwd_kernel");
     maxpool_fwd_kernel<<<stream_grid((size_t)total, 256), 256, 0, current_stream()>>>(
         x, y, indexes, n * c, h, w, out_h, out_w, size, stride, (unsigned)total);
     KERNEL_CHECK();
@@ -530,19 +532,23 @@ void bcnn_hip_maxpool_backward(const float* dy, const int* indexes, float* dx, i
         const bool pairs = size == 3 && stride == 2 && out_w * 2 == w &&
                            ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(indexes)) & 7) == 0;
         if (pairs) {
+            trace_kernel(overwrite ? "maxpool_bwd_vec4_k3s2_pair_kernel:overwrite" : "maxpool_bwd_vec4_k3s2_pair_kernel");
             if (overwrite) maxpool_bwd_vec4_k3s2_pair_kernel<true><<<grid, 256, 0, current_stream()>>>(dy, indexes, dx, h, w, out_h, out_w);
             else maxpool_bwd_vec4_k3s2_pair_kernel<false><<<grid, 256, 0, current_stream()>>>(dy, indexes, dx, h, w, out_h, out_w);
         } else if (size == 3 && stride == 2) {
+            trace_kernel(overwrite ? "maxpool_bwd_vec4_k3s2_kernel:overwrite" : "maxpool_bwd_vec4_k3s2_kernel");
             if (overwrite) maxpool_bwd_vec4_k3s2_kernel<true><<<grid, 256, 0, current_stream()>>>(dy, indexes, dx, h, w, out_h, out_w);
             else maxpool_bwd_vec4_k3s2_kernel<false><<<grid, 256, 0, current_stream()>>>(dy, indexes, dx, h, w, out_h, out_w);
-        } else if (overwrite)
-            maxpool_bwd_vec4_kernel<true><<<grid, 256, 0, current_stream()>>>(dy, indexes, dx, h, w, out_h, out_w, size, stride);
-        else
-            maxpool_bwd_vec4_kernel<false><<<grid, 256, 0, current_stream()>>>(dy, indexes, dx, h, w, out_h, out_w, size, stride);
+        } else {
+            trace_kernel(overwrite ? "maxpool_bwd_vec4_kernel:overwrite" : "maxpool_bwd_vec4_kernel");
+            if (overwrite) maxpool_bwd_vec4_kernel<true><<<grid, 256, 0, current_stream()>>>(dy, indexes, dx, h, w, out_h, out_w, size, stride);
+            else maxpool_bwd_vec4_kernel<false><<<grid, 256, 0, current_stream()>>>(dy, indexes, dx, h, w, out_h, out_w, size, stride);
+        }
         KERNEL_CHECK();
         return;
     }
     if (overwrite) bcnn_hip_fill_f32(dx, (size_t)total, 0.f);
+    trace_kernel(overwrite ? "maxpool_bwd_kernel:overwrite" : "maxpool_bwd_kernel");
     maxpool_bwd_kernel<<<stream_grid((size_t)total, 256), 256, 0, current_stream()>>>(
         dy, indexes, dx, h, w, out_h, out_w, size, stride, (unsigned)total);
     KERNEL_CHECK();
@@ -552,6 +558,7 @@ void bcnn_hip_avgpool_forward(const float* x, float* y, int n, int c, int h, int
     const int planes = n * c;
     if (!planes) return;
     const int grid = stream_grid((size_t)planes * 64, 256);
+    trace_kernel("avgpool_fwd_kernel");
     avgpool_fwd_kernel<<<grid, 256, 0, current_stream()>>>(x, y, planes, h * w);
     KERNEL_CHECK();
 }
@@ -559,6 +566,7 @@ void bcnn_hip_avgpool_forward(const float* x, float* y, int n, int c, int h, int
 void bcnn_hip_avgpool_backward(const float* dy, float* dx, int n, int c, int h, int w) {
     const long long total = (long long)n * c * h * w;
     if (!total) return;
+    trace_kernel("avgpool_bwd_kernel");
     avgpool_bwd_kernel<<<stream_grid((size_t)total, 256), 256, 0, current_stream()>>>(dy, dx, h * w, (unsigned)total);
     KERNEL_CHECK();
 }
