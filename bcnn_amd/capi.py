@@ -125,6 +125,8 @@ def lib():
         "bcnn_free_detections": (None, [C.POINTER(Detection), i]),
         "bcnn_fill_tensor_with_images": (i, [vp, i, i, C.POINTER(vp), C.POINTER(i), C.POINTER(i), C.POINTER(i), i, i, f,
                                              i, f, f, f]),
+        "bcnn_fill_tensor_with_jpegs": (i, [vp, i, i, C.POINTER(vp), C.POINTER(sz), i, f, i, f, f, f, C.POINTER(i)]),
+        "bcnn_set_num_threads": (i, [vp, i, C.POINTER(i)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)
@@ -356,6 +358,26 @@ class Net:
         return self.L.bcnn_fill_tensor_with_images(self.net, tensor, k, (C.c_void_p * k)(*ptrs), (C.c_int * k)(*ws),
                                                    (C.c_int * k)(*hs), (C.c_int * k)(*ss), c if c is not None else 0,
                                                    fit, norm_coeff, 1 if swap_to_bgr else 0, mean[0], mean[1], mean[2])
+
+    def fill_jpegs(self, jpegs, fit=IMAGE_FIT_STRETCH, norm_coeff=1.0, swap_to_bgr=False, mean=(0.0, 0.0, 0.0),
+                   tensor=0, num_images=None):
+        """bcnn_fill_tensor_with_jpegs: `jpegs` is a list of bytes objects, one JPEG stream per batch entry from 0 on;
+        each is entropy-decoded on the host and turned into pixels, resized (or letterboxed) and converted on the
+        device. Returns (bcnn_status, failed_image): (1, index) = BCNN_INVALID_PARAMETER, the tensor is untouched.
+        `num_images` overrides the count passed to the library (tests of the refusals)."""
+        keep = [np.frombuffer(bytes(j), np.uint8) for j in jpegs]
+        k = len(keep)
+        ptrs = (C.c_void_p * max(k, 1))(*[a.ctypes.data if a.size else None for a in keep])
+        lens = (C.c_size_t * max(k, 1))(*[a.size for a in keep])
+        failed = C.c_int(-1)
+        st = self.L.bcnn_fill_tensor_with_jpegs(self.net, tensor, k if num_images is None else num_images, ptrs, lens, fit,
+                                                norm_coeff, 1 if swap_to_bgr else 0, mean[0], mean[1], mean[2],
+                                                C.byref(failed))
+        return st, failed.value
+
+    def set_num_threads(self, num_threads):
+        """bcnn_set_num_threads: host threads of the calls that use them (bcnn_fill_tensor_with_jpegs)"""
+        return self.L.bcnn_set_num_threads(self.net, num_threads, None)
 
     def forward(self):
         self.L.bcnn_forward(self.net)

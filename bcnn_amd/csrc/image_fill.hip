@@ -10,19 +10,11 @@
 #include <cstring>
 
 #include "../host/bip_resize_tap.h"
+#include "image_fill.h"
 #include "store_run.h"
 
 namespace bcnn_hip {
 namespace {
-
-// Per-image record at the head of the staging block. Offsets count from the block's first byte.
-struct ImageDesc {
-    uint32_t data_off;           // packed pixels: h rows of w * c bytes (the caller's row padding is dropped)
-    uint32_t tapx_off, tapy_off; // int2 (index, frac) per column of the resized image / per row
-    int w, h;                    // source extent
-    int new_w, new_h;            // extent of the resized image inside the W x H plane
-    int x_off, y_off;            // where it is pasted; everything outside is the canvas value 128
-};
 
 constexpr int kFillBlock = 256;
 constexpr int kCanvas = 128;     // the letterbox canvas byte (yolo_example.cc:40-75)
@@ -87,6 +79,8 @@ __global__ __launch_bounds__(kFillBlock) void fill_images_kernel(const uint8_t* 
 struct HostStage { uint8_t* p = nullptr; size_t cap = 0; hipEvent_t copied = nullptr; bool in_flight = false; };
 thread_local HostStage g_stage[kMaxDevices];
 
+}  // namespace
+
 uint8_t* host_stage(size_t bytes) {
     HostStage& s = g_stage[current_device()];
     if (s.in_flight) {
@@ -102,7 +96,11 @@ uint8_t* host_stage(size_t bytes) {
     return s.p;
 }
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+void stage_copied(hipStream_t st) {
+    HostStage& hs = g_stage[current_device()];
+    HIP_CHECK(hipEventRecord(hs.copied, st));
+    hs.in_flight = true;
+}
 
 // Extent of image iw x ih inside the W x H plane: the plane itself (stretch), or the largest extent of the image's aspect
 // ratio that fits, by the reference example's integer rule (yolo_example.cc:40-75). False when an extent comes out 0.
@@ -119,7 +117,50 @@ bool fitted_extent(int fit, int W, int H, int iw, int ih, int* new_w, int* new_h
     return *new_w >= 1 && *new_h >= 1 && *new_w <= W && *new_h <= H;
 }
 
-}  // namespace
+size_t stage_geometry(uint8_t* stage, size_t tap_at, ImageDesc& d, int fit, int W, int H, int iw, int ih) {
+    d.w = iw;
+    d.h = ih;
+    fitted_extent(fit, W, H, iw, ih, &d.new_w, &d.new_h);
+    d.x_off = (W - d.new_w) / 2;
+    d.y_off = (H - d.new_h) / 2;
+    d.tapx_off = (uint32_t)tap_at;
+    int2* tx = reinterpret_cast<int2*>(stage + tap_at);
+    const float xs = bip_resize_scale((size_t)iw, (size_t)d.new_w), ys = bip_resize_scale((size_t)ih, (size_t)d.new_h);
+    for (int x = 0; x < d.new_w; ++x) bip_resize_tap((size_t)x, xs, (size_t)iw, &tx[x].x, &tx[x].y);
+    d.tapy_off = (uint32_t)(tap_at + (size_t)d.new_w * sizeof(int2));
+    int2* ty = reinterpret_cast<int2*>(stage + d.tapy_off);
+    for (int y = 0; y < d.new_h; ++y) bip_resize_tap((size_t)y, ys, (size_t)ih, &ty[y].x, &ty[y].y);
+    return ((size_t)d.new_w + d.new_h) * sizeof(int2);
+}
+
+bool fill_grid(int W, int H, int num_images, int* runs_per_row, int* blocks_per_image, long long* blocks) {
+    *runs_per_row = ceil_div(W, kRun);
+    *blocks_per_image = ceil_div((long long)*runs_per_row * H, kFillBlock);
+    *blocks = (long long)*blocks_per_image * num_images;
+    return *blocks <= 0x7fffffff;
+}
+
+void launch_fill_images(const uint8_t* stage_d, float* dst_d, int c, int H, int W, int num_images, float norm_coeff,
+                        int swap_to_bgr, float mean_r, float mean_g, float mean_b, hipStream_t st) {
+    FillParams p;
+    long long blocks;
+    fill_grid(W, H, num_images, &p.runs_per_row, &p.blocks_per_image, &blocks);
+    const float m[3] = {mean_r, mean_g, mean_b};
+    p.swap = (swap_to_bgr && c == 3) ? 1 : 0;
+    for (int k = 0; k < 4; ++k) p.mean[k] = (c == 3 && k < 3) ? m[p.swap ? 2 - k : k] : m[0];
+    p.norm = norm_coeff;
+    p.H = H;
+    p.W = W;
+    const dim3 grid((unsigned)blocks);
+    switch (c) {
+        case 1: fill_images_kernel<1><<<grid, kFillBlock, 0, st>>>(stage_d, dst_d, p); break;
+        case 2: fill_images_kernel<2><<<grid, kFillBlock, 0, st>>>(stage_d, dst_d, p); break;
+        case 3: fill_images_kernel<3><<<grid, kFillBlock, 0, st>>>(stage_d, dst_d, p); break;
+        default: fill_images_kernel<4><<<grid, kFillBlock, 0, st>>>(stage_d, dst_d, p); break;
+    }
+    KERNEL_CHECK();
+}
+
 }  // namespace bcnn_hip
 
 using namespace bcnn_hip;
@@ -140,18 +181,16 @@ int bcnn_hip_fill_images(float* dst_d, int n, int c, int h, int w, int num_image
         if (row > 0x7fffffff || (strides && strides[b] < row)) return 1;
         int new_w, new_h;
         if (!fitted_extent(fit, w, h, widths[b], heights[b], &new_w, &new_h)) return 1;
-        pixels += align_up((size_t)row * heights[b], 16);
+        pixels += stage_align((size_t)row * heights[b], 16);
         if (pixels > (size_t)0x7fffffff) return 1;
     }
     // the staging block: [descriptors][tap tables, room for W + H taps per image][pixels]; its offsets are 32-bit
-    const size_t desc_bytes = align_up((size_t)num_images * sizeof(ImageDesc), 16);
+    const size_t desc_bytes = stage_align((size_t)num_images * sizeof(ImageDesc), 16);
     const size_t taps = (size_t)num_images * ((size_t)w + h) * sizeof(int2);
     const size_t total = desc_bytes + taps + pixels;
-    FillParams p;
-    p.runs_per_row = ceil_div(w, kRun);
-    p.blocks_per_image = ceil_div((long long)p.runs_per_row * h, kFillBlock);
-    const long long blocks = (long long)p.blocks_per_image * num_images;
-    if (total > (size_t)0x7fffffff || blocks > 0x7fffffff) return 1;
+    int runs_per_row, blocks_per_image;
+    long long blocks;
+    if (total > (size_t)0x7fffffff || !fill_grid(w, h, num_images, &runs_per_row, &blocks_per_image, &blocks)) return 1;
 
     uint8_t* stage = host_stage(total);
     ImageDesc* desc = reinterpret_cast<ImageDesc*>(stage);
@@ -159,20 +198,7 @@ int bcnn_hip_fill_images(float* dst_d, int n, int c, int h, int w, int num_image
     for (int b = 0; b < num_images; ++b) {
         const int iw = widths[b], ih = heights[b];
         ImageDesc& d = desc[b];
-        d.w = iw;
-        d.h = ih;
-        fitted_extent(fit, w, h, iw, ih, &d.new_w, &d.new_h);
-        d.x_off = (w - d.new_w) / 2;
-        d.y_off = (h - d.new_h) / 2;
-        d.tapx_off = (uint32_t)tap_at;
-        int2* tx = reinterpret_cast<int2*>(stage + tap_at);
-        const float xs = bip_resize_scale((size_t)iw, (size_t)d.new_w), ys = bip_resize_scale((size_t)ih, (size_t)d.new_h);
-        for (int x = 0; x < d.new_w; ++x) bip_resize_tap((size_t)x, xs, (size_t)iw, &tx[x].x, &tx[x].y);
-        tap_at += (size_t)d.new_w * sizeof(int2);
-        d.tapy_off = (uint32_t)tap_at;
-        int2* ty = reinterpret_cast<int2*>(stage + tap_at);
-        for (int y = 0; y < d.new_h; ++y) bip_resize_tap((size_t)y, ys, (size_t)ih, &ty[y].x, &ty[y].y);
-        tap_at += (size_t)d.new_h * sizeof(int2);
+        tap_at += stage_geometry(stage, tap_at, d, fit, w, h, iw, ih);
         d.data_off = (uint32_t)pix_at;
         const size_t row = (size_t)iw * c, stride = strides ? (size_t)strides[b] : row;
         if (stride == row) {
@@ -180,30 +206,14 @@ int bcnn_hip_fill_images(float* dst_d, int n, int c, int h, int w, int num_image
         } else {
             for (int y = 0; y < ih; ++y) memcpy(stage + pix_at + y * row, images[b] + y * stride, row);
         }
-        pix_at += align_up(row * ih, 16);
+        pix_at += stage_align(row * ih, 16);
     }
     // ---- one copy, one launch
     uint8_t* stage_d = reinterpret_cast<uint8_t*>(scratch(SCRATCH_IMAGES, (total + 3) / 4));
     hipStream_t st = current_stream();
     HIP_CHECK(hipMemcpyAsync(stage_d, stage, total, hipMemcpyHostToDevice, st));
-    HostStage& hs = g_stage[current_device()];
-    HIP_CHECK(hipEventRecord(hs.copied, st));
-    hs.in_flight = true;
-
-    const float m[3] = {mean_r, mean_g, mean_b};
-    p.swap = (swap_to_bgr && c == 3) ? 1 : 0;
-    for (int k = 0; k < 4; ++k) p.mean[k] = (c == 3 && k < 3) ? m[p.swap ? 2 - k : k] : m[0];
-    p.norm = norm_coeff;
-    p.H = h;
-    p.W = w;
-    const dim3 grid((unsigned)blocks);
-    switch (c) {
-        case 1: fill_images_kernel<1><<<grid, kFillBlock, 0, st>>>(stage_d, dst_d, p); break;
-        case 2: fill_images_kernel<2><<<grid, kFillBlock, 0, st>>>(stage_d, dst_d, p); break;
-        case 3: fill_images_kernel<3><<<grid, kFillBlock, 0, st>>>(stage_d, dst_d, p); break;
-        default: fill_images_kernel<4><<<grid, kFillBlock, 0, st>>>(stage_d, dst_d, p); break;
-    }
-    KERNEL_CHECK();
+    stage_copied(st);
+    launch_fill_images(stage_d, dst_d, c, h, w, num_images, norm_coeff, swap_to_bgr, mean_r, mean_g, mean_b, st);
     return 0;
 }
 

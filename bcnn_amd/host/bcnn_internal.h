@@ -21,6 +21,7 @@
 #include <stdlib.h>
 
 #include <bcnn/bcnn.h>
+#include <bip/bip.h>
 
 #ifdef __cplusplus
 extern "C" {
@@ -490,6 +491,12 @@ void bcnn_link_conv_eltwise(bcnn_net *net);        /* bcnn_layers_hot.c; called 
 void bcnn_link_conv_maxpool(bcnn_net *net);
 void bcnn_link_conv_depthwise(bcnn_net *net);
 void bcnn_link_batchnorm_conv(bcnn_net *net);
+/* bcnn_input_jpeg.c: the entropy decoding of a batch of JPEG streams into the caller's coefficient regions, spread over
+ * num_threads host threads; lowest failing index, -1, or -2 (allocation). Not part of the public API: it is not static,
+ * and so exported, only so that tests/test_jpeg_split.py can check on a plain heap block that the bytes do not depend on
+ * the number of threads. */
+int bcnn_jpeg_read_batch(int num_images, const uint8_t *const *buffers, const size_t *lengths, const bip_jpeg_info *infos,
+                         int16_t *const *coeff, int num_threads);
 void bcnn_materialize_data(bcnn_net *net, int tensor);      /* tensor < 0: every pending one */
 void bcnn_materialize_gradients(bcnn_net *net, int tensor); /* tensor < 0: every pending one */
 void bcnn_drop_pending_gradients(bcnn_net *net);

@@ -21,6 +21,7 @@
 #include <string.h>
 
 #include "bip/bip.h"
+#include "bip_jpeg_pixels.h"
 
 /* zig-zag position -> row-major index of the 8 x 8 block */
 static const uint8_t k_unzig[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
@@ -43,8 +44,7 @@ typedef struct {
     int width, height;     /* samples that carry image content */
     int pitch, rows;       /* allocated plane: whole MCUs */
     int blocks_w, blocks_h;
-    uint8_t *plane;
-    int16_t *coeff; /* progressive: all coefficient blocks of the component */
+    int16_t *coeff; /* all coefficient blocks of the component, in the caller's memory */
 } jcomp;
 
 typedef struct {
@@ -138,59 +138,19 @@ static int huff_symbol(jdec *d, const jhuff *h) {
     return -1;
 }
 
-/* ---- inverse DCT ------------------------------------------------------------------------------------------------------ */
-#define FIX(x) ((int)((x) * 4096 + 0.5))
-static uint8_t clamp255(int v) { return (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v)); }
-
-/* one 8-point pass: even part in e[0..3], odd part in o[0..3] (both scaled by 4096); the caller combines e[i] +- o[3-i].
- * All arithmetic is modulo 2^32 (unsigned), which is what the reference's int arithmetic amounts to on every target it
- * runs on and keeps a corrupt stream's oversized coefficients from being undefined behaviour here. */
-typedef uint32_t u32;
-#define UMUL(a, k) ((u32)(a) * (u32)(int32_t)(k))
-static void idct8(int32_t s0, int32_t s1, int32_t s2, int32_t s3, int32_t s4, int32_t s5, int32_t s6, int32_t s7, u32 e[4],
-                  u32 o[4]) {
-    const u32 z = UMUL((u32)s2 + (u32)s6, FIX(0.5411961f));
-    const u32 a = z + UMUL(s6, FIX(-1.847759065f)), b = z + UMUL(s2, FIX(0.765366865f));
-    const u32 c = ((u32)s0 + (u32)s4) * 4096u, dd = ((u32)s0 - (u32)s4) * 4096u;
-    e[0] = c + b; e[3] = c - b; e[1] = dd + a; e[2] = dd - a;
-    const u32 p3 = (u32)s7 + (u32)s3, p4 = (u32)s5 + (u32)s1, p1 = (u32)s7 + (u32)s1, p2 = (u32)s5 + (u32)s3;
-    const u32 p5 = UMUL(p3 + p4, FIX(1.175875602f));
-    const u32 q1 = p5 + UMUL(p1, FIX(-0.899976223f)), q2 = p5 + UMUL(p2, FIX(-2.562915447f));
-    const u32 q3 = UMUL(p3, FIX(-1.961570560f)), q4 = UMUL(p4, FIX(-0.390180644f));
-    o[3] = UMUL(s1, FIX(1.501321110f)) + q1 + q4;
-    o[2] = UMUL(s3, FIX(3.072711026f)) + q2 + q3;
-    o[1] = UMUL(s5, FIX(2.053119869f)) + q2 + q4;
-    o[0] = UMUL(s7, FIX(0.298631336f)) + q1 + q3;
-}
-static int32_t sar(u32 v, int n) { /* arithmetic shift right of the two's-complement value */
-    return (int32_t)(v >> n) | ((v & 0x80000000u) ? (int32_t)(~0u << (32 - n)) : 0);
-}
-
+/* ---- inverse DCT (the arithmetic is bip_jpeg_pixels.h's) ------------------------------------------------------------- */
 static void idct_block(uint8_t *out, int pitch, const int16_t c[64]) {
-    int32_t mid[64];
-    u32 e[4], o[4];
-    for (int x = 0; x < 8; ++x) { /* columns; 2 extra bits of precision are kept */
+    int32_t mid[64], col[8];
+    for (int x = 0; x < 8; ++x) { /* columns */
         if (!(c[x + 8] | c[x + 16] | c[x + 24] | c[x + 32] | c[x + 40] | c[x + 48] | c[x + 56])) {
-            const int32_t dc = c[x] * 4;
+            const int32_t dc = c[x] * 4; /* what the general pass yields for it (see bip_jpeg_idct_column); quicker */
             for (int y = 0; y < 8; ++y) mid[8 * y + x] = dc;
             continue;
         }
-        idct8(c[x], c[x + 8], c[x + 16], c[x + 24], c[x + 32], c[x + 40], c[x + 48], c[x + 56], e, o);
-        for (int i = 0; i < 4; ++i) {
-            mid[8 * i + x] = sar(e[i] + 512u + o[3 - i], 10);
-            mid[8 * (7 - i) + x] = sar(e[i] + 512u - o[3 - i], 10);
-        }
+        bip_jpeg_idct_column(c + x, 8, col);
+        for (int y = 0; y < 8; ++y) mid[8 * y + x] = col[y];
     }
-    for (int y = 0; y < 8; ++y) { /* rows: remove 12 + 2 + 3 bits, re-centre on 128 */
-        const int32_t *m = mid + 8 * y;
-        idct8(m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7], e, o);
-        uint8_t *row = out + (size_t)y * pitch;
-        for (int i = 0; i < 4; ++i) {
-            const u32 base = e[i] + 65536u + (128u << 17);
-            row[i] = clamp255(sar(base + o[3 - i], 17));
-            row[7 - i] = clamp255(sar(base - o[3 - i], 17));
-        }
-    }
+    for (int y = 0; y < 8; ++y) bip_jpeg_idct_row(mid + 8 * y, out + (size_t)y * pitch);
 }
 
 /* ---- coefficient decoding --------------------------------------------------------------------------------------------- */
@@ -315,14 +275,9 @@ static int mcu_done(jdec *d) {
 }
 
 static int one_block(jdec *d, jcomp *c, int bx, int by) {
-    if (d->progressive) {
-        int16_t *blk = c->coeff + 64 * ((size_t)by * c->blocks_w + bx);
-        return d->ss == 0 ? block_prog_dc(d, c, blk) : block_prog_ac(d, c, blk);
-    }
-    int16_t blk[64];
-    if (!block_sequential(d, c, blk)) return 0;
-    idct_block(c->plane + (size_t)by * 8 * c->pitch + bx * 8, c->pitch, blk);
-    return 1;
+    int16_t *blk = c->coeff + 64 * ((size_t)by * c->blocks_w + bx);
+    if (d->progressive) return d->ss == 0 ? block_prog_dc(d, c, blk) : block_prog_ac(d, c, blk);
+    return block_sequential(d, c, blk);
 }
 
 static int decode_scan(jdec *d) {
@@ -433,12 +388,6 @@ static int read_frame(jdec *d) {
         c->pitch = d->mcus_x * c->h * 8;
         c->rows = d->mcus_y * c->v * 8;
         c->blocks_w = c->pitch >> 3; c->blocks_h = c->rows >> 3;
-        c->plane = (uint8_t *)calloc((size_t)c->pitch * c->rows + 16, 1);
-        if (!c->plane) return 0;
-        if (d->progressive) {
-            c->coeff = (int16_t *)calloc((size_t)c->blocks_w * c->blocks_h * 64, sizeof(int16_t));
-            if (!c->coeff) return 0;
-        }
     }
     return 1;
 }
@@ -468,7 +417,28 @@ static int read_scan_header(jdec *d) {
     return 1;
 }
 
-static int decode_planes(jdec *d) {
+static void info_from_frame(const jdec *d, bip_jpeg_info *info) {
+    memset(info, 0, sizeof(*info));
+    info->width = d->width; info->height = d->height; info->ncomp = d->ncomp;
+    info->hmax = d->hmax; info->vmax = d->vmax; info->progressive = d->progressive;
+    for (int i = 0; i < d->ncomp; ++i) {
+        const jcomp *c = &d->comp[i];
+        bip_jpeg_component *o = &info->comp[i];
+        o->h = c->h; o->v = c->v; o->width = c->width; o->height = c->height;
+        o->pitch = c->pitch; o->rows = c->rows; o->blocks_w = c->blocks_w; o->blocks_h = c->blocks_h;
+        /* the one-pass baseline decoder transformed every block it decoded: all of every whole MCU; the progressive one
+         * transforms, after the last scan, only the blocks that carry image content */
+        o->idct_w = d->progressive ? (c->width + 7) >> 3 : c->blocks_w;
+        o->idct_h = d->progressive ? (c->height + 7) >> 3 : c->blocks_h;
+        info->num_coefficients += (size_t)c->blocks_w * c->blocks_h * 64;
+    }
+}
+
+/* SOI, tables and application segments and the frame header; then, unless coeff is NULL (the caller only wants the
+ * frame), every scan up to EOI into coeff: baseline blocks arrive dequantised, progressive ones are dequantised at the
+ * end. `expect` is the frame the caller sized coeff for: a stream with another frame is refused before anything is
+ * written. */
+static int decode_stream(jdec *d, const bip_jpeg_info *expect, int16_t *coeff) {
     if (next_marker(d) != 0xd8) return 0; /* SOI */
     int m = next_marker(d);
     while (m != 0xc0 && m != 0xc1 && m != 0xc2) { /* tables and application segments up to the frame header */
@@ -481,6 +451,20 @@ static int decode_planes(jdec *d) {
     }
     d->progressive = m == 0xc2;
     if (!read_frame(d)) return 0;
+    if (!coeff) return 1;
+    bip_jpeg_info own;
+    info_from_frame(d, &own);
+    if (memcmp(&own, expect, sizeof(own)) != 0) return 0; /* not this buffer's: sizes would not hold */
+    /* Before the scans: a progressive stream accumulates into zeroed blocks; a baseline block that no scan reaches (a
+     * scan may end early at a missing restart marker and still be accepted) holds the block that transforms to bytes 0,
+     * which is what the one-pass decoder's zeroed plane kept there. */
+    memset(coeff, 0, own.num_coefficients * sizeof(int16_t));
+    if (!own.progressive)
+        for (size_t k = 0; k < own.num_coefficients; k += 64) coeff[k] = BIP_JPEG_DC_OF_ZERO_BLOCK;
+    for (int i = 0; i < d->ncomp; ++i) {
+        d->comp[i].coeff = coeff;
+        coeff += (size_t)d->comp[i].blocks_w * d->comp[i].blocks_h * 64;
+    }
     for (m = next_marker(d); m != 0xd9; m = next_marker(d)) { /* until EOI */
         if (m == 0xda) {
             if (!read_scan_header(d) || !decode_scan(d)) return 0;
@@ -495,7 +479,7 @@ static int decode_planes(jdec *d) {
             return 0;
         }
     }
-    if (d->progressive) /* all scans seen: dequantise (16-bit arithmetic) and transform */
+    if (d->progressive) /* all scans seen: dequantise (16-bit arithmetic) the blocks that get transformed */
         for (int i = 0; i < d->ncomp; ++i) {
             jcomp *c = &d->comp[i];
             const int bw = (c->width + 7) >> 3, bh = (c->height + 7) >> 3;
@@ -503,106 +487,118 @@ static int decode_planes(jdec *d) {
                 for (int bx = 0; bx < bw; ++bx) {
                     int16_t *blk = c->coeff + 64 * ((size_t)by * c->blocks_w + bx);
                     for (int k = 0; k < 64; ++k) blk[k] = (int16_t)(blk[k] * d->qt[c->tq][k]);
-                    idct_block(c->plane + (size_t)by * 8 * c->pitch + bx * 8, c->pitch, blk);
                 }
         }
     return 1;
 }
 
+bip_status bip_jpeg_frame_info(const uint8_t *buf, size_t len, bip_jpeg_info *info) {
+    if (!buf || !info) return BIP_INVALID_PTR;
+    jdec *d = (jdec *)calloc(1, sizeof(jdec));
+    if (!d) return BIP_UNKNOWN_ERROR;
+    d->p = buf; d->end = buf + len;
+    const int ok = decode_stream(d, NULL, NULL);
+    if (ok) info_from_frame(d, info);
+    free(d);
+    return ok ? BIP_SUCCESS : BIP_INVALID_PARAMETER;
+}
+
+bip_status bip_jpeg_read_coefficients(const uint8_t *buf, size_t len, const bip_jpeg_info *info, int16_t *coeff) {
+    if (!buf || !info || !coeff) return BIP_INVALID_PTR;
+    jdec *d = (jdec *)calloc(1, sizeof(jdec));
+    if (!d) return BIP_UNKNOWN_ERROR;
+    d->p = buf; d->end = buf + len;
+    const int ok = decode_stream(d, info, coeff);
+    free(d);
+    return ok ? BIP_SUCCESS : BIP_INVALID_PARAMETER;
+}
+
 /* ---- chroma upsampling (one output row from the nearer and the farther source row) ---------------------------------- */
 static const uint8_t *up_rows(uint8_t *out, const uint8_t *near_row, const uint8_t *far_row, int w, int hs, int vs) {
     if (hs == 1 && vs == 1) return near_row;
-    if (hs == 1 && vs == 2) {
-        for (int i = 0; i < w; ++i) out[i] = (uint8_t)((3 * near_row[i] + far_row[i] + 2) >> 2);
-        return out;
-    }
-    if (hs == 2 && vs == 1) {
-        if (w == 1) { out[0] = out[1] = near_row[0]; return out; }
-        out[0] = near_row[0];
-        out[1] = (uint8_t)((near_row[0] * 3 + near_row[1] + 2) >> 2);
-        for (int i = 1; i < w - 1; ++i) {
-            const int n = 3 * near_row[i] + 2;
-            out[2 * i] = (uint8_t)((n + near_row[i - 1]) >> 2);
-            out[2 * i + 1] = (uint8_t)((n + near_row[i + 1]) >> 2);
+    const int n = w * hs;
+    if (hs == 2 && (vs == 1 || vs == 2) && w > 2) {
+        /* the columns at the two ends have forms of their own (bip_jpeg_up_sample); between them every pair of output
+         * samples blends a column's sum with its left and its right neighbour's */
+        out[0] = bip_jpeg_up_sample(near_row, far_row, w, 2, vs, 0);
+        out[1] = bip_jpeg_up_sample(near_row, far_row, w, 2, vs, 1);
+        out[n - 2] = bip_jpeg_up_sample(near_row, far_row, w, 2, vs, n - 2);
+        out[n - 1] = bip_jpeg_up_sample(near_row, far_row, w, 2, vs, n - 1);
+        if (vs == 1) {
+            for (int i = 1; i < w - 1; ++i) {
+                out[2 * i] = BIP_JPEG_UP_DIV4(BIP_JPEG_UP_3TO1(near_row[i], near_row[i - 1]));
+                out[2 * i + 1] = BIP_JPEG_UP_DIV4(BIP_JPEG_UP_3TO1(near_row[i], near_row[i + 1]));
+            }
+        } else {
+            int prev = BIP_JPEG_UP_3TO1(near_row[0], far_row[0]), cur = BIP_JPEG_UP_3TO1(near_row[1], far_row[1]);
+            for (int i = 1; i < w - 1; ++i) {
+                const int next = BIP_JPEG_UP_3TO1(near_row[i + 1], far_row[i + 1]);
+                out[2 * i] = BIP_JPEG_UP_DIV16(cur, prev);
+                out[2 * i + 1] = BIP_JPEG_UP_DIV16(cur, next);
+                prev = cur;
+                cur = next;
+            }
         }
-        out[2 * w - 2] = (uint8_t)((near_row[w - 2] * 3 + near_row[w - 1] + 2) >> 2);
-        out[2 * w - 1] = near_row[w - 1];
         return out;
     }
-    if (hs == 2 && vs == 2) {
-        int prev, cur = 3 * near_row[0] + far_row[0]; /* vertical blend, 4x */
-        if (w == 1) { out[0] = out[1] = (uint8_t)((cur + 2) >> 2); return out; }
-        out[0] = (uint8_t)((cur + 2) >> 2);
-        for (int i = 1; i < w; ++i) {
-            prev = cur;
-            cur = 3 * near_row[i] + far_row[i];
-            out[2 * i - 1] = (uint8_t)((3 * prev + cur + 8) >> 4);
-            out[2 * i] = (uint8_t)((3 * cur + prev + 8) >> 4);
-        }
-        out[2 * w - 1] = (uint8_t)((cur + 2) >> 2);
-        return out;
-    }
-    for (int i = 0; i < w; ++i) /* other ratios: nearest neighbour along the row, the nearer row vertically */
-        for (int j = 0; j < hs; ++j) out[i * hs + j] = near_row[i];
+    for (int x = 0; x < n; ++x) out[x] = bip_jpeg_up_sample(near_row, far_row, w, hs, vs, x);
     return out;
 }
 
-#define CFIX(x) (((int)((x) * 4096.0f + 0.5f)) << 8)
-static void ycc_to_rgb(uint8_t *out, const uint8_t *y, const uint8_t *cb, const uint8_t *cr, int count) {
-    for (int i = 0; i < count; ++i, out += 3) {
-        const int yf = (y[i] << 20) + (1 << 19), r_ = cr[i] - 128, b_ = cb[i] - 128;
-        const int r = (yf + r_ * CFIX(1.40200f)) >> 20;
-        const int g = (int)(yf + (r_ * -CFIX(0.71414f)) + (int)(((unsigned)(b_ * -CFIX(0.34414f))) & 0xffff0000u)) >> 20;
-        const int b = (yf + b_ * CFIX(1.77200f)) >> 20;
-        out[0] = clamp255(r); out[1] = clamp255(g); out[2] = clamp255(b);
+bip_status bip_jpeg_pixels_from_coefficients(const bip_jpeg_info *info, const int16_t *coeff, uint8_t *image) {
+    if (!info || !coeff || !image) return BIP_INVALID_PTR;
+    const int n = info->ncomp, width = info->width, height = info->height;
+    if ((n != 1 && n != 3) || width < 1 || height < 1) return BIP_INVALID_PARAMETER;
+    uint8_t *plane[3] = {NULL, NULL, NULL}, *line[3] = {NULL, NULL, NULL};
+    bip_status st = BIP_UNKNOWN_ERROR;
+    int hs[3], vs[3], w_lores[3];
+    for (int k = 0; k < n; ++k) {
+        const bip_jpeg_component *c = &info->comp[k];
+        if (c->h < 1 || c->v < 1 || c->idct_w > c->blocks_w || c->idct_h > c->blocks_h || c->pitch != 8 * c->blocks_w ||
+            c->rows != 8 * c->blocks_h)
+            { st = BIP_INVALID_PARAMETER; goto done; }
+        plane[k] = (uint8_t *)calloc((size_t)c->pitch * c->rows + 16, 1);
+        line[k] = (uint8_t *)malloc((size_t)width + 8);
+        if (!plane[k] || !line[k]) goto done;
+        for (int by = 0; by < c->idct_h; ++by)
+            for (int bx = 0; bx < c->idct_w; ++bx)
+                idct_block(plane[k] + (size_t)by * 8 * c->pitch + bx * 8, c->pitch, coeff + 64 * ((size_t)by * c->blocks_w + bx));
+        coeff += (size_t)c->blocks_w * c->blocks_h * 64;
+        hs[k] = info->hmax / c->h;
+        vs[k] = info->vmax / c->v;
+        w_lores[k] = (width + hs[k] - 1) / hs[k];
     }
+    for (int y = 0; y < height; ++y) {
+        const uint8_t *src[3] = {NULL, NULL, NULL};
+        for (int k = 0; k < n; ++k) {
+            int near_row, far_row;
+            bip_jpeg_up_source_rows(y, vs[k], info->comp[k].height, &near_row, &far_row);
+            src[k] = up_rows(line[k], plane[k] + (size_t)near_row * info->comp[k].pitch,
+                             plane[k] + (size_t)far_row * info->comp[k].pitch, w_lores[k], hs[k], vs[k]);
+        }
+        uint8_t *out = image + (size_t)n * width * y;
+        if (n == 3) for (int x = 0; x < width; ++x) bip_jpeg_ycc_to_rgb(src[0][x], src[1][x], src[2][x], out + 3 * x);
+        else memcpy(out, src[0], (size_t)width);
+    }
+    st = BIP_SUCCESS;
+done:
+    for (int k = 0; k < 3; ++k) { free(plane[k]); free(line[k]); }
+    return st;
 }
 
 /* NULL unless the buffer holds a JPEG stream this decoder covers; the caller frees the image */
 uint8_t *bip_decode_jpeg(const uint8_t *buf, size_t len, int32_t *w, int32_t *h, int32_t *depth) {
-    jdec *d = (jdec *)calloc(1, sizeof(jdec));
-    uint8_t *image = NULL, *line[3] = {NULL, NULL, NULL};
-    if (!d) return NULL;
-    d->p = buf; d->end = buf + len;
-    if (!decode_planes(d)) goto done;
-    const int n = d->ncomp;
-    image = (uint8_t *)malloc((size_t)n * d->width * d->height + 1);
-    if (!image) goto done;
-    struct { int hs, vs, w_lores, ystep, ypos; const uint8_t *row0, *row1; } up[3];
-    for (int k = 0; k < n; ++k) {
-        line[k] = (uint8_t *)malloc((size_t)d->width + 8);
-        if (!line[k]) { free(image); image = NULL; goto done; }
-        up[k].hs = d->hmax / d->comp[k].h;
-        up[k].vs = d->vmax / d->comp[k].v;
-        up[k].ystep = up[k].vs >> 1;
-        up[k].w_lores = (d->width + up[k].hs - 1) / up[k].hs;
-        up[k].ypos = 0;
-        up[k].row0 = up[k].row1 = d->comp[k].plane;
+    bip_jpeg_info info;
+    if (bip_jpeg_frame_info(buf, len, &info) != BIP_SUCCESS) return NULL;
+    int16_t *coeff = (int16_t *)malloc(info.num_coefficients * sizeof(int16_t));
+    uint8_t *image = (uint8_t *)malloc((size_t)info.ncomp * info.width * info.height + 1);
+    if (!coeff || !image || bip_jpeg_read_coefficients(buf, len, &info, coeff) != BIP_SUCCESS ||
+        bip_jpeg_pixels_from_coefficients(&info, coeff, image) != BIP_SUCCESS) {
+        free(image);
+        image = NULL;
+    } else {
+        *w = info.width; *h = info.height; *depth = info.ncomp;
     }
-    for (int y = 0; y < d->height; ++y) {
-        const uint8_t *src[3] = {NULL, NULL, NULL};
-        for (int k = 0; k < n; ++k) {
-            /* in the lower half of a source row the next row is the nearer one */
-            const int lower = up[k].ystep >= (up[k].vs >> 1);
-            src[k] = up_rows(line[k], lower ? up[k].row1 : up[k].row0, lower ? up[k].row0 : up[k].row1, up[k].w_lores,
-                             up[k].hs, up[k].vs);
-            if (++up[k].ystep >= up[k].vs) {
-                up[k].ystep = 0;
-                up[k].row0 = up[k].row1;
-                if (++up[k].ypos < d->comp[k].height) up[k].row1 += d->comp[k].pitch;
-            }
-        }
-        uint8_t *out = image + (size_t)n * d->width * y;
-        if (n == 3) ycc_to_rgb(out, src[0], src[1], src[2], d->width);
-        else memcpy(out, src[0], (size_t)d->width);
-    }
-    *w = d->width; *h = d->height; *depth = n;
-done:
-    for (int k = 0; k < 3; ++k) {
-        free(line[k]);
-        free(d->comp[k].plane);
-        free(d->comp[k].coeff);
-    }
-    free(d);
+    free(coeff);
     return image;
 }

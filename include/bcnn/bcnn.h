@@ -163,6 +163,24 @@ BCNN_API bcnn_status bcnn_fill_tensor_with_images(bcnn_net *net, int tensor_inde
                                                   const uint8_t *const *images, const int *widths, const int *heights,
                                                   const int *strides, int c, bcnn_image_fit fit, float norm_coeff,
                                                   int swap_to_bgr, float mean_r, float mean_g, float mean_b);
+/* New, without a reference counterpart: the same from COMPRESSED images. buffers[b] / lengths[b] hold one JPEG stream
+ * each (what bip_load_image_from_memory decodes: 8-bit Huffman, baseline or progressive, 1 or 3 components). The host
+ * only parses the headers and runs the entropy decoder, straight into the staging buffer; inverse DCT, chroma upsampling
+ * and colour conversion run on the device, followed by the resize / letterbox / conversion above, so that decoded
+ * pixels never exist on the host. Entry b equals, bit for bit, what bcnn_fill_tensor_with_images makes of the pixels
+ * bip_load_image_from_memory returns for buffers[b]. `fit` is a bcnn_image_fit value; norm_coeff, swap_to_bgr and the
+ * means are as above. With bcnn_set_num_threads(net, T, ...) and T > 1 the entropy decoding of the images is spread over T
+ * host threads, created and joined inside the call; the result does not depend on T.
+ * The call is refused as a whole -- BCNN_INVALID_PARAMETER, a log line, the tensor as it was, nothing queued -- when
+ * tensor_index is out of range or the tensor has no device buffer; num_images < 1 or above the batch size; buffers,
+ * lengths or a buffers[b] is NULL; fit is unknown; a stream cannot be decoded; its component count differs from the
+ * tensor's c; its fitted extent is empty; or the staging block would pass 2 GiB. *failed_image (may be NULL) receives
+ * the index of the image a refusal is about, -1 otherwise. Host data, stream and staging are as above: the buffers may
+ * be freed or overwritten as soon as the call returns. */
+BCNN_API bcnn_status bcnn_fill_tensor_with_jpegs(bcnn_net *net, int tensor_index, int num_images,
+                                                 const uint8_t *const *buffers, const size_t *lengths, int fit,
+                                                 float norm_coeff, int swap_to_bgr, float mean_r, float mean_g,
+                                                 float mean_b, int *failed_image);
 
 /* ---- training set-up ---- */
 BCNN_API bcnn_status bcnn_set_mode(bcnn_net *net, bcnn_mode mode);

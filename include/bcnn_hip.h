@@ -637,6 +637,47 @@ int bcnn_hip_fill_images(float *dst_d, int n, int c, int h, int w, int num_image
                          int swap_to_bgr, float mean_r, float mean_g, float mean_b);
 
 /* ---------------------------------------------------------------------------------------------
+ * The input tensor of a batch from JPEG streams (jpeg_pixels.hip): the decoder's pixel stage on the device. The caller
+ * does the serial half of the decoder -- headers and entropy decoding into DEQUANTISED int16 coefficient blocks
+ * (libbip.so: bip_jpeg_frame_info, bip_jpeg_read_coefficients; this library does not depend on it) -- and this library
+ * does the rest: inverse DCT, chroma upsampling, Y Cb Cr -> R G B, then the resize / letterbox / conversion of
+ * bcnn_hip_fill_images with the same fit, norm_coeff, swap_to_bgr and means. Entries 0 .. num_images - 1 of dst_d
+ * [n][c][h][w] are written, the others are not. The arithmetic is the host decoder's own
+ * (bcnn_amd/host/bip_jpeg_pixels.h, integer throughout), so the tensor equals bcnn_hip_fill_images on the host-decoded
+ * pixels bit for bit.
+ *   bcnn_hip_jpeg_stage_begin  checks every frame and the sizes, lays the batch out in the pinned staging block of the
+ *       calling thread (the one bcnn_hip_fill_images uses; it waits for an earlier call's copy), writes the descriptors
+ *       and tap tables and returns in coeff[b] where image b's coefficients go: frames[b].comp[0]'s blocks_w * blocks_h
+ *       blocks of 64 int16, row-major, then the next component's. Returns 0, or 1 with nothing staged: NULL frames /
+ *       coeff; n, h or w < 1; c not 1 or 3; num_images outside 1..n; unknown fit; a frame whose ncomp is not c or whose
+ *       numbers do not fit together; a letterbox extent of 0; more than 2 GiB for the device block. *failed_image
+ *       (may be NULL) is then the index of the image the refusal is about, or -1.
+ *   bcnn_hip_jpeg_stage_run    after the caller has filled every coeff[b]: ONE copy of descriptors, taps and coefficients
+ *       (2 bytes per sample of every component plane) on the current stream and THREE kernels: jpeg_idct_kernel (8 lanes
+ *       per block, all blocks of all components of all images; blocks bx < idct_w, by < idct_h of a component are
+ *       transformed, the set the host transforms), jpeg_colour_kernel (a lane per 8 pixels of a row) and
+ *       fill_images_kernel. Planes and pixels stay in the library's scratch table. Returns 0, or 1 when no batch is
+ *       pending or dst_d is NULL.
+ *   bcnn_hip_jpeg_stage_cancel drops the pending batch (a stream failed to decode): nothing has been queued.
+ * Between _begin and _run / _cancel the calling thread makes no other call that stages images.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct bcnn_hip_jpeg_component {
+    int h, v;               /* sampling factors */
+    int width, height;      /* samples with image content */
+    int pitch, rows;        /* plane: 8 * blocks_w, 8 * blocks_h */
+    int blocks_w, blocks_h; /* coefficient blocks: whole MCUs */
+    int idct_w, idct_h;     /* blocks that are transformed */
+} bcnn_hip_jpeg_component;
+typedef struct bcnn_hip_jpeg_frame {
+    int width, height, ncomp, hmax, vmax;
+    bcnn_hip_jpeg_component comp[3];
+} bcnn_hip_jpeg_frame;
+int bcnn_hip_jpeg_stage_begin(int n, int c, int h, int w, int num_images, const bcnn_hip_jpeg_frame *frames, int fit,
+                              int16_t **coeff, int *failed_image);
+int bcnn_hip_jpeg_stage_run(float *dst_d, float norm_coeff, int swap_to_bgr, float mean_r, float mean_g, float mean_b);
+void bcnn_hip_jpeg_stage_cancel(void);
+
+/* ---------------------------------------------------------------------------------------------
  * The input tensor of a training batch from the loader's raw uint8 samples (augment.hip): online augmentation, centre
  * crop and conversion on the device. Entries 0 .. num_samples - 1 of the NCHW float tensor dst_d [n][c][h][w] are
  * written; the others are not. pixels (HOST) holds num_samples dense interleaved HWC samples of src_w x src_h x c bytes,

@@ -26,6 +26,31 @@ bip_status bip_write_image(char *filename, uint8_t *src, int32_t src_width, int3
 bip_status bip_load_image(char *filename, uint8_t **src, int32_t *src_width, int32_t *src_height, int32_t *src_depth);
 bip_status bip_load_image_from_memory(unsigned char *buffer, int buffer_size, uint8_t **src, int32_t *src_width,
                                       int32_t *src_height, int32_t *src_depth);
+/* ---- the JPEG decoder split at the coefficient boundary (bip_jpeg.c): entropy decoding on one side, pixel arithmetic
+ * (bcnn_amd/host/bip_jpeg_pixels.h) on the other; bip_load_image* is the three calls below in a row ---- */
+typedef struct {
+    int32_t h, v;               /* sampling factors */
+    int32_t width, height;      /* samples that carry image content */
+    int32_t pitch, rows;        /* the component's plane: whole MCUs */
+    int32_t blocks_w, blocks_h; /* its 8 x 8 blocks; block (bx, by) is the 64 int16 at 64 * (by * blocks_w + bx) */
+    int32_t idct_w, idct_h;     /* blocks (bx < idct_w, by < idct_h) that the pixel stage transforms: every block of a
+                                   baseline stream, the ((width + 7) >> 3) x ((height + 7) >> 3) with content of a
+                                   progressive one */
+} bip_jpeg_component;
+typedef struct {
+    int32_t width, height, ncomp; /* ncomp: 1 (grey) or 3 (Y Cb Cr) */
+    int32_t hmax, vmax, progressive;
+    size_t num_coefficients;      /* int16 the caller provides: the components' blocks one after the other */
+    bip_jpeg_component comp[3];
+} bip_jpeg_info;
+/* parses the stream up to and including its frame header; BIP_SUCCESS only for a stream the decoder covers so far */
+bip_status bip_jpeg_frame_info(const uint8_t *buf, size_t len, bip_jpeg_info *info);
+/* runs every scan and leaves the DEQUANTISED coefficient blocks in coeff[0 .. info->num_coefficients), row-major, 64 per
+ * block. `info` is what bip_jpeg_frame_info returned for the same buffer (anything else is refused). Fails on everything
+ * bip_load_image_from_memory fails on; writes nothing outside coeff. */
+bip_status bip_jpeg_read_coefficients(const uint8_t *buf, size_t len, const bip_jpeg_info *info, int16_t *coeff);
+/* the host pixel stage: inverse DCT, chroma upsampling, colour conversion into image[height][width][ncomp] */
+bip_status bip_jpeg_pixels_from_coefficients(const bip_jpeg_info *info, const int16_t *coeff, uint8_t *image);
 /* bilinear resize with half-pixel centres and 4-bit fixed-point weights per axis, depth 1..4 interleaved
  * channels, strides in bytes (reference src/bip/src/bip.c:1077-1200) */
 bip_status bip_resize_bilinear(uint8_t *src, size_t src_width, size_t src_height, size_t src_stride, uint8_t *dst,
