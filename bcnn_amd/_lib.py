@@ -121,6 +121,8 @@ SIGNATURES = {
     "bcnn_hip_yolo_nms_capacity": (i, []),
     "bcnn_hip_yolo_detect_result_words": (sz, [i, i, i]),
     "bcnn_hip_yolo_detect_batch": (i, [vp, i, i, vp, i, i, i, i, f, i, f, i, i, vp]),
+    "bcnn_hip_yolo_train_workspace_size": (sz, [vp]),
+    "bcnn_hip_yolo_train_forward": (i, [vp, vp, vp, vp, vp, vp, vp]),
     "bcnn_hip_fill_images": (i, [vp, i, i, i, i, i, vp, vp, vp, vp, i, f, i, f, f, f]),
     "bcnn_hip_jpeg_stage_begin": (i, [i, i, i, i, i, vp, i, vp, vp]),
     "bcnn_hip_jpeg_stage_run": (i, [vp, f, i, f, f, f]),

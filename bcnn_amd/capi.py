@@ -35,6 +35,12 @@ class Detection(C.Structure):
                 ("prob", C.POINTER(C.c_float)), ("mask", C.POINTER(C.c_float)), ("objectness", C.c_float)]
 
 
+class YoloTrainStats(C.Structure):
+    """struct bcnn_yolo_train_stats (include/bcnn/bcnn.h)."""
+    _fields_ = [("avg_iou", C.c_float), ("avg_class", C.c_float), ("avg_obj", C.c_float), ("avg_anyobj", C.c_float),
+                ("recall50", C.c_float), ("recall75", C.c_float), ("count", C.c_int), ("cost", C.c_float)]
+
+
 _libc = C.CDLL(None)
 _libc.free.argtypes, _libc.free.restype = [C.c_void_p], None
 
@@ -111,6 +117,9 @@ def lib():
         "bcnn_set_weight_gradient_stream": (None, [vp, i]),
         "bcnn_set_inference_precision": (i, [vp, i]), "bcnn_get_inference_precision": (i, [vp]),
         "bcnn_set_loader_on_device": (i, [vp, i]), "bcnn_get_loader_on_device": (i, [vp]),
+        "bcnn_set_detector_training": (i, [vp, i]), "bcnn_get_detector_training": (i, [vp]),
+        "bcnn_yolo_get_train_stats": (i, [vp, i, C.POINTER(YoloTrainStats)]),
+        "bcnn_set_data_loader": (i, [vp, i, cp, cp, cp, cp]),
         "bcnn_set_gradient_ready_callback": (None, [vp, vp, vp]),
         "bcnn_get_gradient_arena": (vp, [vp, C.POINTER(sz)]), "bcnn_get_parameter_arena": (vp, [vp, C.POINTER(sz)]),
         "bcnn_synchronize": (None, [vp]), "bcnn_peek_tensor": (tp, [vp, i]), "bcnn_get_num_nodes": (i, [vp]),
@@ -285,6 +294,24 @@ class Net:
 
     def get_loader_on_device(self):
         return self.L.bcnn_get_loader_on_device(self.net)
+
+    def set_detector_training(self, on):
+        """bcnn_set_detector_training: YOLO heads may be built on a TRAIN net (or switched to TRAIN), their TRAIN forward
+        computes the YOLOv3 loss gradient on the device and the detection-list loader is accepted. Set it before the
+        heads are built. Returns the bcnn_status."""
+        return self.L.bcnn_set_detector_training(self.net, 1 if on else 0)
+
+    def get_detector_training(self):
+        return self.L.bcnn_get_detector_training(self.net)
+
+    def yolo_train_stats(self, node):
+        """bcnn_yolo_get_train_stats of YOLO node `node` after a TRAIN forward, as a dict (avg_iou, avg_class, avg_obj,
+        avg_anyobj, recall50, recall75, count, cost); raises ValueError for a node that is no YOLO head"""
+        out = YoloTrainStats()
+        st = self.L.bcnn_yolo_get_train_stats(self.net, node, C.byref(out))
+        if st != 0:
+            raise ValueError("node %d is not a YOLO head (status %d)" % (node, st))
+        return {name: getattr(out, name) for name, _ in YoloTrainStats._fields_}
 
     def compile(self):
         assert self.L.bcnn_compile_net(self.net) == 0

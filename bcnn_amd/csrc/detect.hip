@@ -359,6 +359,221 @@ __global__ __launch_bounds__(kDetBlock) void yolo_nms_kernel(const int* __restri
     }
 }
 
+// ---- training loss of the head ---------------------------------------------------------------------------------------
+// Reference bcnn_yolo.c:250-415 (a host loop there, after a read-back of the head, in the CUDA build too). Three stages
+// on the launch stream; every sum is a fixed-order tree, nothing is an atomic: the same inputs give the same bits.
+constexpr int kTrainBlock = 256;
+constexpr int kTruthFloats = BCNN_HIP_YOLO_TRAIN_MAX_TRUTHS * 5;  // truth = x, y, w, h, class (coords == 4)
+constexpr int kCostBlocksMax = 1024;
+constexpr int kStatsPerImage = 6;  // avg_iou, avg_cat, avg_obj, recall, recall75, count
+
+// get_yolo_box, bcnn_yolo.c:137-145: v = the four ACTIVATED box entries
+__device__ __forceinline__ float4 yolo_train_box(const float v[4], int col, int row, int lw, int lh, float aw, float ah,
+                                                 int in_w, int in_h) {
+    float4 b;
+    b.x = ((float)col + v[0]) / (float)lw;
+    b.y = ((float)row + v[1]) / (float)lh;
+    b.z = expf(v[2]) * aw / (float)in_w;
+    b.w = expf(v[3]) * ah / (float)in_h;
+    return b;
+}
+
+// the label row of image b into LDS (label_stride >= kTruthFloats floats per image)
+__device__ __forceinline__ void yolo_stage_truths(float* truths, const float* __restrict__ label, int label_stride, int b) {
+    for (int t = threadIdx.x; t < kTruthFloats; t += blockDim.x) truths[t] = label[(size_t)b * label_stride + t];
+    __syncthreads();
+}
+
+// (a) grid (ceil(num * hw / kTrainBlock), n): a lane owns one predicted box. Writes y and EVERY element of the box's
+// gradient (the reference's memset + the no-object delta), leaves the block's sum of objectness in anyobj_part.
+__global__ __launch_bounds__(kTrainBlock) void yolo_train_forward_kernel(bcnn_hip_yolo_train_head hd,
+                                                                         const float* __restrict__ x,
+                                                                         const float* __restrict__ label,
+                                                                         float* __restrict__ y, float* __restrict__ grad,
+                                                                         float* __restrict__ anyobj_part) {
+    __shared__ float truths[kTruthFloats];
+    __shared__ float red[kTrainBlock / kWave];
+    const int b = blockIdx.y, hw = hd.h * hd.w, per_box = hd.coords + hd.classes + 1;
+    yolo_stage_truths(truths, label, hd.label_stride, b);
+    const int p = blockIdx.x * kTrainBlock + threadIdx.x;
+    float obj = 0.f;
+    if (p < hd.num * hw) {
+        const int a = p / hw, cell = p - a * hw;
+        const size_t base = ((size_t)(b * hd.num + a) * per_box) * hw + cell;
+        float v[4];
+        for (int e = 0; e < 4; ++e) {  // coords == 4 (checked by the launcher)
+            v[e] = yolo_entry(x[base + (size_t)e * hw], e, per_box, hd.coords);
+            y[base + (size_t)e * hw] = v[e];
+            grad[base + (size_t)e * hw] = 0.f;
+        }
+        const float4 pred = yolo_train_box(v, cell % hd.w, cell / hd.w, hd.w, hd.h, hd.biases[2 * hd.mask[a]],
+                                           hd.biases[2 * hd.mask[a] + 1], hd.in_w, hd.in_h);
+        float best_iou = 0.f;
+        for (int t = 0; t < BCNN_HIP_YOLO_TRAIN_MAX_TRUTHS; ++t) {
+            const float* tr = truths + 5 * t;
+            if (!tr[0]) break;
+            const float iou = yolo_box_iou(pred, make_float4(tr[0], tr[1], tr[2], tr[3]));
+            if (iou > best_iou) best_iou = iou;
+        }
+        obj = yolo_entry(x[base + (size_t)hd.coords * hw], hd.coords, per_box, hd.coords);
+        y[base + (size_t)hd.coords * hw] = obj;
+        grad[base + (size_t)hd.coords * hw] = best_iou > 0.5f ? 0.f : obj;
+        for (int e = hd.coords + 1; e < per_box; ++e) {
+            y[base + (size_t)e * hw] = yolo_entry(x[base + (size_t)e * hw], e, per_box, hd.coords);
+            grad[base + (size_t)e * hw] = 0.f;
+        }
+    }
+    const float s = block_sum(obj, red);
+    if (threadIdx.x == 0) anyobj_part[(size_t)b * gridDim.x + blockIdx.x] = s;
+}
+
+// (b) grid n, one wave per image: the truths of the image IN ORDER (two truths of one (cell, anchor) overwrite each
+// other's deltas, and delta_yolo_class branches on what the earlier one left). Every lane follows the same control flow;
+// lane 0 writes the box / objectness deltas and keeps the statistics, the lanes run over the classes.
+__global__ __launch_bounds__(kWave) void yolo_train_truths_kernel(bcnn_hip_yolo_train_head hd,
+                                                                  const float* __restrict__ label,
+                                                                  const float* __restrict__ y, float* grad,
+                                                                  float* __restrict__ stats_part) {
+    __shared__ float truths[kTruthFloats];
+    const int b = blockIdx.x, lane = threadIdx.x, hw = hd.h * hd.w, per_box = hd.coords + hd.classes + 1;
+    yolo_stage_truths(truths, label, hd.label_stride, b);
+    float avg_iou = 0.f, avg_cat = 0.f, avg_obj = 0.f, recall = 0.f, recall75 = 0.f;
+    int count = 0;
+    for (int t = 0; t < BCNN_HIP_YOLO_TRAIN_MAX_TRUTHS; ++t) {
+        const float* tr = truths + 5 * t;
+        if (!tr[0]) break;
+        const float4 truth = make_float4(tr[0], tr[1], tr[2], tr[3]);
+        // i = (int)(truth.x * w), j = (int)(truth.y * h), class = (int)label: a truth whose cell or class falls outside
+        // the head is skipped as a whole (the reference writes out of bounds there)
+        const float fi = truth.x * (float)hd.w, fj = truth.y * (float)hd.h, fc = tr[4];
+        if (!(fi > -1.f && fi < (float)hd.w && fj > -1.f && fj < (float)hd.h && fc > -1.f && fc < (float)hd.classes))
+            continue;
+        const int i = (int)fi, j = (int)fj, cls = (int)fc;
+        float best_iou = 0.f;
+        int best_n = 0;
+        const float4 shifted = make_float4(0.f, 0.f, truth.z, truth.w);
+        for (int n = 0; n < hd.total; ++n) {
+            const float4 anchor = make_float4(0.f, 0.f, hd.biases[2 * n] / (float)hd.in_w, hd.biases[2 * n + 1] / (float)hd.in_h);
+            const float iou = yolo_box_iou(anchor, shifted);
+            if (iou > best_iou) {
+                best_iou = iou;
+                best_n = n;
+            }
+        }
+        int mask_n = -1;
+        for (int k = 0; k < hd.num; ++k)
+            if (hd.mask[k] == best_n) {
+                mask_n = k;
+                break;
+            }
+        if (mask_n < 0) continue;
+        const size_t base = ((size_t)(b * hd.num + mask_n) * per_box) * hw + (size_t)j * hd.w + i;
+        const size_t obj_index = base + (size_t)hd.coords * hw, class_index = obj_index + hw;
+        if (lane == 0) {  // delta_yolo_box, bcnn_yolo.c:147-175, and the objectness delta
+            const float v[4] = {y[base], y[base + hw], y[base + 2 * (size_t)hw], y[base + 3 * (size_t)hw]};
+            const float aw = hd.biases[2 * best_n], ah = hd.biases[2 * best_n + 1];
+            const float iou = yolo_box_iou(yolo_train_box(v, i, j, hd.w, hd.h, aw, ah, hd.in_w, hd.in_h), truth);
+            const float scale = 2 - truth.z * truth.w;
+            const float tx = truth.x * (float)hd.w - (float)i, ty = truth.y * (float)hd.h - (float)j;
+            const float tw = logf(truth.z * (float)hd.in_w / aw), th = logf(truth.w * (float)hd.in_h / ah);
+            grad[base] = -scale * (tx - v[0]);
+            grad[base + hw] = -scale * (ty - v[1]);
+            grad[base + 2 * (size_t)hw] = -scale * (tw - v[2]);
+            grad[base + 3 * (size_t)hw] = -scale * (th - v[3]);
+            avg_obj += y[obj_index];
+            grad[obj_index] = y[obj_index] - 1;
+            ++count;
+            if (iou > 0.5f) recall += 1;
+            if (iou > 0.75f) recall75 += 1;
+            avg_iou += iou;
+        }
+        // delta_yolo_class, bcnn_yolo.c:185-205: what an earlier truth of this image left at class 0 of the slot decides
+        if (grad[class_index]) {
+            if (lane == 0) {
+                const float out = y[class_index + (size_t)cls * hw];
+                grad[class_index + (size_t)cls * hw] = out - 1;
+                avg_cat += out;
+            }
+        } else {
+            for (int c = lane; c < hd.classes; c += kWave) {
+                const float out = y[class_index + (size_t)c * hw];
+                grad[class_index + (size_t)c * hw] = out - (c == cls ? 1 : 0);
+                if (c == cls) avg_cat += out;  // one lane per truth: gathered below
+            }
+        }
+        __syncthreads();  // the wave's stores are in place before the next truth reads class 0 of its slot
+    }
+    // avg_cat lives in whichever lane owned the class: every lane added at most its own terms, in truth order; the
+    // wave tree over them is fixed
+    avg_cat = wave_sum(avg_cat);
+    if (lane == 0) {
+        float* s = stats_part + (size_t)b * kStatsPerImage;
+        s[0] = avg_iou;
+        s[1] = avg_cat;
+        s[2] = avg_obj;
+        s[3] = recall;
+        s[4] = recall75;
+        s[5] = (float)count;  // <= 50: exact
+    }
+}
+
+// (c) cost = sum of grad^2: kCost blocks leave one partial each ...
+__global__ __launch_bounds__(kTrainBlock) void yolo_train_cost_kernel(const float* __restrict__ grad, size_t total,
+                                                                      float* __restrict__ cost_part) {
+    __shared__ float red[kTrainBlock / kWave];
+    const size_t gs = (size_t)gridDim.x * kTrainBlock;
+    float s = 0.f;
+    for (size_t k = (size_t)blockIdx.x * kTrainBlock + threadIdx.x; k < total; k += gs) s += grad[k] * grad[k];
+    s = block_sum(s, red);
+    if (threadIdx.x == 0) cost_part[blockIdx.x] = s;
+}
+
+// ... and one block folds them, the objectness partials of (a) and the per-image statistics of (b) into the record
+__global__ __launch_bounds__(kTrainBlock) void yolo_train_record_kernel(const float* __restrict__ cost_part, int cost_blocks,
+                                                                        const float* __restrict__ anyobj_part, int anyobj_parts,
+                                                                        const float* __restrict__ stats_part, int n,
+                                                                        bcnn_hip_yolo_train_record* __restrict__ rec) {
+    __shared__ float red[kTrainBlock / kWave];
+    __shared__ float stats[kStatsPerImage];
+    float c = 0.f, a = 0.f;
+    for (int k = threadIdx.x; k < cost_blocks; k += kTrainBlock) c += cost_part[k];
+    for (int k = threadIdx.x; k < anyobj_parts; k += kTrainBlock) a += anyobj_part[k];
+    c = block_sum(c, red);
+    a = block_sum(a, red);
+    if (threadIdx.x < kStatsPerImage) {
+        float s = 0.f;
+        for (int b = 0; b < n; ++b) s += stats_part[(size_t)b * kStatsPerImage + threadIdx.x];
+        stats[threadIdx.x] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        rec->cost = c;
+        rec->avg_iou = stats[0];
+        rec->avg_cat = stats[1];
+        rec->avg_obj = stats[2];
+        rec->avg_anyobj = a;
+        rec->recall = stats[3];
+        rec->recall75 = stats[4];
+        rec->count = (int)stats[5];
+    }
+}
+
+static bool yolo_train_head_ok(const bcnn_hip_yolo_train_head* hd) {
+    if (!hd || hd->n < 1 || hd->n > 65535 || hd->h < 1 || hd->w < 1 || hd->num < 1 || hd->num > BCNN_HIP_YOLO_MAX_ANCHORS ||
+        hd->coords != 4 || hd->classes < 0 || hd->total < 1 || hd->total > BCNN_HIP_YOLO_TRAIN_MAX_TOTAL || hd->in_w < 1 ||
+        hd->in_h < 1 || hd->label_stride < kTruthFloats)
+        return false;
+    for (int k = 0; k < hd->num; ++k)
+        if (hd->mask[k] < 0 || hd->mask[k] >= hd->total) return false;
+    const long long total = (long long)hd->n * hd->num * (hd->coords + hd->classes + 1) * hd->h * hd->w;
+    return total <= (1ll << 31) - 1;
+}
+
+static int yolo_train_cost_blocks(size_t total) {
+    const int need = ceil_div((long long)total, 4 * kTrainBlock);
+    return need < 1 ? 1 : (need > kCostBlocksMax ? kCostBlocksMax : need);
+}
+
 }  // namespace bcnn_hip
 
 using namespace bcnn_hip;
@@ -445,6 +660,35 @@ void bcnn_hip_yolo_activate(const float* x_d, float* y_d, int n, int num, int co
     yolo_activate_kernel<<<stream_grid(vec ? total / 4 + 1 : total, 256), 256, 0, current_stream()>>>(
         x_d, y_d, hw, num * per_box, per_box, coords, total, vec);
     KERNEL_CHECK();
+}
+
+// workspace: [cost partials][objectness partials n x blocks of (a)][statistics n x 6]
+size_t bcnn_hip_yolo_train_workspace_size(const bcnn_hip_yolo_train_head* hd) {
+    if (!yolo_train_head_ok(hd)) return 0;
+    const int gx = ceil_div((long long)hd->num * hd->h * hd->w, kTrainBlock);
+    return (size_t)kCostBlocksMax + (size_t)hd->n * gx + (size_t)hd->n * kStatsPerImage;
+}
+
+int bcnn_hip_yolo_train_forward(const bcnn_hip_yolo_train_head* hd, const float* x_d, const float* label_d, float* y_d,
+                                float* grad_d, bcnn_hip_yolo_train_record* record_d, float* workspace_d) {
+    if (!yolo_train_head_ok(hd) || !x_d || !label_d || !y_d || !grad_d || !record_d || !workspace_d) return 1;
+    const int hw = hd->h * hd->w, gx = ceil_div((long long)hd->num * hw, kTrainBlock);
+    const size_t total = (size_t)hd->n * hd->num * (hd->coords + hd->classes + 1) * hw;
+    float* cost_part = workspace_d;
+    float* anyobj_part = cost_part + kCostBlocksMax;
+    float* stats_part = anyobj_part + (size_t)hd->n * gx;
+    const int cost_blocks = yolo_train_cost_blocks(total);
+    hipStream_t st = current_stream();
+    yolo_train_forward_kernel<<<dim3(gx, hd->n), kTrainBlock, 0, st>>>(*hd, x_d, label_d, y_d, grad_d, anyobj_part);
+    KERNEL_CHECK();
+    yolo_train_truths_kernel<<<hd->n, kWave, 0, st>>>(*hd, label_d, y_d, grad_d, stats_part);
+    KERNEL_CHECK();
+    yolo_train_cost_kernel<<<cost_blocks, kTrainBlock, 0, st>>>(grad_d, total, cost_part);
+    KERNEL_CHECK();
+    yolo_train_record_kernel<<<1, kTrainBlock, 0, st>>>(cost_part, cost_blocks, anyobj_part, hd->n * gx, stats_part, hd->n,
+                                                        record_d);
+    KERNEL_CHECK();
+    return 0;
 }
 
 int bcnn_hip_yolo_nms_capacity(void) { return kNmsCapacity; }

@@ -588,10 +588,13 @@ bcnn_status bcnn_resize_net(bcnn_net *net, int w, int h, int c, int need_realloc
 
 bcnn_status bcnn_set_mode(bcnn_net *net, bcnn_mode mode) {
     if (net->mode == mode) return BCNN_SUCCESS;
-    if (mode == BCNN_MODE_TRAIN) /* the YOLO head's training loss is not built: it would train on a zero gradient */
+    if (mode == BCNN_MODE_TRAIN && !hctx(net)->detector_training) /* without the switch a head trains on a zero gradient */
         for (int i = 0; i < net->num_nodes; ++i)
             BCNN_CHECK_AND_LOG(net->log_ctx, net->nodes[i].type != BCNN_LAYER_YOLOV3, BCNN_INVALID_PARAMETER,
                                "bcnn_set_mode: the net holds a YOLO node, whose TRAIN-mode loss is not built\n");
+    if (mode == BCNN_MODE_TRAIN) /* bcnn_set_detector_training: every head needs the label and a gradient to write */
+        BCNN_CHECK_AND_LOG(net->log_ctx, bcnn_yolo_heads_trainable(net), BCNN_INVALID_PARAMETER,
+                           "bcnn_set_mode: a YOLO node was built without detector training or has no gradient buffer\n");
     net->mode = mode;
     /* TRAIN reads the train streams, VALID / PREDICT the (rewound) test streams: reference bcnn_net.c:490-504 */
     if (net->data_loader) bcnn_switch_data_handles(net, net->data_loader);
@@ -715,6 +718,16 @@ bcnn_status bcnn_set_loader_on_device(bcnn_net *net, int on) {
 
 int bcnn_get_loader_on_device(const bcnn_net *net) {
     return net ? ((const bcnn_hip_context *)net->hip_ctx)->loader_on_device : 0;
+}
+
+bcnn_status bcnn_set_detector_training(bcnn_net *net, int on) {
+    if (!net) return BCNN_INVALID_PARAMETER;
+    hctx(net)->detector_training = on ? 1 : 0;
+    return BCNN_SUCCESS;
+}
+
+int bcnn_get_detector_training(const bcnn_net *net) {
+    return net ? ((const bcnn_hip_context *)net->hip_ctx)->detector_training : 0;
 }
 
 void bcnn_set_gradient_ready_callback(bcnn_net *net, bcnn_gradient_ready_fn fn, void *user) {
@@ -869,12 +882,18 @@ void bcnn_node_optim_step(bcnn_net *net, bcnn_tensor *weights, bcnn_tensor *bias
                          ln->beta2, ln->learning_rate, ln->momentum / (float)world, ln->decay);
 }
 
+/* reference bcnn_get_loss, bcnn_net.c:431-449. The heads' costs live on the device: with detector training on, a TRAIN
+ * net reads every head's record here, once, at the end of the step. */
 static float current_loss(bcnn_net *net) {
     float loss = 0.f;
     int n = 0;
+    const int heads = hctx(net)->detector_training && net->mode == BCNN_MODE_TRAIN && bcnn_yolo_refresh_costs(net) > 0;
     for (int i = 0; i < net->num_nodes; ++i)
         if (net->nodes[i].type == BCNN_LAYER_COST) {
             loss += net->tensors[net->nodes[i].dst[0]].data[0];
+            ++n;
+        } else if (heads && net->nodes[i].type == BCNN_LAYER_YOLOV3) {
+            loss += ((const bcnn_yolo_param *)net->nodes[i].param)->cost[0];
             ++n;
         }
     return n ? loss / n : 0.f;

@@ -12,7 +12,8 @@
  *                             that a run seeded like a reference run sees the same samples byte for byte
  *   formats: BCNN_LOAD_MNIST (idx3 images + idx1 labels, big-endian headers), BCNN_LOAD_CIFAR10 (1 + 3072 byte records,
  *            planar RGB), BCNN_LOAD_CLASSIFICATION_LIST ("path label" lines), BCNN_LOAD_REGRESSION_LIST ("path v0 v1 ..").
- *            BCNN_LOAD_DETECTION_LIST belongs to the YOLO head, which is outside this build.
+ *            BCNN_LOAD_DETECTION_LIST ("path (class x y w h)*" lines: bcnn_detection_loader.c) letterboxes the image onto a
+ *            canvas of 128 and moves the boxes with it; it needs detector training or a net that holds a YOLO head.
  *
  * Behaviours of the reference that are kept on purpose (each is visible to a consumer that compares runs):
  *   - bcnn_augment_data_with_flip stores its flag in `apply_fliph`, the flip only happens when the INI key `flip_h` has set
@@ -20,6 +21,9 @@
  *   - bcnn_augment_data_with_distortion stores `distortion`, not `max_distortion`: it enables nothing;
  *   - a shifted or rotated sample is composed over a buffer filled with 128 / 0 respectively;
  *   - the readers wrap around at end of file, and switching to VALID / PREDICT mode rewinds the test streams.
+ * One deliberate difference in the detection-list reader: the reference forms the image's aspect ratio w / h in INTEGER
+ * arithmetic (bcnn_detection_loader.c:103), which gives a portrait image width 0 and stretches a 4:3 image square; here
+ * the ratio is the float one. Batches and labels are the reference's whenever the height divides the width.
  * Not built: Perlin distortion and random spotlights (INI keys max_distortion / max_spots). Their draws still consume
  * rand() call for call like the reference (parameters, the distortion's own seed, four values per spot), so that the other
  * augmentations stay aligned; the image is left untouched and a warning is printed once.
@@ -283,6 +287,7 @@ static void settle_owed(bcnn_net *net, bcnn_loader *it) {
 static loader_stage *stage_begin(bcnn_net *net, bcnn_loader *it) {
     bcnn_hip_context *hc = (bcnn_hip_context *)net->hip_ctx;
     bcnn_tensor *in = &net->tensors[0];
+    if (it->type == BCNN_LOAD_DETECTION_LIST) return NULL; /* the letterbox and its labels are made on the host */
     if (!hc->loader_on_device || !in->data_gpu || in->c < 1 || in->c > 4 || net->batch_size < 1 || in->n < net->batch_size)
         return NULL;
     const int stored = it->type == BCNN_LOAD_MNIST || it->type == BCNN_LOAD_CIFAR10;
@@ -657,6 +662,104 @@ static bcnn_status list_reg_next(bcnn_loader *it, bcnn_net *net, int idx) {
     return BCNN_SUCCESS;
 }
 
+/* ---- detection list: "image-path (class x y w h)*" lines (bcnn_detection_loader.c) --------------------------------- */
+static bcnn_status list_detection_init(bcnn_loader *it, bcnn_net *net, const char *a, const char *b, const char *c,
+                                       const char *d) {
+    BCNN_CHECK_STATUS(list_init(it, net, a, b, c, d));
+    it->input_net = (uint8_t *)calloc((size_t)bcnn_tensor_size3d(&net->tensors[0]), 1);
+    return it->input_net ? BCNN_SUCCESS : BCNN_FAILED_ALLOC;
+}
+
+static bcnn_status list_detection_next(bcnn_loader *it, bcnn_net *net, int idx) {
+    bcnn_tensor *in = &net->tensors[0];
+    char **tok = NULL;
+    const int n = next_line_tokens(it->f_current, &tok);
+    if (n <= 0) {
+        bcnn_log(net->log_ctx, BCNN_LOG_ERROR, "Invalid detection format\n");
+        return BCNN_INVALID_DATA;
+    }
+    if ((n - 1) % 5 != 0) {
+        bcnn_log(net->log_ctx, BCNN_LOG_WARNING,
+                 "Wrong data format for detection %s. Found %d labels but expected multiple of 5\n", tok[0], n - 1);
+        free_tokens(tok, n);
+        return BCNN_INVALID_DATA;
+    }
+    int w_img = 0, h_img = 0, c_img = 0;
+    unsigned char *pimg = NULL;
+    bip_load_image(tok[0], &pimg, &w_img, &h_img, &c_img);
+    if (!(w_img > 0 && h_img > 0 && pimg)) {
+        bcnn_log(net->log_ctx, BCNN_LOG_WARNING, "Skip invalid image %s\n", tok[0]);
+        free(pimg);
+        free_tokens(tok, n);
+        return BCNN_INVALID_DATA;
+    }
+    if (in->c != c_img) {
+        bcnn_log(net->log_ctx, BCNN_LOG_WARNING, "Skip image %s: unexpected number of channels\n", tok[0]);
+        free(pimg);
+        free_tokens(tok, n);
+        return BCNN_INVALID_DATA;
+    }
+    /* the letterbox: the float ratio (file header), the reference's truncations otherwise */
+    const float wh_ratio = (float)w_img / (float)h_img;
+    int nw, nh;
+    if (wh_ratio < 1) {
+        nh = in->h;
+        nw = (int)(nh * wh_ratio);
+    } else {
+        nw = in->w;
+        nh = (int)(nw / wh_ratio);
+    }
+    unsigned char *buf = (nw >= 1 && nh >= 1) ? (unsigned char *)calloc((size_t)nw * nh * c_img, 1) : NULL;
+    if (!buf) { /* an image so narrow that nothing of it is left at this input size */
+        bcnn_log(net->log_ctx, BCNN_LOG_WARNING, "Skip image %s: %d x %d leaves no pixel at the input size\n", tok[0], w_img, h_img);
+        free(pimg);
+        free_tokens(tok, n);
+        return BCNN_INVALID_DATA;
+    }
+    bip_resize_bilinear(pimg, w_img, h_img, (size_t)w_img * c_img, buf, nw, nh, (size_t)nw * c_img, c_img);
+    free(pimg);
+    int dx, dy; /* canvas offsets */
+    if (net->mode == BCNN_MODE_TRAIN) {
+        dx = rand_between(0, in->w - nw);
+        dy = rand_between(0, in->h - nh);
+    } else {
+        dx = (in->w - nw) / 2;
+        dy = (in->h - nh) / 2;
+    }
+    const size_t bytes = (size_t)bcnn_tensor_size3d(in);
+    memset(it->input_net, 128, bytes);
+    bip_crop_image(buf, nw, nh, (size_t)nw * c_img, -dx, -dy, it->input_net, in->w, in->h, (size_t)in->w * in->c, in->c);
+    free(buf);
+    bcnn_data_augmenter *aug = net->data_aug;
+    if (net->mode == BCNN_MODE_TRAIN && aug) { /* the flip draw, then brightness / contrast / flip (:130-140) */
+        aug->apply_fliph = 0;
+        if (aug->random_fliph) aug->apply_fliph = ((float)rand() / RAND_MAX > 0.5f);
+        bcnn_apply_data_augmentation(it->input_net, in->w, in->h, in->c, aug, it->input_uchar);
+    }
+    memcpy(it->input_uchar, it->input_net, bytes);
+    bcnn_convert_img_to_float(it->input_uchar, in->w, in->h, in->c, 1 / 127.5f, aug ? aug->swap_to_bgr : 0, 127.5f, 127.5f,
+                              127.5f, in->data + (size_t)idx * bytes);
+    if (net->mode != BCNN_MODE_PREDICT) {
+        int sz;
+        float *y = label_slot(net, idx, &sz);
+        int num_boxes = (n - 1) / 5;
+        if (num_boxes > BCNN_DETECTION_MAX_BOXES) num_boxes = BCNN_DETECTION_MAX_BOXES;
+        if (num_boxes > sz / 5) num_boxes = sz / 5; /* a label tensor some other builder shaped */
+        const float scale_x = (float)nw / (float)in->w, scale_y = (float)nh / (float)in->h;
+        const float scale_dx = (float)dx / (float)in->w, scale_dy = (float)dy / (float)in->h;
+        for (int i = 0; i < num_boxes; ++i) { /* box centre (x, y), extent (w, h), class */
+            y[i * 5 + 0] = (float)atof(tok[5 * i + 2]) * scale_x + scale_dx;
+            y[i * 5 + 1] = (float)atof(tok[5 * i + 3]) * scale_y + scale_dy;
+            y[i * 5 + 2] = (float)atof(tok[5 * i + 4]) * scale_x;
+            y[i * 5 + 3] = (float)atof(tok[5 * i + 5]) * scale_y;
+            if (aug && aug->apply_fliph) y[i * 5 + 0] = 1.0f - y[i * 5 + 0];
+            y[i * 5 + 4] = (float)atoi(tok[5 * i + 1]);
+        }
+    }
+    free_tokens(tok, n);
+    return BCNN_SUCCESS;
+}
+
 /* ---- public entry points ------------------------------------------------------------------------------------------ */
 static void loader_close(bcnn_loader *it) {
     FILE **fs[4] = {&it->f_train, &it->f_train_extra, &it->f_test, &it->f_test_extra};
@@ -677,7 +780,9 @@ void bcnn_destroy_data_loader(bcnn_net *net) {
 bcnn_status bcnn_set_data_loader(bcnn_net *net, bcnn_loader_type type, const char *train_path_data,
                                  const char *train_path_extra, const char *test_path_data, const char *test_path_extra) {
     bcnn_destroy_data_loader(net);
-    if (type == BCNN_LOAD_DETECTION_LIST || (int)type < 0 || (int)type >= BCNN_NUM_LOADERS) {
+    int detector = bcnn_get_detector_training(net); /* or a net that already holds a head (bcnn-cl in PREDICT / VALID mode) */
+    for (int i = 0; !detector && i < net->num_nodes; ++i) detector = net->nodes[i].type == BCNN_LAYER_YOLOV3;
+    if ((type == BCNN_LOAD_DETECTION_LIST && !detector) || (int)type < 0 || (int)type >= BCNN_NUM_LOADERS) {
         bcnn_log(net->log_ctx, BCNN_LOG_ERROR,
                  "bcnn_set_data_loader: the detection-list format belongs to the YOLO head, which is outside the MI355X "
                  "hot-path build (see INTEGRATION.md)\n");
@@ -691,6 +796,7 @@ bcnn_status bcnn_set_data_loader(bcnn_net *net, bcnn_loader_type type, const cha
     switch (type) {
         case BCNN_LOAD_MNIST: st = mnist_init(it, net, train_path_data, train_path_extra, test_path_data, test_path_extra); break;
         case BCNN_LOAD_CIFAR10: st = cifar10_init(it, net, train_path_data, train_path_extra, test_path_data, test_path_extra); break;
+        case BCNN_LOAD_DETECTION_LIST: st = list_detection_init(it, net, train_path_data, train_path_extra, test_path_data, test_path_extra); break;
         default: st = list_init(it, net, train_path_data, train_path_extra, test_path_data, test_path_extra); break;
     }
     if (st != BCNN_SUCCESS) bcnn_destroy_data_loader(net); /* no half-opened loader for a later bcnn_loader_next to trip over */
@@ -712,6 +818,7 @@ bcnn_status bcnn_loader_next(bcnn_net *net) {
                 case BCNN_LOAD_MNIST: st = mnist_next(it, net, i); break;
                 case BCNN_LOAD_CIFAR10: st = cifar10_next(it, net, i); break;
                 case BCNN_LOAD_CLASSIFICATION_LIST: st = list_classif_next(it, net, i); break;
+                case BCNN_LOAD_DETECTION_LIST: st = list_detection_next(it, net, i); break;
                 default: st = list_reg_next(it, net, i); break;
             }
             if (st != BCNN_SUCCESS) {

@@ -172,6 +172,7 @@ typedef struct bcnn_hip_context {
     int inference_precision; /* bcnn_set_inference_precision (a bcnn_precision); read by the convolution node outside TRAIN mode */
     int loader_on_device; /* bcnn_set_loader_on_device: bcnn_loader_next makes the input batch with bcnn_hip_augment_batch */
     void *loader_stage;   /* its host-side gather block (bcnn_data.c: loader_stage); freed by bcnn_free_loader_stage */
+    int detector_training; /* bcnn_set_detector_training: YOLO heads may be built on / switched to TRAIN, with their loss */
     int detect_capacity; /* 1.25 x the most boxes an image of the latest bcnn_yolo_get_detections_batch had: the next call's record capacity
                           * when above the default (0: never called) */
 } bcnn_hip_context;
@@ -428,7 +429,13 @@ typedef struct bcnn_yolo_param {
     int num, classes, coords, total;
     int *mask;      /* num anchor indices of this head */
     float *biases;  /* host: total * 2 anchor extents (w, h) in input pixels */
-    float *cost;
+    float *cost;    /* cost[0]: sum of the squared deltas of the latest TRAIN forward, as bcnn_yolo_get_train_stats last read it */
+    int max_boxes, truths; /* detector training: BCNN_DETECTION_MAX_BOXES and floats per image of the label (0: built without) */
+#ifdef BCNN_USE_HIP
+    void *train_record_gpu;     /* bcnn_hip_yolo_train_record of the latest TRAIN forward */
+    float *train_workspace_gpu; /* bcnn_hip_yolo_train_workspace_size floats, the node's own */
+    size_t train_workspace_size;
+#endif
 } bcnn_yolo_param;
 
 /* hot-path node workers (installed into bcnn_node) */
@@ -469,6 +476,10 @@ void bcnn_backward_upsample_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_forward_yolo_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_yolo_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_yolo_layer(bcnn_node *node);
+/* bcnn_layers_detect.c: 1 when every head of the net can run its TRAIN forward (label and gradient buffers) */
+int bcnn_yolo_heads_trainable(bcnn_net *net);
+/* reads every head's record back (one small copy each) into param->cost[0]; returns the number of heads */
+int bcnn_yolo_refresh_costs(bcnn_net *net);
 /* bcnn_yolo_get_detections_batch with its capacities exposed (bcnn_layers_detect.c; exported for the tests) */
 bcnn_status bcnn_yolo_detections_batch_worker(bcnn_net *net, const int *widths, const int *heights, int netw, int neth,
                                               float thresh, int relative, int record_cap, int nms_cap,

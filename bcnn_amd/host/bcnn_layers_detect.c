@@ -4,8 +4,11 @@
  *
  * Reference behaviour: bcnn_concat_layer.c:33-146, bcnn_upsample_layer.c:28-147, bcnn_yolo.c:15-107, 207-215, 417-468,
  * 470-639. Deliberate deviations:
- *   - the YOLO head runs in PREDICT / VALID nets only: its training loss (and the detection-list loader it needs) is not
- *     built, so bcnn_add_yolo_layer on a TRAIN net and bcnn_set_mode(TRAIN) on a net holding a head are refused;
+ *   - detector training is opt-in (bcnn_set_detector_training, INI train_detector=1): without the switch
+ *     bcnn_add_yolo_layer on a TRAIN net and bcnn_set_mode(TRAIN) on a net holding a head are refused, as before the
+ *     loss was built; with it the head's TRAIN forward (bcnn_yolo.c:250-415) runs on the device, the per-step
+ *     statistics line is not printed (bcnn_yolo_get_train_stats reads them on demand), and a truth whose cell or class
+ *     lies outside the head is skipped where the reference writes out of bounds;
  *   - bcnn_yolo_get_detections prints nothing per box and sizes `prob` from the classes of the YOLO nodes (the
  *     reference reads them from the LAST node of the net, right only when that node is a head);
  *   - a head whose mask names an anchor outside [0, total) is refused (the reference reads past its anchor table).
@@ -132,7 +135,8 @@ bcnn_status bcnn_add_yolo_layer(bcnn_net *net, int num_boxes_per_cell, int class
                                 float *anchors, const char *src_id, const char *dst_id) {
     BCNN_CHECK_AND_LOG(net->log_ctx, net->num_nodes >= 1, BCNN_INVALID_PARAMETER,
                        "Yolo layer can't be the first layer of the network\n");
-    BCNN_CHECK_AND_LOG(net->log_ctx, net->mode != BCNN_MODE_TRAIN, BCNN_INVALID_PARAMETER,
+    const int train_detector = bcnn_get_detector_training(net);
+    BCNN_CHECK_AND_LOG(net->log_ctx, net->mode != BCNN_MODE_TRAIN || train_detector, BCNN_INVALID_PARAMETER,
                        "Yolo layer: the TRAIN-mode loss of the YOLO head is not built (PREDICT / VALID nets only)\n");
     const int idx = bcnn_net_find_tensor(net, src_id);
     BCNN_CHECK_AND_LOG(net->log_ctx, idx >= 0, BCNN_INVALID_PARAMETER, "Yolo layer: invalid input node name %s\n", src_id);
@@ -142,6 +146,22 @@ bcnn_status bcnn_add_yolo_layer(bcnn_net *net, int num_boxes_per_cell, int class
     for (int i = 0; mask && i < num_boxes_per_cell; ++i)
         BCNN_CHECK_AND_LOG(net->log_ctx, mask[i] >= 0 && mask[i] < total, BCNN_INVALID_PARAMETER,
                            "Yolo layer: mask entry %d names anchor %d of %d\n", i, mask[i], total);
+    if (train_detector) { /* what the device loss takes (include/bcnn_hip.h), and the label tensor every head shares */
+        BCNN_CHECK_AND_LOG(net->log_ctx,
+                           coords == 4 && num_boxes_per_cell >= 1 && num_boxes_per_cell <= BCNN_HIP_YOLO_MAX_ANCHORS &&
+                               total >= 1 && total <= BCNN_HIP_YOLO_TRAIN_MAX_TOTAL && mask,
+                           BCNN_INVALID_PARAMETER,
+                           "Yolo layer: detector training needs coords = 4, a mask of 1 to %d anchors and 1 to %d anchors in all\n",
+                           BCNN_HIP_YOLO_MAX_ANCHORS, BCNN_HIP_YOLO_TRAIN_MAX_TOTAL);
+        bcnn_tensor *label = &net->tensors[1];
+        if (label->data == NULL) { /* reference bcnn_yolo.c:68-73 (there: outside PREDICT mode only) */
+            bcnn_tensor_set_shape(label, s.n, 1, 1, BCNN_DETECTION_MAX_BOXES * 5, 0);
+            BCNN_CHECK_STATUS(bcnn_tensor_allocate(label, net->mode));
+        }
+        BCNN_CHECK_AND_LOG(net->log_ctx, label->n >= s.n && bcnn_tensor_size3d(label) >= BCNN_DETECTION_MAX_BOXES * 5,
+                           BCNN_INVALID_PARAMETER, "Yolo layer: the label tensor holds %d x %d floats, a detector needs %d x %d\n",
+                           label->n, bcnn_tensor_size3d(label), s.n, BCNN_DETECTION_MAX_BOXES * 5);
+    }
     bcnn_node node = {0};
     bcnn_node_add_input(net, &node, idx);
     node.type = BCNN_LAYER_YOLOV3;
@@ -158,6 +178,10 @@ bcnn_status bcnn_add_yolo_layer(bcnn_net *net, int num_boxes_per_cell, int class
     for (int i = 0; i < 2 * total; ++i) param->biases[i] = 0.5f;
     if (anchors) memcpy(param->biases, anchors, (size_t)(2 * total) * sizeof(float));
     param->cost = (float *)calloc(1, sizeof(float));
+    if (train_detector) {
+        param->max_boxes = BCNN_DETECTION_MAX_BOXES;
+        param->truths = param->max_boxes * (coords + 1);
+    }
     node.forward = bcnn_forward_yolo_layer;
     node.backward = bcnn_backward_yolo_layer;
     node.release_param = bcnn_release_param_yolo_layer;
@@ -167,9 +191,54 @@ bcnn_status bcnn_add_yolo_layer(bcnn_net *net, int num_boxes_per_cell, int class
     return BCNN_SUCCESS;
 }
 
-void bcnn_forward_yolo_layer(bcnn_net *net, bcnn_node *node) {
+/* what bcnn_hip_yolo_train_forward needs of a head; 0 when the head cannot train (built without the switch, no label or
+ * gradient buffer) */
+static int yolo_train_head(const bcnn_net *net, const bcnn_node *node, bcnn_hip_yolo_train_head *hd) {
     const bcnn_yolo_param *p = (const bcnn_yolo_param *)node->param;
+    const bcnn_tensor *y = &net->tensors[node->dst[0]], *label = &net->tensors[1];
+    if (p->truths <= 0 || !label->data_gpu || label->n < y->n || bcnn_tensor_size3d(label) < p->truths || !y->grad_data_gpu)
+        return 0;
+    memset(hd, 0, sizeof(*hd));
+    hd->n = y->n; hd->h = y->h; hd->w = y->w;
+    hd->num = p->num; hd->coords = p->coords; hd->classes = p->classes; hd->total = p->total;
+    hd->in_w = net->tensors[0].w; hd->in_h = net->tensors[0].h;
+    hd->label_stride = bcnn_tensor_size3d(label);
+    for (int i = 0; i < p->num; ++i) hd->mask[i] = p->mask[i];
+    memcpy(hd->biases, p->biases, (size_t)(2 * p->total) * sizeof(float));
+    return 1;
+}
+
+int bcnn_yolo_heads_trainable(bcnn_net *net) {
+    bcnn_hip_yolo_train_head hd;
+    for (int i = 0; i < net->num_nodes; ++i)
+        if (net->nodes[i].type == BCNN_LAYER_YOLOV3 && !yolo_train_head(net, &net->nodes[i], &hd)) return 0;
+    return 1;
+}
+
+void bcnn_forward_yolo_layer(bcnn_net *net, bcnn_node *node) {
+    bcnn_yolo_param *p = (bcnn_yolo_param *)node->param;
     bcnn_tensor *x = &net->tensors[node->src[0]], *y = &net->tensors[node->dst[0]];
+    if (net->mode == BCNN_MODE_TRAIN) { /* reference bcnn_yolo.c:250-415, on the device; the statistics stay there */
+        bcnn_hip_yolo_train_head hd;
+        if (!yolo_train_head(net, node, &hd)) { /* bcnn_set_mode and the builder refuse such a net */
+            fprintf(stderr, "[bcnn] YOLO head %s: TRAIN forward without a label or gradient buffer\n", y->name);
+            exit(1);
+        }
+        const size_t need = bcnn_hip_yolo_train_workspace_size(&hd);
+        if (p->train_workspace_size < need) { /* first TRAIN forward */
+            bcnn_hip_sync();
+            bcnn_hip_free(p->train_workspace_gpu);
+            p->train_workspace_gpu = bcnn_hip_malloc_f32(need);
+            p->train_workspace_size = need;
+        }
+        if (!p->train_record_gpu) p->train_record_gpu = bcnn_hip_malloc_f32(sizeof(bcnn_hip_yolo_train_record) / sizeof(float));
+        if (bcnn_hip_yolo_train_forward(&hd, x->data_gpu, net->tensors[1].data_gpu, y->data_gpu, y->grad_data_gpu,
+                                        (bcnn_hip_yolo_train_record *)p->train_record_gpu, p->train_workspace_gpu) != 0) {
+            fprintf(stderr, "[bcnn] YOLO head %s: shape outside the device loss\n", y->name);
+            exit(1);
+        }
+        return;
+    }
     bcnn_hip_yolo_activate(x->data_gpu, y->data_gpu, y->n, p->num, p->coords, p->classes, y->h * y->w);
 }
 
@@ -184,6 +253,45 @@ void bcnn_release_param_yolo_layer(bcnn_node *node) {
     free(p->mask);
     free(p->biases);
     free(p->cost);
+    bcnn_hip_free(p->train_record_gpu);
+    bcnn_hip_free(p->train_workspace_gpu);
+}
+
+/* The reference prints these on every TRAIN forward (bcnn_yolo.c:408-414), which here would cost a synchronisation per
+ * head and step: the sums stay in a 32-byte device record and are read, and divided as there, on demand. */
+static bcnn_status yolo_read_stats(bcnn_net *net, bcnn_node *node, bcnn_yolo_train_stats *out) {
+    bcnn_yolo_param *p = (bcnn_yolo_param *)node->param;
+    const bcnn_tensor *y = &net->tensors[node->dst[0]];
+    bcnn_hip_yolo_train_record rec;
+    memset(&rec, 0, sizeof(rec));
+    if (p->train_record_gpu) bcnn_hip_memcpy_d2h(&rec, p->train_record_gpu, sizeof(rec));
+    p->cost[0] = rec.cost;
+    if (!out) return BCNN_SUCCESS;
+    out->avg_iou = rec.avg_iou / rec.count;
+    out->avg_class = rec.avg_cat / rec.count;
+    out->avg_obj = rec.avg_obj / rec.count;
+    out->avg_anyobj = rec.avg_anyobj / (y->w * y->h * p->num * y->n);
+    out->recall50 = rec.recall / rec.count;
+    out->recall75 = rec.recall75 / rec.count;
+    out->count = rec.count;
+    out->cost = rec.cost;
+    return BCNN_SUCCESS;
+}
+
+bcnn_status bcnn_yolo_get_train_stats(bcnn_net *net, int node_index, bcnn_yolo_train_stats *out) {
+    if (!net || !out || node_index < 0 || node_index >= net->num_nodes || net->nodes[node_index].type != BCNN_LAYER_YOLOV3)
+        return BCNN_INVALID_PARAMETER;
+    return yolo_read_stats(net, &net->nodes[node_index], out);
+}
+
+int bcnn_yolo_refresh_costs(bcnn_net *net) {
+    int heads = 0;
+    for (int i = 0; i < net->num_nodes; ++i)
+        if (net->nodes[i].type == BCNN_LAYER_YOLOV3) {
+            yolo_read_stats(net, &net->nodes[i], NULL);
+            ++heads;
+        }
+    return heads;
 }
 
 /* ================================================================================================

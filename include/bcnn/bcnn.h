@@ -315,8 +315,9 @@ BCNN_API bcnn_precision bcnn_get_inference_precision(const bcnn_net *net);
  * bcnn_get_tensor_by_index / bcnn_download_tensor refresh it from the device as usual. A scale draw that leaves an
  * extent below 1 pixel leaves the sample unscaled, as the host path does. A batch goes the host way regardless when the
  * input tensor has more than 4 channels or no device buffer, or an MNIST / CIFAR-10 record does not match the input's
- * channels. May be called before or after bcnn_set_data_loader / bcnn_compile_net and between batches; without a loader
- * it has no effect. A NULL net returns BCNN_INVALID_PARAMETER. Config files: `loader_on_device=1` in the [net] section. */
+ * channels, and always for BCNN_LOAD_DETECTION_LIST. May be called before or after bcnn_set_data_loader /
+ * bcnn_compile_net and between batches; without a loader it has no effect. A NULL net returns BCNN_INVALID_PARAMETER.
+ * Config files: `loader_on_device=1` in the [net] section. */
 BCNN_API bcnn_status bcnn_set_loader_on_device(bcnn_net *net, int on);
 BCNN_API int bcnn_get_loader_on_device(const bcnn_net *net);
 /* Detections of EVERY image of the batch from the latest forward, in one call. widths[b] / heights[b]: the original
@@ -339,6 +340,32 @@ BCNN_API bcnn_status bcnn_yolo_get_detections_batch(bcnn_net *net, const int *wi
                                                     int neth, float thresh, int relative,
                                                     bcnn_output_detection **dets, int *num_dets);
 BCNN_API void bcnn_free_detections(bcnn_output_detection *dets, int num_dets); /* prob, mask and the array */
+/* Detector training (default 0: off, and then nothing below applies -- bcnn_add_yolo_layer on a TRAIN net,
+ * bcnn_set_mode(TRAIN) on a net with a head and BCNN_LOAD_DETECTION_LIST on a net without one are refused). With on != 0:
+ *   - bcnn_add_yolo_layer is accepted on a TRAIN net; in any mode it shapes tensors[1] (the label) as
+ *     n x 1 x 1 x (BCNN_DETECTION_MAX_BOXES * 5) and allocates it when it has no data yet: per image up to 50 truths
+ *     x, y, w, h, class (centre and extent relative to the input), the list ending at the first x == 0. Such a head
+ *     needs coords = 4, a mask of at most 16 anchors and at most 32 anchors in all;
+ *   - bcnn_set_mode(TRAIN) is accepted on a net whose heads were all built with the switch on and have gradient
+ *     buffers (a net built in PREDICT mode has none and is still refused);
+ *   - bcnn_set_data_loader(BCNN_LOAD_DETECTION_LIST) is accepted (also, without the switch, on a net that holds a head);
+ *   - a TRAIN-mode forward of a head computes the YOLOv3 loss gradient of the reference (bcnn_yolo.c:250-415) into the
+ *     head's output gradient on the device, bcnn_backward carries it on, and bcnn_train_on_batch counts every
+ *     head's cost in its return value next to the cost nodes (the mean over all of them, as in the reference).
+ * Set it before the heads are built. Config files: `train_detector=1` in the [net] section. A NULL net returns
+ * BCNN_INVALID_PARAMETER (the getter: 0). */
+BCNN_API bcnn_status bcnn_set_detector_training(bcnn_net *net, int on);
+BCNN_API int bcnn_get_detector_training(const bcnn_net *net);
+/* The statistics the reference prints on every TRAIN forward of a head ("Yolo Avg IOU: ..."), read on demand instead:
+ * one 32-byte copy from the device, divided as there (a batch without an assigned truth gives 0 / 0 for the averages
+ * over count). node_index: a YOLO node that has run a TRAIN forward (before one: zeros). Also refreshes the cost the
+ * head reports to bcnn_train_on_batch. BCNN_INVALID_PARAMETER for a NULL net / out or a node that is no YOLO head. */
+typedef struct bcnn_yolo_train_stats {
+    float avg_iou, avg_class, avg_obj, avg_anyobj, recall50, recall75;
+    int count;  /* truths that were assigned to an anchor of this head */
+    float cost; /* sum of the squared elements of the head's output gradient */
+} bcnn_yolo_train_stats;
+BCNN_API bcnn_status bcnn_yolo_get_train_stats(bcnn_net *net, int node_index, bcnn_yolo_train_stats *out);
 /* Run ONE node's forward / backward worker on whatever its tensors currently hold (no executor bookkeeping:
  * no zero fill of the dst gradients, no dead-fill elision -- a sole-writer gradient is accumulated like in the
  * reference). Used by the teacher-forced parity walk, which feeds every node the REFERENCE's inputs. */

@@ -609,6 +609,41 @@ int bcnn_hip_yolo_detect_batch(const bcnn_hip_yolo_head *heads, int num_heads, i
                                int record_cap, int nms_cap, void *result_host);
 
 /* ---------------------------------------------------------------------------------------------
+ * TRAIN-mode forward of the YOLOv3 head (bcnn_yolo.c:226-415; a host loop in the reference, behind a read-back of the
+ * head, in its CUDA build too). Four launches on the current stream, no atomics, every sum a fixed-order tree:
+ *   forward : a lane per predicted box (image, anchor, cell). y = the activation of yolo_activate; EVERY element of
+ *             grad is written: objectness gets y, or 0 when the best box_iou against the image's truths is > 0.5,
+ *             everything else 0 (the reference's memset). The truths of an image are label_d[b * label_stride + 5 t ..]
+ *             = x, y, w, h, class, t < BCNN_HIP_YOLO_TRAIN_MAX_TRUTHS; the list ends at the first x == 0.
+ *   truths  : one wave per image, the truths in order: best anchor of all `total` against the truth at the origin
+ *             (strict >, first wins); when `mask` holds it, the four box deltas (scale 2 - w h), the objectness delta
+ *             y - 1 and the class deltas of delta_yolo_class, which depend on what an earlier truth left in the same
+ *             slot. A truth whose cell (int)(x w), (int)(y h) or class lies outside the head is skipped as a whole
+ *             (the reference writes out of bounds there); it still takes part in `forward`.
+ *   cost    : sum of grad^2 over the head, then one block folds it and the statistics partials into *record_d: the
+ *             SUMS the reference divides before printing (avg_iou .. recall75 by count, avg_anyobj by n num h w).
+ * Writes y_d, grad_d, *record_d and workspace_d only. coords must be 4, num <= BCNN_HIP_YOLO_MAX_ANCHORS, total <=
+ * BCNN_HIP_YOLO_TRAIN_MAX_TOTAL, label_stride >= 5 * BCNN_HIP_YOLO_TRAIN_MAX_TRUTHS: otherwise 1 is returned and nothing
+ * is queued (workspace_size: 0). biases: the extents (w, h) of all `total` anchors in input pixels.
+ * ------------------------------------------------------------------------------------------- */
+#define BCNN_HIP_YOLO_TRAIN_MAX_TRUTHS 50
+#define BCNN_HIP_YOLO_TRAIN_MAX_TOTAL 32
+typedef struct bcnn_hip_yolo_train_head {
+    int n, h, w, num, coords, classes, total;
+    int in_w, in_h;   /* extent of the net's input tensor */
+    int label_stride; /* floats per image of label_d */
+    int mask[BCNN_HIP_YOLO_MAX_ANCHORS];
+    float biases[2 * BCNN_HIP_YOLO_TRAIN_MAX_TOTAL];
+} bcnn_hip_yolo_train_head;
+typedef struct bcnn_hip_yolo_train_record {
+    float cost, avg_iou, avg_cat, avg_obj, avg_anyobj, recall, recall75;
+    int count;
+} bcnn_hip_yolo_train_record;
+size_t bcnn_hip_yolo_train_workspace_size(const bcnn_hip_yolo_train_head *head); /* floats */
+int bcnn_hip_yolo_train_forward(const bcnn_hip_yolo_train_head *head, const float *x_d, const float *label_d, float *y_d,
+                                float *grad_d, bcnn_hip_yolo_train_record *record_d, float *workspace_d);
+
+/* ---------------------------------------------------------------------------------------------
  * The input tensor of a batch from raw uint8 images (image_fill.hip): entries 0 .. num_images - 1 of the NCHW float
  * tensor dst_d [n][c][h][w]; entries num_images .. n - 1 are not written. images / widths / heights / strides are HOST
  * arrays of num_images entries: interleaved HWC uint8 pixels, extent in pixels, row pitch in bytes (strides NULL:

@@ -12,6 +12,10 @@ and bcnn_fill_tensor_with_image (which uploads the whole tensor each time) again
 ended by bcnn_synchronize, wall clock, three alternating repeats; the raw record goes to --out (default
 profiles/input_fill_n32.json).
     python tools/exp/yolo_tiny_time.py --pre
+--train: instead, one training step of yolov3-tiny at N = 32 with detector training on (bcnn_set_detector_training): eight
+truths per image, forward + backward + SGD update on device events, and the TRAIN forward of the two heads alone
+(bcnn_forward_node); the raw record goes to --out (default profiles/detect_train_step_n32.json).
+    python tools/exp/yolo_tiny_time.py --train
 Under rocprofv3:  rocprofv3 --kernel-trace --stats -d <dir> -- python tools/exp/yolo_tiny_time.py"""
 import argparse
 import json
@@ -315,18 +319,68 @@ def pre(L, reps, tmp, n, out_path, fw=640, fh=480):
     print(json.dumps(res))
 
 
+def train(L, reps, tmp, n, out_path):
+    """one SGD step of yolov3-tiny at N = n, and the share of the heads' TRAIN forward in it"""
+    cfg = os.path.join(tmp, "tiny_train%d.cfg" % n)
+    with open(cfg, "w") as fp:
+        fp.write(tiny_cfg(batch=n).replace("[net]\n", "[net]\ntrain_detector=1\n", 1))
+    model = os.path.join(tmp, "tiny.weights")
+    if not os.path.exists(model):
+        write_tiny_weights(model)
+    net = capi.Net.load_net(cfg, model, capi.MODE_TRAIN)
+    net.compile()
+    net.set_sgd(1e-5, 0.9, 5e-4)
+    rs = np.random.RandomState(0)
+    net.data(0)[...] = rs.uniform(0, 1, net.shape(0)).astype(np.float32)
+    net.upload(0)
+    lab = np.zeros((n, 50, 5), np.float32)
+    lab[:, :8, 0:2] = rs.uniform(0.05, 0.95, (n, 8, 2))
+    lab[:, :8, 2:4] = rs.uniform(0.03, 0.6, (n, 8, 2))
+    lab[:, :8, 4] = rs.randint(0, 80, (n, 8))
+    net.data(1)[...] = lab.reshape(net.shape(1))
+    net.upload(1)
+    heads = []
+    stats = capi.YoloTrainStats()
+    for node in range(net.num_nodes):
+        if net.L.bcnn_yolo_get_train_stats(net.net, node, C.byref(stats)) == 0:
+            heads.append(node)
+
+    def step():
+        net.forward()
+        net.backward()
+        net.update()
+
+    step_ms = timed(L, step, reps)
+    fwd_ms = timed(L, net.forward, reps)
+    heads_ms = timed(L, lambda: [net.forward_node(h) for h in heads], reps)
+    got = [net.yolo_train_stats(h) for h in heads]
+    net.close()
+    rec = dict(device=torch.cuda.get_device_name(0), n=n, reps=reps, step_ms=step_ms, forward_ms=fwd_ms,
+               heads_train_forward_ms=heads_ms, heads=len(heads), truths_assigned=[g["count"] for g in got])
+    print("yolov3-tiny 416x416 TRAIN N=%d: step %.3f ms (%.0f img/s), forward %.3f ms, TRAIN forward of the %d heads %.3f ms"
+          % (n, step_ms, n / step_ms * 1e3, fwd_ms, len(heads), heads_ms))
+    with open(out_path, "w") as fp:
+        json.dump(rec, fp, indent=1)
+    print(json.dumps(rec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--post", action="store_true", help="time the detection post-processing after the N = 32 forward")
     ap.add_argument("--candidates", type=int, default=300, help="--post: candidates per image the threshold leaves")
     ap.add_argument("--pre", action="store_true", help="time the input fill before the N = 32 forward")
-    ap.add_argument("--out", default=None, help="--post / --pre: where the raw record goes")
+    ap.add_argument("--train", action="store_true", help="time one training step of yolov3-tiny at N = 32")
+    ap.add_argument("--out", default=None, help="--post / --pre / --train: where the raw record goes")
     args = ap.parse_args()
     L = _lib.load()
     if args.pre:
         with tempfile.TemporaryDirectory() as tmp:
             pre(L, args.reps, tmp, 32, args.out or os.path.join(ROOT, "profiles", "input_fill_n32.json"))
+        return
+    if args.train:
+        with tempfile.TemporaryDirectory() as tmp:
+            train(L, args.reps, tmp, 32, args.out or os.path.join(ROOT, "profiles", "detect_train_step_n32.json"))
         return
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", "detect_postprocess_n32.json")
