@@ -86,6 +86,7 @@ __global__ __launch_bounds__(256) void maxpool_fwd_s2_kernel(const float* __rest
 // whose pre-normalisation output x is kept anyway (the ResNet stem). The normalised tensor -- four times the size of the
 // pooled one -- is then never written nor read back. Values, scan order and indexes are those of bn apply + the kernel
 // above (same bn_one arithmetic per element).
+#ifdef BCNN_HIP_EXPERIMENT  // reachable with BCNN_HIP_POOL_PAIR_V1: the reference of the second generation below
 template <int SIZE, int R>  // R consecutive output rows per thread: their 2R + SIZE - 2 source rows are normalised once each
 __global__ __launch_bounds__(256) void maxpool_fwd_s2_bn_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                                 int* __restrict__ idx, int C, int H, int W, int OH, int OW,
@@ -153,6 +154,152 @@ __global__ __launch_bounds__(256) void maxpool_fwd_s2_bn_kernel(const float* __r
             if (keep) raw_at_max[out + 1] = braw[r][1];
         }
     }
+}
+#endif
+
+// ---- the same kernel, second generation: bound by memory instead of the vector ALU -----------------------------------------------
+// What changed against maxpool_fwd_s2_bn_kernel (kept in the experiment build as the bit-for-bit reference):
+//  * a row's fifth column (size 3) is the NEXT thread's first column: its raw and normalised values come over a DPP wave shift
+//    instead of a second load and a fifth bn_one. A wave therefore carries 63 items; lane 63 repeats the next wave's first
+//    item only to feed lane 62 and stores nothing (an instruction issued for one lane costs what it costs for 64, so a
+//    fetched fallback in lane 63 would give the saving back);
+//  * the activation is a template parameter, and the bcnn_scal / bcnn_add_scalar quirks are classified once per wave: unless
+//    a lane's channel has scale 0 or bias 1 the element is mul + add (x * 1.0f and x + -0.0f are identities bit for bit, so
+//    scale 1 and bias 0 need no select), otherwise the whole wave runs bn_one as before;
+//  * the three index divisions are multiply-high by constants from the host; 8-byte stores where the pairs are aligned.
+struct BnFwdCoef {
+    float m, sc, b, badd;  // badd: b, or -0.0f for b == 0 (the add the reference skips)
+    BnDiv rs;
+};
+template <int ACT, bool QUIRK>  // ACT < 0: the run-time `act`
+__device__ __forceinline__ float bn_fwd_t(float x, const BnFwdCoef& k, int act) {
+    const int a = ACT >= 0 ? ACT : act;
+    if (QUIRK) {
+        float dummy;
+        return bn_one(x, k.m, k.rs, k.sc, k.b, 0, a, &dummy);
+    }
+    const float v = __fadd_rn(__fmul_rn(bn_div(__fsub_rn(x, k.m), k.rs), k.sc), k.badd);
+    return act_fwd_cheap(v, a, 0.f);
+}
+// a / d by multiply-high with magic = ceil(2^32 / d): exact while a * d < 2^32; the host passes 0 where that does not hold
+__device__ __forceinline__ unsigned div_by(unsigned a, unsigned d, unsigned magic) { return magic ? __umulhi(a, magic) : a / d; }
+__device__ __forceinline__ float dpp_shl1(float old, float v) {  // lane i takes lane i + 1's value; lane 63 keeps `old`
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, old), __builtin_bit_cast(int, v),
+                                                                 0x130 /* wave_shl:1 */, 0xf, 0xf, false));
+}
+
+struct PoolBnFwdArgs {
+    const float* x; float* y; int* idx; float* raw_at_max;
+    const float *mean, *var, *scale, *bias;
+    int C, H, W, OH, OW, act, vec2;
+    unsigned total_items, ppr, rgs, ppr_magic, rgs_magic, c_magic;
+};
+
+template <int SIZE, int R, int ACT, bool QUIRK>
+__device__ __forceinline__ void maxpool_fwd_s2_bn_body(const PoolBnFwdArgs& a, const BnFwdCoef& k, int base, int w0, unsigned i0,
+                                                       unsigned q, unsigned out0, bool tail, bool self_tail, bool any_self, bool store,
+                                                       const float4 (&rows)[2 * R + SIZE - 2]) {
+    const float* __restrict__ x = a.x;
+    const int H = a.H, W = a.W;
+    const bool keep = a.raw_at_max != nullptr;  // uniform
+    float best[R][2], braw[R][2];
+    int bi[R][2];
+#pragma unroll
+    for (int r = 0; r < R; ++r) { best[r][0] = best[r][1] = -FLT_MAX; bi[r][0] = bi[r][1] = -1; braw[r][0] = braw[r][1] = 0.f; }
+#pragma unroll
+    for (int rr = 0; rr < 2 * R + SIZE - 2; ++rr) {
+        const int hh = (int)i0 * 2 + rr;
+        if (hh >= H) continue;  // bottom padding: the row never wins (a thread and its right neighbour agree on this)
+        const int rb = base + hh * W + w0;
+        const float4 v4 = rows[rr];
+        float raw[5] = {v4.x, v4.y, v4.z, v4.w, 0.f};
+        float v[5] = {bn_fwd_t<ACT, QUIRK>(raw[0], k, a.act), bn_fwd_t<ACT, QUIRK>(raw[1], k, a.act),
+                      bn_fwd_t<ACT, QUIRK>(raw[2], k, a.act), bn_fwd_t<ACT, QUIRK>(raw[3], k, a.act), -FLT_MAX};
+        if (SIZE == 3) {
+            float n4 = dpp_shl1(v[0], v[0]);
+            if (keep) raw[4] = dpp_shl1(raw[0], raw[0]);
+            if (any_self) {  // uniform; a pair that needs a fifth column but ends its row (out_w below the natural size)
+                if (self_tail) {
+                    raw[4] = x[rb + 4];
+                    n4 = bn_fwd_t<ACT, QUIRK>(raw[4], k, a.act);
+                }
+            }
+            v[4] = tail ? n4 : -FLT_MAX;
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int kr = rr - 2 * r;  // window row of output row i0 + r; ascending rr == ascending kr: the scan order
+            if (kr < 0 || kr >= SIZE) continue;
+#pragma unroll
+            for (int o = 0; o < 2; ++o)
+#pragma unroll
+                for (int c = 0; c < SIZE; ++c) {
+                    const float val = v[2 * o + c];
+                    if (val > best[r][o]) {
+                        best[r][o] = val;
+                        bi[r][o] = rb + 2 * o + c;
+                        if (keep) braw[r][o] = raw[2 * o + c];
+                    }
+                }
+        }
+    }
+    if (!store) return;
+    const bool second = (int)(q * 2 + 1) < a.OW;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        if ((int)(i0 + r) >= a.OH) break;
+        const unsigned out = out0 + (unsigned)r * (unsigned)a.OW;
+        if (a.vec2) {
+            *reinterpret_cast<float2*>(a.y + out) = make_float2(best[r][0], best[r][1]);
+            *reinterpret_cast<int2*>(a.idx + out) = make_int2(bi[r][0], bi[r][1]);
+            // the pre-normalisation value that won: what the backward pass needs of x at the only places where the pooled
+            // gradient lands (bcnn_hip_maxpool_bn_backward)
+            if (keep) *reinterpret_cast<float2*>(a.raw_at_max + out) = make_float2(braw[r][0], braw[r][1]);
+        } else {
+            a.y[out] = best[r][0];
+            a.idx[out] = bi[r][0];
+            if (keep) a.raw_at_max[out] = braw[r][0];
+            if (second) {
+                a.y[out + 1] = best[r][1];
+                a.idx[out + 1] = bi[r][1];
+                if (keep) a.raw_at_max[out + 1] = braw[r][1];
+            }
+        }
+    }
+}
+
+template <int SIZE, int R, int ACT>
+__global__ __launch_bounds__(256) void maxpool_fwd_s2_bn_v2_kernel(const PoolBnFwdArgs a) {
+    constexpr unsigned LANES = SIZE == 3 ? 63u : 64u;  // items per wave
+    const unsigned lane = threadIdx.x & 63u;
+    const unsigned t = (blockIdx.x * 4u + (threadIdx.x >> 6)) * LANES + lane;
+    const bool store = lane < LANES && t < a.total_items;
+    const unsigned tt = t < a.total_items ? t : a.total_items - 1u;  // no early return: the wave shift wants every lane
+    const unsigned rowid = div_by(tt, a.ppr, a.ppr_magic), q = tt - rowid * a.ppr;
+    const unsigned plane = div_by(rowid, a.rgs, a.rgs_magic), i0 = (rowid - plane * a.rgs) * R;
+    const int ch = (int)(plane - div_by(plane, (unsigned)a.C, a.c_magic) * (unsigned)a.C);
+    BnFwdCoef k;
+    k.m = a.mean[ch]; k.sc = a.scale[ch]; k.b = a.bias[ch];
+    k.badd = k.b == 0.0f ? -0.0f : k.b;
+    k.rs = bn_divisor(sqrtf(a.var[ch] + 0.000001f));
+    const int base = (int)plane * a.H * a.W;
+    const int w0 = (int)q * 4;
+    const bool tail = SIZE == 3 && w0 + 4 < a.W;
+    const bool self_tail = tail && q + 1 >= a.ppr;  // the next thread is not this row's next pair
+    const bool any_self = __ballot(self_tail) != 0;
+    const bool quirk = k.sc == 0.0f || k.b == 1.0f;
+    const unsigned out0 = (plane * (unsigned)a.OH + i0) * (unsigned)a.OW + q * 2;
+    // every source row's 16 bytes first, from row-clamped addresses and ahead of the branch on the channel's constants: behind
+    // the per-row `hh >= H` test each load would wait for the row before it -- 2R + SIZE - 2 memory round trips in a chain
+    // instead of as many loads in flight
+    float4 rows[2 * R + SIZE - 2];
+#pragma unroll
+    for (int rr = 0; rr < 2 * R + SIZE - 2; ++rr) {
+        const int hh = (int)i0 * 2 + rr;
+        rows[rr] = *reinterpret_cast<const float4*>(a.x + base + (hh < a.H ? hh : a.H - 1) * a.W + w0);
+    }
+    if (__ballot(quirk) != 0) maxpool_fwd_s2_bn_body<SIZE, R, ACT, true>(a, k, base, w0, i0, q, out0, tail, self_tail, any_self, store, rows);
+    else maxpool_fwd_s2_bn_body<SIZE, R, ACT, false>(a, k, base, w0, i0, q, out0, tail, self_tail, any_self, store, rows);
 }
 
 // Gather form of `dx[idx[o]] += dy[o]`: one thread per SOURCE element visits the (at most
@@ -323,6 +470,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_vec4_k3s2_pair_kernel(const f
 // values while they are in registers: dx[s] = bn_bwd(sum of the pooled gradients that selected s) is written straight into
 // the convolution node's output-gradient tensor, which is then never written and re-read in its pooled-gradient form. The
 // coefficients (dmean, dvar) come from sums taken over the POOLED tensors (bcnn_hip_maxpool_bn_backward below).
+#ifdef BCNN_HIP_EXPERIMENT  // reachable with BCNN_HIP_POOL_PAIR_V1
 __global__ __launch_bounds__(256) void maxpool_bwd_pair_bn_kernel(const float* __restrict__ dy, const int* __restrict__ idx,
                                                                   const float* __restrict__ raw, float* __restrict__ dx,
                                                                   int C, int H, int W, int OH, int OW,
@@ -383,6 +531,108 @@ __global__ __launch_bounds__(256) void maxpool_bwd_pair_bn_kernel(const float* _
     o.z = bn_bwd_one(v.z, bn_one(xv.z, m, rs_fwd, sc, bb, 0, act, &dummy), xv.z, m, rs, sc, dmm, dv, fMd, act);
     o.w = bn_bwd_one(v.w, bn_one(xv.w, m, rs_fwd, sc, bb, 0, act, &dummy), xv.w, m, rs, sc, dmm, dv, fMd, act);
     *reinterpret_cast<float4*>(dx + s0) = o;
+}
+#endif
+
+// ---- the same kernel, second generation (maxpool_bwd_pair_bn_kernel stays in the experiment build as the reference) ----------------
+//  * scatter: window column 2k-1 covers source columns 4k-2 .. 4k, column 2k covers 4k .. 4k+2 and column 2k+1 covers
+//    4k+2 .. 4k+4, so of the 6 x 4 (window, component) pairs only 2 x 6 can hit -- given indexes that lie inside their own
+//    windows, which is what every forward kernel here writes. Each is one compare, one select and one add: `v + +0.f` is v bit
+//    for bit (v starts at +0 and a sum is -0 only if both terms are), so a miss adds +0 instead of branching. Rows and
+//    neighbours that do not count are masked once, on the index (-1 matches no source element);
+//  * the channel is blockIdx.y: the activation is a template parameter and the bcnn_scal / bcnn_add_scalar quirks a uniform
+//    branch (scale 0 or bias 1 run the reference expression as before; `g * 1.0f` and `x + -0.0f` are identities);
+//  * ReLU and leaky ReLU: act'(y) asks only whether y > 0, and y > 0 exactly where the pre-activation value is > 0 (0.1f * v
+//    never rounds across zero), so the activation itself is not evaluated; no activation: no forward value at all.
+template <int ACT>  // ACT < 0: the run-time `act`
+__global__ __launch_bounds__(256) void maxpool_bwd_pair_bn_v2_kernel(const float* __restrict__ dy, const int* __restrict__ idx,
+                                                                     const float* __restrict__ raw, float* __restrict__ dx,
+                                                                     int C, int H, int W, int OH, int OW,
+                                                                     const float4* __restrict__ consts, unsigned w4_magic,
+                                                                     float fM, float rfM, int act_rt) {
+    const int act = ACT >= 0 ? ACT : act_rt;
+    const int W4 = W >> 2;
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    const int plane = blockIdx.y;
+    if ((int)(blockIdx.x * 256 + (threadIdx.x & ~63u)) >= H * W4) return;  // a whole wave past the plane (uniform)
+    const bool live = t < H * W4;
+    const int tt = live ? t : 0;
+    // tt / W4 by multiply-high with ceil(2^32 / W4) (exact: tt * W4 < 2^32, checked by the launcher)
+    const int h = W4 > 1 ? (int)__umulhi((unsigned)tt, w4_magic) : tt, k = tt - h * W4, w0 = k * 4;
+    const int s0 = (plane * H + h) * W + w0;
+    const int i0 = h >= 2 ? (h - 1) >> 1 : 0;
+    int i1 = h >> 1; if (i1 > OH - 1) i1 = OH - 1;
+    const bool need_left = k > 0, fetch_left = need_left && (threadIdx.x & 63) == 0;
+    const float4 xv = *reinterpret_cast<const float4*>(raw + s0);
+    int id[2][3], o[2], ie[2] = {-1, -1};
+    float g[2][3], ge[2] = {0.f, 0.f};
+    int2 ip[2];
+    float2 gp[2];
+    bool ok[2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        const int i = i0 + a;
+        ok[a] = live && i <= i1;
+        o[a] = (plane * OH + (i <= i1 ? i : i1)) * OW + 2 * k;
+        ip[a] = *reinterpret_cast<const int2*>(idx + o[a]);
+        gp[a] = *reinterpret_cast<const float2*>(dy + o[a]);
+    }
+    // window column 2k-1 of a wave's first lane: nobody to shift it from. One branch for both rows and ahead of the shifts, so
+    // that these loads go out with the others; the other lanes load nothing
+    if (fetch_left) {
+        ie[0] = idx[o[0] - 1]; ge[0] = dy[o[0] - 1];
+        ie[1] = idx[o[1] - 1]; ge[1] = dy[o[1] - 1];
+    }
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        // rows that do not count, masked on the index; the left neighbour is on this row: the same `ok`
+        ip[a].x = ok[a] ? ip[a].x : -1; ip[a].y = ok[a] ? ip[a].y : -1; ie[a] = ok[a] ? ie[a] : -1;
+        const int il = __builtin_amdgcn_update_dpp(ie[a], ip[a].y, 0x138 /* wave_shr:1 */, 0xf, 0xf, false);
+        id[a][0] = need_left ? il : -1;
+        g[a][0] = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, ge[a]), __builtin_bit_cast(int, gp[a].y),
+                                                                        0x138, 0xf, 0xf, false));
+        id[a][1] = ip[a].x; g[a][1] = gp[a].x;
+        id[a][2] = ip[a].y; g[a][2] = gp[a].y;
+    }
+    // no early return: behind one, the loads that feed no wave shift sink past the branch and queue up behind the first batch
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {  // per component: rows ascending, columns ascending -- the order of the gather kernels above
+        v.x += id[a][0] == s0 ? g[a][0] : 0.f;
+        v.x += id[a][1] == s0 ? g[a][1] : 0.f;
+        v.y += id[a][1] == s0 + 1 ? g[a][1] : 0.f;
+        v.z += id[a][1] == s0 + 2 ? g[a][1] : 0.f;
+        v.z += id[a][2] == s0 + 2 ? g[a][2] : 0.f;
+        v.w += id[a][2] == s0 + 3 ? g[a][2] : 0.f;
+    }
+    // per-channel constants: the table bn_bwd_finalize_kernel left (wave-uniform: scalar loads)
+    const int ch = plane % C;
+    const float4 k0 = consts[3 * ch], k1 = consts[3 * ch + 1], k2 = consts[3 * ch + 2];
+    const float m = k0.x, sc = k0.y, bb = k1.z, dmm = k1.w, dv = k2.x;
+    const BnDiv rs{k0.z, k0.w}, rs_fwd{k1.x, k1.y}, fMd{fM, rfM};
+    const float vin[4] = {v.x, v.y, v.z, v.w}, xin[4] = {xv.x, xv.y, xv.z, xv.w};
+    float out[4];
+    const bool fast_act = ACT == BCNN_HIP_ACT_NONE || ACT == BCNN_HIP_ACT_RELU || ACT == BCNN_HIP_ACT_LRELU;
+    if (!fast_act || sc == 0.0f || (ACT != BCNN_HIP_ACT_NONE && bb == 1.0f)) {  // uniform
+        float dummy;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            out[e] = bn_bwd_one(vin[e], bn_one(xin[e], m, rs_fwd, sc, bb, 0, act, &dummy), xin[e], m, rs, sc, dmm, dv, fMd, act);
+    } else {
+        const float dv2 = __fmul_rn(dv, 2.0f), badd = bb == 0.0f ? -0.0f : bb;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float xm = __fsub_rn(xin[e], m);
+            float gg = vin[e];
+            if (ACT != BCNN_HIP_ACT_NONE) {
+                const float pre = __fadd_rn(__fmul_rn(bn_div(xm, rs_fwd), sc), badd);
+                gg *= ACT == BCNN_HIP_ACT_RELU ? (float)(pre > 0) : (pre > 0 ? 1.0f : 0.1f);
+            }
+            gg = __fmul_rn(gg, sc);
+            out[e] = __fadd_rn(__fadd_rn(bn_div(gg, rs), bn_div(__fmul_rn(dv2, xm), fMd)), dmm);
+        }
+    }
+    if (live) *reinterpret_cast<float4*>(dx + s0) = make_float4(out[0], out[1], out[2], out[3]);
 }
 
 // Global average pooling: one wave64 per (n,c) plane, shuffle reduction, then / (H*W).
@@ -452,19 +702,53 @@ void bcnn_hip_maxpool_forward_bn_keep(const float* x, float* y, int* indexes, in
         fprintf(stderr, "[bcnn_hip] bcnn_hip_maxpool_forward_bn: not fusable (ask bcnn_hip_maxpool_bn_fusable)\n");
         exit(1);
     }
-    KTimer kt(K_POOL, 0.0, 4.0 * ((double)n * c * h * w + 2.0 * (double)total));
-    trace_kernel("maxpool_fwd_s2_bn_kernel");
+    // raw in; pooled values, indexes and (when kept) the raw values that won out
+    KTimer kt(K_POOL, 0.0, 4.0 * ((double)n * c * h * w + (raw_at_max ? 3.0 : 2.0) * (double)total));
     constexpr int R = 4;
     const long long items = (long long)n * c * ((out_h + R - 1) / R) * ((out_w + 1) / 2);
-    const unsigned blocks = (unsigned)((items + 255) / 256);
-    if (size == 2)
-        maxpool_fwd_s2_bn_kernel<2, R><<<blocks, 256, 0, current_stream()>>>(x, y, indexes, c, h, w, out_h, out_w,
-                                                                             (unsigned)items, mean, var, scales, bias, act,
-                                                                             raw_at_max);
-    else
-        maxpool_fwd_s2_bn_kernel<3, R><<<blocks, 256, 0, current_stream()>>>(x, y, indexes, c, h, w, out_h, out_w,
-                                                                             (unsigned)items, mean, var, scales, bias, act,
-                                                                             raw_at_max);
+#ifdef BCNN_HIP_EXPERIMENT
+    if (BCNN_EXP_ENV("BCNN_HIP_POOL_PAIR_V1")) {
+        trace_kernel("maxpool_fwd_s2_bn_kernel:v1");
+        const unsigned blocks = (unsigned)((items + 255) / 256);
+        if (size == 2)
+            maxpool_fwd_s2_bn_kernel<2, R><<<blocks, 256, 0, current_stream()>>>(x, y, indexes, c, h, w, out_h, out_w,
+                                                                                 (unsigned)items, mean, var, scales, bias, act,
+                                                                                 raw_at_max);
+        else
+            maxpool_fwd_s2_bn_kernel<3, R><<<blocks, 256, 0, current_stream()>>>(x, y, indexes, c, h, w, out_h, out_w,
+                                                                                 (unsigned)items, mean, var, scales, bias, act,
+                                                                                 raw_at_max);
+        KERNEL_CHECK();
+        return;
+    }
+#endif
+    trace_kernel("maxpool_fwd_s2_bn_kernel");  // the family name: both generations
+    PoolBnFwdArgs a;
+    a.x = x; a.y = y; a.idx = indexes; a.raw_at_max = raw_at_max;
+    a.mean = mean; a.var = var; a.scale = scales; a.bias = bias;
+    a.C = c; a.H = h; a.W = w; a.OH = out_h; a.OW = out_w; a.act = act;
+    const uintptr_t p8 = reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(indexes) | reinterpret_cast<uintptr_t>(raw_at_max);
+    a.vec2 = (out_w & 1) == 0 && (p8 & 7) == 0;
+    a.total_items = (unsigned)items;
+    a.ppr = (unsigned)((out_w + 1) / 2);
+    a.rgs = (unsigned)((out_h + R - 1) / R);
+    // multiply-high division (the kernel's div_by): exact while dividend * divisor < 2^32; every dividend is below `items`
+    auto magic = [items](unsigned d) {
+        return d > 1 && items * (long long)d < (1LL << 32) ? (unsigned)((0x100000000ULL + d - 1) / d) : 0u;
+    };
+    a.ppr_magic = magic(a.ppr); a.rgs_magic = magic(a.rgs); a.c_magic = magic((unsigned)c);
+    const unsigned per_block = size == 3 ? 4u * 63u : 256u;  // size 3: 63 items per wave (see the kernel)
+    const unsigned blocks = (unsigned)((items + per_block - 1) / per_block);
+#define BCNN_POOL_FWD_V2(SIZE, ACT) maxpool_fwd_s2_bn_v2_kernel<SIZE, R, ACT><<<blocks, 256, 0, current_stream()>>>(a)
+#define BCNN_POOL_FWD_V2_ACT(ACT) do { if (size == 2) BCNN_POOL_FWD_V2(2, ACT); else BCNN_POOL_FWD_V2(3, ACT); } while (0)
+    switch (act) {
+        case BCNN_HIP_ACT_NONE: BCNN_POOL_FWD_V2_ACT(BCNN_HIP_ACT_NONE); break;
+        case BCNN_HIP_ACT_RELU: BCNN_POOL_FWD_V2_ACT(BCNN_HIP_ACT_RELU); break;
+        case BCNN_HIP_ACT_LRELU: BCNN_POOL_FWD_V2_ACT(BCNN_HIP_ACT_LRELU); break;
+        default: BCNN_POOL_FWD_V2_ACT(-1); break;
+    }
+#undef BCNN_POOL_FWD_V2_ACT
+#undef BCNN_POOL_FWD_V2
     KERNEL_CHECK();
 }
 
@@ -511,10 +795,27 @@ void bcnn_hip_maxpool_bn_backward(const float* dpool, const int* indexes, const 
     KTimer kt(K_POOL, 0.0, 4.0 * (2.0 * (double)total + 2.0 * (double)ptotal));
     dim3 grid((unsigned)ceil_div(h * (w / 4), 256), (unsigned)(n * c));
     const unsigned w4 = (unsigned)(w / 4);
-    trace_kernel("maxpool_bwd_pair_bn_kernel");
-    maxpool_bwd_pair_bn_kernel<<<grid, 256, 0, current_stream()>>>(dpool, indexes, raw, dx, c, h, w, out_h, out_w, consts,
-                                                                   w4 > 1 ? (unsigned)((0x100000000ULL + w4 - 1) / w4) : 0u, fM,
-                                                                   1.0f / fM, act);
+    const unsigned w4m = w4 > 1 ? (unsigned)((0x100000000ULL + w4 - 1) / w4) : 0u;
+#ifdef BCNN_HIP_EXPERIMENT
+    if (BCNN_EXP_ENV("BCNN_HIP_POOL_PAIR_V1")) {
+        trace_kernel("maxpool_bwd_pair_bn_kernel:v1");
+        maxpool_bwd_pair_bn_kernel<<<grid, 256, 0, current_stream()>>>(dpool, indexes, raw, dx, c, h, w, out_h, out_w, consts, w4m,
+                                                                       fM, 1.0f / fM, act);
+        KERNEL_CHECK();
+        return;
+    }
+#endif
+    trace_kernel("maxpool_bwd_pair_bn_kernel");  // the family name: both generations
+#define BCNN_POOL_BWD_V2(ACT) \
+    maxpool_bwd_pair_bn_v2_kernel<ACT><<<grid, 256, 0, current_stream()>>>(dpool, indexes, raw, dx, c, h, w, out_h, out_w, consts, \
+                                                                            w4m, fM, 1.0f / fM, act)
+    switch (act) {
+        case BCNN_HIP_ACT_NONE: BCNN_POOL_BWD_V2(BCNN_HIP_ACT_NONE); break;
+        case BCNN_HIP_ACT_RELU: BCNN_POOL_BWD_V2(BCNN_HIP_ACT_RELU); break;
+        case BCNN_HIP_ACT_LRELU: BCNN_POOL_BWD_V2(BCNN_HIP_ACT_LRELU); break;
+        default: BCNN_POOL_BWD_V2(-1); break;
+    }
+#undef BCNN_POOL_BWD_V2
     KERNEL_CHECK();
 }
 
