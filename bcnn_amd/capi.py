@@ -117,6 +117,8 @@ def lib():
         "bcnn_set_weight_gradient_stream": (None, [vp, i]),
         "bcnn_set_inference_precision": (i, [vp, i]), "bcnn_get_inference_precision": (i, [vp]),
         "bcnn_set_loader_on_device": (i, [vp, i]), "bcnn_get_loader_on_device": (i, [vp]),
+        "bcnn_set_loader_decode_on_device": (i, [vp, i]), "bcnn_get_loader_decode_on_device": (i, [vp]),
+        "bcnn_get_loader_device_decoded": (i, [vp]),
         "bcnn_set_detector_training": (i, [vp, i]), "bcnn_get_detector_training": (i, [vp]),
         "bcnn_yolo_get_train_stats": (i, [vp, i, C.POINTER(YoloTrainStats)]),
         "bcnn_set_data_loader": (i, [vp, i, cp, cp, cp, cp]),
@@ -294,6 +296,20 @@ class Net:
 
     def get_loader_on_device(self):
         return self.L.bcnn_get_loader_on_device(self.net)
+
+    def set_loader_decode_on_device(self, on):
+        """bcnn_set_loader_decode_on_device: with set_loader_on_device, the JPEG entries of a classification / regression
+        list are entropy-decoded on the host (on set_num_threads() threads) and become pixels, cropped to the net input,
+        on the device only; every other entry is decoded on the host as before. Same batch, bit for bit. Returns the
+        bcnn_status."""
+        return self.L.bcnn_set_loader_decode_on_device(self.net, 1 if on else 0)
+
+    def get_loader_decode_on_device(self):
+        return self.L.bcnn_get_loader_decode_on_device(self.net)
+
+    def loader_device_decoded(self):
+        """bcnn_get_loader_device_decoded: samples of the latest bcnn_loader_next whose pixels were decoded on the device"""
+        return self.L.bcnn_get_loader_device_decoded(self.net)
 
     def set_detector_training(self, on):
         """bcnn_set_detector_training: YOLO heads may be built on a TRAIN net (or switched to TRAIN), their TRAIN forward

@@ -16,12 +16,20 @@
 // of a CU's 160 KiB of LDS: the LDS design would need a scratch route and a size switch as well), spreads a batch of 128
 // CIFAR samples over 2,000 waves instead of 128 workgroups, and leaves no size at which the route changes (DESIGN.md
 // section 16).
+//
+// bcnn_hip_augment_jpeg_begin / _run / _cancel make the same batch when some samples are still
+// JPEG coefficient blocks: the two kernels of jpeg_pixels.hip decode them behind the uploaded part of the block, and the
+// windowed form of the geometry kernel reads every sample through an AugWindow, which is the list loaders' crop to the
+// net input. One copy, at most four launches.
 #include "common.h"
 
 #include <cstdint>
 #include <cstring>
 
+#include <vector>
+
 #include "../host/bip_resize_tap.h"
+#include "jpeg_pixels.h"
 #include "store_run.h"
 
 namespace bcnn_hip {
@@ -38,7 +46,13 @@ struct AugParams {
     int swap;
     int blocks_per_sample;                        // of the kernel that reads this
     int runs_per_row;
+    uint32_t win_off;                             // the window table of the windowed geometry kernel
 };
+
+// Where the windowed geometry kernel finds one sample's raw bytes: a wi x hi image at `base` (bytes from the block's first
+// byte), of which the sample is the w x h window at (x_ul, y_ul). Outside the image the sample is 0: bip_crop_image onto
+// the loader's zeroed buffer.
+struct AugWindow { uint32_t base; int wi, hi, x_ul, y_ul; };
 
 // One sample as the stages see it
 struct Sample {
@@ -46,41 +60,64 @@ struct Sample {
     const int2* __restrict__ tapx;
     const int2* __restrict__ tapy;
     int w, h, flags, x_ul, y_ul;
+    int wi, hi, wx, wy;   // kWin: the image behind px and the window's origin in it
 };
 
-template <int C>
+// The raw byte of sample pixel (x, y): dense w x h samples, or (kWin) the window of the decoded image. The window sits
+// below the flip, so every stage above sees the cropped sample.
+template <int C, bool kWin>
+__device__ __forceinline__ int32_t raw(const Sample& s, int x, int y, int k) {
+    if constexpr (kWin) {
+        const long long X = (long long)x + s.wx, Y = (long long)y + s.wy;
+        return (X >= 0 && X < s.wi && Y >= 0 && Y < s.hi) ? s.px[((size_t)Y * s.wi + (size_t)X) * C + k] : 0;
+    } else {
+        return s.px[((size_t)y * s.w + x) * C + k];
+    }
+}
+template <int C, bool kWin>
 __device__ __forceinline__ int32_t flipped(const Sample& s, int x, int y, int k) {
     if (s.flags & BCNN_HIP_AUG_FLIP) x = s.w - 1 - x;
-    return s.px[((size_t)y * s.w + x) * C + k];
+    return raw<C, kWin>(s, x, y, k);
 }
-template <int C>
+template <int C, bool kWin>
 __device__ __forceinline__ int32_t shifted(const Sample& s, int x, int y, int k) {
-    if (!(s.flags & BCNN_HIP_AUG_SHIFT)) return flipped<C>(s, x, y, k);
+    if (!(s.flags & BCNN_HIP_AUG_SHIFT)) return flipped<C, kWin>(s, x, y, k);
     const long long X = (long long)x + s.x_ul, Y = (long long)y + s.y_ul;
-    return (X >= 0 && X < s.w && Y >= 0 && Y < s.h) ? flipped<C>(s, (int)X, (int)Y, k) : kCanvas;
+    return (X >= 0 && X < s.w && Y >= 0 && Y < s.h) ? flipped<C, kWin>(s, (int)X, (int)Y, k) : kCanvas;
 }
-template <int C>
+template <int C, bool kWin>
 __device__ __forceinline__ int32_t scaled(const Sample& s, int x, int y, int k) {
     if (s.flags & BCNN_HIP_AUG_SCALE) {
         const int2 tx = s.tapx[x], ty = s.tapy[y];
         if (tx.x >= 0 && ty.x >= 0) {  // covered by the resized image
             const int x1 = tx.x + (s.w > 1 ? 1 : 0), y1 = ty.x + (s.h > 1 ? 1 : 0);
-            return bip_resize_blend(shifted<C>(s, tx.x, ty.x, k), shifted<C>(s, x1, ty.x, k), shifted<C>(s, tx.x, y1, k),
-                                    shifted<C>(s, x1, y1, k), tx.y, ty.y);
+            return bip_resize_blend(shifted<C, kWin>(s, tx.x, ty.x, k), shifted<C, kWin>(s, x1, ty.x, k),
+                                    shifted<C, kWin>(s, tx.x, y1, k), shifted<C, kWin>(s, x1, y1, k), tx.y, ty.y);
         }
     }
-    return shifted<C>(s, x, y, k);
+    return shifted<C, kWin>(s, x, y, k);
 }
 
 // Stages 1 to 4 of every pixel of the batch -> s4, and the channel sums the contrast stage needs. A lane per pixel.
-template <int C>
+// kWin (bcnn_hip_augment_jpeg_run): the raw bytes of sample b are a window of the image its AugWindow names -- the crop
+// of a list image to the net input is this read, not a pass of its own.
+template <int C, bool kWin = false>
 __global__ __launch_bounds__(kAugBlock) void augment_geometry_kernel(uint8_t* __restrict__ block, AugParams p) {
     const int b = blockIdx.x / p.blocks_per_sample;
     const int pix = (blockIdx.x - b * p.blocks_per_sample) * kAugBlock + threadIdx.x;
     const bcnn_hip_augment_record r = reinterpret_cast<const bcnn_hip_augment_record*>(block + p.rec_off)[b];
     const size_t sample_bytes = (size_t)p.sw * p.sh * C;
     Sample s;
-    s.px = block + p.pix_off + b * sample_bytes;
+    if constexpr (kWin) {
+        const AugWindow win = reinterpret_cast<const AugWindow*>(block + p.win_off)[b];
+        s.px = block + win.base;
+        s.wi = win.wi;
+        s.hi = win.hi;
+        s.wx = win.x_ul;
+        s.wy = win.y_ul;
+    } else {
+        s.px = block + p.pix_off + b * sample_bytes;
+    }
     s.tapx = reinterpret_cast<const int2*>(block + p.tap_off) + (size_t)b * (p.sw + p.sh);
     s.tapy = s.tapx + p.sw;
     s.w = p.sw;
@@ -105,8 +142,9 @@ __global__ __launch_bounds__(kAugBlock) void augment_geometry_kernel(uint8_t* __
                 const float fy = (float)(py - (int32_t)((uint32_t)my << 16)) / 65536;
 #pragma unroll
                 for (int k = 0; k < C; ++k) {
-                    const float p00 = (float)scaled<C>(s, mx, my, k), p01 = (float)scaled<C>(s, mx + 1, my, k);
-                    const float p10 = (float)scaled<C>(s, mx, my + 1, k), p11 = (float)scaled<C>(s, mx + 1, my + 1, k);
+                    const float p00 = (float)scaled<C, kWin>(s, mx, my, k), p01 = (float)scaled<C, kWin>(s, mx + 1, my, k);
+                    const float p10 = (float)scaled<C, kWin>(s, mx, my + 1, k);
+                    const float p11 = (float)scaled<C, kWin>(s, mx + 1, my + 1, k);
                     const float level = p00 * (1 - fx) * (1 - fy) + p01 * (fx) * (1 - fy) + p10 * (1 - fx) * (fy) +
                                         p11 * (fx) * (fy);
                     sum[k] = (uint8_t)level;
@@ -114,7 +152,7 @@ __global__ __launch_bounds__(kAugBlock) void augment_geometry_kernel(uint8_t* __
             }  // else 0
         } else {
 #pragma unroll
-            for (int k = 0; k < C; ++k) sum[k] = (uint32_t)scaled<C>(s, x, y, k);
+            for (int k = 0; k < C; ++k) sum[k] = (uint32_t)scaled<C, kWin>(s, x, y, k);
         }
 #pragma unroll
         for (int k = 0; k < C; ++k) out[k] = (uint8_t)sum[k];
@@ -190,16 +228,43 @@ uint8_t* host_stage(size_t bytes) {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-template <int C>
+template <int C, bool kWin = false>
 void launch(uint8_t* block_d, float* dst_d, AugParams p, int num, hipStream_t st) {
     p.blocks_per_sample = ceil_div((long long)p.sw * p.sh, kAugBlock);
-    augment_geometry_kernel<C><<<dim3((unsigned)(p.blocks_per_sample * num)), kAugBlock, 0, st>>>(block_d, p);
+    augment_geometry_kernel<C, kWin><<<dim3((unsigned)(p.blocks_per_sample * num)), kAugBlock, 0, st>>>(block_d, p);
     KERNEL_CHECK();
     p.runs_per_row = ceil_div(p.W, kRun);
     p.blocks_per_sample = ceil_div((long long)p.runs_per_row * p.H, kAugBlock);
     augment_convert_kernel<C><<<dim3((unsigned)(p.blocks_per_sample * num)), kAugBlock, 0, st>>>(block_d, dst_d, p);
     KERNEL_CHECK();
 }
+
+// Every tap index of the samples that scale lies in [-1, max(extent - 2, 0)]: the four reads of the blend stay inside.
+bool taps_in_range(const bcnn_hip_augment_record* records, const int32_t* taps, size_t num, int src_w, int src_h) {
+    const size_t sample_taps = (size_t)src_w + src_h;
+    for (size_t b = 0; b < num; ++b) {
+        if (!(records[b].flags & BCNN_HIP_AUG_SCALE)) continue;
+        const int32_t* t = taps + b * sample_taps * 2;
+        for (size_t i = 0; i < sample_taps; ++i) {
+            const int extent = i < (size_t)src_w ? src_w : src_h;
+            if (t[2 * i] < -1 || t[2 * i] > (extent >= 2 ? extent - 2 : 0)) return false;
+        }
+    }
+    return true;
+}
+
+// What bcnn_hip_augment_jpeg_begin laid out for this thread, until _run or _cancel. Upload part of the block:
+// [records][channel sums][taps][windows][plane table][image table][coefficients of every candidate][raw samples of the
+// host-decoded ones, as many as _run finds]; behind `device_at`, on the device only: [planes][pixels][rotated samples].
+struct PendingJpeg {
+    bool active = false;
+    uint8_t* stage;
+    int c, h, w, num;
+    size_t sum_off, tap_off, win_off, planes_at, images_at, raw_at, device_at, plane_bytes, pixel_bytes, total;
+    std::vector<uint32_t> coeff_off;   // per sample; 0: not a candidate
+    std::vector<bcnn_hip_jpeg_frame> frames;
+};
+thread_local PendingJpeg g_jpeg;
 
 }  // namespace
 }  // namespace bcnn_hip
@@ -224,14 +289,7 @@ int bcnn_hip_augment_batch(float* dst_d, int n, int c, int h, int w, int num_sam
     const size_t pix_bytes = align_up(num * sample_bytes, 16);
     const size_t total = rec_bytes + sum_bytes + tap_bytes + pix_bytes;
     if (total + pix_bytes > (size_t)0x7fffffff) return 1;
-    for (size_t b = 0; any_scale && b < num; ++b) {
-        if (!(records[b].flags & BCNN_HIP_AUG_SCALE)) continue;
-        const int32_t* t = taps + b * sample_taps * 2;
-        for (size_t i = 0; i < sample_taps; ++i) {
-            const int extent = i < (size_t)src_w ? src_w : src_h;
-            if (t[2 * i] < -1 || t[2 * i] > (extent >= 2 ? extent - 2 : 0)) return 1;
-        }
-    }
+    if (any_scale && !taps_in_range(records, taps, num, src_w, src_h)) return 1;
 
     // the staging block: [records][channel sums, zero][taps][pixels]; behind it on the device, the rotated samples
     uint8_t* stage = host_stage(total);
@@ -264,12 +322,137 @@ int bcnn_hip_augment_batch(float* dst_d, int n, int c, int h, int w, int num_sam
     p.cy = (src_h - h) / 2;
     p.swap = (swap_to_bgr && c == 3) ? 1 : 0;
     p.blocks_per_sample = p.runs_per_row = 0;
+    p.win_off = 0;
     switch (c) {
         case 1: launch<1>(block_d, dst_d, p, num_samples, st); break;
         case 2: launch<2>(block_d, dst_d, p, num_samples, st); break;
         case 3: launch<3>(block_d, dst_d, p, num_samples, st); break;
         default: launch<4>(block_d, dst_d, p, num_samples, st); break;
     }
+    return 0;
+}
+
+int bcnn_hip_augment_jpeg_begin(int n, int c, int h, int w, int num_samples, const bcnn_hip_jpeg_frame* frames,
+                                int16_t** coeff) {
+    PendingJpeg& q = g_jpeg;
+    q.active = false;
+    if (!frames || !coeff || n < 1 || h < 1 || w < 1 || (c != 1 && c != 3) || num_samples < 1 || num_samples > n ||
+        (long long)w * h > 0x7fffffff / (c * (long long)num_samples))
+        return 1;
+    // ---- every refusal comes before anything is staged
+    const size_t num = (size_t)num_samples, sample_bytes = (size_t)w * h * c;
+    size_t coeff_bytes = 0, plane_bytes = 0, pixel_bytes = 0;
+    unsigned long long blocks = 0, runs = 0;
+    int candidates = 0;
+    for (size_t b = 0; b < num; ++b) {
+        coeff[b] = nullptr;
+        if (frames[b].ncomp == 0 || !jpeg_frame_ok(frames[b], c)) continue;   // the caller decodes this one
+        const JpegFrameSize s = jpeg_frame_size(frames[b], c);
+        coeff_bytes += s.coeff;
+        plane_bytes += s.planes;
+        pixel_bytes += s.pixels;
+        blocks += s.blocks;
+        runs += s.runs;
+        ++candidates;
+        if (coeff_bytes + plane_bytes + pixel_bytes > (size_t)0x7fffffff) return 1;
+    }
+    if (candidates == 0) return 1;
+    const size_t rec_bytes = align_up(num * sizeof(bcnn_hip_augment_record), 16), sum_bytes = num * 4 * sizeof(uint32_t);
+    const size_t tap_bytes = align_up(num * ((size_t)w + h) * 2 * sizeof(int32_t), 16);
+    const size_t win_bytes = align_up(num * sizeof(AugWindow), 16), raw_bytes = align_up(num * sample_bytes, 16);
+    q.sum_off = rec_bytes;
+    q.tap_off = q.sum_off + sum_bytes;
+    q.win_off = q.tap_off + tap_bytes;
+    q.planes_at = q.win_off + win_bytes;
+    q.images_at = q.planes_at + jpeg_plane_table_bytes(candidates * c);
+    const size_t coeff_at = q.images_at + jpeg_image_table_bytes(candidates);
+    q.raw_at = coeff_at + coeff_bytes;
+    q.device_at = q.raw_at + raw_bytes;
+    q.plane_bytes = plane_bytes;
+    q.pixel_bytes = pixel_bytes;
+    q.total = q.device_at + plane_bytes + pixel_bytes + raw_bytes;
+    if (q.total > (size_t)0x7fffffff || blocks > 0x7fffffffull || runs > 0x7fffffffull) return 1;
+
+    q.stage = host_stage(q.device_at);
+    q.coeff_off.assign(num, 0);
+    q.frames.assign(frames, frames + num);
+    size_t c_at = coeff_at;
+    for (size_t b = 0; b < num; ++b) {
+        if (frames[b].ncomp == 0 || !jpeg_frame_ok(frames[b], c)) continue;
+        q.coeff_off[b] = (uint32_t)c_at;
+        coeff[b] = reinterpret_cast<int16_t*>(q.stage + c_at);
+        c_at += jpeg_frame_size(frames[b], c).coeff;
+    }
+    q.c = c; q.h = h; q.w = w; q.num = num_samples;
+    q.active = true;
+    return 0;
+}
+
+void bcnn_hip_augment_jpeg_cancel(void) { g_jpeg.active = false; }
+
+int bcnn_hip_augment_jpeg_run(float* dst_d, const uint8_t* decoded, const uint8_t* pixels,
+                              const bcnn_hip_augment_record* records, const int32_t* taps, const int32_t* origins,
+                              int swap_to_bgr) {
+    PendingJpeg& q = g_jpeg;
+    if (!q.active) return 1;
+    q.active = false;
+    if (!dst_d || !decoded || !pixels || !records || !origins) return 1;
+    const size_t num = (size_t)q.num, sample_bytes = (size_t)q.w * q.h * q.c, sample_taps = (size_t)q.w + q.h;
+    bool any_scale = false;
+    for (size_t b = 0; b < num; ++b) {
+        if (decoded[b] && q.coeff_off[b] == 0) return 1;
+        any_scale = any_scale || (records[b].flags & BCNN_HIP_AUG_SCALE);
+    }
+    if (any_scale && (!taps || !taps_in_range(records, taps, num, q.w, q.h))) return 1;
+
+    uint8_t* stage = q.stage;
+    memcpy(stage, records, num * sizeof(bcnn_hip_augment_record));
+    memset(stage + q.sum_off, 0, num * 4 * sizeof(uint32_t));
+    if (any_scale) memcpy(stage + q.tap_off, taps, num * sample_taps * 2 * sizeof(int32_t));
+    else  // the tap table holds nothing: no record may ask for it
+        for (size_t b = 0; b < num; ++b) reinterpret_cast<bcnn_hip_augment_record*>(stage)[b].flags &= ~BCNN_HIP_AUG_SCALE;
+    AugWindow* win = reinterpret_cast<AugWindow*>(stage + q.win_off);
+    JpegCursor cur = {0, q.device_at, q.device_at + q.plane_bytes, 0, 0, 0, 0};
+    size_t raw_at = q.raw_at;
+    for (size_t b = 0; b < num; ++b) {
+        if (decoded[b]) {   // a window of the image the colour kernel leaves at cur.pixel_at
+            const bcnn_hip_jpeg_frame& f = q.frames[b];
+            const AugWindow v = {(uint32_t)cur.pixel_at, f.width, f.height, origins[2 * b], origins[2 * b + 1]};
+            win[b] = v;
+            cur.coeff_at = q.coeff_off[b];
+            jpeg_append_image(stage, q.planes_at, q.images_at, f, q.c, cur);
+        } else {            // the caller's cropped sample, whole
+            const AugWindow v = {(uint32_t)raw_at, q.w, q.h, 0, 0};
+            win[b] = v;
+            memcpy(stage + raw_at, pixels + b * sample_bytes, sample_bytes);
+            raw_at += sample_bytes;
+        }
+    }
+    jpeg_close_tables(stage, q.planes_at, q.images_at, cur);
+
+    // ---- one copy, four launches
+    uint8_t* block_d = reinterpret_cast<uint8_t*>(scratch(SCRATCH_AUGMENT, (q.total + 3) / 4));
+    hipStream_t st = current_stream();
+    HIP_CHECK(hipMemcpyAsync(block_d, stage, raw_at, hipMemcpyHostToDevice, st));
+    HostStage& hs = g_stage[current_device()];
+    HIP_CHECK(hipEventRecord(hs.copied, st));
+    hs.in_flight = true;
+    launch_jpeg_pixels(block_d, (uint32_t)q.planes_at, (uint32_t)q.images_at, cur, st);
+
+    AugParams p;
+    p.rec_off = 0;
+    p.sum_off = (uint32_t)q.sum_off;
+    p.tap_off = (uint32_t)q.tap_off;
+    p.pix_off = 0;
+    p.win_off = (uint32_t)q.win_off;
+    p.s4_off = (uint32_t)(q.device_at + q.plane_bytes + q.pixel_bytes);
+    p.sw = p.W = q.w;
+    p.sh = p.H = q.h;
+    p.cx = p.cy = 0;
+    p.swap = (swap_to_bgr && q.c == 3) ? 1 : 0;
+    p.blocks_per_sample = p.runs_per_row = 0;
+    if (q.c == 1) launch<1, true>(block_d, dst_d, p, q.num, st);
+    else launch<3, true>(block_d, dst_d, p, q.num, st);
     return 0;
 }
 

@@ -14,6 +14,7 @@
 
 #include "../host/bip_jpeg_pixels.h"
 #include "image_fill.h"
+#include "jpeg_pixels.h"
 
 namespace bcnn_hip {
 namespace {
@@ -161,15 +162,18 @@ __global__ __launch_bounds__(kColourThreads) void jpeg_colour_kernel(uint8_t* __
 struct Pending {
     bool active = false;
     uint8_t* stage;                       // the pinned block
-    int c, h, w, num_images, num_planes;
+    int c, h, w;
     size_t upload, total;                 // bytes copied up / of the whole device block
-    uint32_t planes_off, images_off, total_blocks, total_runs;
+    uint32_t planes_off, images_off;
+    JpegCursor cur;                       // behind the last image: the totals
 };
 thread_local Pending g_pending;
 
+}  // namespace
+
 // A frame the kernels can run on without leaving its planes: what bip_jpeg_frame_info reports, checked again here
 // because every bound of the two kernels follows from these numbers.
-bool frame_ok(const bcnn_hip_jpeg_frame& f, int c) {
+bool jpeg_frame_ok(const bcnn_hip_jpeg_frame& f, int c) {
     if (f.ncomp != c || (c != 1 && c != 3) || f.width < 1 || f.height < 1 || f.hmax < 1 || f.hmax > 4 || f.vmax < 1 ||
         f.vmax > 4 || (long long)f.width * f.height * c > (1ll << 30))
         return false;
@@ -191,7 +195,75 @@ bool frame_ok(const bcnn_hip_jpeg_frame& f, int c) {
     return true;
 }
 
-}  // namespace
+JpegFrameSize jpeg_frame_size(const bcnn_hip_jpeg_frame& f, int c) {
+    JpegFrameSize s = {0, 0, stage_align((size_t)f.width * f.height * c, 16), 0,
+                       (unsigned long long)ceil_div(f.width, kColourRun) * f.height};
+    for (int k = 0; k < c; ++k) {
+        const bcnn_hip_jpeg_component& p = f.comp[k];
+        s.coeff += (size_t)p.blocks_w * p.blocks_h * 128;
+        s.planes += (size_t)p.pitch * p.rows;
+        s.blocks += (unsigned long long)p.idct_w * p.idct_h;
+    }
+    return s;
+}
+
+size_t jpeg_plane_table_bytes(int num_planes) { return stage_align(((size_t)num_planes + 1) * sizeof(JpegPlane), 16); }
+size_t jpeg_image_table_bytes(int num_images) { return stage_align(((size_t)num_images + 1) * sizeof(JpegImage), 16); }
+
+void jpeg_append_image(uint8_t* stage, size_t planes_at, size_t images_at, const bcnn_hip_jpeg_frame& f, int c,
+                       JpegCursor& cur) {
+    JpegPlane* plane = reinterpret_cast<JpegPlane*>(stage + planes_at);
+    JpegImage& im = reinterpret_cast<JpegImage*>(stage + images_at)[cur.images];
+    memset(&im, 0, sizeof(im));
+    im.first_run = cur.run_at;
+    im.pix_off = (uint32_t)cur.pixel_at;
+    im.width = f.width;
+    im.height = f.height;
+    im.ncomp = c;
+    im.runs_per_row = ceil_div(f.width, kColourRun);
+    for (int k = 0; k < c; ++k) {
+        const bcnn_hip_jpeg_component& p = f.comp[k];
+        JpegPlane& pl = plane[cur.planes++];
+        pl.first_block = cur.block_at;
+        pl.coeff_off = (uint32_t)cur.coeff_at;
+        pl.plane_off = (uint32_t)cur.plane_at;
+        pl.idct_w = p.idct_w;
+        pl.blocks_w = p.blocks_w;
+        pl.pitch = p.pitch;
+        im.comp[k].plane_off = (uint32_t)cur.plane_at;
+        im.comp[k].pitch = p.pitch;
+        im.comp[k].hs = f.hmax / p.h;
+        im.comp[k].vs = f.vmax / p.v;
+        im.comp[k].w_lores = p.width;
+        im.comp[k].rows = p.height;
+        cur.block_at += (uint32_t)(p.idct_w * p.idct_h);
+        cur.coeff_at += (size_t)p.blocks_w * p.blocks_h * 128;
+        cur.plane_at += (size_t)p.pitch * p.rows;
+    }
+    cur.run_at += (uint32_t)(im.runs_per_row * f.height);
+    cur.pixel_at += stage_align((size_t)f.width * f.height * c, 16);
+    ++cur.images;
+}
+
+void jpeg_close_tables(uint8_t* stage, size_t planes_at, size_t images_at, const JpegCursor& cur) {
+    JpegPlane& pl = reinterpret_cast<JpegPlane*>(stage + planes_at)[cur.planes];
+    memset(&pl, 0, sizeof(JpegPlane));
+    pl.first_block = cur.block_at;
+    JpegImage& im = reinterpret_cast<JpegImage*>(stage + images_at)[cur.images];
+    memset(&im, 0, sizeof(JpegImage));
+    im.first_run = cur.run_at;
+}
+
+void launch_jpeg_pixels(uint8_t* stage_d, uint32_t planes_off, uint32_t images_off, const JpegCursor& cur, hipStream_t st) {
+    if (cur.images < 1) return;
+    jpeg_idct_kernel<<<dim3((unsigned)ceil_div(cur.block_at, kIdctBlocks)), kIdctThreads, 0, st>>>(
+        stage_d, planes_off, cur.planes, cur.block_at);
+    KERNEL_CHECK();
+    jpeg_colour_kernel<<<dim3((unsigned)ceil_div(cur.run_at, kColourThreads)), kColourThreads, 0, st>>>(
+        stage_d, images_off, cur.images, cur.run_at);
+    KERNEL_CHECK();
+}
+
 }  // namespace bcnn_hip
 
 using namespace bcnn_hip;
@@ -208,23 +280,19 @@ int bcnn_hip_jpeg_stage_begin(int n, int c, int h, int w, int num_images, const 
     // ---- every refusal comes before anything is staged
     size_t coeff_bytes = 0, plane_bytes = 0, pixel_bytes = 0;
     unsigned long long blocks = 0, runs = 0;
-    int num_planes = 0;
     for (int b = 0; b < num_images; ++b) {
         const bcnn_hip_jpeg_frame& f = frames[b];
         int new_w, new_h;
-        if (!frame_ok(f, c) || !fitted_extent(fit, w, h, f.width, f.height, &new_w, &new_h)) {
+        if (!jpeg_frame_ok(f, c) || !fitted_extent(fit, w, h, f.width, f.height, &new_w, &new_h)) {
             if (failed_image) *failed_image = b;
             return 1;
         }
-        for (int k = 0; k < c; ++k) {
-            const bcnn_hip_jpeg_component& p = f.comp[k];
-            coeff_bytes += (size_t)p.blocks_w * p.blocks_h * 128;
-            plane_bytes += (size_t)p.pitch * p.rows;
-            blocks += (unsigned long long)p.idct_w * p.idct_h;
-            ++num_planes;
-        }
-        pixel_bytes += stage_align((size_t)f.width * f.height * c, 16);
-        runs += (unsigned long long)ceil_div(f.width, kColourRun) * f.height;
+        const JpegFrameSize s = jpeg_frame_size(f, c);
+        coeff_bytes += s.coeff;
+        plane_bytes += s.planes;
+        pixel_bytes += s.pixels;
+        blocks += s.blocks;
+        runs += s.runs;
         if (coeff_bytes + plane_bytes + pixel_bytes > (size_t)0x7fffffff) {
             if (failed_image) *failed_image = b;
             return 1;
@@ -235,8 +303,8 @@ int bcnn_hip_jpeg_stage_begin(int n, int c, int h, int w, int num_images, const 
     const size_t desc_bytes = stage_align((size_t)num_images * sizeof(ImageDesc), 16);
     const size_t taps = stage_align((size_t)num_images * ((size_t)w + h) * sizeof(int2), 16);
     const size_t planes_at = desc_bytes + taps;
-    const size_t images_at = planes_at + stage_align(((size_t)num_planes + 1) * sizeof(JpegPlane), 16);
-    const size_t coeff_at = images_at + stage_align(((size_t)num_images + 1) * sizeof(JpegImage), 16);
+    const size_t images_at = planes_at + jpeg_plane_table_bytes(num_images * c);
+    const size_t coeff_at = images_at + jpeg_image_table_bytes(num_images);
     const size_t upload = coeff_at + coeff_bytes, total = upload + plane_bytes + pixel_bytes;
     int runs_per_row, blocks_per_image;
     long long fill_blocks;
@@ -248,57 +316,24 @@ int bcnn_hip_jpeg_stage_begin(int n, int c, int h, int w, int num_images, const 
 
     uint8_t* stage = host_stage(upload);
     ImageDesc* desc = reinterpret_cast<ImageDesc*>(stage);
-    JpegPlane* plane = reinterpret_cast<JpegPlane*>(stage + planes_at);
-    JpegImage* image = reinterpret_cast<JpegImage*>(stage + images_at);
-    size_t tap_at = desc_bytes, c_at = coeff_at, p_at = upload, x_at = upload + plane_bytes;
-    uint32_t block_at = 0, run_at = 0;
-    int pi = 0;
+    size_t tap_at = desc_bytes;
+    JpegCursor cur = {coeff_at, upload, upload + plane_bytes, 0, 0, 0, 0};
     for (int b = 0; b < num_images; ++b) {
         const bcnn_hip_jpeg_frame& f = frames[b];
         tap_at += stage_geometry(stage, tap_at, desc[b], fit, w, h, f.width, f.height);
-        desc[b].data_off = (uint32_t)x_at;
-        JpegImage& im = image[b];
-        memset(&im, 0, sizeof(im));
-        im.first_run = run_at;
-        im.pix_off = (uint32_t)x_at;
-        im.width = f.width;
-        im.height = f.height;
-        im.ncomp = c;
-        im.runs_per_row = ceil_div(f.width, kColourRun);
-        coeff[b] = reinterpret_cast<int16_t*>(stage + c_at);
-        for (int k = 0; k < c; ++k, ++pi) {
-            const bcnn_hip_jpeg_component& p = f.comp[k];
-            plane[pi].first_block = block_at;
-            plane[pi].coeff_off = (uint32_t)c_at;
-            plane[pi].plane_off = (uint32_t)p_at;
-            plane[pi].idct_w = p.idct_w;
-            plane[pi].blocks_w = p.blocks_w;
-            plane[pi].pitch = p.pitch;
-            im.comp[k].plane_off = (uint32_t)p_at;
-            im.comp[k].pitch = p.pitch;
-            im.comp[k].hs = f.hmax / p.h;
-            im.comp[k].vs = f.vmax / p.v;
-            im.comp[k].w_lores = p.width;
-            im.comp[k].rows = p.height;
-            block_at += (uint32_t)(p.idct_w * p.idct_h);
-            c_at += (size_t)p.blocks_w * p.blocks_h * 128;
-            p_at += (size_t)p.pitch * p.rows;
-        }
-        run_at += (uint32_t)(im.runs_per_row * f.height);
-        x_at += stage_align((size_t)f.width * f.height * c, 16);
+        desc[b].data_off = (uint32_t)cur.pixel_at;
+        coeff[b] = reinterpret_cast<int16_t*>(stage + cur.coeff_at);
+        jpeg_append_image(stage, planes_at, images_at, f, c, cur);
     }
-    memset(&plane[pi], 0, sizeof(JpegPlane));
-    plane[pi].first_block = block_at;
-    memset(&image[num_images], 0, sizeof(JpegImage));
-    image[num_images].first_run = run_at;
+    jpeg_close_tables(stage, planes_at, images_at, cur);
 
     Pending& q = g_pending;
     q.active = true;
     q.stage = stage;
-    q.c = c; q.h = h; q.w = w; q.num_images = num_images; q.num_planes = num_planes;
+    q.c = c; q.h = h; q.w = w;
     q.upload = upload; q.total = total;
     q.planes_off = (uint32_t)planes_at; q.images_off = (uint32_t)images_at;
-    q.total_blocks = block_at; q.total_runs = run_at;
+    q.cur = cur;
     return 0;
 }
 
@@ -313,13 +348,8 @@ int bcnn_hip_jpeg_stage_run(float* dst_d, float norm_coeff, int swap_to_bgr, flo
     hipStream_t st = current_stream();
     HIP_CHECK(hipMemcpyAsync(stage_d, q.stage, q.upload, hipMemcpyHostToDevice, st));
     stage_copied(st);
-    jpeg_idct_kernel<<<dim3((unsigned)ceil_div(q.total_blocks, kIdctBlocks)), kIdctThreads, 0, st>>>(
-        stage_d, q.planes_off, q.num_planes, q.total_blocks);
-    KERNEL_CHECK();
-    jpeg_colour_kernel<<<dim3((unsigned)ceil_div(q.total_runs, kColourThreads)), kColourThreads, 0, st>>>(
-        stage_d, q.images_off, q.num_images, q.total_runs);
-    KERNEL_CHECK();
-    launch_fill_images(stage_d, dst_d, q.c, q.h, q.w, q.num_images, norm_coeff, swap_to_bgr, mean_r, mean_g, mean_b, st);
+    launch_jpeg_pixels(stage_d, q.planes_off, q.images_off, q.cur, st);
+    launch_fill_images(stage_d, dst_d, q.c, q.h, q.w, q.cur.images, norm_coeff, swap_to_bgr, mean_r, mean_g, mean_b, st);
     return 0;
 }
 

@@ -6,7 +6,9 @@
  *   bcnn_loader_next          fills one batch on the host, sample by sample, then uploads inputs (+ labels) to the device
  *                             (the reference's H2D hook, bcnn_data.c:413-425)
  *                             with bcnn_set_loader_on_device the host only reads, decodes and draws; the raw samples and one
- *                             record each go up in one copy and ../csrc/augment.hip makes the float batch (same bits)
+ *                             record each go up in one copy and ../csrc/augment.hip makes the float batch (same bits);
+ *                             with bcnn_set_loader_decode_on_device as well, the JPEG entries of a list batch go up as
+ *                             coefficient blocks and are decoded and cropped there too (list_batch_decoded below)
  *   bcnn_augment_data_with_*  augmentation ranges; bcnn_apply_data_augmentation draws the parameters of one sample from
  *                             libc rand() in the reference's order (flip, shift, scale, rotation, contrast, brightness), so
  *                             that a run seeded like a reference run sees the same samples byte for byte
@@ -260,6 +262,14 @@ typedef struct {
      * holds it raw, and `owed` remembers the pixel work that makes the two equal should a decode fail next. */
     int owed;
     aug_draw owed_draw;
+    /* bcnn_set_loader_decode_on_device. Per sample of the batch being gathered: 1 = its pixels are made on the device, and
+     * the origin of its crop window there. A device-decoded sample leaves no pixels on the host, so `lazy` keeps what
+     * rebuilds the latest one in it->input_uchar should a decode fail next: the file's bytes and the crop origin. */
+    uint8_t *decoded;
+    int32_t *origins;
+    uint8_t *lazy;
+    size_t lazy_len;
+    int lazy_x, lazy_y;
 } loader_stage;
 
 static loader_stage *stage_of(bcnn_net *net) { return (loader_stage *)((bcnn_hip_context *)net->hip_ctx)->loader_stage; }
@@ -267,15 +277,49 @@ static loader_stage *stage_of(bcnn_net *net) { return (loader_stage *)((bcnn_hip
 void bcnn_free_loader_stage(bcnn_net *net) {
     loader_stage *ls = stage_of(net);
     if (!ls) return;
-    free(ls->pixels); free(ls->records); free(ls->taps); free(ls);
+    free(ls->pixels); free(ls->records); free(ls->taps); free(ls->decoded); free(ls->origins); free(ls->lazy); free(ls);
     ((bcnn_hip_context *)net->hip_ctx)->loader_stage = NULL;
 }
 
+/* w x h x c window of the decoded wi x hi image at (x_ul, y_ul) into img, zero outside the image; a plain copy when the
+ * extents are equal (reference bcnn_data.c:352-372) */
+static bcnn_status crop_to_input(unsigned char *buf, int wi, int hi, int x_ul, int y_ul, unsigned char *img, int w, int h,
+                                 int c) {
+    if (wi == w && hi == h) {
+        memcpy(img, buf, (size_t)w * h * c);
+        return BCNN_SUCCESS;
+    }
+    unsigned char *crop = (unsigned char *)calloc((size_t)w * h * c, 1);
+    if (!crop) return BCNN_FAILED_ALLOC;
+    bip_crop_image(buf, wi, hi, (size_t)wi * c, x_ul, y_ul, crop, w, h, (size_t)w * c, c);
+    memcpy(img, crop, (size_t)w * h * c);
+    free(crop);
+    return BCNN_SUCCESS;
+}
+
+static void drop_lazy(loader_stage *ls) {
+    free(ls->lazy);
+    ls->lazy = NULL;
+    ls->lazy_len = 0;
+}
+
+/* Before the sample buffer is used "as it was": the pixels a device-decoded sample would have left in it, then the pixel
+ * work owed to it. */
 static void settle_owed(bcnn_net *net, bcnn_loader *it) {
     loader_stage *ls = stage_of(net);
-    if (!ls || !ls->owed) return;
-    ls->owed = 0;
+    if (!ls) return;
     bcnn_tensor *in = &net->tensors[0];
+    if (ls->lazy) {
+        int wi = 0, hi = 0, ci = 0;
+        unsigned char *buf = NULL;
+        bip_load_image_from_memory(ls->lazy, (int)ls->lazy_len, &buf, &wi, &hi, &ci);
+        if (buf && wi > 0 && hi > 0 && ci == in->c)
+            crop_to_input(buf, wi, hi, ls->lazy_x, ls->lazy_y, it->input_uchar, in->w, in->h, in->c);
+        free(buf);
+        drop_lazy(ls);
+    }
+    if (!ls->owed) return;
+    ls->owed = 0;
     unsigned char *scratch = (unsigned char *)calloc((size_t)bcnn_tensor_size3d(in), 1);
     if (scratch) augment_pixels(it->input_uchar, in->w, in->h, in->c, &ls->owed_draw, scratch);
     free(scratch);
@@ -305,16 +349,18 @@ static loader_stage *stage_begin(bcnn_net *net, bcnn_loader *it) {
         ls->cap_bytes = ls->pixels ? bytes : 0;
     }
     if (ls->cap_records < n) {
-        free(ls->records);
+        free(ls->records); free(ls->decoded); free(ls->origins);
         ls->records = (bcnn_hip_augment_record *)calloc(n, sizeof(bcnn_hip_augment_record));
-        ls->cap_records = ls->records ? n : 0;
+        ls->decoded = (uint8_t *)calloc(n, 1);
+        ls->origins = (int32_t *)calloc(2 * n, sizeof(int32_t));
+        ls->cap_records = (ls->records && ls->decoded && ls->origins) ? n : 0;
     }
     if (ls->cap_taps < taps) {
         free(ls->taps);
         ls->taps = (int32_t *)calloc(taps, sizeof(int32_t));
         ls->cap_taps = ls->taps ? taps : 0;
     }
-    if (!ls->pixels || !ls->records || !ls->taps) return NULL;
+    if (!ls->pixels || !ls->cap_records || !ls->taps) return NULL;
     ls->active = 1;
     return ls;
 }
@@ -364,12 +410,8 @@ static void fill_record(bcnn_hip_augment_record *r, int32_t *taps, const aug_dra
     if (d->brighten) r->brightness = d->brightness;
 }
 
-/* The loader's sample buffer into slot idx of the block, with this sample's draws (TRAIN mode) or the identity record. */
-static bcnn_status stage_sample(bcnn_net *net, bcnn_loader *it, loader_stage *ls, int idx, int w, int h, int c,
-                                int list_loader) {
-    if (w != ls->w || h != ls->h || c != ls->c || idx < 0 || (size_t)idx >= ls->cap_records) return BCNN_INVALID_DATA;
-    const size_t bytes = (size_t)w * h * c;
-    memcpy(ls->pixels + (size_t)idx * bytes, it->input_uchar, bytes);
+/* Slot idx of the block gets this sample's draws (TRAIN mode) or the identity record. */
+static void stage_draws(bcnn_net *net, loader_stage *ls, int idx, int w, int h, int list_loader) {
     bcnn_hip_augment_record *r = &ls->records[idx];
     memset(r, 0, sizeof(*r));
     ls->owed = 0;
@@ -382,6 +424,15 @@ static bcnn_status stage_sample(bcnn_net *net, bcnn_loader *it, loader_stage *ls
             ls->owed_draw = d;
         }
     }
+}
+
+/* The loader's sample buffer into slot idx of the block, with its draws. */
+static bcnn_status stage_sample(bcnn_net *net, bcnn_loader *it, loader_stage *ls, int idx, int w, int h, int c,
+                                int list_loader) {
+    if (w != ls->w || h != ls->h || c != ls->c || idx < 0 || (size_t)idx >= ls->cap_records) return BCNN_INVALID_DATA;
+    const size_t bytes = (size_t)w * h * c;
+    memcpy(ls->pixels + (size_t)idx * bytes, it->input_uchar, bytes);
+    stage_draws(net, ls, idx, w, h, list_loader);
     return BCNN_SUCCESS;
 }
 
@@ -544,12 +595,24 @@ static bcnn_status list_init(bcnn_loader *it, bcnn_net *net, const char *a, cons
     return it->input_uchar ? BCNN_SUCCESS : BCNN_FAILED_ALLOC;
 }
 
-/* decodes the file, crops it to the net input (centred for evaluation, at a random origin for training) */
-static bcnn_status load_image(bcnn_net *net, char *path, int w, int h, int c, unsigned char *img, int *x_shift,
-                              int *y_shift) {
-    int wi = 0, hi = 0, ci = 0, x_ul = 0, y_ul = 0;
-    unsigned char *buf = NULL;
-    bip_load_image(path, &buf, &wi, &hi, &ci);
+/* where a decoded wi x hi image is cropped to the w x h net input: at a random origin for training (two draws, or none
+ * where the range is negative), centred for evaluation; (0, 0) and no draw when the extents are equal */
+static void crop_origin(bcnn_net *net, int wi, int hi, int w, int h, int *x_ul, int *y_ul) {
+    *x_ul = *y_ul = 0;
+    if (wi == w && hi == h) return;
+    if (net->mode == BCNN_MODE_TRAIN) {
+        *x_ul = rand_between(0, wi - w);
+        *y_ul = rand_between(0, hi - h);
+    } else {
+        *x_ul = (wi - w) / 2;
+        *y_ul = (hi - h) / 2;
+    }
+}
+
+/* the decoded file (buf is freed here) cropped to the net input */
+static bcnn_status place_decoded(bcnn_net *net, const char *path, unsigned char *buf, int wi, int hi, int ci, int w, int h,
+                                 int c, unsigned char *img, int *x_shift, int *y_shift) {
+    int x_ul = 0, y_ul = 0;
     if (!(wi > 0 && hi > 0 && buf)) {
         bcnn_log(net->log_ctx, BCNN_LOG_ERROR, "Invalid image %s\n", path);
         free(buf);
@@ -560,25 +623,21 @@ static bcnn_status load_image(bcnn_net *net, char *path, int w, int h, int c, un
         free(buf);
         return BCNN_INVALID_DATA;
     }
-    if (wi != w || hi != h) {
-        if (net->mode == BCNN_MODE_TRAIN) {
-            x_ul = rand_between(0, wi - w);
-            y_ul = rand_between(0, hi - h);
-        } else {
-            x_ul = (wi - w) / 2;
-            y_ul = (hi - h) / 2;
-        }
-        unsigned char *crop = (unsigned char *)calloc((size_t)w * h * c, 1);
-        if (!crop) { free(buf); return BCNN_FAILED_ALLOC; }
-        bip_crop_image(buf, wi, hi, (size_t)wi * ci, x_ul, y_ul, crop, w, h, (size_t)w * c, c);
-        memcpy(img, crop, (size_t)w * h * c);
-        free(crop);
-    } else {
-        memcpy(img, buf, (size_t)w * h * c);
-    }
+    crop_origin(net, wi, hi, w, h, &x_ul, &y_ul);
+    const bcnn_status st = crop_to_input(buf, wi, hi, x_ul, y_ul, img, w, h, c);
     free(buf);
+    if (st != BCNN_SUCCESS) return st;
     if (x_shift && y_shift) { *x_shift = x_ul; *y_shift = y_ul; }
     return BCNN_SUCCESS;
+}
+
+/* decodes the file, crops it to the net input (centred for evaluation, at a random origin for training) */
+static bcnn_status load_image(bcnn_net *net, char *path, int w, int h, int c, unsigned char *img, int *x_shift,
+                              int *y_shift) {
+    int wi = 0, hi = 0, ci = 0;
+    unsigned char *buf = NULL;
+    bip_load_image(path, &buf, &wi, &hi, &ci);
+    return place_decoded(net, path, buf, wi, hi, ci, w, h, c, img, x_shift, y_shift);
 }
 
 /* reference bcnn_fill_input_tensor (bcnn_data.c:336-377): a sample that fails to decode leaves the buffer as it was */
@@ -588,8 +647,10 @@ void bcnn_fill_input_tensor(bcnn_net *net, bcnn_loader *it, char *path_img, int 
     if (load_image(net, path_img, in->w, in->h, in->c, it->input_uchar, net->data_aug ? &net->data_aug->shift_x : NULL,
                    net->data_aug ? &net->data_aug->shift_y : NULL) != BCNN_SUCCESS)
         settle_owed(net, it); /* the buffer as the host path would have left it */
-    else if (ls)
+    else if (ls) {
         ls->owed = 0;
+        drop_lazy(ls);
+    }
     if (ls && ls->active) {
         stage_sample(net, it, ls, idx, in->w, in->h, in->c, 1);
         return;
@@ -660,6 +721,178 @@ static bcnn_status list_reg_next(bcnn_loader *it, bcnn_net *net, int idx) {
     }
     free_tokens(tok, n);
     return BCNN_SUCCESS;
+}
+
+/* ---- a list batch whose JPEG entries are decoded on the device (bcnn_set_loader_decode_on_device) --------------------- */
+/* The batch in three phases instead of sample by sample, because the number of rand() draws of a sample depends on
+ * whether its file decoded, and the entropy decoding of the whole batch runs in parallel in between:
+ *   1 (serial)   lines are accepted or skipped by their token count as list_classif_next / list_reg_next do, labels are
+ *                written, every file is read whole and its JPEG header parsed; a stream whose component count is the
+ *                input's and whose frame fits the staging block is a device candidate;
+ *   2 (parallel) the candidates' coefficients straight into the pinned staging block, a status per image;
+ *   3 (serial)   in batch order, per sample: a file that is no candidate, or whose coefficients failed, is decoded here
+ *                as load_image does; a decoded sample draws its crop origin, then the augmentation; a failed one goes
+ *                the "buffer as it was" way. Only the pixels of a device-decoded sample stay away from the host.
+ * One copy and at most four launches follow (bcnn_hip_augment_jpeg_run); *launched is 0 when no sample ended up decoded
+ * on the device and the caller stages the batch as usual. */
+typedef struct {
+    char **paths;
+    uint8_t **bytes; /* the files, whole; NULL: unreadable */
+    size_t *lengths;
+    bip_jpeg_info *infos;
+    bcnn_hip_jpeg_frame *frames; /* ncomp 0: not a device candidate */
+    int16_t **coeff;
+    int *status;
+} list_batch;
+
+static void list_batch_free(list_batch *lb, int n) {
+    for (int i = 0; i < n; ++i) {
+        if (lb->paths) free(lb->paths[i]);
+        if (lb->bytes) free(lb->bytes[i]);
+    }
+    free(lb->paths); free(lb->bytes); free(lb->lengths); free(lb->infos); free(lb->frames); free(lb->coeff); free(lb->status);
+}
+
+/* the whole file as bip_load_image reads it; NULL when it cannot be read */
+static uint8_t *read_file(const char *path, size_t *len) {
+    FILE *fp = fopen(path, "rb");
+    if (!fp) return NULL;
+    fseek(fp, 0, SEEK_END);
+    const long size = ftell(fp);
+    fseek(fp, 0, SEEK_SET);
+    uint8_t *buf = (size > 0 && size < (1L << 30)) ? (uint8_t *)malloc((size_t)size) : NULL;
+    if (buf && fread(buf, 1, (size_t)size, fp) != (size_t)size) {
+        free(buf);
+        buf = NULL;
+    }
+    fclose(fp);
+    *len = buf ? (size_t)size : 0;
+    return buf;
+}
+
+static bcnn_status list_batch_decoded(bcnn_net *net, bcnn_loader *it, loader_stage *ls, int *launched) {
+    bcnn_hip_context *hc = (bcnn_hip_context *)net->hip_ctx;
+    bcnn_tensor *in = &net->tensors[0];
+    const int n = net->batch_size, w = in->w, h = in->h, c = in->c;
+    const int classif = it->type == BCNN_LOAD_CLASSIFICATION_LIST;
+    *launched = 0;
+    list_batch lb;
+    lb.paths = (char **)calloc((size_t)n, sizeof(char *));
+    lb.bytes = (uint8_t **)calloc((size_t)n, sizeof(uint8_t *));
+    lb.lengths = (size_t *)calloc((size_t)n, sizeof(size_t));
+    lb.infos = (bip_jpeg_info *)calloc((size_t)n, sizeof(bip_jpeg_info));
+    lb.frames = (bcnn_hip_jpeg_frame *)calloc((size_t)n, sizeof(bcnn_hip_jpeg_frame));
+    lb.coeff = (int16_t **)calloc((size_t)n, sizeof(int16_t *));
+    lb.status = (int *)calloc((size_t)n, sizeof(int));
+    if (!lb.paths || !lb.bytes || !lb.lengths || !lb.infos || !lb.frames || !lb.coeff || !lb.status) {
+        list_batch_free(&lb, n);
+        return BCNN_FAILED_ALLOC;
+    }
+    /* ---- phase 1: lines, labels, files, headers */
+    int count = 0, failures = 0, candidates = 0, gave_up = 0;
+    while (count < n) {
+        char **tok = NULL;
+        const int nt = next_line_tokens(it->f_current, &tok);
+        int accepted = nt > 0;
+        if (nt <= 0) {
+            bcnn_log(net->log_ctx, BCNN_LOG_ERROR, "Invalid regression format\n");
+        } else if (classif && net->mode != BCNN_MODE_PREDICT && nt != 2) {
+            bcnn_log(net->log_ctx, BCNN_LOG_WARNING, "Unexpected classif format. Found label size of %d, expected %d.\n", nt - 1, 1);
+            free_tokens(tok, nt);
+            accepted = 0;
+        }
+        if (!accepted) {
+            if (++failures >= 1000) {
+                bcnn_log(net->log_ctx, BCNN_LOG_ERROR, "bcnn_loader_next: 1000 samples in a row could not be read\n");
+                gave_up = 1; /* the samples accepted so far still make their draws, as they have on the host path */
+                break;
+            }
+            continue;
+        }
+        failures = 0;
+        if (net->mode != BCNN_MODE_PREDICT) {
+            int sz;
+            float *y = label_slot(net, count, &sz);
+            if (classif) {
+                const int cls = atoi(tok[1]);
+                if (cls >= 0 && cls < sz) y[cls] = 1;
+            } else {
+                if (nt - 1 != sz)
+                    bcnn_log(net->log_ctx, BCNN_LOG_WARNING, "Unexpected label format. Found label size of %d, expected %d.\n", nt - 1, sz);
+                for (int i = 0; i < nt - 1 && i < sz; ++i) y[i] = (float)atof(tok[i + 1]);
+            }
+        }
+        lb.paths[count] = tok[0];
+        tok[0] = NULL;
+        free_tokens(tok, nt);
+        lb.bytes[count] = read_file(lb.paths[count], &lb.lengths[count]);
+        if (lb.bytes[count] && bip_jpeg_frame_info(lb.bytes[count], lb.lengths[count], &lb.infos[count]) == BIP_SUCCESS &&
+            lb.infos[count].ncomp == c) {
+            bcnn_jpeg_frame_from_info(&lb.infos[count], &lb.frames[count]);
+            ++candidates;
+        }
+        ++count;
+    }
+    /* ---- phase 2: entropy decoding into the staging block. A batch that does not fit it (2 GiB) and a frame the device
+     * side refuses get no coeff[] and are decoded below like every other file. */
+    int staged = candidates > 0 && !gave_up &&
+                 bcnn_hip_augment_jpeg_begin(in->n, c, h, w, count, lb.frames, lb.coeff) == 0;
+    if (staged && bcnn_jpeg_read_batch_each(count, (const uint8_t *const *)lb.bytes, lb.lengths, lb.infos, lb.coeff,
+                                            net->num_threads, lb.status) != 0) {
+        bcnn_hip_augment_jpeg_cancel();
+        staged = 0;
+    }
+    /* ---- phase 3: the draws, in the reference's order */
+    int on_device = 0;
+    memset(ls->decoded, 0, (size_t)n);
+    for (int i = 0; i < count; ++i) {
+        int *x_shift = net->data_aug ? &net->data_aug->shift_x : NULL, *y_shift = net->data_aug ? &net->data_aug->shift_y : NULL;
+        if (staged && lb.coeff[i] && lb.status[i]) {
+            int x_ul, y_ul;
+            crop_origin(net, lb.infos[i].width, lb.infos[i].height, w, h, &x_ul, &y_ul);
+            if (x_shift) { *x_shift = x_ul; *y_shift = y_ul; }
+            ls->decoded[i] = 1;
+            ls->origins[2 * i] = x_ul;
+            ls->origins[2 * i + 1] = y_ul;
+            drop_lazy(ls); /* the bytes that rebuild this sample on the host, should the next one fail */
+            ls->lazy = lb.bytes[i];
+            ls->lazy_len = lb.lengths[i];
+            ls->lazy_x = x_ul;
+            ls->lazy_y = y_ul;
+            lb.bytes[i] = NULL;
+            ls->owed = 0;
+            stage_draws(net, ls, i, w, h, 1);
+            ++on_device;
+            continue;
+        }
+        int wi = 0, hi = 0, ci = 0;
+        unsigned char *buf = NULL;
+        if (lb.bytes[i]) bip_load_image_from_memory(lb.bytes[i], (int)lb.lengths[i], &buf, &wi, &hi, &ci);
+        if (place_decoded(net, lb.paths[i], buf, wi, hi, ci, w, h, c, it->input_uchar, x_shift, y_shift) != BCNN_SUCCESS) {
+            settle_owed(net, it); /* the buffer as the host path would have left it */
+        } else {
+            ls->owed = 0;
+            drop_lazy(ls);
+        }
+        stage_sample(net, it, ls, i, w, h, c, 1);
+    }
+    bcnn_status st = BCNN_SUCCESS;
+    if (gave_up) {
+        st = BCNN_INVALID_DATA;
+    } else if (staged && on_device == 0) {
+        bcnn_hip_augment_jpeg_cancel();
+    } else if (staged) {
+        if (bcnn_hip_augment_jpeg_run(in->data_gpu, ls->decoded, ls->pixels, ls->records, ls->taps, ls->origins,
+                                      net->data_aug ? net->data_aug->swap_to_bgr : 0) != 0) {
+            bcnn_log(net->log_ctx, BCNN_LOG_ERROR, "bcnn_loader_next: the batch does not fit the device loader path\n");
+            st = BCNN_INVALID_PARAMETER;
+        } else {
+            *launched = 1;
+            hc->loader_device_decoded = on_device;
+        }
+    }
+    list_batch_free(&lb, n);
+    return st;
 }
 
 /* ---- detection list: "image-path (class x y w h)*" lines (bcnn_detection_loader.c) --------------------------------- */
@@ -780,6 +1013,7 @@ void bcnn_destroy_data_loader(bcnn_net *net) {
 bcnn_status bcnn_set_data_loader(bcnn_net *net, bcnn_loader_type type, const char *train_path_data,
                                  const char *train_path_extra, const char *test_path_data, const char *test_path_extra) {
     bcnn_destroy_data_loader(net);
+    if (stage_of(net)) drop_lazy(stage_of(net)); /* a sample of the loader that is gone */
     int detector = bcnn_get_detector_training(net); /* or a net that already holds a head (bcnn-cl in PREDICT / VALID mode) */
     for (int i = 0; !detector && i < net->num_nodes; ++i) detector = net->nodes[i].type == BCNN_LAYER_YOLOV3;
     if ((type == BCNN_LOAD_DETECTION_LIST && !detector) || (int)type < 0 || (int)type >= BCNN_NUM_LOADERS) {
@@ -810,7 +1044,17 @@ bcnn_status bcnn_set_data_loader(bcnn_net *net, bcnn_loader_type type, const cha
 bcnn_status bcnn_loader_next(bcnn_net *net) {
     bcnn_loader *it = net->data_loader;
     loader_stage *ls = it ? stage_begin(net, it) : NULL; /* non-NULL: the input batch is made on the device */
-    if (it) {
+    bcnn_hip_context *hc = (bcnn_hip_context *)net->hip_ctx;
+    int launched = 0; /* list_batch_decoded has queued the batch already */
+    hc->loader_device_decoded = 0;
+    if (ls && hc->loader_decode_on_device && (net->tensors[0].c == 1 || net->tensors[0].c == 3) &&
+        (it->type == BCNN_LOAD_CLASSIFICATION_LIST || it->type == BCNN_LOAD_REGRESSION_LIST)) {
+        const bcnn_status st = list_batch_decoded(net, it, ls, &launched);
+        if (st != BCNN_SUCCESS) {
+            ls->active = 0;
+            return st;
+        }
+    } else if (it) {
         int failures = 0;
         for (int i = 0; i < net->batch_size; ++i) {
             bcnn_status st;
@@ -833,9 +1077,9 @@ bcnn_status bcnn_loader_next(bcnn_net *net) {
             failures = 0;
         }
     }
-    if (ls) { /* one copy of the raw samples and their records, two launches; tensors[0].data is not written */
+    if (ls) ls->active = 0;
+    if (ls && !launched) { /* one copy of the raw samples and their records, two launches; tensors[0].data is not written */
         bcnn_tensor *in = &net->tensors[0];
-        ls->active = 0;
         const int list_loader = it->type != BCNN_LOAD_MNIST && it->type != BCNN_LOAD_CIFAR10;
         if (bcnn_hip_augment_batch(in->data_gpu, in->n, in->c, in->h, in->w, net->batch_size, ls->w, ls->h, ls->pixels,
                                    ls->records, ls->taps, list_loader && net->data_aug ? net->data_aug->swap_to_bgr : 0) != 0)

@@ -16,15 +16,18 @@ typedef struct {
     int16_t *const *coeff;
     int num_images, first, step;
     int failed; /* lowest index of this worker's images that failed, or num_images */
+    int *status; /* per image (bcnn_jpeg_read_batch_each), or NULL */
 } jpeg_worker;
 
 static void *jpeg_worker_run(void *arg) {
     jpeg_worker *w = (jpeg_worker *)arg;
     /* no early exit: what each coeff[b] holds afterwards does not depend on the number of workers */
-    for (int b = w->first; b < w->num_images; b += w->step)
-        if (bip_jpeg_read_coefficients(w->buffers[b], w->lengths[b], &w->infos[b], w->coeff[b]) != BIP_SUCCESS &&
-            b < w->failed)
-            w->failed = b;
+    for (int b = w->first; b < w->num_images; b += w->step) {
+        if (w->status && !w->coeff[b]) continue; /* not this routine's image */
+        const int ok = bip_jpeg_read_coefficients(w->buffers[b], w->lengths[b], &w->infos[b], w->coeff[b]) == BIP_SUCCESS;
+        if (w->status) w->status[b] = ok;
+        if (!ok && b < w->failed) w->failed = b;
+    }
     return NULL;
 }
 
@@ -32,14 +35,14 @@ static void *jpeg_worker_run(void *arg) {
  * thread t of T = num_threads; with T <= 1 on the calling thread alone. Returns the lowest index that failed to decode,
  * -1 when all decoded, or -2 when the routine's own bookkeeping could not be allocated (nothing was decoded). The bytes
  * written are the same for every T. */
-int bcnn_jpeg_read_batch(int num_images, const uint8_t *const *buffers, const size_t *lengths, const bip_jpeg_info *infos,
-                         int16_t *const *coeff, int num_threads) {
+static int read_batch(int num_images, const uint8_t *const *buffers, const size_t *lengths, const bip_jpeg_info *infos,
+                      int16_t *const *coeff, int num_threads, int *status) {
     int T = num_threads < 1 ? 1 : (num_threads > num_images ? num_images : num_threads);
     jpeg_worker *workers = (jpeg_worker *)calloc((size_t)T, sizeof(jpeg_worker));
     pthread_t *threads = (pthread_t *)calloc((size_t)T, sizeof(pthread_t));
     if (!workers || !threads) { free(workers); free(threads); return -2; }
     for (int t = 0; t < T; ++t) {
-        jpeg_worker w = {buffers, lengths, infos, coeff, num_images, t, T, num_images};
+        jpeg_worker w = {buffers, lengths, infos, coeff, num_images, t, T, num_images, status};
         workers[t] = w;
     }
     int started = 0;
@@ -57,6 +60,33 @@ int bcnn_jpeg_read_batch(int num_images, const uint8_t *const *buffers, const si
     free(workers);
     free(threads);
     return failed < num_images ? failed : -1;
+}
+
+int bcnn_jpeg_read_batch(int num_images, const uint8_t *const *buffers, const size_t *lengths, const bip_jpeg_info *infos,
+                         int16_t *const *coeff, int num_threads) {
+    return read_batch(num_images, buffers, lengths, infos, coeff, num_threads, NULL);
+}
+
+/* The same with a status PER IMAGE, for a caller that goes on with the images that decoded (the list loaders): images
+ * with coeff[b] == NULL are skipped and keep their status[b]; the others get status[b] = 1 (decoded) or 0. Returns 0, or
+ * -2 when the bookkeeping could not be allocated (nothing was decoded, status untouched). */
+int bcnn_jpeg_read_batch_each(int num_images, const uint8_t *const *buffers, const size_t *lengths,
+                              const bip_jpeg_info *infos, int16_t *const *coeff, int num_threads, int *status) {
+    if (!status || num_images < 1) return num_images < 1 ? 0 : -2;
+    return read_batch(num_images, buffers, lengths, infos, coeff, num_threads, status) == -2 ? -2 : 0;
+}
+
+/* what libbcnn_hip.so needs of a parsed frame header (it does not depend on libbip.so) */
+void bcnn_jpeg_frame_from_info(const bip_jpeg_info *info, bcnn_hip_jpeg_frame *f) {
+    memset(f, 0, sizeof(*f));
+    f->width = info->width; f->height = info->height; f->ncomp = info->ncomp;
+    f->hmax = info->hmax; f->vmax = info->vmax;
+    for (int k = 0; k < info->ncomp && k < 3; ++k) {
+        const bip_jpeg_component *s = &info->comp[k];
+        bcnn_hip_jpeg_component *d = &f->comp[k];
+        d->h = s->h; d->v = s->v; d->width = s->width; d->height = s->height; d->pitch = s->pitch; d->rows = s->rows;
+        d->blocks_w = s->blocks_w; d->blocks_h = s->blocks_h; d->idct_w = s->idct_w; d->idct_h = s->idct_h;
+    }
 }
 
 bcnn_status bcnn_fill_tensor_with_jpegs(bcnn_net *net, int tensor_index, int num_images, const uint8_t *const *buffers,
@@ -96,15 +126,7 @@ bcnn_status bcnn_fill_tensor_with_jpegs(bcnn_net *net, int tensor_index, int num
             failed = b;
             goto done;
         }
-        bcnn_hip_jpeg_frame *f = &frames[b];
-        f->width = infos[b].width; f->height = infos[b].height; f->ncomp = infos[b].ncomp;
-        f->hmax = infos[b].hmax; f->vmax = infos[b].vmax;
-        for (int k = 0; k < infos[b].ncomp; ++k) {
-            const bip_jpeg_component *s = &infos[b].comp[k];
-            bcnn_hip_jpeg_component *d = &f->comp[k];
-            d->h = s->h; d->v = s->v; d->width = s->width; d->height = s->height; d->pitch = s->pitch; d->rows = s->rows;
-            d->blocks_w = s->blocks_w; d->blocks_h = s->blocks_h; d->idct_w = s->idct_w; d->idct_h = s->idct_h;
-        }
+        bcnn_jpeg_frame_from_info(&infos[b], &frames[b]);
     }
     /* ---- the staging block: refused as a whole when an extent comes out empty or the block would pass 2 GiB */
     if (bcnn_hip_jpeg_stage_begin(t->n, t->c, t->h, t->w, num_images, frames, fit, coeff, &failed) != 0) {

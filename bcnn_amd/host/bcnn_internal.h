@@ -172,6 +172,9 @@ typedef struct bcnn_hip_context {
     int inference_precision; /* bcnn_set_inference_precision (a bcnn_precision); read by the convolution node outside TRAIN mode */
     int loader_on_device; /* bcnn_set_loader_on_device: bcnn_loader_next makes the input batch with bcnn_hip_augment_batch */
     void *loader_stage;   /* its host-side gather block (bcnn_data.c: loader_stage); freed by bcnn_free_loader_stage */
+    int loader_decode_on_device; /* bcnn_set_loader_decode_on_device: JPEG entries of a list batch that goes the device way
+                                  * are entropy-decoded on the host and become pixels on the device only */
+    int loader_device_decoded;   /* samples of the latest bcnn_loader_next whose pixels were decoded on the device */
     int detector_training; /* bcnn_set_detector_training: YOLO heads may be built on / switched to TRAIN, with their loss */
     int detect_capacity; /* 1.25 x the most boxes an image of the latest bcnn_yolo_get_detections_batch had: the next call's record capacity
                           * when above the default (0: never called) */
@@ -508,6 +511,11 @@ void bcnn_link_batchnorm_conv(bcnn_net *net);
  * the number of threads. */
 int bcnn_jpeg_read_batch(int num_images, const uint8_t *const *buffers, const size_t *lengths, const bip_jpeg_info *infos,
                          int16_t *const *coeff, int num_threads);
+struct bcnn_hip_jpeg_frame;
+void bcnn_jpeg_frame_from_info(const bip_jpeg_info *info, struct bcnn_hip_jpeg_frame *f);
+/* per-image form: coeff[b] == NULL skips image b; status[b] = 1 / 0 for the others; 0, or -2 (allocation) */
+int bcnn_jpeg_read_batch_each(int num_images, const uint8_t *const *buffers, const size_t *lengths,
+                              const bip_jpeg_info *infos, int16_t *const *coeff, int num_threads, int *status);
 void bcnn_materialize_data(bcnn_net *net, int tensor);      /* tensor < 0: every pending one */
 void bcnn_materialize_gradients(bcnn_net *net, int tensor); /* tensor < 0: every pending one */
 void bcnn_drop_pending_gradients(bcnn_net *net);

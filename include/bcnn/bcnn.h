@@ -320,6 +320,24 @@ BCNN_API bcnn_precision bcnn_get_inference_precision(const bcnn_net *net);
  * Config files: `loader_on_device=1` in the [net] section. */
 BCNN_API bcnn_status bcnn_set_loader_on_device(bcnn_net *net, int on);
 BCNN_API int bcnn_get_loader_on_device(const bcnn_net *net);
+/* Where the list loaders decode their JPEG entries (default 0: on the host, one file after the other). With on != 0,
+ * and only for a batch that goes the device way (bcnn_set_loader_on_device, see above) of a BCNN_LOAD_CLASSIFICATION_LIST
+ * or BCNN_LOAD_REGRESSION_LIST loader into an input of 1 or 3 channels, the host reads every file of the batch, parses the
+ * JPEG headers and runs the entropy decoder on bcnn_get_num_threads(net) threads (created and joined inside
+ * bcnn_loader_next; the batch does not depend on their number). Inverse DCT, chroma upsampling, colour conversion and
+ * the crop to the net input (random origin in BCNN_MODE_TRAIN, centred otherwise, drawn on the host in the reference's
+ * order) run on the device in front of the augmentation: decoded pixels never exist on the host. Entries that are not
+ * JPEG streams the decoder covers, whose component count is not the input's channel count, or that fail to decode are
+ * handled as before (PNG / BMP / PNM are decoded on the host; a failed entry repeats the previous sample). The device
+ * tensor and the labels are, bit for bit, those of the host path for the same files, rand() seed and settings. A batch
+ * whose staging block would pass 2 GiB is decoded on the host. Everywhere else the switch has no effect. Any non-zero
+ * value is stored as 1; may be called before a loader exists and between batches; a NULL net returns
+ * BCNN_INVALID_PARAMETER. Config files: `loader_decode_on_device=1` in the [net] section. */
+BCNN_API bcnn_status bcnn_set_loader_decode_on_device(bcnn_net *net, int on);
+BCNN_API int bcnn_get_loader_decode_on_device(const bcnn_net *net);
+/* Number of samples of the latest bcnn_loader_next whose pixels were decoded on the device; 0 for a batch made any other
+ * way, on a fresh net and for a NULL net. */
+BCNN_API int bcnn_get_loader_device_decoded(const bcnn_net *net);
 /* Detections of EVERY image of the batch from the latest forward, in one call. widths[b] / heights[b]: the original
  * size of image b (what bcnn_yolo_get_detections takes as w, h). dets[b] receives a malloc'ed array of num_dets[b]
  * boxes (NULL / 0 when image b has no candidate); per image, the result is what

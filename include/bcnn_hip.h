@@ -763,6 +763,39 @@ int bcnn_hip_augment_batch(float *dst_d, int n, int c, int h, int w, int num_sam
                            int swap_to_bgr);
 
 /* ---------------------------------------------------------------------------------------------
+ * The same batch when some of its samples are still JPEG coefficient blocks (augment.hip + the two kernels of
+ * jpeg_pixels.hip): the list loaders' opt-in device decoding. The stored sample is the net input itself (w x h x c, c 1
+ * or 3); a sample is either a dense w x h x c block of bytes the caller decoded and cropped, or a JPEG frame whose
+ * entropy decoding the caller did and whose pixels exist only on the device. There the sample is the w x h WINDOW at
+ * (x_ul, y_ul) of the decoded wi x hi image: raw byte (x, y, k) = image[((y + y_ul) wi + x + x_ul) c + k] where
+ * 0 <= x + x_ul < wi and 0 <= y + y_ul < hi, else 0 -- bip_crop_image onto a zeroed buffer. The window is S0 of
+ * bcnn_hip_augment_batch: flip, shift, scale, rotation, contrast, brightness and conversion follow unchanged, and the
+ * result is bit for bit what that call gives on the host-decoded, host-cropped samples.
+ *   bcnn_hip_augment_jpeg_begin  frames[b] describes sample b (bcnn_hip_jpeg_frame as for bcnn_hip_jpeg_stage_begin;
+ *       ncomp 0: not a JPEG candidate). Lays the batch out in the pinned staging block of the calling thread (the one
+ *       bcnn_hip_augment_batch uses; it waits for an earlier call's copy) and returns in coeff[b] where the coefficients
+ *       of sample b go, or NULL for a sample the caller has to decode itself (ncomp 0, ncomp != c, numbers that do not
+ *       fit together). Returns 0, or 1 with nothing pending: NULL frames / coeff; n, h or w < 1; c not 1 or 3;
+ *       num_samples outside 1..n; no candidate at all; more than 2 GiB for the device block.
+ *   bcnn_hip_augment_jpeg_run    decoded[b] != 0: the coefficients of sample b are in place and origins[2 b], [2 b + 1]
+ *       is its window's origin; decoded[b] == 0: sample b is pixels + b w h c (the other slots of `pixels` are not read).
+ *       records / taps / swap_to_bgr as for bcnn_hip_augment_batch with src_w = w, src_h = h. ONE copy of the block
+ *       (records, zeroed sums, taps, windows, plane and image tables, the coefficients of every candidate, the raw
+ *       samples) on the current stream, then at most FOUR kernels: jpeg_idct_kernel and jpeg_colour_kernel over the
+ *       decoded samples (none decoded: skipped), the windowed geometry kernel, the convert kernel. Returns 0, or 1 with
+ *       nothing queued and the batch dropped: nothing pending; a NULL argument; decoded[b] set for a sample that got no
+ *       coeff[b]; a record with SCALE and taps == NULL or a tap index out of range.
+ *   bcnn_hip_augment_jpeg_cancel drops the pending batch: nothing has been queued.
+ * Between _begin and _run / _cancel the calling thread makes no other call that stages a training batch.
+ * ------------------------------------------------------------------------------------------- */
+int bcnn_hip_augment_jpeg_begin(int n, int c, int h, int w, int num_samples, const bcnn_hip_jpeg_frame *frames,
+                                int16_t **coeff);
+int bcnn_hip_augment_jpeg_run(float *dst_d, const uint8_t *decoded, const uint8_t *pixels,
+                              const bcnn_hip_augment_record *records, const int32_t *taps, const int32_t *origins,
+                              int swap_to_bgr);
+void bcnn_hip_augment_jpeg_cancel(void);
+
+/* ---------------------------------------------------------------------------------------------
  * Transposed convolution (deconvolution), implicit GEMMs on fp32 MFMA with no col2im / im2col buffer.
  * Replaces bcnn_forward_deconv_layer_gpu / bcnn_backward_deconv_layer_gpu (bcnn_deconv_layer.c:249-320) with the
  * semantics of the CPU workers (:150-193, :195-246):
