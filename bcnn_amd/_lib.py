@@ -131,6 +131,7 @@ SIGNATURES = {
     "bcnn_hip_augment_jpeg_begin": (i, [i, i, i, i, i, vp, vp]),
     "bcnn_hip_augment_jpeg_run": (i, [vp, vp, vp, vp, vp, vp, i]),
     "bcnn_hip_augment_jpeg_cancel": (None, []),
+    "bcnn_hip_augment_letterbox_batch": (i, [vp, i, i, i, i, i, vp, vp, vp, i]),
     "bcnn_hip_deconv_workspace_size": (sz, [i] * 8),
     "bcnn_hip_deconv_forward": (None, [vp, vp, vp, vp] + [i] * 9),
     "bcnn_hip_deconv_backward": (None, [vp] * 7 + [i] * 9 + [vp, sz]),

@@ -119,6 +119,8 @@ def lib():
         "bcnn_set_loader_on_device": (i, [vp, i]), "bcnn_get_loader_on_device": (i, [vp]),
         "bcnn_set_loader_decode_on_device": (i, [vp, i]), "bcnn_get_loader_decode_on_device": (i, [vp]),
         "bcnn_get_loader_device_decoded": (i, [vp]),
+        "bcnn_set_loader_detection_on_device": (i, [vp, i]), "bcnn_get_loader_detection_on_device": (i, [vp]),
+        "bcnn_get_loader_device_letterboxed": (i, [vp]),
         "bcnn_set_detector_training": (i, [vp, i]), "bcnn_get_detector_training": (i, [vp]),
         "bcnn_yolo_get_train_stats": (i, [vp, i, C.POINTER(YoloTrainStats)]),
         "bcnn_set_data_loader": (i, [vp, i, cp, cp, cp, cp]),
@@ -310,6 +312,19 @@ class Net:
     def loader_device_decoded(self):
         """bcnn_get_loader_device_decoded: samples of the latest bcnn_loader_next whose pixels were decoded on the device"""
         return self.L.bcnn_get_loader_device_decoded(self.net)
+
+    def set_loader_detection_on_device(self, on):
+        """bcnn_set_loader_detection_on_device: with set_loader_on_device, a detection-list batch is resized, pasted on
+        its grey canvas, augmented and converted on the device; the host decodes the files (on set_num_threads() threads),
+        makes the draws and writes the labels. Same batch, labels and rand() state, bit for bit. Returns the bcnn_status."""
+        return self.L.bcnn_set_loader_detection_on_device(self.net, 1 if on else 0)
+
+    def get_loader_detection_on_device(self):
+        return self.L.bcnn_get_loader_detection_on_device(self.net)
+
+    def loader_device_letterboxed(self):
+        """bcnn_get_loader_device_letterboxed: samples of the latest bcnn_loader_next that were letterboxed on the device"""
+        return self.L.bcnn_get_loader_device_letterboxed(self.net)
 
     def set_detector_training(self, on):
         """bcnn_set_detector_training: YOLO heads may be built on a TRAIN net (or switched to TRAIN), their TRAIN forward

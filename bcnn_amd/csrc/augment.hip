@@ -21,6 +21,11 @@
 // JPEG coefficient blocks: the two kernels of jpeg_pixels.hip decode them behind the uploaded part of the block, and the
 // windowed form of the geometry kernel reads every sample through an AugWindow, which is the list loaders' crop to the
 // net input. One copy, at most four launches.
+//
+// bcnn_hip_augment_letterbox_batch makes it when every sample is a decoded image of its own size:
+// augment_letterbox_kernel resizes each (bip_resize_bilinear's rule, taps tabulated on the host side of the entry) and
+// pastes it on a canvas of 128 behind the uploaded part of the block; the canvases are the raw samples of the two kernels
+// above. One copy, three launches.
 #include "common.h"
 
 #include <cstdint>
@@ -166,6 +171,72 @@ __global__ __launch_bounds__(kAugBlock) void augment_geometry_kernel(uint8_t* __
             for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
             if ((threadIdx.x & 63) == 0) atomicAdd(&sums[k], t);
         }
+    }
+}
+
+// bcnn_hip_augment_letterbox_batch: one source image of the batch, in image_fill.h's ImageDesc shape (that header's
+// host_stage is image_fill.hip's own block, so the struct is restated here). Offsets count from the block's first byte.
+struct LetterboxDesc {
+    uint32_t data_off;            // packed pixels: h rows of w * c bytes
+    uint32_t tapx_off, tapy_off;  // int2 (index, frac) per column of the resized image / per row
+    int w, h;                     // source extent
+    int new_w, new_h;             // extent of the resized image inside the W x H canvas
+    int x_off, y_off;             // where it is pasted; everything outside is kCanvas
+};
+struct LetterboxParams {
+    uint32_t desc_off, canvas_off;  // the descriptors; the canvases, dense W x H x C each (AugParams::pix_off)
+    int W, H;
+    int chunks_per_row, blocks_per_sample;
+};
+constexpr int kChunk = 16;  // canvas bytes per lane: one 16-byte store
+
+// The canvases of the whole batch: 128, and the resized image where it is pasted. A lane owns the part of one canvas row
+// that falls into one 16-byte-aligned chunk of the block, so every chunk inside a row goes out as one aligned 16-byte
+// store and only the two chunks a row shares with its neighbours are written byte by byte. Integer work only.
+template <int C>
+__global__ __launch_bounds__(kAugBlock) void augment_letterbox_kernel(uint8_t* __restrict__ block, LetterboxParams p) {
+    const int b = blockIdx.x / p.blocks_per_sample;
+    const int lane = (blockIdx.x - b * p.blocks_per_sample) * kAugBlock + threadIdx.x;
+    const int y = lane / p.chunks_per_row;
+    if (y >= p.H) return;
+    const int row_bytes = p.W * C;
+    const uint32_t row_at = p.canvas_off + (uint32_t)(((size_t)b * p.H + y) * row_bytes);  // below 2 GiB: checked
+    const uint32_t chunk_at = (row_at & ~(uint32_t)(kChunk - 1)) + (uint32_t)(lane - y * p.chunks_per_row) * kChunk;
+    // bytes [first, last) of the chunk belong to this row; q0 is the row byte of the chunk's byte 0 (may be negative)
+    const int q0 = (int)chunk_at - (int)row_at;
+    const int first = q0 < 0 ? -q0 : 0, last = min(kChunk, row_bytes - q0);
+    if (first >= last) return;
+    const LetterboxDesc d = reinterpret_cast<const LetterboxDesc*>(block + p.desc_off)[b];
+    uint32_t word[kChunk / 4];
+#pragma unroll
+    for (int i = 0; i < kChunk / 4; ++i) word[i] = 0x01010101u * kCanvas;
+    const int yr = y - d.y_off;
+    if (yr >= 0 && yr < d.new_h) {
+        const int2 ty = reinterpret_cast<const int2*>(block + d.tapy_off)[yr];  // the row's tap, once
+        const int2* __restrict__ tapx = reinterpret_cast<const int2*>(block + d.tapx_off);
+        const size_t src_row = (size_t)d.w * C;
+        const uint8_t* __restrict__ r0 = block + d.data_off + (size_t)ty.x * src_row;
+        const uint8_t* __restrict__ r1 = r0 + (d.h > 1 ? src_row : 0);  // a one-row source replicates
+        const int step = d.w > 1 ? C : 0;                               // and so does a one-column source
+#pragma unroll
+        for (int i = 0; i < kChunk; ++i) {
+            const int q = q0 + i;
+            if (i < first || i >= last) continue;
+            const int x = q / C, k = q - x * C, xr = x - d.x_off;
+            if (xr < 0 || xr >= d.new_w) continue;
+            const int2 tx = tapx[xr];
+            const int at = tx.x * C + k;
+            const uint32_t v = bip_resize_blend(r0[at], r0[at + step], r1[at], r1[at + step], tx.y, ty.y);
+            word[i / 4] = (word[i / 4] & ~(0xffu << (8 * (i % 4)))) | (v << (8 * (i % 4)));
+        }
+    }
+    uint8_t* __restrict__ out = block + chunk_at;
+    if (first == 0 && last == kChunk) {
+        *reinterpret_cast<uint4*>(out) = make_uint4(word[0], word[1], word[2], word[3]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < kChunk; ++i)
+            if (i >= first && i < last) out[i] = (uint8_t)(word[i / 4] >> (8 * (i % 4)));
     }
 }
 
@@ -320,6 +391,109 @@ int bcnn_hip_augment_batch(float* dst_d, int n, int c, int h, int w, int num_sam
     p.W = w;
     p.cx = (src_w - w) / 2;
     p.cy = (src_h - h) / 2;
+    p.swap = (swap_to_bgr && c == 3) ? 1 : 0;
+    p.blocks_per_sample = p.runs_per_row = 0;
+    p.win_off = 0;
+    switch (c) {
+        case 1: launch<1>(block_d, dst_d, p, num_samples, st); break;
+        case 2: launch<2>(block_d, dst_d, p, num_samples, st); break;
+        case 3: launch<3>(block_d, dst_d, p, num_samples, st); break;
+        default: launch<4>(block_d, dst_d, p, num_samples, st); break;
+    }
+    return 0;
+}
+
+int bcnn_hip_augment_letterbox_batch(float* dst_d, int n, int c, int h, int w, int num_samples,
+                                     const bcnn_hip_letterbox_image* images, const bcnn_hip_augment_record* records,
+                                     const int32_t* taps, int swap_to_bgr) {
+    if (!dst_d || !images || !records || n < 1 || h < 1 || w < 1 || c < 1 || c > 4 || num_samples < 1 || num_samples > n ||
+        (long long)w * h > 0x7fffffff / (c * (long long)num_samples))
+        return 1;
+    // ---- every refusal comes before anything is staged or queued
+    const size_t num = (size_t)num_samples, sample_bytes = (size_t)w * h * c, sample_taps = (size_t)w + h;
+    bool any_scale = false;
+    size_t lb_tap_bytes = 0, src_bytes = 0;
+    for (size_t b = 0; b < num; ++b) {
+        const bcnn_hip_letterbox_image& im = images[b];
+        if (!im.pixels || im.w < 1 || im.h < 1 || im.new_w < 1 || im.new_w > w || im.new_h < 1 || im.new_h > h ||
+            im.x_off < 0 || im.x_off > w - im.new_w || im.y_off < 0 || im.y_off > h - im.new_h ||
+            (long long)im.w * im.h > 0x7fffffff / c)
+            return 1;
+        any_scale = any_scale || (records[b].flags & BCNN_HIP_AUG_SCALE);
+        lb_tap_bytes += ((size_t)im.new_w + im.new_h) * sizeof(int2);
+        src_bytes += align_up((size_t)im.w * im.h * c, 16);
+        if (src_bytes > (size_t)0x7fffffff) return 1;
+    }
+    if (any_scale && !taps) return 1;
+    const size_t rec_bytes = align_up(num * sizeof(bcnn_hip_augment_record), 16), sum_bytes = num * 4 * sizeof(uint32_t);
+    const size_t tap_bytes = any_scale ? align_up(num * sample_taps * 2 * sizeof(int32_t), 16) : 0;
+    const size_t desc_bytes = align_up(num * sizeof(LetterboxDesc), 16);
+    const size_t canvas_bytes = align_up(num * sample_bytes, 16);
+    const size_t desc_at = rec_bytes + sum_bytes + tap_bytes, lb_tap_at = desc_at + desc_bytes;
+    const size_t src_at = lb_tap_at + align_up(lb_tap_bytes, 16), total = src_at + src_bytes;
+    if (total + 2 * canvas_bytes > (size_t)0x7fffffff) return 1;
+    if (any_scale && !taps_in_range(records, taps, num, w, h)) return 1;
+
+    // the staging block: [records][channel sums, zero][augmentation taps][descriptors][letterbox taps][source pixels];
+    // behind it on the device, the canvases and the rotated samples
+    uint8_t* stage = host_stage(total);
+    memcpy(stage, records, num * sizeof(bcnn_hip_augment_record));
+    memset(stage + rec_bytes, 0, sum_bytes);
+    if (any_scale) memcpy(stage + rec_bytes + sum_bytes, taps, num * sample_taps * 2 * sizeof(int32_t));
+    else  // no tap table was staged: no record may ask for one
+        for (size_t b = 0; b < num; ++b) reinterpret_cast<bcnn_hip_augment_record*>(stage)[b].flags &= ~BCNN_HIP_AUG_SCALE;
+    LetterboxDesc* desc = reinterpret_cast<LetterboxDesc*>(stage + desc_at);
+    size_t tap_at = lb_tap_at, pix_at = src_at;
+    for (size_t b = 0; b < num; ++b) {
+        const bcnn_hip_letterbox_image& im = images[b];
+        LetterboxDesc& d = desc[b];
+        d.w = im.w; d.h = im.h; d.new_w = im.new_w; d.new_h = im.new_h; d.x_off = im.x_off; d.y_off = im.y_off;
+        d.tapx_off = (uint32_t)tap_at;
+        d.tapy_off = (uint32_t)(tap_at + (size_t)im.new_w * sizeof(int2));
+        int2* tx = reinterpret_cast<int2*>(stage + d.tapx_off);
+        int2* ty = reinterpret_cast<int2*>(stage + d.tapy_off);
+        const float xs = bip_resize_scale((size_t)im.w, (size_t)im.new_w), ys = bip_resize_scale((size_t)im.h, (size_t)im.new_h);
+        for (int x = 0; x < im.new_w; ++x) bip_resize_tap((size_t)x, xs, (size_t)im.w, &tx[x].x, &tx[x].y);
+        for (int y = 0; y < im.new_h; ++y) bip_resize_tap((size_t)y, ys, (size_t)im.h, &ty[y].x, &ty[y].y);
+        tap_at += ((size_t)im.new_w + im.new_h) * sizeof(int2);
+        d.data_off = (uint32_t)pix_at;
+        memcpy(stage + pix_at, im.pixels, (size_t)im.w * im.h * c);
+        pix_at += align_up((size_t)im.w * im.h * c, 16);
+    }
+
+    // ---- one copy, three launches
+    uint8_t* block_d = reinterpret_cast<uint8_t*>(scratch(SCRATCH_AUGMENT, (total + 2 * canvas_bytes + 3) / 4));
+    hipStream_t st = current_stream();
+    HIP_CHECK(hipMemcpyAsync(block_d, stage, total, hipMemcpyHostToDevice, st));
+    HostStage& hs = g_stage[current_device()];
+    HIP_CHECK(hipEventRecord(hs.copied, st));
+    hs.in_flight = true;
+
+    LetterboxParams lp;
+    lp.desc_off = (uint32_t)desc_at;
+    lp.canvas_off = (uint32_t)total;
+    lp.W = w;
+    lp.H = h;
+    lp.chunks_per_row = (w * c + 2 * (kChunk - 1)) / kChunk;  // a row may begin and end inside a chunk
+    lp.blocks_per_sample = ceil_div((long long)lp.chunks_per_row * h, kAugBlock);
+    const dim3 grid((unsigned)(lp.blocks_per_sample * num_samples));
+    switch (c) {
+        case 1: augment_letterbox_kernel<1><<<grid, kAugBlock, 0, st>>>(block_d, lp); break;
+        case 2: augment_letterbox_kernel<2><<<grid, kAugBlock, 0, st>>>(block_d, lp); break;
+        case 3: augment_letterbox_kernel<3><<<grid, kAugBlock, 0, st>>>(block_d, lp); break;
+        default: augment_letterbox_kernel<4><<<grid, kAugBlock, 0, st>>>(block_d, lp); break;
+    }
+    KERNEL_CHECK();
+
+    AugParams p;
+    p.rec_off = 0;
+    p.sum_off = (uint32_t)rec_bytes;
+    p.tap_off = (uint32_t)(rec_bytes + sum_bytes);
+    p.pix_off = (uint32_t)total;
+    p.s4_off = (uint32_t)(total + canvas_bytes);
+    p.sw = p.W = w;
+    p.sh = p.H = h;
+    p.cx = p.cy = 0;
     p.swap = (swap_to_bgr && c == 3) ? 1 : 0;
     p.blocks_per_sample = p.runs_per_row = 0;
     p.win_off = 0;

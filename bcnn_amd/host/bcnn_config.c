@@ -130,6 +130,7 @@ static void net_set_param(bcnn_net *net, const char *name, const char *val) {
     }
     else if (!strcmp(name, "loader_on_device")) bcnn_set_loader_on_device(net, atoi(val));
     else if (!strcmp(name, "loader_decode_on_device")) bcnn_set_loader_decode_on_device(net, atoi(val));
+    else if (!strcmp(name, "loader_detection_on_device")) bcnn_set_loader_detection_on_device(net, atoi(val));
     else if (!strcmp(name, "train_detector")) bcnn_set_detector_training(net, atoi(val));
     else if (ln && !strcmp(name, "max_batches")) ln->max_batches = atoi(val);
     else if (ln && (!strcmp(name, "learning_policy") || !strcmp(name, "decay_type"))) {

@@ -734,6 +734,20 @@ int bcnn_get_loader_device_decoded(const bcnn_net *net) {
     return net ? ((const bcnn_hip_context *)net->hip_ctx)->loader_device_decoded : 0;
 }
 
+bcnn_status bcnn_set_loader_detection_on_device(bcnn_net *net, int on) {
+    if (!net) return BCNN_INVALID_PARAMETER;
+    hctx(net)->loader_detection_on_device = on ? 1 : 0;
+    return BCNN_SUCCESS;
+}
+
+int bcnn_get_loader_detection_on_device(const bcnn_net *net) {
+    return net ? ((const bcnn_hip_context *)net->hip_ctx)->loader_detection_on_device : 0;
+}
+
+int bcnn_get_loader_device_letterboxed(const bcnn_net *net) {
+    return net ? ((const bcnn_hip_context *)net->hip_ctx)->loader_device_letterboxed : 0;
+}
+
 bcnn_status bcnn_set_detector_training(bcnn_net *net, int on) {
     if (!net) return BCNN_INVALID_PARAMETER;
     hctx(net)->detector_training = on ? 1 : 0;

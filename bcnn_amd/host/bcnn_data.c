@@ -8,7 +8,11 @@
  *                             with bcnn_set_loader_on_device the host only reads, decodes and draws; the raw samples and one
  *                             record each go up in one copy and ../csrc/augment.hip makes the float batch (same bits);
  *                             with bcnn_set_loader_decode_on_device as well, the JPEG entries of a list batch go up as
- *                             coefficient blocks and are decoded and cropped there too (list_batch_decoded below)
+ *                             coefficient blocks and are decoded and cropped there too (list_batch_decoded below);
+ *                             with bcnn_set_loader_detection_on_device a detection-list batch goes up as the decoded images
+ *                             (decoded on the net's host threads) and is resized, pasted on its canvas and augmented there
+ *                             (detection_batch_device below). Nothing reads it->input_net / it->input_uchar for that loader
+ *                             type between samples, so that path writes neither of them, nor tensors[0].data
  *   bcnn_augment_data_with_*  augmentation ranges; bcnn_apply_data_augmentation draws the parameters of one sample from
  *                             libc rand() in the reference's order (flip, shift, scale, rotation, contrast, brightness), so
  *                             that a run seeded like a reference run sees the same samples byte for byte
@@ -31,6 +35,7 @@
  * augmentations stay aligned; the image is left untouched and a warning is printed once.
  */
 #include <math.h>
+#include <pthread.h>
 #include <string.h>
 
 #include <bh/bh_string.h>
@@ -331,7 +336,7 @@ static void settle_owed(bcnn_net *net, bcnn_loader *it) {
 static loader_stage *stage_begin(bcnn_net *net, bcnn_loader *it) {
     bcnn_hip_context *hc = (bcnn_hip_context *)net->hip_ctx;
     bcnn_tensor *in = &net->tensors[0];
-    if (it->type == BCNN_LOAD_DETECTION_LIST) return NULL; /* the letterbox and its labels are made on the host */
+    if (it->type == BCNN_LOAD_DETECTION_LIST) return NULL; /* no block of equal samples: detection_batch_device, or the host */
     if (!hc->loader_on_device || !in->data_gpu || in->c < 1 || in->c > 4 || net->batch_size < 1 || in->n < net->batch_size)
         return NULL;
     const int stored = it->type == BCNN_LOAD_MNIST || it->type == BCNN_LOAD_CIFAR10;
@@ -903,94 +908,248 @@ static bcnn_status list_detection_init(bcnn_loader *it, bcnn_net *net, const cha
     return it->input_net ? BCNN_SUCCESS : BCNN_FAILED_ALLOC;
 }
 
-static bcnn_status list_detection_next(bcnn_loader *it, bcnn_net *net, int idx) {
+/* One entry of the list, split so that the pixel work is separable: the host path (list_detection_next) and the device
+ * path (detection_batch_device) run the same steps in the same order and differ only in who makes the pixels. */
+typedef struct {
+    char **tok;
+    int n;               /* tokens of the line; <= 0: no line */
+    unsigned char *pimg; /* the decoded file, or NULL */
+    int w_img, h_img, c_img;
+    int nw, nh, dx, dy;  /* letterbox extent and canvas offsets */
+    int augmented;       /* `draw` holds this sample's augmentation (TRAIN mode with an augmenter) */
+    aug_draw draw;
+} det_entry;
+
+static void det_entry_free(det_entry *e) {
+    free(e->pimg);
+    if (e->n > 0) free_tokens(e->tok, e->n);
+    memset(e, 0, sizeof(*e));
+}
+
+static void det_read_line(bcnn_loader *it, det_entry *e) {
+    memset(e, 0, sizeof(*e));
+    e->n = next_line_tokens(it->f_current, &e->tok);
+}
+
+/* Decodes the file of a well-formed row. Reads and writes nothing but the entry (bip_load_image keeps no state), so the
+ * entries of a batch may be decoded on several threads. */
+static void det_decode(det_entry *e) {
+    if (e->n > 0 && (e->n - 1) % 5 == 0) bip_load_image(e->tok[0], &e->pimg, &e->w_img, &e->h_img, &e->c_img);
+}
+
+/* The skips, none of which consumes a draw, with their warnings; then the letterbox extent. */
+static bcnn_status det_accept(bcnn_net *net, det_entry *e) {
     bcnn_tensor *in = &net->tensors[0];
-    char **tok = NULL;
-    const int n = next_line_tokens(it->f_current, &tok);
-    if (n <= 0) {
+    if (e->n <= 0) {
         bcnn_log(net->log_ctx, BCNN_LOG_ERROR, "Invalid detection format\n");
         return BCNN_INVALID_DATA;
     }
-    if ((n - 1) % 5 != 0) {
+    if ((e->n - 1) % 5 != 0) {
         bcnn_log(net->log_ctx, BCNN_LOG_WARNING,
-                 "Wrong data format for detection %s. Found %d labels but expected multiple of 5\n", tok[0], n - 1);
-        free_tokens(tok, n);
+                 "Wrong data format for detection %s. Found %d labels but expected multiple of 5\n", e->tok[0], e->n - 1);
         return BCNN_INVALID_DATA;
     }
-    int w_img = 0, h_img = 0, c_img = 0;
-    unsigned char *pimg = NULL;
-    bip_load_image(tok[0], &pimg, &w_img, &h_img, &c_img);
-    if (!(w_img > 0 && h_img > 0 && pimg)) {
-        bcnn_log(net->log_ctx, BCNN_LOG_WARNING, "Skip invalid image %s\n", tok[0]);
-        free(pimg);
-        free_tokens(tok, n);
+    if (!(e->w_img > 0 && e->h_img > 0 && e->pimg)) {
+        bcnn_log(net->log_ctx, BCNN_LOG_WARNING, "Skip invalid image %s\n", e->tok[0]);
         return BCNN_INVALID_DATA;
     }
-    if (in->c != c_img) {
-        bcnn_log(net->log_ctx, BCNN_LOG_WARNING, "Skip image %s: unexpected number of channels\n", tok[0]);
-        free(pimg);
-        free_tokens(tok, n);
+    if (in->c != e->c_img) {
+        bcnn_log(net->log_ctx, BCNN_LOG_WARNING, "Skip image %s: unexpected number of channels\n", e->tok[0]);
         return BCNN_INVALID_DATA;
     }
     /* the letterbox: the float ratio (file header), the reference's truncations otherwise */
-    const float wh_ratio = (float)w_img / (float)h_img;
-    int nw, nh;
+    const float wh_ratio = (float)e->w_img / (float)e->h_img;
     if (wh_ratio < 1) {
-        nh = in->h;
-        nw = (int)(nh * wh_ratio);
+        e->nh = in->h;
+        e->nw = (int)(e->nh * wh_ratio);
     } else {
-        nw = in->w;
-        nh = (int)(nw / wh_ratio);
+        e->nw = in->w;
+        e->nh = (int)(e->nw / wh_ratio);
     }
-    unsigned char *buf = (nw >= 1 && nh >= 1) ? (unsigned char *)calloc((size_t)nw * nh * c_img, 1) : NULL;
-    if (!buf) { /* an image so narrow that nothing of it is left at this input size */
-        bcnn_log(net->log_ctx, BCNN_LOG_WARNING, "Skip image %s: %d x %d leaves no pixel at the input size\n", tok[0], w_img, h_img);
-        free(pimg);
-        free_tokens(tok, n);
+    if (e->nw < 1 || e->nh < 1) { /* an image so narrow that nothing of it is left at this input size */
+        bcnn_log(net->log_ctx, BCNN_LOG_WARNING, "Skip image %s: %d x %d leaves no pixel at the input size\n", e->tok[0],
+                 e->w_img, e->h_img);
         return BCNN_INVALID_DATA;
     }
-    bip_resize_bilinear(pimg, w_img, h_img, (size_t)w_img * c_img, buf, nw, nh, (size_t)nw * c_img, c_img);
-    free(pimg);
-    int dx, dy; /* canvas offsets */
+    return BCNN_SUCCESS;
+}
+
+/* The draws of an accepted entry, in the reference's order: the canvas offsets, the flip (:130-140), the augmentation. */
+static void det_draw(bcnn_net *net, det_entry *e) {
+    bcnn_tensor *in = &net->tensors[0];
     if (net->mode == BCNN_MODE_TRAIN) {
-        dx = rand_between(0, in->w - nw);
-        dy = rand_between(0, in->h - nh);
+        e->dx = rand_between(0, in->w - e->nw);
+        e->dy = rand_between(0, in->h - e->nh);
     } else {
-        dx = (in->w - nw) / 2;
-        dy = (in->h - nh) / 2;
+        e->dx = (in->w - e->nw) / 2;
+        e->dy = (in->h - e->nh) / 2;
     }
-    const size_t bytes = (size_t)bcnn_tensor_size3d(in);
-    memset(it->input_net, 128, bytes);
-    bip_crop_image(buf, nw, nh, (size_t)nw * c_img, -dx, -dy, it->input_net, in->w, in->h, (size_t)in->w * in->c, in->c);
-    free(buf);
     bcnn_data_augmenter *aug = net->data_aug;
-    if (net->mode == BCNN_MODE_TRAIN && aug) { /* the flip draw, then brightness / contrast / flip (:130-140) */
+    e->augmented = net->mode == BCNN_MODE_TRAIN && aug;
+    if (e->augmented) {
         aug->apply_fliph = 0;
         if (aug->random_fliph) aug->apply_fliph = ((float)rand() / RAND_MAX > 0.5f);
-        bcnn_apply_data_augmentation(it->input_net, in->w, in->h, in->c, aug, it->input_uchar);
+        draw_augmentation(aug, &e->draw);
     }
+}
+
+/* The letterboxed, augmented sample into input slot idx on the host. `buf` (nw x nh x c, freed here) takes the resized
+ * image. */
+static void det_pixels_host(bcnn_net *net, bcnn_loader *it, const det_entry *e, unsigned char *buf, int idx) {
+    bcnn_tensor *in = &net->tensors[0];
+    const int c = e->c_img;
+    bip_resize_bilinear(e->pimg, e->w_img, e->h_img, (size_t)e->w_img * c, buf, e->nw, e->nh, (size_t)e->nw * c, c);
+    const size_t bytes = (size_t)bcnn_tensor_size3d(in);
+    memset(it->input_net, 128, bytes);
+    bip_crop_image(buf, e->nw, e->nh, (size_t)e->nw * c, -e->dx, -e->dy, it->input_net, in->w, in->h, (size_t)in->w * in->c,
+                   in->c);
+    free(buf);
+    if (e->augmented) augment_pixels(it->input_net, in->w, in->h, in->c, &e->draw, it->input_uchar);
     memcpy(it->input_uchar, it->input_net, bytes);
-    bcnn_convert_img_to_float(it->input_uchar, in->w, in->h, in->c, 1 / 127.5f, aug ? aug->swap_to_bgr : 0, 127.5f, 127.5f,
-                              127.5f, in->data + (size_t)idx * bytes);
-    if (net->mode != BCNN_MODE_PREDICT) {
-        int sz;
-        float *y = label_slot(net, idx, &sz);
-        int num_boxes = (n - 1) / 5;
-        if (num_boxes > BCNN_DETECTION_MAX_BOXES) num_boxes = BCNN_DETECTION_MAX_BOXES;
-        if (num_boxes > sz / 5) num_boxes = sz / 5; /* a label tensor some other builder shaped */
-        const float scale_x = (float)nw / (float)in->w, scale_y = (float)nh / (float)in->h;
-        const float scale_dx = (float)dx / (float)in->w, scale_dy = (float)dy / (float)in->h;
-        for (int i = 0; i < num_boxes; ++i) { /* box centre (x, y), extent (w, h), class */
-            y[i * 5 + 0] = (float)atof(tok[5 * i + 2]) * scale_x + scale_dx;
-            y[i * 5 + 1] = (float)atof(tok[5 * i + 3]) * scale_y + scale_dy;
-            y[i * 5 + 2] = (float)atof(tok[5 * i + 4]) * scale_x;
-            y[i * 5 + 3] = (float)atof(tok[5 * i + 5]) * scale_y;
-            if (aug && aug->apply_fliph) y[i * 5 + 0] = 1.0f - y[i * 5 + 0];
-            y[i * 5 + 4] = (float)atoi(tok[5 * i + 1]);
+    bcnn_convert_img_to_float(it->input_uchar, in->w, in->h, in->c, 1 / 127.5f, net->data_aug ? net->data_aug->swap_to_bgr : 0,
+                              127.5f, 127.5f, 127.5f, in->data + (size_t)idx * bytes);
+}
+
+static void det_labels(bcnn_net *net, const det_entry *e, int idx) {
+    if (net->mode == BCNN_MODE_PREDICT) return;
+    bcnn_tensor *in = &net->tensors[0];
+    const bcnn_data_augmenter *aug = net->data_aug;
+    char **tok = e->tok;
+    int sz;
+    float *y = label_slot(net, idx, &sz);
+    int num_boxes = (e->n - 1) / 5;
+    if (num_boxes > BCNN_DETECTION_MAX_BOXES) num_boxes = BCNN_DETECTION_MAX_BOXES;
+    if (num_boxes > sz / 5) num_boxes = sz / 5; /* a label tensor some other builder shaped */
+    const float scale_x = (float)e->nw / (float)in->w, scale_y = (float)e->nh / (float)in->h;
+    const float scale_dx = (float)e->dx / (float)in->w, scale_dy = (float)e->dy / (float)in->h;
+    for (int i = 0; i < num_boxes; ++i) { /* box centre (x, y), extent (w, h), class */
+        y[i * 5 + 0] = (float)atof(tok[5 * i + 2]) * scale_x + scale_dx;
+        y[i * 5 + 1] = (float)atof(tok[5 * i + 3]) * scale_y + scale_dy;
+        y[i * 5 + 2] = (float)atof(tok[5 * i + 4]) * scale_x;
+        y[i * 5 + 3] = (float)atof(tok[5 * i + 5]) * scale_y;
+        if (aug && aug->apply_fliph) y[i * 5 + 0] = 1.0f - y[i * 5 + 0];
+        y[i * 5 + 4] = (float)atoi(tok[5 * i + 1]);
+    }
+}
+
+static bcnn_status list_detection_next(bcnn_loader *it, bcnn_net *net, int idx) {
+    det_entry e;
+    det_read_line(it, &e);
+    det_decode(&e);
+    bcnn_status st = det_accept(net, &e);
+    unsigned char *buf = NULL;
+    if (st == BCNN_SUCCESS && !(buf = (unsigned char *)calloc((size_t)e.nw * e.nh * e.c_img, 1))) {
+        bcnn_log(net->log_ctx, BCNN_LOG_WARNING, "Skip image %s: %d x %d leaves no pixel at the input size\n", e.tok[0], e.w_img,
+                 e.h_img);
+        st = BCNN_INVALID_DATA;
+    }
+    if (st == BCNN_SUCCESS) {
+        det_draw(net, &e);
+        det_pixels_host(net, it, &e, buf, idx);
+        det_labels(net, &e, idx);
+    }
+    det_entry_free(&e);
+    return st;
+}
+
+/* ---- a detection batch letterboxed on the device (bcnn_set_loader_detection_on_device) ------------------------------- */
+/* Entries first .. first + count - 1 on up to `threads` threads, entry first + t, first + t + T, ... on thread t. */
+typedef struct { det_entry *entries; int count, first, step; } det_worker;
+
+static void *det_worker_run(void *arg) {
+    det_worker *w = (det_worker *)arg;
+    for (int i = w->first; i < w->count; i += w->step) det_decode(&w->entries[i]);
+    return NULL;
+}
+
+static void det_decode_group(det_entry *entries, int count, int threads) {
+    const int T = threads > count ? count : threads;
+    det_worker *workers = T > 1 ? (det_worker *)calloc((size_t)T, sizeof(det_worker)) : NULL;
+    pthread_t *ids = T > 1 ? (pthread_t *)calloc((size_t)T, sizeof(pthread_t)) : NULL;
+    if (!workers || !ids) { /* one thread: the sequential path */
+        free(workers);
+        free(ids);
+        for (int i = 0; i < count; ++i) det_decode(&entries[i]);
+        return;
+    }
+    for (int t = 0; t < T; ++t) {
+        det_worker w = {entries, count, t, T};
+        workers[t] = w;
+    }
+    int started = 0;
+    for (int t = 1; t < T; ++t) { /* a thread that cannot be created: its entries are decoded below */
+        if (pthread_create(&ids[t], NULL, det_worker_run, &workers[t]) != 0) break;
+        started = t;
+    }
+    det_worker_run(&workers[0]);
+    for (int t = started + 1; t < T; ++t) det_worker_run(&workers[t]);
+    for (int t = 1; t <= started; ++t) pthread_join(ids[t], NULL);
+    free(workers);
+    free(ids);
+}
+
+/* The batch in rounds, because a skipped entry consumes no draw and reading a file consumes none: as many lines as slots
+ * are still empty are read (each fills a slot or is skipped, so no line is read that the host path would not have read),
+ * their files are decoded in parallel, and the results are walked in list order with the skips, warnings, draws, records
+ * and labels of list_detection_next. The decoded images are kept until the batch is complete and go up in one copy;
+ * tensors[0].data and the loader's two sample buffers are not written. Should the device side refuse the batch (2 GiB),
+ * it is made on the host from the images already decoded and the draws already made. *on_device: the input tensor was
+ * made on the device. */
+static bcnn_status detection_batch_device(bcnn_net *net, bcnn_loader *it, int *on_device) {
+    bcnn_hip_context *hc = (bcnn_hip_context *)net->hip_ctx;
+    bcnn_tensor *in = &net->tensors[0];
+    const int n = net->batch_size, w = in->w, h = in->h;
+    const size_t sample_taps = ((size_t)w + h) * 2;
+    *on_device = 0;
+    det_entry *kept = (det_entry *)calloc((size_t)n, sizeof(det_entry)), *group = (det_entry *)calloc((size_t)n, sizeof(det_entry));
+    bcnn_hip_letterbox_image *images = (bcnn_hip_letterbox_image *)calloc((size_t)n, sizeof(bcnn_hip_letterbox_image));
+    bcnn_hip_augment_record *records = (bcnn_hip_augment_record *)calloc((size_t)n, sizeof(bcnn_hip_augment_record));
+    int32_t *taps = (int32_t *)calloc((size_t)n * sample_taps, sizeof(int32_t));
+    bcnn_status st = (kept && group && images && records && taps) ? BCNN_SUCCESS : BCNN_FAILED_ALLOC;
+    int count = 0, failures = 0;
+    while (st == BCNN_SUCCESS && count < n) {
+        const int want = n - count;
+        for (int i = 0; i < want; ++i) det_read_line(it, &group[i]);
+        det_decode_group(group, want, net->num_threads);
+        for (int i = 0; i < want; ++i) {
+            det_entry *e = &group[i];
+            if (st != BCNN_SUCCESS || det_accept(net, e) != BCNN_SUCCESS) {
+                det_entry_free(e);
+                if (st == BCNN_SUCCESS && ++failures >= 1000) {
+                    bcnn_log(net->log_ctx, BCNN_LOG_ERROR, "bcnn_loader_next: 1000 samples in a row could not be read\n");
+                    st = BCNN_INVALID_DATA; /* the entries behind this one are dropped unseen */
+                }
+                continue;
+            }
+            failures = 0;
+            det_draw(net, e);
+            if (e->augmented) fill_record(&records[count], taps + (size_t)count * sample_taps, &e->draw, w, h);
+            det_labels(net, e, count);
+            kept[count++] = *e;
+            memset(e, 0, sizeof(*e));
         }
     }
-    free_tokens(tok, n);
-    return BCNN_SUCCESS;
+    if (st == BCNN_SUCCESS) {
+        for (int i = 0; i < n; ++i) {
+            const bcnn_hip_letterbox_image im = {kept[i].pimg, kept[i].w_img, kept[i].h_img, kept[i].nw, kept[i].nh,
+                                                 kept[i].dx, kept[i].dy};
+            images[i] = im;
+        }
+        if (bcnn_hip_augment_letterbox_batch(in->data_gpu, in->n, in->c, h, w, n, images, records, taps,
+                                             net->data_aug ? net->data_aug->swap_to_bgr : 0) == 0) {
+            *on_device = 1;
+            hc->loader_device_letterboxed = n;
+        } else { /* the host way, from what is already decoded and drawn */
+            for (int i = 0; i < n && st == BCNN_SUCCESS; ++i) {
+                unsigned char *buf = (unsigned char *)calloc((size_t)kept[i].nw * kept[i].nh * kept[i].c_img, 1);
+                if (buf) det_pixels_host(net, it, &kept[i], buf, i);
+                else st = BCNN_FAILED_ALLOC;
+            }
+        }
+    }
+    for (int i = 0; kept && i < n; ++i) det_entry_free(&kept[i]);
+    free(kept); free(group); free(images); free(records); free(taps);
+    return st;
 }
 
 /* ---- public entry points ------------------------------------------------------------------------------------------ */
@@ -1047,7 +1206,13 @@ bcnn_status bcnn_loader_next(bcnn_net *net) {
     bcnn_hip_context *hc = (bcnn_hip_context *)net->hip_ctx;
     int launched = 0; /* list_batch_decoded has queued the batch already */
     hc->loader_device_decoded = 0;
-    if (ls && hc->loader_decode_on_device && (net->tensors[0].c == 1 || net->tensors[0].c == 3) &&
+    hc->loader_device_letterboxed = 0;
+    int letterboxed = 0; /* detection_batch_device has made the input batch on the device */
+    bcnn_tensor *in0 = &net->tensors[0];
+    if (it && it->type == BCNN_LOAD_DETECTION_LIST && hc->loader_on_device && hc->loader_detection_on_device && in0->data_gpu &&
+        in0->c >= 1 && in0->c <= 4 && net->batch_size >= 1 && in0->n >= net->batch_size) {
+        BCNN_CHECK_STATUS(detection_batch_device(net, it, &letterboxed));
+    } else if (ls && hc->loader_decode_on_device && (net->tensors[0].c == 1 || net->tensors[0].c == 3) &&
         (it->type == BCNN_LOAD_CLASSIFICATION_LIST || it->type == BCNN_LOAD_REGRESSION_LIST)) {
         const bcnn_status st = list_batch_decoded(net, it, ls, &launched);
         if (st != BCNN_SUCCESS) {
@@ -1086,7 +1251,7 @@ bcnn_status bcnn_loader_next(bcnn_net *net) {
             BCNN_ERROR(net->log_ctx, BCNN_INVALID_PARAMETER, "bcnn_loader_next: the batch does not fit the device loader path\n");
     }
     for (int i = 0; i < net->num_inputs; ++i) {
-        if (ls && net->inputs[i] == 0) continue; /* the host copy is stale in this mode */
+        if ((ls || letterboxed) && net->inputs[i] == 0) continue; /* the host copy is stale in this mode */
         bcnn_tensor *t = &net->tensors[net->inputs[i]];
         if (t->data && t->data_gpu) bcnn_hip_memcpy_h2d(t->data_gpu, t->data, (size_t)bcnn_tensor_size(t) * sizeof(float));
     }

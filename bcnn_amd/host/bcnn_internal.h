@@ -175,6 +175,9 @@ typedef struct bcnn_hip_context {
     int loader_decode_on_device; /* bcnn_set_loader_decode_on_device: JPEG entries of a list batch that goes the device way
                                   * are entropy-decoded on the host and become pixels on the device only */
     int loader_device_decoded;   /* samples of the latest bcnn_loader_next whose pixels were decoded on the device */
+    int loader_detection_on_device; /* bcnn_set_loader_detection_on_device: a detection-list batch that goes the device way
+                                     * is letterboxed and augmented by bcnn_hip_augment_letterbox_batch */
+    int loader_device_letterboxed;  /* samples of the latest bcnn_loader_next that were letterboxed on the device */
     int detector_training; /* bcnn_set_detector_training: YOLO heads may be built on / switched to TRAIN, with their loss */
     int detect_capacity; /* 1.25 x the most boxes an image of the latest bcnn_yolo_get_detections_batch had: the next call's record capacity
                           * when above the default (0: never called) */

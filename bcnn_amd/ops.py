@@ -5,6 +5,8 @@ lib/libbcnn_hip.so with raw device pointers; argument meaning follows the refere
 (file:line cited per function). torch is plumbing only (device memory + streams); no torch op computes
 anything on this path, and a missing extension raises (bcnn_amd/_lib.py).
 """
+import ctypes as _C
+
 import torch
 
 from . import _lib
@@ -305,3 +307,34 @@ def sgd_update(w, b, dw, db, batch_size, lr, momentum, decay):
     """bcnn_sgd_update_cpu (bcnn_learner.c:67-83)"""
     _lib.load().bcnn_hip_sgd_update(_f32(w), _f32(b), _f32(dw), _f32(db), w.numel() if w is not None else 0,
                                     b.numel() if b is not None else 0, batch_size, lr, momentum, decay)
+
+
+class LetterboxImage(_C.Structure):
+    """bcnn_hip_letterbox_image (include/bcnn_hip.h)"""
+    _fields_ = [("pixels", _C.c_void_p), ("w", _C.c_int32), ("h", _C.c_int32), ("new_w", _C.c_int32), ("new_h", _C.c_int32),
+                ("x_off", _C.c_int32), ("y_off", _C.c_int32)]
+
+
+def augment_letterbox_batch(dst, images, boxes, records=None, taps=None, swap_to_bgr=False, num_samples=None):
+    """bcnn_hip_augment_letterbox_batch: dst is the [n][c][h][w] float32 device tensor; images are HOST uint8 arrays
+    [hi][wi][c] (numpy, C-contiguous), boxes one (new_w, new_h, x_off, y_off) per image, records a HOST int32 array
+    [num][8] (bcnn_hip_augment_record; None: identity records), taps a HOST int32 array [num][(w + h) * 2] or None.
+    Returns the entry's status: 0, or 1 with nothing staged or queued."""
+    import numpy as np
+    n, c, h, w = dst.shape
+    num = len(images) if num_samples is None else num_samples
+    arr = (LetterboxImage * max(len(images), 1))()
+    keep = []
+    for b, (img, box) in enumerate(zip(images, boxes)):
+        img = np.ascontiguousarray(img, dtype=np.uint8)
+        keep.append(img)
+        hi, wi = img.shape[:2]
+        arr[b] = LetterboxImage(img.ctypes.data, wi, hi, *[int(v) for v in box])
+    if records is None:
+        records = np.zeros((max(num, 1), 8), np.int32)
+    records = np.ascontiguousarray(records, dtype=np.int32)
+    if taps is not None:
+        taps = np.ascontiguousarray(taps, dtype=np.int32)
+    return int(_lib.load().bcnn_hip_augment_letterbox_batch(
+        _f32(dst), n, c, h, w, num, _C.cast(arr, _C.c_void_p), records.ctypes.data,
+        None if taps is None else taps.ctypes.data, 1 if swap_to_bgr else 0))

@@ -315,7 +315,8 @@ BCNN_API bcnn_precision bcnn_get_inference_precision(const bcnn_net *net);
  * bcnn_get_tensor_by_index / bcnn_download_tensor refresh it from the device as usual. A scale draw that leaves an
  * extent below 1 pixel leaves the sample unscaled, as the host path does. A batch goes the host way regardless when the
  * input tensor has more than 4 channels or no device buffer, or an MNIST / CIFAR-10 record does not match the input's
- * channels, and always for BCNN_LOAD_DETECTION_LIST. May be called before or after bcnn_set_data_loader /
+ * channels, and always for BCNN_LOAD_DETECTION_LIST (this switch alone; bcnn_set_loader_detection_on_device below moves
+ * that loader's letterbox to the device). May be called before or after bcnn_set_data_loader /
  * bcnn_compile_net and between batches; without a loader it has no effect. A NULL net returns BCNN_INVALID_PARAMETER.
  * Config files: `loader_on_device=1` in the [net] section. */
 BCNN_API bcnn_status bcnn_set_loader_on_device(bcnn_net *net, int on);
@@ -338,6 +339,28 @@ BCNN_API int bcnn_get_loader_decode_on_device(const bcnn_net *net);
 /* Number of samples of the latest bcnn_loader_next whose pixels were decoded on the device; 0 for a batch made any other
  * way, on a fresh net and for a NULL net. */
 BCNN_API int bcnn_get_loader_device_decoded(const bcnn_net *net);
+/* Where a BCNN_LOAD_DETECTION_LIST batch is letterboxed and augmented (default 0: on the host, image by image). With
+ * on != 0, and only while bcnn_set_loader_on_device is on as well and the input tensor has a device buffer and 1 to 4
+ * channels, the host reads the list, decodes every file (on bcnn_get_num_threads(net) threads, created and joined inside
+ * bcnn_loader_next; the batch does not depend on their number), computes the letterbox extent, draws the offsets, the
+ * flip and the augmentation parameters from rand() in the host path's order and number, and writes the labels -- but
+ * touches no pixel: the decoded images of the batch go to the device in one copy, and three kernel launches (whatever the
+ * batch size and the image sizes) resize them with bip_resize_bilinear's integer rule, paste them on the canvas of 128 at
+ * the drawn offsets, augment the canvas and convert it into the float input tensor. The device tensor, the labels and
+ * the state of rand() are, bit for bit, those of the host path for the same files, seed and settings, in every mode;
+ * skipped entries, their warnings, the limit of 1000 failures in a row, wrap-around and rewind are unchanged.
+ * tensors[0].data is NOT written and not uploaded. bcnn_set_loader_decode_on_device has no effect on this loader and
+ * bcnn_get_loader_device_decoded stays 0 there. A batch whose staging block would pass 2 GiB, or that holds an image whose
+ * letterbox is larger than the canvas (a non-square input only: the extent formula is the square input's, and the host
+ * path's paste crops such an image), is made on the host from the images already decoded and the draws already made: no
+ * draw is repeated, and bcnn_get_loader_device_letterboxed is 0 for it. Everywhere else the switch has no effect. Any non-zero value is
+ * stored as 1; may be called before a loader exists and between batches; a NULL net returns BCNN_INVALID_PARAMETER.
+ * Config files: `loader_detection_on_device=1` in the [net] section. */
+BCNN_API bcnn_status bcnn_set_loader_detection_on_device(bcnn_net *net, int on);
+BCNN_API int bcnn_get_loader_detection_on_device(const bcnn_net *net);
+/* Number of samples of the latest bcnn_loader_next that were letterboxed on the device; 0 for a batch made any other
+ * way, on a fresh net and for a NULL net. */
+BCNN_API int bcnn_get_loader_device_letterboxed(const bcnn_net *net);
 /* Detections of EVERY image of the batch from the latest forward, in one call. widths[b] / heights[b]: the original
  * size of image b (what bcnn_yolo_get_detections takes as w, h). dets[b] receives a malloc'ed array of num_dets[b]
  * boxes (NULL / 0 when image b has no candidate); per image, the result is what

@@ -796,6 +796,38 @@ int bcnn_hip_augment_jpeg_run(float *dst_d, const uint8_t *decoded, const uint8_
 void bcnn_hip_augment_jpeg_cancel(void);
 
 /* ---------------------------------------------------------------------------------------------
+ * The same batch when every sample is still a decoded image of its own size that has to be letterboxed first
+ * (augment.hip): the detection-list loader's opt-in device path. For sample b, S0 of bcnn_hip_augment_batch is a
+ * w x h x c canvas (src_w = w, src_h = h: no centre crop) that holds 128 everywhere except at
+ * [x_off, x_off + new_w) x [y_off, y_off + new_h), where it holds bip_resize_bilinear(images[b]) to new_w x new_h:
+ * bip_resize_tap with bip_resize_scale(w, new_w) / bip_resize_scale(h, new_h) per axis and bip_resize_blend. A source
+ * axis of extent 1 replicates. records / taps / swap_to_bgr describe the augmentation of the CANVAS, as for
+ * bcnn_hip_augment_batch; every later stage and the conversion are that call's. The result equals, bit for bit, the host
+ * composition bip_resize_bilinear, memset to 128, bip_crop_image at (-x_off, -y_off), the pixel step of
+ * bcnn_apply_data_augmentation and bcnn_convert_img_to_float with 127.5 / (1 / 127.5).
+ * One pinned staging block goes up in ONE copy on the current stream: [records][zeroed channel sums][augmentation
+ * taps][one descriptor per image][letterbox tap tables, tabulated here with bip_resize_tap][the packed source pixels of
+ * every image]; behind it, on the device only: [canvases][rotated samples]. THREE kernels follow, whatever the batch size
+ * and the image sizes: augment_letterbox_kernel writes all canvases (a lane per run of 16 consecutive canvas bytes of one
+ * row, 16-byte stores where the address allows, integer work only, source images addressed by offsets into the block),
+ * then the geometry and the convert kernel of bcnn_hip_augment_batch, unchanged. The images have been copied when the
+ * call returns.
+ * Returns 0, or 1 with nothing staged or queued: a NULL dst_d / images / records / pixels pointer; n, h or w < 1; c
+ * outside 1..4; num_samples outside 1..n; an image extent < 1; new_w outside 1..w or new_h outside 1..h; x_off outside
+ * 0..w - new_w or y_off outside 0..h - new_h; a record with SCALE and taps == NULL, or a tap index outside
+ * [-1, max(extent - 2, 0)]; more than 2 GiB for the staging block plus the device part.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct bcnn_hip_letterbox_image {
+    const uint8_t *pixels;   /* HOST: h rows of w * c bytes, dense */
+    int32_t w, h;            /* source extent, >= 1 */
+    int32_t new_w, new_h;    /* extent of the resized image, 1 .. W / 1 .. H */
+    int32_t x_off, y_off;    /* where it is pasted, 0 .. W - new_w / 0 .. H - new_h */
+} bcnn_hip_letterbox_image;
+int bcnn_hip_augment_letterbox_batch(float *dst_d, int n, int c, int h, int w, int num_samples,
+                                     const bcnn_hip_letterbox_image *images, const bcnn_hip_augment_record *records,
+                                     const int32_t *taps, int swap_to_bgr);
+
+/* ---------------------------------------------------------------------------------------------
  * Transposed convolution (deconvolution), implicit GEMMs on fp32 MFMA with no col2im / im2col buffer.
  * Replaces bcnn_forward_deconv_layer_gpu / bcnn_backward_deconv_layer_gpu (bcnn_deconv_layer.c:249-320) with the
  * semantics of the CPU workers (:150-193, :195-246):
