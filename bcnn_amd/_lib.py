@@ -132,6 +132,8 @@ SIGNATURES = {
     "bcnn_hip_augment_jpeg_run": (i, [vp, vp, vp, vp, vp, vp, i]),
     "bcnn_hip_augment_jpeg_cancel": (None, []),
     "bcnn_hip_augment_letterbox_batch": (i, [vp, i, i, i, i, i, vp, vp, vp, i]),
+    "bcnn_hip_augment_effects_begin": (i, [i, i, i, vp, vp, vp, vp, i, vp, sz]),
+    "bcnn_hip_augment_effects_cancel": (None, []),
     "bcnn_hip_deconv_workspace_size": (sz, [i] * 8),
     "bcnn_hip_deconv_forward": (None, [vp, vp, vp, vp] + [i] * 9),
     "bcnn_hip_deconv_backward": (None, [vp] * 7 + [i] * 9 + [vp, sz]),

@@ -121,6 +121,7 @@ def lib():
         "bcnn_get_loader_device_decoded": (i, [vp]),
         "bcnn_set_loader_detection_on_device": (i, [vp, i]), "bcnn_get_loader_detection_on_device": (i, [vp]),
         "bcnn_get_loader_device_letterboxed": (i, [vp]),
+        "bcnn_set_loader_effects": (i, [vp, i]), "bcnn_get_loader_effects": (i, [vp]),
         "bcnn_set_detector_training": (i, [vp, i]), "bcnn_get_detector_training": (i, [vp]),
         "bcnn_yolo_get_train_stats": (i, [vp, i, C.POINTER(YoloTrainStats)]),
         "bcnn_set_data_loader": (i, [vp, i, cp, cp, cp, cp]),
@@ -325,6 +326,15 @@ class Net:
     def loader_device_letterboxed(self):
         """bcnn_get_loader_device_letterboxed: samples of the latest bcnn_loader_next that were letterboxed on the device"""
         return self.L.bcnn_get_loader_device_letterboxed(self.net)
+
+    def set_loader_effects(self, on):
+        """bcnn_set_loader_effects: bcnn_loader_next applies Perlin distortion (max_distortion) and random spotlights
+        (max_spots) to TRAIN samples, on the host path and on every device route, bit for bit like the reference; off
+        (the default) their rand() draws are made and the pixels stay. Returns the bcnn_status."""
+        return self.L.bcnn_set_loader_effects(self.net, 1 if on else 0)
+
+    def get_loader_effects(self):
+        return self.L.bcnn_get_loader_effects(self.net)
 
     def set_detector_training(self, on):
         """bcnn_set_detector_training: YOLO heads may be built on a TRAIN net (or switched to TRAIN), their TRAIN forward

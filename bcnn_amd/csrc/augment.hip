@@ -26,6 +26,11 @@
 // augment_letterbox_kernel resizes each (bip_resize_bilinear's rule, taps tabulated on the host side of the entry) and
 // pastes it on a canvas of 128 behind the uploaded part of the block; the canvases are the raw samples of the two kernels
 // above. One copy, three launches.
+//
+// bcnn_hip_augment_effects_begin / _cancel stage Perlin distortion and random spotlights for the
+// next of the three batch calls above, which copies the staged tables into its block (still one copy) and launches
+// augment_convert_effects_kernel in place of the convert kernel. cos and exp were called on the host; the kernel's
+// arithmetic is ../host/bip_effects.h, which libbip's host functions are written on as well.
 #include "common.h"
 
 #include <cstdint>
@@ -33,6 +38,7 @@
 
 #include <vector>
 
+#include "../host/bip_effects.h"
 #include "../host/bip_resize_tap.h"
 #include "jpeg_pixels.h"
 #include "store_run.h"
@@ -52,7 +58,20 @@ struct AugParams {
     int blocks_per_sample;                        // of the kernel that reads this
     int runs_per_row;
     uint32_t win_off;                             // the window table of the windowed geometry kernel
+    uint32_t fx_off;                              // the staged effects (FxHeader); 0: none, the plain convert kernel runs
 };
+
+// What bcnn_hip_augment_effects_begin lays out and a batch call copies into its block at fx_off, 16-byte aligned:
+// [FxHeader][FxSample per sample][FxSpot per spot][per sample with DISTORT: norm_x, norm_y, weight_x, weight_y (floats),
+// cell_x, cell_y (int32)][the spots' tables]. Offsets count from the header's first byte.
+struct FxHeader { uint32_t spot_off, pad[3]; };
+struct FxSample {
+    int32_t flags, seed;
+    float distortion;
+    int32_t first_spot, num_spots;
+    uint32_t perlin_off;
+};
+struct FxSpot { int32_t x0, y0, bw, bh; uint32_t table_off; };
 
 // Where the windowed geometry kernel finds one sample's raw bytes: a wi x hi image at `base` (bytes from the block's first
 // byte), of which the sample is the w x h window at (x_ul, y_ul). Outside the image the sample is 0: bip_crop_image onto
@@ -277,6 +296,107 @@ __global__ __launch_bounds__(kAugBlock) void augment_convert_kernel(const uint8_
     }
 }
 
+// The convert kernel of a batch with staged effects (bcnn_hip_augment_effects_begin): stages 5 to 8 of the kernel above
+// with Perlin distortion and the spotlights between brightness and crop, in the same pass and with no further image.
+// Contrast and brightness are pointwise functions of a rotated byte given the channel sums, so a distorted pixel is the
+// reference's four-tap blend of tone(s4[tap]), and the spots are a pointwise chain on top of it. A lane keeps its kRun
+// destination pixels and store_run's 16-byte stores; its taps are a byte gather that stays within a few rows of one sample
+// (the noise moves a position by at most distortion x extent), which the cache holds. Every table value was made on the
+// host with libm; the arithmetic here is bip_effects.h's, uncontracted: no cos, no exp, no division. A sample without a
+// flag takes the plain path.
+template <int C>
+__global__ __launch_bounds__(kAugBlock) void augment_convert_effects_kernel(const uint8_t* __restrict__ block,
+                                                                            float* __restrict__ dst, AugParams p) {
+    const int b = blockIdx.x / p.blocks_per_sample;
+    const int run = (blockIdx.x - b * p.blocks_per_sample) * kAugBlock + threadIdx.x;
+    const int y = run / p.runs_per_row;
+    if (y >= p.H) return;
+    const int x0 = (run - y * p.runs_per_row) * kRun;
+    const int len = min(kRun, p.W - x0);
+    const bcnn_hip_augment_record r = reinterpret_cast<const bcnn_hip_augment_record*>(block + p.rec_off)[b];
+    const uint32_t* __restrict__ sums = reinterpret_cast<const uint32_t*>(block + p.sum_off) + b * 4;
+    const bool contrast = (r.flags & BCNN_HIP_AUG_CONTRAST) != 0;
+    const uint8_t* __restrict__ fx = block + p.fx_off;
+    const FxSample f = reinterpret_cast<const FxSample*>(fx + sizeof(FxHeader))[b];
+    const uint8_t* __restrict__ s4 = block + p.s4_off + (size_t)b * p.sh * p.sw * C;
+    const int sy = y + p.cy, sx0 = x0 + p.cx;   // the run in sample coordinates
+    int32_t mean[C];
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+        const int ks = (C == 3 && p.swap) ? 2 - k : k;
+        mean[k] = contrast ? (int32_t)(sums[ks] / (uint32_t)(p.sw * p.sh)) : 0;
+    }
+    auto tone = [&](int32_t px, int k) {   // stages 5 and 6 of one byte of channel plane k
+        if (contrast) px = clamp_u8((((px - mean[k]) * r.gain + (1 << 11)) >> 12) + mean[k]);
+        return clamp_u8(px + r.brightness);
+    };
+    int32_t v8[C][kRun];
+    if (f.flags & BCNN_HIP_AUG_DISTORT) {
+        const float* __restrict__ norm_x = reinterpret_cast<const float*>(fx + f.perlin_off);
+        const float* __restrict__ norm_y = norm_x + p.sw;
+        const float* __restrict__ weight_x = norm_y + p.sh;
+        const float* __restrict__ weight_y = weight_x + p.sw;
+        const int32_t* __restrict__ cell_x = reinterpret_cast<const int32_t*>(weight_y + p.sh);
+        const int32_t* __restrict__ cell_y = cell_x + p.sw;
+        const float ny = norm_y[sy], wy = weight_y[sy], fw = (float)p.sw, fh = (float)p.sh;
+        const int32_t cy = cell_y[sy];
+#pragma unroll
+        for (int j = 0; j < kRun; ++j) {
+#pragma unroll
+            for (int k = 0; k < C; ++k) v8[k][j] = 0;
+            if (j >= len) continue;
+            const int sx = sx0 + j;
+            const float noise = bip_perlin_noise(cell_x[sx], cy, weight_x[sx], wy, f.seed);
+            int32_t ix, iy;
+            float xd, yd;
+            if (!bip_distort_map(norm_x[sx], ny, noise, f.distortion, fw, fh, p.sw, p.sh, &ix, &iy, &xd, &yd)) continue;  // 0
+            const uint8_t* __restrict__ t0 = s4 + ((size_t)iy * p.sw + ix) * C;   // ix <= sw - 2, iy <= sh - 2
+            const uint8_t* __restrict__ t1 = t0 + (size_t)p.sw * C;
+#pragma unroll
+            for (int k = 0; k < C; ++k) {
+                const int ks = (C == 3 && p.swap) ? 2 - k : k;
+                v8[k][j] = bip_distort_blend((float)tone(t0[ks], k), (float)tone(t0[C + ks], k), (float)tone(t1[ks], k),
+                                             (float)tone(t1[C + ks], k), xd, yd);
+            }
+        }
+    } else {
+        const uint8_t* __restrict__ row = s4 + ((size_t)sy * p.sw + sx0) * C;
+#pragma unroll
+        for (int j = 0; j < kRun; ++j) {
+#pragma unroll
+            for (int k = 0; k < C; ++k) {
+                const int ks = (C == 3 && p.swap) ? 2 - k : k;
+                v8[k][j] = j < len ? tone(row[j * C + ks], k) : 0;
+            }
+        }
+    }
+    if (f.flags & BCNN_HIP_AUG_SPOTS) {   // one after the other: the result of spot i is the input of spot i + 1
+        const FxSpot* __restrict__ spots =
+            reinterpret_cast<const FxSpot*>(fx + reinterpret_cast<const FxHeader*>(fx)->spot_off) + f.first_spot;
+        for (int s = 0; s < f.num_spots; ++s) {
+            const FxSpot q = spots[s];
+            const int ry = sy - q.y0;
+            if (ry < 0 || ry >= q.bh) continue;
+            const float* __restrict__ tab = reinterpret_cast<const float*>(fx + q.table_off) + (size_t)ry * q.bw;
+#pragma unroll
+            for (int j = 0; j < kRun; ++j) {
+                const int rx = sx0 + j - q.x0;
+                if (j >= len || rx < 0 || rx >= q.bw) continue;
+                const float val = tab[rx];
+#pragma unroll
+                for (int k = 0; k < C; ++k) v8[k][j] = bip_spot_add(val, (uint8_t)v8[k][j]);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+        float v[kRun];
+#pragma unroll
+        for (int j = 0; j < kRun; ++j) v[j] = ((float)v8[k][j] - 127.5f) * (1 / 127.5f);
+        store_run(dst + (((size_t)b * C + k) * p.H + y) * p.W + x0, v, len);
+    }
+}
+
 // Pinned host side of the staging block (image_fill.hip's pattern): grow-only, one per host thread and device. `copied`
 // is recorded behind the latest copy out of it; the next call waits for it before it overwrites (or frees) the block.
 struct HostStage { uint8_t* p = nullptr; size_t cap = 0; hipEvent_t copied = nullptr; bool in_flight = false; };
@@ -299,6 +419,43 @@ uint8_t* host_stage(size_t bytes) {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// The block of this thread, at least `bytes` long, with its first `keep` bytes as they are: for the one caller that has
+// laid a batch out before it learns that effects ride along (bcnn_hip_augment_jpeg_run). No copy is in flight there.
+uint8_t* host_stage_extend(size_t keep, size_t bytes) {
+    HostStage& s = g_stage[current_device()];
+    if (s.p != nullptr && s.cap >= bytes) return s.p;
+    uint8_t* grown = nullptr;
+    const size_t cap = bytes + bytes / 4;
+    HIP_CHECK(hipHostMalloc((void**)&grown, cap, hipHostMallocDefault));
+    if (s.p) {
+        memcpy(grown, s.p, keep);
+        HIP_CHECK(hipHostFree(s.p));
+    }
+    s.p = grown;
+    s.cap = cap;
+    return s.p;
+}
+
+// What bcnn_hip_augment_effects_begin staged for this thread's next batch call: the blob that goes into that call's block
+// as it is (FxHeader ...), and the batch it was made for.
+struct PendingFx {
+    bool active = false;
+    int num = 0, w = 0, h = 0;
+    std::vector<uint8_t> blob;
+};
+thread_local PendingFx g_fx;
+
+// Every batch call begins with this: what is staged is consumed, whatever the call returns. Bytes of the blob (a multiple
+// of 16), 0 when nothing is staged; `mismatch` when it was staged for another batch, which the call then refuses.
+size_t take_effects(int num, int w, int h, bool& mismatch) {
+    PendingFx& f = g_fx;
+    mismatch = false;
+    if (!f.active) return 0;
+    f.active = false;
+    mismatch = f.num != num || f.w != w || f.h != h;
+    return mismatch ? 0 : f.blob.size();
+}
+
 template <int C, bool kWin = false>
 void launch(uint8_t* block_d, float* dst_d, AugParams p, int num, hipStream_t st) {
     p.blocks_per_sample = ceil_div((long long)p.sw * p.sh, kAugBlock);
@@ -306,7 +463,9 @@ void launch(uint8_t* block_d, float* dst_d, AugParams p, int num, hipStream_t st
     KERNEL_CHECK();
     p.runs_per_row = ceil_div(p.W, kRun);
     p.blocks_per_sample = ceil_div((long long)p.runs_per_row * p.H, kAugBlock);
-    augment_convert_kernel<C><<<dim3((unsigned)(p.blocks_per_sample * num)), kAugBlock, 0, st>>>(block_d, dst_d, p);
+    const dim3 grid((unsigned)(p.blocks_per_sample * num));
+    if (p.fx_off) augment_convert_effects_kernel<C><<<grid, kAugBlock, 0, st>>>(block_d, dst_d, p);
+    else augment_convert_kernel<C><<<grid, kAugBlock, 0, st>>>(block_d, dst_d, p);
     KERNEL_CHECK();
 }
 
@@ -347,6 +506,9 @@ extern "C" {
 int bcnn_hip_augment_batch(float* dst_d, int n, int c, int h, int w, int num_samples, int src_w, int src_h,
                            const uint8_t* pixels, const bcnn_hip_augment_record* records, const int32_t* taps,
                            int swap_to_bgr) {
+    bool fx_mismatch;
+    const size_t fx_bytes = take_effects(num_samples, src_w, src_h, fx_mismatch);
+    if (fx_mismatch) return 1;
     if (!dst_d || !pixels || !records || n < 1 || h < 1 || w < 1 || c < 1 || c > 4 || num_samples < 1 || num_samples > n ||
         src_w < w || src_h < h || (long long)src_w * src_h > 0x7fffffff / (c * (long long)num_samples))
         return 1;
@@ -358,11 +520,13 @@ int bcnn_hip_augment_batch(float* dst_d, int n, int c, int h, int w, int num_sam
     const size_t rec_bytes = align_up(num * sizeof(bcnn_hip_augment_record), 16), sum_bytes = num * 4 * sizeof(uint32_t);
     const size_t tap_bytes = any_scale ? num * sample_taps * 2 * sizeof(int32_t) : 0;
     const size_t pix_bytes = align_up(num * sample_bytes, 16);
-    const size_t total = rec_bytes + sum_bytes + tap_bytes + pix_bytes;
+    const size_t plain = rec_bytes + sum_bytes + tap_bytes + pix_bytes;
+    const size_t fx_at = fx_bytes ? align_up(plain, 16) : 0, total = fx_bytes ? fx_at + fx_bytes : plain;
     if (total + pix_bytes > (size_t)0x7fffffff) return 1;
     if (any_scale && !taps_in_range(records, taps, num, src_w, src_h)) return 1;
 
-    // the staging block: [records][channel sums, zero][taps][pixels]; behind it on the device, the rotated samples
+    // the staging block: [records][channel sums, zero][taps][pixels][staged effects]; behind it on the device, the rotated
+    // samples
     uint8_t* stage = host_stage(total);
     AugParams p;
     p.rec_off = 0;
@@ -370,6 +534,8 @@ int bcnn_hip_augment_batch(float* dst_d, int n, int c, int h, int w, int num_sam
     p.tap_off = (uint32_t)(rec_bytes + sum_bytes);
     p.pix_off = (uint32_t)(rec_bytes + sum_bytes + tap_bytes);
     p.s4_off = (uint32_t)total;
+    p.fx_off = (uint32_t)fx_at;
+    if (fx_bytes) memcpy(stage + fx_at, g_fx.blob.data(), fx_bytes);
     memcpy(stage, records, num * sizeof(bcnn_hip_augment_record));
     memset(stage + p.sum_off, 0, sum_bytes);
     if (any_scale) memcpy(stage + p.tap_off, taps, tap_bytes);
@@ -406,6 +572,9 @@ int bcnn_hip_augment_batch(float* dst_d, int n, int c, int h, int w, int num_sam
 int bcnn_hip_augment_letterbox_batch(float* dst_d, int n, int c, int h, int w, int num_samples,
                                      const bcnn_hip_letterbox_image* images, const bcnn_hip_augment_record* records,
                                      const int32_t* taps, int swap_to_bgr) {
+    bool fx_mismatch;
+    const size_t fx_bytes = take_effects(num_samples, w, h, fx_mismatch);
+    if (fx_mismatch) return 1;
     if (!dst_d || !images || !records || n < 1 || h < 1 || w < 1 || c < 1 || c > 4 || num_samples < 1 || num_samples > n ||
         (long long)w * h > 0x7fffffff / (c * (long long)num_samples))
         return 1;
@@ -430,13 +599,14 @@ int bcnn_hip_augment_letterbox_batch(float* dst_d, int n, int c, int h, int w, i
     const size_t desc_bytes = align_up(num * sizeof(LetterboxDesc), 16);
     const size_t canvas_bytes = align_up(num * sample_bytes, 16);
     const size_t desc_at = rec_bytes + sum_bytes + tap_bytes, lb_tap_at = desc_at + desc_bytes;
-    const size_t src_at = lb_tap_at + align_up(lb_tap_bytes, 16), total = src_at + src_bytes;
+    const size_t src_at = lb_tap_at + align_up(lb_tap_bytes, 16), fx_at = src_at + src_bytes, total = fx_at + fx_bytes;
     if (total + 2 * canvas_bytes > (size_t)0x7fffffff) return 1;
     if (any_scale && !taps_in_range(records, taps, num, w, h)) return 1;
 
-    // the staging block: [records][channel sums, zero][augmentation taps][descriptors][letterbox taps][source pixels];
-    // behind it on the device, the canvases and the rotated samples
+    // the staging block: [records][channel sums, zero][augmentation taps][descriptors][letterbox taps][source pixels]
+    // [staged effects]; behind it on the device, the canvases and the rotated samples
     uint8_t* stage = host_stage(total);
+    if (fx_bytes) memcpy(stage + fx_at, g_fx.blob.data(), fx_bytes);
     memcpy(stage, records, num * sizeof(bcnn_hip_augment_record));
     memset(stage + rec_bytes, 0, sum_bytes);
     if (any_scale) memcpy(stage + rec_bytes + sum_bytes, taps, num * sample_taps * 2 * sizeof(int32_t));
@@ -497,6 +667,7 @@ int bcnn_hip_augment_letterbox_batch(float* dst_d, int n, int c, int h, int w, i
     p.swap = (swap_to_bgr && c == 3) ? 1 : 0;
     p.blocks_per_sample = p.runs_per_row = 0;
     p.win_off = 0;
+    p.fx_off = fx_bytes ? (uint32_t)fx_at : 0;
     switch (c) {
         case 1: launch<1>(block_d, dst_d, p, num_samples, st); break;
         case 2: launch<2>(block_d, dst_d, p, num_samples, st); break;
@@ -564,13 +735,86 @@ int bcnn_hip_augment_jpeg_begin(int n, int c, int h, int w, int num_samples, con
 
 void bcnn_hip_augment_jpeg_cancel(void) { g_jpeg.active = false; }
 
+int bcnn_hip_augment_effects_begin(int num_samples, int src_w, int src_h, const bcnn_hip_augment_effect* effects,
+                                   const float* perlin, const int32_t* cells, const bcnn_hip_augment_spot* spots,
+                                   int num_spots, const float* spot_tables, size_t num_table_floats) {
+    PendingFx& q = g_fx;
+    q.active = false;
+    if (!effects || num_samples < 1 || src_w < 1 || src_h < 1 || num_spots < 0 || (num_spots > 0 && (!spots || !spot_tables)))
+        return 1;
+    // ---- every refusal comes before anything is staged
+    const size_t num = (size_t)num_samples, axis = (size_t)src_w + src_h;
+    size_t distorted = 0;
+    for (size_t b = 0; b < num; ++b) {
+        const bcnn_hip_augment_effect& e = effects[b];
+        if (e.flags & ~(BCNN_HIP_AUG_DISTORT | BCNN_HIP_AUG_SPOTS)) return 1;
+        if (e.flags & BCNN_HIP_AUG_DISTORT) {
+            if (!perlin || !cells || !(e.distortion >= -3.4028234e38f && e.distortion <= 3.4028234e38f)) return 1;
+            ++distorted;
+        }
+        if ((e.flags & BCNN_HIP_AUG_SPOTS) &&
+            (e.first_spot < 0 || e.num_spots < 0 || e.first_spot > num_spots || e.num_spots > num_spots - e.first_spot))
+            return 1;
+    }
+    for (int s = 0; s < num_spots; ++s) {   // the box inside the sample, the table inside spot_tables
+        const bcnn_hip_augment_spot& t = spots[s];
+        if (t.x0 < 0 || t.y0 < 0 || t.bw < 1 || t.bh < 1 || t.bw > src_w - t.x0 || t.bh > src_h - t.y0 ||
+            t.table > num_table_floats || (size_t)t.bw * t.bh > num_table_floats - t.table)
+            return 1;
+    }
+    if (num_table_floats > (size_t)0x7fffffff / sizeof(float) || axis > (size_t)0x7fffffff / (12 * num)) return 1;
+    const size_t sample_at = sizeof(FxHeader), spot_at = sample_at + align_up(num * sizeof(FxSample), 16);
+    const size_t perlin_at = spot_at + align_up((size_t)num_spots * sizeof(FxSpot), 16);
+    const size_t table_at = perlin_at + align_up(distorted * axis * 12, 16);
+    const size_t total = table_at + align_up(num_table_floats * sizeof(float), 16);
+    if (total > (size_t)0x7fffffff) return 1;
+
+    q.blob.assign(total, 0);
+    uint8_t* blob = q.blob.data();
+    reinterpret_cast<FxHeader*>(blob)->spot_off = (uint32_t)spot_at;
+    FxSample* fs = reinterpret_cast<FxSample*>(blob + sample_at);
+    size_t at = perlin_at;
+    for (size_t b = 0; b < num; ++b) {
+        const bcnn_hip_augment_effect& e = effects[b];
+        fs[b].flags = e.flags;
+        if (e.flags & BCNN_HIP_AUG_DISTORT) {   // norm and weight (columns, rows), then the cells
+            fs[b].seed = e.seed;
+            fs[b].distortion = e.distortion;
+            fs[b].perlin_off = (uint32_t)at;
+            memcpy(blob + at, perlin + b * axis * 2, axis * 2 * sizeof(float));
+            memcpy(blob + at + axis * 2 * sizeof(float), cells + b * axis, axis * sizeof(int32_t));
+            at += axis * 12;
+        }
+        if (e.flags & BCNN_HIP_AUG_SPOTS) {
+            fs[b].first_spot = e.first_spot;
+            fs[b].num_spots = e.num_spots;
+        }
+    }
+    FxSpot* sp = reinterpret_cast<FxSpot*>(blob + spot_at);
+    for (int s = 0; s < num_spots; ++s) {
+        const FxSpot v = {spots[s].x0, spots[s].y0, spots[s].bw, spots[s].bh,
+                          (uint32_t)(table_at + (size_t)spots[s].table * sizeof(float))};
+        sp[s] = v;
+    }
+    if (num_table_floats) memcpy(blob + table_at, spot_tables, num_table_floats * sizeof(float));
+    q.num = num_samples;
+    q.w = src_w;
+    q.h = src_h;
+    q.active = true;
+    return 0;
+}
+
+void bcnn_hip_augment_effects_cancel(void) { g_fx.active = false; }
+
 int bcnn_hip_augment_jpeg_run(float* dst_d, const uint8_t* decoded, const uint8_t* pixels,
                               const bcnn_hip_augment_record* records, const int32_t* taps, const int32_t* origins,
                               int swap_to_bgr) {
     PendingJpeg& q = g_jpeg;
+    bool fx_mismatch;
+    const size_t fx_bytes = take_effects(q.active ? q.num : 0, q.active ? q.w : 0, q.active ? q.h : 0, fx_mismatch);
     if (!q.active) return 1;
     q.active = false;
-    if (!dst_d || !decoded || !pixels || !records || !origins) return 1;
+    if (fx_mismatch || !dst_d || !decoded || !pixels || !records || !origins) return 1;
     const size_t num = (size_t)q.num, sample_bytes = (size_t)q.w * q.h * q.c, sample_taps = (size_t)q.w + q.h;
     bool any_scale = false;
     for (size_t b = 0; b < num; ++b) {
@@ -578,15 +822,23 @@ int bcnn_hip_augment_jpeg_run(float* dst_d, const uint8_t* decoded, const uint8_
         any_scale = any_scale || (records[b].flags & BCNN_HIP_AUG_SCALE);
     }
     if (any_scale && (!taps || !taps_in_range(records, taps, num, q.w, q.h))) return 1;
+    // staged effects go behind the upload part _begin laid out, and the device-only part moves back by as much
+    const size_t fx_at = fx_bytes ? align_up(q.device_at, 16) : 0, device_at = fx_bytes ? fx_at + fx_bytes : q.device_at;
+    const size_t total = q.total + (device_at - q.device_at);
+    if (total > (size_t)0x7fffffff) return 1;
 
     uint8_t* stage = q.stage;
+    if (fx_bytes) {
+        stage = q.stage = host_stage_extend(q.device_at, fx_at + fx_bytes);
+        memcpy(stage + fx_at, g_fx.blob.data(), fx_bytes);
+    }
     memcpy(stage, records, num * sizeof(bcnn_hip_augment_record));
     memset(stage + q.sum_off, 0, num * 4 * sizeof(uint32_t));
     if (any_scale) memcpy(stage + q.tap_off, taps, num * sample_taps * 2 * sizeof(int32_t));
     else  // the tap table holds nothing: no record may ask for it
         for (size_t b = 0; b < num; ++b) reinterpret_cast<bcnn_hip_augment_record*>(stage)[b].flags &= ~BCNN_HIP_AUG_SCALE;
     AugWindow* win = reinterpret_cast<AugWindow*>(stage + q.win_off);
-    JpegCursor cur = {0, q.device_at, q.device_at + q.plane_bytes, 0, 0, 0, 0};
+    JpegCursor cur = {0, device_at, device_at + q.plane_bytes, 0, 0, 0, 0};
     size_t raw_at = q.raw_at;
     for (size_t b = 0; b < num; ++b) {
         if (decoded[b]) {   // a window of the image the colour kernel leaves at cur.pixel_at
@@ -605,9 +857,9 @@ int bcnn_hip_augment_jpeg_run(float* dst_d, const uint8_t* decoded, const uint8_
     jpeg_close_tables(stage, q.planes_at, q.images_at, cur);
 
     // ---- one copy, four launches
-    uint8_t* block_d = reinterpret_cast<uint8_t*>(scratch(SCRATCH_AUGMENT, (q.total + 3) / 4));
+    uint8_t* block_d = reinterpret_cast<uint8_t*>(scratch(SCRATCH_AUGMENT, (total + 3) / 4));
     hipStream_t st = current_stream();
-    HIP_CHECK(hipMemcpyAsync(block_d, stage, raw_at, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(block_d, stage, fx_bytes ? fx_at + fx_bytes : raw_at, hipMemcpyHostToDevice, st));
     HostStage& hs = g_stage[current_device()];
     HIP_CHECK(hipEventRecord(hs.copied, st));
     hs.in_flight = true;
@@ -619,7 +871,8 @@ int bcnn_hip_augment_jpeg_run(float* dst_d, const uint8_t* decoded, const uint8_
     p.tap_off = (uint32_t)q.tap_off;
     p.pix_off = 0;
     p.win_off = (uint32_t)q.win_off;
-    p.s4_off = (uint32_t)(q.device_at + q.plane_bytes + q.pixel_bytes);
+    p.s4_off = (uint32_t)(device_at + q.plane_bytes + q.pixel_bytes);
+    p.fx_off = (uint32_t)fx_at;
     p.sw = p.W = q.w;
     p.sh = p.H = q.h;
     p.cx = p.cy = 0;

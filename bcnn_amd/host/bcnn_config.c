@@ -13,6 +13,7 @@
  * One deliberate difference: the reference discards the status of the layer builders; here a builder that
  * fails (an out-of-scope layer of this build, a bad tensor name) aborts the load with its status instead of
  * leaving a half-built graph. */
+#include <float.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -131,6 +132,7 @@ static void net_set_param(bcnn_net *net, const char *name, const char *val) {
     else if (!strcmp(name, "loader_on_device")) bcnn_set_loader_on_device(net, atoi(val));
     else if (!strcmp(name, "loader_decode_on_device")) bcnn_set_loader_decode_on_device(net, atoi(val));
     else if (!strcmp(name, "loader_detection_on_device")) bcnn_set_loader_detection_on_device(net, atoi(val));
+    else if (!strcmp(name, "loader_effects")) bcnn_set_loader_effects(net, atoi(val));
     else if (!strcmp(name, "train_detector")) bcnn_set_detector_training(net, atoi(val));
     else if (ln && !strcmp(name, "max_batches")) ln->max_batches = atoi(val);
     else if (ln && (!strcmp(name, "learning_policy") || !strcmp(name, "decay_type"))) {
@@ -159,7 +161,11 @@ static void net_set_param(bcnn_net *net, const char *name, const char *val) {
     else if (da && !strcmp(name, "max_contrast")) da->max_contrast = (float)atof(val);
     else if (da && !strcmp(name, "min_brightness")) da->min_brightness = atoi(val);
     else if (da && !strcmp(name, "max_brightness")) da->max_brightness = atoi(val);
-    else if (da && !strcmp(name, "max_distortion")) da->max_distortion = (float)atof(val);
+    else if (da && !strcmp(name, "max_distortion")) {
+        const float v = (float)atof(val); /* a strength: negative, NaN and infinity are refused and the key is dropped */
+        if (v >= 0.0f && v <= FLT_MAX) da->max_distortion = v;
+        else bcnn_log(net->log_ctx, BCNN_LOG_WARNING, "max_distortion=%s is negative or not finite, keeping the current one\n", val);
+    }
     else if (da && !strcmp(name, "max_spots")) da->max_random_spots = (int)atof(val);
     else if (da && !strcmp(name, "flip_h")) da->random_fliph = 1;
     else if (da && !strcmp(name, "mean_r")) da->mean_r = (float)atof(val) / 255.0f;

@@ -748,6 +748,16 @@ int bcnn_get_loader_device_letterboxed(const bcnn_net *net) {
     return net ? ((const bcnn_hip_context *)net->hip_ctx)->loader_device_letterboxed : 0;
 }
 
+bcnn_status bcnn_set_loader_effects(bcnn_net *net, int on) {
+    if (!net) return BCNN_INVALID_PARAMETER;
+    hctx(net)->loader_effects = on ? 1 : 0;
+    return BCNN_SUCCESS;
+}
+
+int bcnn_get_loader_effects(const bcnn_net *net) {
+    return net ? ((const bcnn_hip_context *)net->hip_ctx)->loader_effects : 0;
+}
+
 bcnn_status bcnn_set_detector_training(bcnn_net *net, int on) {
     if (!net) return BCNN_INVALID_PARAMETER;
     hctx(net)->detector_training = on ? 1 : 0;

@@ -14,8 +14,10 @@
  *                             (detection_batch_device below). Nothing reads it->input_net / it->input_uchar for that loader
  *                             type between samples, so that path writes neither of them, nor tensors[0].data
  *   bcnn_augment_data_with_*  augmentation ranges; bcnn_apply_data_augmentation draws the parameters of one sample from
- *                             libc rand() in the reference's order (flip, shift, scale, rotation, contrast, brightness), so
- *                             that a run seeded like a reference run sees the same samples byte for byte
+ *                             libc rand() in the reference's order (flip, shift, scale, rotation, contrast, brightness,
+ *                             distortion, spotlights), so that a run seeded like a reference run sees the same samples byte
+ *                             for byte
+ *   bcnn_set_loader_effects   (bcnn_core.c) whether bcnn_loader_next applies the last two of them, or only makes their draws
  *   formats: BCNN_LOAD_MNIST (idx3 images + idx1 labels, big-endian headers), BCNN_LOAD_CIFAR10 (1 + 3072 byte records,
  *            planar RGB), BCNN_LOAD_CLASSIFICATION_LIST ("path label" lines), BCNN_LOAD_REGRESSION_LIST ("path v0 v1 ..").
  *            BCNN_LOAD_DETECTION_LIST ("path (class x y w h)*" lines: bcnn_detection_loader.c) letterboxes the image onto a
@@ -30,9 +32,12 @@
  * One deliberate difference in the detection-list reader: the reference forms the image's aspect ratio w / h in INTEGER
  * arithmetic (bcnn_detection_loader.c:103), which gives a portrait image width 0 and stretches a 4:3 image square; here
  * the ratio is the float one. Batches and labels are the reference's whenever the height divides the width.
- * Not built: Perlin distortion and random spotlights (INI keys max_distortion / max_spots). Their draws still consume
- * rand() call for call like the reference (parameters, the distortion's own seed, four values per spot), so that the other
- * augmentations stay aligned; the image is left untouched and a warning is printed once.
+ * Perlin distortion and random spotlights (INI keys max_distortion / max_spots, bcnn_augment_data_with_blobs) are applied
+ * by the loader behind a switch that is off by default, bcnn_set_loader_effects (`loader_effects=1`): stages 7 and 8 of
+ * augment_pixels on the host, the effects kernel of ../csrc/augment.hip on the three device routes. With the switch off
+ * their draws still consume rand() call for call like the reference (parameters, the distortion's own seed, four values per
+ * spot), so that the other augmentations stay aligned; the image is left untouched and a warning is printed once.
+ * bcnn_apply_data_augmentation, which takes no net, always applies them, like the reference's.
  */
 #include <math.h>
 #include <pthread.h>
@@ -94,13 +99,21 @@ typedef struct {
     int x_ul, y_ul;                                     /* shift origin; (0, 0) without a shift */
     float scale_factor, theta, contrast_factor;
     int brightness;
+    int distort;                 /* Perlin distortion runs: its offsets, its strength and the seed of its lattice */
+    float kx, ky, distortion;
+    int32_t seed;
+    int spots;                   /* spotlights that run, in this order (0: the stage is the identity) */
+    bip_spot spot[BCNN_MAX_SPOTS];
 } aug_draw;
 
 /* Draws the parameters of one sample from rand() in the reference's order and number (shift x, shift y, scale, rotation,
- * contrast, brightness, then the draws of the two effects that are not built), leaves them in `p` as the reference does,
- * and touches no pixel. With use_precomputed the values already in `p` are taken instead. */
-static void draw_augmentation(bcnn_data_augmenter *p, aug_draw *d) {
-    memset(d, 0, sizeof(*d));
+ * contrast, brightness, then the two effects: kx, ky, distortion, the seed bip_image_perlin_distortion draws for itself;
+ * the spot count and four values per spot), leaves them in `p` as the reference does, and touches no pixel. With
+ * use_precomputed the values already in `p` are taken instead. `effects` (bcnn_set_loader_effects): the draws of the two
+ * effects are kept in `d` for a width x height sample; without it they are made and dropped, and the sample keeps its
+ * pixels. */
+static void draw_augmentation(bcnn_data_augmenter *p, aug_draw *d, int effects, int width, int height) {
+    memset(d, 0, offsetof(aug_draw, spot)); /* spot[0 .. spots) is all that is read of the list */
     d->flip = p->random_fliph && p->apply_fliph;
     if (p->range_shift_x || p->range_shift_y) {
         d->shift = 1;
@@ -130,8 +143,8 @@ static void draw_augmentation(bcnn_data_augmenter *p, aug_draw *d) {
                             ? p->brightness
                             : (p->brightness = (int)rand_span((float)p->min_brightness, (float)p->max_brightness));
     }
-    /* Not built: Perlin distortion and random spotlights. Their draws are consumed exactly as the reference consumes them,
-     * so that the samples behind this one see the generator in the reference's state: three parameters (when not
+    /* Perlin distortion and random spotlights. Their draws are consumed exactly as the reference consumes them, kept or
+     * not, so that the samples behind this one see the generator in the reference's state: three parameters (when not
      * precomputed) plus the seed bip_image_perlin_distortion draws for itself on every call (bip.c:212); the spot count
      * plus four values per spot (mu_x, mu_y, sigma_x, sigma_y: bip.c:294-298). */
     if (p->max_distortion > 0.0f) {
@@ -140,16 +153,29 @@ static void draw_augmentation(bcnn_data_augmenter *p, aug_draw *d) {
             p->distortion_ky = ((float)rand() - RAND_MAX / 2) / RAND_MAX;
             p->distortion = ((float)rand() / RAND_MAX) * p->max_distortion;
         }
-        (void)rand();
+        const int32_t seed = rand();
+        if (effects) {
+            d->distort = 1;
+            d->kx = p->distortion_kx;
+            d->ky = p->distortion_ky;
+            d->distortion = p->distortion;
+            d->seed = seed;
+        }
     }
     if (p->max_random_spots > 0) {
         const int spots = rand_between(0, p->max_random_spots);
-        for (int i = 0; i < 4 * spots; ++i) (void)rand();
+        for (int i = 0; i < spots; ++i) {
+            bip_spot s; /* the callers refuse a range above BCNN_MAX_SPOTS before they draw */
+            if (effects) bip_draw_spot((size_t)width, (size_t)height, 0.3f, 3.0f, 0.3f, 3.0f, i < BCNN_MAX_SPOTS ? &d->spot[i] : &s);
+            else for (int k = 0; k < 4; ++k) (void)rand();
+        }
+        if (effects) d->spots = spots < BCNN_MAX_SPOTS ? spots : BCNN_MAX_SPOTS;
     }
     static int warned = 0;
-    if ((p->max_distortion > 0.0f || p->max_random_spots > 0) && !warned) {
+    if (!effects && (p->max_distortion > 0.0f || p->max_random_spots > 0) && !warned) {
         warned = 1;
-        fprintf(stderr, "[bcnn] max_distortion / max_spots: Perlin distortion and random spotlights are not built; samples keep "
+        fprintf(stderr, "[bcnn] max_distortion / max_spots: Perlin distortion and random spotlights are off "
+                        "(bcnn_set_loader_effects, or loader_effects=1 in the [net] section, turns them on); samples keep "
                         "their pixels (the random stream stays aligned with the reference)\n");
     }
 }
@@ -184,14 +210,24 @@ static bcnn_status augment_pixels(unsigned char *img, int width, int height, int
     }
     if (d->contrast) bip_contrast_stretch(img, stride, width, height, depth, img, stride, d->contrast_factor);
     if (d->brighten) bip_image_brightness(img, stride, width, height, depth, img, stride, d->brightness);
+    if (d->distort) { /* reads img, writes another image: into the scratch and back */
+        unsigned char *out = scratch ? scratch : (unsigned char *)malloc(bytes);
+        if (!out) return BCNN_FAILED_ALLOC;
+        bip_perlin_distortion_seeded(img, stride, width, height, depth, out, stride, d->distortion, d->kx, d->ky, d->seed);
+        memcpy(img, out, bytes);
+        if (!scratch) free(out);
+    }
+    if (d->spots > 0) bip_add_spotlights(img, stride, width, height, depth, img, stride, d->spot, (uint32_t)d->spots);
     return BCNN_SUCCESS;
 }
 
-/* One sample, in place: the draws, then the pixels. */
+/* One sample, in place: the draws, then the pixels. The reference's function in full: it takes no net, so both effects
+ * run whenever their range is set. The loader does not come through here (augment_if_training). */
 bcnn_status bcnn_apply_data_augmentation(unsigned char *img, int width, int height, int depth, bcnn_data_augmenter *p,
                                          unsigned char *scratch) {
+    if (p->max_random_spots > BCNN_MAX_SPOTS) return BCNN_INVALID_PARAMETER; /* before any draw */
     aug_draw d;
-    draw_augmentation(p, &d);
+    draw_augmentation(p, &d, 1, width, height);
     return augment_pixels(img, width, height, depth, &d, scratch);
 }
 
@@ -259,6 +295,7 @@ typedef struct {
     uint8_t *pixels;                  /* batch x (w * h * c) raw samples */
     bcnn_hip_augment_record *records; /* batch */
     int32_t *taps;                    /* batch x (w + h) (index, fraction) pairs; written for samples that scale */
+    aug_draw *draws;                  /* batch: what the records were made from (the effects' tables, the host fallback) */
     size_t cap_bytes, cap_records, cap_taps;
     int w, h, c;                      /* the stored sample of the batch being gathered */
     int active;                       /* inside a device-mode bcnn_loader_next */
@@ -267,6 +304,7 @@ typedef struct {
      * holds it raw, and `owed` remembers the pixel work that makes the two equal should a decode fail next. */
     int owed;
     aug_draw owed_draw;
+    int refused; /* the device side refused this batch's effects: bcnn_loader_next makes it on the host */
     /* bcnn_set_loader_decode_on_device. Per sample of the batch being gathered: 1 = its pixels are made on the device, and
      * the origin of its crop window there. A device-decoded sample leaves no pixels on the host, so `lazy` keeps what
      * rebuilds the latest one in it->input_uchar should a decode fail next: the file's bytes and the crop origin. */
@@ -282,7 +320,8 @@ static loader_stage *stage_of(bcnn_net *net) { return (loader_stage *)((bcnn_hip
 void bcnn_free_loader_stage(bcnn_net *net) {
     loader_stage *ls = stage_of(net);
     if (!ls) return;
-    free(ls->pixels); free(ls->records); free(ls->taps); free(ls->decoded); free(ls->origins); free(ls->lazy); free(ls);
+    free(ls->pixels); free(ls->records); free(ls->taps); free(ls->draws); free(ls->decoded); free(ls->origins); free(ls->lazy);
+    free(ls);
     ((bcnn_hip_context *)net->hip_ctx)->loader_stage = NULL;
 }
 
@@ -354,11 +393,12 @@ static loader_stage *stage_begin(bcnn_net *net, bcnn_loader *it) {
         ls->cap_bytes = ls->pixels ? bytes : 0;
     }
     if (ls->cap_records < n) {
-        free(ls->records); free(ls->decoded); free(ls->origins);
+        free(ls->records); free(ls->decoded); free(ls->origins); free(ls->draws);
         ls->records = (bcnn_hip_augment_record *)calloc(n, sizeof(bcnn_hip_augment_record));
         ls->decoded = (uint8_t *)calloc(n, 1);
         ls->origins = (int32_t *)calloc(2 * n, sizeof(int32_t));
-        ls->cap_records = (ls->records && ls->decoded && ls->origins) ? n : 0;
+        ls->draws = (aug_draw *)calloc(n, sizeof(aug_draw));
+        ls->cap_records = (ls->records && ls->decoded && ls->origins && ls->draws) ? n : 0;
     }
     if (ls->cap_taps < taps) {
         free(ls->taps);
@@ -415,18 +455,81 @@ static void fill_record(bcnn_hip_augment_record *r, int32_t *taps, const aug_dra
     if (d->brighten) r->brightness = d->brightness;
 }
 
+static int effects_on(const bcnn_net *net) { return ((const bcnn_hip_context *)net->hip_ctx)->loader_effects; }
+
+/* How far from its centre a spotlight of the loader can change a byte. The loader draws sigma in [0.3 + 0.5, 3.0 + 0.5]
+ * (bip_draw_spot; the float sums may round up by an ulp: sigma^2 <= 12.2500015). At |dx| >= 12 or |dy| >= 12 the exponent is
+ * <= -0.5 * 144 / 12.2500015 = -5.877, so val <= exp(-5.877) = 0.00281 and 255 * val <= 0.716: added to a byte d in fp32
+ * (ulp <= 2^-16 there) the sum stays below d + 1 and truncates to d again, and a sum above 255 is clamped to 255 = d. The
+ * farthest pixel that does change is at distance 11 (255 * exp(-0.5 * 121 / 12.25) = 1.83). So the device gets `val` over
+ * the box of radius 12 only; tests/test_augment_effects.py holds the table form to the full-image form. */
+#define BCNN_SPOT_RADIUS 12
+#define BCNN_SPOT_BOX ((2 * BCNN_SPOT_RADIUS + 1) * (2 * BCNN_SPOT_RADIUS + 1))
+
+/* Stages the effects of the batch whose n draws lie `stride` bytes apart from `first` on, for the batch call that follows
+ * (bcnn_hip_augment_effects_begin): every cos and exp is made here, with libm. 0: no sample of the batch has an effect,
+ * nothing is staged; 1: staged; -1: refused -- the caller makes this batch on the host from the same draws. */
+static int stage_effects(const void *first, size_t stride, int n, int w, int h) {
+    size_t spots = 0, distorted = 0;
+    for (int i = 0; i < n; ++i) {
+        const aug_draw *d = (const aug_draw *)((const char *)first + (size_t)i * stride);
+        spots += (size_t)d->spots;
+        distorted += d->distort ? 1 : 0;
+    }
+    if (spots == 0 && distorted == 0) return 0;
+    const size_t axis = (size_t)w + h;
+    bcnn_hip_augment_effect *fx = (bcnn_hip_augment_effect *)calloc((size_t)n, sizeof(*fx));
+    float *perlin = (float *)calloc(distorted ? (size_t)n * axis * 2 : 1, sizeof(float));
+    int32_t *cells = (int32_t *)calloc(distorted ? (size_t)n * axis : 1, sizeof(int32_t));
+    bcnn_hip_augment_spot *sp = (bcnn_hip_augment_spot *)calloc(spots ? spots : 1, sizeof(*sp));
+    float *tables = (float *)calloc(spots ? spots * BCNN_SPOT_BOX : 1, sizeof(float));
+    int rc = (fx && perlin && cells && sp && tables) ? 1 : -1;
+    size_t at = 0, floats = 0;
+    for (int i = 0; rc == 1 && i < n; ++i) {
+        const aug_draw *d = (const aug_draw *)((const char *)first + (size_t)i * stride);
+        if (d->distort) {
+            fx[i].flags |= BCNN_HIP_AUG_DISTORT;
+            fx[i].seed = d->seed;
+            fx[i].distortion = d->distortion;
+            float *norm = perlin + (size_t)i * axis * 2, *weight = norm + axis;
+            bip_perlin_axis((size_t)w, d->kx, norm, weight, cells + (size_t)i * axis);
+            bip_perlin_axis((size_t)h, d->ky, norm + w, weight + w, cells + (size_t)i * axis + w);
+        }
+        if (d->spots > 0) {
+            fx[i].flags |= BCNN_HIP_AUG_SPOTS;
+            fx[i].first_spot = (int32_t)at;
+            fx[i].num_spots = d->spots;
+            for (int s = 0; s < d->spots; ++s, ++at) {
+                int32_t box[4];
+                if (bip_spot_table(&d->spot[s], (size_t)w, (size_t)h, BCNN_SPOT_RADIUS, box, tables + floats) != BIP_SUCCESS) {
+                    rc = -1;
+                    break;
+                }
+                sp[at].x0 = box[0]; sp[at].y0 = box[1]; sp[at].bw = box[2]; sp[at].bh = box[3];
+                sp[at].table = (uint32_t)floats;
+                floats += (size_t)box[2] * box[3];
+            }
+        }
+    }
+    if (rc == 1 && bcnn_hip_augment_effects_begin(n, w, h, fx, perlin, cells, sp, (int)spots, tables, floats) != 0) rc = -1;
+    free(fx); free(perlin); free(cells); free(sp); free(tables);
+    return rc;
+}
+
 /* Slot idx of the block gets this sample's draws (TRAIN mode) or the identity record. */
 static void stage_draws(bcnn_net *net, loader_stage *ls, int idx, int w, int h, int list_loader) {
     bcnn_hip_augment_record *r = &ls->records[idx];
     memset(r, 0, sizeof(*r));
     ls->owed = 0;
-    if (net->mode == BCNN_MODE_TRAIN && net->data_aug) {
-        aug_draw d;
-        draw_augmentation(net->data_aug, &d);
-        fill_record(r, ls->taps + (size_t)idx * ((size_t)w + h) * 2, &d, w, h);
+    if (!(net->mode == BCNN_MODE_TRAIN && net->data_aug)) {
+        memset(&ls->draws[idx], 0, offsetof(aug_draw, spot)); /* the identity */
+    } else {
+        aug_draw *d = &ls->draws[idx];
+        draw_augmentation(net->data_aug, d, effects_on(net), w, h);
+        fill_record(r, ls->taps + (size_t)idx * ((size_t)w + h) * 2, d, w, h);
         if (list_loader) {
             ls->owed = 1;
-            ls->owed_draw = d;
+            ls->owed_draw = *d;
         }
     }
 }
@@ -442,20 +545,49 @@ static bcnn_status stage_sample(bcnn_net *net, bcnn_loader *it, loader_stage *ls
 }
 
 /* ---- sample -> tensors ---------------------------------------------------------------------------------------------- */
-static int needs_scratch(const bcnn_data_augmenter *a, int list_loader) {
+static int needs_scratch(const bcnn_data_augmenter *a, int list_loader, int effects) {
     if (a->range_shift_x != 0 || a->range_shift_y != 0 || a->random_fliph != 0) return 1;
     if (list_loader) return a->rotation_range > 0.0f || a->max_random_spots > 0 || a->max_distortion > 0.0f;
+    if (effects && (a->max_random_spots > 0 || a->max_distortion > 0.0f)) return 1;
     return a->rotation_range != 0;
 }
 
+/* The loader's own pair of steps: the draws, with the net's effects switch, then the pixels. */
 static bcnn_status augment_if_training(bcnn_net *net, unsigned char *img, int w, int h, int c, int list_loader) {
     if (net->mode != BCNN_MODE_TRAIN || !net->data_aug) return BCNN_SUCCESS;
     unsigned char *scratch = NULL;
-    if (needs_scratch(net->data_aug, list_loader)) {
+    if (needs_scratch(net->data_aug, list_loader, effects_on(net))) {
         scratch = (unsigned char *)calloc((size_t)w * h * c, 1);
         if (!scratch) return BCNN_FAILED_ALLOC;
     }
-    const bcnn_status st = bcnn_apply_data_augmentation(img, w, h, c, net->data_aug, scratch);
+    aug_draw d;
+    draw_augmentation(net->data_aug, &d, effects_on(net), w, h);
+    const bcnn_status st = augment_pixels(img, w, h, c, &d, scratch);
+    free(scratch);
+    return st;
+}
+
+/* The batch the device side refused (bcnn_hip_augment_effects_begin), made on the host from the raw samples and the draws
+ * the block holds: pixel step, centre crop of a stored-size sample, conversion into tensors[0].data, which the caller
+ * then uploads. */
+static bcnn_status host_batch_from_stage(bcnn_net *net, loader_stage *ls, int list_loader) {
+    bcnn_tensor *in = &net->tensors[0];
+    const size_t bytes = (size_t)ls->w * ls->h * ls->c, out = (size_t)bcnn_tensor_size3d(in);
+    unsigned char *scratch = (unsigned char *)calloc(bytes + out, 1);
+    if (!scratch) return BCNN_FAILED_ALLOC;
+    bcnn_status st = BCNN_SUCCESS;
+    for (int i = 0; i < net->batch_size && st == BCNN_SUCCESS; ++i) {
+        unsigned char *img = ls->pixels + (size_t)i * bytes;
+        st = augment_pixels(img, ls->w, ls->h, ls->c, &ls->draws[i], scratch);
+        if (in->w < ls->w || in->h < ls->h) {
+            bip_crop_image(img, ls->w, ls->h, (size_t)ls->w * ls->c, (ls->w - in->w) / 2, (ls->h - in->h) / 2, scratch + bytes,
+                           in->w, in->h, (size_t)in->w * in->c, in->c);
+            img = scratch + bytes;
+        }
+        bcnn_convert_img_to_float(img, in->w, in->h, in->c, 1 / 127.5f,
+                                  list_loader && net->data_aug ? net->data_aug->swap_to_bgr : 0, 127.5f, 127.5f, 127.5f,
+                                  in->data + (size_t)i * out);
+    }
     free(scratch);
     return st;
 }
@@ -849,6 +981,7 @@ static bcnn_status list_batch_decoded(bcnn_net *net, bcnn_loader *it, loader_sta
     }
     /* ---- phase 3: the draws, in the reference's order */
     int on_device = 0;
+    const int keep_bytes = effects_on(net) && net->mode == BCNN_MODE_TRAIN && net->data_aug;
     memset(ls->decoded, 0, (size_t)n);
     for (int i = 0; i < count; ++i) {
         int *x_shift = net->data_aug ? &net->data_aug->shift_x : NULL, *y_shift = net->data_aug ? &net->data_aug->shift_y : NULL;
@@ -860,11 +993,17 @@ static bcnn_status list_batch_decoded(bcnn_net *net, bcnn_loader *it, loader_sta
             ls->origins[2 * i] = x_ul;
             ls->origins[2 * i + 1] = y_ul;
             drop_lazy(ls); /* the bytes that rebuild this sample on the host, should the next one fail */
-            ls->lazy = lb.bytes[i];
+            uint8_t *copy = keep_bytes ? (uint8_t *)malloc(lb.lengths[i]) : NULL;
+            if (copy) { /* the batch keeps its own: should the effects be refused, every sample is decoded here (below) */
+                memcpy(copy, lb.bytes[i], lb.lengths[i]);
+                ls->lazy = copy;
+            } else {
+                ls->lazy = lb.bytes[i];
+                lb.bytes[i] = NULL;
+            }
             ls->lazy_len = lb.lengths[i];
             ls->lazy_x = x_ul;
             ls->lazy_y = y_ul;
-            lb.bytes[i] = NULL;
             ls->owed = 0;
             stage_draws(net, ls, i, w, h, 1);
             ++on_device;
@@ -886,6 +1025,24 @@ static bcnn_status list_batch_decoded(bcnn_net *net, bcnn_loader *it, loader_sta
         st = BCNN_INVALID_DATA;
     } else if (staged && on_device == 0) {
         bcnn_hip_augment_jpeg_cancel();
+    } else if (staged && stage_effects(ls->draws, sizeof(aug_draw), count, w, h) < 0) {
+        /* the effects were refused: the batch is made on the host (bcnn_loader_next), so the samples that were to be
+         * decoded on the device are decoded here after all, from the files' bytes, which are still held */
+        bcnn_hip_augment_jpeg_cancel();
+        ls->refused = 1;
+        for (int i = 0; i < count; ++i) {
+            if (!ls->decoded[i]) continue;
+            uint8_t *bytes = lb.bytes[i] ? lb.bytes[i] : ls->lazy; /* the latest one's have moved to `lazy` */
+            const size_t len = lb.bytes[i] ? lb.lengths[i] : ls->lazy_len;
+            int wi = 0, hi = 0, ci = 0;
+            unsigned char *buf = NULL;
+            if (bytes) bip_load_image_from_memory(bytes, (int)len, &buf, &wi, &hi, &ci);
+            if (buf && wi > 0 && hi > 0 && ci == c)
+                crop_to_input(buf, wi, hi, ls->origins[2 * i], ls->origins[2 * i + 1], ls->pixels + (size_t)i * w * h * c, w, h, c);
+            else
+                st = BCNN_INVALID_DATA;
+            free(buf);
+        }
     } else if (staged) {
         if (bcnn_hip_augment_jpeg_run(in->data_gpu, ls->decoded, ls->pixels, ls->records, ls->taps, ls->origins,
                                       net->data_aug ? net->data_aug->swap_to_bgr : 0) != 0) {
@@ -989,7 +1146,7 @@ static void det_draw(bcnn_net *net, det_entry *e) {
     if (e->augmented) {
         aug->apply_fliph = 0;
         if (aug->random_fliph) aug->apply_fliph = ((float)rand() / RAND_MAX > 0.5f);
-        draw_augmentation(aug, &e->draw);
+        draw_augmentation(aug, &e->draw, effects_on(net), in->w, in->h);
     }
 }
 
@@ -1135,7 +1292,9 @@ static bcnn_status detection_batch_device(bcnn_net *net, bcnn_loader *it, int *o
                                                  kept[i].dx, kept[i].dy};
             images[i] = im;
         }
-        if (bcnn_hip_augment_letterbox_batch(in->data_gpu, in->n, in->c, h, w, n, images, records, taps,
+        /* the effects first: a refusal there sends the batch the host way as well */
+        if (stage_effects(&kept[0].draw, sizeof(det_entry), n, w, h) >= 0 &&
+            bcnn_hip_augment_letterbox_batch(in->data_gpu, in->n, in->c, h, w, n, images, records, taps,
                                              net->data_aug ? net->data_aug->swap_to_bgr : 0) == 0) {
             *on_device = 1;
             hc->loader_device_letterboxed = n;
@@ -1202,7 +1361,11 @@ bcnn_status bcnn_set_data_loader(bcnn_net *net, bcnn_loader_type type, const cha
  * tensors itself and only the upload happens. */
 bcnn_status bcnn_loader_next(bcnn_net *net) {
     bcnn_loader *it = net->data_loader;
+    if (it && effects_on(net) && net->mode == BCNN_MODE_TRAIN && net->data_aug && net->data_aug->max_random_spots > BCNN_MAX_SPOTS)
+        BCNN_ERROR(net->log_ctx, BCNN_INVALID_PARAMETER, "bcnn_loader_next: loader_effects draws at most %d spotlights per sample\n",
+                   BCNN_MAX_SPOTS);
     loader_stage *ls = it ? stage_begin(net, it) : NULL; /* non-NULL: the input batch is made on the device */
+    if (ls) ls->refused = 0;
     bcnn_hip_context *hc = (bcnn_hip_context *)net->hip_ctx;
     int launched = 0; /* list_batch_decoded has queued the batch already */
     hc->loader_device_decoded = 0;
@@ -1243,15 +1406,20 @@ bcnn_status bcnn_loader_next(bcnn_net *net) {
         }
     }
     if (ls) ls->active = 0;
+    int host_made = 0; /* the device side refused the effects of a batch gathered for it: made on the host after all */
     if (ls && !launched) { /* one copy of the raw samples and their records, two launches; tensors[0].data is not written */
         bcnn_tensor *in = &net->tensors[0];
         const int list_loader = it->type != BCNN_LOAD_MNIST && it->type != BCNN_LOAD_CIFAR10;
-        if (bcnn_hip_augment_batch(in->data_gpu, in->n, in->c, in->h, in->w, net->batch_size, ls->w, ls->h, ls->pixels,
-                                   ls->records, ls->taps, list_loader && net->data_aug ? net->data_aug->swap_to_bgr : 0) != 0)
+        if (ls->refused || stage_effects(ls->draws, sizeof(aug_draw), net->batch_size, ls->w, ls->h) < 0) {
+            BCNN_CHECK_STATUS(host_batch_from_stage(net, ls, list_loader));
+            host_made = 1;
+        } else if (bcnn_hip_augment_batch(in->data_gpu, in->n, in->c, in->h, in->w, net->batch_size, ls->w, ls->h, ls->pixels,
+                                          ls->records, ls->taps,
+                                          list_loader && net->data_aug ? net->data_aug->swap_to_bgr : 0) != 0)
             BCNN_ERROR(net->log_ctx, BCNN_INVALID_PARAMETER, "bcnn_loader_next: the batch does not fit the device loader path\n");
     }
     for (int i = 0; i < net->num_inputs; ++i) {
-        if ((ls || letterboxed) && net->inputs[i] == 0) continue; /* the host copy is stale in this mode */
+        if (((ls && !host_made) || letterboxed) && net->inputs[i] == 0) continue; /* the host copy is stale in this mode */
         bcnn_tensor *t = &net->tensors[net->inputs[i]];
         if (t->data && t->data_gpu) bcnn_hip_memcpy_h2d(t->data_gpu, t->data, (size_t)bcnn_tensor_size(t) * sizeof(float));
     }

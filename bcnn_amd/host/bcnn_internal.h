@@ -119,6 +119,10 @@ struct bcnn_net;
 bcnn_status bcnn_loader_next(struct bcnn_net *net);
 void bcnn_convert_img_to_float(const uint8_t *src, int w, int h, int c, float norm_coeff, int swap_to_bgr, float mean_r,
                                float mean_g, float mean_b, float *dst);
+/* The reference's function in full: all eight stages, the two effects included whenever max_distortion > 0 or
+ * max_random_spots > 0 (it takes no net, so bcnn_set_loader_effects does not reach it). A max_random_spots above
+ * BCNN_MAX_SPOTS is refused before any draw. */
+#define BCNN_MAX_SPOTS 64 /* spotlights one sample can draw: what a sample's draws hold (bcnn_data.c) */
 bcnn_status bcnn_apply_data_augmentation(unsigned char *img, int width, int height, int depth, bcnn_data_augmenter *param,
                                          unsigned char *buffer);
 bcnn_status bcnn_open_dataset(bcnn_loader *iter, struct bcnn_net *net, const char *train_path, const char *train_path_extra,
@@ -178,6 +182,8 @@ typedef struct bcnn_hip_context {
     int loader_detection_on_device; /* bcnn_set_loader_detection_on_device: a detection-list batch that goes the device way
                                      * is letterboxed and augmented by bcnn_hip_augment_letterbox_batch */
     int loader_device_letterboxed;  /* samples of the latest bcnn_loader_next that were letterboxed on the device */
+    int loader_effects; /* bcnn_set_loader_effects: bcnn_loader_next applies Perlin distortion and random spotlights, on
+                         * the host path and on every device route; off, their draws are made and dropped */
     int detector_training; /* bcnn_set_detector_training: YOLO heads may be built on / switched to TRAIN, with their loss */
     int detect_capacity; /* 1.25 x the most boxes an image of the latest bcnn_yolo_get_detections_batch had: the next call's record capacity
                           * when above the default (0: never called) */

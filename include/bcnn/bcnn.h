@@ -361,6 +361,21 @@ BCNN_API int bcnn_get_loader_detection_on_device(const bcnn_net *net);
 /* Number of samples of the latest bcnn_loader_next that were letterboxed on the device; 0 for a batch made any other
  * way, on a fresh net and for a NULL net. */
 BCNN_API int bcnn_get_loader_device_letterboxed(const bcnn_net *net);
+/* Whether bcnn_loader_next applies the augmenter's last two stages, Perlin distortion (config key `max_distortion`) and
+ * random spotlights (`max_spots`, bcnn_augment_data_with_blobs), to TRAIN-mode samples (default 0: off). Off, a net whose
+ * augmenter has one of the two ranges set draws their parameters from rand() exactly as the reference does (so every other
+ * stage sees the reference's random stream) and leaves the pixels alone; one line on stderr says so. On, both effects
+ * run after the brightness stage on the stored-size sample, as in the reference, and a run seeded like a reference run
+ * sees the reference's samples bit for bit -- on the host path and on the three device routes
+ * (bcnn_set_loader_on_device, bcnn_set_loader_decode_on_device, bcnn_set_loader_detection_on_device), which stay
+ * bit-identical to the host path: the host draws and tabulates every cos and exp, the device does the per-pixel work in
+ * the launch that converts the batch. The switch is independent of those three; the number of rand() calls does not
+ * depend on it; outside TRAIN mode nothing is drawn or applied. At most 64 spotlights per sample: bcnn_loader_next returns
+ * BCNN_INVALID_PARAMETER for a larger `max_spots` while the switch is on. Any non-zero value is stored as 1; may be
+ * called before a loader exists and between batches; a NULL net returns BCNN_INVALID_PARAMETER.
+ * Config files: `loader_effects=1` in the [net] section. */
+BCNN_API bcnn_status bcnn_set_loader_effects(bcnn_net *net, int on);
+BCNN_API int bcnn_get_loader_effects(const bcnn_net *net);
 /* Detections of EVERY image of the batch from the latest forward, in one call. widths[b] / heights[b]: the original
  * size of image b (what bcnn_yolo_get_detections takes as w, h). dets[b] receives a malloc'ed array of num_dets[b]
  * boxes (NULL / 0 when image b has no candidate); per image, the result is what

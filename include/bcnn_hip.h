@@ -757,7 +757,7 @@ typedef struct bcnn_hip_augment_record {
     int32_t gain;       /* CONTRAST */
     int32_t brightness; /* added last; 0 = none */
     int32_t reserved;   /* 0 */
-} bcnn_hip_augment_record;
+} bcnn_hip_augment_record; /* the bits BCNN_HIP_AUG_DISTORT / _SPOTS of `flags` are ignored: see bcnn_hip_augment_effects_begin */
 int bcnn_hip_augment_batch(float *dst_d, int n, int c, int h, int w, int num_samples, int src_w, int src_h,
                            const uint8_t *pixels, const bcnn_hip_augment_record *records, const int32_t *taps,
                            int swap_to_bgr);
@@ -826,6 +826,50 @@ typedef struct bcnn_hip_letterbox_image {
 int bcnn_hip_augment_letterbox_batch(float *dst_d, int n, int c, int h, int w, int num_samples,
                                      const bcnn_hip_letterbox_image *images, const bcnn_hip_augment_record *records,
                                      const int32_t *taps, int swap_to_bgr);
+
+/* ---------------------------------------------------------------------------------------------
+ * The augmenter's last two stages on the device (augment.hip): Perlin distortion and random spotlights, between S6 and the
+ * centre crop of bcnn_hip_augment_batch. bcnn_hip_augment_effects_begin stages them for the calling thread's NEXT batch
+ * call -- bcnn_hip_augment_batch, bcnn_hip_augment_jpeg_run or bcnn_hip_augment_letterbox_batch, whichever comes first --
+ * which consumes them on every return: it puts them into its one staging block (still ONE copy per batch) and launches
+ * augment_convert_effects_kernel in place of the convert kernel. A batch call with nothing staged does what it always
+ * did, launch for launch. The two flag bits below live in effects[b].flags; the same bits of a record are ignored.
+ * With T = S6 (contrast and brightness are pointwise, so T is evaluated at the taps), per pixel (x, y) of sample b:
+ *   DISTORT  n = bip_perlin_noise(cell_x[x], cell_y[y], weight_x[x], weight_y[y], seed); (px, py) = ((norm_x[x] + n *
+ *            distortion) * src_w, (norm_y[y] + n * distortion) * src_h); S7 = bip_distort_blend of T at (ix, iy) ..
+ *            (ix + 1, iy + 1) where bip_distort_map accepts the position, else 0. perlin (HOST) holds per sample
+ *            2 (src_w + src_h) floats -- norm of the columns, norm of the rows, weight of the columns, weight of the rows
+ *            -- and cells (HOST) per sample src_w + src_h int32, columns then rows, all as bip_perlin_axis
+ *            (include/bip/bip.h) tabulates them; read for the samples with DISTORT only, and both may be NULL when no
+ *            sample has it
+ *   SPOTS    for spots[first_spot .. first_spot + num_spots) in order: inside the spot's box {x0, y0, bw, bh},
+ *            S8 = bip_spot_add(spot_tables[table + (y - y0) bw + (x - x0)], S8), outside it the byte stays. The tables
+ *            are bip_spot_table's; the caller chooses the box so that no byte outside it would change.
+ * The arithmetic is bcnn_amd/host/bip_effects.h on both sides: no cos, exp or division on the device, so the bytes are
+ * the host functions' (bip_perlin_distortion_seeded, bip_add_spotlights) bit for bit.
+ * Returns 0, or 1 with nothing staged: a NULL effects; num_samples, src_w or src_h < 1; flags other than the two below;
+ * DISTORT with a NULL perlin / cells or a distortion that is not finite; SPOTS with a range outside
+ * [0, num_spots] or spots / spot_tables NULL; a box that is empty, leaves the sample or whose bw x bh floats end
+ * behind num_table_floats; more than 2 GiB to stage. The batch call returns 1 (nothing queued, the staged data dropped)
+ * when num_samples, src_w (w for the two other routes) or src_h do not equal its own, or when its block with the effects
+ * would pass 2 GiB. bcnn_hip_augment_effects_cancel drops what is staged.
+ * ------------------------------------------------------------------------------------------- */
+#define BCNN_HIP_AUG_DISTORT 32
+#define BCNN_HIP_AUG_SPOTS 64
+typedef struct bcnn_hip_augment_effect {
+    int32_t flags;                 /* BCNN_HIP_AUG_DISTORT | BCNN_HIP_AUG_SPOTS */
+    int32_t seed;                  /* DISTORT */
+    float distortion;
+    int32_t first_spot, num_spots; /* SPOTS */
+} bcnn_hip_augment_effect;
+typedef struct bcnn_hip_augment_spot {
+    int32_t x0, y0, bw, bh; /* the box of its table, inside the sample */
+    uint32_t table;         /* first float of its table in spot_tables */
+} bcnn_hip_augment_spot;
+int bcnn_hip_augment_effects_begin(int num_samples, int src_w, int src_h, const bcnn_hip_augment_effect *effects,
+                                   const float *perlin, const int32_t *cells, const bcnn_hip_augment_spot *spots,
+                                   int num_spots, const float *spot_tables, size_t num_table_floats);
+void bcnn_hip_augment_effects_cancel(void);
 
 /* ---------------------------------------------------------------------------------------------
  * Transposed convolution (deconvolution), implicit GEMMs on fp32 MFMA with no col2im / im2col buffer.

@@ -6,7 +6,8 @@
  * reference's -- stb_image's -- exact pixels, PNG with a full inflate),
  * and the reference's fixed-point bilinear resize (bit-identical, tests/test_bip.py); bip_augment.c holds the operations
  * of the online data augmenter (crop / shift, horizontal flip, rotation, contrast, brightness: bcnn_data.c:211-334),
- * byte for byte like the reference (tests/test_data_loader.py). Perlin distortion and random spotlights are not built. */
+ * byte for byte like the reference (tests/test_data_loader.py); bip_effects.c holds its last two, Perlin distortion and
+ * random spotlights (tests/test_augment_effects.py). */
 #ifndef BIP_H
 #define BIP_H
 #include <stddef.h>
@@ -70,6 +71,37 @@ bip_status bip_contrast_stretch(uint8_t *src, size_t src_stride, size_t width, s
                                 size_t dst_stride, float contrast);
 bip_status bip_image_brightness(uint8_t *src, size_t src_stride, size_t width, size_t height, size_t depth, uint8_t *dst,
                                 size_t dst_stride, int32_t brightness);
+/* ---- the augmenter's two effects (bip_effects.c; per-pixel arithmetic in bcnn_amd/host/bip_effects.h) ---- */
+/* One octave of cosine-interpolated lattice noise, seeded by ONE rand() call made on entry, moves every pixel's source
+ * position by noise * distortion (in units of the image extent) along both axes; four-tap float blend, truncated. A pixel
+ * whose taps leave the image becomes 0: the last row and column always do, and an image of width or height 1 becomes
+ * all 0. Both images are dense width x depth rows (the strides are not used), and may not overlap (bip.c:205-266). */
+bip_status bip_image_perlin_distortion(uint8_t *src, size_t src_stride, size_t width, size_t height, size_t depth,
+                                       uint8_t *dst, size_t dst_stride, float distortion, float kx, float ky);
+/* num_spots Gaussian spots one after the other, each drawn with FOUR rand() calls (centre x, centre y in the image; sigma
+ * x, sigma y in [min + 0.5, max + 0.5]): every byte becomes (uint8)clamp(255 * exp(-(dx^2 / sx^2 + dy^2 / sy^2) / 2) +
+ * byte, 0, 255), truncated per spot. src == dst works in place (bip.c:268-316). */
+bip_status bip_add_random_spotlights(uint8_t *src, size_t src_stride, size_t width, size_t height, size_t depth, uint8_t *dst,
+                                     size_t dst_stride, uint32_t num_spots, float min_spot_width, float max_spot_width,
+                                     float min_spot_height, float max_spot_height);
+/* The same pixels from draws the caller has made (not in the reference): the seed; the spot list. bip_draw_spot makes the
+ * four draws of one spot. */
+typedef struct { int32_t mu_x, mu_y; float sigma_x, sigma_y; } bip_spot;
+bip_status bip_perlin_distortion_seeded(uint8_t *src, size_t src_stride, size_t width, size_t height, size_t depth,
+                                        uint8_t *dst, size_t dst_stride, float distortion, float kx, float ky, int32_t seed);
+bip_status bip_add_spotlights(uint8_t *src, size_t src_stride, size_t width, size_t height, size_t depth, uint8_t *dst,
+                              size_t dst_stride, const bip_spot *spots, uint32_t num_spots);
+void bip_draw_spot(size_t width, size_t height, float min_spot_width, float max_spot_width, float min_spot_height,
+                   float max_spot_height, bip_spot *spot);
+/* What a device needs instead of cos and exp. bip_perlin_axis: for the `extent` columns (rows) of an image and the
+ * offset kx (ky), the normalised coordinate, the cosine weight and the lattice cell of the noise argument, `extent`
+ * values each. bip_spot_table: `val` of one spot over the box of `radius` around its centre clipped to the image,
+ * box = {x0, y0, bw, bh}, row-major bw x bh floats (room for (2 radius + 1)^2); bip_apply_spot_table applies one such
+ * table in place and leaves every pixel outside the box alone. */
+void bip_perlin_axis(size_t extent, float k, float *norm, float *weight, int32_t *cell);
+bip_status bip_spot_table(const bip_spot *spot, size_t width, size_t height, int32_t radius, int32_t box[4], float *val);
+bip_status bip_apply_spot_table(uint8_t *img, size_t stride, size_t width, size_t height, size_t depth, const int32_t box[4],
+                                const float *val);
 #ifdef __cplusplus
 }
 #endif

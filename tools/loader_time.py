@@ -18,6 +18,12 @@ least 80 ms and 3 batches, then times --batches batches. The list loaders are no
 both paths and dominates them.
 
     python tools/loader_time.py [--parent-tree DIR] [--out profiles/loader_device.json]
+
+--effects times the effects switch instead (bcnn_set_loader_effects): two legs of this tree with the
+switch on, the host path (fx_host) and the device path (fx_device), ms per batch on the CIFAR-10 loader (N = 128) and on a
+list of 160 x 160 x 3 PPM files (N = 32).
+
+    python tools/loader_time.py --effects [--out profiles/loader_effects.json]
 """
 import argparse
 import ctypes as C
@@ -143,6 +149,82 @@ def _leg(tree, on, data, batches, train_steps):
     print(json.dumps(out))
 
 
+FX_CONF = """[net]
+batch=%d
+width=%d
+height=%d
+channels=3
+max_distortion=0.3
+max_spots=3
+range_shift_x=4
+range_shift_y=4
+min_contrast=0.8
+max_contrast=1.2
+loader_effects=1
+loader_on_device=%d
+[connected]
+output=10
+src=input
+dst=fc
+[softmax]
+src=fc
+dst=prob
+[cost]
+src=prob
+dst=out
+loss=euclidean
+metric=error
+"""
+
+
+def _effects_leg(tree, device, data, batches):
+    """--effects: bcnn_set_loader_effects on, host path against device path, ms per batch: the
+    CIFAR-10 loader at N = 128 and a classification list of 160 x 160 x 3 PPM files at N = 32 (PPM: reading a file is a
+    copy, so the list leg times the augmentation and not a decoder). The nets come from config files, which is how
+    max_distortion reaches a net."""
+    sys.path.insert(0, tree)
+    import numpy as np
+    import torch
+    from bcnn_amd import capi
+    assert torch.cuda.is_available(), "needs a GPU: a timing without one says nothing"
+    libc = C.CDLL(None)
+    rs = np.random.RandomState(1)
+    lines = []
+    for k in range(64):
+        p = os.path.join(data, "fx%d.ppm" % k)
+        with open(p, "wb") as f:
+            f.write(b"P6\n160 160\n255\n" + rs.randint(0, 256, (160, 160, 3)).astype(np.uint8).tobytes())
+        lines.append("%s %d" % (p, k % 10))
+    lst = os.path.join(data, "fx_list.txt")
+    with open(lst, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    cifar = os.path.join(data, "cifar.bin")
+    out = {}
+    for name, kind, path, side, n in (("cifar10_fx_batch_ms", 1, cifar, 32, 128), ("list160_fx_batch_ms", 2, lst, 160, 32)):
+        cfg = os.path.join(data, "fx_%d_%d.conf" % (side, device))
+        with open(cfg, "w") as f:
+            f.write(FX_CONF % (n, side, side, device))
+        net = capi.Net.load_net(cfg, None, mode=capi.MODE_TRAIN)
+        assert net.get_loader_effects() == 1 and net.get_loader_on_device() == device
+        net.L.bcnn_set_data_loader.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]
+        net.L.bcnn_loader_next.argtypes = [C.c_void_p]
+        assert net.L.bcnn_set_data_loader(net.net, kind, path.encode(), None, path.encode(), None) == 0
+        net.compile()
+        libc.srand(1)
+        t0, warm = time.perf_counter(), 0
+        while warm < 3 or time.perf_counter() - t0 < MIN_WARM_S:
+            assert net.L.bcnn_loader_next(net.net) == 0
+            net.sync()
+            warm += 1
+        t0 = time.perf_counter()
+        for _ in range(batches):
+            assert net.L.bcnn_loader_next(net.net) == 0
+            net.sync()
+        out[name] = (time.perf_counter() - t0) / batches * 1e3
+        net.close()
+    print(json.dumps(out))
+
+
 def _child(args_list):
     r = subprocess.run([sys.executable, os.path.abspath(__file__)] + args_list, capture_output=True, text=True, cwd=ROOT)
     if r.returncode != 0:
@@ -161,23 +243,31 @@ def main():
     ap.add_argument("--leg", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--tree", default=ROOT, help=argparse.SUPPRESS)
     ap.add_argument("--data", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--effects", action="store_true",
+                    help="time bcnn_set_loader_effects instead: host path (fx_host) against device path (fx_device)")
     args = ap.parse_args()
+    if args.leg in ("fx_host", "fx_device"):
+        return _effects_leg(args.tree, 1 if args.leg == "fx_device" else 0, args.data, args.batches)
     if args.leg:
         return _leg(args.tree, args.leg == "on", args.data, args.batches, args.train_steps)
 
     legs = [("off", ROOT), ("on", ROOT)]
     if args.parent_tree:
         legs.insert(0, ("parent", os.path.abspath(args.parent_tree)))
+    keys = ("cifar10_batch_ms", "mnist_batch_ms", "train_img_s")
+    if args.effects:
+        legs, keys = [("fx_host", ROOT), ("fx_device", ROOT)], ("cifar10_fx_batch_ms", "list160_fx_batch_ms")
     runs = {name: [] for name, _ in legs}
     with tempfile.TemporaryDirectory() as data:
         write_datasets(data, args.samples)
         for _ in range(args.repeats):          # alternating: whatever else the machine does hits every leg alike
             for name, tree in legs:
-                runs[name].append(_child(["--leg", "on" if name == "on" else "off", "--tree", tree, "--data", data,
+                leg = name if args.effects else ("on" if name == "on" else "off")
+                runs[name].append(_child(["--leg", leg, "--tree", tree, "--data", data,
                                           "--batches", str(args.batches), "--train-steps", str(args.train_steps)]))
     result = dict(samples=args.samples, batches=args.batches, train_steps=args.train_steps, raw=runs, summary={})
     print("%-18s %-8s %12s %12s   runs" % ("measurement", "leg", "median", "spread"))
-    for key in ("cifar10_batch_ms", "mnist_batch_ms", "train_img_s"):
+    for key in keys:
         result["summary"][key] = {}
         for name, _ in legs:
             v = sorted(r[key] for r in runs[name])
