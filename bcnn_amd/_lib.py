@@ -68,6 +68,9 @@ SIGNATURES = {
     "bcnn_hip_maxpool_backward": (None, [vp, vp, vp] + [i] * 9),
     "bcnn_hip_avgpool_forward": (None, [vp, vp, i, i, i, i]),
     "bcnn_hip_avgpool_backward": (None, [vp, vp, i, i, i, i]),
+    "bcnn_hip_pool2d_out_extent": (i, [vp, i]),
+    "bcnn_hip_pool2d_forward": (None, [vp, vp, vp, vp, i, i, i, i]),
+    "bcnn_hip_pool2d_backward": (None, [vp, vp, vp, vp, i, i, i, i, i]),
     "bcnn_hip_depthwise_forward": (None, [vp, vp, vp, vp] + [i] * 8),
     "bcnn_hip_depthwise_backward": (None, [vp] * 7 + [i] * 9),
     "bcnn_hip_depthwise_stats_size": (sz, [i] * 7),

@@ -20,6 +20,7 @@ FILLER_FIXED, FILLER_XAVIER, FILLER_MSRA = 0, 1, 2
 LOSS_EUCLIDEAN, LOSS_LIFTED_STRUCT = 0, 1
 LOG_SILENT = 3
 IMAGE_FIT_STRETCH, IMAGE_FIT_LETTERBOX = 0, 1
+POOL2D_MAX, POOL2D_AVG = 0, 1
 
 
 class Tensor(C.Structure):
@@ -110,6 +111,7 @@ def lib():
         "bcnn_get_lifted_struct_loss": (i, [vp, C.POINTER(f), C.POINTER(i)]),
         "bcnn_add_batchnorm_layer": (i, [vp, cp, cp]), "bcnn_add_maxpool_layer": (i, [vp, i, i, i, cp, cp]),
         "bcnn_add_avgpool_layer": (i, [vp, cp, cp]), "bcnn_add_activation_layer": (i, [vp, i, cp]),
+        "bcnn_add_pool2d_layer": (i, [vp, i, i, i, i, i, i, cp, cp]),
         "bcnn_add_eltwise_layer": (i, [vp, i, cp, cp, cp]), "bcnn_add_fullc_layer": (i, [vp, i, i, i, i, cp, cp]),
         "bcnn_add_softmax_layer": (i, [vp, cp, cp]), "bcnn_add_cost_layer": (i, [vp, i, i, f, cp, cp, cp]),
         "bcnn_upload_tensor": (i, [vp, i, i]), "bcnn_download_tensor": (i, [vp, i, i]),
@@ -205,6 +207,13 @@ class Net:
 
     def avgpool(self, src, dst):
         return self._added(self.L.bcnn_add_avgpool_layer(self.net, src.encode(), dst.encode()))
+
+    def pool2d(self, kind, size, stride, pad=0, ceil_mode=False, count_include_pad=True, src="input", dst="pool"):
+        """bcnn_add_pool2d_layer: POOL2D_MAX / POOL2D_AVG (or "max" / "avg") over a size x size window, `stride` apart,
+        `pad` on all four sides -- the rules of torch's max_pool2d / avg_pool2d"""
+        kind = {"max": POOL2D_MAX, "avg": POOL2D_AVG}.get(kind, kind)
+        return self._added(self.L.bcnn_add_pool2d_layer(self.net, kind, size, stride, pad, 1 if ceil_mode else 0,
+                                                         1 if count_include_pad else 0, src.encode(), dst.encode()))
 
     def activation(self, act, src):
         return self._added(self.L.bcnn_add_activation_layer(self.net, act, src.encode()))

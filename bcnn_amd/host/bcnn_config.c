@@ -191,6 +191,9 @@ typedef struct {
     int boxes_per_cell, num_anchors, num_classes, num_coords, num_anchor_vals; /* [yolo] */
     int *anchors_mask;
     float *anchors;
+    /* [pool] / [local_avgpool]: which of size / stride the section set (their defaults differ from the other sections'),
+     * `pad` as written (a count per side in both dialects), and the three keys only these sections read */
+    int has_size, has_stride, pool_pad, pool_avg, ceil_mode, count_include_pad;
 } layer_param;
 
 static void lp_reset(layer_param *lp) {
@@ -203,6 +206,7 @@ static void lp_reset(layer_param *lp) {
     lp->padding_type = BCNN_PADDING_SAME; lp->a = BCNN_ACT_NONE; lp->init = BCNN_FILLER_XAVIER;
     lp->cost = BCNN_METRIC_SSE; lp->loss = BCNN_LOSS_EUCLIDEAN;
     lp->k = 1.0f; /* [lrn] without a k key: the Caffe / torch default */
+    lp->count_include_pad = 1; /* [pool] type=avg: the Caffe / torch default */
 }
 
 static void lp_set_srcs(layer_param *lp, const char *list) {
@@ -249,11 +253,18 @@ static void lp_set(bcnn_net *net, int section_idx, layer_param *lp, const char *
     if (!strcmp(name, "dropout_rate") || !strcmp(name, "rate") || !strcmp(name, "probability")) /* Darknet: probability */
         lp->rate = (float)atof(val);
     else if (!strcmp(name, "filters")) lp->n_filts = atoi(val);
-    else if (!strcmp(name, "size")) lp->size = atoi(val);
-    else if (!strcmp(name, "stride")) lp->stride = atoi(val);
+    else if (!strcmp(name, "size")) { lp->size = atoi(val); lp->has_size = 1; }
+    else if (!strcmp(name, "stride")) { lp->stride = atoi(val); lp->has_stride = 1; }
+    else if (!strcmp(name, "type")) { /* [pool] */
+        if (!strcmp(val, "avg") || !strcmp(val, "average")) lp->pool_avg = 1;
+        else if (!strcmp(val, "max")) lp->pool_avg = 0;
+        else bcnn_log(net->log_ctx, BCNN_LOG_WARNING, "Unknown pooling type %s, going with max\n", val);
+    } else if (!strcmp(name, "ceil_mode")) lp->ceil_mode = atoi(val);
+    else if (!strcmp(name, "count_include_pad")) lp->count_include_pad = atoi(val);
     else if (!strcmp(name, "padding")) {
         if (format == 1) { lp->pad = atoi(val); lp->padding_type = lp->pad ? BCNN_PADDING_SAME : BCNN_PADDING_VALID; }
     } else if (!strcmp(name, "pad")) {
+        lp->pool_pad = atoi(val);
         if (format == 0) lp->pad = atoi(val);
         else lp->pad = atoi(val) ? lp->size / 2 : 0; /* Darknet: boolean, needs `size` to come first */
     } else if (!strcmp(name, "num_groups") || !strcmp(name, "groups")) lp->num_groups = atoi(val);
@@ -372,6 +383,14 @@ static bcnn_status add_layer(bcnn_net *net, const char *name, layer_param *lp) {
     if (is_any(name, "[max]", "[maxpool]", NULL, NULL))
         return bcnn_add_maxpool_layer(net, lp->size, lp->stride, lp->padding_type, src, dst);
     if (!strcmp(name, "[avgpool]")) return bcnn_add_avgpool_layer(net, src, dst);
+    if (is_any(name, "[pool]", "[pool2d]", "[local_avgpool]", NULL)) {
+        /* the windowed, centred pools ([maxpool] pads at the bottom / right only and [avgpool] is global, in both dialects).
+         * Defaults: max, size 2, stride = size, pad 0, floor mode, padding counted; [local_avgpool] is type=avg */
+        const int size = lp->has_size ? lp->size : 2, stride = lp->has_stride ? lp->stride : size;
+        const int avg = lp->pool_avg || !strcmp(name, "[local_avgpool]");
+        return bcnn_add_pool2d_layer(net, avg ? BCNN_POOL2D_AVG : BCNN_POOL2D_MAX, size, stride, lp->pool_pad, lp->ceil_mode,
+                                     lp->count_include_pad, src, dst);
+    }
     if (!strcmp(name, "[upsample]")) return bcnn_add_upsample_layer(net, lp->stride, src, dst);
     if (!strcmp(name, "[dropout]")) return bcnn_add_dropout_layer(net, lp->rate, src);
     if (is_any(name, "[concat]", "[route]", NULL, NULL))

@@ -402,9 +402,10 @@ static void mark_dead_grad_fills(bcnn_net *net) {
          * `0 + sum` instead of accumulating: mark 2, the node's backward asks bcnn_grad_sole_writer(). Holds for
          * the forward -> backward order every caller of the reference uses (bcnn_train_on_batch). */
         if (uses == 1 && (nd->type == BCNN_LAYER_MAXPOOL || nd->type == BCNN_LAYER_DEPTHWISE_CONV2D ||
-                          nd->type == BCNN_LAYER_LRN)) {
+                          nd->type == BCNN_LAYER_LRN || nd->type == BCNN_LAYER_POOL2D)) {
             /* max-pooling's gather, the depthwise data gradient (a gather too: one thread owns a dx element,
-             * bcnn_depthwise_conv_layer.c:432-547 accumulates onto the zero fill) and LRN's (one lane per column) */
+             * bcnn_depthwise_conv_layer.c:432-547 accumulates onto the zero fill), LRN's (one lane per column) and the
+             * pool2d gather, whose overwrite form also writes the elements no window covers */
             hc->grad_fill_dead[t] = 2;
             continue;
         }
@@ -554,6 +555,12 @@ bcnn_status bcnn_resize_net(bcnn_net *net, int w, int h, int c, int need_realloc
         } else if (nd->type == BCNN_LAYER_MAXPOOL) {
             const bcnn_maxpool_param *p = (const bcnn_maxpool_param *)nd->param;
             bcnn_tensor_set_shape(d, s->n, s->c, (s->h - 1) / p->stride + 1, (s->w - 1) / p->stride + 1, 1);
+        } else if (nd->type == BCNN_LAYER_POOL2D) {
+            int oh = 0, ow = 0;
+            BCNN_CHECK_AND_LOG(net->log_ctx, bcnn_pool2d_out_extents((const bcnn_pool2d_param *)nd->param, s->h, s->w, &oh, &ow),
+                               BCNN_INVALID_PARAMETER,
+                               "bcnn_resize_net: node %d pools a %d x %d tensor, smaller than its padded window\n", i, s->w, s->h);
+            bcnn_tensor_set_shape(d, s->n, s->c, oh, ow, 1);
         } else {
             bcnn_tensor_set_shape(d, s->n, s->c, s->h, s->w, 1);
         }
@@ -567,6 +574,10 @@ bcnn_status bcnn_resize_net(bcnn_net *net, int w, int h, int c, int need_realloc
             bcnn_batchnorm_param *p = (bcnn_batchnorm_param *)nd->param;
             BCNN_CHECK_STATUS(resize_private_f32(&p->workspace_gpu, old_elems, new_elems, need_realloc));
             BCNN_CHECK_STATUS(resize_private_f32(&p->x_norm_gpu, old_elems, new_elems, need_realloc));
+        } else if (nd->type == BCNN_LAYER_POOL2D) {
+            /* by capacity: after a shrink, growing back to a size the buffer already holds allocates nothing, and growing
+             * past it is never missed because the shape before happened to be larger than the buffer */
+            BCNN_CHECK_STATUS(bcnn_pool2d_reserve_indexes((bcnn_pool2d_param *)nd->param, new_elems, need_realloc));
         } else if (nd->type == BCNN_LAYER_MAXPOOL && new_elems > old_elems) {
             bcnn_maxpool_param *p = (bcnn_maxpool_param *)nd->param;
             if (!need_realloc) return BCNN_INVALID_PARAMETER;
@@ -1060,6 +1071,7 @@ void *bcnn_get_node_state(bcnn_net *net, int node, int which) {
     const bcnn_node *nd = &net->nodes[node];
     const bcnn_tensor *sm = NULL, *sv = NULL;
     if (nd->type == BCNN_LAYER_MAXPOOL) return which == 0 ? (void *)((bcnn_maxpool_param *)nd->param)->indexes_gpu : NULL;
+    if (nd->type == BCNN_LAYER_POOL2D) return which == 0 ? (void *)((bcnn_pool2d_param *)nd->param)->indexes_gpu : NULL;
     if (nd->type == BCNN_LAYER_CONV2D && ((bcnn_conv_param *)nd->param)->batch_norm) {
         sm = &((bcnn_conv_param *)nd->param)->saved_mean;
         sv = &((bcnn_conv_param *)nd->param)->saved_variance;

@@ -425,6 +425,17 @@ typedef struct bcnn_lrn_param {
     float k;
 } bcnn_lrn_param;
 
+/* windowed pooling with symmetric padding (bcnn_add_pool2d_layer; no reference counterpart). A param block of its own:
+ * nothing that keys on BCNN_LAYER_MAXPOOL / _AVGPOOL (the conv / batch-norm fusion links) ever sees this node */
+typedef struct bcnn_pool2d_param {
+    bcnn_pool2d_kind kind;
+    int size, stride, pad, ceil_mode, count_include_pad;
+#ifdef BCNN_USE_HIP
+    int *indexes_gpu;        /* max, nets built in TRAIN / VALID mode: the winner of every window (the output's shape) */
+    size_t indexes_capacity; /* elements allocated; bcnn_resize_net grows the buffer past this, not past the last shape */
+#endif
+} bcnn_pool2d_param;
+
 /* in-place dropout (reference src/layers/bcnn_dropout_layer.h); the mask is regenerated from (key, step) of the last
  * TRAIN forward instead of being stored (include/bcnn_hip.h) */
 typedef struct bcnn_dropout_param {
@@ -507,6 +518,13 @@ void bcnn_forward_dropout_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_dropout_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_dropout_layer(bcnn_node *node);
 uint64_t bcnn_dropout_key(uint64_t seed, int node, int rank);
+void bcnn_forward_pool2d_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_backward_pool2d_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_release_param_pool2d_layer(bcnn_node *node);
+/* bcnn_layers_pool2d.c: the node's output extents for an h x w source; 0 if the parameters refuse that source */
+int bcnn_pool2d_out_extents(const bcnn_pool2d_param *p, int h, int w, int *out_h, int *out_w);
+/* bcnn_resize_net: makes the index buffer hold `elems` winners (no-op for average pooling and PREDICT-built nets) */
+bcnn_status bcnn_pool2d_reserve_indexes(bcnn_pool2d_param *p, size_t elems, int need_realloc);
 
 /* SGD step on one node's parameters (bcnn_learner.c:67-104 in the reference) */
 void bcnn_link_depthwise_batchnorm(bcnn_net *net); /* bcnn_layers_hot.c; called by bcnn_compile_net */

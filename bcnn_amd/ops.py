@@ -197,6 +197,48 @@ def avgpool_backward(dy, dx):
     _lib.load().bcnn_hip_avgpool_backward(_f32(dy), _f32(dx), n, c, h, w)
 
 
+POOL2D_MAX, POOL2D_AVG = 0, 1
+
+
+class Pool2dDesc(_C.Structure):
+    """struct bcnn_hip_pool2d_desc (include/bcnn_hip.h)"""
+    _fields_ = [("kind", _C.c_int), ("size", _C.c_int), ("stride", _C.c_int), ("pad", _C.c_int),
+                ("ceil_mode", _C.c_int), ("count_include_pad", _C.c_int)]
+
+
+def _pool2d_desc(kind, size, stride, pad, ceil_mode, count_include_pad):
+    kind = {"max": POOL2D_MAX, "avg": POOL2D_AVG}.get(kind, kind)
+    return Pool2dDesc(kind, size, stride, pad, 1 if ceil_mode else 0, 1 if count_include_pad else 0)
+
+
+def pool2d_out_hw(kind, h, w, size, stride, pad=0, ceil_mode=False):
+    """bcnn_hip_pool2d_out_extent per axis (torch's max_pool2d / avg_pool2d shape rule); (0, 0) axes are refused
+    parameter sets. Needs the library, not a device."""
+    d = _pool2d_desc(kind, size, stride, pad, ceil_mode, True)
+    L = _lib.load()
+    return int(L.bcnn_hip_pool2d_out_extent(_C.byref(d), h)), int(L.bcnn_hip_pool2d_out_extent(_C.byref(d), w))
+
+
+def pool2d_forward(x, y, indexes, kind, size, stride, pad=0, ceil_mode=False, count_include_pad=True):
+    """bcnn_hip_pool2d_forward: windowed max / average pooling with `pad` on all four sides. indexes (int32, y's shape)
+    may be None: max pooling then stores no winners; average pooling never does."""
+    n, c, h, w = x.shape
+    d = _pool2d_desc(kind, size, stride, pad, ceil_mode, count_include_pad)
+    assert tuple(y.shape) == (n, c) + pool2d_out_hw(kind, h, w, size, stride, pad, ceil_mode), "y has the pooled shape"
+    assert indexes is None or (indexes.dtype == torch.int32 and indexes.numel() == y.numel())
+    _lib.load().bcnn_hip_pool2d_forward(_C.byref(d), _f32(x), _f32(y), _p(indexes), n, c, h, w)
+
+
+def pool2d_backward(dy, indexes, dx, kind, size, stride, pad=0, ceil_mode=False, count_include_pad=True, overwrite=False):
+    """bcnn_hip_pool2d_backward: dx += (overwrite: dx = 0 +) the gathered gradient; indexes as the forward stored them
+    (max), ignored for average pooling."""
+    n, c, h, w = dx.shape
+    d = _pool2d_desc(kind, size, stride, pad, ceil_mode, count_include_pad)
+    assert tuple(dy.shape) == (n, c) + pool2d_out_hw(kind, h, w, size, stride, pad, ceil_mode), "dy has the pooled shape"
+    assert indexes is None or (indexes.dtype == torch.int32 and indexes.numel() == dy.numel())
+    _lib.load().bcnn_hip_pool2d_backward(_C.byref(d), _f32(dy), _p(indexes), _f32(dx), n, c, h, w, 1 if overwrite else 0)
+
+
 def activation_forward(x, act, slopes=None, spatial=1, channels=1):
     """bcnn_forward_activation_cpu (bcnn_activation_layer.c:90-146), in place"""
     _lib.load().bcnn_hip_activation_forward(_f32(x), x.numel(), act, _f32(slopes), spatial, channels)

@@ -55,7 +55,8 @@ typedef enum {
     BCNN_LAYER_CONV2D, BCNN_LAYER_TRANSPOSE_CONV2D, BCNN_LAYER_DEPTHWISE_CONV2D, BCNN_LAYER_ACTIVATION,
     BCNN_LAYER_FULL_CONNECTED, BCNN_LAYER_MAXPOOL, BCNN_LAYER_AVGPOOL, BCNN_LAYER_SOFTMAX, BCNN_LAYER_DROPOUT,
     BCNN_LAYER_BATCHNORM, BCNN_LAYER_LRN, BCNN_LAYER_CONCAT, BCNN_LAYER_ELTWISE, BCNN_LAYER_UPSAMPLE,
-    BCNN_LAYER_YOLOV3, BCNN_LAYER_RESHAPE, BCNN_LAYER_COST
+    BCNN_LAYER_YOLOV3, BCNN_LAYER_RESHAPE, BCNN_LAYER_COST,
+    BCNN_LAYER_POOL2D /* windowed pooling with padding (bcnn_add_pool2d_layer); appended: the values above are the reference's */
 } bcnn_layer_type;
 
 typedef enum {
@@ -224,6 +225,20 @@ BCNN_API bcnn_status bcnn_add_softmax_layer(bcnn_net *net, const char *src_id, c
 BCNN_API bcnn_status bcnn_add_maxpool_layer(bcnn_net *net, int size, int stride, bcnn_padding padding,
                                             const char *src_id, const char *dst_id);
 BCNN_API bcnn_status bcnn_add_avgpool_layer(bcnn_net *net, const char *src_id, const char *dst_id);
+/* New, without a reference counterpart: max or average pooling over a square window of `size`, `stride` apart, with `pad`
+ * on all four sides -- the rules of torch.nn.functional.max_pool2d / avg_pool2d, which are Caffe's. The two builders above
+ * keep their meaning (max pooling padded at the bottom / right only, average pooling over the whole plane).
+ *   out = floor_or_ceil((in + 2 pad - size) / stride) + 1 per axis; with ceil_mode, one less if the last window would start
+ *   past the input and its leading padding. Window (i, j) covers rows i stride - pad .. + size - 1, clipped to the input.
+ *   BCNN_POOL2D_MAX: the first maximum in row-major order wins, padding never does. BCNN_POOL2D_AVG: the sum of the real
+ *   elements over the window's extent clipped to input + padding (count_include_pad != 0), or over the number of real
+ *   elements (count_include_pad == 0); count_include_pad is ignored for max pooling.
+ * Refused with BCNN_INVALID_PARAMETER and a log line, nothing added to the net: an unknown kind, size < 1, stride < 1,
+ * pad < 0, pad > size / 2, in + 2 pad < size on either axis, an output extent <= 0. Works in TRAIN, VALID and PREDICT
+ * mode, has no weights (model files skip it) and follows bcnn_resize_net. */
+typedef enum { BCNN_POOL2D_MAX = 0, BCNN_POOL2D_AVG = 1 } bcnn_pool2d_kind;
+BCNN_API bcnn_status bcnn_add_pool2d_layer(bcnn_net *net, bcnn_pool2d_kind kind, int size, int stride, int pad,
+                                           int ceil_mode, int count_include_pad, const char *src_id, const char *dst_id);
 BCNN_API bcnn_status bcnn_add_concat_layer(bcnn_net *net, int num_src, char *const *src_ids, const char *dst_id);
 BCNN_API bcnn_status bcnn_add_eltwise_layer(bcnn_net *net, bcnn_activation activation, const char *src_id1,
                                             const char *src_id2, const char *dst_id);

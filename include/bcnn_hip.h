@@ -363,6 +363,39 @@ void bcnn_hip_avgpool_forward(const float *x_d, float *y_d, int n, int c, int h,
 void bcnn_hip_avgpool_backward(const float *dy_d, float *dx_d, int n, int c, int h, int w);
 
 /* ---------------------------------------------------------------------------------------------
+ * Windowed pooling with symmetric padding (the pool2d node; pool2d.hip). No reference counterpart: the semantics are
+ * those of torch.nn.functional.max_pool2d / avg_pool2d, which are Caffe's. The two nodes above are untouched by it.
+ *   A square window of `size`, `stride` apart, with `pad` (0 <= pad <= size / 2) on all four sides. Output extent per
+ *   axis: out = floor_or_ceil((in + 2 pad - size) / stride) + 1 and, in ceil mode, out - 1 if (out - 1) stride >= in + pad
+ *   (the last window starts inside the input or its leading padding). bcnn_hip_pool2d_out_extent returns it, or 0 for a
+ *   parameter set that is refused: kind unknown, size < 1, stride < 1, pad < 0, pad > size / 2, in < 1, in + 2 pad < size.
+ *   Window (i, j) covers rows i stride - pad .. + size - 1 and the same columns, clipped to the input.
+ *   max: rows outer / columns inner, replace only on `>` (first maximum wins, a NaN never wins, padding never wins);
+ *     indexes_d = int32 flat offset into the whole source tensor, the format of bcnn_hip_maxpool_forward; it may be NULL
+ *     (PREDICT: nothing is stored). average: sum of the real elements / divisor (a true division), divisor =
+ *     (min(hstart + size, h + pad) - hstart) (min(wstart + size, w + pad) - wstart) with count_include_pad, else the
+ *     number of real elements; indexes_d is ignored.
+ *   backward: gather form, one thread per source element (or four), the covering windows in ascending output order, no
+ *     atomics: dx += dy[o] where indexes_d[o] selects the element (max), dx += dy[o] / divisor(o) (average).
+ *     overwrite != 0: the caller guarantees dx is semantically all-zero (this node is the gradient's only writer and the
+ *     zero fill was skipped): dx = 0 + the same sums, and an element no window covers (stride > size) becomes 0; with
+ *     overwrite == 0 such an element keeps its value.
+ *   Tensors of 2^31 elements or more do not fit the index format; the two workers exit on them as on refused parameters.
+ * ------------------------------------------------------------------------------------------- */
+enum { BCNN_HIP_POOL2D_MAX = 0, BCNN_HIP_POOL2D_AVG = 1 };
+typedef struct bcnn_hip_pool2d_desc {
+    int kind;              /* BCNN_HIP_POOL2D_MAX / _AVG */
+    int size, stride, pad;
+    int ceil_mode;         /* 0: floor */
+    int count_include_pad; /* average only */
+} bcnn_hip_pool2d_desc;
+int bcnn_hip_pool2d_out_extent(const bcnn_hip_pool2d_desc *desc, int in);
+void bcnn_hip_pool2d_forward(const bcnn_hip_pool2d_desc *desc, const float *x_d, float *y_d, int *indexes_d, int n, int c,
+                             int h, int w);
+void bcnn_hip_pool2d_backward(const bcnn_hip_pool2d_desc *desc, const float *dy_d, const int *indexes_d, float *dx_d, int n,
+                              int c, int h, int w, int overwrite);
+
+/* ---------------------------------------------------------------------------------------------
  * Depthwise convolution.  Replaces the kernels of bcnn_depthwise_conv_layer.cu:33-200; CPU semantics
  * bcnn_depthwise_conv_layer.c:165-293, 295-547: weights [c][k][k]; y = act(dwconv + bias);
  * backward: dy *= act'(y) in place, dbias += ..., and ONLY IF dx_d != NULL: dw += ..., dx += ...
