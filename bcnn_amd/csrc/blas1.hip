@@ -66,6 +66,15 @@ struct SumF {
         acc[0] += (v.x + v.y) + (v.z + v.w);
     }
 };
+// the same sums in the same order for a tensor that does not start on a 16-byte boundary: four 4-byte loads
+struct SumUnalignedF {
+    static constexpr int kInFlight = 4;
+    const float* g;
+    __device__ void operator()(long long off, int, float (&acc)[1]) const { acc[0] += g[off]; }
+    __device__ void vec4(long long off, int, float (&acc)[1]) const {
+        acc[0] += (g[off] + g[off + 1]) + (g[off + 2] + g[off + 3]);
+    }
+};
 // g = dy * act'(y) written back over dy, and summed: the activation backward and the bias gradient of a layer in
 // one sweep (the depthwise node runs them back to back, bcnn_depthwise_conv_layer.c:311-317)
 struct ActBwdSumF {
@@ -212,7 +221,8 @@ void bcnn_hip_grad_bias(float* dbias, const float* g, int n, int c, int hw) {
     if (!M || !c) return;
     const int splits = chan_splits(c, M);
     float* part = scratch(SCRATCH_REDUCE, (size_t)c * splits);
-    launch_chan_reduce<1>(SumF{g}, c, hw, M, splits, part);
+    if ((reinterpret_cast<uintptr_t>(g) & 15) == 0) launch_chan_reduce<1>(SumF{g}, c, hw, M, splits, part);
+    else launch_chan_reduce<1>(SumUnalignedF{g}, c, hw, M, splits, part);
     chan_accumulate_kernel<<<ceil_div(c, 256), 256, 0, current_stream()>>>(part, c, splits, dbias);
     KERNEL_CHECK();
 }

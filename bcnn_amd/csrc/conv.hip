@@ -159,6 +159,8 @@ static const void* prepack_table(PrepackStore& st, int kind, int mode, const voi
 // pointers or buffers can still refuse it, whose `usable` agrees; the last row of each takes every shape. A new family is a
 // row here and its declarations in conv_paths.h. (The opt-in bf16 forward, bcnn_hip_conv_forward_bf16, is one family for
 // every shape: conv_forward_bf16. A folded batch-norm in front goes straight to the dma kernels: conv_forward_impl.)
+// kDwFamilies in the dispatch trace, row by row: conv_dw_rows_kernel, conv_dw_stem_kernel, conv_dw_direct_kernel<1|2>, wino43_dw_kernel,
+// wino_dw_fused_kernel, wino_unfused:dw, conv_dw_dma_kernel, conv_small_c:dw, conv_large_dw_kernel, conv_dw_kernel<TM,TN>.
 // A/B switches of the experiment build that take a family out: BCNN_HIP_NO_WINDOW, BCNN_HIP_NO_DMA, BCNN_HIP_NO_SMALLC_DX
 enum ConvGate { GATE_NONE, GATE_WINDOW, GATE_DMA, GATE_SMALLC_DX, GATE_COUNT };
 static bool gate_open(ConvGate g) {

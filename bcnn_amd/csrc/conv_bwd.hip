@@ -233,18 +233,31 @@ bool conv_backward_weights(const float* x, const float* dy, float* dw, float* db
     a.mtiles = p.mtiles; a.ntiles = p.ntiles; a.qsplits = p.qsplits; a.q_per_split = p.q_per_split;
     a.bias_col = p.bias_col;
     dim3 grid((unsigned)(p.mtiles * p.ntiles), (unsigned)p.qsplits, (unsigned)s.groups);
-    if (p.TM == 1 && p.TN == 1) conv_dw_kernel<1, 1><<<grid, 256, 0, current_stream()>>>(a);
-    else if (p.TM == 1 && p.TN == 2) conv_dw_kernel<1, 2><<<grid, 256, 0, current_stream()>>>(a);
-    else if (p.TM == 2 && p.TN == 1) conv_dw_kernel<2, 1><<<grid, 256, 0, current_stream()>>>(a);
-    else conv_dw_kernel<2, 2><<<grid, 256, 0, current_stream()>>>(a);
+    if (p.TM == 1 && p.TN == 1) {
+        trace_kernel("conv_dw_kernel<1,1>");
+        conv_dw_kernel<1, 1><<<grid, 256, 0, current_stream()>>>(a);
+    } else if (p.TM == 1 && p.TN == 2) {
+        trace_kernel("conv_dw_kernel<1,2>");
+        conv_dw_kernel<1, 2><<<grid, 256, 0, current_stream()>>>(a);
+    } else if (p.TM == 2 && p.TN == 1) {
+        trace_kernel("conv_dw_kernel<2,1>");
+        conv_dw_kernel<2, 1><<<grid, 256, 0, current_stream()>>>(a);
+    } else {
+        trace_kernel("conv_dw_kernel<2,2>");
+        conv_dw_kernel<2, 2><<<grid, 256, 0, current_stream()>>>(a);
+    }
     KERNEL_CHECK();
+    if (p.bias_col) trace_kernel("conv_dw_kernel:biascol");
     const long long total = (long long)s.groups * s.Mg * (s.K + p.bias_col);
-    if (p.qsplits * 4 >= 256)
+    if (p.qsplits * 4 >= 256) {
+        trace_kernel("conv_dw_finalize:4");
         conv_dw_finalize_kernel<4><<<(unsigned)((total + 3) / 4), 256, 0, current_stream()>>>(
             workspace, p.qsplits * 4, s.groups, s.Mg, s.K, p.mtiles * p.TM * 32, p.ntiles * p.TN * 32, p.bias_col, dw, dbias);
-    else
+    } else {
+        trace_kernel("conv_dw_finalize:16");
         conv_dw_finalize_kernel<16><<<(unsigned)((total + 15) / 16), 256, 0, current_stream()>>>(
             workspace, p.qsplits * 4, s.groups, s.Mg, s.K, p.mtiles * p.TM * 32, p.ntiles * p.TN * 32, p.bias_col, dw, dbias);
+    }
     KERNEL_CHECK();
     *bias_done = p.bias_col != 0;
     return true;

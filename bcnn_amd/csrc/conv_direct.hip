@@ -558,6 +558,7 @@ bool conv_backward_weights_direct(const float* x, const float* dy, float* dw, fl
     a.x = x; a.dy = dy; a.partials = workspace; a.s = s; a.nwin = nwin; a.win_per_block = wpb;
     a.bias_col = dbias ? 1 : 0;
     dim3 grid((unsigned)blocks, (unsigned)s.groups);
+    trace_kernel(tm == 1 ? "conv_dw_direct_kernel<1>" : "conv_dw_direct_kernel<2>");
     if (tm == 1) conv_dw_direct_kernel<1><<<grid, 256, 0, current_stream()>>>(a);
     else conv_dw_direct_kernel<2><<<grid, 256, 0, current_stream()>>>(a);
     KERNEL_CHECK();

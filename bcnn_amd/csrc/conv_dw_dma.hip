@@ -391,15 +391,19 @@ bool conv_backward_weights_dma(const float* x, const float* dy, float* dw, const
     const size_t total = (size_t)s.groups * s.Mg * s.Cg * p.kk2;
     static const bool x4_on = BCNN_EXP_ENV("BCNN_HIP_NO_DW_FINALIZE_X4") == nullptr;  // A/B switch (experiment build only)
     if (x4_on && p.kk2 == 1 && p.qsplits > 16 && (s.Cg & 3) == 0 && (p.Npad & 3) == 0 &&
-        ((reinterpret_cast<uintptr_t>(dw) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0)
+        ((reinterpret_cast<uintptr_t>(dw) | reinterpret_cast<uintptr_t>(workspace)) & 15) == 0) {
+        trace_kernel("conv_dw_dma_finalize:x4");
         conv_dw_dma_finalize_x4_kernel<16><<<(unsigned)((total / 4 + 63) / 64), 1024, 0, current_stream()>>>(
             workspace, p.qsplits, s.groups, s.Mg, s.Cg, p.Mpad, p.Npad, dw, fold ? fold->var : nullptr, fold ? fold->scales : nullptr);
-    else if (p.qsplits > 16)
+    } else if (p.qsplits > 16) {
+        trace_kernel("conv_dw_dma_finalize:16");
         conv_dw_dma_finalize_kernel<16><<<(unsigned)((total + 63) / 64), 1024, 0, current_stream()>>>(
             workspace, p.qsplits, s.groups, s.Mg, s.Cg, p.kk2, p.Mpad, p.Npad, dw, fold ? fold->var : nullptr, fold ? fold->scales : nullptr);
-    else
+    } else {
+        trace_kernel("conv_dw_dma_finalize:4");
         conv_dw_dma_finalize_kernel<4><<<(unsigned)((total + 63) / 64), 256, 0, current_stream()>>>(
             workspace, p.qsplits, s.groups, s.Mg, s.Cg, p.kk2, p.Mpad, p.Npad, dw, fold ? fold->var : nullptr, fold ? fold->scales : nullptr);
+    }
     KERNEL_CHECK();
     return true;
 }
@@ -458,16 +462,20 @@ bool conv_backward_weights_small_c(const float* x, const float* dy, float* dw, f
     a.rowmode = 1; a.nrows = s.K; a.row_kk = s.ksz * s.ksz; a.row_ks = s.ksz; a.row_plane = Hp * Wp; a.row_pitch = Wp;
     a.row_kk_magic = magic_of(a.row_kk); a.row_ks_magic = magic_of(a.row_ks);
     dim3 grid((unsigned)(p.mtiles * p.ntiles * p.qsplits), 1u);
+    trace_kernel("conv_small_c:dw");
     conv_dw_dma_kernel<2, 2, 1, 1><<<grid, (unsigned)kDwTiles[0].threads, 0, current_stream()>>>(a);
     KERNEL_CHECK();
     // partials [qs][1][1][Mpad][Npad] -> dw[f][j] += ..., j = (c, kr, kc): the weight tensor's own layout
     const size_t total = (size_t)s.Mg * s.K;
-    if (p.qsplits > 16)
+    if (p.qsplits > 16) {
+        trace_kernel("conv_dw_dma_finalize:16");
         conv_dw_dma_finalize_kernel<16><<<(unsigned)((total + 63) / 64), 1024, 0, current_stream()>>>(
             workspace, p.qsplits, 1, s.Mg, s.K, 1, p.Mpad, p.Npad, dw, nullptr, nullptr);
-    else
+    } else {
+        trace_kernel("conv_dw_dma_finalize:4");
         conv_dw_dma_finalize_kernel<4><<<(unsigned)((total + 63) / 64), 256, 0, current_stream()>>>(
             workspace, p.qsplits, 1, s.Mg, s.K, 1, p.Mpad, p.Npad, dw, nullptr, nullptr);
+    }
     KERNEL_CHECK();
     return true;
 }

@@ -376,6 +376,7 @@ bool conv_backward_weights_winograd(const float* x, const float* dy, float* dw, 
     const size_t need = conv_dw_dma_workspace_floats(gs);
     if (need == 0) return false;
     KTimer kt(K_CONV_DW_WINO, wino_flops(s), conv_gemm_bytes(s), wino_useful_flops(s));
+    trace_kernel("wino_unfused:dw");  // the grouped GEMM below adds conv_dw_dma_kernel and its finalize variant
     WinoGeom g;
     g.N = s.N; g.C = s.C; g.H = s.H; g.W = s.W;
     g.TH = (s.H + 1) / 2; g.TW = (s.W + 1) / 2;
