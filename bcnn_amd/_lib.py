@@ -58,6 +58,10 @@ SIGNATURES = {
     "bcnn_hip_col2im": (None, [vp, i, i, i, i, i, i, vp]),
     "bcnn_hip_activation_forward": (None, [vp, sz, i, vp, i, i]),
     "bcnn_hip_activation_backward": (None, [vp, vp, sz, i, vp, vp, i, i]),
+    "bcnn_hip_activation_forward_keep": (None, [vp, vp, sz, i]),
+    "bcnn_hip_activation_backward_from_input": (None, [vp, vp, sz, i]),
+    "bcnn_hip_scale_channels_forward": (None, [vp, vp, vp, i, i, i, i]),
+    "bcnn_hip_scale_channels_backward": (None, [vp, vp, vp, vp, vp, i, i, i, i]),
     "bcnn_hip_batchnorm_forward": (None, [vp] * 10 + [i, i, i, i, i]),
     "bcnn_hip_batchnorm_backward": (None, [vp, vp, vp, i] + [vp] * 9 + [i, i, i]),
     "bcnn_hip_conv_workspace_size": (sz, [i] * 9),

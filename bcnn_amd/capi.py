@@ -14,13 +14,14 @@ LIB_PATH = os.environ.get("BCNN_LIB", os.path.join(_HERE, "lib", "libbcnn.so")) 
 MODE_PREDICT, MODE_TRAIN, MODE_VALID = 0, 1, 2
 PRECISION_FP32, PRECISION_BF16 = 0, 1
 (ACT_NONE, ACT_TANH, ACT_RELU, ACT_RAMP, ACT_SOFTPLUS, ACT_LRELU, ACT_ABS, ACT_CLAMP, ACT_PRELU,
- ACT_LOGISTIC) = range(10)
+ ACT_LOGISTIC, ACT_RELU6, ACT_HARD_SIGMOID, ACT_HARD_SWISH, ACT_SWISH, ACT_MISH) = range(15)
 PADDING_SAME, PADDING_VALID, PADDING_CAFFE = 0, 1, 2
 FILLER_FIXED, FILLER_XAVIER, FILLER_MSRA = 0, 1, 2
 LOSS_EUCLIDEAN, LOSS_LIFTED_STRUCT = 0, 1
 LOG_SILENT = 3
 IMAGE_FIT_STRETCH, IMAGE_FIT_LETTERBOX = 0, 1
 POOL2D_MAX, POOL2D_AVG = 0, 1
+LAYER_ACTIVATION, LAYER_POOL2D, LAYER_SCALE_CHANNELS = 3, 17, 18
 
 
 class Tensor(C.Structure):
@@ -112,6 +113,7 @@ def lib():
         "bcnn_add_batchnorm_layer": (i, [vp, cp, cp]), "bcnn_add_maxpool_layer": (i, [vp, i, i, i, cp, cp]),
         "bcnn_add_avgpool_layer": (i, [vp, cp, cp]), "bcnn_add_activation_layer": (i, [vp, i, cp]),
         "bcnn_add_pool2d_layer": (i, [vp, i, i, i, i, i, i, cp, cp]),
+        "bcnn_add_scale_channels_layer": (i, [vp, cp, cp, cp]),
         "bcnn_add_eltwise_layer": (i, [vp, i, cp, cp, cp]), "bcnn_add_fullc_layer": (i, [vp, i, i, i, i, cp, cp]),
         "bcnn_add_softmax_layer": (i, [vp, cp, cp]), "bcnn_add_cost_layer": (i, [vp, i, i, f, cp, cp, cp]),
         "bcnn_upload_tensor": (i, [vp, i, i]), "bcnn_download_tensor": (i, [vp, i, i]),
@@ -131,6 +133,7 @@ def lib():
         "bcnn_get_gradient_arena": (vp, [vp, C.POINTER(sz)]), "bcnn_get_parameter_arena": (vp, [vp, C.POINTER(sz)]),
         "bcnn_synchronize": (None, [vp]), "bcnn_peek_tensor": (tp, [vp, i]), "bcnn_get_num_nodes": (i, [vp]),
         "bcnn_get_node_tensor": (i, [vp, i, i, i]), "bcnn_get_node_state": (vp, [vp, i, i]),
+        "bcnn_get_node_type": (i, [vp, i]), "bcnn_get_node_activation": (i, [vp, i]),
         "bcnn_forward_node": (i, [vp, i]), "bcnn_backward_node": (i, [vp, i]),
         "bcnn_load_net": (i, [vp, cp, cp]), "bcnn_save_weights": (i, [vp, cp]), "bcnn_load_weights": (i, [vp, cp]),
         "bcnn_add_concat_layer": (i, [vp, i, C.POINTER(cp), cp]), "bcnn_add_upsample_layer": (i, [vp, i, cp, cp]),
@@ -214,6 +217,10 @@ class Net:
         kind = {"max": POOL2D_MAX, "avg": POOL2D_AVG}.get(kind, kind)
         return self._added(self.L.bcnn_add_pool2d_layer(self.net, kind, size, stride, pad, 1 if ceil_mode else 0,
                                                          1 if count_include_pad else 0, src.encode(), dst.encode()))
+
+    def scale_channels(self, src, gate, dst):
+        """bcnn_add_scale_channels_layer: dst = src * gate, gate [N,C,1,1] (squeeze-and-excitation) or src's shape (sam)"""
+        return self._added(self.L.bcnn_add_scale_channels_layer(self.net, src.encode(), gate.encode(), dst.encode()))
 
     def activation(self, act, src):
         return self._added(self.L.bcnn_add_activation_layer(self.net, act, src.encode()))
@@ -383,6 +390,13 @@ class Net:
 
     def node_dst(self, node, i=0):
         return self.L.bcnn_get_node_tensor(self.net, node, 1, i)
+
+    def node_type(self, node):
+        return int(self.L.bcnn_get_node_type(self.net, node))
+
+    def node_activation(self, node):
+        """the bcnn_activation of a node that has one, else -1"""
+        return int(self.L.bcnn_get_node_activation(self.net, node))
 
     def node_state(self, node, which):
         return self.L.bcnn_get_node_state(self.net, node, which)

@@ -169,15 +169,27 @@ __device__ __forceinline__ float act_fwd(float x, int act, float slope) {
         case BCNN_HIP_ACT_CLAMP: return (x < 0) ? 0.f : ((x > 1) ? 1.f : x);
         case BCNN_HIP_ACT_LOGISTIC: return 1.0f / (1.0f + (float)exp((double)(-x)));
         case BCNN_HIP_ACT_PRELU: return x > 0 ? x : slope * x;
+        // appended, no reference counterpart (torch's relu6 / hardsigmoid). `+ 0.f`: +0 for every x <= 0, whichever zero
+        // fmaxf(-0, +0) picks; a NaN goes through (fmaxf alone would turn it into 0)
+        case BCNN_HIP_ACT_RELU6: return x != x ? x : fminf(fmaxf(x, 0.f), 6.f) + 0.f;
+        case BCNN_HIP_ACT_HARD_SIGMOID: return x != x ? x : fminf(fmaxf(x + 3.f, 0.f), 6.f) / 6.0f;
         default: return x;
     }
+}
+// The self-gated activations (hard-swish, swish, mish): their derivative is no function of the output, so no fused
+// epilogue and no `act` argument but the stand-alone activation entry points' (activation.hip) takes them.
+__host__ __device__ __forceinline__ bool act_needs_input(int act) {
+    return act == BCNN_HIP_ACT_HARD_SWISH || act == BCNN_HIP_ACT_SWISH || act == BCNN_HIP_ACT_MISH;
 }
 
 // Activations cheap enough to fuse into a producer's epilogue (no double-precision exp/log). The
 // other three (tanh, softplus, logistic) run as a separate in-place pass (activation.hip) so that
-// the MFMA kernels keep their register budget.
+// the MFMA kernels keep their register budget. So do the appended ones (relu6, hard-sigmoid: not measured inside an
+// epilogue yet; the self-gated three never fuse), in both directions: the switches of act_fwd_cheap / act_bwd_cheap
+// hold the reference's ids only.
 __host__ __device__ __forceinline__ bool act_is_cheap(int act) {
-    return act != BCNN_HIP_ACT_TANH && act != BCNN_HIP_ACT_SOFTPLUS && act != BCNN_HIP_ACT_LOGISTIC;
+    return act != BCNN_HIP_ACT_TANH && act != BCNN_HIP_ACT_SOFTPLUS && act != BCNN_HIP_ACT_LOGISTIC &&
+           act < BCNN_HIP_ACT_RELU6;
 }
 __device__ __forceinline__ float act_fwd_cheap(float x, int act, float slope) {
     switch (act) {
@@ -203,7 +215,9 @@ __device__ __forceinline__ float act_bwd_cheap(float y, int act, float slope) {
         default: return 1.0f;
     }
 }
-__host__ __device__ __forceinline__ bool act_bwd_is_cheap(int act) { return act != BCNN_HIP_ACT_SOFTPLUS; }
+__host__ __device__ __forceinline__ bool act_bwd_is_cheap(int act) {
+    return act != BCNN_HIP_ACT_SOFTPLUS && act < BCNN_HIP_ACT_RELU6;
+}
 
 // derivative factor from the POST-activation value, bcnn_activation_layer.c:165-226
 __device__ __forceinline__ float act_bwd_factor(float y, int act, float slope) {
@@ -217,6 +231,8 @@ __device__ __forceinline__ float act_bwd_factor(float y, int act, float slope) {
         case BCNN_HIP_ACT_CLAMP: return (float)(y > 0.0f && y < 1.0f);
         case BCNN_HIP_ACT_LOGISTIC: return (1 - y) * y;
         case BCNN_HIP_ACT_PRELU: return y > 0 ? 1.0f : slope;
+        case BCNN_HIP_ACT_RELU6: return (float)(y > 0.0f && y < 6.0f);
+        case BCNN_HIP_ACT_HARD_SIGMOID: return (y > 0.0f && y < 1.0f) ? 1 / 6.0f : 0.f;
         default: return 1.0f;
     }
 }

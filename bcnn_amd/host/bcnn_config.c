@@ -194,6 +194,7 @@ typedef struct {
     /* [pool] / [local_avgpool]: which of size / stride the section set (their defaults differ from the other sections'),
      * `pad` as written (a count per side in both dialects), and the three keys only these sections read */
     int has_size, has_stride, pool_pad, pool_avg, ceil_mode, count_include_pad;
+    int has_from; /* Darknet `from=`: src_id[0] is the previous section, src_id[1] the named one */
 } layer_param;
 
 static void lp_reset(layer_param *lp) {
@@ -293,6 +294,12 @@ static void lp_set(bcnn_net *net, int section_idx, layer_param *lp, const char *
         else if (!strcmp(val, "prelu")) lp->a = BCNN_ACT_PRELU;
         else if (!strcmp(val, "abs")) lp->a = BCNN_ACT_ABS;
         else if (!strcmp(val, "none") || !strcmp(val, "linear")) lp->a = BCNN_ACT_NONE;
+        else if (!strcmp(val, "logistic") || !strcmp(val, "sigmoid")) lp->a = BCNN_ACT_LOGISTIC;
+        else if (!strcmp(val, "relu6")) lp->a = BCNN_ACT_RELU6;
+        else if (!strcmp(val, "hard_sigmoid") || !strcmp(val, "hardsigmoid")) lp->a = BCNN_ACT_HARD_SIGMOID;
+        else if (!strcmp(val, "hard_swish") || !strcmp(val, "hardswish") || !strcmp(val, "hswish")) lp->a = BCNN_ACT_HARD_SWISH;
+        else if (!strcmp(val, "swish") || !strcmp(val, "silu")) lp->a = BCNN_ACT_SWISH;
+        else if (!strcmp(val, "mish")) lp->a = BCNN_ACT_MISH;
         else {
             bcnn_log(net->log_ctx, BCNN_LOG_WARNING, "Unknown activation type %s, going with ReLU\n", val);
             lp->a = BCNN_ACT_RELU;
@@ -328,8 +335,9 @@ static void lp_set(bcnn_net *net, int section_idx, layer_param *lp, const char *
             const int l = atoi(lp->src_id[i]);
             lp_set_lid(&lp->src_id[i], l >= 0 ? l + 1 : section_idx + l);
         }
-    } else if (!strcmp(name, "from")) { /* Darknet [shortcut]: previous section + the named one */
+    } else if (!strcmp(name, "from")) { /* Darknet [shortcut] / [scale_channels] / [sam]: previous section + the named one */
         const int l = atoi(val);
+        lp->has_from = 1;
         lp_set_srcs(lp, "a,b");
         lp_set_lid(&lp->src_id[0], section_idx - 1);
         lp_set_lid(&lp->src_id[1], l >= 0 ? l + 1 : section_idx + l);
@@ -354,6 +362,15 @@ static int is_any(const char *name, const char *a, const char *b, const char *c,
     return !strcmp(name, a) || (b && !strcmp(name, b)) || (c && !strcmp(name, c)) || (d && !strcmp(name, d));
 }
 
+/* A section with a fused activation that asks for hard-swish, swish or mish -- whose derivative needs the layer's output
+ * BEFORE the activation, which a fused layer does not keep -- is built as the layer with no activation plus the in-place
+ * activation node on its output. The section still stands for that output (Darknet's lid chain). */
+static bcnn_activation fused_act(const layer_param *lp) { return bcnn_act_needs_input(lp->a) ? BCNN_ACT_NONE : lp->a; }
+static bcnn_status add_split_act(bcnn_net *net, bcnn_status st, const layer_param *lp) {
+    if (st != BCNN_SUCCESS || !bcnn_act_needs_input(lp->a)) return st;
+    return bcnn_add_activation_layer(net, lp->a, lp->dst_id);
+}
+
 static bcnn_status add_layer(bcnn_net *net, const char *name, layer_param *lp) {
     if (net->num_nodes == 0) {
         BCNN_CHECK_AND_LOG(net->log_ctx, net->tensors[0].w > 0 && net->tensors[0].h > 0 && net->tensors[0].c > 0,
@@ -368,17 +385,19 @@ static bcnn_status add_layer(bcnn_net *net, const char *name, layer_param *lp) {
                        "Invalid output node name. Hint: Are you sure that 'dst' field is correctly setup?\n");
     if (!strcmp(name, "[input]")) return bcnn_add_input(net, lp->in_w, lp->in_h, lp->in_c, src);
     if (is_any(name, "[conv]", "[convolutional]", NULL, NULL))
-        return bcnn_add_convolutional_layer(net, lp->n_filts, lp->size, lp->stride, lp->pad, lp->num_groups,
-                                            lp->batchnorm, lp->init, lp->a, 0, src, dst);
+        return add_split_act(net, bcnn_add_convolutional_layer(net, lp->n_filts, lp->size, lp->stride, lp->pad, lp->num_groups,
+                                                               lp->batchnorm, lp->init, fused_act(lp), 0, src, dst), lp);
     if (is_any(name, "[deconv]", "[deconvolutional]", NULL, NULL))
-        return bcnn_add_deconvolutional_layer(net, lp->n_filts, lp->size, lp->stride, lp->pad, lp->init, lp->a, src, dst);
+        return add_split_act(net, bcnn_add_deconvolutional_layer(net, lp->n_filts, lp->size, lp->stride, lp->pad, lp->init,
+                                                                 fused_act(lp), src, dst), lp);
     if (is_any(name, "[depthwise-conv]", "[dw-conv]", NULL, NULL))
-        return bcnn_add_depthwise_conv_layer(net, lp->size, lp->stride, lp->pad, 0, lp->init, lp->a, src, dst);
+        return add_split_act(net, bcnn_add_depthwise_conv_layer(net, lp->size, lp->stride, lp->pad, 0, lp->init, fused_act(lp),
+                                                                src, dst), lp);
     if (is_any(name, "[activation]", "[nl]", NULL, NULL)) return bcnn_add_activation_layer(net, lp->a, src);
     if (is_any(name, "[batchnorm]", "[bn]", NULL, NULL)) return bcnn_add_batchnorm_layer(net, src, dst);
     if (!strcmp(name, "[lrn]")) return bcnn_add_lrn_layer(net, lp->size, lp->alpha, lp->beta, lp->k, src, dst);
     if (is_any(name, "[connected]", "[fullconnected]", "[fc]", "[ip]"))
-        return bcnn_add_fullc_layer(net, lp->outputs, lp->init, lp->a, 0, src, dst);
+        return add_split_act(net, bcnn_add_fullc_layer(net, lp->outputs, lp->init, fused_act(lp), 0, src, dst), lp);
     if (!strcmp(name, "[softmax]")) return bcnn_add_softmax_layer(net, src, dst);
     if (is_any(name, "[max]", "[maxpool]", NULL, NULL))
         return bcnn_add_maxpool_layer(net, lp->size, lp->stride, lp->padding_type, src, dst);
@@ -398,7 +417,17 @@ static bcnn_status add_layer(bcnn_net *net, const char *name, layer_param *lp) {
     if (is_any(name, "[eltwise]", "[shortcut]", NULL, NULL)) {
         BCNN_CHECK_AND_LOG(net->log_ctx, lp->num_srcs >= 2, BCNN_INVALID_PARAMETER,
                            "Eltwise layer needs two sources (src=a,b)\n");
-        return bcnn_add_eltwise_layer(net, lp->a, lp->src_id[0], lp->src_id[1], dst);
+        return add_split_act(net, bcnn_add_eltwise_layer(net, fused_act(lp), lp->src_id[0], lp->src_id[1], dst), lp);
+    }
+    if (is_any(name, "[scale_channels]", "[sam]", NULL, NULL)) {
+        /* bcnn dialect: src=features,gate. Darknet: `from=` names the FEATURES and the previous section is the gate
+         * (scale_channels_layer.c / sam_layer.c), the reverse of [shortcut]'s order in src_id. The gate's shape picks the
+         * form, so the two names build the same node. */
+        BCNN_CHECK_AND_LOG(net->log_ctx, lp->num_srcs >= 2, BCNN_INVALID_PARAMETER,
+                           "Scale-channels layer needs two sources (src=features,gate or from=)\n");
+        BCNN_CHECK_AND_LOG(net->log_ctx, lp->a == BCNN_ACT_NONE, BCNN_INVALID_PARAMETER,
+                           "Scale-channels layer %s: only activation=linear is supported; add an [activation] section\n", dst);
+        return bcnn_add_scale_channels_layer(net, lp->src_id[lp->has_from ? 1 : 0], lp->src_id[lp->has_from ? 0 : 1], dst);
     }
     if (!strcmp(name, "[yolo]")) {
         /* the builder copies 2 * num values (the reference reads past a shorter list); pad a short one with zeros */

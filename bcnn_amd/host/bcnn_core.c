@@ -521,30 +521,21 @@ static bcnn_status resize_private_f32(float **buf, size_t old_elems, size_t new_
     return *buf ? BCNN_SUCCESS : BCNN_FAILED_ALLOC;
 }
 
-bcnn_status bcnn_resize_net(bcnn_net *net, int w, int h, int c, int need_realloc) {
-    if (!net || w <= 0 || h <= 0 || c <= 0) return BCNN_INVALID_PARAMETER;
-    /* The reference gives every node type other than convolution and max-pooling its source's shape, which is wrong for
-     * upsample (scaled extent), concat (summed depth) and deconvolution (scaled extent, own depth). Such graphs are
-     * refused before any shape changes. */
-    for (int i = 0; i < net->num_nodes; ++i) {
-        const bcnn_layer_type t = net->nodes[i].type;
-        BCNN_CHECK_AND_LOG(net->log_ctx, t != BCNN_LAYER_CONCAT && t != BCNN_LAYER_UPSAMPLE && t != BCNN_LAYER_YOLOV3 &&
-                                             t != BCNN_LAYER_TRANSPOSE_CONV2D,
-                           BCNN_INVALID_PARAMETER,
-                           "bcnn_resize_net: node %d is a concat / upsample / YOLO / deconvolution node, whose resize is "
-                           "not supported\n", i);
-        /* every node but convolution and max-pooling takes its source's shape below, so the [n][c][1][1] embedding the
-         * lifted-structure loss was built on (and its label) would not survive the call */
-        BCNN_CHECK_AND_LOG(net->log_ctx,
-                           t != BCNN_LAYER_COST || ((const bcnn_cost_param *)net->nodes[i].param)->loss != BCNN_LOSS_LIFTED_STRUCT,
-                           BCNN_INVALID_PARAMETER,
-                           "bcnn_resize_net: node %d is a lifted-structure cost node, whose resize is not supported\n", i);
-    }
+/* the walk of bcnn_resize_net; *saved_input_node: the hard-swish / swish / mish node whose saved-input buffer refused, if any */
+static bcnn_status resize_walk(bcnn_net *net, int w, int h, int c, int need_realloc, int *saved_input_node) {
     bcnn_set_input_shape(net, w, h, c, 1);
     for (int i = 0; i < net->num_nodes; ++i) {
         bcnn_node *nd = &net->nodes[i];
         if (nd->num_src < 1 || nd->num_dst < 1) continue;
         if (nd->type == BCNN_LAYER_DROPOUT) continue; /* in place: its tensor was re-shaped by its producer */
+        if (nd->type == BCNN_LAYER_ACTIVATION && bcnn_act_needs_input(((bcnn_activation_param *)nd->param)->activation)) {
+            /* in place as well; its saved input follows the tensor by capacity, like the pool2d indexes below */
+            const bcnn_status st = bcnn_activation_reserve_saved((bcnn_activation_param *)nd->param,
+                                                                 (size_t)bcnn_tensor_size(&net->tensors[nd->dst[0]]), need_realloc);
+            if (st != BCNN_SUCCESS) *saved_input_node = i;
+            BCNN_CHECK_STATUS(st);
+            continue;
+        }
         const bcnn_tensor *s = &net->tensors[nd->src[0]];
         bcnn_tensor *d = &net->tensors[nd->dst[0]];
         const size_t old_elems = (size_t)bcnn_tensor_size(d);
@@ -593,6 +584,54 @@ bcnn_status bcnn_resize_net(bcnn_net *net, int w, int h, int c, int need_realloc
             }
         }
     }
+    return BCNN_SUCCESS;
+}
+
+bcnn_status bcnn_resize_net(bcnn_net *net, int w, int h, int c, int need_realloc) {
+    if (!net || w <= 0 || h <= 0 || c <= 0) return BCNN_INVALID_PARAMETER;
+    /* The reference gives every node type other than convolution and max-pooling its source's shape, which is wrong for
+     * upsample (scaled extent), concat (summed depth) and deconvolution (scaled extent, own depth). Such graphs are
+     * refused before any shape changes. */
+    for (int i = 0; i < net->num_nodes; ++i) {
+        const bcnn_layer_type t = net->nodes[i].type;
+        BCNN_CHECK_AND_LOG(net->log_ctx, t != BCNN_LAYER_CONCAT && t != BCNN_LAYER_UPSAMPLE && t != BCNN_LAYER_YOLOV3 &&
+                                             t != BCNN_LAYER_TRANSPOSE_CONV2D,
+                           BCNN_INVALID_PARAMETER,
+                           "bcnn_resize_net: node %d is a concat / upsample / YOLO / deconvolution node, whose resize is "
+                           "not supported\n", i);
+        /* every node but convolution and max-pooling takes its source's shape below, so the [n][c][1][1] embedding the
+         * lifted-structure loss was built on (and its label) would not survive the call */
+        BCNN_CHECK_AND_LOG(net->log_ctx,
+                           t != BCNN_LAYER_COST || ((const bcnn_cost_param *)net->nodes[i].param)->loss != BCNN_LOSS_LIFTED_STRUCT,
+                           BCNN_INVALID_PARAMETER,
+                           "bcnn_resize_net: node %d is a lifted-structure cost node, whose resize is not supported\n", i);
+    }
+    /* Without need_realloc nothing is allocated, so the shapes are all the walk changes: kept to put them back when a
+     * hard-swish / swish / mish node's saved-input buffer turns out too small -- that refusal leaves the net as it was. */
+    int *old_shapes = NULL;
+    const int old_batch = net->batch_size;
+    if (!need_realloc) {
+        old_shapes = (int *)malloc(((size_t)net->num_tensors + 1) * 5 * sizeof(int));
+        if (!old_shapes) return BCNN_FAILED_ALLOC;
+        for (int t = 0; t < net->num_tensors; ++t) {
+            const bcnn_tensor *x = &net->tensors[t];
+            old_shapes[5 * t] = x->n; old_shapes[5 * t + 1] = x->c; old_shapes[5 * t + 2] = x->h; old_shapes[5 * t + 3] = x->w;
+            old_shapes[5 * t + 4] = x->has_grad;
+        }
+    }
+    int saved_input_node = -1;
+    const bcnn_status st = resize_walk(net, w, h, c, need_realloc, &saved_input_node);
+    if (saved_input_node >= 0 && old_shapes) {
+        for (int t = 0; t < net->num_tensors; ++t)
+            bcnn_tensor_set_shape(&net->tensors[t], old_shapes[5 * t], old_shapes[5 * t + 1], old_shapes[5 * t + 2],
+                                  old_shapes[5 * t + 3], old_shapes[5 * t + 4]);
+        net->batch_size = old_batch;
+        bcnn_log(net->log_ctx, BCNN_LOG_ERROR,
+                 "bcnn_resize_net: node %d keeps its input for the backward pass and its buffer is smaller than the new shape; "
+                 "call with need_realloc\n", saved_input_node);
+    }
+    free(old_shapes);
+    BCNN_CHECK_STATUS(st);
     if (hctx(net)->compiled) return bcnn_compile_net(net); /* input tensor, conv scratch, links */
     return BCNN_SUCCESS;
 }
@@ -1066,12 +1105,32 @@ int bcnn_get_node_tensor(bcnn_net *net, int node, int is_dst, int slot) {
     return slot < nd->num_src ? nd->src[slot] : -1;
 }
 
+int bcnn_get_node_type(bcnn_net *net, int node) {
+    return (node < 0 || node >= net->num_nodes) ? -1 : (int)net->nodes[node].type;
+}
+
+int bcnn_get_node_activation(bcnn_net *net, int node) {
+    if (node < 0 || node >= net->num_nodes) return -1;
+    const bcnn_node *nd = &net->nodes[node];
+    switch (nd->type) {
+        case BCNN_LAYER_CONV2D: return (int)((const bcnn_conv_param *)nd->param)->activation;
+        case BCNN_LAYER_TRANSPOSE_CONV2D: return (int)((const bcnn_deconv_param *)nd->param)->activation;
+        case BCNN_LAYER_DEPTHWISE_CONV2D: return (int)((const bcnn_depthwise_conv_param *)nd->param)->activation;
+        case BCNN_LAYER_ACTIVATION: return (int)((const bcnn_activation_param *)nd->param)->activation;
+        case BCNN_LAYER_FULL_CONNECTED: return (int)((const bcnn_fullc_param *)nd->param)->activation;
+        case BCNN_LAYER_ELTWISE: return (int)((const bcnn_eltwise_param *)nd->param)->activation;
+        default: return -1;
+    }
+}
+
 void *bcnn_get_node_state(bcnn_net *net, int node, int which) {
     if (node < 0 || node >= net->num_nodes) return NULL;
     const bcnn_node *nd = &net->nodes[node];
     const bcnn_tensor *sm = NULL, *sv = NULL;
     if (nd->type == BCNN_LAYER_MAXPOOL) return which == 0 ? (void *)((bcnn_maxpool_param *)nd->param)->indexes_gpu : NULL;
     if (nd->type == BCNN_LAYER_POOL2D) return which == 0 ? (void *)((bcnn_pool2d_param *)nd->param)->indexes_gpu : NULL;
+    if (nd->type == BCNN_LAYER_ACTIVATION) /* hard-swish / swish / mish: the input the last TRAIN forward kept */
+        return which == 0 ? (void *)((bcnn_activation_param *)nd->param)->x_saved_gpu : NULL;
     if (nd->type == BCNN_LAYER_CONV2D && ((bcnn_conv_param *)nd->param)->batch_norm) {
         sm = &((bcnn_conv_param *)nd->param)->saved_mean;
         sv = &((bcnn_conv_param *)nd->param)->saved_variance;

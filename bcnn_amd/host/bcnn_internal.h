@@ -257,9 +257,25 @@ static inline const char *bcnn_act2str(bcnn_activation a) {
         case BCNN_ACT_CLAMP: return "Clamp";
         case BCNN_ACT_PRELU: return "PReLU";
         case BCNN_ACT_LOGISTIC: return "Logistic";
+        case BCNN_ACT_RELU6: return "ReLU6";
+        case BCNN_ACT_HARD_SIGMOID: return "Hard-Sigmoid";
+        case BCNN_ACT_HARD_SWISH: return "Hard-Swish";
+        case BCNN_ACT_SWISH: return "Swish";
+        case BCNN_ACT_MISH: return "Mish";
         default: return "None";
     }
 }
+
+/* hard-swish, swish, mish: the derivative is no function of the output, so only the stand-alone activation node (which
+ * keeps its input) takes them */
+static inline int bcnn_act_needs_input(bcnn_activation a) {
+    return a == BCNN_ACT_HARD_SWISH || a == BCNN_ACT_SWISH || a == BCNN_ACT_MISH;
+}
+/* the refusal every builder with a fused activation starts with; nothing has been added to the net at that point */
+#define BCNN_REFUSE_INPUT_ACTIVATION(net, a, layer)                                                                        \
+    BCNN_CHECK_AND_LOG((net)->log_ctx, !bcnn_act_needs_input(a), BCNN_INVALID_PARAMETER,                                   \
+                       "%s layer: %s takes its derivative from the layer's input and cannot be fused; build the layer "   \
+                       "with BCNN_ACT_NONE and add bcnn_add_activation_layer on its output\n", layer, bcnn_act2str(a))
 
 /* ---- layer parameter blocks (member names follow src/layers/<layer>.h of the reference) ---------- */
 typedef struct bcnn_conv_param {
@@ -363,7 +379,17 @@ typedef struct bcnn_maxpool_param {
 
 typedef struct bcnn_activation_param {
     bcnn_activation activation;
+#ifdef BCNN_USE_HIP
+    float *x_saved_gpu;       /* hard-swish / swish / mish, nets built in TRAIN / VALID mode: the input of the last TRAIN forward */
+    size_t x_saved_capacity;  /* elements allocated; bcnn_resize_net grows the buffer past this, not past the last shape */
+#endif
 } bcnn_activation_param;
+
+/* dst = src[0] * src[1] (bcnn_add_scale_channels_layer; no reference counterpart); the gate's form follows from the two
+ * shapes at every call, so bcnn_resize_net has nothing to update here */
+typedef struct bcnn_scale_channels_param {
+    int same_shape; /* as built: 0 = [N,C,1,1] gate, 1 = a gate of the source's shape (log line only) */
+} bcnn_scale_channels_param;
 
 typedef struct bcnn_eltwise_param {
     bcnn_activation activation;
@@ -518,6 +544,12 @@ void bcnn_forward_dropout_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_dropout_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_dropout_layer(bcnn_node *node);
 uint64_t bcnn_dropout_key(uint64_t seed, int node, int rank);
+void bcnn_forward_scale_channels_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_backward_scale_channels_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_release_param_activation_layer(bcnn_node *node);
+/* bcnn_resize_net: makes a hard-swish / swish / mish node's saved-input buffer hold `elems` floats (no-op for every other
+ * activation and for PREDICT-built nets); without need_realloc a size past the capacity is BCNN_INVALID_PARAMETER */
+bcnn_status bcnn_activation_reserve_saved(bcnn_activation_param *p, size_t elems, int need_realloc);
 void bcnn_forward_pool2d_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_pool2d_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_pool2d_layer(bcnn_node *node);

@@ -28,6 +28,7 @@ bcnn_status bcnn_add_deconvolutional_layer(bcnn_net *net, int n, int size, int s
     }
     BCNN_CHECK_AND_LOG(net->log_ctx, activation != BCNN_ACT_PRELU, BCNN_INVALID_PARAMETER,
                        "Deconvolution layer %s: PReLU is not supported\n", dst_id);
+    BCNN_REFUSE_INPUT_ACTIVATION(net, activation, "Deconvolution");
     BCNN_CHECK_AND_LOG(net->log_ctx, n > 0 && size >= 1 && stride >= 1 && pad >= 0, BCNN_INVALID_PARAMETER,
                        "Deconvolution layer %s: invalid filters %d / size %d / stride %d / pad %d\n", dst_id, n, size,
                        stride, pad);

@@ -64,6 +64,7 @@ bcnn_status bcnn_add_convolutional_layer(bcnn_net *net, int num_filters, int siz
                                          const char *dst_id) {
     (void)quantize;
     bcnn_node node = {0};
+    BCNN_REFUSE_INPUT_ACTIVATION(net, activation, "Convolution");
     if (net->num_nodes == 0)
         BCNN_CHECK_AND_LOG(net->log_ctx, bcnn_tensor_size(&net->tensors[0]) > 0, BCNN_INVALID_PARAMETER,
                            "Invalid input size of the network. Hint: use 'bcnn_set_input_shape'\n");
@@ -360,6 +361,7 @@ bcnn_status bcnn_add_depthwise_conv_layer(bcnn_net *net, int size, int stride, i
                                           const char *dst_id) {
     (void)batch_norm; /* ignored by the reference as well (bcnn_depthwise_conv_layer.c:42-163) */
     bcnn_node node = {0};
+    BCNN_REFUSE_INPUT_ACTIVATION(net, activation, "Depthwise convolution");
     BCNN_CHECK_STATUS(attach_source(net, &node, src_id, "Depthwise convolution"));
     const bcnn_tensor s = net->tensors[node.src[0]];
     char name[256];
@@ -1066,6 +1068,11 @@ bcnn_status bcnn_add_activation_layer(bcnn_net *net, bcnn_activation type, const
     node.forward = bcnn_forward_activation_layer;
     node.backward = bcnn_backward_activation_layer;
     node.update = bcnn_update_activation_layer;
+    node.release_param = bcnn_release_param_activation_layer;
+    if (bcnn_act_needs_input(type) && net->mode != BCNN_MODE_PREDICT) { /* the backward's input; a PREDICT net has no backward */
+        param->x_saved_capacity = (size_t)bcnn_tensor_size(&net->tensors[idx]);
+        param->x_saved_gpu = bcnn_hip_malloc_f32(param->x_saved_capacity);
+    }
     if (type == BCNN_ACT_PRELU) {
         char name[256];
         snprintf(name, sizeof(name), "%s_w_prelu", src_id);
@@ -1084,6 +1091,11 @@ void bcnn_forward_activation_layer(bcnn_net *net, bcnn_node *node) {
     bcnn_activation_param *p = (bcnn_activation_param *)node->param;
     bcnn_tensor *t = &net->tensors[node->dst[0]];
     const float *slopes = (p->activation == BCNN_ACT_PRELU) ? net->tensors[node->src[1]].data_gpu : NULL;
+    if (bcnn_act_needs_input(p->activation)) { /* TRAIN: the same sweep keeps the input for the backward; VALID / PREDICT store nothing */
+        bcnn_hip_activation_forward_keep(t->data_gpu, net->mode == BCNN_MODE_TRAIN ? p->x_saved_gpu : NULL,
+                                         (size_t)bcnn_tensor_size(t), (int)p->activation);
+        return;
+    }
     bcnn_hip_activation_forward(t->data_gpu, (size_t)bcnn_tensor_size(t), (int)p->activation, slopes, t->w * t->h, t->c);
 }
 
@@ -1091,9 +1103,30 @@ void bcnn_backward_activation_layer(bcnn_net *net, bcnn_node *node) {
     bcnn_activation_param *p = (bcnn_activation_param *)node->param;
     bcnn_tensor *t = &net->tensors[node->dst[0]];
     if (!t->grad_data_gpu) return;
+    if (bcnn_act_needs_input(p->activation)) {
+        if (!p->x_saved_gpu) return; /* built in PREDICT mode: no forward kept an input */
+        bcnn_hip_activation_backward_from_input(p->x_saved_gpu, t->grad_data_gpu, (size_t)bcnn_tensor_size(t),
+                                                (int)p->activation);
+        return;
+    }
     bcnn_tensor *sl = (p->activation == BCNN_ACT_PRELU) ? &net->tensors[node->src[1]] : NULL;
     bcnn_hip_activation_backward(t->data_gpu, t->grad_data_gpu, (size_t)bcnn_tensor_size(t), (int)p->activation,
                                  sl ? sl->data_gpu : NULL, sl ? sl->grad_data_gpu : NULL, t->w * t->h, t->c);
+}
+
+void bcnn_release_param_activation_layer(bcnn_node *node) {
+    bcnn_activation_param *p = (bcnn_activation_param *)node->param;
+    bcnn_hip_free(p->x_saved_gpu);
+}
+
+bcnn_status bcnn_activation_reserve_saved(bcnn_activation_param *p, size_t elems, int need_realloc) {
+    if (!p->x_saved_gpu || elems <= p->x_saved_capacity) return BCNN_SUCCESS;
+    if (!need_realloc) return BCNN_INVALID_PARAMETER;
+    bcnn_hip_sync();
+    bcnn_hip_free(p->x_saved_gpu);
+    p->x_saved_gpu = bcnn_hip_malloc_f32(elems);
+    p->x_saved_capacity = p->x_saved_gpu ? elems : 0;
+    return p->x_saved_gpu ? BCNN_SUCCESS : BCNN_FAILED_ALLOC;
 }
 
 void bcnn_update_activation_layer(bcnn_net *net, bcnn_node *node) {

@@ -39,6 +39,7 @@ bcnn_status bcnn_add_eltwise_layer(bcnn_net *net, bcnn_activation activation, co
                                    const char *src_id2, const char *dst_id) {
     bcnn_node node = {0};
     int found1 = 0, found2 = 0;
+    BCNN_REFUSE_INPUT_ACTIVATION(net, activation, "Eltwise");
     for (int i = net->num_tensors - 1; i >= 0 && !(found1 && found2); --i) {
         const char *nm = net->tensors[i].name;
         if (!nm) continue;
@@ -118,6 +119,7 @@ bcnn_status bcnn_add_fullc_layer(bcnn_net *net, int output_size, bcnn_filler_typ
                                  int quantize, const char *src_id, const char *dst_id) {
     (void)quantize;
     bcnn_node node = {0};
+    BCNN_REFUSE_INPUT_ACTIVATION(net, activation, "Full-connected");
     if (net->num_nodes > 0) {
         const int idx = bcnn_net_find_tensor(net, src_id);
         BCNN_CHECK_AND_LOG(net->log_ctx, idx >= 0, BCNN_INVALID_PARAMETER,

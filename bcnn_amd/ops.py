@@ -12,6 +12,11 @@ import torch
 from . import _lib
 
 ACT = dict(none=0, tanh=1, relu=2, ramp=3, softplus=4, lrelu=5, abs=6, clamp=7, prelu=8, logistic=9)
+# The appended activations (no reference counterpart), and every name. ACT itself stays the reference's ten: tests iterate
+# over it as "every activation the reference has". relu6 / hard_sigmoid go wherever an `act` argument is taken; hard_swish,
+# swish and mish through activation_forward[_keep] / activation_backward_from_input only.
+ACT_APPENDED = dict(relu6=10, hard_sigmoid=11, hard_swish=12, swish=13, mish=14)
+ACT_ALL = dict(ACT, **ACT_APPENDED)
 MODE_PREDICT, MODE_TRAIN, MODE_VALID = 0, 1, 2
 
 
@@ -242,6 +247,43 @@ def pool2d_backward(dy, indexes, dx, kind, size, stride, pad=0, ceil_mode=False,
 def activation_forward(x, act, slopes=None, spatial=1, channels=1):
     """bcnn_forward_activation_cpu (bcnn_activation_layer.c:90-146), in place"""
     _lib.load().bcnn_hip_activation_forward(_f32(x), x.numel(), act, _f32(slopes), spatial, channels)
+
+
+def activation_forward_keep(x, x_saved, act):
+    """bcnn_hip_activation_forward_keep: x = act(x) in place and, unless x_saved is None, x_saved = the input. The forward
+    of hard_swish / swish / mish, whose backward (activation_backward_from_input) needs the input."""
+    assert x_saved is None or x_saved.numel() == x.numel()
+    _lib.load().bcnn_hip_activation_forward_keep(_f32(x), _f32(x_saved), x.numel(), act)
+
+
+def activation_backward_from_input(x_saved, dx, act):
+    """bcnn_hip_activation_backward_from_input: dx *= act'(x_saved) in place; hard_swish / swish / mish only"""
+    assert x_saved.numel() == dx.numel()
+    _lib.load().bcnn_hip_activation_backward_from_input(_f32(x_saved), _f32(dx), dx.numel(), act)
+
+
+def _scale_gate_form(x, gate):
+    n, c, h, w = x.shape
+    if tuple(gate.shape) == (n, c, h, w) and h * w > 1:
+        return 1
+    assert gate.numel() == n * c, "the gate is [N,C,1,1] or has x's shape"
+    return 0
+
+
+def scale_channels_forward(x, gate, y):
+    """bcnn_hip_scale_channels_forward: y = x * gate; gate is [N,C,1,1] (one factor per plane) or x's shape"""
+    n, c, h, w = x.shape
+    assert y.shape == x.shape
+    _lib.load().bcnn_hip_scale_channels_forward(_f32(x), _f32(gate), _f32(y), n, c, h * w, _scale_gate_form(x, gate))
+
+
+def scale_channels_backward(x, gate, dy, dx, dgate):
+    """bcnn_hip_scale_channels_backward: dx += dy * gate, dgate += the plane sums of dy * x (dy * x itself for a gate of
+    x's shape), in one sweep; dx or dgate may be None (that half is skipped)"""
+    n, c, h, w = x.shape
+    assert dy.shape == x.shape and (dx is None or dx.shape == x.shape) and (dgate is None or dgate.numel() == gate.numel())
+    _lib.load().bcnn_hip_scale_channels_backward(_f32(x), _f32(gate), _f32(dy), _f32(dx), _f32(dgate), n, c, h * w,
+                                                 _scale_gate_form(x, gate))
 
 
 def activation_backward(x, dx, act, slopes=None, dslopes=None, spatial=1, channels=1):

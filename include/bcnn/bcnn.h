@@ -58,11 +58,22 @@ typedef enum {
     BCNN_LAYER_YOLOV3, BCNN_LAYER_RESHAPE, BCNN_LAYER_COST,
     BCNN_LAYER_POOL2D /* windowed pooling with padding (bcnn_add_pool2d_layer); appended: the values above are the reference's */
 } bcnn_layer_type;
+/* The layer type of bcnn_add_scale_channels_layer (a feature map times a per-channel or same-shape gate), the value behind
+ * BCNN_LAYER_POOL2D. A constant of the enum's type next to the enum, not an enumerator: the enumerator list stays the one
+ * tests/test_pool2d_abi.py pins, which ends with BCNN_LAYER_POOL2D. */
+#define BCNN_LAYER_SCALE_CHANNELS ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 1))
 
 typedef enum {
     BCNN_ACT_NONE, BCNN_ACT_TANH, BCNN_ACT_RELU, BCNN_ACT_RAMP, BCNN_ACT_SOFTPLUS,
     BCNN_ACT_LRELU, /* negative slope 0.1 in the code (the reference's comment says 0.01) */
-    BCNN_ACT_ABS, BCNN_ACT_CLAMP, BCNN_ACT_PRELU, BCNN_ACT_LOGISTIC
+    BCNN_ACT_ABS, BCNN_ACT_CLAMP, BCNN_ACT_PRELU, BCNN_ACT_LOGISTIC,
+    /* appended, without a reference counterpart (the values above are the reference's).
+     * RELU6 = min(max(x, 0), 6) and HARD_SIGMOID = min(max(x + 3, 0), 6) / 6 (torch's hardsigmoid) are accepted wherever
+     * an activation is taken. HARD_SWISH = x min(max(x + 3, 0), 6) / 6, SWISH = x sigmoid(x) and MISH = x tanh(softplus(x))
+     * have a derivative that is no function of the output: they exist in the stand-alone activation node
+     * (bcnn_add_activation_layer) only, and every builder that takes a fused activation refuses them with
+     * BCNN_INVALID_PARAMETER. */
+    BCNN_ACT_RELU6, BCNN_ACT_HARD_SIGMOID, BCNN_ACT_HARD_SWISH, BCNN_ACT_SWISH, BCNN_ACT_MISH
 } bcnn_activation;
 
 typedef enum { BCNN_LOSS_EUCLIDEAN, BCNN_LOSS_LIFTED_STRUCT } bcnn_loss;
@@ -239,6 +250,17 @@ BCNN_API bcnn_status bcnn_add_avgpool_layer(bcnn_net *net, const char *src_id, c
 typedef enum { BCNN_POOL2D_MAX = 0, BCNN_POOL2D_AVG = 1 } bcnn_pool2d_kind;
 BCNN_API bcnn_status bcnn_add_pool2d_layer(bcnn_net *net, bcnn_pool2d_kind kind, int size, int stride, int pad,
                                            int ceil_mode, int count_include_pad, const char *src_id, const char *dst_id);
+/* New, without a reference counterpart: dst = src * gate, the last step of a squeeze-and-excitation block (Darknet's
+ * [scale_channels]) or, with a gate of src's shape, of a spatial attention module (Darknet's [sam]).
+ *   src is [N,C,H,W]; gate is [N,C,1,1] (one factor per plane) or [N,C,H,W] (the plain product); dst gets src's shape.
+ *   Backward: dsrc += ddst * gate and dgate += sum over the plane of ddst * src (elementwise for the same-shape gate);
+ *   both accumulate, and a source without a gradient buffer is skipped. The plane sums use no atomics: two runs give
+ *   the same bits.
+ * Refused with BCNN_INVALID_PARAMETER and a log line, nothing added to the net: an unknown src or gate name, a gate of
+ * any other shape. Works in TRAIN, VALID and PREDICT mode, has no weights (model files skip it) and follows
+ * bcnn_resize_net (dst is reshaped like src). */
+BCNN_API bcnn_status bcnn_add_scale_channels_layer(bcnn_net *net, const char *src_id, const char *gate_id,
+                                                   const char *dst_id);
 BCNN_API bcnn_status bcnn_add_concat_layer(bcnn_net *net, int num_src, char *const *src_ids, const char *dst_id);
 BCNN_API bcnn_status bcnn_add_eltwise_layer(bcnn_net *net, bcnn_activation activation, const char *src_id1,
                                             const char *src_id2, const char *dst_id);
@@ -296,6 +318,11 @@ BCNN_API int bcnn_get_node_tensor(bcnn_net *net, int node, int is_dst, int slot)
  * from (the reference's param->workspace: a fused-BN convolution's raw output / a batch-norm node's kept input);
  * returns a DEVICE pointer or NULL */
 BCNN_API void *bcnn_get_node_state(bcnn_net *net, int node, int which);
+/* On a stand-alone activation node, which = 0 is the input the last TRAIN forward kept (hard-swish / swish / mish; NULL for
+ * every other activation and in a net built in PREDICT mode).
+ * The node's bcnn_layer_type, and the bcnn_activation of a node that has one (-1: it has none, or `node` is out of range) */
+BCNN_API int bcnn_get_node_type(bcnn_net *net, int node);
+BCNN_API int bcnn_get_node_activation(bcnn_net *net, int node);
 /* Seed of the dropout masks (default 0). Node i of data-parallel rank r draws its mask from a Philox4x32-10 keyed by
  * (seed, i, r), counted by its TRAIN forwards (include/bcnn_hip.h): the same seed gives the same masks run after run.
  * Takes effect at the next TRAIN forward. */

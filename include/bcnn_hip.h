@@ -28,7 +28,12 @@ extern "C" {
 enum {
     BCNN_HIP_ACT_NONE = 0, BCNN_HIP_ACT_TANH, BCNN_HIP_ACT_RELU, BCNN_HIP_ACT_RAMP,
     BCNN_HIP_ACT_SOFTPLUS, BCNN_HIP_ACT_LRELU, BCNN_HIP_ACT_ABS, BCNN_HIP_ACT_CLAMP,
-    BCNN_HIP_ACT_PRELU, BCNN_HIP_ACT_LOGISTIC
+    BCNN_HIP_ACT_PRELU, BCNN_HIP_ACT_LOGISTIC,
+    /* appended, no reference counterpart. RELU6 / HARD_SIGMOID: derivative from the output, accepted by every `act`
+     * argument (always as a separate pass, like SOFTPLUS). HARD_SWISH / SWISH / MISH: derivative from the INPUT; forward
+     * through bcnn_hip_activation_forward[_keep], backward through bcnn_hip_activation_backward_from_input only; every
+     * other `act` argument handed one of them exits. */
+    BCNN_HIP_ACT_RELU6, BCNN_HIP_ACT_HARD_SIGMOID, BCNN_HIP_ACT_HARD_SWISH, BCNN_HIP_ACT_SWISH, BCNN_HIP_ACT_MISH
 };
 /* enum bcnn_mode values (inc/bcnn/bcnn.h:105-112) -- passed as int `mode`. */
 enum { BCNN_HIP_MODE_PREDICT = 0, BCNN_HIP_MODE_TRAIN = 1, BCNN_HIP_MODE_VALID = 2 };
@@ -131,6 +136,17 @@ void bcnn_hip_activation_forward(float *x_d, size_t size, int act, const float *
                                  int spatial, int channels);
 void bcnn_hip_activation_backward(const float *x_d, float *dx_d, size_t size, int act,
                                   const float *slopes_d, float *dslopes_d, int spatial, int channels);
+/* The self-gated activations (HARD_SWISH, SWISH, MISH; activation.hip), whose derivative needs the input.
+ *   forward_keep: one sweep; reads x_d once, stores the input into x_saved_d (may be NULL: nothing is stored) and f(x) in
+ *     place. 12 bytes per element with a saved copy, 8 without. Any other activation id is accepted too (its value is
+ *     that of bcnn_hip_activation_forward without slopes); PRELU exits.
+ *   backward_from_input: one sweep; dx_d *= f'(x_saved_d), 12 bytes per element. Only the three ids above (others exit).
+ *   hard_swish: f = (x min(max(x + 3, 0), 6)) / 6, f' = x < -3 ? 0 : x <= 3 ? x / 3 + 0.5 : 1 (torch's choices at the kinks).
+ *   swish: f = x s, f' = s (1 + x (1 - s)), s = 1 / (1 + exp(-x)) with exp evaluated in double like LOGISTIC.
+ *   mish: f = x tanh(softplus(x)), f' = t + x s (1 - t t), t = tanh(softplus(x)); evaluated in double, rounded once.
+ * 16-byte accesses where the bases allow (both bases 16-byte aligned), a scalar route otherwise and for the tail. */
+void bcnn_hip_activation_forward_keep(float *x_d, float *x_saved_d, size_t size, int act);
+void bcnn_hip_activation_backward_from_input(const float *x_saved_d, float *dx_d, size_t size, int act);
 
 /* ---------------------------------------------------------------------------------------------
  * Batch normalisation.  Replaces bcnn_forward/backward_batchnorm_gpu (bcnn_batchnorm_layer.cu:187-377);
@@ -394,6 +410,22 @@ void bcnn_hip_pool2d_forward(const bcnn_hip_pool2d_desc *desc, const float *x_d,
                              int h, int w);
 void bcnn_hip_pool2d_backward(const bcnn_hip_pool2d_desc *desc, const float *dy_d, const int *indexes_d, float *dx_d, int n,
                               int c, int h, int w, int overwrite);
+
+/* ---------------------------------------------------------------------------------------------
+ * Channel scaling (the scale-channels node; scale_channels.hip). No reference counterpart.
+ *   x is [n][c][hw]; gate is [n][c] (same_shape == 0: one factor per plane) or [n][c][hw] (same_shape != 0).
+ *   forward : y = x * gate, one multiply per element (8 bytes per element moved, 12 with a same-shape gate).
+ *   backward: ONE sweep over (x, dy[, gate]): dx += dy * gate, and dgate[n][c] += sum over the plane of dy * x
+ *     (dgate += dy * x elementwise for the same-shape gate). dx_d or dgate_d may be NULL: that half is skipped and what
+ *     only it needs is not read. The plane sums use no atomics: each plane is cut into a fixed number of slices by the
+ *     shape alone, a slice is summed by one wave or one workgroup in a fixed order, and the slice sums are added in
+ *     ascending order (in double) -- two runs give the same bits.
+ *   Tensors of 2^31 elements or more exit, like the other entry points handed a shape they cannot run.
+ * ------------------------------------------------------------------------------------------- */
+void bcnn_hip_scale_channels_forward(const float *x_d, const float *gate_d, float *y_d, int n, int c, int hw,
+                                     int same_shape);
+void bcnn_hip_scale_channels_backward(const float *x_d, const float *gate_d, const float *dy_d, float *dx_d,
+                                      float *dgate_d, int n, int c, int hw, int same_shape);
 
 /* ---------------------------------------------------------------------------------------------
  * Depthwise convolution.  Replaces the kernels of bcnn_depthwise_conv_layer.cu:33-200; CPU semantics
