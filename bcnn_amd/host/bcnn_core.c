@@ -502,138 +502,137 @@ static void relink_graph(bcnn_net *net) {
     hc->num_fill_chunks = -1;
 }
 
-/* Reference bcnn_net.c:287-335: new input extent (batch 1, like the reference's bcnn_set_input_shape(net, w, h, c, 1)), then
+/* ---- bcnn_resize_net --------------------------------------------------------------------------------------------------
+ * Reference bcnn_net.c:287-335: new input extent (batch 1, like the reference's bcnn_set_input_shape(net, w, h, c, 1)), then
  * the first destination tensor of every node re-shaped from its first source -- convolution and max-pooling by their output
  * rules, every other node as a copy of the source's shape -- and, with need_realloc, re-allocated (host and device mirrors).
  * In the reference, layer-private buffers (batch-norm workspaces, pooling indexes) keep the size they were built with, so a
- * net resized to a LARGER extent -- the usual detection use of this call -- overruns them (there: host heap; here it
- * would be device memory). Deliberate deviation: with need_realloc the private buffers whose size follows a dst tensor
- * (pooling indexes and kept maxima, the batch-norm workspaces of convolution and batch-norm nodes) are re-allocated for the
- * new shape as well; without it, a shape that outgrew them is refused (BCNN_INVALID_PARAMETER) instead of corrupting memory.
- * What this build derives from shapes (the conv scratch, the node-to-node links and their sums buffers) is brought up to
- * date before returning; the reference's function falls off its end without a return value, here the status is BCNN_SUCCESS. */
-static bcnn_status resize_private_f32(float **buf, size_t old_elems, size_t new_elems, int need_realloc) {
-    if (!*buf || new_elems <= old_elems) return BCNN_SUCCESS;
-    if (!need_realloc) return BCNN_INVALID_PARAMETER;
+ * net resized to a LARGER extent -- the usual detection use of this call -- overruns them. Deliberate deviation, one rule
+ * for every such buffer (bcnn_reserve_device): a shape within the capacity it was allocated with allocates nothing, whatever
+ * the shapes in between were; past it the buffer grows with need_realloc and the call is refused (BCNN_INVALID_PARAMETER)
+ * without. Whether a TENSOR's own allocation holds the new shape stays the caller's contract: bcnn_tensor has no capacity.
+ * Two passes. resize_plan only reads and finds every refusal (an unsupported node, a pool2d source smaller than its window,
+ * a buffer too small): a refused call leaves the net, its tensors, batch_size and every buffer exactly as they were.
+ * resize_commit cannot refuse, only run out of memory: after BCNN_FAILED_ALLOC the net is fit for bcnn_end_net alone. Then
+ * what this build derives from shapes (the conv scratch, the links and their sums buffers) is brought up to date; the
+ * reference's function falls off its end without a return value, here the status is BCNN_SUCCESS. */
+bcnn_status bcnn_reserve_device(void **buf, size_t *capacity, size_t elems, size_t elem_size, int may_grow) {
+    if (!*buf || elems <= *capacity) return BCNN_SUCCESS;
+    if (!may_grow) return BCNN_INVALID_PARAMETER;
     bcnn_hip_sync();
     bcnn_hip_free(*buf);
-    *buf = bcnn_hip_malloc_f32(new_elems);
+    *buf = bcnn_hip_malloc_f32((elems * elem_size + sizeof(float) - 1) / sizeof(float));
+    *capacity = *buf ? elems : 0;
     return *buf ? BCNN_SUCCESS : BCNN_FAILED_ALLOC;
 }
 
-/* the walk of bcnn_resize_net; *saved_input_node: the hard-swish / swish / mish node whose saved-input buffer refused, if any */
-static bcnn_status resize_walk(bcnn_net *net, int w, int h, int c, int need_realloc, int *saved_input_node) {
+/* every private device buffer of a node that follows its first dst tensor, made to hold `elems` elements */
+static bcnn_status node_reserve_buffers(const bcnn_node *nd, size_t elems, int may_grow) {
+#define RESERVE(T, buf, cap) \
+    bcnn_reserve_device((void **)&((T *)nd->param)->buf, &((T *)nd->param)->cap, elems, sizeof(*((T *)nd->param)->buf), may_grow)
+    switch (nd->type) {
+        case BCNN_LAYER_CONV2D: return RESERVE(bcnn_conv_param, bn_workspace_gpu, bn_workspace_capacity);
+        case BCNN_LAYER_BATCHNORM: return RESERVE(bcnn_batchnorm_param, workspace_gpu, workspace_capacity);
+        case BCNN_LAYER_POOL2D: return RESERVE(bcnn_pool2d_param, indexes_gpu, indexes_capacity);
+        case BCNN_LAYER_ACTIVATION: return RESERVE(bcnn_activation_param, x_saved_gpu, x_saved_capacity);
+        case BCNN_LAYER_MAXPOOL:
+            BCNN_CHECK_STATUS(RESERVE(bcnn_maxpool_param, indexes_gpu, indexes_capacity));
+            return RESERVE(bcnn_maxpool_param, raw_at_max_gpu, raw_at_max_capacity);
+        default: return BCNN_SUCCESS;
+    }
+#undef RESERVE
+}
+
+/* in-place nodes whose tensor is re-shaped (and re-allocated) by its producer alone */
+static int keeps_producer_shape(const bcnn_node *nd) {
+    return nd->type == BCNN_LAYER_DROPOUT ||
+           (nd->type == BCNN_LAYER_ACTIVATION && bcnn_act_needs_input(((const bcnn_activation_param *)nd->param)->activation));
+}
+
+/* gives d, a node's first dst tensor, its shape for the first source s (d may be s); 0, d untouched: the node refuses s */
+static int node_dst_shape(const bcnn_node *nd, const bcnn_tensor *s, bcnn_tensor *d) {
+    int oc = s->c, oh = s->h, ow = s->w;
+    if (nd->type == BCNN_LAYER_CONV2D) {
+        const bcnn_conv_param *p = (const bcnn_conv_param *)nd->param;
+        oc = p->num;
+        oh = (s->h + 2 * p->pad - p->size) / p->stride + 1;
+        ow = (s->w + 2 * p->pad - p->size) / p->stride + 1;
+    } else if (nd->type == BCNN_LAYER_MAXPOOL) {
+        const bcnn_maxpool_param *p = (const bcnn_maxpool_param *)nd->param;
+        oh = (s->h - 1) / p->stride + 1;
+        ow = (s->w - 1) / p->stride + 1;
+    } else if (nd->type == BCNN_LAYER_POOL2D) {
+        if (!bcnn_pool2d_out_extents((const bcnn_pool2d_param *)nd->param, s->h, s->w, &oh, &ow)) return 0;
+    }
+    bcnn_tensor_set_shape(d, s->n, oc, oh, ow, 1);
+    return 1;
+}
+
+/* reads the net only; plan: a scratch copy of its tensors that takes the new shapes (no pointer of a copy is followed) */
+static bcnn_status resize_plan(bcnn_net *net, int w, int h, int c, int need_realloc, bcnn_tensor *plan) {
+    for (int i = 0; i < net->num_nodes; ++i) {
+        /* The reference gives every node type other than convolution and max-pooling its source's shape, which is wrong for
+         * upsample (scaled extent), concat (summed depth) and deconvolution (scaled extent, own depth); nor would the
+         * [n][c][1][1] embedding the lifted-structure loss was built on (and its label) survive the call. */
+        const bcnn_layer_type t = net->nodes[i].type;
+        BCNN_CHECK_AND_LOG(net->log_ctx, t != BCNN_LAYER_CONCAT && t != BCNN_LAYER_UPSAMPLE && t != BCNN_LAYER_YOLOV3 &&
+                                             t != BCNN_LAYER_TRANSPOSE_CONV2D, BCNN_INVALID_PARAMETER,
+                           "bcnn_resize_net: node %d is a concat / upsample / YOLO / deconvolution node, whose resize is "
+                           "not supported\n", i);
+        BCNN_CHECK_AND_LOG(net->log_ctx,
+                           t != BCNN_LAYER_COST || ((const bcnn_cost_param *)net->nodes[i].param)->loss != BCNN_LOSS_LIFTED_STRUCT,
+                           BCNN_INVALID_PARAMETER,
+                           "bcnn_resize_net: node %d is a lifted-structure cost node, whose resize is not supported\n", i);
+    }
+    memcpy(plan, net->tensors, (size_t)net->num_tensors * sizeof(*plan));
+    bcnn_tensor_set_shape(&plan[0], 1, c, h, w, 0);
+    for (int i = 0; i < net->num_nodes; ++i) {
+        const bcnn_node *nd = &net->nodes[i];
+        if (nd->num_src < 1 || nd->num_dst < 1) continue;
+        const bcnn_tensor *s = &plan[nd->src[0]];
+        bcnn_tensor *d = &plan[nd->dst[0]];
+        BCNN_CHECK_AND_LOG(net->log_ctx, keeps_producer_shape(nd) || node_dst_shape(nd, s, d), BCNN_INVALID_PARAMETER,
+                           "bcnn_resize_net: node %d pools a %d x %d tensor, smaller than its padded window\n", i, s->w, s->h);
+        BCNN_CHECK_AND_LOG(net->log_ctx, need_realloc || node_reserve_buffers(nd, (size_t)bcnn_tensor_size(d), 0) == BCNN_SUCCESS,
+                           BCNN_INVALID_PARAMETER,
+                           "bcnn_resize_net: node %d keeps a buffer for the backward pass that is smaller than the new shape; "
+                           "call with need_realloc\n", i);
+    }
+    return BCNN_SUCCESS;
+}
+
+/* the plan carried out on the tensors themselves, by the same two functions; BCNN_FAILED_ALLOC is the only error */
+static bcnn_status resize_commit(bcnn_net *net, int w, int h, int c, int need_realloc) {
     bcnn_set_input_shape(net, w, h, c, 1);
     for (int i = 0; i < net->num_nodes; ++i) {
-        bcnn_node *nd = &net->nodes[i];
+        const bcnn_node *nd = &net->nodes[i];
         if (nd->num_src < 1 || nd->num_dst < 1) continue;
-        if (nd->type == BCNN_LAYER_DROPOUT) continue; /* in place: its tensor was re-shaped by its producer */
-        if (nd->type == BCNN_LAYER_ACTIVATION && bcnn_act_needs_input(((bcnn_activation_param *)nd->param)->activation)) {
-            /* in place as well; its saved input follows the tensor by capacity, like the pool2d indexes below */
-            const bcnn_status st = bcnn_activation_reserve_saved((bcnn_activation_param *)nd->param,
-                                                                 (size_t)bcnn_tensor_size(&net->tensors[nd->dst[0]]), need_realloc);
-            if (st != BCNN_SUCCESS) *saved_input_node = i;
-            BCNN_CHECK_STATUS(st);
-            continue;
-        }
-        const bcnn_tensor *s = &net->tensors[nd->src[0]];
         bcnn_tensor *d = &net->tensors[nd->dst[0]];
-        const size_t old_elems = (size_t)bcnn_tensor_size(d);
-        if (nd->type == BCNN_LAYER_CONV2D) {
-            const bcnn_conv_param *p = (const bcnn_conv_param *)nd->param;
-            bcnn_tensor_set_shape(d, s->n, p->num, (s->h + 2 * p->pad - p->size) / p->stride + 1,
-                                  (s->w + 2 * p->pad - p->size) / p->stride + 1, 1);
-        } else if (nd->type == BCNN_LAYER_MAXPOOL) {
-            const bcnn_maxpool_param *p = (const bcnn_maxpool_param *)nd->param;
-            bcnn_tensor_set_shape(d, s->n, s->c, (s->h - 1) / p->stride + 1, (s->w - 1) / p->stride + 1, 1);
-        } else if (nd->type == BCNN_LAYER_POOL2D) {
-            int oh = 0, ow = 0;
-            BCNN_CHECK_AND_LOG(net->log_ctx, bcnn_pool2d_out_extents((const bcnn_pool2d_param *)nd->param, s->h, s->w, &oh, &ow),
-                               BCNN_INVALID_PARAMETER,
-                               "bcnn_resize_net: node %d pools a %d x %d tensor, smaller than its padded window\n", i, s->w, s->h);
-            bcnn_tensor_set_shape(d, s->n, s->c, oh, ow, 1);
-        } else {
-            bcnn_tensor_set_shape(d, s->n, s->c, s->h, s->w, 1);
+        if (!keeps_producer_shape(nd)) {
+            node_dst_shape(nd, &net->tensors[nd->src[0]], d);
+            if (need_realloc && bcnn_tensor_allocate(d, net->mode) != BCNN_SUCCESS) return BCNN_FAILED_ALLOC;
         }
-        if (need_realloc) BCNN_CHECK_STATUS(bcnn_tensor_allocate(d, net->mode));
-        const size_t new_elems = (size_t)bcnn_tensor_size(d);
-        if (nd->type == BCNN_LAYER_CONV2D) {
-            bcnn_conv_param *p = (bcnn_conv_param *)nd->param;
-            BCNN_CHECK_STATUS(resize_private_f32(&p->bn_workspace_gpu, old_elems, new_elems, need_realloc));
-            BCNN_CHECK_STATUS(resize_private_f32(&p->x_norm_gpu, old_elems, new_elems, need_realloc));
-        } else if (nd->type == BCNN_LAYER_BATCHNORM) {
-            bcnn_batchnorm_param *p = (bcnn_batchnorm_param *)nd->param;
-            BCNN_CHECK_STATUS(resize_private_f32(&p->workspace_gpu, old_elems, new_elems, need_realloc));
-            BCNN_CHECK_STATUS(resize_private_f32(&p->x_norm_gpu, old_elems, new_elems, need_realloc));
-        } else if (nd->type == BCNN_LAYER_POOL2D) {
-            /* by capacity: after a shrink, growing back to a size the buffer already holds allocates nothing, and growing
-             * past it is never missed because the shape before happened to be larger than the buffer */
-            BCNN_CHECK_STATUS(bcnn_pool2d_reserve_indexes((bcnn_pool2d_param *)nd->param, new_elems, need_realloc));
-        } else if (nd->type == BCNN_LAYER_MAXPOOL && new_elems > old_elems) {
+        if (!need_realloc) continue; /* the plan found every buffer large enough */
+        if (node_reserve_buffers(nd, (size_t)bcnn_tensor_size(d), 1) != BCNN_SUCCESS) return BCNN_FAILED_ALLOC;
+        if (nd->type == BCNN_LAYER_MAXPOOL) { /* the reference's host copy of the indexes follows the device one */
             bcnn_maxpool_param *p = (bcnn_maxpool_param *)nd->param;
-            if (!need_realloc) return BCNN_INVALID_PARAMETER;
-            bcnn_hip_sync();
-            bcnn_hip_free(p->indexes_gpu);
-            p->indexes_gpu = bcnn_hip_malloc_i32(new_elems);
-            int *host = (int *)realloc(p->indexes, new_elems * sizeof(int));
-            if (!host || !p->indexes_gpu) return BCNN_FAILED_ALLOC;
+            int *host = (int *)realloc(p->indexes, p->indexes_capacity * sizeof(int));
+            if (!host) return BCNN_FAILED_ALLOC;
             p->indexes = host;
-            if (p->raw_at_max_gpu) { /* re-made by bcnn_link_conv_maxpool for the new shape */
-                bcnn_hip_free(p->raw_at_max_gpu);
-                p->raw_at_max_gpu = NULL;
-            }
         }
     }
     return BCNN_SUCCESS;
 }
 
 bcnn_status bcnn_resize_net(bcnn_net *net, int w, int h, int c, int need_realloc) {
-    if (!net || w <= 0 || h <= 0 || c <= 0) return BCNN_INVALID_PARAMETER;
-    /* The reference gives every node type other than convolution and max-pooling its source's shape, which is wrong for
-     * upsample (scaled extent), concat (summed depth) and deconvolution (scaled extent, own depth). Such graphs are
-     * refused before any shape changes. */
-    for (int i = 0; i < net->num_nodes; ++i) {
-        const bcnn_layer_type t = net->nodes[i].type;
-        BCNN_CHECK_AND_LOG(net->log_ctx, t != BCNN_LAYER_CONCAT && t != BCNN_LAYER_UPSAMPLE && t != BCNN_LAYER_YOLOV3 &&
-                                             t != BCNN_LAYER_TRANSPOSE_CONV2D,
-                           BCNN_INVALID_PARAMETER,
-                           "bcnn_resize_net: node %d is a concat / upsample / YOLO / deconvolution node, whose resize is "
-                           "not supported\n", i);
-        /* every node but convolution and max-pooling takes its source's shape below, so the [n][c][1][1] embedding the
-         * lifted-structure loss was built on (and its label) would not survive the call */
-        BCNN_CHECK_AND_LOG(net->log_ctx,
-                           t != BCNN_LAYER_COST || ((const bcnn_cost_param *)net->nodes[i].param)->loss != BCNN_LOSS_LIFTED_STRUCT,
-                           BCNN_INVALID_PARAMETER,
-                           "bcnn_resize_net: node %d is a lifted-structure cost node, whose resize is not supported\n", i);
-    }
-    /* Without need_realloc nothing is allocated, so the shapes are all the walk changes: kept to put them back when a
-     * hard-swish / swish / mish node's saved-input buffer turns out too small -- that refusal leaves the net as it was. */
-    int *old_shapes = NULL;
-    const int old_batch = net->batch_size;
-    if (!need_realloc) {
-        old_shapes = (int *)malloc(((size_t)net->num_tensors + 1) * 5 * sizeof(int));
-        if (!old_shapes) return BCNN_FAILED_ALLOC;
-        for (int t = 0; t < net->num_tensors; ++t) {
-            const bcnn_tensor *x = &net->tensors[t];
-            old_shapes[5 * t] = x->n; old_shapes[5 * t + 1] = x->c; old_shapes[5 * t + 2] = x->h; old_shapes[5 * t + 3] = x->w;
-            old_shapes[5 * t + 4] = x->has_grad;
-        }
-    }
-    int saved_input_node = -1;
-    const bcnn_status st = resize_walk(net, w, h, c, need_realloc, &saved_input_node);
-    if (saved_input_node >= 0 && old_shapes) {
-        for (int t = 0; t < net->num_tensors; ++t)
-            bcnn_tensor_set_shape(&net->tensors[t], old_shapes[5 * t], old_shapes[5 * t + 1], old_shapes[5 * t + 2],
-                                  old_shapes[5 * t + 3], old_shapes[5 * t + 4]);
-        net->batch_size = old_batch;
-        bcnn_log(net->log_ctx, BCNN_LOG_ERROR,
-                 "bcnn_resize_net: node %d keeps its input for the backward pass and its buffer is smaller than the new shape; "
-                 "call with need_realloc\n", saved_input_node);
-    }
-    free(old_shapes);
-    BCNN_CHECK_STATUS(st);
-    if (hctx(net)->compiled) return bcnn_compile_net(net); /* input tensor, conv scratch, links */
-    return BCNN_SUCCESS;
+    if (!net || net->num_tensors < 1 || w <= 0 || h <= 0 || c <= 0) return BCNN_INVALID_PARAMETER;
+    bcnn_tensor *plan = (bcnn_tensor *)malloc((size_t)net->num_tensors * sizeof(*plan));
+    if (!plan) return BCNN_FAILED_ALLOC;
+    const bcnn_status planned = resize_plan(net, w, h, c, need_realloc, plan);
+    free(plan);
+    BCNN_CHECK_STATUS(planned);
+    BCNN_CHECK_STATUS(resize_commit(net, w, h, c, need_realloc));
+    return hctx(net)->compiled ? bcnn_compile_net(net) : BCNN_SUCCESS; /* input tensor, conv scratch, links */
 }
 
 bcnn_status bcnn_set_mode(bcnn_net *net, bcnn_mode mode) {

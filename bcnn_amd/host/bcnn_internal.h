@@ -230,6 +230,12 @@ void bcnn_tensor_destroy(bcnn_tensor *t);
 void bcnn_tensor_set_shape(bcnn_tensor *t, int n, int c, int h, int w, int has_grad);
 bcnn_status bcnn_tensor_allocate_buffer(bcnn_tensor *t, int net_state, size_t size);
 bcnn_status bcnn_tensor_allocate(bcnn_tensor *t, int net_state);
+/* The one rule for a layer's private device buffer whose size follows a tensor (bcnn_resize_net): `*capacity` is the number
+ * of elements `*buf` was allocated with, set wherever the buffer is made. A NULL buffer stays NULL (PREDICT-built nets,
+ * average pooling) and `elems <= *capacity` touches nothing: both BCNN_SUCCESS. Past the capacity: BCNN_INVALID_PARAMETER
+ * with nothing touched when !may_grow; else the buffer is re-made (zero-filled) for `elems` elements of `elem_size` bytes, or
+ * left NULL with capacity 0 and BCNN_FAILED_ALLOC. */
+bcnn_status bcnn_reserve_device(void **buf, size_t *capacity, size_t elems, size_t elem_size, int may_grow);
 void bcnn_tensor_free(bcnn_tensor *t);
 int bcnn_tensor_size(const bcnn_tensor *t);
 int bcnn_tensor_size3d(const bcnn_tensor *t);
@@ -291,7 +297,8 @@ typedef struct bcnn_conv_param {
 #ifdef BCNN_USE_HIP
     float *conv_workspace_gpu;  /* = net hip_ctx workspace (dW split-K partials) */
     float *bn_workspace_gpu;    /* pre-normalisation conv output, kept for backward */
-    float *x_norm_gpu;          /* NULL: recomputed in backward */
+    size_t bn_workspace_capacity; /* floats allocated (bcnn_reserve_device) */
+    float *x_norm_gpu;          /* never allocated: recomputed in backward */
     float *adam_m_gpu, *adam_v_gpu; /* weight moments, allocated by the first Adam step */
     /* set by bcnn_compile_net when the node that follows is an eltwise node adding something to this node's (batch-norm,
      * no activation) output (bcnn_link_conv_eltwise): inside a whole pass the eltwise work rides on this node's
@@ -347,7 +354,8 @@ typedef struct bcnn_batchnorm_param {
     float *x_norm;
 #ifdef BCNN_USE_HIP
     float *workspace_gpu;
-    float *x_norm_gpu;
+    size_t workspace_capacity; /* floats allocated (bcnn_reserve_device); 0 while bcnn_link_depthwise_batchnorm keeps no copy */
+    float *x_norm_gpu;   /* never allocated: recomputed in backward */
     int dw_node;         /* the depthwise node that produces this node's input (see bcnn_depthwise_conv_param), -1: none */
     int dw_fused_bwd;    /* that node applies this node's backward to the gradient it consumes */
     int sums_conv;       /* the 1x1 convolution node that is this node's only consumer: inside a backward pass its
@@ -370,9 +378,11 @@ typedef struct bcnn_maxpool_param {
     int *indexes;
 #ifdef BCNN_USE_HIP
     int *indexes_gpu;
+    size_t indexes_capacity; /* elements allocated, of indexes_gpu and of the host `indexes` (bcnn_reserve_device) */
     int conv_node;  /* the convolution node whose batch-norm this node applies on the fly (see bcnn_conv_param), -1: none */
     float *raw_at_max_gpu; /* conv_node >= 0: per pooled element the pre-normalisation value that won its window, kept by
                             * the forward pass for bcnn_hip_maxpool_bn_backward (the output tensor's shape) */
+    size_t raw_at_max_capacity; /* floats allocated: bcnn_link_conv_maxpool makes it as large as the indexes */
     int raw_fwd;    /* the running pass's forward took that route (raw_at_max_gpu is current) */
 #endif
 } bcnn_maxpool_param;
@@ -381,7 +391,7 @@ typedef struct bcnn_activation_param {
     bcnn_activation activation;
 #ifdef BCNN_USE_HIP
     float *x_saved_gpu;       /* hard-swish / swish / mish, nets built in TRAIN / VALID mode: the input of the last TRAIN forward */
-    size_t x_saved_capacity;  /* elements allocated; bcnn_resize_net grows the buffer past this, not past the last shape */
+    size_t x_saved_capacity;  /* floats allocated (bcnn_reserve_device) */
 #endif
 } bcnn_activation_param;
 
@@ -458,7 +468,7 @@ typedef struct bcnn_pool2d_param {
     int size, stride, pad, ceil_mode, count_include_pad;
 #ifdef BCNN_USE_HIP
     int *indexes_gpu;        /* max, nets built in TRAIN / VALID mode: the winner of every window (the output's shape) */
-    size_t indexes_capacity; /* elements allocated; bcnn_resize_net grows the buffer past this, not past the last shape */
+    size_t indexes_capacity; /* elements allocated (bcnn_reserve_device) */
 #endif
 } bcnn_pool2d_param;
 
@@ -547,16 +557,11 @@ uint64_t bcnn_dropout_key(uint64_t seed, int node, int rank);
 void bcnn_forward_scale_channels_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_scale_channels_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_activation_layer(bcnn_node *node);
-/* bcnn_resize_net: makes a hard-swish / swish / mish node's saved-input buffer hold `elems` floats (no-op for every other
- * activation and for PREDICT-built nets); without need_realloc a size past the capacity is BCNN_INVALID_PARAMETER */
-bcnn_status bcnn_activation_reserve_saved(bcnn_activation_param *p, size_t elems, int need_realloc);
 void bcnn_forward_pool2d_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_pool2d_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_pool2d_layer(bcnn_node *node);
 /* bcnn_layers_pool2d.c: the node's output extents for an h x w source; 0 if the parameters refuse that source */
 int bcnn_pool2d_out_extents(const bcnn_pool2d_param *p, int h, int w, int *out_h, int *out_w);
-/* bcnn_resize_net: makes the index buffer hold `elems` winners (no-op for average pooling and PREDICT-built nets) */
-bcnn_status bcnn_pool2d_reserve_indexes(bcnn_pool2d_param *p, size_t elems, int need_realloc);
 
 /* SGD step on one node's parameters (bcnn_learner.c:67-104 in the reference) */
 void bcnn_link_depthwise_batchnorm(bcnn_net *net); /* bcnn_layers_hot.c; called by bcnn_compile_net */

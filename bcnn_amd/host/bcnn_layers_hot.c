@@ -129,8 +129,10 @@ bcnn_status bcnn_add_convolutional_layer(bcnn_net *net, int num_filters, int siz
         /* scales accumulate a gradient but no update function ever applies it (reference
          * bcnn_conv_layer.c:810-855 updates weights and biases only) -- kept out of the arena */
         BCNN_CHECK_STATUS(add_vector_param(net, &node, num_filters, 1, src_id, "scales", 1.0f, 0));
-        if (net->mode != BCNN_MODE_PREDICT)
-            param->bn_workspace_gpu = bcnn_hip_malloc_f32((size_t)sn * num_filters * oh * ow);
+        if (net->mode != BCNN_MODE_PREDICT) {
+            param->bn_workspace_capacity = (size_t)sn * num_filters * oh * ow;
+            param->bn_workspace_gpu = bcnn_hip_malloc_f32(param->bn_workspace_capacity);
+        }
     }
     if (activation == BCNN_ACT_PRELU)
         BCNN_CHECK_STATUS(add_vector_param(net, &node, num_filters, 0, src_id, "prelu_slopes", 0.0f, 0));
@@ -517,7 +519,10 @@ bcnn_status bcnn_add_batchnorm_layer(bcnn_net *net, const char *src_id, const ch
     BCNN_CHECK_STATUS(add_vector_param(net, &node, s.c, 0, src_id, "run_var", 0.0f, 0));
     BCNN_CHECK_STATUS(add_vector_param(net, &node, s.c, 1, src_id, "scales", 1.0f, 0));
     BCNN_CHECK_STATUS(add_vector_param(net, &node, s.c, 1, src_id, "b", 0.0f, 0));
-    if (net->mode != BCNN_MODE_PREDICT) param->workspace_gpu = bcnn_hip_malloc_f32((size_t)bcnn_tensor_size(&s));
+    if (net->mode != BCNN_MODE_PREDICT) {
+        param->workspace_capacity = (size_t)bcnn_tensor_size(&s);
+        param->workspace_gpu = bcnn_hip_malloc_f32(param->workspace_capacity);
+    }
     BCNN_CHECK_STATUS(bcnn_net_add_node(net, node));
     BCNN_INFO(net->log_ctx, "[Batchnorm] %-8s (%4d x%4d x%4d) -> %-8s\n", src_id, s.w, s.h, s.c, dst_id);
     return BCNN_SUCCESS;
@@ -672,7 +677,12 @@ void bcnn_link_conv_maxpool(bcnn_net *net) {
             continue;
         cp->pool_node = m;
         mp->conv_node = m - 1;
-        if (!mp->raw_at_max_gpu) mp->raw_at_max_gpu = bcnn_hip_malloc_f32((size_t)bcnn_tensor_size(py));
+        /* as large as the indexes, not as the pooled tensor happens to be now: a net resized below its built shape and
+         * compiled there may grow back to what the indexes hold without a re-allocation (bcnn_resize_net) */
+        if (!mp->raw_at_max_gpu) {
+            mp->raw_at_max_capacity = mp->indexes_capacity;
+            mp->raw_at_max_gpu = bcnn_hip_malloc_f32(mp->raw_at_max_capacity);
+        }
     }
 }
 
@@ -896,8 +906,11 @@ void bcnn_link_depthwise_batchnorm(bcnn_net *net) {
             bcnn_hip_sync();
             bcnn_hip_free(bp->workspace_gpu);
             bp->workspace_gpu = NULL;
+            bp->workspace_capacity = 0;
         } else if (!private_input && !bp->workspace_gpu && net->mode != BCNN_MODE_PREDICT) {
-            bp->workspace_gpu = bcnn_hip_malloc_f32((size_t)bcnn_tensor_size(&net->tensors[t]));
+            /* for the shape of now: bcnn_resize_net takes a later grow past it for what it is, by this capacity */
+            bp->workspace_capacity = (size_t)bcnn_tensor_size(&net->tensors[t]);
+            bp->workspace_gpu = bcnn_hip_malloc_f32(bp->workspace_capacity);
         }
         if (producer != j - 1 || writers != 1 || net->nodes[producer].type != BCNN_LAYER_DEPTHWISE_CONV2D) continue;
         bcnn_node *dw = &net->nodes[producer];
@@ -963,9 +976,9 @@ bcnn_status bcnn_add_maxpool_layer(bcnn_net *net, int size, int stride, bcnn_pad
     node.param = param;
     param->size = size; param->stride = stride; param->padding = padding;
     param->conv_node = -1;
-    const size_t sz = (size_t)s.n * s.c * oh * ow;
-    param->indexes = (int *)calloc(sz, sizeof(int));
-    param->indexes_gpu = bcnn_hip_malloc_i32(sz);
+    param->indexes_capacity = (size_t)s.n * s.c * oh * ow;
+    param->indexes = (int *)calloc(param->indexes_capacity, sizeof(int));
+    param->indexes_gpu = bcnn_hip_malloc_i32(param->indexes_capacity);
     node.forward = bcnn_forward_maxpool_layer;
     node.backward = bcnn_backward_maxpool_layer;
     node.release_param = bcnn_release_param_maxpool_layer;
@@ -1117,16 +1130,6 @@ void bcnn_backward_activation_layer(bcnn_net *net, bcnn_node *node) {
 void bcnn_release_param_activation_layer(bcnn_node *node) {
     bcnn_activation_param *p = (bcnn_activation_param *)node->param;
     bcnn_hip_free(p->x_saved_gpu);
-}
-
-bcnn_status bcnn_activation_reserve_saved(bcnn_activation_param *p, size_t elems, int need_realloc) {
-    if (!p->x_saved_gpu || elems <= p->x_saved_capacity) return BCNN_SUCCESS;
-    if (!need_realloc) return BCNN_INVALID_PARAMETER;
-    bcnn_hip_sync();
-    bcnn_hip_free(p->x_saved_gpu);
-    p->x_saved_gpu = bcnn_hip_malloc_f32(elems);
-    p->x_saved_capacity = p->x_saved_gpu ? elems : 0;
-    return p->x_saved_gpu ? BCNN_SUCCESS : BCNN_FAILED_ALLOC;
 }
 
 void bcnn_update_activation_layer(bcnn_net *net, bcnn_node *node) {

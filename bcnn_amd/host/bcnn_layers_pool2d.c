@@ -1,7 +1,7 @@
 /*
  * bcnn_layers_pool2d.c -- the pool2d node: max or average pooling over a square window with the same padding on all four
- * sides (torch.nn.functional.max_pool2d / avg_pool2d, i.e. Caffe's rules). Builder, node workers, release and the two
- * helpers bcnn_resize_net uses. One whole-batch call into the C-ABI per direction (pool2d.hip).
+ * sides (torch.nn.functional.max_pool2d / avg_pool2d, i.e. Caffe's rules). Builder, node workers, release and the
+ * output-extent rule bcnn_resize_net uses. One whole-batch call into the C-ABI per direction (pool2d.hip).
  *
  * No reference counterpart: the reference's max pooling pads at the bottom / right only and its average pooling is
  * global; those two nodes (bcnn_layers_hot.c) keep their code, their dispatch and their fusions with the convolution and
@@ -32,16 +32,6 @@ int bcnn_pool2d_out_extents(const bcnn_pool2d_param *p, int h, int w, int *out_h
     *out_h = bcnn_hip_pool2d_out_extent(&d, h);
     *out_w = bcnn_hip_pool2d_out_extent(&d, w);
     return *out_h > 0 && *out_w > 0;
-}
-
-bcnn_status bcnn_pool2d_reserve_indexes(bcnn_pool2d_param *p, size_t elems, int need_realloc) {
-    if (!p->indexes_gpu || elems <= p->indexes_capacity) return BCNN_SUCCESS;
-    if (!need_realloc) return BCNN_INVALID_PARAMETER;
-    bcnn_hip_sync();
-    bcnn_hip_free(p->indexes_gpu);
-    p->indexes_gpu = bcnn_hip_malloc_i32(elems);
-    p->indexes_capacity = p->indexes_gpu ? elems : 0;
-    return p->indexes_gpu ? BCNN_SUCCESS : BCNN_FAILED_ALLOC;
 }
 
 bcnn_status bcnn_add_pool2d_layer(bcnn_net *net, bcnn_pool2d_kind kind, int size, int stride, int pad, int ceil_mode,

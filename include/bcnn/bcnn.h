@@ -129,6 +129,11 @@ BCNN_API int bcnn_get_num_threads(bcnn_net *net);
 BCNN_API void bcnn_set_input_shape(bcnn_net *net, int width, int height, int channels, int batch_size);
 BCNN_API bcnn_status bcnn_add_input(bcnn_net *net, int width, int height, int channels, const char *name);
 BCNN_API int bcnn_get_batch_size(bcnn_net *net);
+/* New input extent at batch 1; every node's first destination tensor is re-shaped and, with need_realloc, re-allocated.
+ * A layer's private buffers (batch-norm workspaces, pooling indexes, saved activation inputs) follow by their allocated
+ * capacity: a shape within it allocates nothing; past it they grow with need_realloc and the call is refused without.
+ * Every refusal (BCNN_INVALID_PARAMETER) is found before anything changes: the net is left exactly as it was.
+ * After BCNN_FAILED_ALLOC the net is only fit for bcnn_end_net. */
 BCNN_API bcnn_status bcnn_resize_net(bcnn_net *net, int w, int h, int c, int need_realloc);
 BCNN_API bcnn_status bcnn_compile_net(bcnn_net *net);
 BCNN_API bcnn_status bcnn_load_weights(bcnn_net *net, const char *model_path);

@@ -393,7 +393,13 @@ def test_resize_shrinks_and_grows_both_kinds():
             net.backward()
             net.sync()
     # a 1 x 1 input leaves the last node (2 x 2 window, no padding) a 1 x 1 source: refused, BCNN_INVALID_PARAMETER
+    shapes = [net.shape(0)] + [net.shape(net.node_dst(node)) for node in range(len(specs))]
     assert net.resize(1, 1, 3) == 1
+    # found at the last node, with need_realloc: the nodes in front of it were not resized on the way there
+    assert [net.shape(0)] + [net.shape(net.node_dst(node)) for node in range(len(specs))] == shapes
+    assert net.L.bcnn_get_batch_size(net.net) == 1
+    _feed_and_forward(net, 5)
+    _check_nodes_against_torch(net, specs)
     net.close()
 
 

@@ -505,10 +505,18 @@ def test_predict_forward_has_train_bits_and_keeps_nothing(sam):
 
 
 def test_resize_follows_the_saved_input_capacity():
+    _resize_follows_the_capacity(bn=0)
+
+
+def test_resize_follows_the_capacity_behind_a_fused_batchnorm():
+    _resize_follows_the_capacity(bn=1)
+
+
+def _resize_follows_the_capacity(bn):
     from bcnn_amd import capi
-    # no fc (its weights are tied to the extent), no fused batch-norm (its workspace refuses first, in the middle of the walk)
-    # and no global avgpool (bcnn_resize_net gives its output the source's extent, as the reference does)
-    kw = dict(act1=capi.ACT_MISH, gate_act=capi.ACT_LOGISTIC, head=False, bn=0, sam=True)
+    # no fc (its weights are tied to the extent) and no global avgpool (bcnn_resize_net gives its output the source's extent,
+    # as the reference does); bn=1: the fused batch-norm's workspace sits in front of the saved input and follows the same rule
+    kw = dict(act1=capi.ACT_MISH, gate_act=capi.ACT_LOGISTIC, head=False, bn=bn, sam=True)
     net, (n_act, _) = _new_net(capi.MODE_TRAIN, shape=(2, 3, 12, 12), **kw)
     shapes = [net.shape(k) for k in range(_num_tensors(net))]
     # 1 x 16 x 20 x 20 > 2 x 16 x 12 x 12: refused without need_realloc, and nothing has changed
