@@ -89,6 +89,13 @@ struct KTimer {
 extern thread_local bool g_trace_on;
 void trace_kernel_slow(const char* name);
 inline void trace_kernel(const char* name) { if (g_trace_on) trace_kernel_slow(name); }
+// a name that ends in a count the host chose, e.g. conv_dx_classes:4
+inline void trace_kernel_count(const char* prefix, int count) {
+    if (!g_trace_on) return;
+    char name[64];
+    snprintf(name, sizeof(name), "%s%d", prefix, count);
+    trace_kernel_slow(name);
+}
 
 constexpr int kWave = 64;      // CDNA wavefront
 constexpr int kCUs = 256;      // MI355X

@@ -161,6 +161,8 @@ static const void* prepack_table(PrepackStore& st, int kind, int mode, const voi
 // every shape: conv_forward_bf16. A folded batch-norm in front goes straight to the dma kernels: conv_forward_impl.)
 // kDwFamilies in the dispatch trace, row by row: conv_dw_rows_kernel, conv_dw_stem_kernel, conv_dw_direct_kernel<1|2>, wino43_dw_kernel,
 // wino_dw_fused_kernel, wino_unfused:dw, conv_dw_dma_kernel, conv_small_c:dw, conv_large_dw_kernel, conv_dw_kernel<TM,TN>.
+// The forward and data-gradient launchers name their host-chosen sub-branches next to the family: conv_igemm_tile:32x128|64x128|
+// 128x128, conv_fwd_window_kernel:tm1|tm2, conv_fwd_direct_kernel:tm1|tm2, wino_fused:halfblocks, conv_dx_classes:<launches>.
 // A/B switches of the experiment build that take a family out: BCNN_HIP_NO_WINDOW, BCNN_HIP_NO_DMA, BCNN_HIP_NO_SMALLC_DX
 enum ConvGate { GATE_NONE, GATE_WINDOW, GATE_DMA, GATE_SMALLC_DX, GATE_COUNT };
 static bool gate_open(ConvGate g) {

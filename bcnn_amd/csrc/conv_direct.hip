@@ -325,6 +325,7 @@ void conv_forward_direct(const ConvFwdCall& c) {
     const int tm = (s.Mg <= 32) ? 1 : 2;
     KTimer kt(K_CONV_FWD, conv_gemm_flops(s), conv_gemm_bytes(s));
     trace_kernel("conv_fwd_direct_kernel");
+    trace_kernel(tm == 1 ? "conv_fwd_direct_kernel:tm1" : "conv_fwd_direct_kernel:tm2");
     conv_prefetch_input(c.x, s, c.y);
     const int actm = (a.act == BCNN_HIP_ACT_NONE) ? 0 : (a.act == BCNN_HIP_ACT_RELU ? 1 : 2);
 #define LAUNCH(TMv, KSv, KZ)                                                                            \

@@ -296,8 +296,10 @@ static void launch_igemm(IgemmArgs& a, long long max_cols) {
 
 static void dispatch_igemm(IgemmArgs& a, long long max_cols) {
     const long long big_tiles = (long long)ceil_div(a.M, 128) * ceil_div(max_cols, 128) * a.s.groups * a.nclass;
-    if (a.M <= 32) launch_igemm<1, 4, 1, 1, 16>(a, max_cols);        // 32 x 128
-    else if (a.M <= 64 || big_tiles < 2 * kCUs) launch_igemm<2, 2, 1, 2, 16>(a, max_cols);  // 64 x 128
+    const int tile = a.M <= 32 ? 0 : (a.M <= 64 || big_tiles < 2 * kCUs) ? 1 : 2;
+    trace_kernel(tile == 0 ? "conv_igemm_tile:32x128" : tile == 1 ? "conv_igemm_tile:64x128" : "conv_igemm_tile:128x128");
+    if (tile == 0) launch_igemm<1, 4, 1, 1, 16>(a, max_cols);        // 32 x 128
+    else if (tile == 1) launch_igemm<2, 2, 1, 2, 16>(a, max_cols);   // 64 x 128
     else launch_igemm<2, 2, 2, 2, 16>(a, max_cols);                  // 128 x 128
 }
 
@@ -420,7 +422,7 @@ void conv_backward_data_igemm(const ConvDxCall& c) {
     a.ntaps = 0; a.ntaps_magic = 0; a.KR = 0;
     // stride-parity classes, up to kMaxClassesPerLaunch per launch
     const int st = s.stride;
-    int nc = 0;
+    int nc = 0, launches = 0;
     long long max_cols = 0;
     for (int ra = 0; ra < st; ++ra)
         for (int rb = 0; rb < st; ++rb) {
@@ -437,11 +439,15 @@ void conv_backward_data_igemm(const ConvDxCall& c) {
             if (cols > max_cols) max_cols = cols;
             if (++nc == kMaxClassesPerLaunch || (ra == st - 1 && rb == st - 1)) {
                 a.nclass = nc;
-                if (max_cols > 0) dispatch_igemm(a, max_cols);
+                if (max_cols > 0) {
+                    dispatch_igemm(a, max_cols);
+                    ++launches;
+                }
                 nc = 0;
                 max_cols = 0;
             }
         }
+    trace_kernel_count("conv_dx_classes:", launches);
 }
 
 }  // namespace bcnn_hip

@@ -801,14 +801,13 @@ void conv_backward_data_dma(const ConvDxCall& c) {
         if (a.bs_out) bs->splits = a.stats_splits;
         return;
     }
-    // stride-parity classes; the packed tap order is class-major
+    // stride-parity classes, up to kDmaMaxClasses per launch; the packed tap order is class-major
     const int st = s.stride;
-    struct Pending { DmaClass c; int cols; };
-    Pending all[49];
-    int ncls = 0, tap0 = 0;
+    if (!packed) pack_weights(w, at, s, 1, a.M, a.J, a.Jpad, a.Mpad, kk2, tapoff);
+    int nc = 0, max_cols = 0, tap0 = 0, launches = 0;
     for (int ra = 0; ra < st; ++ra)
         for (int rb = 0; rb < st; ++rb) {
-            DmaClass ci;
+            DmaClass& ci = a.cls[nc];
             ci.ih0 = ((ra - s.pad) % st + st) % st;  // first row with (ih + pad) % st == ra
             ci.iw0 = ((rb - s.pad) % st + st) % st;
             ci.Hc = ci.ih0 < s.H ? (s.H - ci.ih0 + st - 1) / st : 0;
@@ -818,20 +817,19 @@ void conv_backward_data_dma(const ConvDxCall& c) {
             for (int kr = ra; kr < s.ksz; kr += st)
                 for (int kc = rb; kc < s.ksz; kc += st) ++ci.ntaps;  // dx_tap_order lists them in this order
             tap0 += ci.ntaps;
-            all[ncls].c = ci;
-            all[ncls].cols = s.N * ci.Hc * ci.Wc;
-            ++ncls;
+            const int cols = s.N * ci.Hc * ci.Wc;
+            if (cols > max_cols) max_cols = cols;
+            if (++nc == kDmaMaxClasses || (ra == st - 1 && rb == st - 1)) {
+                a.nclass = nc;
+                if (max_cols > 0) {
+                    launch_dma(a, max_cols);
+                    ++launches;
+                }
+                nc = 0;
+                max_cols = 0;
+            }
         }
-    if (!packed) pack_weights(w, at, s, 1, a.M, a.J, a.Jpad, a.Mpad, kk2, tapoff);
-    for (int c0 = 0; c0 < ncls; c0 += kDmaMaxClasses) {
-        int nc = 0, max_cols = 0;
-        for (int c = c0; c < ncls && nc < kDmaMaxClasses; ++c, ++nc) {
-            a.cls[nc] = all[c].c;
-            if (all[c].cols > max_cols) max_cols = all[c].cols;
-        }
-        a.nclass = nc;
-        if (max_cols > 0) launch_dma(a, max_cols);
-    }
+    trace_kernel_count("conv_dx_classes:", launches);
 }
 
 }  // namespace bcnn_hip

@@ -404,6 +404,7 @@ void conv_forward_window(const ConvFwdCall& c) {
 #define LAUNCH2(CGv, Pv) do { if (tm == 1) LAUNCH3(CGv, Pv, 1); else LAUNCH3(CGv, Pv, 2); } while (0)
 #define LAUNCH1(CGv) do { if (pitch == 232) LAUNCH2(CGv, 232); else LAUNCH2(CGv, 264); } while (0)
     trace_kernel("conv_fwd_window_kernel");
+    trace_kernel(tm == 1 ? "conv_fwd_window_kernel:tm1" : "conv_fwd_window_kernel:tm2");
     if (s.Cg == 1) LAUNCH1(1);
     else if (s.Cg == 2) LAUNCH1(2);
     else LAUNCH1(3);

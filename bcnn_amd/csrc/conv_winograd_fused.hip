@@ -606,6 +606,7 @@ static void wino_fused_run(const float* src, const float* w, float* dst, const C
         abort();
     }
     trace_kernel(dx_mode ? "wino_fused_kernel:dx" : "wino_fused_kernel:fwd");
+    if (a.nfull < nblocks) trace_kernel("wino_fused:halfblocks");  // the last round runs as half blocks
 #ifdef BCNN_HIP_EXPERIMENT
     if (parts == 2) { wino_bf16_launch<2>(a, w, s, dx_mode, grid, plain); }
     else if (parts == 3) { wino_bf16_launch<3>(a, w, s, dx_mode, grid, plain); }

@@ -25,7 +25,7 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-NONE, RELU = 0, 2
+NONE, RELU, PRELU = 0, 2, 8
 SENTINEL = -777.25
 LIMIT = 2.0 ** 24 / 64
 
@@ -142,18 +142,27 @@ def _integers(layer):
                 dw0=T(-8, 8, f, c // g, k, k), db0=T(-8, 8, f))
 
 
-def _reference(t, layer, act):
-    """float64: y, dx, dw, db and the largest value of the same convolutions on the absolute values"""
+def _reference(t, layer, act, slopes=None):
+    """float64: y, dx, dw, db and the largest value of the same convolutions on the absolute values; z: the convolution
+    plus bias in front of the activation (tests/test_conv_fwd_dx_ladder.py applies the other cheap activations to it).
+    act: NONE, RELU or PRELU with one float32 slope per filter"""
     n, c, h, w, f, k, st, pad, g = layer
     x, wt, dy = t["x"].double().requires_grad_(), t["w"].double().requires_grad_(), t["dy"].double()
     b = t["b"].double()
     b = torch.where(b == 1.0, torch.zeros_like(b), b)                    # bcnn_add_scalar adds nothing for exactly 1.0f
-    y = F.conv2d(x, wt, None, st, pad, 1, g) + b.view(1, f, 1, 1)
+    z = F.conv2d(x, wt, None, st, pad, 1, g) + b.view(1, f, 1, 1)
+    y = z
     if act == RELU:
-        y = torch.relu(y)
+        y = torch.relu(z)
+    elif act == PRELU:
+        y = torch.where(z > 0, z, z * slopes.double().view(1, f, 1, 1))
+    else:
+        assert act == NONE, act
     y.backward(dy)
     gy = dy * (y > 0) if act == RELU else dy
-    ref = dict(y=y.detach(), dx=x.grad, dw=wt.grad, db=gy.sum(dim=(0, 2, 3)))
+    if act == PRELU:
+        gy = dy * torch.where(y > 0, torch.ones_like(y), slopes.double().view(1, f, 1, 1).expand_as(y))
+    ref = dict(y=y.detach(), dx=x.grad, dw=wt.grad, db=gy.sum(dim=(0, 2, 3)), z=z.detach())
     xa, wa = t["x"].double().abs().requires_grad_(), t["w"].double().abs().requires_grad_()
     ya = F.conv2d(xa, wa, None, st, pad, 1, g) + t["b"].double().abs().view(1, f, 1, 1)
     ya.backward(dy.abs())
@@ -213,8 +222,8 @@ def _ran(i):
     return r
 
 
-def _assert_exact(r, layer, keys=("y", "dx", "dw", "db")):
-    assert r["largest"] < LIMIT, (layer, r["largest"])            # the reference alone: what makes equality legitimate
+def _assert_exact(r, layer, keys=("y", "dx", "dw", "db"), limit=LIMIT):
+    assert r["largest"] < limit, (layer, r["largest"])            # the reference alone: what makes equality legitimate
     for key in keys:
         want = r["ref"][key].float()
         assert torch.equal(want.double(), r["ref"][key]), (layer, key)
