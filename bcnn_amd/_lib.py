@@ -62,6 +62,9 @@ SIGNATURES = {
     "bcnn_hip_activation_backward_from_input": (None, [vp, vp, sz, i]),
     "bcnn_hip_scale_channels_forward": (None, [vp, vp, vp, i, i, i, i]),
     "bcnn_hip_scale_channels_backward": (None, [vp, vp, vp, vp, vp, i, i, i, i]),
+    "bcnn_hip_group_norm_forward": (None, [vp] * 6 + [i, i, i, i, f]),
+    "bcnn_hip_group_norm_backward": (None, [vp] * 8 + [i, i, i, i, i]),
+    "bcnn_hip_group_norm_path": (i, [i, i, i, i, i]),
     "bcnn_hip_batchnorm_forward": (None, [vp] * 10 + [i, i, i, i, i]),
     "bcnn_hip_batchnorm_backward": (None, [vp, vp, vp, i] + [vp] * 9 + [i, i, i]),
     "bcnn_hip_conv_workspace_size": (sz, [i] * 9),

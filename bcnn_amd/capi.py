@@ -21,7 +21,7 @@ LOSS_EUCLIDEAN, LOSS_LIFTED_STRUCT = 0, 1
 LOG_SILENT = 3
 IMAGE_FIT_STRETCH, IMAGE_FIT_LETTERBOX = 0, 1
 POOL2D_MAX, POOL2D_AVG = 0, 1
-LAYER_ACTIVATION, LAYER_POOL2D, LAYER_SCALE_CHANNELS = 3, 17, 18
+LAYER_ACTIVATION, LAYER_POOL2D, LAYER_SCALE_CHANNELS, LAYER_GROUPNORM = 3, 17, 18, 19
 
 
 class Tensor(C.Structure):
@@ -114,6 +114,7 @@ def lib():
         "bcnn_add_avgpool_layer": (i, [vp, cp, cp]), "bcnn_add_activation_layer": (i, [vp, i, cp]),
         "bcnn_add_pool2d_layer": (i, [vp, i, i, i, i, i, i, cp, cp]),
         "bcnn_add_scale_channels_layer": (i, [vp, cp, cp, cp]),
+        "bcnn_add_groupnorm_layer": (i, [vp, i, f, cp, cp]),
         "bcnn_add_eltwise_layer": (i, [vp, i, cp, cp, cp]), "bcnn_add_fullc_layer": (i, [vp, i, i, i, i, cp, cp]),
         "bcnn_add_softmax_layer": (i, [vp, cp, cp]), "bcnn_add_cost_layer": (i, [vp, i, i, f, cp, cp, cp]),
         "bcnn_upload_tensor": (i, [vp, i, i]), "bcnn_download_tensor": (i, [vp, i, i]),
@@ -221,6 +222,11 @@ class Net:
     def scale_channels(self, src, gate, dst):
         """bcnn_add_scale_channels_layer: dst = src * gate, gate [N,C,1,1] (squeeze-and-excitation) or src's shape (sam)"""
         return self._added(self.L.bcnn_add_scale_channels_layer(self.net, src.encode(), gate.encode(), dst.encode()))
+
+    def groupnorm(self, groups, src, dst, eps=0.0):
+        """bcnn_add_groupnorm_layer: group normalisation over `groups` groups of channels (1: layer norm over (C,H,W),
+        C: instance norm with affine); eps <= 0 selects 1e-5"""
+        return self._added(self.L.bcnn_add_groupnorm_layer(self.net, groups, eps, src.encode(), dst.encode()))
 
     def activation(self, act, src):
         return self._added(self.L.bcnn_add_activation_layer(self.net, act, src.encode()))

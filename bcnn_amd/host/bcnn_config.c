@@ -195,6 +195,8 @@ typedef struct {
      * `pad` as written (a count per side in both dialects), and the three keys only these sections read */
     int has_size, has_stride, pool_pad, pool_avg, ceil_mode, count_include_pad;
     int has_from; /* Darknet `from=`: src_id[0] is the previous section, src_id[1] the named one */
+    int has_groups; /* [groupnorm]: the section wrote groups= (the default of num_groups, 1, belongs to convolutions) */
+    float eps;      /* [groupnorm] / [layernorm] / [instancenorm]; 0: the builder's default */
 } layer_param;
 
 static void lp_reset(layer_param *lp) {
@@ -268,7 +270,8 @@ static void lp_set(bcnn_net *net, int section_idx, layer_param *lp, const char *
         lp->pool_pad = atoi(val);
         if (format == 0) lp->pad = atoi(val);
         else lp->pad = atoi(val) ? lp->size / 2 : 0; /* Darknet: boolean, needs `size` to come first */
-    } else if (!strcmp(name, "num_groups") || !strcmp(name, "groups")) lp->num_groups = atoi(val);
+    } else if (!strcmp(name, "num_groups") || !strcmp(name, "groups")) { lp->num_groups = atoi(val); lp->has_groups = 1; }
+    else if (!strcmp(name, "eps")) lp->eps = (float)atof(val);
     /* only [lrn] reads these three; atof, where the reference's atoi loads a Caffe LRN (alpha=0.0001) as the identity */
     else if (!strcmp(name, "alpha")) lp->alpha = (float)atof(val);
     else if (!strcmp(name, "beta")) lp->beta = (float)atof(val);
@@ -428,6 +431,22 @@ static bcnn_status add_layer(bcnn_net *net, const char *name, layer_param *lp) {
         BCNN_CHECK_AND_LOG(net->log_ctx, lp->a == BCNN_ACT_NONE, BCNN_INVALID_PARAMETER,
                            "Scale-channels layer %s: only activation=linear is supported; add an [activation] section\n", dst);
         return bcnn_add_scale_channels_layer(net, lp->src_id[lp->has_from ? 1 : 0], lp->src_id[lp->has_from ? 0 : 1], dst);
+    }
+    if (is_any(name, "[groupnorm]", "[gn]", "[layernorm]", "[instancenorm]")) {
+        /* one node: layer norm over (C,H,W) is one group, instance norm one group per channel of the source */
+        BCNN_CHECK_AND_LOG(net->log_ctx, lp->a == BCNN_ACT_NONE, BCNN_INVALID_PARAMETER,
+                           "Group-norm layer %s: only activation=linear is supported; add an [activation] section\n", dst);
+        int groups = lp->num_groups;
+        if (!strcmp(name, "[layernorm]")) groups = 1;
+        else if (!strcmp(name, "[instancenorm]")) {
+            const int idx = net->num_nodes > 0 ? bcnn_net_find_tensor(net, src) : 0;
+            BCNN_CHECK_AND_LOG(net->log_ctx, idx >= 0, BCNN_INVALID_PARAMETER,
+                               "Instance-norm layer: invalid input node name %s\n", src);
+            groups = net->tensors[idx].c;
+        } else
+            BCNN_CHECK_AND_LOG(net->log_ctx, lp->has_groups, BCNN_INVALID_PARAMETER,
+                               "Group-norm layer %s: the section needs a groups= key\n", dst);
+        return bcnn_add_groupnorm_layer(net, groups, lp->eps, src, dst);
     }
     if (!strcmp(name, "[yolo]")) {
         /* the builder copies 2 * num values (the reference reads past a shorter list); pad a short one with zeros */

@@ -402,10 +402,12 @@ static void mark_dead_grad_fills(bcnn_net *net) {
          * `0 + sum` instead of accumulating: mark 2, the node's backward asks bcnn_grad_sole_writer(). Holds for
          * the forward -> backward order every caller of the reference uses (bcnn_train_on_batch). */
         if (uses == 1 && (nd->type == BCNN_LAYER_MAXPOOL || nd->type == BCNN_LAYER_DEPTHWISE_CONV2D ||
-                          nd->type == BCNN_LAYER_LRN || nd->type == BCNN_LAYER_POOL2D)) {
+                          nd->type == BCNN_LAYER_LRN || nd->type == BCNN_LAYER_POOL2D ||
+                          nd->type == BCNN_LAYER_GROUPNORM)) {
             /* max-pooling's gather, the depthwise data gradient (a gather too: one thread owns a dx element,
-             * bcnn_depthwise_conv_layer.c:432-547 accumulates onto the zero fill), LRN's (one lane per column) and the
-             * pool2d gather, whose overwrite form also writes the elements no window covers */
+             * bcnn_depthwise_conv_layer.c:432-547 accumulates onto the zero fill), LRN's (one lane per column), the
+             * pool2d gather, whose overwrite form also writes the elements no window covers, and group-norm's sweep (one
+             * thread owns a dx element) */
             hc->grad_fill_dead[t] = 2;
             continue;
         }
@@ -526,10 +528,16 @@ bcnn_status bcnn_reserve_device(void **buf, size_t *capacity, size_t elems, size
     return *buf ? BCNN_SUCCESS : BCNN_FAILED_ALLOC;
 }
 
-/* every private device buffer of a node that follows its first dst tensor, made to hold `elems` elements */
-static bcnn_status node_reserve_buffers(const bcnn_node *nd, size_t elems, int may_grow) {
+/* every private device buffer of a node that follows its first dst tensor d, made to hold d's elements (the group-norm
+ * statistics: mean and rstd of d's n * groups rows) */
+static bcnn_status node_reserve_buffers(const bcnn_node *nd, const bcnn_tensor *d, int may_grow) {
+    size_t elems = (size_t)bcnn_tensor_size(d);
 #define RESERVE(T, buf, cap) \
     bcnn_reserve_device((void **)&((T *)nd->param)->buf, &((T *)nd->param)->cap, elems, sizeof(*((T *)nd->param)->buf), may_grow)
+    if (nd->type == BCNN_LAYER_GROUPNORM) { /* (a constant behind the enum: no case label) */
+        elems = 2 * (size_t)d->n * (size_t)((const bcnn_groupnorm_param *)nd->param)->num_groups;
+        return RESERVE(bcnn_groupnorm_param, stats_gpu, stats_capacity);
+    }
     switch (nd->type) {
         case BCNN_LAYER_CONV2D: return RESERVE(bcnn_conv_param, bn_workspace_gpu, bn_workspace_capacity);
         case BCNN_LAYER_BATCHNORM: return RESERVE(bcnn_batchnorm_param, workspace_gpu, workspace_capacity);
@@ -593,7 +601,7 @@ static bcnn_status resize_plan(bcnn_net *net, int w, int h, int c, int need_real
         bcnn_tensor *d = &plan[nd->dst[0]];
         BCNN_CHECK_AND_LOG(net->log_ctx, keeps_producer_shape(nd) || node_dst_shape(nd, s, d), BCNN_INVALID_PARAMETER,
                            "bcnn_resize_net: node %d pools a %d x %d tensor, smaller than its padded window\n", i, s->w, s->h);
-        BCNN_CHECK_AND_LOG(net->log_ctx, need_realloc || node_reserve_buffers(nd, (size_t)bcnn_tensor_size(d), 0) == BCNN_SUCCESS,
+        BCNN_CHECK_AND_LOG(net->log_ctx, need_realloc || node_reserve_buffers(nd, d, 0) == BCNN_SUCCESS,
                            BCNN_INVALID_PARAMETER,
                            "bcnn_resize_net: node %d keeps a buffer for the backward pass that is smaller than the new shape; "
                            "call with need_realloc\n", i);
@@ -613,7 +621,7 @@ static bcnn_status resize_commit(bcnn_net *net, int w, int h, int c, int need_re
             if (need_realloc && bcnn_tensor_allocate(d, net->mode) != BCNN_SUCCESS) return BCNN_FAILED_ALLOC;
         }
         if (!need_realloc) continue; /* the plan found every buffer large enough */
-        if (node_reserve_buffers(nd, (size_t)bcnn_tensor_size(d), 1) != BCNN_SUCCESS) return BCNN_FAILED_ALLOC;
+        if (node_reserve_buffers(nd, d, 1) != BCNN_SUCCESS) return BCNN_FAILED_ALLOC;
         if (nd->type == BCNN_LAYER_MAXPOOL) { /* the reference's host copy of the indexes follows the device one */
             bcnn_maxpool_param *p = (bcnn_maxpool_param *)nd->param;
             int *host = (int *)realloc(p->indexes, p->indexes_capacity * sizeof(int));
@@ -1128,6 +1136,8 @@ void *bcnn_get_node_state(bcnn_net *net, int node, int which) {
     const bcnn_tensor *sm = NULL, *sv = NULL;
     if (nd->type == BCNN_LAYER_MAXPOOL) return which == 0 ? (void *)((bcnn_maxpool_param *)nd->param)->indexes_gpu : NULL;
     if (nd->type == BCNN_LAYER_POOL2D) return which == 0 ? (void *)((bcnn_pool2d_param *)nd->param)->indexes_gpu : NULL;
+    if (nd->type == BCNN_LAYER_GROUPNORM) /* mean [N * G] then rstd [N * G] of the last forward; NULL in a PREDICT-built net */
+        return which == 0 ? (void *)((bcnn_groupnorm_param *)nd->param)->stats_gpu : NULL;
     if (nd->type == BCNN_LAYER_ACTIVATION) /* hard-swish / swish / mish: the input the last TRAIN forward kept */
         return which == 0 ? (void *)((bcnn_activation_param *)nd->param)->x_saved_gpu : NULL;
     if (nd->type == BCNN_LAYER_CONV2D && ((bcnn_conv_param *)nd->param)->batch_norm) {

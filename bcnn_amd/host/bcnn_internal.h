@@ -217,6 +217,9 @@ bcnn_status bcnn_node_add_input(bcnn_net *net, bcnn_node *node, int index);
 bcnn_status bcnn_node_add_output(bcnn_net *net, bcnn_node *node, int index);
 /* new n x c x h x w tensor `dst_id` (with gradient, allocated for the net's mode) as the node's next output */
 bcnn_status bcnn_node_new_output(bcnn_net *net, bcnn_node *node, int n, int c, int h, int w, const char *dst_id);
+/* new [1,1,1,count] tensor `<src_id>_<suffix>`, filled with `fill`, as the node's next input; trainable ones join the arena */
+bcnn_status bcnn_node_new_vector_param(bcnn_net *net, bcnn_node *node, int count, int has_grad, const char *src_id,
+                                       const char *suffix, float fill, int trainable);
 
 typedef struct tensor_filler {
     int range;
@@ -401,6 +404,17 @@ typedef struct bcnn_scale_channels_param {
     int same_shape; /* as built: 0 = [N,C,1,1] gate, 1 = a gate of the source's shape (log line only) */
 } bcnn_scale_channels_param;
 
+/* group normalisation (bcnn_add_groupnorm_layer; no reference counterpart): src[1] = scales, src[2] = b */
+typedef struct bcnn_groupnorm_param {
+    int num_groups;
+    float eps;
+#ifdef BCNN_USE_HIP
+    float *stats_gpu;       /* nets built in TRAIN / VALID mode: mean [N * G] then rstd [N * G] of the last forward */
+    size_t stats_capacity;  /* floats allocated (bcnn_reserve_device) */
+    float *adam_m_gpu, *adam_v_gpu; /* moments of the scales, allocated by the first Adam step */
+#endif
+} bcnn_groupnorm_param;
+
 typedef struct bcnn_eltwise_param {
     bcnn_activation activation;
     int stride[2];
@@ -556,6 +570,10 @@ void bcnn_release_param_dropout_layer(bcnn_node *node);
 uint64_t bcnn_dropout_key(uint64_t seed, int node, int rank);
 void bcnn_forward_scale_channels_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_scale_channels_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_forward_groupnorm_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_backward_groupnorm_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_update_groupnorm_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_release_param_groupnorm_layer(bcnn_node *node);
 void bcnn_release_param_activation_layer(bcnn_node *node);
 void bcnn_forward_pool2d_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_pool2d_layer(bcnn_net *net, bcnn_node *node);

@@ -29,8 +29,8 @@ static bcnn_status attach_source(bcnn_net *net, bcnn_node *node, const char *src
 }
 
 /* creates a [1,1,1,count] parameter tensor, registers it with the node (and the arena if trainable) */
-static bcnn_status add_vector_param(bcnn_net *net, bcnn_node *node, int count, int has_grad, const char *src_id,
-                                    const char *suffix, float fill, int trainable) {
+bcnn_status bcnn_node_new_vector_param(bcnn_net *net, bcnn_node *node, int count, int has_grad, const char *src_id,
+                                       const char *suffix, float fill, int trainable) {
     char name[256];
     snprintf(name, sizeof(name), "%s_%s", src_id, suffix);
     bcnn_tensor t = {0};
@@ -98,7 +98,7 @@ bcnn_status bcnn_add_convolutional_layer(bcnn_net *net, int num_filters, int siz
     BCNN_CHECK_STATUS(bcnn_net_add_tensor(net, weights));
     BCNN_CHECK_STATUS(bcnn_node_add_input(net, &node, net->num_tensors - 1));
     bcnn_net_register_param(net, net->num_tensors - 1);
-    BCNN_CHECK_STATUS(add_vector_param(net, &node, num_filters, 1, src_id, "b", 0.0f, 1));
+    BCNN_CHECK_STATUS(bcnn_node_new_vector_param(net, &node, num_filters, 1, src_id, "b", 0.0f, 1));
 
     node.type = BCNN_LAYER_CONV2D;
     node.param_size = sizeof(bcnn_conv_param);
@@ -124,18 +124,18 @@ bcnn_status bcnn_add_convolutional_layer(bcnn_net *net, int num_filters, int siz
         bcnn_tensor_create(&param->saved_mean, 1, 1, 1, num_filters, 1, name, net->mode);
         snprintf(name, sizeof(name), "%s_sav_var", src_id);
         bcnn_tensor_create(&param->saved_variance, 1, 1, 1, num_filters, 1, name, net->mode);
-        BCNN_CHECK_STATUS(add_vector_param(net, &node, num_filters, 0, src_id, "run_mean", 0.0f, 0));
-        BCNN_CHECK_STATUS(add_vector_param(net, &node, num_filters, 0, src_id, "run_var", 0.0f, 0));
+        BCNN_CHECK_STATUS(bcnn_node_new_vector_param(net, &node, num_filters, 0, src_id, "run_mean", 0.0f, 0));
+        BCNN_CHECK_STATUS(bcnn_node_new_vector_param(net, &node, num_filters, 0, src_id, "run_var", 0.0f, 0));
         /* scales accumulate a gradient but no update function ever applies it (reference
          * bcnn_conv_layer.c:810-855 updates weights and biases only) -- kept out of the arena */
-        BCNN_CHECK_STATUS(add_vector_param(net, &node, num_filters, 1, src_id, "scales", 1.0f, 0));
+        BCNN_CHECK_STATUS(bcnn_node_new_vector_param(net, &node, num_filters, 1, src_id, "scales", 1.0f, 0));
         if (net->mode != BCNN_MODE_PREDICT) {
             param->bn_workspace_capacity = (size_t)sn * num_filters * oh * ow;
             param->bn_workspace_gpu = bcnn_hip_malloc_f32(param->bn_workspace_capacity);
         }
     }
     if (activation == BCNN_ACT_PRELU)
-        BCNN_CHECK_STATUS(add_vector_param(net, &node, num_filters, 0, src_id, "prelu_slopes", 0.0f, 0));
+        BCNN_CHECK_STATUS(bcnn_node_new_vector_param(net, &node, num_filters, 0, src_id, "prelu_slopes", 0.0f, 0));
     BCNN_CHECK_STATUS(bcnn_net_add_node(net, node));
     BCNN_INFO(net->log_ctx, "[Conv2D%s%s] %-8s (%4d x%4d x%4d) -> %-8s (%4d x%4d x%4d) %d x %d / %d pad %d groups %d\n",
               batch_norm ? "+BN" : "", activation != BCNN_ACT_NONE ? "+act" : "", src_id, sw, sh, sc, dst_id, ow, oh,
@@ -375,7 +375,7 @@ bcnn_status bcnn_add_depthwise_conv_layer(bcnn_net *net, int size, int stride, i
     BCNN_CHECK_STATUS(bcnn_net_add_tensor(net, weights));
     BCNN_CHECK_STATUS(bcnn_node_add_input(net, &node, net->num_tensors - 1));
     bcnn_net_register_param(net, net->num_tensors - 1);
-    BCNN_CHECK_STATUS(add_vector_param(net, &node, s.c, 1, src_id, "b", 0.0f, 1));
+    BCNN_CHECK_STATUS(bcnn_node_new_vector_param(net, &node, s.c, 1, src_id, "b", 0.0f, 1));
     node.type = BCNN_LAYER_DEPTHWISE_CONV2D;
     node.param_size = sizeof(bcnn_depthwise_conv_param);
     bcnn_depthwise_conv_param *param = (bcnn_depthwise_conv_param *)calloc(1, node.param_size);
@@ -515,10 +515,10 @@ bcnn_status bcnn_add_batchnorm_layer(bcnn_net *net, const char *src_id, const ch
     bcnn_tensor_create(&param->saved_mean, 1, 1, 1, s.c, 1, name, net->mode);
     snprintf(name, sizeof(name), "%s_sav_var", src_id);
     bcnn_tensor_create(&param->saved_variance, 1, 1, 1, s.c, 1, name, net->mode);
-    BCNN_CHECK_STATUS(add_vector_param(net, &node, s.c, 0, src_id, "run_mean", 0.0f, 0));
-    BCNN_CHECK_STATUS(add_vector_param(net, &node, s.c, 0, src_id, "run_var", 0.0f, 0));
-    BCNN_CHECK_STATUS(add_vector_param(net, &node, s.c, 1, src_id, "scales", 1.0f, 0));
-    BCNN_CHECK_STATUS(add_vector_param(net, &node, s.c, 1, src_id, "b", 0.0f, 0));
+    BCNN_CHECK_STATUS(bcnn_node_new_vector_param(net, &node, s.c, 0, src_id, "run_mean", 0.0f, 0));
+    BCNN_CHECK_STATUS(bcnn_node_new_vector_param(net, &node, s.c, 0, src_id, "run_var", 0.0f, 0));
+    BCNN_CHECK_STATUS(bcnn_node_new_vector_param(net, &node, s.c, 1, src_id, "scales", 1.0f, 0));
+    BCNN_CHECK_STATUS(bcnn_node_new_vector_param(net, &node, s.c, 1, src_id, "b", 0.0f, 0));
     if (net->mode != BCNN_MODE_PREDICT) {
         param->workspace_capacity = (size_t)bcnn_tensor_size(&s);
         param->workspace_gpu = bcnn_hip_malloc_f32(param->workspace_capacity);

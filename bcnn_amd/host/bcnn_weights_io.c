@@ -5,6 +5,7 @@
  *     conv / depthwise / full-connected : biases, weights [, conv with batch-norm: means, variances, scales]
  *     PReLU activation node             : slopes
  *     batch-norm node                   : means, variances, scales, biases (dst channels each)
+ *     group-norm node (no reference counterpart) : biases, scales (dst channels each)
  * The reader additionally expects a fused convolution's PReLU slopes after its batch-norm block although the
  * writer never stores them (reference asymmetry, kept: such a file fails with BCNN_INVALID_MODEL in both
  * implementations). Files named *.weights are read in the Darknet layout (int header, `seen` counter, scales
@@ -60,6 +61,9 @@ bcnn_status bcnn_save_weights(bcnn_net *net, const char *filename) {
         } else if (nd->type == BCNN_LAYER_BATCHNORM) {
             const int c = net->tensors[nd->dst[0]].c;
             for (int k = 1; ok && k <= 4; ++k) ok = put(fp, &net->tensors[nd->src[k]], c);
+        } else if (nd->type == BCNN_LAYER_GROUPNORM) { /* biases, then scales, like a layer's biases and weights */
+            const int c = net->tensors[nd->dst[0]].c;
+            ok = put(fp, &net->tensors[nd->src[2]], c) && put(fp, &net->tensors[nd->src[1]], c);
         }
     }
     fclose(fp);
@@ -135,6 +139,17 @@ static bcnn_status load_batchnorm(bcnn_net *net, bcnn_node *nd, FILE *fp, int fo
     }
     if (net->mode == BCNN_MODE_PREDICT) fold_batchnorm(m, v, s, b, c);
     push(m, c); push(v, c); push(s, c); push(b, c);
+    return BCNN_SUCCESS;
+}
+
+/* the group-norm node: biases then scales, C floats each; Darknet has no such layer and its files hold nothing for it */
+static bcnn_status load_groupnorm(bcnn_net *net, bcnn_node *nd, FILE *fp, int format) {
+    if (format != 0) return BCNN_SUCCESS;
+    bcnn_tensor *s = &net->tensors[nd->src[1]], *b = &net->tensors[nd->src[2]];
+    const int c = net->tensors[nd->dst[0]].c;
+    READ_OR_FAIL(net, fp, b, c, "group-norm biases");
+    READ_OR_FAIL(net, fp, s, c, "group-norm scales");
+    push(s, c); push(b, c);
     return BCNN_SUCCESS;
 }
 
@@ -220,6 +235,8 @@ bcnn_status bcnn_load_weights(bcnn_net *net, const char *filename) {
             st = load_batchnorm(net, nd, fp, format);
         } else if (nd->type == BCNN_LAYER_FULL_CONNECTED) {
             st = load_fullc(net, nd, fp, need_transpose);
+        } else if (nd->type == BCNN_LAYER_GROUPNORM) {
+            st = load_groupnorm(net, nd, fp, format);
         }
     }
     fclose(fp);

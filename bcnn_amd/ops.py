@@ -286,6 +286,35 @@ def scale_channels_backward(x, gate, dy, dx, dgate):
                                                  _scale_gate_form(x, gate))
 
 
+GROUP_NORM_PATHS = ("lanes", "resident", "split")
+
+
+def group_norm_path(n, c, hw, groups, backward=False):
+    """bcnn_hip_group_norm_path: the kernel family of the shape, 0 lanes, 1 resident, 2 split (GROUP_NORM_PATHS)"""
+    return int(_lib.load().bcnn_hip_group_norm_path(n, c, hw, groups, 1 if backward else 0))
+
+
+def group_norm_forward(x, gamma, beta, y, mean, rstd, groups, eps=1e-5):
+    """bcnn_hip_group_norm_forward: y = (x - mean) * rstd * gamma[ch] + beta[ch], statistics per (image, group) over its
+    (C / groups) * H * W values; mean and rstd ([N * groups]) receive them, or are both None (nothing is stored)"""
+    n, c, h, w = x.shape
+    assert y.shape == x.shape and gamma.numel() == c and beta.numel() == c and groups > 0 and c % groups == 0
+    assert (mean is None) == (rstd is None) and (mean is None or (mean.numel() == n * groups and rstd.numel() == n * groups))
+    _lib.load().bcnn_hip_group_norm_forward(_f32(x), _f32(gamma), _f32(beta), _f32(y), _f32(mean), _f32(rstd), n, c, h * w,
+                                            groups, eps)
+
+
+def group_norm_backward(x, gamma, mean, rstd, dy, dx, dgamma, dbeta, groups, overwrite=False):
+    """bcnn_hip_group_norm_backward from the stored mean and rstd: dx = (overwrite) or += the data gradient,
+    dgamma += sum dy * xh, dbeta += sum dy; each of dx, dgamma, dbeta may be None (that output is skipped)"""
+    n, c, h, w = x.shape
+    assert dy.shape == x.shape and (dx is None or dx.shape == x.shape) and gamma.numel() == c and c % groups == 0
+    assert mean.numel() == n * groups and rstd.numel() == n * groups
+    assert (dgamma is None or dgamma.numel() == c) and (dbeta is None or dbeta.numel() == c)
+    _lib.load().bcnn_hip_group_norm_backward(_f32(x), _f32(gamma), _f32(mean), _f32(rstd), _f32(dy), _f32(dx), _f32(dgamma),
+                                             _f32(dbeta), n, c, h * w, groups, 1 if overwrite else 0)
+
+
 def activation_backward(x, dx, act, slopes=None, dslopes=None, spatial=1, channels=1):
     """bcnn_backward_activation_cpu (bcnn_activation_layer.c:165-226), dx in place"""
     _lib.load().bcnn_hip_activation_backward(_f32(x), _f32(dx), x.numel(), act, _f32(slopes), _f32(dslopes),

@@ -62,6 +62,8 @@ typedef enum {
  * BCNN_LAYER_POOL2D. A constant of the enum's type next to the enum, not an enumerator: the enumerator list stays the one
  * tests/test_pool2d_abi.py pins, which ends with BCNN_LAYER_POOL2D. */
 #define BCNN_LAYER_SCALE_CHANNELS ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 1))
+/* The layer type of bcnn_add_groupnorm_layer, likewise a constant behind the enumerator list. */
+#define BCNN_LAYER_GROUPNORM ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 2))
 
 typedef enum {
     BCNN_ACT_NONE, BCNN_ACT_TANH, BCNN_ACT_RELU, BCNN_ACT_RAMP, BCNN_ACT_SOFTPLUS,
@@ -266,6 +268,21 @@ BCNN_API bcnn_status bcnn_add_pool2d_layer(bcnn_net *net, bcnn_pool2d_kind kind,
  * bcnn_resize_net (dst is reshaped like src). */
 BCNN_API bcnn_status bcnn_add_scale_channels_layer(bcnn_net *net, const char *src_id, const char *gate_id,
                                                    const char *dst_id);
+/* New, without a reference counterpart: group normalisation of src [N,C,H,W] over num_groups groups of C / num_groups
+ * consecutive channels, per image: dst = (src - mean) * rstd * scales[ch] + b[ch], mean and the biased variance over the
+ * group's (C / num_groups) * H * W values, rstd = 1 / sqrt(var + eps). num_groups == 1 is layer norm over (C,H,W),
+ * num_groups == C instance norm with affine. eps <= 0 selects 1e-5. The same function in TRAIN, VALID and PREDICT mode: no
+ * running statistics.
+ *   Parameters <src>_gn_scales (filled with 1) and <src>_gn_b (0), [1,1,1,C], trained like a layer's weights and biases
+ *   (the scales take the weights' rule, weight decay included). Model files hold b then scales, C floats each; the
+ *   Darknet reader skips the node.
+ *   A net built in TRAIN or VALID mode keeps mean and rstd of the last forward, [2][N * num_groups] floats:
+ *   bcnn_get_node_state(net, node, 0). The backward recomputes the normalised values from them. It adds into the source
+ *   gradient (assigns when it is its sole writer); a source without a gradient buffer is skipped.
+ * Refused with BCNN_INVALID_PARAMETER and a log line, nothing added to the net: an unknown src name, num_groups <= 0,
+ * num_groups that does not divide C. May be the first node of a net. Follows bcnn_resize_net (dst is reshaped like src). */
+BCNN_API bcnn_status bcnn_add_groupnorm_layer(bcnn_net *net, int num_groups, float eps, const char *src_id,
+                                              const char *dst_id);
 BCNN_API bcnn_status bcnn_add_concat_layer(bcnn_net *net, int num_src, char *const *src_ids, const char *dst_id);
 BCNN_API bcnn_status bcnn_add_eltwise_layer(bcnn_net *net, bcnn_activation activation, const char *src_id1,
                                             const char *src_id2, const char *dst_id);

@@ -428,6 +428,34 @@ void bcnn_hip_scale_channels_backward(const float *x_d, const float *gate_d, con
                                       float *dgate_d, int n, int c, int hw, int same_shape);
 
 /* ---------------------------------------------------------------------------------------------
+ * Group normalisation (the group-norm node; group_norm.hip). No reference counterpart. Layer norm over (C,H,W) is
+ * groups == 1, instance norm groups == c.
+ *   x is [n][c][hw]; gamma, beta are [c]; mean, rstd are [n * groups]. Group g of image n is the contiguous row of
+ *   m = (c / groups) * hw floats at row n * groups + g; element i of it has channel ch = g * (c / groups) + i / hw.
+ *   forward : mean and the biased variance of every row (float32 sums of x and x^2 in a fixed order, combined and
+ *     finalised in double), rstd = (float)(1 / sqrt(var + eps)); xh = (x - mean) * rstd; y = xh * gamma[ch] + beta[ch] with
+ *     the float32 mean and rstd, one float32 rounding per operation: y is the bits of that expression. mean_d / rstd_d
+ *     may be NULL (nothing is stored).
+ *   backward: takes mean and rstd and recomputes xh. t = dy * gamma[ch]; ds = sum_m t * xh; db = sum_m t;
+ *     dxv = (t - (xh * ds + db) / m) * rstd; dx = dxv (overwrite != 0) or dx + dxv. dgamma[ch] += sum_n sum_hw dy * xh,
+ *     dbeta[ch] += sum_n sum_hw dy: plane sums added over n in ascending order in double, the start value enters as one
+ *     float32 addition. Each of dx_d, dgamma_d, dbeta_d may be NULL: that output is skipped.
+ *   No atomics; the order of every sum follows from the shape alone: two runs give the same bits.
+ *   bcnn_hip_group_norm_path: the kernel family the shape runs on, 0 lanes (rows of up to 1024 floats: a group of lanes
+ *     per row), 1 resident (one workgroup keeps the row in LDS: up to 16128 floats forward, 8064 backward), 2 split
+ *     (slices, a finalize kernel, a map sweep); -1 for a shape the workers refuse. With the dispatch trace on, every
+ *     launch is named group_norm_fwd:<path> / group_norm_bwd:<path>, the parameter-gradient kernel group_norm_bwd:params:
+ *     forward 1 launch (split 3), backward at most 2 (split 4).
+ *   groups <= 0, groups that do not divide c and tensors of 2^31 elements or more exit.
+ * ------------------------------------------------------------------------------------------- */
+void bcnn_hip_group_norm_forward(const float *x_d, const float *gamma_d, const float *beta_d, float *y_d, float *mean_d,
+                                 float *rstd_d, int n, int c, int hw, int groups, float eps);
+void bcnn_hip_group_norm_backward(const float *x_d, const float *gamma_d, const float *mean_d, const float *rstd_d,
+                                  const float *dy_d, float *dx_d, float *dgamma_d, float *dbeta_d, int n, int c, int hw,
+                                  int groups, int overwrite);
+int bcnn_hip_group_norm_path(int n, int c, int hw, int groups, int backward);
+
+/* ---------------------------------------------------------------------------------------------
  * Depthwise convolution.  Replaces the kernels of bcnn_depthwise_conv_layer.cu:33-200; CPU semantics
  * bcnn_depthwise_conv_layer.c:165-293, 295-547: weights [c][k][k]; y = act(dwconv + bias);
  * backward: dy *= act'(y) in place, dbias += ..., and ONLY IF dx_d != NULL: dw += ..., dx += ...
