@@ -147,6 +147,9 @@ SIGNATURES = {
     "bcnn_hip_deconv_workspace_size": (sz, [i] * 8),
     "bcnn_hip_deconv_forward": (None, [vp, vp, vp, vp] + [i] * 9),
     "bcnn_hip_deconv_backward": (None, [vp] * 7 + [i] * 9 + [vp, sz]),
+    "bcnn_hip_dilated_conv_workspace_size": (sz, [i] * 10),
+    "bcnn_hip_dilated_conv_forward": (None, [vp, vp, vp, vp] + [i] * 11),
+    "bcnn_hip_dilated_conv_backward": (None, [vp] * 7 + [i] * 11 + [vp, sz]),
     "bcnn_hip_lrn_forward": (None, [vp, vp] + [i] * 5 + [f] * 3),
     "bcnn_hip_lrn_backward": (None, [vp, vp, vp] + [i] * 5 + [f] * 3 + [i]),
     "bcnn_hip_dropout_forward": (None, [vp, sz, f, u64, u64]),

@@ -22,6 +22,7 @@ LOG_SILENT = 3
 IMAGE_FIT_STRETCH, IMAGE_FIT_LETTERBOX = 0, 1
 POOL2D_MAX, POOL2D_AVG = 0, 1
 LAYER_ACTIVATION, LAYER_POOL2D, LAYER_SCALE_CHANNELS, LAYER_GROUPNORM = 3, 17, 18, 19
+LAYER_CONV2D, LAYER_BATCHNORM, LAYER_DILATED_CONV2D = 0, 9, 20
 
 
 class Tensor(C.Structure):
@@ -107,6 +108,7 @@ def lib():
         "bcnn_add_convolutional_layer": (i, [vp, i, i, i, i, i, i, i, i, i, cp, cp]),
         "bcnn_add_depthwise_conv_layer": (i, [vp, i, i, i, i, i, i, cp, cp]),
         "bcnn_add_deconvolutional_layer": (i, [vp, i, i, i, i, i, i, cp, cp]),
+        "bcnn_add_dilated_conv_layer": (i, [vp, i, i, i, i, i, i, i, i, cp, cp]),
         "bcnn_add_lrn_layer": (i, [vp, i, f, f, f, cp, cp]), "bcnn_add_dropout_layer": (i, [vp, f, cp]),
         "bcnn_set_dropout_seed": (None, [vp, C.c_uint64]),
         "bcnn_get_lifted_struct_loss": (i, [vp, C.POINTER(f), C.POINTER(i)]),
@@ -190,6 +192,12 @@ class Net:
         """bcnn_add_deconvolutional_layer: f output channels, k x k kernel, stride s, pad p"""
         return self._added(self.L.bcnn_add_deconvolutional_layer(self.net, f, k, s, p, init, act, src.encode(),
                                                                   dst.encode()))
+
+    def dilated_conv(self, f, k, s, p, d, g=1, act=ACT_NONE, src="input", dst="dconv", init=FILLER_XAVIER):
+        """bcnn_add_dilated_conv_layer: f filters, k x k kernel with taps d apart, stride s, pad p, g groups; d == 1
+        builds an ordinary convolution node"""
+        return self._added(self.L.bcnn_add_dilated_conv_layer(self.net, f, k, s, p, d, g, init, act, src.encode(),
+                                                               dst.encode()))
 
     def lrn(self, local_size, alpha, beta, k=1.0, src="input", dst="lrn"):
         """bcnn_add_lrn_layer: local response normalisation across channels"""
@@ -306,7 +314,7 @@ class Net:
 
     def set_inference_precision(self, precision):
         """bcnn_set_inference_precision: PRECISION_BF16 runs every convolution node of a PREDICT / VALID forward on the
-        bf16 matrix cores (fp32 accumulator; depthwise, deconvolution and full-connected nodes stay fp32); a TRAIN-mode
+        bf16 matrix cores (fp32 accumulator; depthwise, deconvolution, dilated-convolution and full-connected nodes stay fp32); a TRAIN-mode
         pass is never affected. Returns the bcnn_status (1 = BCNN_INVALID_PARAMETER for an unknown value)."""
         return self.L.bcnn_set_inference_precision(self.net, precision)
 

@@ -197,6 +197,7 @@ typedef struct {
     int has_from; /* Darknet `from=`: src_id[0] is the previous section, src_id[1] the named one */
     int has_groups; /* [groupnorm]: the section wrote groups= (the default of num_groups, 1, belongs to convolutions) */
     float eps;      /* [groupnorm] / [layernorm] / [instancenorm]; 0: the builder's default */
+    int dilation;   /* [conv] / [convolutional]: > 1 builds the dilated-convolution node; default 1 */
 } layer_param;
 
 static void lp_reset(layer_param *lp) {
@@ -210,6 +211,7 @@ static void lp_reset(layer_param *lp) {
     lp->cost = BCNN_METRIC_SSE; lp->loss = BCNN_LOSS_EUCLIDEAN;
     lp->k = 1.0f; /* [lrn] without a k key: the Caffe / torch default */
     lp->count_include_pad = 1; /* [pool] type=avg: the Caffe / torch default */
+    lp->dilation = 1;
 }
 
 static void lp_set_srcs(layer_param *lp, const char *list) {
@@ -272,6 +274,7 @@ static void lp_set(bcnn_net *net, int section_idx, layer_param *lp, const char *
         else lp->pad = atoi(val) ? lp->size / 2 : 0; /* Darknet: boolean, needs `size` to come first */
     } else if (!strcmp(name, "num_groups") || !strcmp(name, "groups")) { lp->num_groups = atoi(val); lp->has_groups = 1; }
     else if (!strcmp(name, "eps")) lp->eps = (float)atof(val);
+    else if (!strcmp(name, "dilation")) lp->dilation = atoi(val);
     /* only [lrn] reads these three; atof, where the reference's atoi loads a Caffe LRN (alpha=0.0001) as the identity */
     else if (!strcmp(name, "alpha")) lp->alpha = (float)atof(val);
     else if (!strcmp(name, "beta")) lp->beta = (float)atof(val);
@@ -387,8 +390,22 @@ static bcnn_status add_layer(bcnn_net *net, const char *name, layer_param *lp) {
     BCNN_CHECK_AND_LOG(net->log_ctx, !needs_dst || dst, BCNN_INVALID_PARAMETER,
                        "Invalid output node name. Hint: Are you sure that 'dst' field is correctly setup?\n");
     if (!strcmp(name, "[input]")) return bcnn_add_input(net, lp->in_w, lp->in_h, lp->in_c, src);
+    if (is_any(name, "[conv]", "[convolutional]", NULL, NULL) && lp->dilation > 1) {
+        if (!lp->batchnorm)
+            return add_split_act(net, bcnn_add_dilated_conv_layer(net, lp->n_filts, lp->size, lp->stride, lp->pad, lp->dilation,
+                                                                  lp->num_groups, lp->init, fused_act(lp), src, dst), lp);
+        /* The dilated node has no fused batch-norm: the section becomes the node with no activation into "<dst>_dc", a
+         * batch-norm node from there into dst, and the activation in place on dst. The section still stands for dst. */
+        char inner[256];
+        snprintf(inner, sizeof(inner), "%s_dc", dst);
+        BCNN_CHECK_STATUS(bcnn_add_dilated_conv_layer(net, lp->n_filts, lp->size, lp->stride, lp->pad, lp->dilation,
+                                                      lp->num_groups, lp->init, BCNN_ACT_NONE, src, inner));
+        ((bcnn_dilated_conv_param *)net->nodes[net->num_nodes - 1].param)->section_bn = 1;
+        BCNN_CHECK_STATUS(bcnn_add_batchnorm_layer(net, inner, dst));
+        return lp->a == BCNN_ACT_NONE ? BCNN_SUCCESS : bcnn_add_activation_layer(net, lp->a, dst);
+    }
     if (is_any(name, "[conv]", "[convolutional]", NULL, NULL))
-        return add_split_act(net, bcnn_add_convolutional_layer(net, lp->n_filts, lp->size, lp->stride, lp->pad, lp->num_groups,
+        return add_split_act(net,bcnn_add_convolutional_layer(net, lp->n_filts, lp->size, lp->stride, lp->pad, lp->num_groups,
                                                                lp->batchnorm, lp->init, fused_act(lp), 0, src, dst), lp);
     if (is_any(name, "[deconv]", "[deconvolutional]", NULL, NULL))
         return add_split_act(net, bcnn_add_deconvolutional_layer(net, lp->n_filts, lp->size, lp->stride, lp->pad, lp->init,

@@ -584,9 +584,10 @@ static bcnn_status resize_plan(bcnn_net *net, int w, int h, int c, int need_real
          * [n][c][1][1] embedding the lifted-structure loss was built on (and its label) survive the call. */
         const bcnn_layer_type t = net->nodes[i].type;
         BCNN_CHECK_AND_LOG(net->log_ctx, t != BCNN_LAYER_CONCAT && t != BCNN_LAYER_UPSAMPLE && t != BCNN_LAYER_YOLOV3 &&
-                                             t != BCNN_LAYER_TRANSPOSE_CONV2D, BCNN_INVALID_PARAMETER,
-                           "bcnn_resize_net: node %d is a concat / upsample / YOLO / deconvolution node, whose resize is "
-                           "not supported\n", i);
+                                             t != BCNN_LAYER_TRANSPOSE_CONV2D && t != BCNN_LAYER_DILATED_CONV2D,
+                           BCNN_INVALID_PARAMETER,
+                           "bcnn_resize_net: node %d is a concat / upsample / YOLO / deconvolution / dilated-convolution "
+                           "node, whose resize is not supported\n", i);
         BCNN_CHECK_AND_LOG(net->log_ctx,
                            t != BCNN_LAYER_COST || ((const bcnn_cost_param *)net->nodes[i].param)->loss != BCNN_LOSS_LIFTED_STRUCT,
                            BCNN_INVALID_PARAMETER,
@@ -898,7 +899,8 @@ static void sgd_table_add(bcnn_hip_context *hc, float *w, float *g, size_t n, in
 /* update workers whose whole effect is bcnn_node_sgd_step on their own tensors: safe to replay from the table */
 static int update_is_tabled(const bcnn_node *nd) {
     return nd->update == bcnn_update_conv_layer || nd->update == bcnn_update_depthwise_conv_layer ||
-           nd->update == bcnn_update_fullc_layer || nd->update == bcnn_update_deconv_layer;
+           nd->update == bcnn_update_fullc_layer || nd->update == bcnn_update_deconv_layer ||
+           nd->update == bcnn_update_dilated_conv_layer;
 }
 
 void bcnn_update(bcnn_net *net) {
@@ -1119,6 +1121,8 @@ int bcnn_get_node_type(bcnn_net *net, int node) {
 int bcnn_get_node_activation(bcnn_net *net, int node) {
     if (node < 0 || node >= net->num_nodes) return -1;
     const bcnn_node *nd = &net->nodes[node];
+    if (nd->type == BCNN_LAYER_DILATED_CONV2D) /* (a constant behind the enum: no case label) */
+        return (int)((const bcnn_dilated_conv_param *)nd->param)->activation;
     switch (nd->type) {
         case BCNN_LAYER_CONV2D: return (int)((const bcnn_conv_param *)nd->param)->activation;
         case BCNN_LAYER_TRANSPOSE_CONV2D: return (int)((const bcnn_deconv_param *)nd->param)->activation;

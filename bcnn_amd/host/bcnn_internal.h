@@ -466,6 +466,20 @@ typedef struct bcnn_deconv_param {
 #endif
 } bcnn_deconv_param;
 
+/* dilated convolution (bcnn_add_dilated_conv_layer with dilation > 1; no reference counterpart); weights
+ * [num][c / num_groups][size][size] */
+typedef struct bcnn_dilated_conv_param {
+    int num, size, stride, pad, dilation, num_groups;
+    bcnn_activation activation;
+    int section_bn; /* the config loader split one section into this node, a batch-norm node and an activation node: a
+                       Darknet .weights file, which interleaves the section's values, cannot be loaded into them */
+#ifdef BCNN_USE_HIP
+    float *conv_workspace_gpu;  /* the node's own dW split partials (bcnn_hip_dilated_conv_workspace_size), first backward */
+    size_t workspace_size;
+    float *adam_m_gpu, *adam_v_gpu; /* weight moments, allocated by the first Adam step */
+#endif
+} bcnn_dilated_conv_param;
+
 /* local response normalisation across channels (reference src/layers/bcnn_lrn_layer.h); no buffers: the backward
  * recomputes the scale from the input */
 typedef struct bcnn_lrn_param {
@@ -561,6 +575,10 @@ void bcnn_forward_deconv_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_deconv_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_update_deconv_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_deconv_layer(bcnn_node *node);
+void bcnn_forward_dilated_conv_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_backward_dilated_conv_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_update_dilated_conv_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_release_param_dilated_conv_layer(bcnn_node *node);
 void bcnn_forward_lrn_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_lrn_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_lrn_layer(bcnn_node *node);

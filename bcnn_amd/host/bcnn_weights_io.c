@@ -2,7 +2,8 @@
  *
  * Byte-compatible with the reference (src/bcnn_net.c:595-681 writer, :1219-1558 reader):
  *   "BCNN" | u32 major | u32 minor | u32 patch | per node, in node order:
- *     conv / depthwise / full-connected : biases, weights [, conv with batch-norm: means, variances, scales]
+ *     conv / deconv / dilated conv / depthwise / full-connected : biases, weights [, conv with batch-norm: means,
+ *                                         variances, scales]
  *     PReLU activation node             : slopes
  *     batch-norm node                   : means, variances, scales, biases (dst channels each)
  *     group-norm node (no reference counterpart) : biases, scales (dst channels each)
@@ -45,7 +46,8 @@ bcnn_status bcnn_save_weights(bcnn_net *net, const char *filename) {
     for (int i = 0; ok && i < net->num_nodes; ++i) {
         bcnn_node *nd = &net->nodes[i];
         if (nd->type == BCNN_LAYER_CONV2D || nd->type == BCNN_LAYER_TRANSPOSE_CONV2D ||
-            nd->type == BCNN_LAYER_DEPTHWISE_CONV2D || nd->type == BCNN_LAYER_FULL_CONNECTED) {
+            nd->type == BCNN_LAYER_DILATED_CONV2D || nd->type == BCNN_LAYER_DEPTHWISE_CONV2D ||
+            nd->type == BCNN_LAYER_FULL_CONNECTED) {
             bcnn_tensor *w = &net->tensors[nd->src[1]], *b = &net->tensors[nd->src[2]];
             ok = put(fp, b, bcnn_tensor_size(b)) && put(fp, w, bcnn_tensor_size(w));
             if (ok && nd->type == BCNN_LAYER_CONV2D && ((bcnn_conv_param *)nd->param)->batch_norm == 1)
@@ -178,6 +180,15 @@ static bcnn_status load_fullc(bcnn_net *net, bcnn_node *nd, FILE *fp, int need_t
 bcnn_status bcnn_load_weights(bcnn_net *net, const char *filename) {
     BCNN_CHECK_AND_LOG(net->log_ctx, filename, BCNN_INVALID_PARAMETER, "Can not open file %s\n", "(null)");
     const int format = model_format(filename);
+    /* A config section with dilation > 1 and batch-norm is three nodes here; Darknet stores that section as biases, scales,
+     * means, variances, weights, an order the node-by-node reader below cannot follow. Refused before anything is read. */
+    for (int i = 0; format == 1 && i < net->num_nodes; ++i)
+        BCNN_CHECK_AND_LOG(net->log_ctx,
+                           net->nodes[i].type != BCNN_LAYER_DILATED_CONV2D ||
+                               !((const bcnn_dilated_conv_param *)net->nodes[i].param)->section_bn,
+                           BCNN_INVALID_MODEL,
+                           "Node %d is a dilated convolution whose section has batch-norm: Darknet .weights files are not "
+                           "supported for it, use the native model format\n", i);
     FILE *fp = fopen(filename, "rb");
     BCNN_CHECK_AND_LOG(net->log_ctx, fp, BCNN_INVALID_PARAMETER, "Can not open file %s\n", filename);
     int need_transpose = 0;
@@ -216,7 +227,7 @@ bcnn_status bcnn_load_weights(bcnn_net *net, const char *filename) {
     for (int i = 0; st == BCNN_SUCCESS && i < net->num_nodes; ++i) {
         bcnn_node *nd = &net->nodes[i];
         if (nd->type == BCNN_LAYER_CONV2D || nd->type == BCNN_LAYER_TRANSPOSE_CONV2D ||
-            nd->type == BCNN_LAYER_DEPTHWISE_CONV2D) {
+            nd->type == BCNN_LAYER_DILATED_CONV2D || nd->type == BCNN_LAYER_DEPTHWISE_CONV2D) {
             st = load_conv(net, nd, fp, format);
         } else if (nd->type == BCNN_LAYER_ACTIVATION) {
             if (((bcnn_activation_param *)nd->param)->activation == BCNN_ACT_PRELU && format == 0) {

@@ -112,6 +112,36 @@ def deconv_backward(x, wt, y, dy, dx, dw, dbias, k, stride, pad, act, workspace)
                                          workspace.numel() if workspace is not None else 0)
 
 
+def dilated_conv_out_hw(h, w, k, s, p, d):
+    """extent of a k x k kernel with taps d apart: torch.nn.functional.conv2d(dilation=d)"""
+    return (h + 2 * p - d * (k - 1) - 1) // s + 1, (w + 2 * p - d * (k - 1) - 1) // s + 1
+
+
+def dilated_conv_workspace_size(n, c, h, w, f, k, s, p, d, g=1):
+    return int(_lib.load().bcnn_hip_dilated_conv_workspace_size(n, c, h, w, f, k, s, p, d, g))
+
+
+def dilated_conv_forward(x, wt, bias, y, k, stride, pad, dilation, groups=1, act=0):
+    """bcnn_hip_dilated_conv_forward (conv_dilated.hip). wt: [f][c / groups][k][k] (any shape of that size), y is
+    overwritten with act(dilated convolution + bias)."""
+    n, c, h, w = x.shape
+    f = y.shape[1]
+    assert wt.numel() == f * (c // groups) * k * k
+    _lib.load().bcnn_hip_dilated_conv_forward(_f32(x), _f32(wt), _f32(bias), _f32(y), n, c, h, w, f, k, stride, pad,
+                                              dilation, groups, act)
+
+
+def dilated_conv_backward(x, wt, y, dy, dx, dw, dbias, k, stride, pad, dilation, groups, act, workspace):
+    """bcnn_hip_dilated_conv_backward. dy is updated in place (dy * act'(y)), dbias and dw accumulate (dw += x dyᵀ, no
+    scaling), dx (may be None) is overwritten. workspace: at least f * (c / groups) * k * k floats."""
+    n, c, h, w = x.shape
+    f = y.shape[1]
+    assert wt.numel() == f * (c // groups) * k * k
+    _lib.load().bcnn_hip_dilated_conv_backward(_f32(x), _f32(wt), _f32(y), _f32(dy), _f32(dx), _f32(dw), _f32(dbias), n,
+                                               c, h, w, f, k, stride, pad, dilation, groups, act, _f32(workspace),
+                                               workspace.numel() if workspace is not None else 0)
+
+
 def lrn_forward(x, y, local_size, alpha, beta, k):
     """LRN across channels (include/bcnn_hip.h; the reference's bcnn_lrn_layer.c:106-149 with its deviations fixed):
     y = x * (k + alpha/n sum_window x^2)^-beta, overwritten."""

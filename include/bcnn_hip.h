@@ -988,6 +988,29 @@ void bcnn_hip_deconv_backward(const float *x_d, const float *w_d, const float *y
                               int act, float *workspace_d, size_t workspace_elems);
 
 /* ---------------------------------------------------------------------------------------------
+ * Dilated (atrous) convolution, implicit GEMMs on fp32 MFMA with no im2col / col2im buffer and no zero-expanded weights
+ * (conv_dilated.hip). No reference counterpart; torch.nn.functional.conv2d(stride, padding, dilation, groups) is the oracle.
+ *   - x [n][c][h][w], weights [f][c / groups][k][k], bias [f], y [n][f][oh][ow] with
+ *     oh = (h + 2 pad - dilation (k - 1) - 1) / stride + 1; groups divides c and f; dilation >= 1 (1: a plain convolution);
+ *   - forward: y = act(conv + bias), OVERWRITTEN; out-of-range taps read zero; PReLU is not supported;
+ *   - backward: dy_d <- dy_d * act'(y_d) in place; dbias += sum dy; dw += sum x dy (beta = 1, no scaling, as the
+ *     convolution node); dx_d (if non-NULL) is OVERWRITTEN; dw_d may be NULL (no weight gradient).
+ * workspace_d: at least bcnn_hip_dilated_conv_workspace_size(...) floats (the K-split partials of dw; a smaller one of
+ * at least f (c / groups) k k floats splits less; smaller than that, or NULL with dw_d set, ends the process). The split is
+ * a function of the shape and workspace_elems only and the partials are added in split order: the weight gradient is
+ * bit-identical from run to run. An unsupported shape (a non-positive extent, a tensor of 2^31 elements or more) ends the
+ * process with a message.
+ * ------------------------------------------------------------------------------------------- */
+size_t bcnn_hip_dilated_conv_workspace_size(int n, int c, int h, int w, int f, int k, int stride, int pad, int dilation,
+                                            int groups);
+void bcnn_hip_dilated_conv_forward(const float *x_d, const float *w_d, const float *bias_d, float *y_d, int n, int c,
+                                   int h, int w, int f, int k, int stride, int pad, int dilation, int groups, int act);
+void bcnn_hip_dilated_conv_backward(const float *x_d, const float *w_d, const float *y_d, float *dy_d, float *dx_d,
+                                    float *dw_d, float *dbias_d, int n, int c, int h, int w, int f, int k, int stride,
+                                    int pad, int dilation, int groups, int act, float *workspace_d,
+                                    size_t workspace_elems);
+
+/* ---------------------------------------------------------------------------------------------
  * Local response normalisation across channels (Caffe / torch.nn.functional.local_response_norm). The reference's
  * device workers are empty (bcnn_lrn_layer.c:207-225); its CPU workers (:106-201) are wrong for every local_size
  * (INTEGRATION.md). NCHW, channel stride h*w; with n_w = local_size:
