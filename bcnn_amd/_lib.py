@@ -150,6 +150,9 @@ SIGNATURES = {
     "bcnn_hip_dilated_conv_workspace_size": (sz, [i] * 10),
     "bcnn_hip_dilated_conv_forward": (None, [vp, vp, vp, vp] + [i] * 11),
     "bcnn_hip_dilated_conv_backward": (None, [vp] * 7 + [i] * 11 + [vp, sz]),
+    "bcnn_hip_interp_forward": (None, [vp, vp, vp, i, i, i, i]),
+    "bcnn_hip_interp_backward": (None, [vp, vp, vp, i, i, i, i, i]),
+    "bcnn_hip_interp_axis_taps": (None, [i, i, i, vp, vp, vp]),
     "bcnn_hip_lrn_forward": (None, [vp, vp] + [i] * 5 + [f] * 3),
     "bcnn_hip_lrn_backward": (None, [vp, vp, vp] + [i] * 5 + [f] * 3 + [i]),
     "bcnn_hip_dropout_forward": (None, [vp, sz, f, u64, u64]),

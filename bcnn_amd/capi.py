@@ -22,7 +22,7 @@ LOG_SILENT = 3
 IMAGE_FIT_STRETCH, IMAGE_FIT_LETTERBOX = 0, 1
 POOL2D_MAX, POOL2D_AVG = 0, 1
 LAYER_ACTIVATION, LAYER_POOL2D, LAYER_SCALE_CHANNELS, LAYER_GROUPNORM = 3, 17, 18, 19
-LAYER_CONV2D, LAYER_BATCHNORM, LAYER_DILATED_CONV2D = 0, 9, 20
+LAYER_CONV2D, LAYER_BATCHNORM, LAYER_DILATED_CONV2D, LAYER_INTERP = 0, 9, 20, 21
 
 
 class Tensor(C.Structure):
@@ -109,6 +109,7 @@ def lib():
         "bcnn_add_depthwise_conv_layer": (i, [vp, i, i, i, i, i, i, cp, cp]),
         "bcnn_add_deconvolutional_layer": (i, [vp, i, i, i, i, i, i, cp, cp]),
         "bcnn_add_dilated_conv_layer": (i, [vp, i, i, i, i, i, i, i, i, cp, cp]),
+        "bcnn_add_interp_layer": (i, [vp, i, i, i, i, i, cp, cp]),
         "bcnn_add_lrn_layer": (i, [vp, i, f, f, f, cp, cp]), "bcnn_add_dropout_layer": (i, [vp, f, cp]),
         "bcnn_set_dropout_seed": (None, [vp, C.c_uint64]),
         "bcnn_get_lifted_struct_loss": (i, [vp, C.POINTER(f), C.POINTER(i)]),
@@ -267,6 +268,12 @@ class Net:
 
     def upsample(self, size, src, dst):
         return self._added(self.L.bcnn_add_upsample_layer(self.net, size, src.encode(), dst.encode()))
+
+    def interp(self, src, dst, scale=0, zoom=0, out_w=0, out_h=0, align_corners=False):
+        """bcnn_add_interp_layer: bilinear interpolation to in * scale, to (in - 1) * zoom + 1 or to out_w x out_h (exactly
+        one form) -- torch's interpolate(mode="bilinear", align_corners=...); Caffe-DeepLab's Interp is align_corners"""
+        return self._added(self.L.bcnn_add_interp_layer(self.net, out_w, out_h, scale, zoom, 1 if align_corners else 0,
+                                                        src.encode(), dst.encode()))
 
     def yolo(self, num, classes, mask, anchors, src, dst, coords=4):
         """bcnn_add_yolo_layer: `mask` (num anchor indices), `anchors` (2 * total extents) or None (all 0.5 x total)"""

@@ -61,6 +61,7 @@ enum ScratchSlot {
     SCRATCH_DETECT,        // current stream: image sizes, counts, sort order and box records of the batched YOLO decode (detect.hip)
     SCRATCH_IMAGES,        // current stream: descriptors, tap tables and uint8 pixels of the batched input fill (image_fill.hip)
     SCRATCH_AUGMENT,       // current stream: records, channel sums, tap tables, raw and augmented uint8 samples of a training batch (augment.hip)
+    SCRATCH_INTERP,        // current stream: tap and contributor-range tables of one bilinear interpolation call (interp.hip)
     SCRATCH_SLOTS
 };
 // A block of at least `floats` floats for `slot` on the calling thread's device; valid until that slot's next call.
@@ -116,7 +117,21 @@ inline int stream_grid(size_t work_items, int block) {
     return (int)(need < cap ? need : cap);
 }
 
+// a / d by multiply-high with magic = ceil(2^32 / d): exact while a * d < 2^32; the host passes magic 0 where that does not
+// hold for the largest dividend of the launch (or d == 1), and the kernel divides (pool2d.hip, interp.hip)
+struct FastDiv {
+    unsigned d, magic;
+};
+inline FastDiv make_fdiv(unsigned d, unsigned long long max_dividend) {
+    FastDiv f;
+    f.d = d;
+    f.magic = d > 1 && max_dividend * d < (1ULL << 32) ? (unsigned)((0x100000000ULL + d - 1) / d) : 0u;
+    return f;
+}
+
 #ifdef __HIPCC__
+__device__ __forceinline__ unsigned fdiv(unsigned a, const FastDiv& f) { return f.magic ? __umulhi(a, f.magic) : a / f.d; }
+
 // XCD-aware block remap: the dispatcher places block b on XCD b % 8; give each XCD a contiguous run
 // of logical tiles so neighbours (which share operand panels / halos) hit the same L2.
 // Bijective for any nblk (guide section 5 "XCD swizzle must be bijective").

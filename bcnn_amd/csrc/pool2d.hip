@@ -19,19 +19,6 @@ namespace bcnn_hip {
 
 enum { POOL_MAX = BCNN_HIP_POOL2D_MAX, POOL_AVG = BCNN_HIP_POOL2D_AVG };
 
-// a / d by multiply-high with magic = ceil(2^32 / d): exact while a * d < 2^32; the host passes magic 0 where that does not
-// hold for the largest dividend of the launch (or d == 1), and the kernel divides
-struct FastDiv {
-    unsigned d, magic;
-};
-__device__ __forceinline__ unsigned fdiv(unsigned a, const FastDiv& f) { return f.magic ? __umulhi(a, f.magic) : a / f.d; }
-static FastDiv make_fdiv(unsigned d, unsigned long long max_dividend) {
-    FastDiv f;
-    f.d = d;
-    f.magic = d > 1 && max_dividend * d < (1ULL << 32) ? (unsigned)((0x100000000ULL + d - 1) / d) : 0u;
-    return f;
-}
-
 struct Pool2dGeom {
     int H, W, OH, OW, size, stride, pad, include_pad;
 };

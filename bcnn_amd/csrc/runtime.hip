@@ -39,6 +39,7 @@ static constexpr ScratchPolicy kScratchPolicy[] = {  // in ScratchSlot order
     /* DETECT        */ {1u << 16, 1, 1},  // the caller's record capacity already carries the headroom
     /* IMAGES        */ {1u << 18, 5, 4},  // 1 MiB to start with; frame sizes vary from batch to batch
     /* AUGMENT       */ {1u << 18, 1, 1},  // 1 MiB to start with; a loader's batches all have one size
+    /* INTERP        */ {1u << 14, 2, 1},  // 64 KiB: 4 floats per output row / column, 2 per input row / column
 };
 static_assert(sizeof(kScratchPolicy) / sizeof(kScratchPolicy[0]) == SCRATCH_SLOTS, "one policy row per ScratchSlot");
 struct ScratchBlock { float* p = nullptr; size_t cap = 0; };

@@ -198,6 +198,7 @@ typedef struct {
     int has_groups; /* [groupnorm]: the section wrote groups= (the default of num_groups, 1, belongs to convolutions) */
     float eps;      /* [groupnorm] / [layernorm] / [instancenorm]; 0: the builder's default */
     int dilation;   /* [conv] / [convolutional]: > 1 builds the dilated-convolution node; default 1 */
+    int scale, zoom, out_w, out_h, align_corners; /* [interp] / [bilinear]; scale= may be written stride= (has_stride) */
 } layer_param;
 
 static void lp_reset(layer_param *lp) {
@@ -275,6 +276,11 @@ static void lp_set(bcnn_net *net, int section_idx, layer_param *lp, const char *
     } else if (!strcmp(name, "num_groups") || !strcmp(name, "groups")) { lp->num_groups = atoi(val); lp->has_groups = 1; }
     else if (!strcmp(name, "eps")) lp->eps = (float)atof(val);
     else if (!strcmp(name, "dilation")) lp->dilation = atoi(val);
+    else if (!strcmp(name, "scale")) lp->scale = atoi(val);
+    else if (!strcmp(name, "zoom")) lp->zoom = atoi(val);
+    else if (!strcmp(name, "out_w")) lp->out_w = atoi(val);
+    else if (!strcmp(name, "out_h")) lp->out_h = atoi(val);
+    else if (!strcmp(name, "align_corners")) lp->align_corners = atoi(val);
     /* only [lrn] reads these three; atof, where the reference's atoi loads a Caffe LRN (alpha=0.0001) as the identity */
     else if (!strcmp(name, "alpha")) lp->alpha = (float)atof(val);
     else if (!strcmp(name, "beta")) lp->beta = (float)atof(val);
@@ -431,6 +437,16 @@ static bcnn_status add_layer(bcnn_net *net, const char *name, layer_param *lp) {
                                      lp->count_include_pad, src, dst);
     }
     if (!strcmp(name, "[upsample]")) return bcnn_add_upsample_layer(net, lp->stride, src, dst);
+    if (is_any(name, "[interp]", "[bilinear]", NULL, NULL)) {
+        /* exactly one of scale= (Darknet's word: stride=), zoom= and out_w= / out_h=; the builder refuses anything else.
+         * As the first section it reads the net input whatever src says, like every other first section. */
+        BCNN_CHECK_AND_LOG(net->log_ctx, lp->a == BCNN_ACT_NONE, BCNN_INVALID_PARAMETER,
+                           "Interp layer %s: only activation=linear is supported; add an [activation] section\n", dst);
+        BCNN_CHECK_AND_LOG(net->log_ctx, !(lp->scale && lp->has_stride), BCNN_INVALID_PARAMETER,
+                           "Interp layer %s: scale= and stride= are two words for one key\n", dst);
+        return bcnn_add_interp_layer(net, lp->out_w, lp->out_h, lp->has_stride ? lp->stride : lp->scale, lp->zoom,
+                                     lp->align_corners, net->num_nodes == 0 ? net->tensors[0].name : src, dst);
+    }
     if (!strcmp(name, "[dropout]")) return bcnn_add_dropout_layer(net, lp->rate, src);
     if (is_any(name, "[concat]", "[route]", NULL, NULL))
         return bcnn_add_concat_layer(net, lp->num_srcs, (char *const *)lp->src_id, dst);

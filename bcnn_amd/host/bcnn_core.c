@@ -403,11 +403,12 @@ static void mark_dead_grad_fills(bcnn_net *net) {
          * the forward -> backward order every caller of the reference uses (bcnn_train_on_batch). */
         if (uses == 1 && (nd->type == BCNN_LAYER_MAXPOOL || nd->type == BCNN_LAYER_DEPTHWISE_CONV2D ||
                           nd->type == BCNN_LAYER_LRN || nd->type == BCNN_LAYER_POOL2D ||
-                          nd->type == BCNN_LAYER_GROUPNORM)) {
+                          nd->type == BCNN_LAYER_GROUPNORM || nd->type == BCNN_LAYER_INTERP)) {
             /* max-pooling's gather, the depthwise data gradient (a gather too: one thread owns a dx element,
              * bcnn_depthwise_conv_layer.c:432-547 accumulates onto the zero fill), LRN's (one lane per column), the
-             * pool2d gather, whose overwrite form also writes the elements no window covers, and group-norm's sweep (one
-             * thread owns a dx element) */
+             * pool2d gather, whose overwrite form also writes the elements no window covers, group-norm's sweep (one
+             * thread owns a dx element) and the bilinear interpolation's gather, whose overwrite form also writes the
+             * elements a downsampling skips */
             hc->grad_fill_dead[t] = 2;
             continue;
         }
@@ -571,6 +572,8 @@ static int node_dst_shape(const bcnn_node *nd, const bcnn_tensor *s, bcnn_tensor
         ow = (s->w - 1) / p->stride + 1;
     } else if (nd->type == BCNN_LAYER_POOL2D) {
         if (!bcnn_pool2d_out_extents((const bcnn_pool2d_param *)nd->param, s->h, s->w, &oh, &ow)) return 0;
+    } else if (nd->type == BCNN_LAYER_INTERP) { /* scale and zoom follow the source, the fixed form keeps its extents */
+        if (!bcnn_interp_out_extents((const bcnn_interp_param *)nd->param, s->h, s->w, &oh, &ow)) return 0;
     }
     bcnn_tensor_set_shape(d, s->n, oc, oh, ow, 1);
     return 1;
@@ -601,7 +604,8 @@ static bcnn_status resize_plan(bcnn_net *net, int w, int h, int c, int need_real
         const bcnn_tensor *s = &plan[nd->src[0]];
         bcnn_tensor *d = &plan[nd->dst[0]];
         BCNN_CHECK_AND_LOG(net->log_ctx, keeps_producer_shape(nd) || node_dst_shape(nd, s, d), BCNN_INVALID_PARAMETER,
-                           "bcnn_resize_net: node %d pools a %d x %d tensor, smaller than its padded window\n", i, s->w, s->h);
+                           "bcnn_resize_net: node %d refuses a %d x %d source (a pooling window larger than the padded tensor, or an "
+                           "interpolation extent out of range)\n", i, s->w, s->h);
         BCNN_CHECK_AND_LOG(net->log_ctx, need_realloc || node_reserve_buffers(nd, d, 0) == BCNN_SUCCESS,
                            BCNN_INVALID_PARAMETER,
                            "bcnn_resize_net: node %d keeps a buffer for the backward pass that is smaller than the new shape; "

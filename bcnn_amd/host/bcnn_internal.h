@@ -500,6 +500,12 @@ typedef struct bcnn_pool2d_param {
 #endif
 } bcnn_pool2d_param;
 
+/* bilinear interpolation (bcnn_add_interp_layer; no reference counterpart). Exactly one of scale, zoom and
+ * (out_w, out_h) is set; no device buffer of its own */
+typedef struct bcnn_interp_param {
+    int scale, zoom, out_w, out_h, align_corners;
+} bcnn_interp_param;
+
 /* in-place dropout (reference src/layers/bcnn_dropout_layer.h); the mask is regenerated from (key, step) of the last
  * TRAIN forward instead of being stored (include/bcnn_hip.h) */
 typedef struct bcnn_dropout_param {
@@ -598,6 +604,10 @@ void bcnn_backward_pool2d_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_pool2d_layer(bcnn_node *node);
 /* bcnn_layers_pool2d.c: the node's output extents for an h x w source; 0 if the parameters refuse that source */
 int bcnn_pool2d_out_extents(const bcnn_pool2d_param *p, int h, int w, int *out_h, int *out_w);
+void bcnn_forward_interp_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_backward_interp_layer(bcnn_net *net, bcnn_node *node);
+/* bcnn_layers_interp.c: the node's output extents for an h x w source (the builder's rule); 0 if the extents are refused */
+int bcnn_interp_out_extents(const bcnn_interp_param *p, int h, int w, int *out_h, int *out_w);
 
 /* SGD step on one node's parameters (bcnn_learner.c:67-104 in the reference) */
 void bcnn_link_depthwise_batchnorm(bcnn_net *net); /* bcnn_layers_hot.c; called by bcnn_compile_net */

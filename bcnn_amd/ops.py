@@ -254,6 +254,57 @@ def pool2d_out_hw(kind, h, w, size, stride, pad=0, ceil_mode=False):
     return int(L.bcnn_hip_pool2d_out_extent(_C.byref(d), h)), int(L.bcnn_hip_pool2d_out_extent(_C.byref(d), w))
 
 
+class InterpDesc(_C.Structure):
+    """struct bcnn_hip_interp_desc (include/bcnn_hip.h)"""
+    _fields_ = [("out_h", _C.c_int), ("out_w", _C.c_int), ("align_corners", _C.c_int)]
+
+
+def interp_out_hw(h, w, scale=0, zoom=0, out_h=0, out_w=0):
+    """the interp node's output extents, exactly one form: scale >= 1 (in * scale), zoom >= 1 ((in - 1) * zoom + 1,
+    Caffe-DeepLab's Interp) or out_h, out_w > 0; (0, 0) for anything else, an extent of 2^31 - 1 or more included.
+    A restatement in Python for shaping tensors: the library's rule is bcnn_interp_out_extent (csrc/interp_rule.h), which
+    is inline in the builder and in bcnn_resize_net and not exported; tests/test_interp_graph.py holds the node's shapes
+    to this function."""
+    if min(h, w) < 1 or min(scale, zoom, out_h, out_w) < 0 or (out_h > 0) != (out_w > 0):
+        return 0, 0
+    if (scale > 0) + (zoom > 0) + (out_w > 0) != 1:
+        return 0, 0
+    if scale:
+        out = h * scale, w * scale
+    elif zoom:
+        out = (h - 1) * zoom + 1, (w - 1) * zoom + 1
+    else:
+        out = out_h, out_w
+    return out if max(out) < 0x7fffffff else (0, 0)
+
+
+def interp_forward(x, y, align_corners=False):
+    """bcnn_hip_interp_forward: y (its shape gives the output extents) = bilinear interpolation of x, the rule of
+    torch.nn.functional.interpolate(x, size=y.shape[2:], mode="bilinear", align_corners=align_corners)"""
+    n, c, h, w = x.shape
+    assert tuple(y.shape[:2]) == (n, c) and y.dim() == 4, "y is [n][c][out_h][out_w]"
+    d = InterpDesc(y.shape[2], y.shape[3], 1 if align_corners else 0)
+    _lib.load().bcnn_hip_interp_forward(_C.byref(d), _f32(x), _f32(y), n, c, h, w)
+
+
+def interp_backward(dy, dx, align_corners=False, overwrite=False):
+    """bcnn_hip_interp_backward: dx += (overwrite: dx = 0 +) the gathered gradient of interp_forward; no atomics"""
+    n, c, h, w = dx.shape
+    assert tuple(dy.shape[:2]) == (n, c) and dy.dim() == 4, "dy is [n][c][out_h][out_w]"
+    d = InterpDesc(dy.shape[2], dy.shape[3], 1 if align_corners else 0)
+    _lib.load().bcnn_hip_interp_backward(_C.byref(d), _f32(dy), _f32(dx), n, c, h, w, 1 if overwrite else 0)
+
+
+def interp_axis_taps(size_in, size_out, align_corners=False):
+    """bcnn_hip_interp_axis_taps (host code of the library, no device): numpy (i0, i1, l1) of one axis"""
+    import numpy as np
+    i0, i1 = np.zeros(size_out, np.int32), np.zeros(size_out, np.int32)
+    l1 = np.zeros(size_out, np.float32)
+    _lib.load().bcnn_hip_interp_axis_taps(size_in, size_out, 1 if align_corners else 0, i0.ctypes.data, i1.ctypes.data,
+                                          l1.ctypes.data)
+    return i0, i1, l1
+
+
 def pool2d_forward(x, y, indexes, kind, size, stride, pad=0, ceil_mode=False, count_include_pad=True):
     """bcnn_hip_pool2d_forward: windowed max / average pooling with `pad` on all four sides. indexes (int32, y's shape)
     may be None: max pooling then stores no winners; average pooling never does."""

@@ -66,6 +66,8 @@ typedef enum {
 #define BCNN_LAYER_GROUPNORM ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 2))
 /* The layer type of bcnn_add_dilated_conv_layer with dilation > 1, likewise a constant behind the enumerator list. */
 #define BCNN_LAYER_DILATED_CONV2D ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 3))
+/* The layer type of bcnn_add_interp_layer, likewise a constant behind the enumerator list. */
+#define BCNN_LAYER_INTERP ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 4))
 
 typedef enum {
     BCNN_ACT_NONE, BCNN_ACT_TANH, BCNN_ACT_RELU, BCNN_ACT_RAMP, BCNN_ACT_SOFTPLUS,
@@ -300,6 +302,24 @@ BCNN_API bcnn_status bcnn_add_eltwise_layer(bcnn_net *net, bcnn_activation activ
                                             const char *src_id2, const char *dst_id);
 BCNN_API bcnn_status bcnn_add_dropout_layer(bcnn_net *net, float rate, const char *id);
 BCNN_API bcnn_status bcnn_add_upsample_layer(bcnn_net *net, int size, const char *src_id, const char *dst_id);
+/* New, without a reference counterpart: bilinear interpolation of every plane of src to a new extent, with a gradient --
+ * torch.nn.functional.interpolate(mode="bilinear", align_corners=...) with the extents given as size=; Caffe-DeepLab's
+ * Interp layer is align_corners = 1. The upsample builder above keeps its meaning (nearest neighbour, integer factor).
+ *   The output extent is given in exactly one of three forms, the other arguments 0:
+ *     scale >= 1               out = in * scale
+ *     zoom >= 1                out = (in - 1) * zoom + 1      (Interp's zoom_factor: 65 -> 513 with zoom 8)
+ *     out_w > 0 && out_h > 0   out_w x out_h; downsampling is allowed
+ *   Per axis (float32, every operation rounded on its own): align_corners != 0: src = o * (in - 1) / (out - 1), 0 for
+ *   out == 1; align_corners == 0: src = max((o + 0.5) * in / out - 0.5, 0). i0 = min((int)src, in - 1), i1 = i0 + 1
+ *   clipped to the axis, l1 = src - i0 clamped to [0, 1], l0 = 1 - l1; dst = h0 (w0 a + w1 b) + h1 (w0 c + w1 d).
+ *   Backward: a gather without atomics, the same bits on every run. It adds into the source gradient (assigns when it is
+ *   its sole writer); a source without a gradient buffer is skipped.
+ * Refused with BCNN_INVALID_PARAMETER and a log line, nothing added to the net: an unknown src name, a negative argument,
+ * no form or more than one, only one of out_w and out_h, an output extent of 2^31 - 1 or more. May be the first node of a
+ * net (src_id is then the input tensor's name). Works in TRAIN, VALID and PREDICT mode in fp32, has no weights (model
+ * files skip it) and follows bcnn_resize_net: scale and zoom follow the new source extent, the fixed form keeps its own. */
+BCNN_API bcnn_status bcnn_add_interp_layer(bcnn_net *net, int out_w, int out_h, int scale, int zoom, int align_corners,
+                                           const char *src_id, const char *dst_id);
 BCNN_API bcnn_status bcnn_add_cost_layer(bcnn_net *net, bcnn_loss loss, bcnn_loss_metric loss_metric, float scale,
                                          const char *src_id, const char *label_id, const char *dst_id);
 BCNN_API bcnn_status bcnn_add_yolo_layer(bcnn_net *net, int num_boxes_per_cell, int num_classes, int coords,

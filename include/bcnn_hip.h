@@ -412,6 +412,33 @@ void bcnn_hip_pool2d_backward(const bcnn_hip_pool2d_desc *desc, const float *dy_
                               int c, int h, int w, int overwrite);
 
 /* ---------------------------------------------------------------------------------------------
+ * Bilinear interpolation to a given extent (the interp node; interp.hip). No reference counterpart: the semantics are
+ * those of torch.nn.functional.interpolate(mode="bilinear", size=(out_h, out_w)) for both values of align_corners.
+ *   Per axis, input extent I, output extent O, output index o, all in float32 and every operation rounded on its own
+ *   (csrc/interp_rule.h is the one definition; host and device share it):
+ *     align_corners != 0: s = O > 1 ? (float)(I - 1) / (float)(O - 1) : 0;  src = s * (float)o
+ *     align_corners == 0: s = (float)I / (float)O;  src = max(s * ((float)o + 0.5f) - 0.5f, 0)
+ *     i0 = min((int)src, I - 1);  i1 = i0 + (i0 < I - 1);  l1 = clamp(src - (float)i0, 0, 1);  l0 = 1 - l1
+ *   forward : y = h0 * (w0 * x[y0][x0] + w1 * x[y0][x1]) + h1 * (w0 * x[y1][x0] + w1 * x[y1][x1]) in this association
+ *     (h*: the row weights l0 / l1, w*: the column weights). Every element of y is written.
+ *   backward: gather form, one thread per source element, no atomics, the same bits on every run: dx += the sum of
+ *     h * (w * dy) over every (output row, output column, row tap, column tap) that names the element, output rows and
+ *     columns ascending, tap 0 before tap 1. overwrite != 0: the caller guarantees dx is semantically all-zero (this node
+ *     is the gradient's only writer and the zero fill was skipped): dx = 0 + the same sums, and an element no output
+ *     names (downsampling) becomes 0; with overwrite == 0 such an element keeps its bits.
+ *   bcnn_hip_interp_axis_taps: host only, needs no device: i0[o], i1[o], l1[o] for o in [0, out) by the same rule.
+ *   Tensors of 2^31 elements or more, and extents below 1, exit like the other entry points handed a shape they cannot run.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct bcnn_hip_interp_desc {
+    int out_h, out_w;
+    int align_corners; /* 0: half-pixel centres (torch's default) */
+} bcnn_hip_interp_desc;
+void bcnn_hip_interp_forward(const bcnn_hip_interp_desc *desc, const float *x_d, float *y_d, int n, int c, int h, int w);
+void bcnn_hip_interp_backward(const bcnn_hip_interp_desc *desc, const float *dy_d, float *dx_d, int n, int c, int h, int w,
+                              int overwrite);
+void bcnn_hip_interp_axis_taps(int in, int out, int align_corners, int *i0, int *i1, float *l1);
+
+/* ---------------------------------------------------------------------------------------------
  * Channel scaling (the scale-channels node; scale_channels.hip). No reference counterpart.
  *   x is [n][c][hw]; gate is [n][c] (same_shape == 0: one factor per plane) or [n][c][hw] (same_shape != 0).
  *   forward : y = x * gate, one multiply per element (8 bytes per element moved, 12 with a same-shape gate).
