@@ -153,6 +153,10 @@ SIGNATURES = {
     "bcnn_hip_interp_forward": (None, [vp, vp, vp, i, i, i, i]),
     "bcnn_hip_interp_backward": (None, [vp, vp, vp, i, i, i, i, i]),
     "bcnn_hip_interp_axis_taps": (None, [i, i, i, vp, vp, vp]),
+    "bcnn_hip_softmax_loss_forward": (None, [vp, vp, vp, vp, vp, i, i, i]),
+    "bcnn_hip_softmax_loss_backward": (None, [vp, vp, vp, vp, vp, i, i, i, i]),
+    "bcnn_hip_softmax_loss_confusion": (None, [vp, vp, vp, vp, i, i, i]),
+    "bcnn_hip_softmax_loss_c_reg": (i, []),
     "bcnn_hip_lrn_forward": (None, [vp, vp] + [i] * 5 + [f] * 3),
     "bcnn_hip_lrn_backward": (None, [vp, vp, vp] + [i] * 5 + [f] * 3 + [i]),
     "bcnn_hip_dropout_forward": (None, [vp, sz, f, u64, u64]),

@@ -23,6 +23,9 @@ IMAGE_FIT_STRETCH, IMAGE_FIT_LETTERBOX = 0, 1
 POOL2D_MAX, POOL2D_AVG = 0, 1
 LAYER_ACTIVATION, LAYER_POOL2D, LAYER_SCALE_CHANNELS, LAYER_GROUPNORM = 3, 17, 18, 19
 LAYER_CONV2D, LAYER_BATCHNORM, LAYER_DILATED_CONV2D, LAYER_INTERP = 0, 9, 20, 21
+LAYER_SOFTMAX_LOSS = 22
+LOSS_NORM_NONE, LOSS_NORM_VALID, LOSS_NORM_VALID_PER_IMAGE = 0, 1, 2
+LOSS_NORMS = {"none": LOSS_NORM_NONE, "valid": LOSS_NORM_VALID, "valid_per_image": LOSS_NORM_VALID_PER_IMAGE}
 
 
 class Tensor(C.Structure):
@@ -42,6 +45,12 @@ class YoloTrainStats(C.Structure):
     """struct bcnn_yolo_train_stats (include/bcnn/bcnn.h)."""
     _fields_ = [("avg_iou", C.c_float), ("avg_class", C.c_float), ("avg_obj", C.c_float), ("avg_anyobj", C.c_float),
                 ("recall50", C.c_float), ("recall75", C.c_float), ("count", C.c_int), ("cost", C.c_float)]
+
+
+class SoftmaxLossStats(C.Structure):
+    """struct bcnn_softmax_loss_stats (include/bcnn/bcnn.h)."""
+    _fields_ = [("loss", C.c_float), ("valid", C.c_int64), ("ignored", C.c_int64), ("out_of_range", C.c_int64),
+                ("correct", C.c_int64)]
 
 
 _libc = C.CDLL(None)
@@ -110,6 +119,9 @@ def lib():
         "bcnn_add_deconvolutional_layer": (i, [vp, i, i, i, i, i, i, cp, cp]),
         "bcnn_add_dilated_conv_layer": (i, [vp, i, i, i, i, i, i, i, i, cp, cp]),
         "bcnn_add_interp_layer": (i, [vp, i, i, i, i, i, cp, cp]),
+        "bcnn_add_softmax_loss_layer": (i, [vp, i, i, f, cp, cp, cp]),
+        "bcnn_get_softmax_loss_stats": (i, [vp, i, C.POINTER(SoftmaxLossStats)]),
+        "bcnn_get_confusion_matrix": (i, [vp, i, C.POINTER(C.c_int64)]),
         "bcnn_add_lrn_layer": (i, [vp, i, f, f, f, cp, cp]), "bcnn_add_dropout_layer": (i, [vp, f, cp]),
         "bcnn_set_dropout_seed": (None, [vp, C.c_uint64]),
         "bcnn_get_lifted_struct_loss": (i, [vp, C.POINTER(f), C.POINTER(i)]),
@@ -274,6 +286,30 @@ class Net:
         one form) -- torch's interpolate(mode="bilinear", align_corners=...); Caffe-DeepLab's Interp is align_corners"""
         return self._added(self.L.bcnn_add_interp_layer(self.net, out_w, out_h, scale, zoom, 1 if align_corners else 0,
                                                         src.encode(), dst.encode()))
+
+    def softmax_loss(self, src, dst, ignore_label=-1, normalize="valid_per_image", scale=1.0):
+        """bcnn_add_softmax_loss_layer: softmax over the channels of src and cross-entropy against the class-index label
+        map in tensor 1 ([n][1][h][w], floats); normalize: "none", "valid", "valid_per_image" or a LOSS_NORM_* value"""
+        return self._added(self.L.bcnn_add_softmax_loss_layer(self.net, ignore_label, LOSS_NORMS.get(normalize, normalize),
+                                                              scale, src.encode(), b"label", dst.encode()))
+
+    def softmax_loss_stats(self, node):
+        """bcnn_get_softmax_loss_stats of the node's latest TRAIN / VALID forward, as a dict (loss, valid, ignored,
+        out_of_range, correct); raises ValueError when the node has none (not such a node, a PREDICT forward)"""
+        out = SoftmaxLossStats()
+        st = self.L.bcnn_get_softmax_loss_stats(self.net, node, C.byref(out))
+        if st != 0:
+            raise ValueError("node %d has no softmax-loss statistics (status %d)" % (node, st))
+        return {name: getattr(out, name) for name, _ in SoftmaxLossStats._fields_}
+
+    def confusion_matrix(self, node):
+        """bcnn_get_confusion_matrix: the C x C int64 matrix (row = label, column = argmax) of the node's latest forward"""
+        c = self.shape(self.node_dst(node))[1]
+        counts = np.zeros((c, c), np.int64)
+        st = self.L.bcnn_get_confusion_matrix(self.net, node, counts.ctypes.data_as(C.POINTER(C.c_int64)))
+        if st != 0:
+            raise ValueError("node %d has no confusion matrix (status %d)" % (node, st))
+        return counts
 
     def yolo(self, num, classes, mask, anchors, src, dst, coords=4):
         """bcnn_add_yolo_layer: `mask` (num anchor indices), `anchors` (2 * total extents) or None (all 0.5 x total)"""

@@ -199,6 +199,10 @@ typedef struct {
     float eps;      /* [groupnorm] / [layernorm] / [instancenorm]; 0: the builder's default */
     int dilation;   /* [conv] / [convolutional]: > 1 builds the dilated-convolution node; default 1 */
     int scale, zoom, out_w, out_h, align_corners; /* [interp] / [bilinear]; scale= may be written stride= (has_stride) */
+    /* [softmax_loss] / [softmaxwithloss]: ignore_label (default -1), normalize (a bcnn_loss_norm, -1: a value the section
+     * wrote that is none of the three names; default valid_per_image) and scale= read as a float (default 1) */
+    int ignore_label, loss_norm;
+    float loss_scale;
 } layer_param;
 
 static void lp_reset(layer_param *lp) {
@@ -213,6 +217,7 @@ static void lp_reset(layer_param *lp) {
     lp->k = 1.0f; /* [lrn] without a k key: the Caffe / torch default */
     lp->count_include_pad = 1; /* [pool] type=avg: the Caffe / torch default */
     lp->dilation = 1;
+    lp->ignore_label = -1; lp->loss_norm = (int)BCNN_LOSS_NORM_VALID_PER_IMAGE; lp->loss_scale = 1.0f;
 }
 
 static void lp_set_srcs(layer_param *lp, const char *list) {
@@ -276,7 +281,14 @@ static void lp_set(bcnn_net *net, int section_idx, layer_param *lp, const char *
     } else if (!strcmp(name, "num_groups") || !strcmp(name, "groups")) { lp->num_groups = atoi(val); lp->has_groups = 1; }
     else if (!strcmp(name, "eps")) lp->eps = (float)atof(val);
     else if (!strcmp(name, "dilation")) lp->dilation = atoi(val);
-    else if (!strcmp(name, "scale")) lp->scale = atoi(val);
+    else if (!strcmp(name, "scale")) { lp->scale = atoi(val); lp->loss_scale = (float)atof(val); }
+    else if (!strcmp(name, "ignore_label")) lp->ignore_label = atoi(val);
+    else if (!strcmp(name, "normalize")) {
+        if (!strcmp(val, "none")) lp->loss_norm = (int)BCNN_LOSS_NORM_NONE;
+        else if (!strcmp(val, "valid")) lp->loss_norm = (int)BCNN_LOSS_NORM_VALID;
+        else if (!strcmp(val, "valid_per_image")) lp->loss_norm = (int)BCNN_LOSS_NORM_VALID_PER_IMAGE;
+        else lp->loss_norm = -1; /* refused by the section that reads it: no silent fallback */
+    }
     else if (!strcmp(name, "zoom")) lp->zoom = atoi(val);
     else if (!strcmp(name, "out_w")) lp->out_w = atoi(val);
     else if (!strcmp(name, "out_h")) lp->out_h = atoi(val);
@@ -492,6 +504,12 @@ static bcnn_status add_layer(bcnn_net *net, const char *name, layer_param *lp) {
         }
         return bcnn_add_yolo_layer(net, lp->boxes_per_cell, lp->num_classes, lp->num_coords, lp->num_anchors,
                                    lp->anchors_mask, lp->anchors, src, dst);
+    }
+    if (is_any(name, "[softmax_loss]", "[softmaxwithloss]", NULL, NULL)) {
+        BCNN_CHECK_AND_LOG(net->log_ctx, lp->loss_norm >= 0, BCNN_INVALID_PARAMETER,
+                           "Softmax-loss layer %s: normalize must be none, valid or valid_per_image\n", dst);
+        return bcnn_add_softmax_loss_layer(net, lp->ignore_label, (bcnn_loss_norm)lp->loss_norm, lp->loss_scale, src, "label",
+                                           dst);
     }
     if (!strcmp(name, "[cost]")) return bcnn_add_cost_layer(net, lp->loss, lp->cost, 1.0f, src, "label", dst);
     bcnn_log(net->log_ctx, BCNN_LOG_ERROR, "Unknown Layer %s\n", name);

@@ -403,12 +403,14 @@ static void mark_dead_grad_fills(bcnn_net *net) {
          * the forward -> backward order every caller of the reference uses (bcnn_train_on_batch). */
         if (uses == 1 && (nd->type == BCNN_LAYER_MAXPOOL || nd->type == BCNN_LAYER_DEPTHWISE_CONV2D ||
                           nd->type == BCNN_LAYER_LRN || nd->type == BCNN_LAYER_POOL2D ||
-                          nd->type == BCNN_LAYER_GROUPNORM || nd->type == BCNN_LAYER_INTERP)) {
+                          nd->type == BCNN_LAYER_GROUPNORM || nd->type == BCNN_LAYER_INTERP ||
+                          nd->type == BCNN_LAYER_SOFTMAX_LOSS)) {
             /* max-pooling's gather, the depthwise data gradient (a gather too: one thread owns a dx element,
              * bcnn_depthwise_conv_layer.c:432-547 accumulates onto the zero fill), LRN's (one lane per column), the
              * pool2d gather, whose overwrite form also writes the elements no window covers, group-norm's sweep (one
-             * thread owns a dx element) and the bilinear interpolation's gather, whose overwrite form also writes the
-             * elements a downsampling skips */
+             * thread owns a dx element), the bilinear interpolation's gather, whose overwrite form also writes the
+             * elements a downsampling skips, and the softmax loss, whose overwrite form writes +0.0 on the pixels that are
+             * not valid */
             hc->grad_fill_dead[t] = 2;
             continue;
         }
@@ -610,6 +612,13 @@ static bcnn_status resize_plan(bcnn_net *net, int w, int h, int c, int need_real
                            BCNN_INVALID_PARAMETER,
                            "bcnn_resize_net: node %d keeps a buffer for the backward pass that is smaller than the new shape; "
                            "call with need_realloc\n", i);
+        /* the class-index label map of a softmax-loss node follows as [n][1][h][w] */
+        BCNN_CHECK_AND_LOG(net->log_ctx,
+                           nd->type != BCNN_LAYER_SOFTMAX_LOSS || need_realloc ||
+                               (size_t)d->n * d->h * d->w <= ((const bcnn_softmax_loss_param *)nd->param)->label_capacity,
+                           BCNN_INVALID_PARAMETER,
+                           "bcnn_resize_net: the label map of softmax-loss node %d would outgrow its allocation; call with "
+                           "need_realloc\n", i);
     }
     return BCNN_SUCCESS;
 }
@@ -624,6 +633,15 @@ static bcnn_status resize_commit(bcnn_net *net, int w, int h, int c, int need_re
         if (!keeps_producer_shape(nd)) {
             node_dst_shape(nd, &net->tensors[nd->src[0]], d);
             if (need_realloc && bcnn_tensor_allocate(d, net->mode) != BCNN_SUCCESS) return BCNN_FAILED_ALLOC;
+        }
+        if (nd->type == BCNN_LAYER_SOFTMAX_LOSS) { /* the label map follows the new shape */
+            bcnn_softmax_loss_param *p = (bcnn_softmax_loss_param *)nd->param;
+            bcnn_tensor *label = &net->tensors[1];
+            bcnn_tensor_set_shape(label, d->n, 1, d->h, d->w, 0);
+            if (need_realloc) {
+                if (bcnn_tensor_allocate(label, net->mode) != BCNN_SUCCESS) return BCNN_FAILED_ALLOC;
+                p->label_capacity = (size_t)d->n * d->h * d->w;
+            }
         }
         if (!need_realloc) continue; /* the plan found every buffer large enough */
         if (node_reserve_buffers(nd, d, 1) != BCNN_SUCCESS) return BCNN_FAILED_ALLOC;
@@ -984,7 +1002,8 @@ void bcnn_node_optim_step(bcnn_net *net, bcnn_tensor *weights, bcnn_tensor *bias
 }
 
 /* reference bcnn_get_loss, bcnn_net.c:431-449. The heads' costs live on the device: with detector training on, a TRAIN
- * net reads every head's record here, once, at the end of the step. */
+ * net reads every head's record here, once, at the end of the step. So does every softmax-loss node's loss (0 after a
+ * PREDICT forward). */
 static float current_loss(bcnn_net *net) {
     float loss = 0.f;
     int n = 0;
@@ -995,6 +1014,9 @@ static float current_loss(bcnn_net *net) {
             ++n;
         } else if (heads && net->nodes[i].type == BCNN_LAYER_YOLOV3) {
             loss += ((const bcnn_yolo_param *)net->nodes[i].param)->cost[0];
+            ++n;
+        } else if (net->nodes[i].type == BCNN_LAYER_SOFTMAX_LOSS) { /* counted like a cost node; its record is read here */
+            loss += bcnn_softmax_loss_read_loss(net, &net->nodes[i]);
             ++n;
         }
     return n ? loss / n : 0.f;

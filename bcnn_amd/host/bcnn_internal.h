@@ -506,6 +506,18 @@ typedef struct bcnn_interp_param {
     int scale, zoom, out_w, out_h, align_corners;
 } bcnn_interp_param;
 
+/* softmax + cross-entropy against a class-index label map (bcnn_add_softmax_loss_layer; no reference counterpart) */
+typedef struct bcnn_softmax_loss_param {
+    int ignore_label;
+    bcnn_loss_norm norm;
+    float scale;
+    int has_stats;         /* the latest forward wrote the record (TRAIN / VALID with a label on the device) */
+    size_t label_capacity; /* floats the label tensor was allocated with by this node (bcnn_tensor has no capacity) */
+#ifdef BCNN_USE_HIP
+    float *record_gpu;     /* bcnn_hip_softmax_loss_record: 6 words */
+#endif
+} bcnn_softmax_loss_param;
+
 /* in-place dropout (reference src/layers/bcnn_dropout_layer.h); the mask is regenerated from (key, step) of the last
  * TRAIN forward instead of being stored (include/bcnn_hip.h) */
 typedef struct bcnn_dropout_param {
@@ -608,6 +620,11 @@ void bcnn_forward_interp_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_interp_layer(bcnn_net *net, bcnn_node *node);
 /* bcnn_layers_interp.c: the node's output extents for an h x w source (the builder's rule); 0 if the extents are refused */
 int bcnn_interp_out_extents(const bcnn_interp_param *p, int h, int w, int *out_h, int *out_w);
+void bcnn_forward_softmax_loss_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_backward_softmax_loss_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_release_param_softmax_loss_layer(bcnn_node *node);
+/* bcnn_layers_softmax_loss.c: the loss of the node's latest forward, read from its device record; 0 without statistics */
+float bcnn_softmax_loss_read_loss(bcnn_net *net, bcnn_node *node);
 
 /* SGD step on one node's parameters (bcnn_learner.c:67-104 in the reference) */
 void bcnn_link_depthwise_batchnorm(bcnn_net *net); /* bcnn_layers_hot.c; called by bcnn_compile_net */

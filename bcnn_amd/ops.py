@@ -305,6 +305,77 @@ def interp_axis_taps(size_in, size_out, align_corners=False):
     return i0, i1, l1
 
 
+LOSS_NORM_NONE, LOSS_NORM_VALID, LOSS_NORM_VALID_PER_IMAGE = 0, 1, 2
+LOSS_NORMS = {"none": LOSS_NORM_NONE, "valid": LOSS_NORM_VALID, "valid_per_image": LOSS_NORM_VALID_PER_IMAGE}
+
+
+class SoftmaxLossDesc(_C.Structure):
+    """struct bcnn_hip_softmax_loss_desc (include/bcnn_hip.h)"""
+    _fields_ = [("ignore_label", _C.c_int), ("norm", _C.c_int), ("scale", _C.c_float)]
+
+
+class SoftmaxLossRecord(_C.Structure):
+    """struct bcnn_hip_softmax_loss_record (include/bcnn_hip.h): what a forward with a label leaves on the device"""
+    _fields_ = [("loss", _C.c_float), ("grad_factor", _C.c_float), ("valid", _C.c_int), ("ignored", _C.c_int),
+                ("out_of_range", _C.c_int), ("correct", _C.c_int)]
+
+
+def softmax_loss_c_reg():
+    """the largest class count whose logits the pixel kernels of the softmax loss hold in registers"""
+    return int(_lib.load().bcnn_hip_softmax_loss_c_reg())
+
+
+def softmax_loss_record():
+    """a zeroed device record (6 words, as an int32 tensor) for softmax_loss_forward / softmax_loss_backward"""
+    import torch
+    return torch.zeros(_C.sizeof(SoftmaxLossRecord) // 4, dtype=torch.int32, device="cuda")
+
+
+def softmax_loss_read_record(record):
+    """the device record as a dict (loss, grad_factor, valid, ignored, out_of_range, correct); synchronises"""
+    raw = record.cpu().numpy().tobytes()
+    r = SoftmaxLossRecord.from_buffer_copy(raw)
+    return {name: getattr(r, name) for name, _ in SoftmaxLossRecord._fields_}
+
+
+def _softmax_loss_desc(ignore_label, normalize, scale):
+    return SoftmaxLossDesc(int(ignore_label), LOSS_NORMS.get(normalize, normalize), float(scale))
+
+
+def softmax_loss_forward(x, label, p, record, ignore_label=-1, normalize="valid_per_image", scale=1.0):
+    """bcnn_hip_softmax_loss_forward: p = softmax over dim 1 of x ([n][C][hw] or [n][C][h][w]); with `label` ([n][1][...],
+    class indices as floats) and `record` also the loss, scale / D and the counts, into the record. label None: p only."""
+    n, c = x.shape[:2]
+    hw = x.numel() // max(n * c, 1)
+    assert p.numel() == x.numel() and (label is None or label.numel() == n * hw)
+    d = _softmax_loss_desc(ignore_label, normalize, scale)
+    _lib.load().bcnn_hip_softmax_loss_forward(_C.byref(d), _f32(x), _f32(label) if label is not None else None, _f32(p),
+                                              record.data_ptr() if record is not None else None, n, c, hw)
+
+
+def softmax_loss_backward(p, label, record, dx, ignore_label=-1, normalize="valid_per_image", scale=1.0, overwrite=False):
+    """bcnn_hip_softmax_loss_backward: dx += (overwrite: dx =) record.grad_factor * (p - onehot(label)) on valid pixels"""
+    n, c = p.shape[:2]
+    hw = p.numel() // max(n * c, 1)
+    assert dx.numel() == p.numel() and label.numel() == n * hw
+    d = _softmax_loss_desc(ignore_label, normalize, scale)
+    _lib.load().bcnn_hip_softmax_loss_backward(_C.byref(d), _f32(p), _f32(label), record.data_ptr(), _f32(dx), n, c, hw,
+                                               1 if overwrite else 0)
+
+
+def softmax_loss_confusion(p, label, ignore_label=-1):
+    """bcnn_hip_softmax_loss_confusion: the C x C matrix (row = label, column = first argmax of p) over valid pixels, as an
+    int64 numpy array; synchronises"""
+    import torch
+    n, c = p.shape[:2]
+    hw = p.numel() // max(n * c, 1)
+    assert label.numel() == n * hw
+    counts = torch.empty(c * c, dtype=torch.int32, device=p.device)
+    d = _softmax_loss_desc(ignore_label, LOSS_NORM_NONE, 1.0)
+    _lib.load().bcnn_hip_softmax_loss_confusion(_C.byref(d), _f32(p), _f32(label), counts.data_ptr(), n, c, hw)
+    return counts.cpu().numpy().astype("int64").reshape(c, c)
+
+
 def pool2d_forward(x, y, indexes, kind, size, stride, pad=0, ceil_mode=False, count_include_pad=True):
     """bcnn_hip_pool2d_forward: windowed max / average pooling with `pad` on all four sides. indexes (int32, y's shape)
     may be None: max pooling then stores no winners; average pooling never does."""

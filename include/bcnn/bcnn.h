@@ -68,6 +68,8 @@ typedef enum {
 #define BCNN_LAYER_DILATED_CONV2D ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 3))
 /* The layer type of bcnn_add_interp_layer, likewise a constant behind the enumerator list. */
 #define BCNN_LAYER_INTERP ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 4))
+/* The layer type of bcnn_add_softmax_loss_layer, likewise a constant behind the enumerator list. */
+#define BCNN_LAYER_SOFTMAX_LOSS ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 5))
 
 typedef enum {
     BCNN_ACT_NONE, BCNN_ACT_TANH, BCNN_ACT_RELU, BCNN_ACT_RAMP, BCNN_ACT_SOFTPLUS,
@@ -88,6 +90,14 @@ typedef enum {
     BCNN_METRIC_ERROR_RATE, BCNN_METRIC_LOGLOSS, BCNN_METRIC_SSE, BCNN_METRIC_MSE, BCNN_METRIC_CRPS,
     BCNN_METRIC_DICE
 } bcnn_loss_metric;
+
+/* The denominator D of the softmax-loss node (bcnn_add_softmax_loss_layer): loss = (sum l) / D, dx = scale / D * (p - y).
+ * V is the number of valid pixels of the batch of n images. */
+typedef enum {
+    BCNN_LOSS_NORM_NONE,           /* D = 1: with no ignored pixel, the gradient of the softmax -> Euclidean cost chain */
+    BCNN_LOSS_NORM_VALID,          /* D = max(V, 1): torch's reduction="mean", Caffe's VALID */
+    BCNN_LOSS_NORM_VALID_PER_IMAGE /* D = max(V, 1) / n: the learner divides by n again, so the step is the mean over V */
+} bcnn_loss_norm;
 
 typedef enum { BCNN_PADDING_SAME, BCNN_PADDING_VALID, BCNN_PADDING_CAFFE } bcnn_padding;
 
@@ -325,6 +335,39 @@ BCNN_API bcnn_status bcnn_add_cost_layer(bcnn_net *net, bcnn_loss loss, bcnn_los
 BCNN_API bcnn_status bcnn_add_yolo_layer(bcnn_net *net, int num_boxes_per_cell, int num_classes, int coords,
                                          int total, int *mask, float *anchors, const char *src_id,
                                          const char *dst_id);
+/* New, without a reference counterpart: softmax over the channels of src ([n][C][h][w] logits) and cross-entropy against a
+ * class-index label map -- torch's F.cross_entropy(src, label, ignore_index=ignore_label). The softmax and cost builders
+ * above keep their meaning. dst is [n][C][h][w] and holds the probabilities; the label is tensor 1, which the builder
+ * shapes and allocates as [n][1][h][w]: class indices stored as floats, written and uploaded by the caller
+ * (bcnn_upload_tensor(net, 1, 0)). label_id is ignored like the cost builder's.
+ *   One label value t is: ignored if ignore_label >= 0 and t == ignore_label; valid if it is an integer value in [0, C);
+ *   out of range otherwise (negative, >= C, fractional, not finite) -- that pixel contributes nothing, like an ignored
+ *   one, and is counted on its own. ignore_label < 0: nothing is ignored on purpose.
+ *   loss = (sum over valid pixels of lse(x) - x[t]) / D and dx = scale / D * (p - [c == t]), exactly +0.0 on every other
+ *   pixel, with D by `norm` (bcnn_loss_norm above). V = 0 gives loss 0 and a zero gradient. bcnn_update divides every
+ *   gradient by the batch size again: BCNN_LOSS_NORM_VALID_PER_IMAGE makes the step the mean over the valid pixels.
+ *   TRAIN and VALID forwards compute probabilities, loss and counts on the device without a host synchronisation;
+ *   bcnn_train_on_batch / bcnn_predict_on_batch return the loss like a cost node's, read once at the end of the step.
+ *   A PREDICT forward writes the probabilities only. The node's own dst gradient is never read or written.
+ * Refused with BCNN_INVALID_PARAMETER and a log line, nothing added or allocated: the first node of a net, an unknown src
+ * name, an unknown norm, ignore_label >= 2^24 (no float holds it as an index), a label tensor another node has already
+ * shaped differently (a cost node, a YOLO head under detector training). Weightless (model files skip it); follows
+ * bcnn_resize_net: dst follows src, the label becomes [n][1][h][w] -- re-allocated with need_realloc, refused in the plan
+ * phase when it would outgrow its allocation without. */
+BCNN_API bcnn_status bcnn_add_softmax_loss_layer(bcnn_net *net, int ignore_label, bcnn_loss_norm norm, float scale,
+                                                 const char *src_id, const char *label_id, const char *dst_id);
+/* What the latest TRAIN / VALID forward of softmax-loss node `node` left in its device record (one 24-byte read).
+ * BCNN_INVALID_PARAMETER, *out zeroed: not such a node, or its latest forward computed no statistics (PREDICT mode, no
+ * forward yet). */
+typedef struct {
+    float loss;
+    int64_t valid, ignored, out_of_range, correct; /* correct: valid pixels whose first argmax of the logits is the label */
+} bcnn_softmax_loss_stats;
+BCNN_API bcnn_status bcnn_get_softmax_loss_stats(bcnn_net *net, int node, bcnn_softmax_loss_stats *out);
+/* counts[t * C + a] = valid pixels with label t whose first argmax of the probabilities is a, from the probabilities and
+ * the label the latest forward left on the device (one kernel, launched by this call; not on the training path). Its trace
+ * is the record's `correct`, its total `valid`. BCNN_INVALID_PARAMETER: not such a node, counts NULL, no label on the device. */
+BCNN_API bcnn_status bcnn_get_confusion_matrix(bcnn_net *net, int node, int64_t *counts);
 
 /* ---------------------------------------------------------------------------------------------
  * Additions of the MI355X build (no reference counterpart).

@@ -439,6 +439,50 @@ void bcnn_hip_interp_backward(const bcnn_hip_interp_desc *desc, const float *dy_
 void bcnn_hip_interp_axis_taps(int in, int out, int align_corners, int *i0, int *i1, float *l1);
 
 /* ---------------------------------------------------------------------------------------------
+ * Softmax over the channels + cross-entropy against a class-index label map (the softmax-loss node; softmax_loss.hip).
+ * No reference counterpart: torch's F.cross_entropy(x, t, ignore_index=...) with three normalisers.
+ *   x, p, dx are [n][c][hw]; label is [n][1][hw], class indices stored as floats. One label value t is (the one definition
+ *   is csrc/softmax_loss_rule.h, shared by host and device):
+ *     ignored       ignore_label >= 0 and t == (float)ignore_label
+ *     valid         t is an integer value in [0, c)
+ *     out of range  anything else (negative, >= c, fractional, not finite): contributes like an ignored pixel, is counted
+ *                   on its own, never indexes memory
+ *   forward : p = softmax over c of x (float arithmetic, one reciprocal per pixel). With label_d and record_d:
+ *     l = log(sum_c exp(x_c - max)) - (x_t - max) per valid pixel, V = the number of valid pixels,
+ *     D = 1 (norm 0, NONE), max(V, 1) (norm 1, VALID) or max(V, 1) / n (norm 2, VALID_PER_IMAGE),
+ *     record = {(sum l) / D, scale / D, V, ignored, out of range, valid pixels whose first argmax of x is t}.
+ *     The sums are per-workgroup partials (l in double) added in a fixed order by a finalize kernel: no host
+ *     synchronisation, no floating-point atomics, the same bits on every run. label_d or record_d NULL: p only.
+ *   backward: dx += record.grad_factor * (p - [c == t]) on valid pixels; the elements of every other pixel keep their bits.
+ *     overwrite != 0: the caller guarantees dx is semantically all-zero: dx = the same values, +0.0 on the other pixels.
+ *     Reads the record on the device: nothing is read back on the host between forward and backward.
+ *   confusion: counts_d[t * c + a] (c * c unsigned, zeroed by the call) = valid pixels with label t whose first argmax
+ *     of p is a. Not on the training path; integer atomics.
+ *   16-byte accesses when hw % 4 == 0 and the tensors of the call are 16-byte aligned, 4-byte accesses otherwise. The
+ *   forward's dispatch is a function of (c, hw, alignment) alone; bcnn_hip_softmax_loss_c_reg() is the largest c whose
+ *   logits the pixel kernels hold in registers. Tensors of 2^31 elements or more, an ignore label of 2^24 or more and an
+ *   unknown normaliser exit like the other entry points handed arguments they cannot run.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct bcnn_hip_softmax_loss_desc {
+    int ignore_label; /* negative: no label is ignored on purpose */
+    int norm;         /* 0 none, 1 valid, 2 valid per image (bcnn_loss_norm of include/bcnn/bcnn.h) */
+    float scale;
+} bcnn_hip_softmax_loss_desc;
+typedef struct bcnn_hip_softmax_loss_record {
+    float loss;        /* (sum l) / D */
+    float grad_factor; /* scale / D */
+    int valid, ignored, out_of_range, correct;
+} bcnn_hip_softmax_loss_record;
+void bcnn_hip_softmax_loss_forward(const bcnn_hip_softmax_loss_desc *desc, const float *x_d, const float *label_d, float *p_d,
+                                   bcnn_hip_softmax_loss_record *record_d, int n, int c, int hw);
+void bcnn_hip_softmax_loss_backward(const bcnn_hip_softmax_loss_desc *desc, const float *p_d, const float *label_d,
+                                    const bcnn_hip_softmax_loss_record *record_d, float *dx_d, int n, int c, int hw,
+                                    int overwrite);
+void bcnn_hip_softmax_loss_confusion(const bcnn_hip_softmax_loss_desc *desc, const float *p_d, const float *label_d,
+                                     unsigned *counts_d, int n, int c, int hw);
+int bcnn_hip_softmax_loss_c_reg(void);
+
+/* ---------------------------------------------------------------------------------------------
  * Channel scaling (the scale-channels node; scale_channels.hip). No reference counterpart.
  *   x is [n][c][hw]; gate is [n][c] (same_shape == 0: one factor per plane) or [n][c][hw] (same_shape != 0).
  *   forward : y = x * gate, one multiply per element (8 bytes per element moved, 12 with a same-shape gate).
