@@ -138,6 +138,7 @@ SIGNATURES = {
     "bcnn_hip_jpeg_stage_run": (i, [vp, f, i, f, f, f]),
     "bcnn_hip_jpeg_stage_cancel": (None, []),
     "bcnn_hip_augment_batch": (i, [vp, i, i, i, i, i, i, i, vp, vp, vp, i]),
+    "bcnn_hip_augment_label_batch": (i, [vp, i, i, i, i, vp, vp, vp, i]),
     "bcnn_hip_augment_jpeg_begin": (i, [i, i, i, i, i, vp, vp]),
     "bcnn_hip_augment_jpeg_run": (i, [vp, vp, vp, vp, vp, vp, i]),
     "bcnn_hip_augment_jpeg_cancel": (None, []),

@@ -19,6 +19,8 @@ PADDING_SAME, PADDING_VALID, PADDING_CAFFE = 0, 1, 2
 FILLER_FIXED, FILLER_XAVIER, FILLER_MSRA = 0, 1, 2
 LOSS_EUCLIDEAN, LOSS_LIFTED_STRUCT = 0, 1
 LOG_SILENT = 3
+(LOAD_MNIST, LOAD_CIFAR10, LOAD_CLASSIFICATION_LIST, LOAD_REGRESSION_LIST, LOAD_DETECTION_LIST) = range(5)
+LOAD_SEGMENTATION_LIST = 6  # BCNN_NUM_LOADERS + 1: a constant behind the enumerator list (bcnn.h)
 IMAGE_FIT_STRETCH, IMAGE_FIT_LETTERBOX = 0, 1
 POOL2D_MAX, POOL2D_AVG = 0, 1
 LAYER_ACTIVATION, LAYER_POOL2D, LAYER_SCALE_CHANNELS, LAYER_GROUPNORM = 3, 17, 18, 19
@@ -141,6 +143,7 @@ def lib():
         "bcnn_get_loader_device_decoded": (i, [vp]),
         "bcnn_set_loader_detection_on_device": (i, [vp, i]), "bcnn_get_loader_detection_on_device": (i, [vp]),
         "bcnn_get_loader_device_letterboxed": (i, [vp]),
+        "bcnn_get_loader_device_labels": (i, [vp]), "bcnn_loader_next": (i, [vp]),
         "bcnn_set_loader_effects": (i, [vp, i]), "bcnn_get_loader_effects": (i, [vp]),
         "bcnn_set_detector_training": (i, [vp, i]), "bcnn_get_detector_training": (i, [vp]),
         "bcnn_yolo_get_train_stats": (i, [vp, i, C.POINTER(YoloTrainStats)]),
@@ -399,6 +402,20 @@ class Net:
     def loader_device_letterboxed(self):
         """bcnn_get_loader_device_letterboxed: samples of the latest bcnn_loader_next that were letterboxed on the device"""
         return self.L.bcnn_get_loader_device_letterboxed(self.net)
+
+    def set_data_loader(self, kind, train, train_extra=None, test=None, test_extra=None):
+        """bcnn_set_data_loader: opens the train / test streams of one of the LOAD_* formats; returns the status.
+        LOAD_SEGMENTATION_LIST ("image-path mask-path" lines) needs a softmax-loss node in the net."""
+        enc = lambda s: s.encode() if s else None
+        return self.L.bcnn_set_data_loader(self.net, kind, enc(train), enc(train_extra), enc(test), enc(test_extra))
+
+    def loader_next(self):
+        """bcnn_loader_next: one batch into tensors 0 and 1 (host and device); returns the status"""
+        return self.L.bcnn_loader_next(self.net)
+
+    def loader_device_labels(self):
+        """bcnn_get_loader_device_labels: label maps of the latest bcnn_loader_next that were made on the device"""
+        return self.L.bcnn_get_loader_device_labels(self.net)
 
     def set_loader_effects(self, on):
         """bcnn_set_loader_effects: bcnn_loader_next applies Perlin distortion (max_distortion) and random spotlights

@@ -63,6 +63,7 @@ enum ScratchSlot {
     SCRATCH_AUGMENT,       // current stream: records, channel sums, tap tables, raw and augmented uint8 samples of a training batch (augment.hip)
     SCRATCH_INTERP,        // current stream: tap and contributor-range tables of one bilinear interpolation call (interp.hip)
     SCRATCH_SOFTMAX_LOSS,  // current stream: per-workgroup loss and count partials of one softmax-loss forward (softmax_loss.hip)
+    SCRATCH_AUGMENT_LABEL, // current stream: records, tap tables and raw uint8 masks of a batch of label maps (augment_label.hip)
     SCRATCH_SLOTS
 };
 // A block of at least `floats` floats for `slot` on the calling thread's device; valid until that slot's next call.

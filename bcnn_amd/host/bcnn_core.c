@@ -828,6 +828,10 @@ int bcnn_get_loader_device_letterboxed(const bcnn_net *net) {
     return net ? ((const bcnn_hip_context *)net->hip_ctx)->loader_device_letterboxed : 0;
 }
 
+int bcnn_get_loader_device_labels(const bcnn_net *net) {
+    return net ? ((const bcnn_hip_context *)net->hip_ctx)->loader_device_labels : 0;
+}
+
 bcnn_status bcnn_set_loader_effects(bcnn_net *net, int on) {
     if (!net) return BCNN_INVALID_PARAMETER;
     hctx(net)->loader_effects = on ? 1 : 0;

@@ -22,6 +22,10 @@
  *            planar RGB), BCNN_LOAD_CLASSIFICATION_LIST ("path label" lines), BCNN_LOAD_REGRESSION_LIST ("path v0 v1 ..").
  *            BCNN_LOAD_DETECTION_LIST ("path (class x y w h)*" lines: bcnn_detection_loader.c) letterboxes the image onto a
  *            canvas of 128 and moves the boxes with it; it needs detector training or a net that holds a YOLO head.
+ *            BCNN_LOAD_SEGMENTATION_LIST ("image-path mask-path" lines, no reference counterpart) is read by
+ *            bcnn_data_segmentation.c through the doors near the end of this file; it needs a softmax-loss node.
+ *   class-index labels: on a net that holds a softmax-loss node and whose label slot is one float, the classification
+ *            readers write the class index itself instead of a one-hot row (write_class_label).
  *
  * Behaviours of the reference that are kept on purpose (each is visible to a consumer that compares runs):
  *   - bcnn_augment_data_with_flip stores its flag in `apply_fliph`, the flip only happens when the INI key `flip_h` has set
@@ -614,6 +618,23 @@ static float *label_slot(bcnn_net *net, int idx, int *label_sz) {
     return y;
 }
 
+static int has_softmax_loss(const bcnn_net *net) {
+    for (int i = 0; i < net->num_nodes; ++i)
+        if (net->nodes[i].type == BCNN_LAYER_SOFTMAX_LOSS) return 1;
+    return 0;
+}
+
+/* The label of a classification sample into slot idx: a one-hot row (a class outside the row leaves it zero), or, on a net
+ * that holds a softmax-loss node and whose slot is one float ([n][1][1][1]), the class index itself, as that node reads it
+ * (a negative class is written as is: the node counts it as out of range). */
+static void write_class_label(bcnn_net *net, int idx, int cls) {
+    int sz;
+    float *y = label_slot(net, idx, &sz);
+    const bcnn_tensor *lab = &net->tensors[1];
+    if (sz == 1 && lab->c == 1 && lab->h == 1 && lab->w == 1 && has_softmax_loss(net)) y[0] = (float)cls;
+    else if (cls >= 0 && cls < sz) y[cls] = 1;
+}
+
 static bcnn_status check_input_shape(bcnn_net *net) {
     if (net->tensors[0].w > 0 && net->tensors[0].h > 0 && net->tensors[0].c > 0) return BCNN_SUCCESS;
     bcnn_log(net->log_ctx, BCNN_LOG_ERROR, "Input's width, height and channels must be > 0\n");
@@ -680,11 +701,7 @@ static bcnn_status mnist_next(bcnn_loader *it, bcnn_net *net, int idx) {
         BCNN_CHECK_STATUS(augment_if_training(net, it->input_uchar, it->input_width, it->input_height, it->input_depth, 0));
         sample_to_input(net, it, idx);
     }
-    if (net->mode != BCNN_MODE_PREDICT) {
-        int n;
-        float *y = label_slot(net, idx, &n);
-        if ((int)label < n) y[label] = 1;
-    }
+    if (net->mode != BCNN_MODE_PREDICT) write_class_label(net, idx, (int)label);
     return BCNN_SUCCESS;
 }
 
@@ -716,11 +733,7 @@ static bcnn_status cifar10_next(bcnn_loader *it, bcnn_net *net, int idx) {
         BCNN_CHECK_STATUS(augment_if_training(net, it->input_uchar, 32, 32, 3, 0));
         sample_to_input(net, it, idx);
     }
-    if (net->mode != BCNN_MODE_PREDICT) {
-        int n;
-        float *y = label_slot(net, idx, &n);
-        if ((int)rec[0] < n) y[rec[0]] = 1;
-    }
+    if (net->mode != BCNN_MODE_PREDICT) write_class_label(net, idx, (int)rec[0]);
     return BCNN_SUCCESS;
 }
 
@@ -831,12 +844,7 @@ static bcnn_status list_classif_next(bcnn_loader *it, bcnn_net *net, int idx) {
         return BCNN_INVALID_DATA;
     }
     bcnn_fill_input_tensor(net, it, tok[0], idx);
-    if (net->mode != BCNN_MODE_PREDICT) {
-        int sz;
-        float *y = label_slot(net, idx, &sz);
-        const int cls = atoi(tok[1]);
-        if (cls >= 0 && cls < sz) y[cls] = 1;
-    }
+    if (net->mode != BCNN_MODE_PREDICT) write_class_label(net, idx, atoi(tok[1]));
     free_tokens(tok, n);
     return BCNN_SUCCESS;
 }
@@ -947,17 +955,14 @@ static bcnn_status list_batch_decoded(bcnn_net *net, bcnn_loader *it, loader_sta
             continue;
         }
         failures = 0;
-        if (net->mode != BCNN_MODE_PREDICT) {
+        if (net->mode != BCNN_MODE_PREDICT && classif) {
+            write_class_label(net, count, atoi(tok[1]));
+        } else if (net->mode != BCNN_MODE_PREDICT) {
             int sz;
             float *y = label_slot(net, count, &sz);
-            if (classif) {
-                const int cls = atoi(tok[1]);
-                if (cls >= 0 && cls < sz) y[cls] = 1;
-            } else {
-                if (nt - 1 != sz)
-                    bcnn_log(net->log_ctx, BCNN_LOG_WARNING, "Unexpected label format. Found label size of %d, expected %d.\n", nt - 1, sz);
-                for (int i = 0; i < nt - 1 && i < sz; ++i) y[i] = (float)atof(tok[i + 1]);
-            }
+            if (nt - 1 != sz)
+                bcnn_log(net->log_ctx, BCNN_LOG_WARNING, "Unexpected label format. Found label size of %d, expected %d.\n", nt - 1, sz);
+            for (int i = 0; i < nt - 1 && i < sz; ++i) y[i] = (float)atof(tok[i + 1]);
         }
         lb.paths[count] = tok[0];
         tok[0] = NULL;
@@ -1311,6 +1316,75 @@ static bcnn_status detection_batch_device(bcnn_net *net, bcnn_loader *it, int *o
     return st;
 }
 
+/* ---- what bcnn_data_segmentation.c uses of this file (bcnn_internal.h) ------------------------------------------------ */
+/* Thin doors onto the statics above, which do what they did: the segmentation-list reader decodes, skips and crops by its
+ * own rules and takes the draws, the pixel work and the staging from here, so that its input batch is the classification
+ * list's bit for bit. */
+int bcnn_loader_line_tokens(FILE *f, char ***tok) { return next_line_tokens(f, tok); }
+void bcnn_loader_free_tokens(char **tok, int n) { free_tokens(tok, n); }
+void bcnn_loader_crop_origin(bcnn_net *net, int wi, int hi, int w, int h, int *x_ul, int *y_ul) {
+    crop_origin(net, wi, hi, w, h, x_ul, y_ul);
+}
+bcnn_status bcnn_loader_crop_to_input(unsigned char *buf, int wi, int hi, int x_ul, int y_ul, unsigned char *img, int w, int h,
+                                      int c) {
+    return crop_to_input(buf, wi, hi, x_ul, y_ul, img, w, h, c);
+}
+int bcnn_loader_effects_on(const bcnn_net *net) { return effects_on(net); }
+int bcnn_loader_staging(bcnn_net *net) {
+    loader_stage *ls = stage_of(net);
+    return ls && ls->active;
+}
+/* The loader's sample buffer into slot idx of the block with its draws (stage_sample, with no pixel work owed to a later
+ * sample); *record and *taps then point at what fill_record made of them. */
+bcnn_status bcnn_loader_stage_sample(bcnn_net *net, bcnn_loader *it, int idx, const bcnn_hip_augment_record **record,
+                                     const int32_t **taps) {
+    loader_stage *ls = stage_of(net);
+    bcnn_tensor *in = &net->tensors[0];
+    if (!ls || !ls->active) return BCNN_INVALID_PARAMETER;
+    BCNN_CHECK_STATUS(stage_sample(net, it, ls, idx, in->w, in->h, in->c, 0));
+    *record = &ls->records[idx];
+    *taps = ls->taps + (size_t)idx * ((size_t)in->w + in->h) * 2;
+    return BCNN_SUCCESS;
+}
+/* The records and tap tables of the batch gathered last (batch x 2 (w + h) taps). */
+void bcnn_loader_staged_records(bcnn_net *net, const bcnn_hip_augment_record **records, const int32_t **taps) {
+    loader_stage *ls = stage_of(net);
+    *records = ls ? ls->records : NULL;
+    *taps = ls ? ls->taps : NULL;
+}
+/* augment_if_training, which also leaves the record and the w + h tap pairs of the draws it made (the identity outside
+ * TRAIN mode): the draws once, then the pixels of `img` in place. */
+bcnn_status bcnn_loader_augment_recorded(bcnn_net *net, unsigned char *img, int w, int h, int c,
+                                         bcnn_hip_augment_record *record, int32_t *taps) {
+    memset(record, 0, sizeof(*record));
+    if (net->mode != BCNN_MODE_TRAIN || !net->data_aug) return BCNN_SUCCESS;
+    unsigned char *scratch = (unsigned char *)calloc((size_t)w * h * c, 1);
+    if (!scratch) return BCNN_FAILED_ALLOC;
+    aug_draw d;
+    draw_augmentation(net->data_aug, &d, effects_on(net), w, h);
+    fill_record(record, taps, &d, w, h);
+    const bcnn_status st = augment_pixels(img, w, h, c, &d, scratch);
+    free(scratch);
+    return st;
+}
+
+/* fill_record for a caller that holds the draws as numbers (tests and tools restate the label rule from them): the record
+ * and the w + h tap pairs of one w x h sample. */
+void bcnn_loader_fill_record(int flip, int shift, int x_ul, int y_ul, int scale, float scale_factor, int rotate, float theta,
+                             int w, int h, bcnn_hip_augment_record *record, int32_t *taps) {
+    aug_draw d;
+    memset(&d, 0, offsetof(aug_draw, spot));
+    d.flip = flip;
+    d.shift = shift;
+    d.x_ul = shift ? x_ul : 0;
+    d.y_ul = shift ? y_ul : 0;
+    d.scale = scale;
+    d.scale_factor = scale_factor;
+    d.rotate = rotate;
+    d.theta = theta;
+    fill_record(record, taps, &d, w, h);
+}
+
 /* ---- public entry points ------------------------------------------------------------------------------------------ */
 static void loader_close(bcnn_loader *it) {
     FILE **fs[4] = {&it->f_train, &it->f_train_extra, &it->f_test, &it->f_test_extra};
@@ -1334,7 +1408,14 @@ bcnn_status bcnn_set_data_loader(bcnn_net *net, bcnn_loader_type type, const cha
     if (stage_of(net)) drop_lazy(stage_of(net)); /* a sample of the loader that is gone */
     int detector = bcnn_get_detector_training(net); /* or a net that already holds a head (bcnn-cl in PREDICT / VALID mode) */
     for (int i = 0; !detector && i < net->num_nodes; ++i) detector = net->nodes[i].type == BCNN_LAYER_YOLOV3;
-    if ((type == BCNN_LOAD_DETECTION_LIST && !detector) || (int)type < 0 || (int)type >= BCNN_NUM_LOADERS) {
+    if (type == BCNN_LOAD_SEGMENTATION_LIST && !has_softmax_loss(net)) {
+        bcnn_log(net->log_ctx, BCNN_LOG_ERROR,
+                 "bcnn_set_data_loader: the segmentation-list format fills a class-index label map, which only the "
+                 "softmax-loss node reads; the net holds none\n");
+        return BCNN_INVALID_PARAMETER;
+    }
+    if ((type == BCNN_LOAD_DETECTION_LIST && !detector) || (int)type < 0 ||
+        ((int)type >= BCNN_NUM_LOADERS && type != BCNN_LOAD_SEGMENTATION_LIST)) {
         bcnn_log(net->log_ctx, BCNN_LOG_ERROR,
                  "bcnn_set_data_loader: the detection-list format belongs to the YOLO head, which is outside the MI355X "
                  "hot-path build (see INTEGRATION.md)\n");
@@ -1351,6 +1432,7 @@ bcnn_status bcnn_set_data_loader(bcnn_net *net, bcnn_loader_type type, const cha
         case BCNN_LOAD_DETECTION_LIST: st = list_detection_init(it, net, train_path_data, train_path_extra, test_path_data, test_path_extra); break;
         default: st = list_init(it, net, train_path_data, train_path_extra, test_path_data, test_path_extra); break;
     }
+    if (st == BCNN_SUCCESS && type == BCNN_LOAD_SEGMENTATION_LIST) st = bcnn_segmentation_init(it, net);
     if (st != BCNN_SUCCESS) bcnn_destroy_data_loader(net); /* no half-opened loader for a later bcnn_loader_next to trip over */
     return st;
 }
@@ -1364,12 +1446,15 @@ bcnn_status bcnn_loader_next(bcnn_net *net) {
     if (it && effects_on(net) && net->mode == BCNN_MODE_TRAIN && net->data_aug && net->data_aug->max_random_spots > BCNN_MAX_SPOTS)
         BCNN_ERROR(net->log_ctx, BCNN_INVALID_PARAMETER, "bcnn_loader_next: loader_effects draws at most %d spotlights per sample\n",
                    BCNN_MAX_SPOTS);
+    const int segmentation = it && it->type == BCNN_LOAD_SEGMENTATION_LIST;
+    if (segmentation) BCNN_CHECK_STATUS(bcnn_segmentation_check(net)); /* before any draw as well */
     loader_stage *ls = it ? stage_begin(net, it) : NULL; /* non-NULL: the input batch is made on the device */
     if (ls) ls->refused = 0;
     bcnn_hip_context *hc = (bcnn_hip_context *)net->hip_ctx;
     int launched = 0; /* list_batch_decoded has queued the batch already */
     hc->loader_device_decoded = 0;
     hc->loader_device_letterboxed = 0;
+    hc->loader_device_labels = 0;
     int letterboxed = 0; /* detection_batch_device has made the input batch on the device */
     bcnn_tensor *in0 = &net->tensors[0];
     if (it && it->type == BCNN_LOAD_DETECTION_LIST && hc->loader_on_device && hc->loader_detection_on_device && in0->data_gpu &&
@@ -1391,7 +1476,8 @@ bcnn_status bcnn_loader_next(bcnn_net *net) {
                 case BCNN_LOAD_CIFAR10: st = cifar10_next(it, net, i); break;
                 case BCNN_LOAD_CLASSIFICATION_LIST: st = list_classif_next(it, net, i); break;
                 case BCNN_LOAD_DETECTION_LIST: st = list_detection_next(it, net, i); break;
-                default: st = list_reg_next(it, net, i); break;
+                case BCNN_LOAD_REGRESSION_LIST: st = list_reg_next(it, net, i); break;
+                default: st = bcnn_segmentation_next(it, net, i); break; /* BCNN_LOAD_SEGMENTATION_LIST, behind the enumerators */
             }
             if (st != BCNN_SUCCESS) {
                 if (++failures >= 1000) {
@@ -1423,6 +1509,9 @@ bcnn_status bcnn_loader_next(bcnn_net *net) {
         bcnn_tensor *t = &net->tensors[net->inputs[i]];
         if (t->data && t->data_gpu) bcnn_hip_memcpy_h2d(t->data_gpu, t->data, (size_t)bcnn_tensor_size(t) * sizeof(float));
     }
+    /* a segmentation batch gathered for the device: its label maps are made there from the staged masks and the batch's
+     * records (bcnn_data_segmentation.c), and tensors[1].data is then neither written nor uploaded */
+    if (segmentation && ls && bcnn_segmentation_labels(net, it, !host_made) != 0) return BCNN_SUCCESS;
     bcnn_tensor *lab = &net->tensors[1];
     if (net->mode != BCNN_MODE_PREDICT && lab->data && lab->data_gpu)
         bcnn_hip_memcpy_h2d(lab->data_gpu, lab->data, (size_t)bcnn_tensor_size(lab) * sizeof(float));

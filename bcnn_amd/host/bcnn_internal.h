@@ -131,6 +131,32 @@ bcnn_status bcnn_switch_data_handles(struct bcnn_net *net, bcnn_loader *iter);
 void bcnn_fill_input_tensor(struct bcnn_net *net, bcnn_loader *iter, char *path_img, int idx);
 void bcnn_destroy_data_loader(struct bcnn_net *net);
 void bcnn_free_loader_stage(struct bcnn_net *net);
+/* bcnn_data.c, for the segmentation-list reader (bcnn_data_segmentation.c): doors onto its statics -- the list lines, the
+ * crop, the effects switch, the device route's gather block, and augment_if_training with the record of its draws */
+struct bcnn_hip_augment_record;
+int bcnn_loader_line_tokens(FILE *f, char ***tok);
+void bcnn_loader_free_tokens(char **tok, int n);
+void bcnn_loader_crop_origin(struct bcnn_net *net, int wi, int hi, int w, int h, int *x_ul, int *y_ul);
+bcnn_status bcnn_loader_crop_to_input(unsigned char *buf, int wi, int hi, int x_ul, int y_ul, unsigned char *img, int w, int h,
+                                      int c);
+int bcnn_loader_effects_on(const struct bcnn_net *net);
+int bcnn_loader_staging(struct bcnn_net *net);
+bcnn_status bcnn_loader_stage_sample(struct bcnn_net *net, bcnn_loader *it, int idx,
+                                     const struct bcnn_hip_augment_record **record, const int32_t **taps);
+void bcnn_loader_staged_records(struct bcnn_net *net, const struct bcnn_hip_augment_record **records, const int32_t **taps);
+bcnn_status bcnn_loader_augment_recorded(struct bcnn_net *net, unsigned char *img, int w, int h, int c,
+                                         struct bcnn_hip_augment_record *record, int32_t *taps);
+void bcnn_loader_fill_record(int flip, int shift, int x_ul, int y_ul, int scale, float scale_factor, int rotate, float theta,
+                             int w, int h, struct bcnn_hip_augment_record *record, int32_t *taps);
+/* bcnn_data_segmentation.c: BCNN_LOAD_SEGMENTATION_LIST ("image-path mask-path" lines). _init sizes the mask buffer of a
+ * loader list_init has opened; _check holds the refusals of bcnn_loader_next (label extents, distortion), made before any
+ * draw; _next reads one sample into slot idx, or skips its line before any draw; _labels finishes a batch that was gathered
+ * for the device: 1 when its label maps were made there (tensors[1].data is then not to be uploaded), 0 when they are in
+ * tensors[1].data (device_ok 0: the image batch was made on the host, and so are they). */
+bcnn_status bcnn_segmentation_init(bcnn_loader *it, struct bcnn_net *net);
+bcnn_status bcnn_segmentation_check(struct bcnn_net *net);
+bcnn_status bcnn_segmentation_next(bcnn_loader *it, struct bcnn_net *net, int idx);
+int bcnn_segmentation_labels(struct bcnn_net *net, bcnn_loader *it, int device_ok);
 
 /* ---- device context of a net (reference analogue: bcnn_cuda_context, src/bcnn_net.h:37-42) ------ */
 typedef struct bcnn_hip_context {
@@ -184,6 +210,7 @@ typedef struct bcnn_hip_context {
     int loader_device_letterboxed;  /* samples of the latest bcnn_loader_next that were letterboxed on the device */
     int loader_effects; /* bcnn_set_loader_effects: bcnn_loader_next applies Perlin distortion and random spotlights, on
                          * the host path and on every device route; off, their draws are made and dropped */
+    int loader_device_labels; /* label maps of the latest bcnn_loader_next that were made on the device (segmentation list) */
     int detector_training; /* bcnn_set_detector_training: YOLO heads may be built on / switched to TRAIN, with their loss */
     int detect_capacity; /* 1.25 x the most boxes an image of the latest bcnn_yolo_get_detections_batch had: the next call's record capacity
                           * when above the default (0: never called) */

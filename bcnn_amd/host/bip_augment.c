@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include "bip/bip.h"
+#include "bip_label_warp.h" /* the label rule, shared with the device kernel */
 
 static int32_t clamp_u8(int32_t v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
@@ -117,5 +118,16 @@ bip_status bip_image_brightness(uint8_t *src, size_t src_stride, size_t width, s
     for (size_t y = 0; y < height; ++y)
         for (size_t x = 0; x < width * depth; ++x)
             dst[y * dst_stride + x] = (uint8_t)clamp_u8((int32_t)src[y * src_stride + x] + brightness);
+    return BIP_SUCCESS;
+}
+
+/* The label map of an augmented image: a double loop over the rule of bip_label_warp.h. */
+bip_status bip_warp_label_map(const uint8_t *map, int32_t width, int32_t height, int32_t flags, int32_t x_ul, int32_t y_ul,
+                              int32_t ca, int32_t sa, const int32_t *tapx, const int32_t *tapy, int32_t fill, uint8_t *out) {
+    if (!map || !out || ((flags & BIP_LABEL_SCALE) && (!tapx || !tapy))) return BIP_INVALID_PTR;
+    if (width < 1 || height < 1) return BIP_INVALID_SIZE;
+    if (fill < 0 || fill > 255 || !bip_label_taps_ok(flags, tapx, tapy, width, height)) return BIP_INVALID_PARAMETER;
+    const bip_label_sample s = {map, tapx, tapy, width, height, flags, x_ul, y_ul, ca, sa, fill};
+    bip_label_warp_map(&s, out);
     return BIP_SUCCESS;
 }

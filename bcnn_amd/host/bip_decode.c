@@ -203,7 +203,10 @@ static int paeth(int a, int b, int c) {
     return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
 }
 
-static bip_status decode_png(const uint8_t *buf, size_t len, uint8_t **out, int32_t *w, int32_t *h, int32_t *depth) {
+/* keep_indices (bip_load_index_map): a palette image comes out as its indices, one byte per pixel, and only the two
+ * colour types that hold one index per pixel are taken. */
+static bip_status decode_png_as(const uint8_t *buf, size_t len, uint8_t **out, int32_t *w, int32_t *h, int32_t *depth,
+                                int keep_indices) {
     size_t pos = 8, zcap = 0, zlen = 0;
     uint8_t *z = NULL, palette[256 * 3];
     uint32_t width = 0, height = 0;
@@ -249,6 +252,12 @@ static bip_status decode_png(const uint8_t *buf, size_t len, uint8_t **out, int3
         free(z);
         return BIP_UNKNOWN_ERROR;
     }
+    if (keep_indices && ctype != 0 && ctype != 3) {
+        fprintf(stderr, "[ERROR] bip_load_index_map: a PNG mask must be 8-bit grey or 8-bit palette (colour type %d has no class "
+                        "indices)\n", ctype);
+        free(z);
+        return BIP_UNKNOWN_ERROR;
+    }
     const size_t row = (size_t)width * ch, raw_len = (row + 1) * height;
     uint8_t *raw = (uint8_t *)malloc(raw_len);
     if (!raw || zlib_inflate(z, zlen, raw, raw_len) != 0) {
@@ -257,7 +266,7 @@ static bip_status decode_png(const uint8_t *buf, size_t len, uint8_t **out, int3
         return BIP_UNKNOWN_ERROR;
     }
     free(z);
-    const int out_ch = (ctype == 3) ? 3 : ch;
+    const int out_ch = (ctype == 3 && !keep_indices) ? 3 : ch;
     uint8_t *img = (uint8_t *)malloc((size_t)width * height * out_ch);
     uint8_t *lines = (uint8_t *)calloc(2, row); /* previous / current reconstructed scanline */
     if (!img || !lines) { free(raw); free(img); free(lines); return BIP_UNKNOWN_ERROR; }
@@ -279,7 +288,7 @@ static bip_status decode_png(const uint8_t *buf, size_t len, uint8_t **out, int3
             cur[x] = (uint8_t)v;
         }
         uint8_t *dst = img + (size_t)y * width * out_ch;
-        if (ctype == 3) {
+        if (ctype == 3 && !keep_indices) {
             for (uint32_t x = 0; x < width; ++x) memcpy(dst + 3 * x, palette + 3 * cur[x], 3);
         } else {
             memcpy(dst, cur, row);
@@ -289,6 +298,10 @@ static bip_status decode_png(const uint8_t *buf, size_t len, uint8_t **out, int3
     free(raw); free(lines);
     *out = img; *w = (int32_t)width; *h = (int32_t)height; *depth = out_ch;
     return BIP_SUCCESS;
+}
+
+static bip_status decode_png(const uint8_t *buf, size_t len, uint8_t **out, int32_t *w, int32_t *h, int32_t *depth) {
+    return decode_png_as(buf, len, out, w, h, depth, 0);
 }
 
 /* ---------------------------------------------------------------------------------------------- PNM */
@@ -386,6 +399,44 @@ bip_status bip_load_image_from_memory(unsigned char *buffer, int buffer_size, ui
     }
     fprintf(stderr, "[ERROR] Cannot load image from buffer: format not supported by this build (PNG, JPEG, PNM and BMP are)\n");
     return BIP_UNKNOWN_ERROR;
+}
+
+/* A class-index mask (bip.h): the formats that hold one index per pixel, everything else refused by name. */
+bip_status bip_load_index_map_from_memory(unsigned char *buffer, int buffer_size, uint8_t **map, int32_t *width,
+                                          int32_t *height) {
+    static const uint8_t png_sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+    if (!buffer || !map || !width || !height) return BIP_INVALID_PTR;
+    const size_t len = buffer_size > 0 ? (size_t)buffer_size : 0;
+    int32_t depth = 0;
+    if (len >= 8 && !memcmp(buffer, png_sig, 8)) return decode_png_as(buffer, len, map, width, height, &depth, 1);
+    if (len >= 3 && buffer[0] == 'P' && (buffer[1] == '2' || buffer[1] == '5'))
+        return decode_pnm(buffer, len, map, width, height, &depth);
+    const char *what = "an unknown format";
+    if (len >= 3 && buffer[0] == 'P' && (buffer[1] == '3' || buffer[1] == '6')) what = "a colour PNM";
+    else if (len >= 2 && buffer[0] == 'B' && buffer[1] == 'M') what = "a BMP";
+    else if (len >= 4 && buffer[0] == 0xff && buffer[1] == 0xd8) what = "a JPEG (lossy)";
+    fprintf(stderr, "[ERROR] bip_load_index_map: %s holds no class indices (8-bit grey or palette PNG and PNM P5 / P2 do)\n", what);
+    return BIP_UNKNOWN_ERROR;
+}
+
+bip_status bip_load_index_map(char *filename, uint8_t **map, int32_t *width, int32_t *height) {
+    if (!filename || !map) return BIP_INVALID_PTR;
+    FILE *fp = fopen(filename, "rb");
+    if (!fp) {
+        fprintf(stderr, "[ERROR] Cannot load mask file %s\n", filename);
+        return BIP_UNKNOWN_ERROR;
+    }
+    fseek(fp, 0, SEEK_END);
+    const long size = ftell(fp);
+    fseek(fp, 0, SEEK_SET);
+    uint8_t *buf = (size > 0 && size < (1L << 30)) ? (uint8_t *)malloc((size_t)size) : NULL;
+    const int ok = buf && fread(buf, 1, (size_t)size, fp) == (size_t)size;
+    fclose(fp);
+    bip_status st = BIP_UNKNOWN_ERROR;
+    if (ok) st = bip_load_index_map_from_memory(buf, (int)size, map, width, height);
+    if (st != BIP_SUCCESS) fprintf(stderr, "[ERROR] Cannot load mask file %s\n", filename);
+    free(buf);
+    return st;
 }
 
 bip_status bip_load_image(char *filename, uint8_t **src, int32_t *src_width, int32_t *src_height, int32_t *src_depth) {

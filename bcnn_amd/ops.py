@@ -603,3 +603,57 @@ def augment_letterbox_batch(dst, images, boxes, records=None, taps=None, swap_to
     return int(_lib.load().bcnn_hip_augment_letterbox_batch(
         _f32(dst), n, c, h, w, num, _C.cast(arr, _C.c_void_p), records.ctypes.data,
         None if taps is None else taps.ctypes.data, 1 if swap_to_bgr else 0))
+
+
+def augment_label_batch(label, maps, records=None, taps=None, fill=255, num_samples=None):
+    """bcnn_hip_augment_label_batch: label is the [n][1][h][w] float32 device tensor (written in place and returned by
+    reference: planes num_samples .. n - 1 are left alone); maps a HOST uint8 array [num][h][w] of class indices, records
+    a HOST int32 array [num][8] (bcnn_hip_augment_record; None: identity records), taps a HOST int32 array
+    [num][(w + h) * 2] or None. Returns the entry's status: 0, or 1 with nothing staged or queued."""
+    import numpy as np
+    n, _, h, w = label.shape
+    maps = np.ascontiguousarray(maps, dtype=np.uint8)
+    num = maps.shape[0] if num_samples is None else num_samples
+    if records is None:
+        records = np.zeros((max(num, 1), 8), np.int32)
+    records = np.ascontiguousarray(records, dtype=np.int32)
+    if taps is not None:
+        taps = np.ascontiguousarray(taps, dtype=np.int32)
+    return int(_lib.load().bcnn_hip_augment_label_batch(
+        _f32(label), n, h, w, num, maps.ctypes.data, records.ctypes.data, None if taps is None else taps.ctypes.data,
+        int(fill)))
+
+
+_bip = None
+
+
+def _libbip():
+    global _bip
+    if _bip is None:
+        import os
+        _bip = _C.CDLL(os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libbip.so"))
+        i32, vp = _C.c_int32, _C.c_void_p
+        _bip.bip_warp_label_map.restype = _C.c_int
+        _bip.bip_warp_label_map.argtypes = [vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, i32, vp]
+    return _bip
+
+
+def warp_label_map(label_map, record=None, taps=None, fill=255):
+    """bip_warp_label_map (libbip, host): the label map that belongs to an augmented image. label_map is a HOST uint8
+    array [h][w], record the 8 int32 of a bcnn_hip_augment_record (flags, x_ul, y_ul, ca, sa, ...; None: the identity),
+    taps the (w + h) * 2 int32 of its tap table or None. Returns the warped uint8 array [h][w]; raises ValueError with
+    the bip_status when the function refuses."""
+    import numpy as np
+    m = np.ascontiguousarray(label_map, dtype=np.uint8)
+    h, w = m.shape
+    r = np.zeros(8, np.int32) if record is None else np.ascontiguousarray(record, dtype=np.int32).reshape(-1)
+    tx = ty = None
+    if taps is not None:
+        t = np.ascontiguousarray(taps, dtype=np.int32).reshape(-1)
+        tx, ty = t.ctypes.data, t.ctypes.data + 8 * w
+    out = np.empty_like(m)
+    st = _libbip().bip_warp_label_map(m.ctypes.data, w, h, int(r[0]), int(r[1]), int(r[2]), int(r[3]), int(r[4]), tx, ty,
+                                      int(fill), out.ctypes.data)
+    if st != 0:
+        raise ValueError("bip_warp_label_map: status %d" % st)
+    return out

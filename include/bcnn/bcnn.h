@@ -45,6 +45,10 @@ typedef enum {
     BCNN_LOAD_MNIST, BCNN_LOAD_CIFAR10, BCNN_LOAD_CLASSIFICATION_LIST, BCNN_LOAD_REGRESSION_LIST,
     BCNN_LOAD_DETECTION_LIST, BCNN_NUM_LOADERS
 } bcnn_loader_type;
+/* The segmentation-list loader ("image-path mask-path" lines; bcnn_set_data_loader below), the value behind the
+ * enumerator list: a constant of the enum's type next to the enum, like the layer types since BCNN_LAYER_POOL2D, so that
+ * the enumerators and BCNN_NUM_LOADERS keep the reference's values. */
+#define BCNN_LOAD_SEGMENTATION_LIST ((bcnn_loader_type)(BCNN_NUM_LOADERS + 1))
 
 typedef enum {
     BCNN_LR_DECAY_CONSTANT, BCNN_LR_DECAY_STEP, BCNN_LR_DECAY_INV, BCNN_LR_DECAY_EXP, BCNN_LR_DECAY_POLY,
@@ -500,6 +504,11 @@ BCNN_API int bcnn_get_loader_detection_on_device(const bcnn_net *net);
 /* Number of samples of the latest bcnn_loader_next that were letterboxed on the device; 0 for a batch made any other
  * way, on a fresh net and for a NULL net. */
 BCNN_API int bcnn_get_loader_device_letterboxed(const bcnn_net *net);
+/* BCNN_LOAD_SEGMENTATION_LIST: number of label maps of the latest bcnn_loader_next that were made on the device (with
+ * bcnn_set_loader_on_device the cropped masks of the batch go up in one copy and one kernel writes tensors[1]'s device
+ * buffer from the image batch's own records; tensors[1].data is then not written and not uploaded). 0 on the host route,
+ * for a batch whose image or labels the device side refused, and for every other loader type; 0 for a NULL net. */
+BCNN_API int bcnn_get_loader_device_labels(const bcnn_net *net);
 /* Whether bcnn_loader_next applies the augmenter's last two stages, Perlin distortion (config key `max_distortion`) and
  * random spotlights (`max_spots`, bcnn_augment_data_with_blobs), to TRAIN-mode samples (default 0: off). Off, a net whose
  * augmenter has one of the two ranges set draws their parameters from rand() exactly as the reference does (so every other

@@ -927,6 +927,26 @@ int bcnn_hip_augment_batch(float *dst_d, int n, int c, int h, int w, int num_sam
                            int swap_to_bgr);
 
 /* ---------------------------------------------------------------------------------------------
+ * The class-index label maps that belong to such a batch (augment_label.hip): plane b of the float tensor label_d
+ * [n][1][h][w] gets, per pixel, (float) of ONE byte of the b-th mask or of `fill` -- the pull-back of the mask through the
+ * geometry stages of its image (FLIP, SHIFT, SCALE, ROTATE of bcnn_hip_augment_batch; nearest picks where the image
+ * blends; `fill` where the image gets its canvas). The rule is bcnn_amd/host/bip_label_warp.h, which libbip's
+ * bip_warp_label_map is written on as well: the result equals that function's byte for byte. maps (HOST) holds
+ * num_samples dense w x h byte maps; records and taps (HOST) are laid out as for bcnn_hip_augment_batch with src_w = w and
+ * src_h = h (taps may be NULL when no record has SCALE); CONTRAST, brightness and the effects are ignored. Planes
+ * num_samples .. n - 1 are not written.
+ * One pinned staging block of its own (records, taps, maps; grow-only, one per host thread and device -- the image
+ * batch's copy in flight is not waited for) goes up in ONE copy on the current stream; ONE kernel follows: a lane per four
+ * consecutive pixels of a row and one 16-byte store when w % 4 == 0 and label_d is 16-byte aligned (dispatch trace
+ * `augment_label:v4`), else a lane per pixel (`augment_label`). The maps have been copied when the call returns.
+ * Returns 0, or 1 with nothing staged or queued: a NULL label_d / maps / records; n, h or w < 1; num_samples outside
+ * 1..n; fill outside 0..255; a record with SCALE and taps == NULL, or a tap index outside [-1, max(extent - 2, 0)]; more
+ * than 2 GiB to stage.
+ * ------------------------------------------------------------------------------------------- */
+int bcnn_hip_augment_label_batch(float *label_d, int n, int h, int w, int num_samples, const uint8_t *maps,
+                                 const bcnn_hip_augment_record *records, const int32_t *taps, int fill);
+
+/* ---------------------------------------------------------------------------------------------
  * The same batch when some of its samples are still JPEG coefficient blocks (augment.hip + the two kernels of
  * jpeg_pixels.hip): the list loaders' opt-in device decoding. The stored sample is the net input itself (w x h x c, c 1
  * or 3); a sample is either a dense w x h x c block of bytes the caller decoded and cropped, or a JPEG frame whose

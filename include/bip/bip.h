@@ -27,6 +27,13 @@ bip_status bip_write_image(char *filename, uint8_t *src, int32_t src_width, int3
 bip_status bip_load_image(char *filename, uint8_t **src, int32_t *src_width, int32_t *src_height, int32_t *src_depth);
 bip_status bip_load_image_from_memory(unsigned char *buffer, int buffer_size, uint8_t **src, int32_t *src_width,
                                       int32_t *src_height, int32_t *src_depth);
+/* A class-index mask: *map gets width x height bytes (malloc), one class index per pixel. Accepted: 8-bit grey PNG (its
+ * values), 8-bit palette PNG (the INDICES, not the colours: VOC's SegmentationClass files), PNM P5 / P2 with maxval <= 255
+ * (its values). Everything else -- RGB / RGBA / grey+alpha PNG, JPEG, BMP, colour PNM -- fails with BIP_UNKNOWN_ERROR and a
+ * line on stderr that names the reason: a lossy or coloured mask has no class indices. */
+bip_status bip_load_index_map(char *filename, uint8_t **map, int32_t *width, int32_t *height);
+bip_status bip_load_index_map_from_memory(unsigned char *buffer, int buffer_size, uint8_t **map, int32_t *width,
+                                          int32_t *height);
 /* ---- the JPEG decoder split at the coefficient boundary (bip_jpeg.c): entropy decoding on one side, pixel arithmetic
  * (bcnn_amd/host/bip_jpeg_pixels.h) on the other; bip_load_image* is the three calls below in a row ---- */
 typedef struct {
@@ -67,6 +74,15 @@ bip_status bip_fliph_image(uint8_t *src, size_t width, size_t height, size_t dep
 bip_status bip_rotate_image(uint8_t *src, size_t src_width, size_t src_height, size_t src_stride, uint8_t *dst,
                             size_t dst_width, size_t dst_height, size_t dst_stride, size_t depth, float angle,
                             int32_t center_x, int32_t center_y, bip_interpolation interpolation);
+/* The label map that belongs to an augmented image: out[y * width + x] is one byte of `map` (width x height, dense) or
+ * `fill`, by the rule of bcnn_amd/host/bip_label_warp.h -- the pull-back through horizontal flip, shift, scale and
+ * rotation as the loader's record describes them (flags: bits 1 / 2 / 4 / 8; x_ul, y_ul; ca, sa = cos, sin * 65536; tapx /
+ * tapy: width / height (index, fraction) int32 pairs of bip_resize_bilinear's rule, index -1 where the resized image does
+ * not cover the column or row; read only with the scale bit). BIP_INVALID_PTR for a NULL map / out (or taps with the scale
+ * bit), BIP_INVALID_SIZE for an extent < 1, BIP_INVALID_PARAMETER for fill outside 0 ... 255 or a tap index outside
+ * [-1, max(extent - 2, 0)]; nothing is written then. */
+bip_status bip_warp_label_map(const uint8_t *map, int32_t width, int32_t height, int32_t flags, int32_t x_ul, int32_t y_ul,
+                              int32_t ca, int32_t sa, const int32_t *tapx, const int32_t *tapy, int32_t fill, uint8_t *out);
 bip_status bip_contrast_stretch(uint8_t *src, size_t src_stride, size_t width, size_t height, size_t depth, uint8_t *dst,
                                 size_t dst_stride, float contrast);
 bip_status bip_image_brightness(uint8_t *src, size_t src_stride, size_t width, size_t height, size_t depth, uint8_t *dst,
