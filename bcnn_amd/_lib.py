@@ -158,6 +158,10 @@ SIGNATURES = {
     "bcnn_hip_softmax_loss_backward": (None, [vp, vp, vp, vp, vp, i, i, i, i]),
     "bcnn_hip_softmax_loss_confusion": (None, [vp, vp, vp, vp, i, i, i]),
     "bcnn_hip_softmax_loss_c_reg": (i, []),
+    "bcnn_hip_label_map_fit": (i, [i, i, i, i, i, vp]),
+    "bcnn_hip_label_maps_plan": (i, [vp, i, i, i, i, i, vp, vp, vp]),
+    "bcnn_hip_label_maps_batch": (i, [vp, i, i, i, i, i, vp, i, vp, vp, vp, vp, i, vp, vp, vp]),
+    "bcnn_hip_label_maps_kernel_ms": (f, [i]),
     "bcnn_hip_lrn_forward": (None, [vp, vp] + [i] * 5 + [f] * 3),
     "bcnn_hip_lrn_backward": (None, [vp, vp, vp] + [i] * 5 + [f] * 3 + [i]),
     "bcnn_hip_dropout_forward": (None, [vp, sz, f, u64, u64]),

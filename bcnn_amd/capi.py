@@ -49,6 +49,24 @@ class YoloTrainStats(C.Structure):
                 ("recall50", C.c_float), ("recall75", C.c_float), ("count", C.c_int), ("cost", C.c_float)]
 
 
+class LabelMapEval(C.Structure):
+    """struct bcnn_label_map_eval (include/bcnn/bcnn.h)."""
+    _fields_ = [("truths", C.POINTER(C.c_void_p)), ("strides", C.POINTER(C.c_int)), ("ignore_label", C.c_int),
+                ("counts", C.POINTER(C.c_int64)), ("ignored", C.c_int64), ("out_of_range", C.c_int64)]
+
+
+def iou_from_confusion(counts):
+    """per-class IoU and their mean from a C x C confusion matrix (row = truth, column = label):
+    IoU_k = counts[k][k] / (row sum k + column sum k - counts[k][k]); NaN for a class that is absent from both the truths
+    and the labels, which the mean skips (NaN when every class is absent)"""
+    m = np.asarray(counts, dtype=np.float64)
+    assert m.ndim == 2 and m.shape[0] == m.shape[1], "a square matrix"
+    inter = np.diag(m)
+    union = m.sum(0) + m.sum(1) - inter
+    iou = np.where(union > 0, inter / np.where(union > 0, union, 1.0), np.nan)
+    return iou, (float(np.nanmean(iou)) if (union > 0).any() else float("nan"))
+
+
 class SoftmaxLossStats(C.Structure):
     """struct bcnn_softmax_loss_stats (include/bcnn/bcnn.h)."""
     _fields_ = [("loss", C.c_float), ("valid", C.c_int64), ("ignored", C.c_int64), ("out_of_range", C.c_int64),
@@ -124,6 +142,8 @@ def lib():
         "bcnn_add_softmax_loss_layer": (i, [vp, i, i, f, cp, cp, cp]),
         "bcnn_get_softmax_loss_stats": (i, [vp, i, C.POINTER(SoftmaxLossStats)]),
         "bcnn_get_confusion_matrix": (i, [vp, i, C.POINTER(C.c_int64)]),
+        "bcnn_get_label_maps_batch": (i, [vp, i, i, C.POINTER(i), C.POINTER(i), i, i, C.POINTER(vp), C.POINTER(i),
+                                          C.POINTER(LabelMapEval)]),
         "bcnn_add_lrn_layer": (i, [vp, i, f, f, f, cp, cp]), "bcnn_add_dropout_layer": (i, [vp, f, cp]),
         "bcnn_set_dropout_seed": (None, [vp, C.c_uint64]),
         "bcnn_get_lifted_struct_loss": (i, [vp, C.POINTER(f), C.POINTER(i)]),
@@ -523,6 +543,33 @@ class Net:
         return self.L.bcnn_fill_tensor_with_images(self.net, tensor, k, (C.c_void_p * k)(*ptrs), (C.c_int * k)(*ws),
                                                    (C.c_int * k)(*hs), (C.c_int * k)(*ss), c if c is not None else 0,
                                                    fit, norm_coeff, 1 if swap_to_bgr else 0, mean[0], mean[1], mean[2])
+
+    def label_maps(self, tensor, sizes, fit=IMAGE_FIT_STRETCH, align_corners=False, truths=None, ignore_label=255,
+                   labels=True):
+        """bcnn_get_label_maps_batch: one uint8 array [h][w] of class indices per (w, h) of `sizes` (the original sizes of
+        the images the batch was filled with, with the same `fit`), from tensor `tensor` ([n][C][h][w] logits or
+        probabilities). With `truths` (uint8 arrays of those sizes) returns (labels, counts, ignored, out_of_range), counts
+        the C x C int64 matrix (row = truth, column = label); labels=False skips the label maps (None in their place).
+        Raises ValueError with the bcnn_status when the library refuses."""
+        k = len(sizes)
+        ws, hs = (C.c_int * max(k, 1))(*[int(s[0]) for s in sizes]), (C.c_int * max(k, 1))(*[int(s[1]) for s in sizes])
+        out = [np.empty((int(s[1]), int(s[0])), np.uint8) for s in sizes] if labels else None
+        lptr = (C.c_void_p * max(k, 1))(*[a.ctypes.data for a in out]) if labels else None
+        ev = None
+        if truths is not None:
+            keep = [np.ascontiguousarray(t, dtype=np.uint8) for t in truths]
+            assert len(keep) == k and all(t.shape == (int(s[1]), int(s[0])) for t, s in zip(keep, sizes))
+            c = self.shape(tensor)[1]
+            counts = np.zeros((c, c), np.int64)
+            tptr = (C.c_void_p * max(k, 1))(*[t.ctypes.data for t in keep])
+            ev = LabelMapEval(tptr, None, int(ignore_label), counts.ctypes.data_as(C.POINTER(C.c_int64)), 0, 0)
+        st = self.L.bcnn_get_label_maps_batch(self.net, tensor, k, ws, hs, fit, 1 if align_corners else 0, lptr, None,
+                                              C.byref(ev) if ev is not None else None)
+        if st != 0:
+            raise ValueError("bcnn_get_label_maps_batch failed with status %d" % st)
+        if ev is None:
+            return out
+        return out, counts, int(ev.ignored), int(ev.out_of_range)
 
     def fill_jpegs(self, jpegs, fit=IMAGE_FIT_STRETCH, norm_coeff=1.0, swap_to_bgr=False, mean=(0.0, 0.0, 0.0),
                    tensor=0, num_images=None):

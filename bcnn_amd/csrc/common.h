@@ -64,6 +64,7 @@ enum ScratchSlot {
     SCRATCH_INTERP,        // current stream: tap and contributor-range tables of one bilinear interpolation call (interp.hip)
     SCRATCH_SOFTMAX_LOSS,  // current stream: per-workgroup loss and count partials of one softmax-loss forward (softmax_loss.hip)
     SCRATCH_AUGMENT_LABEL, // current stream: records, tap tables and raw uint8 masks of a batch of label maps (augment_label.hip)
+    SCRATCH_LABEL_MAP,     // current stream: descriptors, truth bytes, counts and label bytes of one label-map call (label_map.hip)
     SCRATCH_SLOTS
 };
 // A block of at least `floats` floats for `slot` on the calling thread's device; valid until that slot's next call.

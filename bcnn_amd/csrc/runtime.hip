@@ -42,6 +42,7 @@ static constexpr ScratchPolicy kScratchPolicy[] = {  // in ScratchSlot order
     /* INTERP        */ {1u << 14, 2, 1},  // 64 KiB: 4 floats per output row / column, 2 per input row / column
     /* SOFTMAX_LOSS  */ {2048 * 6, 1, 1},  // 48 KiB: a double and four ints per workgroup of the largest capped grid
     /* AUGMENT_LABEL */ {1u << 16, 1, 1},  // 256 KiB to start with; a loader's batches all have one size
+    /* LABEL_MAP     */ {1u << 18, 5, 4},  // 1 MiB to start with; image sizes vary from batch to batch
 };
 static_assert(sizeof(kScratchPolicy) / sizeof(kScratchPolicy[0]) == SCRATCH_SLOTS, "one policy row per ScratchSlot");
 struct ScratchBlock { float* p = nullptr; size_t cap = 0; };

@@ -376,6 +376,85 @@ def softmax_loss_confusion(p, label, ignore_label=-1):
     return counts.cpu().numpy().astype("int64").reshape(c, c)
 
 
+IMAGE_FIT_STRETCH, IMAGE_FIT_LETTERBOX = 0, 1
+
+
+class LabelMapImage(_C.Structure):
+    """struct bcnn_hip_label_map_image (include/bcnn_hip.h): the extent of an image and its rectangle of the tensor plane"""
+    _fields_ = [("out_w", _C.c_int), ("out_h", _C.c_int), ("roi_x", _C.c_int), ("roi_y", _C.c_int), ("roi_w", _C.c_int),
+                ("roi_h", _C.c_int)]
+
+
+def _label_map_images(images):
+    """a C array of LabelMapImage from LabelMapImage objects or (out_w, out_h, roi_x, roi_y, roi_w, roi_h) tuples"""
+    arr = (LabelMapImage * max(len(images), 1))()
+    for b, im in enumerate(images):
+        arr[b] = im if isinstance(im, LabelMapImage) else LabelMapImage(*[int(v) for v in im])
+    return arr
+
+
+def label_map_fit(fit, w, h, iw, ih):
+    """bcnn_hip_label_map_fit (host code of the library, no device): (out_w, out_h, roi_x, roi_y, roi_w, roi_h) of an
+    iw x ih image in the w x h plane for IMAGE_FIT_STRETCH / IMAGE_FIT_LETTERBOX, or None when the library refuses"""
+    out = LabelMapImage(-1, -1, -1, -1, -1, -1)
+    if _lib.load().bcnn_hip_label_map_fit(int(fit), int(w), int(h), int(iw), int(ih), _C.byref(out)) != 0:
+        assert tuple(getattr(out, name) for name, _ in LabelMapImage._fields_) == (-1,) * 6, "a refusal wrote its output"
+        return None
+    return tuple(getattr(out, name) for name, _ in LabelMapImage._fields_)
+
+
+def label_maps_plan(images, c, h, w, with_truths=False):
+    """bcnn_hip_label_maps_plan (host, no device): (row_strides, offsets, total_bytes) of the result block of a call over
+    `images` (see label_maps), or None when the library refuses (and then wrote nothing)"""
+    import numpy as np
+    k = len(images)
+    strides = np.full(max(k, 1), 0xFFFFFFFF, np.uint32)
+    offsets = np.full(max(k, 1), 2 ** 64 - 1, np.uint64)
+    total = _C.c_ulonglong(2 ** 64 - 1)
+    st = _lib.load().bcnn_hip_label_maps_plan(_C.cast(_label_map_images(images), _C.c_void_p), k, int(c), int(h), int(w),
+                                              1 if with_truths else 0, strides.ctypes.data, offsets.ctypes.data,
+                                              _C.cast(_C.pointer(total), _C.c_void_p))
+    if st != 0:
+        assert (strides == 0xFFFFFFFF).all() and (offsets == 2 ** 64 - 1).all() and total.value == 2 ** 64 - 1
+        return None
+    return [int(v) for v in strides[:k]], [int(v) for v in offsets[:k]], int(total.value)
+
+
+def label_maps(x, images, align_corners=False, truths=None, ignore_label=-1, labels=True, counts=None):
+    """bcnn_hip_label_maps_batch: x is the [n][C][h][w] float32 device tensor, images one LabelMapImage or (out_w, out_h,
+    roi_x, roi_y, roi_w, roi_h) per batch entry from 0 on (label_map_fit makes them). Returns the list of uint8 numpy
+    arrays [out_h][out_w]: per pixel the first argmax over C of the bilinear resampling of the rectangle. With `truths`
+    (uint8 arrays of the same extents) returns (labels, counts, ignored, out_of_range): counts the C x C int64 matrix
+    (row = truth, column = label) over the valid pixels -- added into `counts` when one is given. labels=False asks for
+    the counts alone (None in place of the list). Synchronises. Raises ValueError when the library refuses."""
+    import numpy as np
+    n, c, h, w = x.shape
+    k = len(images)
+    arr = _label_map_images(images)
+    out = [np.empty((arr[b].out_h, arr[b].out_w), np.uint8) for b in range(k)] if labels else None
+    lptr = (_C.c_void_p * max(k, 1))(*[a.ctypes.data for a in out]) if labels else None
+    tptr, keep = None, []
+    ign, oor = _C.c_longlong(0), _C.c_longlong(0)
+    if truths is not None:
+        keep = [np.ascontiguousarray(t, dtype=np.uint8) for t in truths]
+        assert len(keep) == k and all(t.shape == (arr[b].out_h, arr[b].out_w) for b, t in enumerate(keep)), \
+            "one truth map per image, of its size"
+        tptr = (_C.c_void_p * max(k, 1))(*[t.ctypes.data for t in keep])
+        if counts is None:
+            counts = np.zeros((c, c), np.int64)
+        assert counts.dtype == np.int64 and counts.size == c * c and counts.flags.c_contiguous
+    st = _lib.load().bcnn_hip_label_maps_batch(
+        _f32(x), n, c, h, w, 1 if align_corners else 0, _C.cast(arr, _C.c_void_p), k,
+        None if lptr is None else _C.cast(lptr, _C.c_void_p), None, None if tptr is None else _C.cast(tptr, _C.c_void_p),
+        None, int(ignore_label), None if truths is None else counts.ctypes.data, _C.cast(_C.pointer(ign), _C.c_void_p),
+        _C.cast(_C.pointer(oor), _C.c_void_p))
+    if st != 0:
+        raise ValueError("bcnn_hip_label_maps_batch refused the call (status %d)" % st)
+    if truths is None:
+        return out
+    return out, counts, int(ign.value), int(oor.value)
+
+
 def pool2d_forward(x, y, indexes, kind, size, stride, pad=0, ceil_mode=False, count_include_pad=True):
     """bcnn_hip_pool2d_forward: windowed max / average pooling with `pad` on all four sides. indexes (int32, y's shape)
     may be None: max pooling then stores no winners; average pooling never does."""

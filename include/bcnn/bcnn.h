@@ -372,6 +372,46 @@ BCNN_API bcnn_status bcnn_get_softmax_loss_stats(bcnn_net *net, int node, bcnn_s
  * the label the latest forward left on the device (one kernel, launched by this call; not on the training path). Its trace
  * is the record's `correct`, its total `valid`. BCNN_INVALID_PARAMETER: not such a node, counts NULL, no label on the device. */
 BCNN_API bcnn_status bcnn_get_confusion_matrix(bcnn_net *net, int node, int64_t *counts);
+/* New, without a reference counterpart: the output end of semantic segmentation. Tensor `tensor_index` -- any
+ * [n][C][h][w] tensor with a device buffer, the logits or the softmax-loss node's probabilities -- becomes one class index
+ * (a byte) per pixel of each of the first num_images images of the batch AT THAT IMAGE'S OWN SIZE widths[b] x heights[b],
+ * on the device: the part of plane b that image b occupies is resampled bilinearly to the image's extent (the interp
+ * node's rule for the given align_corners, bit for bit) and the label is the first maximum over the C classes. The
+ * resampled floats are never stored and only the bytes are read back: one copy in, one kernel for the whole batch whatever
+ * the sizes, one copy back. The call interpolates what it is given: the argmax of interpolated logits and of interpolated
+ * probabilities can differ (softmax is not linear), so name the tensor you mean.
+ *   fit is a bcnn_image_fit value (an int here, as in bcnn_fill_tensor_with_jpegs) and must be the one the batch was
+ *   filled with (bcnn_fill_tensor_with_images / _jpegs):
+ *     STRETCH   : the whole plane is the image, for a tensor of any extent -- a DeepLab head's 65 x 65 logits go straight
+ *                 to image size;
+ *     LETTERBOX : the image occupies the integer rectangle (x_off, y_off, new_w, new_h) documented at
+ *                 bcnn_fill_tensor_with_images; accepted only when the tensor's h x w equals tensor 0's (resampling a
+ *                 letterboxed low-resolution head needs a fractional rectangle and is out of scope).
+ *   labels[b] receives heights[b] rows of widths[b] bytes, strides[b] bytes apart (strides NULL: widths[b]); the bytes
+ *   between the width and the stride are not written. labels may be NULL when eval is given.
+ *   eval (may be NULL) scores the labels against truth maps of the images' own sizes -- what VOC / Cityscapes / ADE20K
+ *   call mIoU; bcnn_get_confusion_matrix counts at the net's extent against the augmented label tensor, a training
+ *   statistic. truths[b]: heights[b] rows of widths[b] bytes, eval->strides[b] apart (NULL: widths[b]). A truth byte t is
+ *   ignored (ignore_label >= 0 and t == ignore_label), valid (t < C) or out of range; a valid pixel labelled a adds 1 to
+ *   counts[t * C + a]. counts (C * C), ignored and out_of_range are ADDED into: zero them before the first batch of a
+ *   validation set. Integer arithmetic only: two runs give the same counts.
+ * The results are complete when the call returns (it synchronises the calling thread's stream once).
+ * Returns BCNN_INVALID_PARAMETER with a log line, every output untouched and nothing queued, when tensor_index is out of
+ * range or the tensor has no device buffer; num_images < 1 or above the batch size; the tensor has more than 256 channels;
+ * widths or heights is NULL or holds a value below 1; fit is unknown, or LETTERBOX on a tensor of another extent than
+ * tensor 0's, or a letterbox extent comes out 0; labels and eval are both NULL; a labels[b] or truths[b] is NULL; a stride
+ * is below widths[b]; eval has no truths or no counts; eval->ignore_label >= 256 (no byte equals it; negative: nothing is
+ * ignored); or the label maps of the batch, with their truths, exceed 2 GiB. */
+typedef struct {
+    const uint8_t *const *truths;
+    const int *strides;
+    int ignore_label;
+    int64_t *counts;
+    int64_t ignored, out_of_range;
+} bcnn_label_map_eval;
+BCNN_API bcnn_status bcnn_get_label_maps_batch(bcnn_net *net, int tensor_index, int num_images, const int *widths,
+                                               const int *heights, int fit, int align_corners,
+                                               uint8_t *const *labels, const int *strides, bcnn_label_map_eval *eval);
 
 /* ---------------------------------------------------------------------------------------------
  * Additions of the MI355X build (no reference counterpart).

@@ -483,6 +483,53 @@ void bcnn_hip_softmax_loss_confusion(const bcnn_hip_softmax_loss_desc *desc, con
 int bcnn_hip_softmax_loss_c_reg(void);
 
 /* ---------------------------------------------------------------------------------------------
+ * Label maps at each image's own size (label_map.hip). No reference counterpart: the output end of semantic
+ * segmentation, as bcnn_hip_yolo_detect_batch is the detector's. From x_d, [n][c][h][w] on the device (logits or
+ * probabilities: the call resamples what it is given), image b of the call gets one class index per pixel of ITS extent:
+ *   a rectangle (roi_x, roi_y, roi_w, roi_h) of plane b is resampled bilinearly to out_w x out_h -- the interp node's rule
+ *   (csrc/interp_rule.h) applied to the rectangle as if it were a tensor of that extent, the same float32 association,
+ *   so every value is, bit for bit, what bcnn_hip_interp_forward writes for the cropped rectangle -- and the label is the
+ *   FIRST maximum over the classes (start at class 0, replace on strict >; a NaN never wins and a NaN at class 0 is never
+ *   replaced). The resampled c x out_h x out_w floats are never stored. The one definition is csrc/label_map_rule.h.
+ *   label_map_fit (host only, no device needed): the rectangle of an iw x ih image in the W x H plane for a fit of
+ *     BCNN_HIP_IMAGE_FIT_*: the whole plane (STRETCH) or the letterbox geometry of bcnn_hip_fill_images, (x_off, y_off,
+ *     new_w, new_h). 1 with *out untouched: out NULL, an extent below 1, an unknown fit, a letterbox extent of 0.
+ *   label_maps_plan (host only): the layout of the result block the call stages -- image b's labels are out_h rows of
+ *     row_strides[b] = round_up(out_w, 4) bytes at offsets[b], every image on a 16-byte boundary, *total_bytes in all
+ *     (each output may be NULL). The truths of an evaluating call are staged in a second block of the same layout. 1 with
+ *     nothing written: what label_maps_batch refuses about imgs, num_images (< 1), c, h, w, or a total -- doubled when
+ *     with_truths != 0 -- past 2^31 bytes.
+ *   label_maps_batch: labels[b] (host) receives out_h rows of out_w bytes, label_strides[b] bytes apart (label_strides
+ *     NULL: out_w); bytes between out_w and the stride are not written. labels may be NULL when truths are given.
+ *     truths[b] (host, same extents, truth_strides likewise) turns the call into an evaluation: a truth byte t is ignored
+ *     (ignore_label >= 0 and t == ignore_label), valid (t < c) or out of range (csrc/softmax_loss_rule.h on (float)t);
+ *     a valid pixel with label a adds 1 to counts[t * c + a]. counts (c * c), *ignored and *out_of_range (either may be
+ *     NULL) are ADDED into, so that a validation set accumulates over its batches. Integer atomics only: two runs give
+ *     the same counts.
+ *     One host-to-device copy (descriptors, truths), one kernel for the whole batch whatever the image sizes, one
+ *     device-to-host copy (label bytes, counts), one synchronise of the calling thread's stream: the outputs are complete
+ *     when the call returns.
+ *     Returns 1, with every output untouched and nothing queued, for: x_d or imgs NULL; n < 1; num_images < 1 or > n;
+ *     c < 1 or > 256; h or w < 1; an output extent < 1; a rectangle that is empty or leaves the plane; labels and truths
+ *     both NULL; a NULL labels[b] / truths[b]; a stride below out_w; truths without counts; ignore_label >= 256 (no byte
+ *     equals it; negative: nothing is ignored); a plane of more than 2^30 elements; a total past 2^31 bytes.
+ *   label_maps_kernel_ms (measurement only): enable != 0 makes the later calls of this thread bracket their kernel with
+ *     two device events -- the call is synchronous, so events recorded around it span its copies too; returns the kernel
+ *     time of the latest bracketed call in milliseconds (-1: none yet).
+ * ------------------------------------------------------------------------------------------- */
+typedef struct bcnn_hip_label_map_image {
+    int out_w, out_h, roi_x, roi_y, roi_w, roi_h;
+} bcnn_hip_label_map_image;
+int bcnn_hip_label_map_fit(int fit, int W, int H, int iw, int ih, bcnn_hip_label_map_image *out);
+int bcnn_hip_label_maps_plan(const bcnn_hip_label_map_image *imgs, int num_images, int c, int h, int w, int with_truths,
+                             unsigned *row_strides, unsigned long long *offsets, unsigned long long *total_bytes);
+int bcnn_hip_label_maps_batch(const float *x_d, int n, int c, int h, int w, int align_corners,
+                              const bcnn_hip_label_map_image *imgs, int num_images, uint8_t *const *labels,
+                              const int *label_strides, const uint8_t *const *truths, const int *truth_strides,
+                              int ignore_label, long long *counts, long long *ignored, long long *out_of_range);
+float bcnn_hip_label_maps_kernel_ms(int enable);
+
+/* ---------------------------------------------------------------------------------------------
  * Channel scaling (the scale-channels node; scale_channels.hip). No reference counterpart.
  *   x is [n][c][hw]; gate is [n][c] (same_shape == 0: one factor per plane) or [n][c][hw] (same_shape != 0).
  *   forward : y = x * gate, one multiply per element (8 bytes per element moved, 12 with a same-shape gate).
