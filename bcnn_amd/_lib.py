@@ -151,6 +151,10 @@ SIGNATURES = {
     "bcnn_hip_dilated_conv_workspace_size": (sz, [i] * 10),
     "bcnn_hip_dilated_conv_forward": (None, [vp, vp, vp, vp] + [i] * 11),
     "bcnn_hip_dilated_conv_backward": (None, [vp] * 7 + [i] * 11 + [vp, sz]),
+    "bcnn_hip_dilated_depthwise_workspace_size": (sz, [i] * 8),
+    "bcnn_hip_dilated_depthwise_forward": (None, [vp, vp, vp, vp] + [i] * 9),
+    "bcnn_hip_dilated_depthwise_backward": (None, [vp] * 7 + [i] * 10 + [vp, sz]),
+    "bcnn_hip_dilated_depthwise_path": (i, [i] * 9),
     "bcnn_hip_interp_forward": (None, [vp, vp, vp, i, i, i, i]),
     "bcnn_hip_interp_backward": (None, [vp, vp, vp, i, i, i, i, i]),
     "bcnn_hip_interp_axis_taps": (None, [i, i, i, vp, vp, vp]),

@@ -26,6 +26,7 @@ POOL2D_MAX, POOL2D_AVG = 0, 1
 LAYER_ACTIVATION, LAYER_POOL2D, LAYER_SCALE_CHANNELS, LAYER_GROUPNORM = 3, 17, 18, 19
 LAYER_CONV2D, LAYER_BATCHNORM, LAYER_DILATED_CONV2D, LAYER_INTERP = 0, 9, 20, 21
 LAYER_SOFTMAX_LOSS = 22
+LAYER_DEPTHWISE_CONV2D, LAYER_DILATED_DEPTHWISE_CONV2D = 2, 23
 LOSS_NORM_NONE, LOSS_NORM_VALID, LOSS_NORM_VALID_PER_IMAGE = 0, 1, 2
 LOSS_NORMS = {"none": LOSS_NORM_NONE, "valid": LOSS_NORM_VALID, "valid_per_image": LOSS_NORM_VALID_PER_IMAGE}
 
@@ -138,6 +139,7 @@ def lib():
         "bcnn_add_depthwise_conv_layer": (i, [vp, i, i, i, i, i, i, cp, cp]),
         "bcnn_add_deconvolutional_layer": (i, [vp, i, i, i, i, i, i, cp, cp]),
         "bcnn_add_dilated_conv_layer": (i, [vp, i, i, i, i, i, i, i, i, cp, cp]),
+        "bcnn_add_dilated_depthwise_conv_layer": (i, [vp, i, i, i, i, i, i, cp, cp]),
         "bcnn_add_interp_layer": (i, [vp, i, i, i, i, i, cp, cp]),
         "bcnn_add_softmax_loss_layer": (i, [vp, i, i, f, cp, cp, cp]),
         "bcnn_get_softmax_loss_stats": (i, [vp, i, C.POINTER(SoftmaxLossStats)]),
@@ -246,6 +248,12 @@ class Net:
     def depthwise(self, k, s, p, act=ACT_NONE, src="input", dst="dw"):
         return self._added(self.L.bcnn_add_depthwise_conv_layer(self.net, k, s, p, 0, FILLER_XAVIER, act,
                                                                  src.encode(), dst.encode()))
+
+    def dilated_depthwise(self, k, s, p, d, act=ACT_NONE, src="input", dst="ddw", init=FILLER_XAVIER):
+        """bcnn_add_dilated_depthwise_conv_layer: one k x k filter per channel with taps d apart, stride s, pad p; d == 1
+        builds an ordinary depthwise node"""
+        return self._added(self.L.bcnn_add_dilated_depthwise_conv_layer(self.net, k, s, p, d, init, act, src.encode(),
+                                                                         dst.encode()))
 
     def batchnorm(self, src, dst):
         return self._added(self.L.bcnn_add_batchnorm_layer(self.net, src.encode(), dst.encode()))
@@ -380,7 +388,7 @@ class Net:
 
     def set_inference_precision(self, precision):
         """bcnn_set_inference_precision: PRECISION_BF16 runs every convolution node of a PREDICT / VALID forward on the
-        bf16 matrix cores (fp32 accumulator; depthwise, deconvolution, dilated-convolution and full-connected nodes stay fp32); a TRAIN-mode
+        bf16 matrix cores (fp32 accumulator; depthwise (dilated or not), deconvolution, dilated-convolution and full-connected nodes stay fp32); a TRAIN-mode
         pass is never affected. Returns the bcnn_status (1 = BCNN_INVALID_PARAMETER for an unknown value)."""
         return self.L.bcnn_set_inference_precision(self.net, precision)
 

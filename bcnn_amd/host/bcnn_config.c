@@ -197,7 +197,7 @@ typedef struct {
     int has_from; /* Darknet `from=`: src_id[0] is the previous section, src_id[1] the named one */
     int has_groups; /* [groupnorm]: the section wrote groups= (the default of num_groups, 1, belongs to convolutions) */
     float eps;      /* [groupnorm] / [layernorm] / [instancenorm]; 0: the builder's default */
-    int dilation;   /* [conv] / [convolutional]: > 1 builds the dilated-convolution node; default 1 */
+    int dilation;   /* [conv] / [convolutional], [depthwise-conv] / [dw-conv]: > 1 builds the dilated node; default 1 */
     int scale, zoom, out_w, out_h, align_corners; /* [interp] / [bilinear]; scale= may be written stride= (has_stride) */
     /* [softmax_loss] / [softmaxwithloss]: ignore_label (default -1), normalize (a bcnn_loss_norm, -1: a value the section
      * wrote that is none of the three names; default valid_per_image) and scale= read as a float (default 1) */
@@ -428,6 +428,9 @@ static bcnn_status add_layer(bcnn_net *net, const char *name, layer_param *lp) {
     if (is_any(name, "[deconv]", "[deconvolutional]", NULL, NULL))
         return add_split_act(net, bcnn_add_deconvolutional_layer(net, lp->n_filts, lp->size, lp->stride, lp->pad, lp->init,
                                                                  fused_act(lp), src, dst), lp);
+    if (is_any(name, "[depthwise-conv]", "[dw-conv]", NULL, NULL) && lp->dilation > 1)
+        return add_split_act(net, bcnn_add_dilated_depthwise_conv_layer(net, lp->size, lp->stride, lp->pad, lp->dilation,
+                                                                        lp->init, fused_act(lp), src, dst), lp);
     if (is_any(name, "[depthwise-conv]", "[dw-conv]", NULL, NULL))
         return add_split_act(net, bcnn_add_depthwise_conv_layer(net, lp->size, lp->stride, lp->pad, 0, lp->init, fused_act(lp),
                                                                 src, dst), lp);

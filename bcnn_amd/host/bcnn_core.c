@@ -404,13 +404,14 @@ static void mark_dead_grad_fills(bcnn_net *net) {
         if (uses == 1 && (nd->type == BCNN_LAYER_MAXPOOL || nd->type == BCNN_LAYER_DEPTHWISE_CONV2D ||
                           nd->type == BCNN_LAYER_LRN || nd->type == BCNN_LAYER_POOL2D ||
                           nd->type == BCNN_LAYER_GROUPNORM || nd->type == BCNN_LAYER_INTERP ||
-                          nd->type == BCNN_LAYER_SOFTMAX_LOSS)) {
+                          nd->type == BCNN_LAYER_SOFTMAX_LOSS || nd->type == BCNN_LAYER_DILATED_DEPTHWISE_CONV2D)) {
             /* max-pooling's gather, the depthwise data gradient (a gather too: one thread owns a dx element,
              * bcnn_depthwise_conv_layer.c:432-547 accumulates onto the zero fill), LRN's (one lane per column), the
              * pool2d gather, whose overwrite form also writes the elements no window covers, group-norm's sweep (one
              * thread owns a dx element), the bilinear interpolation's gather, whose overwrite form also writes the
              * elements a downsampling skips, and the softmax loss, whose overwrite form writes +0.0 on the pixels that are
-             * not valid */
+             * not valid, and the dilated depthwise data gradient, a gather like the depthwise one whose overwrite form also
+             * writes the elements no tap reaches */
             hc->grad_fill_dead[t] = 2;
             continue;
         }
@@ -589,10 +590,11 @@ static bcnn_status resize_plan(bcnn_net *net, int w, int h, int c, int need_real
          * [n][c][1][1] embedding the lifted-structure loss was built on (and its label) survive the call. */
         const bcnn_layer_type t = net->nodes[i].type;
         BCNN_CHECK_AND_LOG(net->log_ctx, t != BCNN_LAYER_CONCAT && t != BCNN_LAYER_UPSAMPLE && t != BCNN_LAYER_YOLOV3 &&
-                                             t != BCNN_LAYER_TRANSPOSE_CONV2D && t != BCNN_LAYER_DILATED_CONV2D,
+                                             t != BCNN_LAYER_TRANSPOSE_CONV2D && t != BCNN_LAYER_DILATED_CONV2D &&
+                                             t != BCNN_LAYER_DILATED_DEPTHWISE_CONV2D,
                            BCNN_INVALID_PARAMETER,
-                           "bcnn_resize_net: node %d is a concat / upsample / YOLO / deconvolution / dilated-convolution "
-                           "node, whose resize is not supported\n", i);
+                           "bcnn_resize_net: node %d is a concat / upsample / YOLO / deconvolution / dilated-convolution / "
+                           "dilated-depthwise-convolution node, whose resize is not supported\n", i);
         BCNN_CHECK_AND_LOG(net->log_ctx,
                            t != BCNN_LAYER_COST || ((const bcnn_cost_param *)net->nodes[i].param)->loss != BCNN_LOSS_LIFTED_STRUCT,
                            BCNN_INVALID_PARAMETER,
@@ -926,7 +928,7 @@ static void sgd_table_add(bcnn_hip_context *hc, float *w, float *g, size_t n, in
 static int update_is_tabled(const bcnn_node *nd) {
     return nd->update == bcnn_update_conv_layer || nd->update == bcnn_update_depthwise_conv_layer ||
            nd->update == bcnn_update_fullc_layer || nd->update == bcnn_update_deconv_layer ||
-           nd->update == bcnn_update_dilated_conv_layer;
+           nd->update == bcnn_update_dilated_conv_layer || nd->update == bcnn_update_dilated_depthwise_layer;
 }
 
 void bcnn_update(bcnn_net *net) {
@@ -1153,6 +1155,8 @@ int bcnn_get_node_activation(bcnn_net *net, int node) {
     const bcnn_node *nd = &net->nodes[node];
     if (nd->type == BCNN_LAYER_DILATED_CONV2D) /* (a constant behind the enum: no case label) */
         return (int)((const bcnn_dilated_conv_param *)nd->param)->activation;
+    if (nd->type == BCNN_LAYER_DILATED_DEPTHWISE_CONV2D)
+        return (int)((const bcnn_dilated_depthwise_param *)nd->param)->activation;
     switch (nd->type) {
         case BCNN_LAYER_CONV2D: return (int)((const bcnn_conv_param *)nd->param)->activation;
         case BCNN_LAYER_TRANSPOSE_CONV2D: return (int)((const bcnn_deconv_param *)nd->param)->activation;

@@ -507,6 +507,18 @@ typedef struct bcnn_dilated_conv_param {
 #endif
 } bcnn_dilated_conv_param;
 
+/* dilated depthwise convolution (bcnn_add_dilated_depthwise_conv_layer with dilation > 1; no reference counterpart);
+ * weights [c][size][size], the depthwise node's layout */
+typedef struct bcnn_dilated_depthwise_param {
+    int size, stride, pad, dilation;
+    bcnn_activation activation;
+#ifdef BCNN_USE_HIP
+    float *workspace_gpu; /* the node's own dW / dbias partials (bcnn_hip_dilated_depthwise_workspace_size), first backward */
+    size_t workspace_size;
+    float *adam_m_gpu, *adam_v_gpu; /* weight moments, allocated by the first Adam step */
+#endif
+} bcnn_dilated_depthwise_param;
+
 /* local response normalisation across channels (reference src/layers/bcnn_lrn_layer.h); no buffers: the backward
  * recomputes the scale from the input */
 typedef struct bcnn_lrn_param {
@@ -624,6 +636,10 @@ void bcnn_forward_dilated_conv_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_dilated_conv_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_update_dilated_conv_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_dilated_conv_layer(bcnn_node *node);
+void bcnn_forward_dilated_depthwise_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_backward_dilated_depthwise_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_update_dilated_depthwise_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_release_param_dilated_depthwise_layer(bcnn_node *node);
 void bcnn_forward_lrn_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_lrn_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_lrn_layer(bcnn_node *node);

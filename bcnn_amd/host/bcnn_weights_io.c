@@ -2,7 +2,7 @@
  *
  * Byte-compatible with the reference (src/bcnn_net.c:595-681 writer, :1219-1558 reader):
  *   "BCNN" | u32 major | u32 minor | u32 patch | per node, in node order:
- *     conv / deconv / dilated conv / depthwise / full-connected : biases, weights [, conv with batch-norm: means,
+ *     conv / deconv / dilated conv / depthwise (dilated or not) / full-connected : biases, weights [, conv with batch-norm: means,
  *                                         variances, scales]
  *     PReLU activation node             : slopes
  *     batch-norm node                   : means, variances, scales, biases (dst channels each)
@@ -47,6 +47,7 @@ bcnn_status bcnn_save_weights(bcnn_net *net, const char *filename) {
         bcnn_node *nd = &net->nodes[i];
         if (nd->type == BCNN_LAYER_CONV2D || nd->type == BCNN_LAYER_TRANSPOSE_CONV2D ||
             nd->type == BCNN_LAYER_DILATED_CONV2D || nd->type == BCNN_LAYER_DEPTHWISE_CONV2D ||
+            nd->type == BCNN_LAYER_DILATED_DEPTHWISE_CONV2D ||
             nd->type == BCNN_LAYER_FULL_CONNECTED) {
             bcnn_tensor *w = &net->tensors[nd->src[1]], *b = &net->tensors[nd->src[2]];
             ok = put(fp, b, bcnn_tensor_size(b)) && put(fp, w, bcnn_tensor_size(w));
@@ -227,7 +228,8 @@ bcnn_status bcnn_load_weights(bcnn_net *net, const char *filename) {
     for (int i = 0; st == BCNN_SUCCESS && i < net->num_nodes; ++i) {
         bcnn_node *nd = &net->nodes[i];
         if (nd->type == BCNN_LAYER_CONV2D || nd->type == BCNN_LAYER_TRANSPOSE_CONV2D ||
-            nd->type == BCNN_LAYER_DILATED_CONV2D || nd->type == BCNN_LAYER_DEPTHWISE_CONV2D) {
+            nd->type == BCNN_LAYER_DILATED_CONV2D || nd->type == BCNN_LAYER_DEPTHWISE_CONV2D ||
+            nd->type == BCNN_LAYER_DILATED_DEPTHWISE_CONV2D) {
             st = load_conv(net, nd, fp, format);
         } else if (nd->type == BCNN_LAYER_ACTIVATION) {
             if (((bcnn_activation_param *)nd->param)->activation == BCNN_ACT_PRELU && format == 0) {

@@ -142,6 +142,40 @@ def dilated_conv_backward(x, wt, y, dy, dx, dw, dbias, k, stride, pad, dilation,
                                                workspace.numel() if workspace is not None else 0)
 
 
+DILATED_DEPTHWISE_PATHS = ("generic", "plane", "bands")
+
+
+def dilated_depthwise_path(n, c, h, w, k, s, p, d, backward=False):
+    """bcnn_hip_dilated_depthwise_path: the kernel family of the shape, 0 generic, 1 plane, 2 bands
+    (DILATED_DEPTHWISE_PATHS); -1 for a shape the workers refuse. Needs no device."""
+    return int(_lib.load().bcnn_hip_dilated_depthwise_path(n, c, h, w, k, s, p, d, 1 if backward else 0))
+
+
+def dilated_depthwise_workspace_size(n, c, h, w, k, s, p, d):
+    return int(_lib.load().bcnn_hip_dilated_depthwise_workspace_size(n, c, h, w, k, s, p, d))
+
+
+def dilated_depthwise_forward(x, wt, bias, y, k, stride, pad, dilation, act=0):
+    """bcnn_hip_dilated_depthwise_forward (depthwise_dilated.hip). wt: [c][k][k] (any shape of that size), y
+    [n][c][oh][ow] with (oh, ow) = dilated_conv_out_hw(...) is overwritten with act(dilated depthwise convolution + bias)."""
+    n, c, h, w = x.shape
+    assert wt.numel() == c * k * k and y.shape[1] == c
+    _lib.load().bcnn_hip_dilated_depthwise_forward(_f32(x), _f32(wt), _f32(bias), _f32(y), n, c, h, w, k, stride, pad,
+                                                   dilation, act)
+
+
+def dilated_depthwise_backward(x, wt, y, dy, dx, dw, dbias, k, stride, pad, dilation, act, overwrite, workspace):
+    """bcnn_hip_dilated_depthwise_backward. dy is updated in place (dy * act'(y)), dbias and dw accumulate (no scaling), dx
+    (may be None) accumulates, or is assigned when overwrite is set. workspace: at least
+    dilated_depthwise_workspace_size(...) floats."""
+    n, c, h, w = x.shape
+    assert wt.numel() == c * k * k
+    _lib.load().bcnn_hip_dilated_depthwise_backward(_f32(x), _f32(wt), _f32(y), _f32(dy), _f32(dx), _f32(dw),
+                                                    _f32(dbias), n, c, h, w, k, stride, pad, dilation, act,
+                                                    1 if overwrite else 0, _f32(workspace),
+                                                    workspace.numel() if workspace is not None else 0)
+
+
 def lrn_forward(x, y, local_size, alpha, beta, k):
     """LRN across channels (include/bcnn_hip.h; the reference's bcnn_lrn_layer.c:106-149 with its deviations fixed):
     y = x * (k + alpha/n sum_window x^2)^-beta, overwritten."""

@@ -74,6 +74,8 @@ typedef enum {
 #define BCNN_LAYER_INTERP ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 4))
 /* The layer type of bcnn_add_softmax_loss_layer, likewise a constant behind the enumerator list. */
 #define BCNN_LAYER_SOFTMAX_LOSS ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 5))
+/* The layer type of bcnn_add_dilated_depthwise_conv_layer with dilation > 1, likewise a constant behind the enumerator list. */
+#define BCNN_LAYER_DILATED_DEPTHWISE_CONV2D ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 6))
 
 typedef enum {
     BCNN_ACT_NONE, BCNN_ACT_TANH, BCNN_ACT_RELU, BCNN_ACT_RAMP, BCNN_ACT_SOFTPLUS,
@@ -257,6 +259,17 @@ BCNN_API bcnn_status bcnn_add_deconvolutional_layer(bcnn_net *net, int num_filte
 BCNN_API bcnn_status bcnn_add_dilated_conv_layer(bcnn_net *net, int num_filters, int size, int stride, int pad,
                                                  int dilation, int num_groups, bcnn_filler_type init,
                                                  bcnn_activation activation, const char *src_id, const char *dst_id);
+/* Dilated (atrous) depthwise convolution: one size x size filter per channel whose taps sit `dilation` pixels apart, output
+ * extent (h + 2 pad - dilation (size - 1) - 1) / stride + 1; weights "<src>_w" (c * size * size floats laid out
+ * [c][size][size]), biases "<src>_b", the depthwise node's tensors. dilation == 1 delegates to
+ * bcnn_add_depthwise_conv_layer and builds an ordinary BCNN_LAYER_DEPTHWISE_CONV2D; dilation > 1 builds a
+ * BCNN_LAYER_DILATED_DEPTHWISE_CONV2D node (fp32 in every precision mode, no batch-norm fusion; bcnn_resize_net refuses a
+ * net that holds one). Refused with BCNN_INVALID_PARAMETER, nothing added: an unknown src, size < 1, stride < 1, pad < 0,
+ * dilation < 1, a non-positive output extent, PReLU, and the activations that need the layer's input (hard-swish, swish,
+ * mish). */
+BCNN_API bcnn_status bcnn_add_dilated_depthwise_conv_layer(bcnn_net *net, int size, int stride, int pad, int dilation,
+                                                           bcnn_filler_type init, bcnn_activation activation,
+                                                           const char *src_id, const char *dst_id);
 BCNN_API bcnn_status bcnn_add_depthwise_conv_layer(bcnn_net *net, int size, int stride, int pad, int batch_norm,
                                                    bcnn_filler_type init, bcnn_activation activation,
                                                    const char *src_id, const char *dst_id);
@@ -479,7 +492,7 @@ BCNN_API bcnn_status bcnn_get_lifted_struct_loss(bcnn_net *net, float *loss, int
  * bias / fused batch-norm / activation are computed as before. The output of a node then differs from the fp32 one by at
  * most about 2^-8 * sum |x| |w| per element, which is outside the 1e-4 parity the default path holds:
  * hence opt-in. Every convolution node takes it, whatever its shape, so that the numerics of a net are predictable.
- * Depthwise-convolution, deconvolution, dilated-convolution and full-connected nodes stay fp32. The value may be set in any mode and takes
+ * Depthwise-convolution (dilated or not), deconvolution, dilated-convolution and full-connected nodes stay fp32. The value may be set in any mode and takes
  * effect only while the net's mode is PREDICT or VALID: a BCNN_MODE_TRAIN pass never uses it (its backward needs the fp32
  * forward). An unknown value returns BCNN_INVALID_PARAMETER and changes nothing. Config files: `inference_precision=bf16`
  * (or `fp32`) in the [net] section. */

@@ -1149,6 +1149,36 @@ void bcnn_hip_dilated_conv_backward(const float *x_d, const float *w_d, const fl
                                     size_t workspace_elems);
 
 /* ---------------------------------------------------------------------------------------------
+ * Dilated (atrous) depthwise convolution: one k x k filter per channel, taps `dilation` pixels apart
+ * (depthwise_dilated.hip). No reference counterpart; torch.nn.functional.conv2d(groups = c,
+ * dilation) is the oracle. The entry points mirror bcnn_hip_depthwise_forward / _backward with `dilation` added.
+ *   - x [n][c][h][w], weights [c][k][k] (the depthwise node's layout; the same floats are the dilated node's
+ *     [c][1][k][k] at groups == c), bias [c], y [n][c][oh][ow], oh = (h + 2 pad - dilation (k - 1) - 1) / stride + 1;
+ *     any k >= 1, stride >= 1, pad >= 0, dilation >= 1;
+ *   - forward: y = act(sum of taps + bias), OVERWRITTEN; out-of-range taps read zero. The taps are added ky outer, kx
+ *     inner, every product and add rounded on its own: at dilation 1 y has the bits of bcnn_hip_depthwise_forward
+ *     (except that a bias of exactly 1.0 is added here too);
+ *   - backward, in this order: dy_d <- dy_d * act'(y_d) in place; dbias_d += and dw_d += (unscaled; either may be NULL);
+ *     dx_d NULL: no data gradient, else dx_d += or, with overwrite != 0, assigned (every element, those no tap reaches
+ *     too). At dilation 1 dx has the bits of bcnn_hip_depthwise_backward. The weight gradient does not depend on dx_d;
+ *   - activations: those of the dilated convolution (no PReLU, none that need the layer's input).
+ * workspace_d: at least bcnn_hip_dilated_depthwise_workspace_size floats, the per-(plane, band) partial sums of dw and
+ * dbias that a finalize kernel adds in index order: no atomics, the same bits on every run; a smaller one ends the
+ * process. bcnn_hip_dilated_depthwise_path: the kernel family of the shape, 0 generic (k != 3, stride > 1, rows too wide
+ * for a band), 1 plane (the staged plane, x forward and dy backward, is at most 12288 floats: one workgroup per plane in
+ * LDS), 2 bands (row bands with a 2 dilation halo); -1 for a shape the workers refuse. The two queries need no device. An
+ * unsupported shape (a non-positive extent, a tensor of 2^31 elements or more) ends the process with a message.
+ * ------------------------------------------------------------------------------------------- */
+size_t bcnn_hip_dilated_depthwise_workspace_size(int n, int c, int h, int w, int k, int stride, int pad, int dilation);
+void bcnn_hip_dilated_depthwise_forward(const float *x_d, const float *w_d, const float *bias_d, float *y_d, int n, int c,
+                                        int h, int w, int k, int stride, int pad, int dilation, int act);
+void bcnn_hip_dilated_depthwise_backward(const float *x_d, const float *w_d, const float *y_d, float *dy_d, float *dx_d,
+                                         float *dw_d, float *dbias_d, int n, int c, int h, int w, int k, int stride,
+                                         int pad, int dilation, int act, int overwrite, float *workspace_d,
+                                         size_t workspace_elems);
+int bcnn_hip_dilated_depthwise_path(int n, int c, int h, int w, int k, int stride, int pad, int dilation, int backward);
+
+/* ---------------------------------------------------------------------------------------------
  * Local response normalisation across channels (Caffe / torch.nn.functional.local_response_norm). The reference's
  * device workers are empty (bcnn_lrn_layer.c:207-225); its CPU workers (:106-201) are wrong for every local_size
  * (INTEGRATION.md). NCHW, channel stride h*w; with n_w = local_size:
