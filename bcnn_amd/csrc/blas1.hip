@@ -107,6 +107,16 @@ struct DotF {
         acc[0] += (a.x * b.x + a.y * b.y) + (a.z * b.z + a.w * b.w);
     }
 };
+// the same products in the same association for tensors of which one does not start on a 16-byte boundary: 4-byte loads
+struct DotUnalignedF {
+    static constexpr int kInFlight = 4;
+    const float* g;
+    const float* x;
+    __device__ void operator()(long long off, int, float (&acc)[1]) const { acc[0] += g[off] * x[off]; }
+    __device__ void vec4(long long off, int, float (&acc)[1]) const {
+        acc[0] += (g[off] * x[off] + g[off + 1] * x[off + 1]) + (g[off + 2] * x[off + 2] + g[off + 3] * x[off + 3]);
+    }
+};
 
 // out[c] += sum over splits (fixed order, double)
 __global__ void chan_accumulate_kernel(const float* __restrict__ partials, int C, int splits,
@@ -148,7 +158,9 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ w, float*
         const float vi = __fadd_rn(__fmul_rn(one_m_b2, __fmul_rn(gi, gi)), __fmul_rn(b2, v[i]));
         m[i] = mi;
         v[i] = vi;
-        const float q = __fdiv_rn(mi, __fadd_rn(__fsqrt_rn(vi), 0.0000001f));
+        // sqrtf, not __fsqrt_rn: without OCML_BASIC_ROUNDED_OPERATIONS the intrinsic is the bare v_sqrt_f32 (1 ulp); sqrtf is
+        // the correctly rounded root
+        const float q = __fdiv_rn(mi, __fadd_rn(sqrtf(vi), 0.0000001f));
         w[i] = __fadd_rn(__fmul_rn(q, step), wi);
         g[i] = 0.f;
     }
@@ -256,7 +268,9 @@ void bcnn_hip_grad_scales(const float* x_norm, const float* g, int n, int c, int
     if (!M || !c) return;
     const int splits = chan_splits(c, M);
     float* part = scratch(SCRATCH_REDUCE, (size_t)c * splits);
-    launch_chan_reduce<1>(DotF{g, x_norm}, c, hw, M, splits, part);
+    if (((reinterpret_cast<uintptr_t>(x_norm) | reinterpret_cast<uintptr_t>(g)) & 15) == 0)
+        launch_chan_reduce<1>(DotF{g, x_norm}, c, hw, M, splits, part);
+    else launch_chan_reduce<1>(DotUnalignedF{g, x_norm}, c, hw, M, splits, part);
     chan_accumulate_kernel<<<ceil_div(c, 256), 256, 0, current_stream()>>>(part, c, splits, dscales);
     KERNEL_CHECK();
 }

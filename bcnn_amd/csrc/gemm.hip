@@ -199,6 +199,7 @@ void bcnn_hip_gemm(int ta, int tb, int m, int n, int k, float alpha, const float
 void bcnn_hip_im2col(const float* im, int channels, int height, int width, int ksize, int pad, int stride,
                      float* col) {
     const int oh = (height + 2 * pad - ksize) / stride + 1, ow = (width + 2 * pad - ksize) / stride + 1;
+    if (oh <= 0 || ow <= 0) return;  // no window fits (both negative would give a positive product)
     const long long total = (long long)channels * ksize * ksize * oh * ow;
     if (total <= 0) return;
     im2col_kernel<<<stream_grid((size_t)total, 256), 256, 0, current_stream()>>>(

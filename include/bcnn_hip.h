@@ -53,7 +53,9 @@ void bcnn_hip_free(void *p_d);                    /* bcnn_cuda_free, bcnn_utils.
 void bcnn_hip_memcpy_h2d(void *dst_d, const void *src_h, size_t bytes); /* bcnn_cuda_memcpy_host2dev */
 void bcnn_hip_memcpy_d2h(void *dst_h, const void *src_d, size_t bytes); /* bcnn_cuda_memcpy_dev2host */
 void bcnn_hip_memcpy_d2d(void *dst_d, const void *src_d, size_t bytes);
-void bcnn_hip_fill_f32(float *x_d, size_t n, float value); /* bcnn_cuda_fill_f32, bcnn_mat.cu:52-60 */
+/* bcnn_cuda_fill_f32, bcnn_mat.cu:52-60. A zero of either sign is a memset: value == -0.0f stores +0.0f (all-zero bits);
+ * every other value is stored with its own bits. x_d needs float alignment only. */
+void bcnn_hip_fill_f32(float *x_d, size_t n, float value);
 void bcnn_hip_sync(void);                         /* waits for the calling thread's stream */
 /* The stream all entry points launch on (per host thread). NULL = the device's null stream, which
  * is also PyTorch-ROCm's default stream. bcnn_hip_stream_create returns an opaque hipStream_t. */
@@ -98,12 +100,15 @@ size_t bcnn_hip_trace_read(char *buf, size_t cap);
  * BLAS-1 / per-channel helpers.  Replaces bcnn_cuda_axpy/scal/copy (bcnn_mat.cu:44-100),
  * bcnn_cuda_add_bias / bcnn_cuda_grad_bias (bcnn_mat.cu:348-391), bcnn_scales_gpu /
  * bcnn_grad_scales_gpu (bcnn_mat.cu:393-438); CPU semantics bcnn_mat.c:52-115, 319-412, 761-811.
- * Tensor pointers of the per-channel helpers must be 16-byte aligned: the reduction sweeps behind the gradient helpers take
- * their float4 path on hw % 4 == 0 alone.
+ * Tensor pointers need float alignment only: every helper takes its 16-byte accesses when the pointers it is handed are
+ * 16-byte aligned and 4-byte accesses otherwise; the two gradient helpers add the same terms in the same order either
+ * way, so a misaligned call gives the bits of the aligned one.
  * ------------------------------------------------------------------------------------------- */
-void bcnn_hip_axpy(size_t n, float a, const float *x_d, float *y_d);   /* y += a*x */
-void bcnn_hip_scal(size_t n, float a, float *x_d);                      /* x *= a (a==0 -> zero-fill) */
-void bcnn_hip_copy_f32(size_t n, const float *x_d, float *y_d);
+/* y = fl(fl(x*a) + y): the product and the sum are rounded separately (never one fused multiply-add) */
+void bcnn_hip_axpy(size_t n, float a, const float *x_d, float *y_d);
+/* x *= a; a == 0 stores +0.0f whatever x holds (NaN included), a == 1 touches nothing */
+void bcnn_hip_scal(size_t n, float a, float *x_d);
+void bcnn_hip_copy_f32(size_t n, const float *x_d, float *y_d);          /* bit copy; x_d == y_d is a no-op */
 /* y[b][c][:] += bias[c]; channels whose bias is exactly 0.0f or 1.0f are left untouched, as in
  * the reference AVX build (bcnn_add_scalar, bcnn_mat.c:366-412). */
 void bcnn_hip_add_bias(float *y_d, const float *bias_d, int n, int c, int hw);
@@ -117,6 +122,10 @@ void bcnn_hip_grad_scales(const float *x_norm_d, const float *g_d, int n, int c,
  * bcnn_cuda_col2im (:526-576); semantics of bcnn_gemm (bcnn_mat.c:2627-2650), bcnn_im2col (:817-854),
  * bcnn_col2im (:935-970, zero-fills then scatter-adds => OVERWRITES im).
  * Row-major C[m x n] = alpha * op(A) * op(B) + beta * C on the fp32 MFMA path.
+ * im2col writes every element of col (zeros for padding); col2im writes every element of im (zeros where no window
+ * reaches) and adds a pixel's terms in ascending (kr, kc) order, the order the reference's scatter reaches it in.
+ * A shape no window fits in (height + 2 pad < ksize or width + 2 pad < ksize): im2col has no output and touches
+ * nothing; col2im reads nothing and zero-fills im, as the reference's does.
  * ------------------------------------------------------------------------------------------- */
 void bcnn_hip_gemm(int trans_a, int trans_b, int m, int n, int k, float alpha, const float *a_d,
                    int lda, const float *b_d, int ldb, float beta, float *c_d, int ldc);
@@ -687,7 +696,9 @@ void bcnn_hip_sgd_update(float *w_d, float *b_d, float *dw_d, float *db_d, size_
  *   dw += (decay*batch)*w; m = (1-b1)*dw + b1*m; v = (1-b2)*dw^2 + b2*v;
  *   w -= (lr/batch)*mu * m/(sqrt(v)+1e-7); dw = 0,  mu = sqrt(1-b2^(iter+1))/(1-b1^(iter+1)).
  * `iter` is what the reference passes: learner->seen (samples, not steps). adam_m_d / adam_v_d are
- * w_size floats each, zero before the first step, owned by the caller. */
+ * w_size floats each, zero before the first step, owned by the caller.
+ * Every product, sum, the division and the square root are single correctly rounded float operations; the reference
+ * takes powf(v, 0.5f) for the root, so w may differ from it in the last bits while m, v and dw are its bits. */
 void bcnn_hip_adam_update(float *w_d, float *b_d, float *dw_d, float *db_d, float *adam_m_d,
                           float *adam_v_d, size_t w_size, size_t b_size, int batch_size, int iter,
                           float beta1, float beta2, float learning_rate, float momentum, float decay);
