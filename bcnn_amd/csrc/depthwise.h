@@ -104,13 +104,17 @@ inline bool dw_in_sums_wanted(const DwBwdCall& c) {
 // activations its kernels can apply (dw_fused_fwd_ok / dw_fused_bwd_ok of depthwise.hip). `takes` decides everything else that
 // can refuse the layer -- plane geometry, alignment, LDS -- and touches nothing; `run` then launches. `slots`: partials per
 // channel of its statistics / sums / weight-gradient partials, 0 when the shape is not the family's.
+// The marching family also asks its tensors to be aligned to a lane's access (16 / 8 / 4 bytes), which no shape tells: slots
+// for a shape do not promise that it takes a call. The LDS family asks nothing of the pointers and has one `slots` per
+// direction: non-zero exactly for the shapes that direction's `takes` accepts (the tiling AND a workgroup's LDS).
 size_t depthwise_march_splits(const DwShape& s);
 bool depthwise_march_fwd_takes(const DwFwdCall& c);
 void depthwise_march_forward(const DwFwdCall& c);
 bool depthwise_march_bwd_takes(const DwBwdCall& c);
 void depthwise_march_backward(const DwBwdCall& c);
 
-size_t depthwise_lds_slots(const DwShape& s);
+size_t depthwise_lds_fwd_slots(const DwShape& s);
+size_t depthwise_lds_bwd_slots(const DwShape& s);
 bool depthwise_lds_fwd_takes(const DwFwdCall& c);
 void depthwise_lds_forward(const DwFwdCall& c);
 bool depthwise_lds_bwd_takes(const DwBwdCall& c);

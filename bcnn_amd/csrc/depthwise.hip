@@ -606,24 +606,27 @@ static void dw_unfused_backward(const DwBwdCall& c) {
 // The first two of each are the FUSED families, asked only behind dw_fused_shape and the activation rules below; only they can
 // serve `stats` / `in` / `bn` / `in_sums`. The size queries and the backward scratch are the maximum of `slots` over the rows.
 // A new family is a row here and its declarations in depthwise.h.
+// `by_shape`: `takes` looks at the shape alone, so non-zero `slots` are its yes. A family without it (the marching one: aligned
+// tensors) may refuse a call whose shape it has slots for; the *_fusable predicates, which see no pointers, do not count on it.
 template <class Call>
 struct DwFamily {
     bool fused;
     bool (*takes)(const Call& c);  // decides everything that can refuse the layer, touches nothing
     void (*run)(const Call& c);    // cannot refuse
     size_t (*slots)(const DwShape& s);
+    bool by_shape;
 };
 static size_t dw_no_slots(const DwShape&) { return 0; }
 static const DwFamily<DwFwdCall> kDwFwdFamilies[] = {
-    {true, depthwise_march_fwd_takes, depthwise_march_forward, depthwise_march_splits},
-    {true, depthwise_lds_fwd_takes, depthwise_lds_forward, depthwise_lds_slots},
-    {false, dw_window3_fwd_takes, dw_window3_forward, dw_no_slots},
-    {false, [](const DwFwdCall&) { return true; }, dw_generic_forward, dw_no_slots},
+    {true, depthwise_march_fwd_takes, depthwise_march_forward, depthwise_march_splits, false},
+    {true, depthwise_lds_fwd_takes, depthwise_lds_forward, depthwise_lds_fwd_slots, true},
+    {false, dw_window3_fwd_takes, dw_window3_forward, dw_no_slots, false},
+    {false, [](const DwFwdCall&) { return true; }, dw_generic_forward, dw_no_slots, false},
 };
 static const DwFamily<DwBwdCall> kDwBwdFamilies[] = {
-    {true, depthwise_march_bwd_takes, depthwise_march_backward, depthwise_march_splits},
-    {true, depthwise_lds_bwd_takes, depthwise_lds_backward, depthwise_lds_slots},
-    {false, [](const DwBwdCall&) { return true; }, dw_unfused_backward, dw_no_slots},
+    {true, depthwise_march_bwd_takes, depthwise_march_backward, depthwise_march_splits, false},
+    {true, depthwise_lds_bwd_takes, depthwise_lds_backward, depthwise_lds_bwd_slots, true},
+    {false, [](const DwBwdCall&) { return true; }, dw_unfused_backward, dw_no_slots, false},
 };
 
 // the fused families' shape gate. Experiment build: BCNN_HIP_NO_DW_LDS turns both off, BCNN_HIP_NO_DW_MARCH the marching one
@@ -654,6 +657,15 @@ static size_t dw_slots(const DwFamily<Call> (&rows)[R], const DwShape& s) {
     if (dw_fused_shape(s))
         for (const DwFamily<Call>& fam : rows) m = std::max(m, fam.slots(s));
     return m;
+}
+// a fused family takes this shape whatever the pointers of the call turn out to be: what an entry point that has nothing to
+// fall back to needs, and so what the *_fusable predicates answer
+template <class Call, size_t R>
+static bool dw_fused_by_shape(const DwFamily<Call> (&rows)[R], const DwShape& s) {
+    if (!dw_fused_shape(s)) return false;
+    for (const DwFamily<Call>& fam : rows)
+        if (fam.fused && fam.by_shape && fam.slots(s)) return true;
+    return false;
 }
 
 // false: no family takes the layer (one with `in` that the fused families refuse); nothing has been launched
@@ -746,13 +758,20 @@ size_t bcnn_hip_depthwise_insums_size(int n, int c, int h, int wd, int k, int st
     return (size_t)c * dw_slots(kDwBwdFamilies, dw_shape(n, c, h, wd, k, stride, pad)) * 2;
 }
 
+// The two predicates see a shape and no pointers, and the entry points behind them end the process when refused: they say yes
+// only where a fused family takes the shape by itself. Slots alone are not that -- the marching family has them for every row
+// of up to 64 column groups and then wants aligned tensors, and the LDS family's tiling has them for 2 x 500 planes whose
+// backward workgroup (four padded planes per tile, twice) needs more LDS than there is.
 int bcnn_hip_depthwise_bn_fusable(int n, int c, int h, int wd, int k, int stride, int pad, int act) {
-    return dw_slots(kDwBwdFamilies, dw_shape(n, c, h, wd, k, stride, pad)) && act_bwd_is_cheap(act) && act != BCNN_HIP_ACT_PRELU;
+    return dw_fused_by_shape(kDwBwdFamilies, dw_shape(n, c, h, wd, k, stride, pad)) && act_bwd_is_cheap(act) &&
+           act != BCNN_HIP_ACT_PRELU;
 }
 
+// forward and backward of the layer go together: the producer's normalised output exists in neither pass
 int bcnn_hip_depthwise_bnin_fusable(int n, int c, int h, int wd, int k, int stride, int pad, int act, int in_act) {
-    return bcnn_hip_depthwise_bn_fusable(n, c, h, wd, k, stride, pad, act) && act_is_cheap(act) && act_is_cheap(in_act) &&
-           in_act != BCNN_HIP_ACT_PRELU;
+    return bcnn_hip_depthwise_bn_fusable(n, c, h, wd, k, stride, pad, act) &&
+           dw_fused_by_shape(kDwFwdFamilies, dw_shape(n, c, h, wd, k, stride, pad)) && act_is_cheap(act) &&
+           act_is_cheap(in_act) && in_act != BCNN_HIP_ACT_PRELU;
 }
 
 void bcnn_hip_depthwise_backward(const float* x, const float* w, const float* y, float* dy, float* dx,

@@ -862,6 +862,7 @@ __global__ __launch_bounds__(256) void dwl_finalize_kernel(const float* __restri
 }
 
 constexpr int kVR1 = 4, kVR2 = 2;  // output rows per thread, stride 1 / 2
+constexpr size_t kDwlMaxLds = 64 * 1024;  // bytes of LDS a workgroup of these kernels may ask for
 
 }  // namespace
 
@@ -871,7 +872,7 @@ void dwl_finalize_launch(const float* partials, int splits, int C, float* dw, fl
 }
 
 // what the tiling adds to the fused-shape gate of depthwise.hip; slots per channel: one per image and band
-size_t depthwise_lds_slots(const DwShape& s) {
+static size_t dwl_slots(const DwShape& s) {
     if (s.W > kTileFloats / 8) return 0;  // a band needs at least 3 + stride input rows of <= kTileFloats floats
     const DwlGeom g = dwl_plan(s);
     const long long tiles = (long long)ceil_div((long long)s.N * s.C, g.P) * g.NB;
@@ -892,10 +893,15 @@ static size_t dwl_fwd_plan(const DwShape& s, DwlFwdArgs* a) {
     return (size_t)(a->x_floats + a->g.stage_floats + a->g.P * kConst) * sizeof(float);
 }
 
-bool depthwise_lds_fwd_takes(const DwFwdCall& c) {
+// Slots of a shape the forward kernel takes, 0 for one it refuses: the tiling and a workgroup's LDS are all that can refuse (no
+// alignment is asked of any pointer), so a shape with slots is taken whatever the call's pointers are
+size_t depthwise_lds_fwd_slots(const DwShape& s) {
     DwlFwdArgs a;
-    return depthwise_lds_slots(c.s) && dwl_fwd_plan(c.s, &a) <= 64 * 1024;
+    const size_t slots = dwl_slots(s);
+    return slots && dwl_fwd_plan(s, &a) <= kDwlMaxLds ? slots : 0;
 }
+
+bool depthwise_lds_fwd_takes(const DwFwdCall& c) { return depthwise_lds_fwd_slots(c.s) != 0; }
 
 void depthwise_lds_forward(const DwFwdCall& c) {
     const DwShape& s = c.s;
@@ -940,17 +946,24 @@ static size_t dwl_bwd_plan(const DwBwdCall& c, DwlBwdArgs* ap, bool* sums) {
     // hold a dx piece (stride 2); where that does not fit the layer is still taken, without the sums
     *sums = dw_in_sums_wanted(c) && c.in_sums->partials && c.in_sums->capacity >= (size_t)s.C * a.splits * 2;
     if (*sums && a.g.P > 1 && a.g_floats < a.g.stage_floats) {
-        if ((size_t)(a.x_floats + a.g.stage_floats + a.g.P * kConst) * sizeof(float) <= 64 * 1024) a.g_floats = a.g.stage_floats;
+        if ((size_t)(a.x_floats + a.g.stage_floats + a.g.P * kConst) * sizeof(float) <= kDwlMaxLds) a.g_floats = a.g.stage_floats;
         else *sums = false;
     }
     return (size_t)(a.x_floats + a.g_floats + a.g.P * kConst) * sizeof(float);
 }
 
-bool depthwise_lds_bwd_takes(const DwBwdCall& c) {
+// The same for the backward kernel, every variant of it (`bn`, `in`, in_sums): dwl_bwd_plan enlarges the g image for the sums
+// only where the enlarged workgroup still fits and drops the sums otherwise, so the plan without them is the one that decides
+size_t depthwise_lds_bwd_slots(const DwShape& s) {
+    DwBwdCall c{};
+    c.s = s;
     DwlBwdArgs a;
     bool sums;
-    return depthwise_lds_slots(c.s) && dwl_bwd_plan(c, &a, &sums) <= 64 * 1024;
+    const size_t slots = dwl_slots(s);
+    return slots && dwl_bwd_plan(c, &a, &sums) <= kDwlMaxLds ? slots : 0;
 }
+
+bool depthwise_lds_bwd_takes(const DwBwdCall& c) { return depthwise_lds_bwd_slots(c.s) != 0; }
 
 void depthwise_lds_backward(const DwBwdCall& c) {
     const DwShape& s = c.s;

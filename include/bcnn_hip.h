@@ -326,7 +326,9 @@ int bcnn_hip_conv_backward_bnsums(const float *x_d, const float *w_d, const floa
  * g = dx * act'(act(bn(raw))) per channel in in_sums_d (bcnn_hip_depthwise_insums_size floats) and returns the number of
  * partials per channel (0: not emitted -- overwrite == 0, or the buffer is too small). bcnn_hip_conv_backward_presummed is
  * bcnn_hip_conv_backward_bnsums (prev_* may be NULL) that takes those partials (own_sums_d, own_splits > 0) instead of
- * sweeping (dy, pre-normalisation tensor) for them; with own_splits == 0 it is bcnn_hip_conv_backward_bnsums. */
+ * sweeping (dy, pre-normalisation tensor) for them; with own_splits == 0 it is bcnn_hip_conv_backward_bnsums.
+ * bcnn_hip_depthwise_insums_size is the most any kernel that may take the shape writes: a non-zero size does NOT say that the
+ * layer is fusable (a kernel that wants aligned tensors counts towards it); ask bcnn_hip_depthwise_bnin_fusable for that. */
 size_t bcnn_hip_depthwise_insums_size(int n, int c, int h, int w, int k, int stride, int pad);
 int bcnn_hip_depthwise_backward_bnin_sums(const float *x_raw_d, const float *w_d, const float *y_d, float *dy_d, float *dx_d,
                                           float *dw_d, float *dbias_d, int n, int c, int h, int w, int k, int stride, int pad,
@@ -605,13 +607,20 @@ void bcnn_hip_depthwise_backward(const float *x_d, const float *w_d, const float
  * runs whole passes share work between the two workers. Results are those of the separate calls (forward, dx: the
  * same operations in the same order; statistics and gradient sums: fixed-order two-level sums).
  *   bcnn_hip_depthwise_stats_size      floats the statistics scratch of this layer shape needs; 0 = this shape's
- *                                      forward kernel emits no statistics
+ *                                      forward kernel emits no statistics. The most any kernel that may take the shape
+ *                                      writes: a non-zero size promises neither statistics (the return value of
+ *                                      bcnn_hip_depthwise_forward_stats does) nor that the layer is fusable
  *   bcnn_hip_depthwise_forward_stats   bcnn_hip_depthwise_forward that also leaves per-channel partial sums
  *                                      (sum, sum of squares of y) in stats_d; returns the number of partials per
  *                                      channel, 0 when none were written
  *   bcnn_hip_batchnorm_forward_stats   bcnn_hip_batchnorm_forward (TRAIN mode) that takes those partials instead of
  *                                      reading x_d for its statistics (splits == 0: plain bcnn_hip_batchnorm_forward)
- *   bcnn_hip_depthwise_bn_fusable      non-zero when bcnn_hip_depthwise_backward_bn handles this layer
+ *   bcnn_hip_depthwise_bn_fusable      non-zero when bcnn_hip_depthwise_backward_bn handles this layer, whatever the
+ *                                      alignment of the tensors it is then given. (A layer only the kernels that want
+ *                                      16- / 8- / 4-byte aligned tensors could take -- planes of a few columns and
+ *                                      hundreds of rows -- is not fusable; nor is one whose LDS tile does not fit: 2 rows
+ *                                      of 476 to 511 columns at stride 1.) bcnn_hip_depthwise_backward_bn ends the
+ *                                      process on a layer this refuses.
  *   bcnn_hip_batchnorm_backward_sums   first half of bcnn_hip_batchnorm_backward: dbias / dscales accumulate, dmean /
  *                                      dvar are written; dy_d is NOT rewritten (x_d: the batch-norm input)
  *   bcnn_hip_batchnorm_backward_apply  second half of bcnn_hip_batchnorm_backward alone (dmean / dvar from the first):
