@@ -40,6 +40,7 @@
 
 #include "../host/bip_effects.h"
 #include "../host/bip_resize_tap.h"
+#include "image_fill.h"
 #include "jpeg_pixels.h"
 #include "store_run.h"
 
@@ -193,17 +194,9 @@ __global__ __launch_bounds__(kAugBlock) void augment_geometry_kernel(uint8_t* __
     }
 }
 
-// bcnn_hip_augment_letterbox_batch: one source image of the batch, in image_fill.h's ImageDesc shape (that header's
-// host_stage is image_fill.hip's own block, so the struct is restated here). Offsets count from the block's first byte.
-struct LetterboxDesc {
-    uint32_t data_off;            // packed pixels: h rows of w * c bytes
-    uint32_t tapx_off, tapy_off;  // int2 (index, frac) per column of the resized image / per row
-    int w, h;                     // source extent
-    int new_w, new_h;             // extent of the resized image inside the W x H canvas
-    int x_off, y_off;             // where it is pasted; everything outside is kCanvas
-};
+// bcnn_hip_augment_letterbox_batch: a source image of the batch is an ImageDesc (image_fill.h) whose plane is the canvas.
 struct LetterboxParams {
-    uint32_t desc_off, canvas_off;  // the descriptors; the canvases, dense W x H x C each (AugParams::pix_off)
+    uint32_t desc_off, canvas_off;  // the ImageDescs; the canvases, dense W x H x C each (AugParams::pix_off)
     int W, H;
     int chunks_per_row, blocks_per_sample;
 };
@@ -225,7 +218,7 @@ __global__ __launch_bounds__(kAugBlock) void augment_letterbox_kernel(uint8_t* _
     const int q0 = (int)chunk_at - (int)row_at;
     const int first = q0 < 0 ? -q0 : 0, last = min(kChunk, row_bytes - q0);
     if (first >= last) return;
-    const LetterboxDesc d = reinterpret_cast<const LetterboxDesc*>(block + p.desc_off)[b];
+    const ImageDesc d = reinterpret_cast<const ImageDesc*>(block + p.desc_off)[b];
     uint32_t word[kChunk / 4];
 #pragma unroll
     for (int i = 0; i < kChunk / 4; ++i) word[i] = 0x01010101u * kCanvas;
@@ -397,44 +390,7 @@ __global__ __launch_bounds__(kAugBlock) void augment_convert_effects_kernel(cons
     }
 }
 
-// Pinned host side of the staging block (image_fill.hip's pattern): grow-only, one per host thread and device. `copied`
-// is recorded behind the latest copy out of it; the next call waits for it before it overwrites (or frees) the block.
-struct HostStage { uint8_t* p = nullptr; size_t cap = 0; hipEvent_t copied = nullptr; bool in_flight = false; };
-thread_local HostStage g_stage[kMaxDevices];
-
-uint8_t* host_stage(size_t bytes) {
-    HostStage& s = g_stage[current_device()];
-    if (s.in_flight) {
-        HIP_CHECK(hipEventSynchronize(s.copied));
-        s.in_flight = false;
-    }
-    if (!s.copied) HIP_CHECK(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
-    if (s.p == nullptr || s.cap < bytes) {
-        if (s.p) HIP_CHECK(hipHostFree(s.p));
-        s.cap = bytes + bytes / 4;
-        HIP_CHECK(hipHostMalloc((void**)&s.p, s.cap, hipHostMallocDefault));
-    }
-    return s.p;
-}
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// The block of this thread, at least `bytes` long, with its first `keep` bytes as they are: for the one caller that has
-// laid a batch out before it learns that effects ride along (bcnn_hip_augment_jpeg_run). No copy is in flight there.
-uint8_t* host_stage_extend(size_t keep, size_t bytes) {
-    HostStage& s = g_stage[current_device()];
-    if (s.p != nullptr && s.cap >= bytes) return s.p;
-    uint8_t* grown = nullptr;
-    const size_t cap = bytes + bytes / 4;
-    HIP_CHECK(hipHostMalloc((void**)&grown, cap, hipHostMallocDefault));
-    if (s.p) {
-        memcpy(grown, s.p, keep);
-        HIP_CHECK(hipHostFree(s.p));
-    }
-    s.p = grown;
-    s.cap = cap;
-    return s.p;
-}
+// Every entry point below stages its batch in the pinned block of STAGE_AUGMENT (common.h) and sends it up with stage_upload.
 
 // What bcnn_hip_augment_effects_begin staged for this thread's next batch call: the blob that goes into that call's block
 // as it is (FxHeader ...), and the batch it was made for.
@@ -489,6 +445,8 @@ bool taps_in_range(const bcnn_hip_augment_record* records, const int32_t* taps, 
 struct PendingJpeg {
     bool active = false;
     uint8_t* stage;
+    int device;            // where _begin took the block, and the block's generation then: _run refuses when another
+    uint64_t generation;   // call has taken it since (`stage` may point into freed memory)
     int c, h, w, num;
     size_t sum_off, tap_off, win_off, planes_at, images_at, raw_at, device_at, plane_bytes, pixel_bytes, total;
     std::vector<uint32_t> coeff_off;   // per sample; 0: not a candidate
@@ -527,7 +485,7 @@ int bcnn_hip_augment_batch(float* dst_d, int n, int c, int h, int w, int num_sam
 
     // the staging block: [records][channel sums, zero][taps][pixels][staged effects]; behind it on the device, the rotated
     // samples
-    uint8_t* stage = host_stage(total);
+    uint8_t* stage = host_stage(STAGE_AUGMENT, total);
     AugParams p;
     p.rec_off = 0;
     p.sum_off = (uint32_t)rec_bytes;
@@ -544,12 +502,8 @@ int bcnn_hip_augment_batch(float* dst_d, int n, int c, int h, int w, int num_sam
         for (size_t b = 0; b < num; ++b) reinterpret_cast<bcnn_hip_augment_record*>(stage)[b].flags &= ~BCNN_HIP_AUG_SCALE;
 
     // ---- one copy, two launches
-    uint8_t* block_d = reinterpret_cast<uint8_t*>(scratch(SCRATCH_AUGMENT, (total + pix_bytes + 3) / 4));
     hipStream_t st = current_stream();
-    HIP_CHECK(hipMemcpyAsync(block_d, stage, total, hipMemcpyHostToDevice, st));
-    HostStage& hs = g_stage[current_device()];
-    HIP_CHECK(hipEventRecord(hs.copied, st));
-    hs.in_flight = true;
+    uint8_t* block_d = stage_upload(STAGE_AUGMENT, SCRATCH_AUGMENT, total, total + pix_bytes, st);
 
     p.sw = src_w;
     p.sh = src_h;
@@ -596,7 +550,7 @@ int bcnn_hip_augment_letterbox_batch(float* dst_d, int n, int c, int h, int w, i
     if (any_scale && !taps) return 1;
     const size_t rec_bytes = align_up(num * sizeof(bcnn_hip_augment_record), 16), sum_bytes = num * 4 * sizeof(uint32_t);
     const size_t tap_bytes = any_scale ? align_up(num * sample_taps * 2 * sizeof(int32_t), 16) : 0;
-    const size_t desc_bytes = align_up(num * sizeof(LetterboxDesc), 16);
+    const size_t desc_bytes = align_up(num * sizeof(ImageDesc), 16);
     const size_t canvas_bytes = align_up(num * sample_bytes, 16);
     const size_t desc_at = rec_bytes + sum_bytes + tap_bytes, lb_tap_at = desc_at + desc_bytes;
     const size_t src_at = lb_tap_at + align_up(lb_tap_bytes, 16), fx_at = src_at + src_bytes, total = fx_at + fx_bytes;
@@ -605,39 +559,28 @@ int bcnn_hip_augment_letterbox_batch(float* dst_d, int n, int c, int h, int w, i
 
     // the staging block: [records][channel sums, zero][augmentation taps][descriptors][letterbox taps][source pixels]
     // [staged effects]; behind it on the device, the canvases and the rotated samples
-    uint8_t* stage = host_stage(total);
+    uint8_t* stage = host_stage(STAGE_AUGMENT, total);
     if (fx_bytes) memcpy(stage + fx_at, g_fx.blob.data(), fx_bytes);
     memcpy(stage, records, num * sizeof(bcnn_hip_augment_record));
     memset(stage + rec_bytes, 0, sum_bytes);
     if (any_scale) memcpy(stage + rec_bytes + sum_bytes, taps, num * sample_taps * 2 * sizeof(int32_t));
     else  // no tap table was staged: no record may ask for one
         for (size_t b = 0; b < num; ++b) reinterpret_cast<bcnn_hip_augment_record*>(stage)[b].flags &= ~BCNN_HIP_AUG_SCALE;
-    LetterboxDesc* desc = reinterpret_cast<LetterboxDesc*>(stage + desc_at);
+    ImageDesc* desc = reinterpret_cast<ImageDesc*>(stage + desc_at);
     size_t tap_at = lb_tap_at, pix_at = src_at;
     for (size_t b = 0; b < num; ++b) {
         const bcnn_hip_letterbox_image& im = images[b];
-        LetterboxDesc& d = desc[b];
+        ImageDesc& d = desc[b];
         d.w = im.w; d.h = im.h; d.new_w = im.new_w; d.new_h = im.new_h; d.x_off = im.x_off; d.y_off = im.y_off;
-        d.tapx_off = (uint32_t)tap_at;
-        d.tapy_off = (uint32_t)(tap_at + (size_t)im.new_w * sizeof(int2));
-        int2* tx = reinterpret_cast<int2*>(stage + d.tapx_off);
-        int2* ty = reinterpret_cast<int2*>(stage + d.tapy_off);
-        const float xs = bip_resize_scale((size_t)im.w, (size_t)im.new_w), ys = bip_resize_scale((size_t)im.h, (size_t)im.new_h);
-        for (int x = 0; x < im.new_w; ++x) bip_resize_tap((size_t)x, xs, (size_t)im.w, &tx[x].x, &tx[x].y);
-        for (int y = 0; y < im.new_h; ++y) bip_resize_tap((size_t)y, ys, (size_t)im.h, &ty[y].x, &ty[y].y);
-        tap_at += ((size_t)im.new_w + im.new_h) * sizeof(int2);
+        tap_at += stage_taps(stage, tap_at, d);
         d.data_off = (uint32_t)pix_at;
         memcpy(stage + pix_at, im.pixels, (size_t)im.w * im.h * c);
         pix_at += align_up((size_t)im.w * im.h * c, 16);
     }
 
     // ---- one copy, three launches
-    uint8_t* block_d = reinterpret_cast<uint8_t*>(scratch(SCRATCH_AUGMENT, (total + 2 * canvas_bytes + 3) / 4));
     hipStream_t st = current_stream();
-    HIP_CHECK(hipMemcpyAsync(block_d, stage, total, hipMemcpyHostToDevice, st));
-    HostStage& hs = g_stage[current_device()];
-    HIP_CHECK(hipEventRecord(hs.copied, st));
-    hs.in_flight = true;
+    uint8_t* block_d = stage_upload(STAGE_AUGMENT, SCRATCH_AUGMENT, total, total + 2 * canvas_bytes, st);
 
     LetterboxParams lp;
     lp.desc_off = (uint32_t)desc_at;
@@ -718,7 +661,9 @@ int bcnn_hip_augment_jpeg_begin(int n, int c, int h, int w, int num_samples, con
     q.total = q.device_at + plane_bytes + pixel_bytes + raw_bytes;
     if (q.total > (size_t)0x7fffffff || blocks > 0x7fffffffull || runs > 0x7fffffffull) return 1;
 
-    q.stage = host_stage(q.device_at);
+    q.stage = host_stage(STAGE_AUGMENT, q.device_at);
+    q.device = current_device();
+    q.generation = stage_generation(STAGE_AUGMENT);
     q.coeff_off.assign(num, 0);
     q.frames.assign(frames, frames + num);
     size_t c_at = coeff_at;
@@ -814,6 +759,7 @@ int bcnn_hip_augment_jpeg_run(float* dst_d, const uint8_t* decoded, const uint8_
     const size_t fx_bytes = take_effects(q.active ? q.num : 0, q.active ? q.w : 0, q.active ? q.h : 0, fx_mismatch);
     if (!q.active) return 1;
     q.active = false;
+    if (current_device() != q.device || stage_generation(STAGE_AUGMENT) != q.generation) return 1;  // the block is another call's
     if (fx_mismatch || !dst_d || !decoded || !pixels || !records || !origins) return 1;
     const size_t num = (size_t)q.num, sample_bytes = (size_t)q.w * q.h * q.c, sample_taps = (size_t)q.w + q.h;
     bool any_scale = false;
@@ -829,7 +775,7 @@ int bcnn_hip_augment_jpeg_run(float* dst_d, const uint8_t* decoded, const uint8_
 
     uint8_t* stage = q.stage;
     if (fx_bytes) {
-        stage = q.stage = host_stage_extend(q.device_at, fx_at + fx_bytes);
+        stage = q.stage = host_stage_extend(STAGE_AUGMENT, q.device_at, fx_at + fx_bytes);
         memcpy(stage + fx_at, g_fx.blob.data(), fx_bytes);
     }
     memcpy(stage, records, num * sizeof(bcnn_hip_augment_record));
@@ -857,12 +803,8 @@ int bcnn_hip_augment_jpeg_run(float* dst_d, const uint8_t* decoded, const uint8_
     jpeg_close_tables(stage, q.planes_at, q.images_at, cur);
 
     // ---- one copy, four launches
-    uint8_t* block_d = reinterpret_cast<uint8_t*>(scratch(SCRATCH_AUGMENT, (total + 3) / 4));
     hipStream_t st = current_stream();
-    HIP_CHECK(hipMemcpyAsync(block_d, stage, fx_bytes ? fx_at + fx_bytes : raw_at, hipMemcpyHostToDevice, st));
-    HostStage& hs = g_stage[current_device()];
-    HIP_CHECK(hipEventRecord(hs.copied, st));
-    hs.in_flight = true;
+    uint8_t* block_d = stage_upload(STAGE_AUGMENT, SCRATCH_AUGMENT, fx_bytes ? fx_at + fx_bytes : raw_at, total, st);
     launch_jpeg_pixels(block_d, (uint32_t)q.planes_at, (uint32_t)q.images_at, cur, st);
 
     AugParams p;

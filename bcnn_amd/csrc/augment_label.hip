@@ -6,9 +6,9 @@
 // batch's own); the kernel does integer work only.
 //
 // One pinned staging block [records][taps][maps] goes up in ONE copy on the current stream and ONE kernel follows: a
-// pointwise function of one mask byte per pixel -- wave64, no LDS, no atomics, no barrier. The block is this file's own
-// (grow-only, one per host thread and device), so a call does not wait for the copy of the image batch that is still in
-// flight out of augment.hip's block; the device side is the slot SCRATCH_AUGMENT_LABEL of the library's table.
+// pointwise function of one mask byte per pixel -- wave64, no LDS, no atomics, no barrier. The block is the slot STAGE_AUGMENT_LABEL of the
+// library's pinned table (common.h), not the image batch's STAGE_AUGMENT, so a call does not wait for the copy of the image
+// batch that is still in flight; the device side is the slot SCRATCH_AUGMENT_LABEL of the scratch table.
 // The minimum traffic is 1 byte read and 4 bytes written per pixel, so the stores are what matters: when w % 4 == 0 and
 // the tensor is 16-byte aligned a lane owns four consecutive pixels of a row and issues one 16-byte store (a wave writes
 // 1 KiB of consecutive floats); otherwise a lane owns one pixel. The mask bytes are a gather through the cache (a rotated
@@ -76,29 +76,6 @@ __global__ __launch_bounds__(kLabelBlock) void augment_label_kernel(const uint8_
     }
 }
 
-// Pinned host side of the staging block (augment.hip's pattern, a block of this file's own): grow-only, one per host
-// thread and device. `copied` is recorded behind the latest copy out of it; the next call waits for it before it
-// overwrites (or frees) the block.
-struct LabelStage { uint8_t* p = nullptr; size_t cap = 0; hipEvent_t copied = nullptr; bool in_flight = false; };
-thread_local LabelStage g_label_stage[kMaxDevices];
-
-uint8_t* label_stage(size_t bytes) {
-    LabelStage& s = g_label_stage[current_device()];
-    if (s.in_flight) {
-        HIP_CHECK(hipEventSynchronize(s.copied));
-        s.in_flight = false;
-    }
-    if (!s.copied) HIP_CHECK(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
-    if (s.p == nullptr || s.cap < bytes) {
-        if (s.p) HIP_CHECK(hipHostFree(s.p));
-        s.cap = bytes + bytes / 4;
-        HIP_CHECK(hipHostMalloc((void**)&s.p, s.cap, hipHostMallocDefault));
-    }
-    return s.p;
-}
-
-inline size_t align16(size_t v) { return (v + 15) / 16 * 16; }
-
 }  // namespace
 }  // namespace bcnn_hip
 
@@ -114,8 +91,8 @@ extern "C" int bcnn_hip_augment_label_batch(float* label_d, int n, int h, int w,
     bool any_scale = false;
     for (size_t b = 0; b < num; ++b) any_scale = any_scale || (records[b].flags & BCNN_HIP_AUG_SCALE);
     if (any_scale && !taps) return 1;
-    const size_t rec_bytes = align16(num * sizeof(bcnn_hip_augment_record));
-    const size_t tap_bytes = any_scale ? align16(num * sample_taps * sizeof(int32_t)) : 0;
+    const size_t rec_bytes = align_up(num * sizeof(bcnn_hip_augment_record), 16);
+    const size_t tap_bytes = any_scale ? align_up(num * sample_taps * sizeof(int32_t), 16) : 0;
     const size_t total = rec_bytes + tap_bytes + num * map_bytes;
     if (total > (size_t)0x7fff0000) return 1;  // the block, and every lane index of the launch, below 2 GiB
     if (any_scale)  // the range taps_in_range (augment.hip) allows: index + 1 stays inside the sample
@@ -123,18 +100,14 @@ extern "C" int bcnn_hip_augment_label_batch(float* label_d, int n, int h, int w,
             if (!bip_label_taps_ok(records[b].flags, taps + b * sample_taps, taps + b * sample_taps + 2 * (size_t)w, w, h))
                 return 1;
 
-    uint8_t* stage = label_stage(total);
+    uint8_t* stage = host_stage(STAGE_AUGMENT_LABEL, total);
     memcpy(stage, records, num * sizeof(bcnn_hip_augment_record));
     if (any_scale) memcpy(stage + rec_bytes, taps, num * sample_taps * sizeof(int32_t));
     memcpy(stage + rec_bytes + tap_bytes, maps, num * map_bytes);
 
     // ---- one copy, one launch
-    uint8_t* block_d = reinterpret_cast<uint8_t*>(scratch(SCRATCH_AUGMENT_LABEL, (total + 3) / 4));
     hipStream_t st = current_stream();
-    HIP_CHECK(hipMemcpyAsync(block_d, stage, total, hipMemcpyHostToDevice, st));
-    LabelStage& hs = g_label_stage[current_device()];
-    HIP_CHECK(hipEventRecord(hs.copied, st));
-    hs.in_flight = true;
+    uint8_t* block_d = stage_upload(STAGE_AUGMENT_LABEL, SCRATCH_AUGMENT_LABEL, total, total, st);
 
     LabelParams p;
     p.rec_off = 0;

@@ -71,6 +71,30 @@ enum ScratchSlot {
 float* scratch(ScratchSlot slot, size_t floats);
 inline float4* scratch_f4(ScratchSlot slot, size_t n) { return reinterpret_cast<float4*>(scratch(slot, n * 4)); }
 
+// ---- library-private pinned host staging (runtime.hip) ------------------------------------------------------------------------
+// The host side of "stage a batch in pinned memory, send it up in one copy": grow-only blocks, one per host thread, device and
+// slot. The one rule: the copy in flight out of a block is waited for before the block is overwritten or freed. Two slots never
+// wait for each other, so an image batch and its label batch overlap.
+enum StageSlot {
+    STAGE_IMAGES,        // descriptors, tap tables and pixels / JPEG coefficients of the batched input fill (image_fill.hip, jpeg_pixels.hip)
+    STAGE_AUGMENT,       // records, channel sums, tap tables, samples, JPEG tables and staged effects of a training batch (augment.hip)
+    STAGE_AUGMENT_LABEL, // records, tap tables and raw uint8 masks of a batch of label maps (augment_label.hip)
+    STAGE_LABEL_MAP,     // descriptors, truth bytes, counts and label bytes of one label-map call, both ways (label_map.hip)
+    STAGE_SLOTS
+};
+// The slot's block on the calling thread's device, at least `bytes` long (a new one has bytes / 4 of headroom; contents are not
+// kept). Waits first for the copy that stage_upload queued out of it. Valid until the slot's next host_stage call.
+uint8_t* host_stage(StageSlot slot, size_t bytes);
+// The same block, at least `bytes` long, with its first `keep` bytes as they are: for a caller that has laid a batch out
+// before it learns how much rides along. No copy is in flight there; the block host_stage returned may have moved.
+uint8_t* host_stage_extend(StageSlot slot, size_t keep, size_t bytes);
+// Queues ONE copy of the block's first `upload_bytes` on `st` into the block of `device_bytes` of `device_slot` and marks the
+// copy as in flight. Returns the device block.
+uint8_t* stage_upload(StageSlot slot, ScratchSlot device_slot, size_t upload_bytes, size_t device_bytes, hipStream_t st);
+// Counts the slot's host_stage calls on the calling thread's device. A _begin / _run pair keeps it, with current_device(), to
+// tell that no other call has taken the block in between.
+uint64_t stage_generation(StageSlot slot);
+
 // dy *= act'(y) in place and dbias += the per-channel sums of the result (depthwise.hip's backward). blas1.hip
 void activation_backward_grad_bias(const float* y, float* dy, float* dbias, int n, int c, int hw, int act);
 
@@ -106,6 +130,7 @@ constexpr int kCUs = 256;      // MI355X
 constexpr int kXCDs = 8;
 
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // what a float4 access needs of a pointer; an absent (null) optional tensor passes
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 

@@ -1,6 +1,7 @@
 // image_fill.h -- what the batched input fill (image_fill.hip) shares with the device JPEG pixel stage
 // (jpeg_pixels.hip), which produces the uint8 pixels on the device and then runs the same fill kernel on them: the
-// per-image record, the pinned staging block of the calling thread, and the launch of fill_images_kernel.
+// per-image record, its geometry and tap tables (which augment.hip's letterbox kernel reads as well), and the launch of
+// fill_images_kernel. The pinned staging block itself is the slot STAGE_IMAGES of the library's table (common.h).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -18,15 +19,11 @@ struct ImageDesc {
     int x_off, y_off;            // where it is pasted; everything outside is the canvas value 128
 };
 
-inline size_t stage_align(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-// Pinned host side of the staging block of this thread and device, at least `bytes` long; waits for the copy that an
-// earlier call queued out of it. stage_copied() records the event behind the copy just queued on `st`.
-uint8_t* host_stage(size_t bytes);
-void stage_copied(hipStream_t st);
-
 // Extent of image iw x ih inside the W x H plane (stretch or letterbox); false when an extent comes out 0.
 bool fitted_extent(int fit, int W, int H, int iw, int ih, int* new_w, int* new_h);
+// d.w, d.h, d.new_w and d.new_h are set: writes the tap tables of the resize (new_w columns, then new_h rows) at
+// stage + tap_at and d.tapx_off / d.tapy_off; returns the bytes written.
+size_t stage_taps(uint8_t* stage, size_t tap_at, ImageDesc& d);
 // Fills d (all but data_off) and the tap tables of an iw x ih image at stage + tap_at; returns the bytes of taps written.
 size_t stage_geometry(uint8_t* stage, size_t tap_at, ImageDesc& d, int fit, int W, int H, int iw, int ih);
 // Grid of the fill kernel for num_images planes of W x H; false when it does not fit 31 bits.

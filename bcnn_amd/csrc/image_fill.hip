@@ -74,33 +74,7 @@ __global__ __launch_bounds__(kFillBlock) void fill_images_kernel(const uint8_t* 
         store_run(dst + (((size_t)b * C + k) * p.H + y) * p.W + x0, v[k], len);
 }
 
-// Pinned host side of the staging block: grow-only, one per host thread and device. `copied` is recorded behind the
-// latest copy out of it; the next call waits for it before it overwrites (or frees) the block.
-struct HostStage { uint8_t* p = nullptr; size_t cap = 0; hipEvent_t copied = nullptr; bool in_flight = false; };
-thread_local HostStage g_stage[kMaxDevices];
-
 }  // namespace
-
-uint8_t* host_stage(size_t bytes) {
-    HostStage& s = g_stage[current_device()];
-    if (s.in_flight) {
-        HIP_CHECK(hipEventSynchronize(s.copied));
-        s.in_flight = false;
-    }
-    if (!s.copied) HIP_CHECK(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
-    if (s.p == nullptr || s.cap < bytes) {
-        if (s.p) HIP_CHECK(hipHostFree(s.p));
-        s.cap = bytes + bytes / 4;
-        HIP_CHECK(hipHostMalloc((void**)&s.p, s.cap, hipHostMallocDefault));
-    }
-    return s.p;
-}
-
-void stage_copied(hipStream_t st) {
-    HostStage& hs = g_stage[current_device()];
-    HIP_CHECK(hipEventRecord(hs.copied, st));
-    hs.in_flight = true;
-}
 
 // Extent of image iw x ih inside the W x H plane: the plane itself (stretch), or the largest extent of the image's aspect
 // ratio that fits, by the reference example's integer rule (yolo_example.cc:40-75). False when an extent comes out 0.
@@ -117,20 +91,24 @@ bool fitted_extent(int fit, int W, int H, int iw, int ih, int* new_w, int* new_h
     return *new_w >= 1 && *new_h >= 1 && *new_w <= W && *new_h <= H;
 }
 
+size_t stage_taps(uint8_t* stage, size_t tap_at, ImageDesc& d) {
+    d.tapx_off = (uint32_t)tap_at;
+    int2* tx = reinterpret_cast<int2*>(stage + tap_at);
+    const float xs = bip_resize_scale((size_t)d.w, (size_t)d.new_w), ys = bip_resize_scale((size_t)d.h, (size_t)d.new_h);
+    for (int x = 0; x < d.new_w; ++x) bip_resize_tap((size_t)x, xs, (size_t)d.w, &tx[x].x, &tx[x].y);
+    d.tapy_off = (uint32_t)(tap_at + (size_t)d.new_w * sizeof(int2));
+    int2* ty = reinterpret_cast<int2*>(stage + d.tapy_off);
+    for (int y = 0; y < d.new_h; ++y) bip_resize_tap((size_t)y, ys, (size_t)d.h, &ty[y].x, &ty[y].y);
+    return ((size_t)d.new_w + d.new_h) * sizeof(int2);
+}
+
 size_t stage_geometry(uint8_t* stage, size_t tap_at, ImageDesc& d, int fit, int W, int H, int iw, int ih) {
     d.w = iw;
     d.h = ih;
     fitted_extent(fit, W, H, iw, ih, &d.new_w, &d.new_h);
     d.x_off = (W - d.new_w) / 2;
     d.y_off = (H - d.new_h) / 2;
-    d.tapx_off = (uint32_t)tap_at;
-    int2* tx = reinterpret_cast<int2*>(stage + tap_at);
-    const float xs = bip_resize_scale((size_t)iw, (size_t)d.new_w), ys = bip_resize_scale((size_t)ih, (size_t)d.new_h);
-    for (int x = 0; x < d.new_w; ++x) bip_resize_tap((size_t)x, xs, (size_t)iw, &tx[x].x, &tx[x].y);
-    d.tapy_off = (uint32_t)(tap_at + (size_t)d.new_w * sizeof(int2));
-    int2* ty = reinterpret_cast<int2*>(stage + d.tapy_off);
-    for (int y = 0; y < d.new_h; ++y) bip_resize_tap((size_t)y, ys, (size_t)ih, &ty[y].x, &ty[y].y);
-    return ((size_t)d.new_w + d.new_h) * sizeof(int2);
+    return stage_taps(stage, tap_at, d);
 }
 
 bool fill_grid(int W, int H, int num_images, int* runs_per_row, int* blocks_per_image, long long* blocks) {
@@ -181,18 +159,18 @@ int bcnn_hip_fill_images(float* dst_d, int n, int c, int h, int w, int num_image
         if (row > 0x7fffffff || (strides && strides[b] < row)) return 1;
         int new_w, new_h;
         if (!fitted_extent(fit, w, h, widths[b], heights[b], &new_w, &new_h)) return 1;
-        pixels += stage_align((size_t)row * heights[b], 16);
+        pixels += align_up((size_t)row * heights[b], 16);
         if (pixels > (size_t)0x7fffffff) return 1;
     }
     // the staging block: [descriptors][tap tables, room for W + H taps per image][pixels]; its offsets are 32-bit
-    const size_t desc_bytes = stage_align((size_t)num_images * sizeof(ImageDesc), 16);
+    const size_t desc_bytes = align_up((size_t)num_images * sizeof(ImageDesc), 16);
     const size_t taps = (size_t)num_images * ((size_t)w + h) * sizeof(int2);
     const size_t total = desc_bytes + taps + pixels;
     int runs_per_row, blocks_per_image;
     long long blocks;
     if (total > (size_t)0x7fffffff || !fill_grid(w, h, num_images, &runs_per_row, &blocks_per_image, &blocks)) return 1;
 
-    uint8_t* stage = host_stage(total);
+    uint8_t* stage = host_stage(STAGE_IMAGES, total);
     ImageDesc* desc = reinterpret_cast<ImageDesc*>(stage);
     size_t tap_at = desc_bytes, pix_at = desc_bytes + taps;
     for (int b = 0; b < num_images; ++b) {
@@ -206,13 +184,11 @@ int bcnn_hip_fill_images(float* dst_d, int n, int c, int h, int w, int num_image
         } else {
             for (int y = 0; y < ih; ++y) memcpy(stage + pix_at + y * row, images[b] + y * stride, row);
         }
-        pix_at += stage_align(row * ih, 16);
+        pix_at += align_up(row * ih, 16);
     }
     // ---- one copy, one launch
-    uint8_t* stage_d = reinterpret_cast<uint8_t*>(scratch(SCRATCH_IMAGES, (total + 3) / 4));
     hipStream_t st = current_stream();
-    HIP_CHECK(hipMemcpyAsync(stage_d, stage, total, hipMemcpyHostToDevice, st));
-    stage_copied(st);
+    uint8_t* stage_d = stage_upload(STAGE_IMAGES, SCRATCH_IMAGES, total, total, st);
     launch_fill_images(stage_d, dst_d, c, h, w, num_images, norm_coeff, swap_to_bgr, mean_r, mean_g, mean_b, st);
     return 0;
 }

@@ -158,10 +158,11 @@ __global__ __launch_bounds__(kColourThreads) void jpeg_colour_kernel(uint8_t* __
     }
 }
 
-// What bcnn_hip_jpeg_stage_begin laid out for this thread, until _run or _cancel.
+// What bcnn_hip_jpeg_stage_begin laid out for this thread in the block of STAGE_IMAGES, until _run or _cancel.
 struct Pending {
     bool active = false;
-    uint8_t* stage;                       // the pinned block
+    int device;                           // where _begin took the block, and the block's generation then: _run refuses
+    uint64_t generation;                  // when another call has taken it since
     int c, h, w;
     size_t upload, total;                 // bytes copied up / of the whole device block
     uint32_t planes_off, images_off;
@@ -196,7 +197,7 @@ bool jpeg_frame_ok(const bcnn_hip_jpeg_frame& f, int c) {
 }
 
 JpegFrameSize jpeg_frame_size(const bcnn_hip_jpeg_frame& f, int c) {
-    JpegFrameSize s = {0, 0, stage_align((size_t)f.width * f.height * c, 16), 0,
+    JpegFrameSize s = {0, 0, align_up((size_t)f.width * f.height * c, 16), 0,
                        (unsigned long long)ceil_div(f.width, kColourRun) * f.height};
     for (int k = 0; k < c; ++k) {
         const bcnn_hip_jpeg_component& p = f.comp[k];
@@ -207,8 +208,8 @@ JpegFrameSize jpeg_frame_size(const bcnn_hip_jpeg_frame& f, int c) {
     return s;
 }
 
-size_t jpeg_plane_table_bytes(int num_planes) { return stage_align(((size_t)num_planes + 1) * sizeof(JpegPlane), 16); }
-size_t jpeg_image_table_bytes(int num_images) { return stage_align(((size_t)num_images + 1) * sizeof(JpegImage), 16); }
+size_t jpeg_plane_table_bytes(int num_planes) { return align_up(((size_t)num_planes + 1) * sizeof(JpegPlane), 16); }
+size_t jpeg_image_table_bytes(int num_images) { return align_up(((size_t)num_images + 1) * sizeof(JpegImage), 16); }
 
 void jpeg_append_image(uint8_t* stage, size_t planes_at, size_t images_at, const bcnn_hip_jpeg_frame& f, int c,
                        JpegCursor& cur) {
@@ -241,7 +242,7 @@ void jpeg_append_image(uint8_t* stage, size_t planes_at, size_t images_at, const
         cur.plane_at += (size_t)p.pitch * p.rows;
     }
     cur.run_at += (uint32_t)(im.runs_per_row * f.height);
-    cur.pixel_at += stage_align((size_t)f.width * f.height * c, 16);
+    cur.pixel_at += align_up((size_t)f.width * f.height * c, 16);
     ++cur.images;
 }
 
@@ -300,8 +301,8 @@ int bcnn_hip_jpeg_stage_begin(int n, int c, int h, int w, int num_images, const 
     }
     // the device block: [image records][tap tables, room for W + H taps per image][plane table][image table]
     // [coefficients] -- so far it is the pinned block too and goes up -- [planes][pixels]; its offsets are 32-bit
-    const size_t desc_bytes = stage_align((size_t)num_images * sizeof(ImageDesc), 16);
-    const size_t taps = stage_align((size_t)num_images * ((size_t)w + h) * sizeof(int2), 16);
+    const size_t desc_bytes = align_up((size_t)num_images * sizeof(ImageDesc), 16);
+    const size_t taps = align_up((size_t)num_images * ((size_t)w + h) * sizeof(int2), 16);
     const size_t planes_at = desc_bytes + taps;
     const size_t images_at = planes_at + jpeg_plane_table_bytes(num_images * c);
     const size_t coeff_at = images_at + jpeg_image_table_bytes(num_images);
@@ -314,7 +315,7 @@ int bcnn_hip_jpeg_stage_begin(int n, int c, int h, int w, int num_images, const 
         return 1;
     }
 
-    uint8_t* stage = host_stage(upload);
+    uint8_t* stage = host_stage(STAGE_IMAGES, upload);
     ImageDesc* desc = reinterpret_cast<ImageDesc*>(stage);
     size_t tap_at = desc_bytes;
     JpegCursor cur = {coeff_at, upload, upload + plane_bytes, 0, 0, 0, 0};
@@ -329,7 +330,8 @@ int bcnn_hip_jpeg_stage_begin(int n, int c, int h, int w, int num_images, const 
 
     Pending& q = g_pending;
     q.active = true;
-    q.stage = stage;
+    q.device = current_device();
+    q.generation = stage_generation(STAGE_IMAGES);
     q.c = c; q.h = h; q.w = w;
     q.upload = upload; q.total = total;
     q.planes_off = (uint32_t)planes_at; q.images_off = (uint32_t)images_at;
@@ -343,11 +345,10 @@ int bcnn_hip_jpeg_stage_run(float* dst_d, float norm_coeff, int swap_to_bgr, flo
     Pending& q = g_pending;
     if (!q.active || !dst_d) return 1;
     q.active = false;
+    if (current_device() != q.device || stage_generation(STAGE_IMAGES) != q.generation) return 1;  // the block is another call's
     // ---- one copy, three launches
-    uint8_t* stage_d = reinterpret_cast<uint8_t*>(scratch(SCRATCH_IMAGES, (q.total + 3) / 4));
     hipStream_t st = current_stream();
-    HIP_CHECK(hipMemcpyAsync(stage_d, q.stage, q.upload, hipMemcpyHostToDevice, st));
-    stage_copied(st);
+    uint8_t* stage_d = stage_upload(STAGE_IMAGES, SCRATCH_IMAGES, q.upload, q.total, st);
     launch_jpeg_pixels(stage_d, q.planes_off, q.images_off, q.cur, st);
     launch_fill_images(stage_d, dst_d, q.c, q.h, q.w, q.cur.images, norm_coeff, swap_to_bgr, mean_r, mean_g, mean_b, st);
     return 0;

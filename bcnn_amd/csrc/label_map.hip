@@ -8,7 +8,7 @@
 // first maximum on strict >, the class of a truth byte through softmax_loss_rule.h, the block layout); this file is
 // compiled with -ffp-contract=off like the rest of the library.
 //
-// One block per call, on the device (SCRATCH_LABEL_MAP) and pinned on the host, the same layout on both sides:
+// One block per call, on the device (SCRATCH_LABEL_MAP) and pinned on the host (STAGE_LABEL_MAP), the same layout on both sides:
 //   [descriptors, one per image][truth bytes][counts: C * C + 2 words][label bytes]
 // The host fills the first three parts (the counts with zeros) and copies that prefix in; the kernel writes the last two,
 // and that suffix is copied back (without truths there are no counts, without `labels` no label bytes). Label and truth
@@ -156,27 +156,11 @@ __global__ __launch_bounds__(kLmBlock, 4) void label_map_kernel(const float* __r
     }
 }
 
-// Pinned host side of the call's block: grow-only, one per host thread and device (the pattern of host_stage,
-// image_fill.hip). Every call ends in a stream synchronise, so no copy is in flight when the next one writes it.
-struct LabelMapStage { uint8_t* p = nullptr; size_t cap = 0; };
-thread_local LabelMapStage g_lm_stage[kMaxDevices];
-
-uint8_t* label_map_stage(size_t bytes) {
-    LabelMapStage& s = g_lm_stage[current_device()];
-    if (s.p == nullptr || s.cap < bytes) {
-        if (s.p) HIP_CHECK(hipHostFree(s.p));
-        s.cap = bytes + bytes / 4;
-        HIP_CHECK(hipHostMalloc((void**)&s.p, s.cap, hipHostMallocDefault));
-    }
-    return s.p;
-}
-
 // Optional timing of the kernel alone (bcnn_hip_label_maps_kernel_ms): the call is synchronous, so device events recorded
 // around it from outside span the two copies as well.
 struct LabelMapTimer { bool on = false; hipEvent_t a = nullptr, b = nullptr; float ms = -1.0f; };
 thread_local LabelMapTimer g_lm_timer;
 
-inline size_t align16(size_t v) { return (v + 15) & ~(size_t)15; }
 inline const bcnn_label_map_geom* geoms(const bcnn_hip_label_map_image* imgs) {
     return reinterpret_cast<const bcnn_label_map_geom*>(imgs);
 }
@@ -230,9 +214,10 @@ int bcnn_hip_label_maps_batch(const float* x_d, int n, int c, int h, int w, int 
     const size_t desc_bytes = (size_t)num_images * sizeof(LabelMapDesc);
     const size_t truth_at = desc_bytes, truth_bytes = truths ? (size_t)label_bytes : 0;
     const size_t count_at = truth_at + truth_bytes, count_words = truths ? (size_t)c * c + 2 : 0;
-    const size_t label_at = count_at + align16(count_words * sizeof(unsigned));
+    const size_t label_at = count_at + align_up(count_words * sizeof(unsigned), 16);
     const size_t total = label_at + (labels ? (size_t)label_bytes : 0);
-    uint8_t* stage = label_map_stage(total);
+    // the pinned side: every call ends in a stream synchronise, so this slot never has a copy in flight to wait for
+    uint8_t* stage = host_stage(STAGE_LABEL_MAP, total);
     LabelMapDesc* desc = reinterpret_cast<LabelMapDesc*>(stage);
     const bcnn_label_map_geom* g = geoms(imgs);
     unsigned long long wgs = 0, at = 0;
@@ -254,7 +239,7 @@ int bcnn_hip_label_maps_batch(const float* x_d, int n, int c, int h, int w, int 
             for (int y = 0; y < g[b].out_h; ++y) memcpy(dst + y * row, truths[b] + y * stride, (size_t)g[b].out_w);
         }
         wgs += (d.items + kLmBlock - 1) / kLmBlock;
-        at += align16((size_t)d.items * 4);
+        at += align_up((size_t)d.items * 4, 16);
     }
     if (truths) memset(stage + count_at, 0, count_words * sizeof(unsigned));
 
@@ -297,7 +282,7 @@ int bcnn_hip_label_maps_batch(const float* x_d, int n, int c, int h, int w, int 
             const size_t row = (size_t)desc[b].items_per_row * 4, stride = label_strides ? (size_t)label_strides[b] : (size_t)g[b].out_w;
             const uint8_t* src = stage + label_at + at;
             for (int y = 0; y < g[b].out_h; ++y) memcpy(labels[b] + y * stride, src + y * row, (size_t)g[b].out_w);
-            at += align16(row * g[b].out_h);
+            at += align_up(row * g[b].out_h, 16);
         }
     }
     if (truths) {

@@ -1,6 +1,7 @@
 // runtime.hip -- device, memory, stream and event entry points of the C-ABI (include/bcnn_hip.h).
 // Replaces the bcnn_cuda_* helper family (reference src/bcnn_utils.c:101-201). No process-global
-// library handles: the state is per host thread -- one current stream, and the table of library-private device scratch.
+// library handles: the state is per host thread -- one current stream, and the tables of library-private device scratch and
+// pinned host staging.
 #include "common.h"
 
 #include <cstring>
@@ -60,6 +61,53 @@ float* scratch(ScratchSlot slot, size_t floats) {
         HIP_CHECK(hipMalloc((void**)&b.p, b.cap * sizeof(float)));
     }
     return b.p;
+}
+
+// ---- library-private pinned host staging (common.h: StageSlot) ----------------------------------------------------------------
+// `copied` is recorded behind the latest copy out of the block; `generation` counts the calls that handed the block out.
+struct StageBlock { uint8_t* p = nullptr; size_t cap = 0; hipEvent_t copied = nullptr; bool in_flight = false; uint64_t generation = 0; };
+static thread_local StageBlock g_stage[kMaxDevices][STAGE_SLOTS];
+
+uint8_t* host_stage(StageSlot slot, size_t bytes) {
+    StageBlock& s = g_stage[current_device()][slot];
+    if (s.in_flight) {
+        HIP_CHECK(hipEventSynchronize(s.copied));
+        s.in_flight = false;
+    }
+    if (!s.copied) HIP_CHECK(hipEventCreateWithFlags(&s.copied, hipEventDisableTiming));
+    if (s.p == nullptr || s.cap < bytes) {
+        if (s.p) HIP_CHECK(hipHostFree(s.p));
+        s.cap = bytes + bytes / 4;
+        HIP_CHECK(hipHostMalloc((void**)&s.p, s.cap, hipHostMallocDefault));
+    }
+    ++s.generation;
+    return s.p;
+}
+
+uint8_t* host_stage_extend(StageSlot slot, size_t keep, size_t bytes) {
+    StageBlock& s = g_stage[current_device()][slot];
+    if (s.p != nullptr && s.cap >= bytes) return s.p;
+    uint8_t* grown = nullptr;
+    const size_t cap = bytes + bytes / 4;
+    HIP_CHECK(hipHostMalloc((void**)&grown, cap, hipHostMallocDefault));
+    if (s.p) {
+        memcpy(grown, s.p, keep);
+        HIP_CHECK(hipHostFree(s.p));
+    }
+    s.p = grown;
+    s.cap = cap;
+    return s.p;
+}
+
+uint64_t stage_generation(StageSlot slot) { return g_stage[current_device()][slot].generation; }
+
+uint8_t* stage_upload(StageSlot slot, ScratchSlot device_slot, size_t upload_bytes, size_t device_bytes, hipStream_t st) {
+    StageBlock& s = g_stage[current_device()][slot];
+    uint8_t* block_d = reinterpret_cast<uint8_t*>(scratch(device_slot, (device_bytes + 3) / 4));
+    HIP_CHECK(hipMemcpyAsync(block_d, s.p, upload_bytes, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipEventRecord(s.copied, st));
+    s.in_flight = true;
+    return block_d;
 }
 
 // ---- per-kernel-class event timing ---------------------------------------------------------------

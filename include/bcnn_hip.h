@@ -925,7 +925,8 @@ int bcnn_hip_fill_images(float *dst_d, int n, int c, int h, int w, int num_image
  *       fill_images_kernel. Planes and pixels stay in the library's scratch table. Returns 0, or 1 when no batch is
  *       pending or dst_d is NULL.
  *   bcnn_hip_jpeg_stage_cancel drops the pending batch (a stream failed to decode): nothing has been queued.
- * Between _begin and _run / _cancel the calling thread makes no other call that stages images.
+ * Between _begin and _run / _cancel the calling thread makes no other call that stages images. _run checks it: after such
+ * a call, or on another device than _begin's, it returns 1 as when no batch is pending (the batch is dropped).
  * ------------------------------------------------------------------------------------------- */
 typedef struct bcnn_hip_jpeg_component {
     int h, v;               /* sampling factors */
@@ -1037,7 +1038,8 @@ int bcnn_hip_augment_label_batch(float *label_d, int n, int h, int w, int num_sa
  *       nothing queued and the batch dropped: nothing pending; a NULL argument; decoded[b] set for a sample that got no
  *       coeff[b]; a record with SCALE and taps == NULL or a tap index out of range.
  *   bcnn_hip_augment_jpeg_cancel drops the pending batch: nothing has been queued.
- * Between _begin and _run / _cancel the calling thread makes no other call that stages a training batch.
+ * Between _begin and _run / _cancel the calling thread makes no other call that stages a training batch. _run checks it:
+ * after such a call, or on another device than _begin's, it returns 1 as when nothing is pending (the batch is dropped).
  * ------------------------------------------------------------------------------------------- */
 int bcnn_hip_augment_jpeg_begin(int n, int c, int h, int w, int num_samples, const bcnn_hip_jpeg_frame *frames,
                                 int16_t **coeff);
