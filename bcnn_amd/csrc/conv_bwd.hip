@@ -13,6 +13,8 @@
 //       keeps the `+=` onto the momentum carry). One extra all-ones im2col column yields the bias
 //       gradient for free when the padded K tile has room (saves a full re-read of dy).
 //   dX lives in conv_igemm.hip (it is the same gather-GEMM as the forward pass).
+// The two split-K finalizers the other weight-gradient families share live here too: conv_dw_tiles_finalize and
+// conv_dw_taps_reduce (declared in conv_common.h).
 #include "conv_paths.h"
 
 namespace bcnn_hip {
@@ -193,6 +195,50 @@ __global__ __launch_bounds__(256) void conv_dw_finalize_kernel(const float* __re
     }
 }
 
+// the one finalize of every family that writes [part][group][MP][NP] partial tiles (this file, conv_large.hip,
+// conv_direct.hip, conv_window.hip); callers name it in the dispatch trace themselves where they want it there
+void conv_dw_tiles_finalize(const float* partials, int nparts, int groups, int Mg, int K, int MP, int NP, int bias_col,
+                            float* dw, float* dbias, int outs) {
+    const long long total = (long long)groups * Mg * (K + bias_col);
+    if (outs == 4)
+        conv_dw_finalize_kernel<4><<<(unsigned)((total + 3) / 4), 256, 0, current_stream()>>>(partials, nparts, groups, Mg, K, MP,
+                                                                                              NP, bias_col, dw, dbias);
+    else
+        conv_dw_finalize_kernel<16><<<(unsigned)((total + 15) / 16), 256, 0, current_stream()>>>(partials, nparts, groups, Mg, K,
+                                                                                                 MP, NP, bias_col, dw, dbias);
+    KERNEL_CHECK();
+}
+
+// dw[(row, col)][tap] += alpha * (ws[0][tap][row][col] + ws[1][tap][row][col] + ...): the per-tap GEMMs of deconv.hip
+// (rows x cols = ci x co, alpha = 1/n) and conv_dilated.hip (f x cg, alpha = 1). A block takes 64 consecutive workspace
+// positions (coalesced reads) with 4 lanes each: lane q adds splits q, q + 4, q + 8, ... in order, and the four partial
+// sums are added in q order -- a fixed order, so the result is the same in every run.
+__global__ __launch_bounds__(256) void conv_dw_taps_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw,
+                                                                  int splits, int kk2, int rows_cols, float alpha) {
+    __shared__ float part[4][64];
+    const size_t total = (size_t)kk2 * rows_cols;
+    const int el = threadIdx.x & 63, q = threadIdx.x >> 6;
+    for (size_t base = (size_t)blockIdx.x * 64; base < total; base += (size_t)gridDim.x * 64) {
+        const size_t j = base + el;  // workspace position: tap * rows_cols + (row * cols + col)
+        float sum = 0.f;
+        if (j < total)
+            for (int sp = q; sp < splits; sp += 4) sum += ws[(size_t)sp * total + j];
+        part[q][el] = sum;
+        __syncthreads();
+        if (q == 0 && j < total) {
+            const size_t e = (j % rows_cols) * kk2 + j / rows_cols;
+            dw[e] = dw[e] + alpha * (((part[0][el] + part[1][el]) + part[2][el]) + part[3][el]);
+        }
+        __syncthreads();
+    }
+}
+
+void conv_dw_taps_reduce(const float* ws, float* dw, int splits, int kk2, int rows_cols, float alpha) {
+    conv_dw_taps_reduce_kernel<<<stream_grid((size_t)kk2 * rows_cols, 64), 256, 0, current_stream()>>>(ws, dw, splits, kk2,
+                                                                                                       rows_cols, alpha);
+    KERNEL_CHECK();
+}
+
 struct DwPlan {
     int TM, TN, mtiles, ntiles, qsplits, q_per_split, bias_col;
     size_t partial_floats;
@@ -206,15 +252,10 @@ static DwPlan plan_dw(const ConvShape& s, bool want_bias_col) {
     p.mtiles = ceil_div(s.Mg, BM);
     p.bias_col = (want_bias_col && (s.K % BN) != 0) ? 1 : 0;  // needs a free slot in the padded k tile
     p.ntiles = ceil_div(s.K, BN);
-    const long long tiles = (long long)p.mtiles * p.ntiles * s.groups;
-    long long want = (4LL * kCUs + tiles - 1) / tiles;       // ~4 workgroups per CU
-    const long long maxs = (s.total_q + 4 * DW_BQ - 1) / (4 * DW_BQ);  // >= 4 steps per workgroup
-    if (want > maxs) want = maxs;
-    if (want < 1) want = 1;
-    long long per = (s.total_q + want - 1) / want;
-    per = (per + DW_BQ - 1) / DW_BQ * DW_BQ;
-    p.q_per_split = (int)per;
-    p.qsplits = (int)((s.total_q + per - 1) / per);
+    // ~4 workgroups per CU, >= 4 steps per workgroup
+    const SplitK sk = split_k(s.total_q, (long long)p.mtiles * p.ntiles * s.groups, 4, DW_BQ, 4);
+    p.q_per_split = sk.chunk;
+    p.qsplits = sk.splits;
     p.partial_floats = (size_t)p.qsplits * 4 * s.groups * (size_t)(p.mtiles * BM) * (size_t)(p.ntiles * BN);
     return p;
 }
@@ -248,17 +289,10 @@ bool conv_backward_weights(const float* x, const float* dy, float* dw, float* db
     }
     KERNEL_CHECK();
     if (p.bias_col) trace_kernel("conv_dw_kernel:biascol");
-    const long long total = (long long)s.groups * s.Mg * (s.K + p.bias_col);
-    if (p.qsplits * 4 >= 256) {
-        trace_kernel("conv_dw_finalize:4");
-        conv_dw_finalize_kernel<4><<<(unsigned)((total + 3) / 4), 256, 0, current_stream()>>>(
-            workspace, p.qsplits * 4, s.groups, s.Mg, s.K, p.mtiles * p.TM * 32, p.ntiles * p.TN * 32, p.bias_col, dw, dbias);
-    } else {
-        trace_kernel("conv_dw_finalize:16");
-        conv_dw_finalize_kernel<16><<<(unsigned)((total + 15) / 16), 256, 0, current_stream()>>>(
-            workspace, p.qsplits * 4, s.groups, s.Mg, s.K, p.mtiles * p.TM * 32, p.ntiles * p.TN * 32, p.bias_col, dw, dbias);
-    }
-    KERNEL_CHECK();
+    const int outs = p.qsplits * 4 >= 256 ? 4 : 16;
+    trace_kernel(outs == 4 ? "conv_dw_finalize:4" : "conv_dw_finalize:16");
+    conv_dw_tiles_finalize(workspace, p.qsplits * 4, s.groups, s.Mg, s.K, p.mtiles * p.TM * 32, p.ntiles * p.TN * 32, p.bias_col,
+                           dw, dbias, outs);
     *bias_done = p.bias_col != 0;
     return true;
 }

@@ -39,6 +39,27 @@ inline void conv_require_workspace(const float* workspace, size_t given, size_t 
     fprintf(stderr, "[bcnn_hip] conv backward: workspace too small (%zu floats given, %zu needed)\n", given, need);
     exit(1);
 }
+// How a split-K weight gradient cuts its reduction of `total` into `splits` chunks of `chunk` (a multiple of the kernel's K
+// `step`): enough workgroups for `per_cu` per CU over `tiles` output tiles, at least `min_steps` steps per chunk, at most
+// `max_splits` chunks (0: unlimited). A function of its arguments only, so two runs split alike.
+struct SplitK {
+    int chunk, splits;
+};
+inline SplitK split_k(long long total, long long tiles, int per_cu, int step, int min_steps, size_t max_splits = 0) {
+    long long want = ((long long)per_cu * kCUs + tiles - 1) / tiles;
+    const long long by_len = (total + (long long)min_steps * step - 1) / ((long long)min_steps * step);
+    if (want > by_len) want = by_len;
+    if (max_splits > 0 && want > (long long)max_splits) want = (long long)max_splits;
+    if (want < 1) want = 1;
+    const long long chunk = ((total + want - 1) / want + step - 1) / step * step;
+    return {(int)chunk, (int)((total + chunk - 1) / chunk)};
+}
+// conv_bwd.hip. dw[g][f][k] += the sum over p of partials[p][g][f][k] (partial tiles of MP x NP), column K (bias_col) to
+// dbias[g * Mg + f]; `outs` outputs x 256 / outs interleaved sub-sums per workgroup (4 or 16), added in a fixed order
+void conv_dw_tiles_finalize(const float* partials, int nparts, int groups, int Mg, int K, int MP, int NP, int bias_col,
+                            float* dw, float* dbias, int outs);
+// conv_bwd.hip. dw[(row, col)][tap] += alpha * the sum over the splits of ws[split][tap][rows_cols], in a fixed order
+void conv_dw_taps_reduce(const float* ws, float* dw, int splits, int kk2, int rows_cols, float alpha);
 // ceil(2^32 / d), the multiplier of the kernels' multiply-high divisions by d (0 for d <= 1); every caller's d is >= 0
 inline unsigned magic_of(int d) { return d > 1 ? (unsigned)((0x100000000ULL + (unsigned)d - 1) / (unsigned)d) : 0u; }
 

@@ -240,29 +240,6 @@ __global__ __launch_bounds__(256) void dilated_kernel(const DlArgs a) {
     }
 }
 
-// dW[f][c][tap] += ws[0][tap][f][c] + ws[1][tap][f][c] + ... A block takes 64 consecutive workspace positions
-// (coalesced reads) with 4 lanes each: lane q adds splits q, q + 4, q + 8, ... in order, and the four partial sums are
-// added in q order -- a fixed order, so the result is the same in every run.
-__global__ __launch_bounds__(256) void dilated_dw_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw,
-                                                                int splits, int kk2, int fc) {
-    __shared__ float part[4][64];
-    const size_t total = (size_t)kk2 * fc;
-    const int el = threadIdx.x & 63, q = threadIdx.x >> 6;
-    for (size_t base = (size_t)blockIdx.x * 64; base < total; base += (size_t)gridDim.x * 64) {
-        const size_t j = base + el;  // workspace position: tap * fc + (f * cg + c)
-        float sum = 0.f;
-        if (j < total)
-            for (int sp = q; sp < splits; sp += 4) sum += ws[(size_t)sp * total + j];
-        part[q][el] = sum;
-        __syncthreads();
-        if (q == 0 && j < total) {
-            const size_t e = (j % fc) * kk2 + j / fc;
-            dw[e] = dw[e] + (((part[0][el] + part[1][el]) + part[2][el]) + part[3][el]);
-        }
-        __syncthreads();
-    }
-}
-
 template <int MODE>
 void launch(const DlArgs& a, int M, int NP, int gz) {
     const dim3 blk(256);
@@ -277,19 +254,10 @@ void launch(const DlArgs& a, int M, int NP, int gz) {
 
 // K-split of the weight gradient: enough blocks for two per CU, chunks of at least 4 K steps, at most `max_splits`
 // (0: unlimited). A function of the shape and the workspace size only, so two runs split alike.
-void dw_split(const DlArgs& a, size_t max_splits, int* kchunk, int* splits) {
-    const int ktot = a.n * a.oh * a.ow;
+SplitK dw_split(const DlArgs& a, size_t max_splits) {
     const long long blocks = (long long)a.k * a.k * a.g * ceil_div(a.mg, a.mg > 64 ? 128 : 64) *
                              ceil_div(a.cg, a.cg > 64 ? 128 : 64);
-    long long want = (2LL * kCUs + blocks - 1) / blocks;
-    const long long by_len = (ktot + 4 * kDlBK - 1) / (4 * kDlBK);
-    if (want > by_len) want = by_len;
-    if (max_splits > 0 && want > (long long)max_splits) want = (long long)max_splits;
-    if (want < 1) want = 1;
-    int chunk = ceil_div(ktot, want);
-    chunk = ceil_div(chunk, kDlBK) * kDlBK;
-    *kchunk = chunk;
-    *splits = ceil_div(ktot, chunk);
+    return split_k(a.n * a.oh * a.ow, blocks, 2, kDlBK, 4, max_splits);
 }
 
 DlArgs make_args(const char* what, int n, int c, int h, int w, int f, int k, int stride, int pad, int dilation,
@@ -334,9 +302,7 @@ extern "C" {
 size_t bcnn_hip_dilated_conv_workspace_size(int n, int c, int h, int w, int f, int k, int stride, int pad, int dilation,
                                             int groups) {
     const DlArgs a = make_args("bcnn_hip_dilated_conv_workspace_size", n, c, h, w, f, k, stride, pad, dilation, groups);
-    int kchunk, splits;
-    dw_split(a, 0, &kchunk, &splits);
-    return (size_t)splits * k * k * a.cg * f;
+    return (size_t)dw_split(a, 0).splits * k * k * a.cg * f;
 }
 
 void bcnn_hip_dilated_conv_forward(const float* x_d, const float* w_d, const float* bias_d, float* y_d, int n, int c,
@@ -367,13 +333,12 @@ void bcnn_hip_dilated_conv_backward(const float* x_d, const float* w_d, const fl
                     workspace_elems, per_split);
             exit(1);
         }
-        dw_split(a, max_splits, &a.kchunk, &a.splits);
+        const SplitK sk = dw_split(a, max_splits);
+        a.kchunk = sk.chunk; a.splits = sk.splits;
         a.out = workspace_d;
         trace_kernel("dilated_dw_kernel");
         launch<DL_DW>(a, a.mg, a.cg, groups * k * k * a.splits);
-        dilated_dw_reduce_kernel<<<stream_grid(per_split, 64), 256, 0, current_stream()>>>(workspace_d, dw_d, a.splits,
-                                                                                         k * k, f * a.cg);
-        KERNEL_CHECK();
+        conv_dw_taps_reduce(workspace_d, dw_d, a.splits, k * k, f * a.cg, 1.0f);
     }
     if (dx_d) {
         a.out = dx_d;

@@ -483,45 +483,6 @@ __global__ __launch_bounds__(256) void conv_dw_direct_kernel(const ConvDirectDwA
     }
 }
 
-// dW[g][f][k] += sum_p partials[p][g][f][k] (k < K), dbias[g*Mg + f] += column K. One workgroup per 16
-// output elements, 16 partial-lanes each, fixed summation order.
-__global__ __launch_bounds__(256) void conv_dw_direct_finalize_kernel(const float* __restrict__ partials,
-                                                                      int nparts, int groups, int Mg, int K,
-                                                                      int MP, int bias_col,
-                                                                      float* __restrict__ dw,
-                                                                      float* __restrict__ dbias) {
-    __shared__ float red[16][17];
-    const int kcols = K + (bias_col ? 1 : 0);
-    const int total = groups * Mg * kcols;
-    const int e = blockIdx.x * 16 + (threadIdx.x & 15), pl = threadIdx.x >> 4;
-    float sum = 0.f;
-    int g = 0, f = 0, k = 0;
-    if (e < total) {
-        k = e % kcols;
-        const int t = e / kcols;
-        f = t % Mg; g = t / Mg;
-        for (int p = pl; p < nparts; p += 16) sum += partials[(((size_t)p * groups + g) * MP + f) * 32 + k];
-    }
-    red[pl][threadIdx.x & 15] = sum;
-    __syncthreads();
-    if (pl == 0 && e < total) {
-        float tot = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) tot += red[i][threadIdx.x & 15];
-        if (k < K) dw[((size_t)g * Mg + f) * K + k] += tot;
-        else dbias[g * Mg + f] += tot;
-    }
-}
-
-// shared with conv_window.hip (same partial layout)
-void conv_dw_direct_finalize(const float* partials, int nparts, int groups, int Mg, int K, int MP, int bias_col, float* dw,
-                             float* dbias) {
-    const int total = groups * Mg * (K + bias_col);
-    conv_dw_direct_finalize_kernel<<<ceil_div(total, 16), 256, 0, current_stream()>>>(partials, nparts, groups, Mg, K, MP,
-                                                                                       bias_col, dw, dbias);
-    KERNEL_CHECK();
-}
-
 static bool dw_direct_ok(const ConvShape& s) {
     return !s.pointwise && s.K < 32 && s.Mg <= 64 && s.stride == 1 && (s.OW % 16) == 0 && s.total_q > 0 &&
            (long long)s.N * s.F * s.OHOW < (1LL << 32) && (long long)s.N * s.C * s.HW < (1LL << 32) &&
@@ -563,7 +524,7 @@ bool conv_backward_weights_direct(const float* x, const float* dy, float* dw, fl
     if (tm == 1) conv_dw_direct_kernel<1><<<grid, 256, 0, current_stream()>>>(a);
     else conv_dw_direct_kernel<2><<<grid, 256, 0, current_stream()>>>(a);
     KERNEL_CHECK();
-    conv_dw_direct_finalize(workspace, blocks, s.groups, s.Mg, s.K, tm * 32, a.bias_col, dw, dbias);
+    conv_dw_tiles_finalize(workspace, blocks, s.groups, s.Mg, s.K, tm * 32, 32, a.bias_col, dw, dbias, 16);
     *bias_done = dbias != nullptr;
     return true;
 }

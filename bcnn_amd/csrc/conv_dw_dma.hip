@@ -344,15 +344,10 @@ static DwDmaPlan plan_dw_dma(const ConvShape& s) {
     const int BM = kDwTiles[p.cfg].bm, BN = kDwTiles[p.cfg].bn;
     p.mtiles = ceil_div(s.Mg, BM); p.ntiles = ceil_div(s.Cg, BN);
     p.Mpad = p.mtiles * BM; p.Npad = p.ntiles * BN;
-    const long long tiles = (long long)p.mtiles * p.ntiles * p.kk2 * s.groups;
-    long long want = ((long long)want_per_cu * kCUs + tiles - 1) / tiles;  // workgroups per CU in total
-    const long long maxs = (s.total_q + 8 * DWQ - 1) / (8 * DWQ);      // >= 8 K-tiles per workgroup
-    if (want > maxs) want = maxs;
-    if (want < 1) want = 1;
-    long long per = (s.total_q + want - 1) / want;
-    per = (per + DWQ - 1) / DWQ * DWQ;
-    p.q_per_split = (int)per;
-    p.qsplits = (int)((s.total_q + per - 1) / per);
+    // want_per_cu workgroups per CU in total, >= 8 K-tiles per workgroup
+    const SplitK sk = split_k(s.total_q, (long long)p.mtiles * p.ntiles * p.kk2 * s.groups, want_per_cu, DWQ, 8);
+    p.q_per_split = sk.chunk;
+    p.qsplits = sk.splits;
     p.partial_floats = (size_t)p.qsplits * s.groups * p.kk2 * (size_t)p.Mpad * p.Npad;
     p.ok = true;
     return p;
@@ -426,15 +421,9 @@ static DwDmaPlan plan_dw_small_c(const ConvShape& s) {
     const int BM = kDwTiles[p.cfg].bm, BN = kDwTiles[p.cfg].bn;
     p.mtiles = ceil_div(s.Mg, BM); p.ntiles = ceil_div(s.K, BN);
     p.Mpad = p.mtiles * BM; p.Npad = p.ntiles * BN;
-    const long long tiles = (long long)p.mtiles * p.ntiles;
-    long long want = (8LL * kCUs + tiles - 1) / tiles;
-    const long long maxs = (s.total_q + 8 * DWQ - 1) / (8 * DWQ);
-    if (want > maxs) want = maxs;
-    if (want < 1) want = 1;
-    long long per = (s.total_q + want - 1) / want;
-    per = (per + DWQ - 1) / DWQ * DWQ;
-    p.q_per_split = (int)per;
-    p.qsplits = (int)((s.total_q + per - 1) / per);
+    const SplitK sk = split_k(s.total_q, (long long)p.mtiles * p.ntiles, 8, DWQ, 8);
+    p.q_per_split = sk.chunk;
+    p.qsplits = sk.splits;
     p.partial_floats = (size_t)p.qsplits * (size_t)p.Mpad * p.Npad;
     p.ok = true;
     return p;

@@ -496,35 +496,6 @@ __global__ __launch_bounds__(256) void conv_large_dw_kernel(const LargeDwArgs a)
             }
 }
 
-// dw[g][f][k] += sum_p partials[p][g][f][k]; column K (bias_col) goes to dbias[g*Mg + f]. 16 outputs x 16 interleaved
-// sub-sums per workgroup, combined in a fixed order: the same bits on every run.
-__global__ __launch_bounds__(256) void conv_large_dw_finalize_kernel(const float* __restrict__ partials, int nparts, int groups,
-                                                                     int Mg, int K, int MP, int NP, int bias_col,
-                                                                     float* __restrict__ dw, float* __restrict__ dbias) {
-    __shared__ float red[16][17];
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-    const int kcols = K + (bias_col ? 1 : 0);
-    const long long total = (long long)groups * Mg * kcols;
-    const long long i = (long long)blockIdx.x * 16 + tx;
-    int k = 0, f = 0, g = 0;
-    float sum = 0.f;
-    if (i < total) {
-        k = (int)(i % kcols);
-        const long long t = i / kcols;
-        f = (int)(t % Mg); g = (int)(t / Mg);
-        for (int p = ty; p < nparts; p += 16) sum += partials[(((size_t)p * groups + g) * MP + f) * NP + k];
-    }
-    red[ty][tx] = sum;
-    __syncthreads();
-    if (ty == 0 && i < total) {
-        float tot = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) tot += red[r][tx];
-        if (k < K) dw[((size_t)g * Mg + f) * K + k] += tot;
-        else dbias[g * Mg + f] += tot;
-    }
-}
-
 struct LargeDwPlan {
     int TM, mtiles, ntiles, qsplits, q_per_split, bias_col;
     size_t partial_floats;
@@ -543,15 +514,10 @@ static LargeDwPlan plan_large_dw(const ConvShape& s, bool want_bias_col) {
     p.mtiles = ceil_div(s.Mg, BM);
     p.ntiles = ceil_div(s.K, LDW_BN);
     p.bias_col = (want_bias_col && (s.K % LDW_BN) != 0) ? 1 : 0;  // needs a free slot in the padded column tile
-    const long long tiles = (long long)p.mtiles * p.ntiles * s.groups;
-    long long want = (4LL * kCUs + tiles - 1) / tiles;                       // ~4 workgroups per CU
-    const long long maxs = (s.total_q + 4 * LDW_BQ - 1) / (4 * LDW_BQ);      // >= 4 steps per workgroup
-    if (want > maxs) want = maxs;
-    if (want < 1) want = 1;
-    long long per = (s.total_q + want - 1) / want;
-    per = (per + LDW_BQ - 1) / LDW_BQ * LDW_BQ;
-    p.q_per_split = (int)per;
-    p.qsplits = (int)((s.total_q + per - 1) / per);
+    // ~4 workgroups per CU, >= 4 steps per workgroup
+    const SplitK sk = split_k(s.total_q, (long long)p.mtiles * p.ntiles * s.groups, 4, LDW_BQ, 4);
+    p.q_per_split = sk.chunk;
+    p.qsplits = sk.splits;
     p.partial_floats = (size_t)p.qsplits * 4 * s.groups * (size_t)(p.mtiles * BM) * (size_t)(p.ntiles * LDW_BN);
     return p;
 }
@@ -592,10 +558,8 @@ bool conv_backward_weights_large(const float* x, const float* dy, float* dw, flo
         else if (p.TM == 2) conv_large_dw_kernel<2><<<grid, 256, 0, current_stream()>>>(a);
         else conv_large_dw_kernel<3><<<grid, 256, 0, current_stream()>>>(a);
         KERNEL_CHECK();
-        const long long total = (long long)s.groups * s.Mg * (s.K + p.bias_col);
-        conv_large_dw_finalize_kernel<<<(unsigned)((total + 15) / 16), 256, 0, current_stream()>>>(
-            workspace, p.qsplits * 4, s.groups, s.Mg, s.K, p.mtiles * p.TM * 32, p.ntiles * LDW_BN, p.bias_col, dw, dbias);
-        KERNEL_CHECK();
+        conv_dw_tiles_finalize(workspace, p.qsplits * 4, s.groups, s.Mg, s.K, p.mtiles * p.TM * 32, p.ntiles * LDW_BN, p.bias_col,
+                               dw, dbias, 16);
     }
     *bias_done = bias_col != 0;
     return true;

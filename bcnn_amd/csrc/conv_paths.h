@@ -120,9 +120,6 @@ bool conv_backward_weights(const float* x, const float* dy, float* dw, float* db
 // fold: the layer ran on W diag(a) (BnFold): the weight gradient's columns take the same factors
 bool conv_backward_weights_dma(const float* x, const float* dy, float* dw, const ConvShape& s, float* workspace,
                                size_t workspace_floats, const BnFold* fold = nullptr);
-// conv_direct.hip: dw, dbias += the partials of its kernel and of conv_window.hip's (same layout)
-void conv_dw_direct_finalize(const float* partials, int nparts, int groups, int Mg, int K, int MP, int bias_col, float* dw,
-                             float* dbias);
 
 // conv_winograd43b.hip: the second form of the F(4x4, 3x3) kernel (whole-tile planes), run by conv_winograd43.hip
 void wino43b_run(const float* src, const float* w, float* dst, const ConvShape& s, int dx_mode, ConvStats* stats);

@@ -1016,33 +1016,6 @@ __global__ __launch_bounds__(512, 1) void conv_dw_stem_kernel(const ConvStemDwAr
             out[(fb * 16 + 4 * kq + rr) * kStemTapCols + (th * 5 + b) * 16 + l15] = acc[b][rr];
 }
 
-// dW[g][f][k] += sum_p partials[p][g][f][k] (k < K), dbias[g*Mg + f] += column K; fixed summation order
-__global__ __launch_bounds__(256) void conv_dw_stem_finalize_kernel(const float* __restrict__ partials, int nparts, int groups,
-                                                                   int Mg, int K, int bias_col, float* __restrict__ dw,
-                                                                   float* __restrict__ dbias) {
-    __shared__ float red[16][17];
-    const int kcols = K + (bias_col ? 1 : 0);
-    const int total = groups * Mg * kcols;
-    const int e = blockIdx.x * 16 + (threadIdx.x & 15), pl = threadIdx.x >> 4;
-    float sum = 0.f;
-    int g = 0, f = 0, k = 0;
-    if (e < total) {
-        k = e % kcols;
-        const int t = e / kcols;
-        f = t % Mg; g = t / Mg;
-        for (int p = pl; p < nparts; p += 16) sum += partials[(((size_t)p * groups + g) * 64 + f) * kStemTapCols + k];
-    }
-    red[pl][threadIdx.x & 15] = sum;
-    __syncthreads();
-    if (pl == 0 && e < total) {
-        float tot = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) tot += red[i][threadIdx.x & 15];
-        if (k < K) dw[((size_t)g * Mg + f) * K + k] += tot;
-        else dbias[g * Mg + f] += tot;
-    }
-}
-
 static bool dw_stem_ok(const ConvShape& s) {
     return stem_ok(s) && (s.OW % 4) == 0 && ((s.OW + 15) & ~15) <= 120 && 2 * (((s.OW + 15) & ~15) - 1) + 7 + (kWinOrg - s.pad) <= 232;
 }
@@ -1080,10 +1053,7 @@ bool conv_backward_weights_stem(const float* x, const float* dy, float* dw, floa
     else if (s.Cg == 2) conv_dw_stem_kernel<2, 120, 232><<<grid, 512, 0, current_stream()>>>(a);
     else conv_dw_stem_kernel<3, 120, 232><<<grid, 512, 0, current_stream()>>>(a);
     KERNEL_CHECK();
-    const int total = s.groups * s.Mg * (s.K + a.bias_col);
-    conv_dw_stem_finalize_kernel<<<ceil_div(total, 16), 256, 0, current_stream()>>>(workspace, blocks, s.groups, s.Mg, s.K,
-                                                                                    a.bias_col, dw, dbias);
-    KERNEL_CHECK();
+    conv_dw_tiles_finalize(workspace, blocks, s.groups, s.Mg, s.K, 64, kStemTapCols, a.bias_col, dw, dbias, 16);
     *bias_done = dbias != nullptr;
     return true;
 }
@@ -1145,7 +1115,7 @@ bool conv_backward_weights_window(const float* x, const float* dy, float* dw, fl
 #undef RLAUNCH1
 #undef RLAUNCH2
     KERNEL_CHECK();
-    conv_dw_direct_finalize(workspace, rblocks, s.groups, s.Mg, s.K, tm * 32, ra.bias_col, dw, dbias);
+    conv_dw_tiles_finalize(workspace, rblocks, s.groups, s.Mg, s.K, tm * 32, 32, ra.bias_col, dw, dbias, 16);
     *bias_done = dbias != nullptr;
     return true;
 }

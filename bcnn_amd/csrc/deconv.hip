@@ -266,29 +266,6 @@ __global__ __launch_bounds__(256) void deconv_kernel(const DcArgs a) {
     }
 }
 
-// dW[ci][co][tap] += alpha * (ws[0][tap][ci][co] + ws[1][tap][ci][co] + ...). A block takes 64 consecutive workspace
-// positions (coalesced reads) with 4 lanes each: lane q adds splits q, q + 4, q + 8, ... in order, and the four partial
-// sums are added in q order -- a fixed order, so the result is the same in every run.
-__global__ __launch_bounds__(256) void deconv_dw_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw,
-                                                               int splits, int kk2, int cico, float alpha) {
-    __shared__ float part[4][64];
-    const size_t total = (size_t)kk2 * cico;
-    const int el = threadIdx.x & 63, q = threadIdx.x >> 6;
-    for (size_t base = (size_t)blockIdx.x * 64; base < total; base += (size_t)gridDim.x * 64) {
-        const size_t j = base + el;  // workspace position: tap * cico + (ci * co + co)
-        float sum = 0.f;
-        if (j < total)
-            for (int sp = q; sp < splits; sp += 4) sum += ws[(size_t)sp * total + j];
-        part[q][el] = sum;
-        __syncthreads();
-        if (q == 0 && j < total) {
-            const size_t e = (j % cico) * kk2 + j / cico;
-            dw[e] = dw[e] + alpha * (((part[0][el] + part[1][el]) + part[2][el]) + part[3][el]);
-        }
-        __syncthreads();
-    }
-}
-
 template <int MODE>
 void launch(const DcArgs& a, int M, int NP, int gz) {
     const dim3 blk(256);
@@ -303,18 +280,9 @@ void launch(const DcArgs& a, int M, int NP, int gz) {
 
 // K-split of the weight gradient: enough blocks for two per CU, chunks of at least 4 K steps, at most `max_splits`
 // (0: unlimited). A function of the shape only, so two runs split alike.
-void dw_split(int n, int c, int h, int w, int f, int k, size_t max_splits, int* kchunk, int* splits) {
-    const int ktot = n * h * w;
+SplitK dw_split(int n, int c, int h, int w, int f, int k, size_t max_splits) {
     const long long blocks = (long long)k * k * ceil_div(c, c > 64 ? 128 : 64) * ceil_div(f, f > 64 ? 128 : 64);
-    long long want = (2LL * kCUs + blocks - 1) / blocks;
-    const long long by_len = (ktot + 4 * kDcBK - 1) / (4 * kDcBK);
-    if (want > by_len) want = by_len;
-    if (max_splits > 0 && want > (long long)max_splits) want = (long long)max_splits;
-    if (want < 1) want = 1;
-    int chunk = ceil_div(ktot, want);
-    chunk = ceil_div(chunk, kDcBK) * kDcBK;
-    *kchunk = chunk;
-    *splits = ceil_div(ktot, chunk);
+    return split_k(n * h * w, blocks, 2, kDcBK, 4, max_splits);
 }
 
 void check_shape(const char* what, int n, int c, int h, int w, int f, int k, int stride, int pad) {
@@ -346,9 +314,7 @@ extern "C" {
 
 size_t bcnn_hip_deconv_workspace_size(int n, int c, int h, int w, int f, int k, int stride, int pad) {
     (void)stride; (void)pad;
-    int kchunk, splits;
-    dw_split(n, c, h, w, f, k, 0, &kchunk, &splits);
-    return (size_t)splits * k * k * c * f;
+    return (size_t)dw_split(n, c, h, w, f, k, 0).splits * k * k * c * f;
 }
 
 void bcnn_hip_deconv_forward(const float* x_d, const float* w_d, const float* bias_d, float* y_d, int n, int c, int h,
@@ -384,13 +350,12 @@ void bcnn_hip_deconv_backward(const float* x_d, const float* w_d, const float* y
                     workspace_elems, per_split);
             exit(1);
         }
-        dw_split(n, c, h, w, f, k, max_splits, &a.kchunk, &a.splits);
+        const SplitK sk = dw_split(n, c, h, w, f, k, max_splits);
+        a.kchunk = sk.chunk; a.splits = sk.splits;
         a.out = workspace_d;
         trace_kernel("deconv_dw_kernel");
         launch<DC_DW>(a, c, f, k * k * a.splits);
-        deconv_dw_reduce_kernel<<<stream_grid(per_split, 64), 256, 0, current_stream()>>>(
-            workspace_d, dw_d, a.splits, k * k, c * f, 1.0f / (float)n);
-        KERNEL_CHECK();
+        conv_dw_taps_reduce(workspace_d, dw_d, a.splits, k * k, c * f, 1.0f / (float)n);
     }
     if (dx_d) {
         a.out = dx_d;

@@ -13,8 +13,10 @@ Reference: torch conv2d in float64 and its autograd on the same integers. Two co
 are not the subject of this file: a bias of exactly 1.0f is not added (bcnn_add_scalar of the reference's AVX build,
 bcnn_mat.c:381-383; every forward epilogue reproduces it) and the bias gradient is the plain sum of dy * act'(y).
 
-The expected names come from a port of the families' shape rules at kCUs = 256 (plan_dw_dma, plan_dw_small_c, plan_dw,
-dw_direct_plan, wino_dw_fused_plan, wino_dw_applicable); the trace assertion is the check."""
+The expected names come from a port of the families' shape rules at kCUs = 256 (plan_dw_dma, plan_dw_small_c and plan_dw,
+all three on split_k of conv_common.h, dw_direct_plan, wino_dw_fused_plan, wino_dw_applicable); the trace assertion is the
+check. The rows, stem, direct, large and register-staged rows all end in conv_dw_tiles_finalize (conv_bwd.hip), which writes
+no name of its own: only conv_backward_weights names its branch (conv_dw_finalize:4 / :16)."""
 import ctypes
 import functools
 

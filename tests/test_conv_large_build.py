@@ -1,5 +1,6 @@
 """What of the large-kernel convolution family (bcnn_amd/csrc/conv_large.hip) can be checked without a
-GPU: its three kernels compile for gfx950 without scratch memory (a spilled accumulator or staging register turns the
+GPU: its kernels, and the split-K finalize and per-tap reduce kernels of conv_bwd.hip (the family's weight gradient ends in
+the former), compile for gfx950 without scratch memory (a spilled accumulator or staging register turns the
 inner loop into scratch traffic that nothing but the code object shows), the family is wired into the three dispatch
 ladders ahead of the catch-all kernels. With a GPU: an INI graph with an 11x11 / s4 layer loads through bcnn_load_net (the
 loader allocates device tensors, so that one test carries the gpu marker)."""
@@ -65,20 +66,25 @@ dst=cost
 
 @pytest.fixture(scope="module")
 def metadata(tmp_path_factory):
-    """kernel name -> bytes of scratch per work-item, from the code object metadata of the compiled file"""
+    """kernel name -> bytes of scratch per work-item, from the code object metadata of the compiled files: the family's own,
+    and conv_bwd.hip, which holds the finalize kernel the family shares (and the per-tap reduce kernel next to it)"""
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not found")
-    out = tmp_path_factory.mktemp("isa") / "conv_large.s"
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-function",
-           "-Wno-inline-asm", "-S", "--cuda-device-only", "-o", str(out), "conv_large.hip"]
-    r = subprocess.run(cmd, cwd=SRC, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    found = re.findall(r"\.name:\s+(\S+)\s*\n\s*\.private_segment_fixed_size:\s+(\d+)", out.read_text())
-    return {name: int(size) for name, size in found}
+    found = {}
+    for source in ("conv_large.hip", "conv_bwd.hip"):
+        out = tmp_path_factory.mktemp("isa") / (source[:-4] + ".s")
+        cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-function",
+               "-Wno-inline-asm", "-S", "--cuda-device-only", "-o", str(out), source]
+        r = subprocess.run(cmd, cwd=SRC, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        for name, size in re.findall(r"\.name:\s+(\S+)\s*\n\s*\.private_segment_fixed_size:\s+(\d+)", out.read_text()):
+            assert name not in found, name
+            found[name] = int(size)
+    return found
 
 
 @pytest.mark.parametrize("kernel,instances", [("conv_large_gemm_kernel", 4), ("conv_large_dw_kernel", 3),
-                                              ("conv_large_dw_finalize_kernel", 1)])
+                                              ("conv_dw_finalize_kernel", 2), ("conv_dw_taps_reduce_kernel", 1)])
 def test_kernels_use_no_scratch(metadata, kernel, instances):
     mine = {k: v for k, v in metadata.items() if kernel in k}
     assert len(mine) == instances, (kernel, sorted(metadata))

@@ -83,8 +83,9 @@ def _close(tag, got, want, tol=OP_TOL):
 
 
 # ---- the kernels ------------------------------------------------------------------------------------------------------
-def _run_op(n, c, h, w, f, k, s, p, act, seed, with_dx=True):
-    """one forward + backward on the device; returns the inputs and every result (float64 numpy)"""
+def _run_op(n, c, h, w, f, k, s, p, act, seed, with_dx=True, ws_elems=None):
+    """one forward + backward on the device; returns the inputs and every result (float64 numpy). ws_elems: floats of
+    workspace handed to the backward pass (default: what bcnn_hip_deconv_workspace_size asks for)"""
     from bcnn_amd import ops
     rs = np.random.RandomState(seed)
     ho, wo = ops.deconv_out_hw(h, w, k, s, p)
@@ -98,7 +99,8 @@ def _run_op(n, c, h, w, f, k, s, p, act, seed, with_dx=True):
     tx, tw, tb, tdy, tdw, tdb = map(dev, (x, wt, b, dy, dw0, db0))
     ty = torch.full((n, f, ho, wo), float("nan"), device="cuda")
     tdx = torch.full(x.shape, float("nan"), device="cuda") if with_dx else None
-    ws = torch.zeros(ops.deconv_workspace_size(n, c, h, w, f, k, s, p), device="cuda")
+    full = ops.deconv_workspace_size(n, c, h, w, f, k, s, p)
+    ws = torch.zeros(full if ws_elems is None else ws_elems, device="cuda")
     ops.deconv_forward(tx, tw, tb, ty, k, s, p, act)
     y = ty.cpu().numpy().astype(np.float64)
     ops.deconv_backward(tx, tw, ty, tdy, tdx, tdw, tdb, k, s, p, act, ws)
@@ -162,6 +164,24 @@ def test_weight_gradient_is_bit_identical_across_runs():
     runs = [_run_op(*shape, act=ACTS["relu"], seed=3)[1] for _ in range(2)]
     for key in ("y", "g", "dw", "db", "dx"):
         assert np.array_equal(runs[0][key], runs[1][key]), key
+
+
+def test_weight_gradient_takes_a_one_split_workspace():
+    """K = 2 * 9 * 11 = 198 pixels per tap: the full workspace splits it four ways (chunks of 64, the last one 6 long); a
+    workspace of one split clamps the plan to a single chunk of 208, and the result is the same sum"""
+    from bcnn_amd import ops
+    n, c, h, w, f, k, s, p = shape = (2, 70, 9, 11, 130, 3, 2, 1)
+    act = ACTS["relu"]
+    per_split = k * k * c * f
+    assert ops.deconv_workspace_size(*shape) == 4 * per_split
+    inp, got = _run_op(*shape, act=act, seed=21, ws_elems=per_split)
+    _close("y", got["y"], np_forward(inp["x"], inp["wt"], inp["b"], k, s, p, act))
+    g_ref = inp["dy"] * _act_grad(got["y"], act)
+    _close("dy * act'(y)", got["g"], g_ref)
+    dw_ref, dx_ref = np_backward(inp["x"], inp["wt"], g_ref, k, s, p)
+    _close("dw", got["dw"], inp["dw0"] + dw_ref / n)
+    _close("db", got["db"], inp["db0"] + g_ref.sum(axis=(0, 2, 3)))
+    _close("dx", got["dx"], dx_ref)
 
 
 def test_backward_without_data_gradient():
