@@ -65,6 +65,9 @@ SIGNATURES = {
     "bcnn_hip_group_norm_forward": (None, [vp] * 6 + [i, i, i, i, f]),
     "bcnn_hip_group_norm_backward": (None, [vp] * 8 + [i, i, i, i, i]),
     "bcnn_hip_group_norm_path": (i, [i, i, i, i, i]),
+    "bcnn_hip_attention_forward": (None, [vp] * 5 + [i] * 6 + [f]),
+    "bcnn_hip_attention_backward": (None, [vp] * 9 + [i] * 6 + [f, i, i, i]),
+    "bcnn_hip_attention_lse_size": (sz, [i, i, i]),
     "bcnn_hip_batchnorm_forward": (None, [vp] * 10 + [i, i, i, i, i]),
     "bcnn_hip_batchnorm_backward": (None, [vp, vp, vp, i] + [vp] * 9 + [i, i, i]),
     "bcnn_hip_conv_workspace_size": (sz, [i] * 9),

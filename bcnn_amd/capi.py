@@ -27,6 +27,7 @@ LAYER_ACTIVATION, LAYER_POOL2D, LAYER_SCALE_CHANNELS, LAYER_GROUPNORM = 3, 17, 1
 LAYER_CONV2D, LAYER_BATCHNORM, LAYER_DILATED_CONV2D, LAYER_INTERP = 0, 9, 20, 21
 LAYER_SOFTMAX_LOSS = 22
 LAYER_DEPTHWISE_CONV2D, LAYER_DILATED_DEPTHWISE_CONV2D = 2, 23
+LAYER_ATTENTION = 24
 LOSS_NORM_NONE, LOSS_NORM_VALID, LOSS_NORM_VALID_PER_IMAGE = 0, 1, 2
 LOSS_NORMS = {"none": LOSS_NORM_NONE, "valid": LOSS_NORM_VALID, "valid_per_image": LOSS_NORM_VALID_PER_IMAGE}
 
@@ -154,6 +155,7 @@ def lib():
         "bcnn_add_pool2d_layer": (i, [vp, i, i, i, i, i, i, cp, cp]),
         "bcnn_add_scale_channels_layer": (i, [vp, cp, cp, cp]),
         "bcnn_add_groupnorm_layer": (i, [vp, i, f, cp, cp]),
+        "bcnn_add_attention_layer": (i, [vp, i, f, cp, cp, cp, cp]),
         "bcnn_add_eltwise_layer": (i, [vp, i, cp, cp, cp]), "bcnn_add_fullc_layer": (i, [vp, i, i, i, i, cp, cp]),
         "bcnn_add_softmax_layer": (i, [vp, cp, cp]), "bcnn_add_cost_layer": (i, [vp, i, i, f, cp, cp, cp]),
         "bcnn_upload_tensor": (i, [vp, i, i]), "bcnn_download_tensor": (i, [vp, i, i]),
@@ -279,6 +281,12 @@ class Net:
         """bcnn_add_groupnorm_layer: group normalisation over `groups` groups of channels (1: layer norm over (C,H,W),
         C: instance norm with affine); eps <= 0 selects 1e-5"""
         return self._added(self.L.bcnn_add_groupnorm_layer(self.net, groups, eps, src.encode(), dst.encode()))
+
+    def add_attention(self, heads, q, k, v, dst, scale=0.0):
+        """bcnn_add_attention_layer: dst = V softmax(scale Q^T K)^T per image and head over the positions of tensors q, k, v
+        (which may be one tensor); scale 0 selects 1 / sqrt(channels of a head of q)"""
+        return self._added(self.L.bcnn_add_attention_layer(self.net, heads, scale, q.encode(), k.encode(), v.encode(),
+                                                           dst.encode()))
 
     def activation(self, act, src):
         return self._added(self.L.bcnn_add_activation_layer(self.net, act, src.encode()))

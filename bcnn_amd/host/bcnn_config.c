@@ -203,6 +203,8 @@ typedef struct {
      * wrote that is none of the three names; default valid_per_image) and scale= read as a float (default 1) */
     int ignore_label, loss_norm;
     float loss_scale;
+    int heads; /* [attention] / [self_attention]; its scale= is loss_scale's float, read only when the section wrote it */
+    int has_scale;
 } layer_param;
 
 static void lp_reset(layer_param *lp) {
@@ -281,7 +283,8 @@ static void lp_set(bcnn_net *net, int section_idx, layer_param *lp, const char *
     } else if (!strcmp(name, "num_groups") || !strcmp(name, "groups")) { lp->num_groups = atoi(val); lp->has_groups = 1; }
     else if (!strcmp(name, "eps")) lp->eps = (float)atof(val);
     else if (!strcmp(name, "dilation")) lp->dilation = atoi(val);
-    else if (!strcmp(name, "scale")) { lp->scale = atoi(val); lp->loss_scale = (float)atof(val); }
+    else if (!strcmp(name, "scale")) { lp->scale = atoi(val); lp->loss_scale = (float)atof(val); lp->has_scale = 1; }
+    else if (!strcmp(name, "heads") || !strcmp(name, "num_heads")) lp->heads = atoi(val);
     else if (!strcmp(name, "ignore_label")) lp->ignore_label = atoi(val);
     else if (!strcmp(name, "normalize")) {
         if (!strcmp(val, "none")) lp->loss_norm = (int)BCNN_LOSS_NORM_NONE;
@@ -495,6 +498,16 @@ static bcnn_status add_layer(bcnn_net *net, const char *name, layer_param *lp) {
             BCNN_CHECK_AND_LOG(net->log_ctx, lp->has_groups, BCNN_INVALID_PARAMETER,
                                "Group-norm layer %s: the section needs a groups= key\n", dst);
         return bcnn_add_groupnorm_layer(net, groups, lp->eps, src, dst);
+    }
+    if (is_any(name, "[attention]", "[self_attention]", NULL, NULL)) {
+        /* src=q,k,v; a single src=x is self-attention off one tensor. Without scale= the builder's default, 1 / sqrt(d) */
+        BCNN_CHECK_AND_LOG(net->log_ctx, lp->a == BCNN_ACT_NONE, BCNN_INVALID_PARAMETER,
+                           "Attention layer %s: only activation=linear is supported; add an [activation] section\n", dst);
+        BCNN_CHECK_AND_LOG(net->log_ctx, lp->num_srcs == 1 || lp->num_srcs == 3, BCNN_INVALID_PARAMETER,
+                           "Attention layer %s: src= names q,k,v or one tensor for all three\n", dst);
+        const int three = lp->num_srcs == 3;
+        return bcnn_add_attention_layer(net, lp->heads, lp->has_scale ? lp->loss_scale : 0.0f, src,
+                                        lp->src_id[three ? 1 : 0], lp->src_id[three ? 2 : 0], dst);
     }
     if (!strcmp(name, "[yolo]")) {
         /* the builder copies 2 * num values (the reference reads past a shorter list); pad a short one with zeros */

@@ -396,6 +396,12 @@ static void mark_dead_grad_fills(bcnn_net *net) {
                           ((const bcnn_cost_param *)net->nodes[i].param)->loss == BCNN_LOSS_LIFTED_STRUCT;
         if (lifted_src) continue;
         const bcnn_node *nd = &net->nodes[first];
+        if (uses == 1 && nd->type == BCNN_LAYER_ATTENTION) {
+            /* the attention node writes every element of dq, dk and dv once, whichever of its three slots t is in; a tensor
+             * in two slots counts two uses and keeps its fill: the node's launches then add up in it */
+            hc->grad_fill_dead[t] = 2;
+            continue;
+        }
         if (nd->src[0] != t) continue;
         /* A gradient with exactly ONE writer that touches every element once per backward pass (max-pooling's
          * gather; the full-size operand of a same-shape eltwise add) needs no fill either if that writer assigns
@@ -542,6 +548,12 @@ static bcnn_status node_reserve_buffers(const bcnn_node *nd, const bcnn_tensor *
         elems = 2 * (size_t)d->n * (size_t)((const bcnn_groupnorm_param *)nd->param)->num_groups;
         return RESERVE(bcnn_groupnorm_param, stats_gpu, stats_capacity);
     }
+    if (nd->type == BCNN_LAYER_ATTENTION) { /* the log-sum-exp of d's n * heads * h * w queries */
+        elems = bcnn_hip_attention_lse_size(d->n, ((const bcnn_attention_param *)nd->param)->num_heads, d->h * d->w);
+        BCNN_CHECK_STATUS(RESERVE(bcnn_attention_param, lse_gpu, lse_capacity));
+        elems = (size_t)bcnn_tensor_size(d); /* the copy of the output kept for the backward, where one exists */
+        return RESERVE(bcnn_attention_param, out_gpu, out_capacity);
+    }
     switch (nd->type) {
         case BCNN_LAYER_CONV2D: return RESERVE(bcnn_conv_param, bn_workspace_gpu, bn_workspace_capacity);
         case BCNN_LAYER_BATCHNORM: return RESERVE(bcnn_batchnorm_param, workspace_gpu, workspace_capacity);
@@ -577,6 +589,8 @@ static int node_dst_shape(const bcnn_node *nd, const bcnn_tensor *s, bcnn_tensor
         if (!bcnn_pool2d_out_extents((const bcnn_pool2d_param *)nd->param, s->h, s->w, &oh, &ow)) return 0;
     } else if (nd->type == BCNN_LAYER_INTERP) { /* scale and zoom follow the source, the fixed form keeps its extents */
         if (!bcnn_interp_out_extents((const bcnn_interp_param *)nd->param, s->h, s->w, &oh, &ow)) return 0;
+    } else if (nd->type == BCNN_LAYER_ATTENTION) { /* the queries' extent (s is q), the values' depth */
+        oc = ((const bcnn_attention_param *)nd->param)->out_channels;
     }
     bcnn_tensor_set_shape(d, s->n, oc, oh, ow, 1);
     return 1;
@@ -614,6 +628,12 @@ static bcnn_status resize_plan(bcnn_net *net, int w, int h, int c, int need_real
                            BCNN_INVALID_PARAMETER,
                            "bcnn_resize_net: node %d keeps a buffer for the backward pass that is smaller than the new shape; "
                            "call with need_realloc\n", i);
+        BCNN_CHECK_AND_LOG(net->log_ctx,
+                           nd->type != BCNN_LAYER_ATTENTION ||
+                               (nd->num_src == 3 && bcnn_attention_fits(s, &plan[nd->src[1]], &plan[nd->src[2]])),
+                           BCNN_INVALID_PARAMETER,
+                           "bcnn_resize_net: the k and v of attention node %d would differ in their number of positions, or a "
+                           "tensor reach 2^31 elements\n", i);
         /* the class-index label map of a softmax-loss node follows as [n][1][h][w] */
         BCNN_CHECK_AND_LOG(net->log_ctx,
                            nd->type != BCNN_LAYER_SOFTMAX_LOSS || need_realloc ||
@@ -1176,6 +1196,8 @@ void *bcnn_get_node_state(bcnn_net *net, int node, int which) {
     if (nd->type == BCNN_LAYER_POOL2D) return which == 0 ? (void *)((bcnn_pool2d_param *)nd->param)->indexes_gpu : NULL;
     if (nd->type == BCNN_LAYER_GROUPNORM) /* mean [N * G] then rstd [N * G] of the last forward; NULL in a PREDICT-built net */
         return which == 0 ? (void *)((bcnn_groupnorm_param *)nd->param)->stats_gpu : NULL;
+    if (nd->type == BCNN_LAYER_ATTENTION) /* the log-sum-exp [N][heads][Lq] of the last forward; NULL in a PREDICT-built net */
+        return which == 0 ? (void *)((bcnn_attention_param *)nd->param)->lse_gpu : NULL;
     if (nd->type == BCNN_LAYER_ACTIVATION) /* hard-swish / swish / mish: the input the last TRAIN forward kept */
         return which == 0 ? (void *)((bcnn_activation_param *)nd->param)->x_saved_gpu : NULL;
     if (nd->type == BCNN_LAYER_CONV2D && ((bcnn_conv_param *)nd->param)->batch_norm) {

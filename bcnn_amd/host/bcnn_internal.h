@@ -442,6 +442,21 @@ typedef struct bcnn_groupnorm_param {
 #endif
 } bcnn_groupnorm_param;
 
+/* multi-head attention (bcnn_add_attention_layer; no reference counterpart): src[0] = q, src[1] = k, src[2] = v */
+#define BCNN_ATTENTION_MAX_HEAD_DIM 128 /* channels of one head of q / k and of v (attention.hip) */
+typedef struct bcnn_attention_param {
+    int num_heads;
+    float scale;       /* 0: 1 / sqrt(channels of a head of q) */
+    int out_channels;  /* v's depth, dst's too: what a resize gives dst besides q's extent */
+#ifdef BCNN_USE_HIP
+    float *lse_gpu;       /* nets built in TRAIN / VALID mode: the log-sum-exp [N][heads][Lq] of the last forward */
+    size_t lse_capacity;  /* floats allocated (bcnn_reserve_device) */
+    float *out_gpu;       /* the last forward's output, kept only while another node rewrites dst in place */
+    size_t out_capacity;
+    int out_kept;         /* the last forward filled out_gpu: the backward reads it instead of dst */
+#endif
+} bcnn_attention_param;
+
 typedef struct bcnn_eltwise_param {
     bcnn_activation activation;
     int stride[2];
@@ -653,6 +668,11 @@ void bcnn_forward_groupnorm_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_groupnorm_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_update_groupnorm_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_groupnorm_layer(bcnn_node *node);
+void bcnn_forward_attention_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_backward_attention_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_release_param_attention_layer(bcnn_node *node);
+/* bcnn_layers_attention.c: k and v have the same number of positions, and q, k, v and the output stay below 2^31 elements */
+int bcnn_attention_fits(const bcnn_tensor *q, const bcnn_tensor *k, const bcnn_tensor *v);
 void bcnn_release_param_activation_layer(bcnn_node *node);
 void bcnn_forward_pool2d_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_pool2d_layer(bcnn_net *net, bcnn_node *node);

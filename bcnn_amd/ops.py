@@ -580,6 +580,32 @@ def group_norm_backward(x, gamma, mean, rstd, dy, dx, dgamma, dbeta, groups, ove
                                              _f32(dbeta), n, c, h * w, groups, 1 if overwrite else 0)
 
 
+def _attention_dims(q, k, v, heads):
+    n, cqk, lq = q.shape[0], q.shape[1], q.shape[2] * q.shape[3]
+    cv, lk = v.shape[1], k.shape[2] * k.shape[3]
+    assert k.shape[0] == n and v.shape[0] == n and k.shape[1] == cqk and v.shape[2] * v.shape[3] == lk
+    assert heads > 0 and cqk % heads == 0 and cv % heads == 0
+    return n, cqk // heads, cv // heads, lq, lk
+
+
+def attention_forward(q, k, v, o, lse, heads, scale=0.0):
+    """bcnn_hip_attention_forward: o = V softmax(scale Q^T K)^T per image and head over the positions of NCHW q, k, v
+    (scale 0: 1 / sqrt(d)); lse ([N * heads * Lq]) receives the log-sum-exp of every query, or is None"""
+    n, d, c, lq, lk = _attention_dims(q, k, v, heads)
+    assert o.numel() == n * heads * c * lq and (lse is None or lse.numel() == n * heads * lq)
+    _lib.load().bcnn_hip_attention_forward(_f32(q), _f32(k), _f32(v), _f32(o), _f32(lse), n, heads, d, c, lq, lk, scale)
+
+
+def attention_backward(q, k, v, o, lse, do, dq, dk, dv, heads, scale=0.0, overwrite=(False, False, False)):
+    """bcnn_hip_attention_backward from the stored o and lse: each of dq, dk, dv is assigned (its overwrite flag) or added
+    to, or is None (skipped)"""
+    n, d, c, lq, lk = _attention_dims(q, k, v, heads)
+    assert do.numel() == o.numel() == n * heads * c * lq and lse.numel() == n * heads * lq
+    assert all(g is None or g.numel() == x.numel() for g, x in ((dq, q), (dk, k), (dv, v)))
+    _lib.load().bcnn_hip_attention_backward(_f32(q), _f32(k), _f32(v), _f32(o), _f32(lse), _f32(do), _f32(dq), _f32(dk),
+                                            _f32(dv), n, heads, d, c, lq, lk, scale, *[1 if w else 0 for w in overwrite])
+
+
 def activation_backward(x, dx, act, slopes=None, dslopes=None, spatial=1, channels=1):
     """bcnn_backward_activation_cpu (bcnn_activation_layer.c:165-226), dx in place"""
     _lib.load().bcnn_hip_activation_backward(_f32(x), _f32(dx), x.numel(), act, _f32(slopes), _f32(dslopes),

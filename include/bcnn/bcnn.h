@@ -76,6 +76,8 @@ typedef enum {
 #define BCNN_LAYER_SOFTMAX_LOSS ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 5))
 /* The layer type of bcnn_add_dilated_depthwise_conv_layer with dilation > 1, likewise a constant behind the enumerator list. */
 #define BCNN_LAYER_DILATED_DEPTHWISE_CONV2D ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 6))
+/* The layer type of bcnn_add_attention_layer, likewise a constant behind the enumerator list. */
+#define BCNN_LAYER_ATTENTION ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 7))
 
 typedef enum {
     BCNN_ACT_NONE, BCNN_ACT_TANH, BCNN_ACT_RELU, BCNN_ACT_RAMP, BCNN_ACT_SOFTPLUS,
@@ -324,6 +326,24 @@ BCNN_API bcnn_status bcnn_add_scale_channels_layer(bcnn_net *net, const char *sr
  * num_groups that does not divide C. May be the first node of a net. Follows bcnn_resize_net (dst is reshaped like src). */
 BCNN_API bcnn_status bcnn_add_groupnorm_layer(bcnn_net *net, int num_groups, float eps, const char *src_id,
                                               const char *dst_id);
+/* New, without a reference counterpart: multi-head attention over the positions of feature maps, fp32. With q [N,Cqk,Hq,Wq],
+ * k [N,Cqk,Hk,Wk], v [N,Cv,Hk,Wk], d = Cqk / num_heads and c = Cv / num_heads, head h of an image owns channels
+ * [h d, (h + 1) d) of q and k and [h c, (h + 1) c) of v and dst [N,Cv,Hq,Wq]:
+ *   S[i][j] = scale * sum_t q[t][i] k[t][j],  P[i][.] = softmax_j S[i][.],  dst[r][i] = sum_j v[r][j] P[i][j]
+ * over the Hq * Wq queries i and the Hk * Wk keys j. scale == 0 selects 1 / sqrt(d). q, k and v may be one tensor (self-attention
+ * straight off a feature map) or alias in pairs; the extents of q and k may differ, and so may d and c. No mask, no position
+ * bias, no dropout, no projections (those are the 1x1 convolution nodes in front and behind). The same function in TRAIN,
+ * VALID and PREDICT mode.
+ *   A net built in TRAIN or VALID mode keeps the log-sum-exp of every (image, head, query) of the last forward, N * num_heads *
+ *   Hq * Wq floats: bcnn_get_node_state(net, node, 0). The backward recomputes P from it. It adds into the three source
+ *   gradients (assigns one whose sole writer it is); a source without a gradient buffer is skipped.
+ * Refused with BCNN_INVALID_PARAMETER and a log line, nothing added to the net: an unknown q, k or v name, different batch
+ * sizes, q and k of different depth, k and v of a different number of positions, num_heads <= 0, num_heads that does not
+ * divide both depths, d or c above 128, a tensor of 2^31 elements or more. Follows bcnn_resize_net (dst takes q's extent and
+ * v's depth; a resize after which k and v differ in their number of positions is refused). An in-place node on dst
+ * (activation, dropout) is allowed: the node then keeps its own copy of the output for the backward. */
+BCNN_API bcnn_status bcnn_add_attention_layer(bcnn_net *net, int num_heads, float scale, const char *q_id, const char *k_id,
+                                              const char *v_id, const char *dst_id);
 BCNN_API bcnn_status bcnn_add_concat_layer(bcnn_net *net, int num_src, char *const *src_ids, const char *dst_id);
 BCNN_API bcnn_status bcnn_add_eltwise_layer(bcnn_net *net, bcnn_activation activation, const char *src_id1,
                                             const char *src_id2, const char *dst_id);

@@ -585,6 +585,31 @@ void bcnn_hip_group_norm_backward(const float *x_d, const float *gamma_d, const 
 int bcnn_hip_group_norm_path(int n, int c, int hw, int groups, int backward);
 
 /* ---------------------------------------------------------------------------------------------
+ * Multi-head attention over the positions of a feature map (the attention node; attention.hip). No reference counterpart.
+ *   q is [n][heads * d][lq], k [n][heads * d][lk], v [n][heads * c][lk], o [n][heads * c][lq]; head h of image n owns
+ *   channels [h * d, (h + 1) * d) of q and k and [h * c, (h + 1) * c) of v and o. Per image and head
+ *     S[i][j] = scale * sum_t q[t][i] k[t][j],  P[i][.] = softmax_j S[i][.],  o[r][i] = sum_j v[r][j] P[i][j];
+ *   scale == 0 means 1 / sqrt(d). Flash style on the fp32 matrix cores: S and P never reach memory.
+ *   forward : lse_d, [n][heads][lq], receives log sum_j exp S[i][j] (what the backward recomputes P from); NULL: nothing
+ *     is stored, o has the same bits.
+ *   backward: dP = dO^T v, dS = P (dP - sum_r dO[r][i] o[r][i]); dv = dO P, dq = scale k dS^T, dk = scale q dS. Each of
+ *     dq_d, dk_d, dv_d may be NULL (skipped, the others' bits unchanged) and has its own flag: overwrite != 0 assigns,
+ *     0 adds to what is there (the bits of start + the overwrite result). q_d, k_d, v_d may alias, and so may the three
+ *     gradients when all of them add: the launches that write them follow each other on the stream.
+ *   No atomics, every sum in a fixed order: two runs give the same bits; a pointer that is not 16-byte aligned or a row
+ *   length that is no multiple of 4 changes the loads, not the bits.
+ *   d and c outside 1 .. 128, a negative extent and a tensor of 2^31 elements or more exit. With the dispatch trace on the
+ *   launches are named attention_fwd, attention_bwd:dl, attention_bwd:kv, attention_bwd:q.
+ *   bcnn_hip_attention_lse_size: the floats behind lse_d.
+ * ------------------------------------------------------------------------------------------- */
+void bcnn_hip_attention_forward(const float *q_d, const float *k_d, const float *v_d, float *o_d, float *lse_d, int n,
+                                int heads, int d, int c, int lq, int lk, float scale);
+void bcnn_hip_attention_backward(const float *q_d, const float *k_d, const float *v_d, const float *o_d, const float *lse_d,
+                                 const float *do_d, float *dq_d, float *dk_d, float *dv_d, int n, int heads, int d, int c,
+                                 int lq, int lk, float scale, int overwrite_q, int overwrite_k, int overwrite_v);
+size_t bcnn_hip_attention_lse_size(int n, int heads, int lq);
+
+/* ---------------------------------------------------------------------------------------------
  * Depthwise convolution.  Replaces the kernels of bcnn_depthwise_conv_layer.cu:33-200; CPU semantics
  * bcnn_depthwise_conv_layer.c:165-293, 295-547: weights [c][k][k]; y = act(dwconv + bias);
  * backward: dy *= act'(y) in place, dbias += ..., and ONLY IF dx_d != NULL: dw += ..., dx += ...
