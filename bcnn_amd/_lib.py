@@ -13,6 +13,16 @@ CSRC = os.path.join(_HERE, "csrc")
 
 vp, i, f, sz, u64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_uint64
 
+
+class ChannelNormFwdArgs(C.Structure):  # bcnn_hip_channel_norm_fwd_args
+    _fields_ = [(k, vp) for k in ("x", "scales", "b", "y", "mean", "rstd")] + [("n", i), ("c", i), ("hw", i), ("eps", f)]
+
+
+class ChannelNormBwdArgs(C.Structure):  # bcnn_hip_channel_norm_bwd_args
+    _fields_ = [(k, vp) for k in ("x", "scales", "mean", "rstd", "dy", "dx", "dscales", "db")] + \
+               [("n", i), ("c", i), ("hw", i), ("overwrite", i)]
+
+
 # name -> (restype, [argtypes]); mirrors include/bcnn_hip.h one to one
 SIGNATURES = {
     "bcnn_hip_device_count": (i, []),
@@ -65,6 +75,9 @@ SIGNATURES = {
     "bcnn_hip_group_norm_forward": (None, [vp] * 6 + [i, i, i, i, f]),
     "bcnn_hip_group_norm_backward": (None, [vp] * 8 + [i, i, i, i, i]),
     "bcnn_hip_group_norm_path": (i, [i, i, i, i, i]),
+    "bcnn_hip_channel_norm_forward": (None, [vp]),
+    "bcnn_hip_channel_norm_backward": (None, [vp]),
+    "bcnn_hip_channel_norm_path": (i, [i, i, i, i]),
     "bcnn_hip_attention_forward": (None, [vp] * 5 + [i] * 6 + [f]),
     "bcnn_hip_attention_backward": (None, [vp] * 9 + [i] * 6 + [f, i, i, i]),
     "bcnn_hip_attention_lse_size": (sz, [i, i, i]),

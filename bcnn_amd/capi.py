@@ -28,6 +28,7 @@ LAYER_CONV2D, LAYER_BATCHNORM, LAYER_DILATED_CONV2D, LAYER_INTERP = 0, 9, 20, 21
 LAYER_SOFTMAX_LOSS = 22
 LAYER_DEPTHWISE_CONV2D, LAYER_DILATED_DEPTHWISE_CONV2D = 2, 23
 LAYER_ATTENTION = 24
+LAYER_CHANNEL_NORM = 25
 LOSS_NORM_NONE, LOSS_NORM_VALID, LOSS_NORM_VALID_PER_IMAGE = 0, 1, 2
 LOSS_NORMS = {"none": LOSS_NORM_NONE, "valid": LOSS_NORM_VALID, "valid_per_image": LOSS_NORM_VALID_PER_IMAGE}
 
@@ -156,6 +157,7 @@ def lib():
         "bcnn_add_scale_channels_layer": (i, [vp, cp, cp, cp]),
         "bcnn_add_groupnorm_layer": (i, [vp, i, f, cp, cp]),
         "bcnn_add_attention_layer": (i, [vp, i, f, cp, cp, cp, cp]),
+        "bcnn_add_channel_norm_layer": (i, [vp, f, cp, cp]),
         "bcnn_add_eltwise_layer": (i, [vp, i, cp, cp, cp]), "bcnn_add_fullc_layer": (i, [vp, i, i, i, i, cp, cp]),
         "bcnn_add_softmax_layer": (i, [vp, cp, cp]), "bcnn_add_cost_layer": (i, [vp, i, i, f, cp, cp, cp]),
         "bcnn_upload_tensor": (i, [vp, i, i]), "bcnn_download_tensor": (i, [vp, i, i]),
@@ -281,6 +283,11 @@ class Net:
         """bcnn_add_groupnorm_layer: group normalisation over `groups` groups of channels (1: layer norm over (C,H,W),
         C: instance norm with affine); eps <= 0 selects 1e-5"""
         return self._added(self.L.bcnn_add_groupnorm_layer(self.net, groups, eps, src.encode(), dst.encode()))
+
+    def channelnorm(self, src, dst, eps=0.0):
+        """bcnn_add_channel_norm_layer: every position normalised over its C channels (torch's LayerNorm(C) on tokens,
+        LayerNorm2d) with a per-channel scale and bias; eps <= 0 selects 1e-5"""
+        return self._added(self.L.bcnn_add_channel_norm_layer(self.net, eps, src.encode(), dst.encode()))
 
     def add_attention(self, heads, q, k, v, dst, scale=0.0):
         """bcnn_add_attention_layer: dst = V softmax(scale Q^T K)^T per image and head over the positions of tensors q, k, v

@@ -196,7 +196,7 @@ typedef struct {
     int has_size, has_stride, pool_pad, pool_avg, ceil_mode, count_include_pad;
     int has_from; /* Darknet `from=`: src_id[0] is the previous section, src_id[1] the named one */
     int has_groups; /* [groupnorm]: the section wrote groups= (the default of num_groups, 1, belongs to convolutions) */
-    float eps;      /* [groupnorm] / [layernorm] / [instancenorm]; 0: the builder's default */
+    float eps;      /* [groupnorm] / [layernorm] / [instancenorm] / [channelnorm]; 0: the builder's default */
     int dilation;   /* [conv] / [convolutional], [depthwise-conv] / [dw-conv]: > 1 builds the dilated node; default 1 */
     int scale, zoom, out_w, out_h, align_corners; /* [interp] / [bilinear]; scale= may be written stride= (has_stride) */
     /* [softmax_loss] / [softmaxwithloss]: ignore_label (default -1), normalize (a bcnn_loss_norm, -1: a value the section
@@ -498,6 +498,12 @@ static bcnn_status add_layer(bcnn_net *net, const char *name, layer_param *lp) {
             BCNN_CHECK_AND_LOG(net->log_ctx, lp->has_groups, BCNN_INVALID_PARAMETER,
                                "Group-norm layer %s: the section needs a groups= key\n", dst);
         return bcnn_add_groupnorm_layer(net, groups, lp->eps, src, dst);
+    }
+    if (is_any(name, "[channelnorm]", "[layernorm2d]", "[tokennorm]", NULL)) {
+        /* every position over its channels; [layernorm] above stays the norm over (C,H,W) */
+        BCNN_CHECK_AND_LOG(net->log_ctx, lp->a == BCNN_ACT_NONE, BCNN_INVALID_PARAMETER,
+                           "Channel-norm layer %s: only activation=linear is supported; add an [activation] section\n", dst);
+        return bcnn_add_channel_norm_layer(net, lp->eps, src, dst);
     }
     if (is_any(name, "[attention]", "[self_attention]", NULL, NULL)) {
         /* src=q,k,v; a single src=x is self-attention off one tensor. Without scale= the builder's default, 1 / sqrt(d) */

@@ -410,6 +410,7 @@ static void mark_dead_grad_fills(bcnn_net *net) {
         if (uses == 1 && (nd->type == BCNN_LAYER_MAXPOOL || nd->type == BCNN_LAYER_DEPTHWISE_CONV2D ||
                           nd->type == BCNN_LAYER_LRN || nd->type == BCNN_LAYER_POOL2D ||
                           nd->type == BCNN_LAYER_GROUPNORM || nd->type == BCNN_LAYER_INTERP ||
+                          nd->type == BCNN_LAYER_CHANNEL_NORM ||
                           nd->type == BCNN_LAYER_SOFTMAX_LOSS || nd->type == BCNN_LAYER_DILATED_DEPTHWISE_CONV2D)) {
             /* max-pooling's gather, the depthwise data gradient (a gather too: one thread owns a dx element,
              * bcnn_depthwise_conv_layer.c:432-547 accumulates onto the zero fill), LRN's (one lane per column), the
@@ -417,7 +418,7 @@ static void mark_dead_grad_fills(bcnn_net *net) {
              * thread owns a dx element), the bilinear interpolation's gather, whose overwrite form also writes the
              * elements a downsampling skips, and the softmax loss, whose overwrite form writes +0.0 on the pixels that are
              * not valid, and the dilated depthwise data gradient, a gather like the depthwise one whose overwrite form also
-             * writes the elements no tap reaches */
+             * writes the elements no tap reaches, and channel-norm's sweep (one thread owns a dx element) */
             hc->grad_fill_dead[t] = 2;
             continue;
         }
@@ -548,6 +549,10 @@ static bcnn_status node_reserve_buffers(const bcnn_node *nd, const bcnn_tensor *
         elems = 2 * (size_t)d->n * (size_t)((const bcnn_groupnorm_param *)nd->param)->num_groups;
         return RESERVE(bcnn_groupnorm_param, stats_gpu, stats_capacity);
     }
+    if (nd->type == BCNN_LAYER_CHANNEL_NORM) { /* mean and rstd of d's n * h * w positions */
+        elems = 2 * (size_t)d->n * (size_t)d->h * (size_t)d->w;
+        return RESERVE(bcnn_channel_norm_param, stats_gpu, stats_capacity);
+    }
     if (nd->type == BCNN_LAYER_ATTENTION) { /* the log-sum-exp of d's n * heads * h * w queries */
         elems = bcnn_hip_attention_lse_size(d->n, ((const bcnn_attention_param *)nd->param)->num_heads, d->h * d->w);
         BCNN_CHECK_STATUS(RESERVE(bcnn_attention_param, lse_gpu, lse_capacity));
@@ -634,6 +639,10 @@ static bcnn_status resize_plan(bcnn_net *net, int w, int h, int c, int need_real
                            BCNN_INVALID_PARAMETER,
                            "bcnn_resize_net: the k and v of attention node %d would differ in their number of positions, or a "
                            "tensor reach 2^31 elements\n", i);
+        BCNN_CHECK_AND_LOG(net->log_ctx,
+                           nd->type != BCNN_LAYER_CHANNEL_NORM || (long long)d->n * d->c * d->h * d->w < 0x7fffffffLL,
+                           BCNN_INVALID_PARAMETER, "bcnn_resize_net: the tensors of channel-norm node %d would reach 2^31 elements\n",
+                           i);
         /* the class-index label map of a softmax-loss node follows as [n][1][h][w] */
         BCNN_CHECK_AND_LOG(net->log_ctx,
                            nd->type != BCNN_LAYER_SOFTMAX_LOSS || need_realloc ||
@@ -1196,6 +1205,8 @@ void *bcnn_get_node_state(bcnn_net *net, int node, int which) {
     if (nd->type == BCNN_LAYER_POOL2D) return which == 0 ? (void *)((bcnn_pool2d_param *)nd->param)->indexes_gpu : NULL;
     if (nd->type == BCNN_LAYER_GROUPNORM) /* mean [N * G] then rstd [N * G] of the last forward; NULL in a PREDICT-built net */
         return which == 0 ? (void *)((bcnn_groupnorm_param *)nd->param)->stats_gpu : NULL;
+    if (nd->type == BCNN_LAYER_CHANNEL_NORM) /* mean [N * H * W] then rstd [N * H * W] of the last forward; NULL in a PREDICT-built net */
+        return which == 0 ? (void *)((bcnn_channel_norm_param *)nd->param)->stats_gpu : NULL;
     if (nd->type == BCNN_LAYER_ATTENTION) /* the log-sum-exp [N][heads][Lq] of the last forward; NULL in a PREDICT-built net */
         return which == 0 ? (void *)((bcnn_attention_param *)nd->param)->lse_gpu : NULL;
     if (nd->type == BCNN_LAYER_ACTIVATION) /* hard-swish / swish / mish: the input the last TRAIN forward kept */

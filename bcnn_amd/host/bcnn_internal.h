@@ -442,6 +442,16 @@ typedef struct bcnn_groupnorm_param {
 #endif
 } bcnn_groupnorm_param;
 
+/* channel normalisation (bcnn_add_channel_norm_layer; no reference counterpart): src[1] = scales, src[2] = b */
+typedef struct bcnn_channel_norm_param {
+    float eps;
+#ifdef BCNN_USE_HIP
+    float *stats_gpu;       /* nets built in TRAIN / VALID mode: mean [N * H * W] then rstd [N * H * W] of the last forward */
+    size_t stats_capacity;  /* floats allocated (bcnn_reserve_device) */
+    float *adam_m_gpu, *adam_v_gpu; /* moments of the scales, allocated by the first Adam step */
+#endif
+} bcnn_channel_norm_param;
+
 /* multi-head attention (bcnn_add_attention_layer; no reference counterpart): src[0] = q, src[1] = k, src[2] = v */
 #define BCNN_ATTENTION_MAX_HEAD_DIM 128 /* channels of one head of q / k and of v (attention.hip) */
 typedef struct bcnn_attention_param {
@@ -668,6 +678,10 @@ void bcnn_forward_groupnorm_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_groupnorm_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_update_groupnorm_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_groupnorm_layer(bcnn_node *node);
+void bcnn_forward_channel_norm_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_backward_channel_norm_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_update_channel_norm_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_release_param_channel_norm_layer(bcnn_node *node);
 void bcnn_forward_attention_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_attention_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_attention_layer(bcnn_node *node);

@@ -64,7 +64,8 @@ bcnn_status bcnn_save_weights(bcnn_net *net, const char *filename) {
         } else if (nd->type == BCNN_LAYER_BATCHNORM) {
             const int c = net->tensors[nd->dst[0]].c;
             for (int k = 1; ok && k <= 4; ++k) ok = put(fp, &net->tensors[nd->src[k]], c);
-        } else if (nd->type == BCNN_LAYER_GROUPNORM) { /* biases, then scales, like a layer's biases and weights */
+        } else if (nd->type == BCNN_LAYER_GROUPNORM || nd->type == BCNN_LAYER_CHANNEL_NORM) {
+            /* biases, then scales, like a layer's biases and weights */
             const int c = net->tensors[nd->dst[0]].c;
             ok = put(fp, &net->tensors[nd->src[2]], c) && put(fp, &net->tensors[nd->src[1]], c);
         }
@@ -145,7 +146,7 @@ static bcnn_status load_batchnorm(bcnn_net *net, bcnn_node *nd, FILE *fp, int fo
     return BCNN_SUCCESS;
 }
 
-/* the group-norm node: biases then scales, C floats each; Darknet has no such layer and its files hold nothing for it */
+/* the group-norm and channel-norm nodes: biases then scales, C floats each; Darknet has no such layer and its files hold nothing for it */
 static bcnn_status load_groupnorm(bcnn_net *net, bcnn_node *nd, FILE *fp, int format) {
     if (format != 0) return BCNN_SUCCESS;
     bcnn_tensor *s = &net->tensors[nd->src[1]], *b = &net->tensors[nd->src[2]];
@@ -248,7 +249,7 @@ bcnn_status bcnn_load_weights(bcnn_net *net, const char *filename) {
             st = load_batchnorm(net, nd, fp, format);
         } else if (nd->type == BCNN_LAYER_FULL_CONNECTED) {
             st = load_fullc(net, nd, fp, need_transpose);
-        } else if (nd->type == BCNN_LAYER_GROUPNORM) {
+        } else if (nd->type == BCNN_LAYER_GROUPNORM || nd->type == BCNN_LAYER_CHANNEL_NORM) {
             st = load_groupnorm(net, nd, fp, format);
         }
     }

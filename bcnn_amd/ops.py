@@ -580,6 +580,36 @@ def group_norm_backward(x, gamma, mean, rstd, dy, dx, dgamma, dbeta, groups, ove
                                              _f32(dbeta), n, c, h * w, groups, 1 if overwrite else 0)
 
 
+CHANNEL_NORM_PATHS = ("column", "resident", "stream")
+
+
+def channel_norm_path(n, c, hw, backward=False):
+    """bcnn_hip_channel_norm_path: the kernel family of the shape, 0 column, 1 resident, 2 stream (CHANNEL_NORM_PATHS)"""
+    return int(_lib.load().bcnn_hip_channel_norm_path(n, c, hw, 1 if backward else 0))
+
+
+def channel_norm_forward(x, scales, b, y, mean, rstd, eps=1e-5):
+    """bcnn_hip_channel_norm_forward: y = ((x - mean) * rstd) * scales[ch] + b[ch], statistics per position (n, p) over its C
+    channels; mean and rstd ([N * H * W]) receive them, or are both None (nothing is stored)"""
+    n, c, h, w = x.shape
+    assert y.shape == x.shape and scales.numel() == c and b.numel() == c
+    assert (mean is None) == (rstd is None) and (mean is None or (mean.numel() == n * h * w and rstd.numel() == n * h * w))
+    args = _lib.ChannelNormFwdArgs(_f32(x), _f32(scales), _f32(b), _f32(y), _f32(mean), _f32(rstd), n, c, h * w, eps)
+    _lib.load().bcnn_hip_channel_norm_forward(_C.byref(args))
+
+
+def channel_norm_backward(x, scales, mean, rstd, dy, dx, dscales, db, overwrite=False):
+    """bcnn_hip_channel_norm_backward from the stored mean and rstd: dx = (overwrite) or += the data gradient,
+    dscales += sum dy * xh, db += sum dy; each of dx, dscales, db may be None (that output is skipped)"""
+    n, c, h, w = x.shape
+    assert dy.shape == x.shape and (dx is None or dx.shape == x.shape) and scales.numel() == c
+    assert mean.numel() == n * h * w and rstd.numel() == n * h * w
+    assert (dscales is None or dscales.numel() == c) and (db is None or db.numel() == c)
+    args = _lib.ChannelNormBwdArgs(_f32(x), _f32(scales), _f32(mean), _f32(rstd), _f32(dy), _f32(dx), _f32(dscales), _f32(db),
+                                   n, c, h * w, 1 if overwrite else 0)
+    _lib.load().bcnn_hip_channel_norm_backward(_C.byref(args))
+
+
 def _attention_dims(q, k, v, heads):
     n, cqk, lq = q.shape[0], q.shape[1], q.shape[2] * q.shape[3]
     cv, lk = v.shape[1], k.shape[2] * k.shape[3]

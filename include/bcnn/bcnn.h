@@ -78,6 +78,8 @@ typedef enum {
 #define BCNN_LAYER_DILATED_DEPTHWISE_CONV2D ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 6))
 /* The layer type of bcnn_add_attention_layer, likewise a constant behind the enumerator list. */
 #define BCNN_LAYER_ATTENTION ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 7))
+/* The layer type of bcnn_add_channel_norm_layer, likewise a constant behind the enumerator list. */
+#define BCNN_LAYER_CHANNEL_NORM ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 8))
 
 typedef enum {
     BCNN_ACT_NONE, BCNN_ACT_TANH, BCNN_ACT_RELU, BCNN_ACT_RAMP, BCNN_ACT_SOFTPLUS,
@@ -326,6 +328,19 @@ BCNN_API bcnn_status bcnn_add_scale_channels_layer(bcnn_net *net, const char *sr
  * num_groups that does not divide C. May be the first node of a net. Follows bcnn_resize_net (dst is reshaped like src). */
 BCNN_API bcnn_status bcnn_add_groupnorm_layer(bcnn_net *net, int num_groups, float eps, const char *src_id,
                                               const char *dst_id);
+
+/* New, without a reference counterpart: channel normalisation. Every position (n, y, x) of src [N,C,H,W] is normalised over
+ * its C channels: dst = ((src - mean) * rstd) * scales[ch] + b[ch], mean and the biased variance over the position's C
+ * values, rstd = 1 / sqrt(var + eps) -- torch's LayerNorm(C) on [N,L,C] tokens and LayerNorm2d(C). eps <= 0 selects 1e-5.
+ * The same function in TRAIN, VALID and PREDICT mode.
+ *   Parameters <src>_cn_scales (filled with 1) and <src>_cn_b (0), [1,1,1,C], trained like a layer's weights and biases.
+ *   Model files hold b then scales, C floats each; the Darknet reader skips the node.
+ *   A net built in TRAIN or VALID mode keeps mean and rstd of the last forward, [2][N * H * W] floats:
+ *   bcnn_get_node_state(net, node, 0). The backward adds into the source gradient (assigns when it is its sole writer); a
+ *   source without a gradient buffer is skipped.
+ * Refused with BCNN_INVALID_PARAMETER and a log line, nothing added to the net: an unknown src name, a tensor of 2^31
+ * elements or more. May be the first node of a net. Follows bcnn_resize_net (dst is reshaped like src). */
+BCNN_API bcnn_status bcnn_add_channel_norm_layer(bcnn_net *net, float eps, const char *src_id, const char *dst_id);
 /* New, without a reference counterpart: multi-head attention over the positions of feature maps, fp32. With q [N,Cqk,Hq,Wq],
  * k [N,Cqk,Hk,Wk], v [N,Cv,Hk,Wk], d = Cqk / num_heads and c = Cv / num_heads, head h of an image owns channels
  * [h d, (h + 1) d) of q and k and [h c, (h + 1) c) of v and dst [N,Cv,Hq,Wq]:

@@ -585,6 +585,45 @@ void bcnn_hip_group_norm_backward(const float *x_d, const float *gamma_d, const 
 int bcnn_hip_group_norm_path(int n, int c, int hw, int groups, int backward);
 
 /* ---------------------------------------------------------------------------------------------
+ * Channel normalisation (the channel-norm node; channel_norm.hip). No reference counterpart: every position (n, p) of
+ * x [n][c][hw] is normalised over its c channels -- torch's LayerNorm(c) on [N,L,c] tokens, LayerNorm2d(c).
+ *   scales, b are [c]; mean, rstd are [n * hw], position q = n * hw + p.
+ *   forward : mean = sum_c x / c and the biased variance max(sum_c x^2 / c - mean^2, 0), float32 sums in an order that
+ *     follows from the shape, combined and finalised in double; rstd = (float)(1 / sqrt(var + eps)); eps <= 0 selects 1e-5.
+ *     y = ((x - mean) * rstd) * scales[ch] + b[ch], one float32 rounding per operation: y is the bits of that expression
+ *     on the stored float32 mean and rstd. mean / rstd may be NULL (nothing is stored, y has the same bits).
+ *   backward: takes mean and rstd and recomputes xh = (x - mean) * rstd. t = dy * scales[ch]; per position
+ *     ds = sum_c t * xh, db = sum_c t, dxv = (t - (xh * ds + db) / c) * rstd; dx = dxv (overwrite != 0) or dx + dxv.
+ *     dscales[ch] += sum_{n,p} dy * xh, db[ch] += sum_{n,p} dy: per-workgroup partials added in ascending order in double, the
+ *     start value enters as one float32 addition. Each of dx, dscales, db may be NULL: that output is skipped, the others
+ *     keep their bits.
+ *   No atomics; two runs give the same bits; a pointer that is not 16-byte aligned or an hw that is no multiple of 4
+ *   changes the loads and stores, not the bits.
+ *   bcnn_hip_channel_norm_path: the kernel family, from c alone: 0 column (c <= 16 forward, 8 backward: a lane keeps a
+ *     position's channels in registers), 1 resident (forward only, c <= 238: a workgroup keeps a tile of 64 positions in
+ *     LDS), 2 stream (two sweeps over the tile's channels); -1 for c < 1 or hw < 1. With the dispatch trace on every launch is named
+ *     channel_norm_fwd:<path> / channel_norm_bwd:<path>, the parameter-gradient kernel channel_norm_bwd:params: forward 1
+ *     launch, backward at most 2.
+ *   A negative extent and tensors of 2^31 elements or more exit.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct bcnn_hip_channel_norm_fwd_args {
+    const float *x, *scales, *b;
+    float *y;
+    float *mean, *rstd; /* may be NULL */
+    int n, c, hw;
+    float eps;
+} bcnn_hip_channel_norm_fwd_args;
+typedef struct bcnn_hip_channel_norm_bwd_args {
+    const float *x, *scales, *mean, *rstd, *dy;
+    float *dx, *dscales, *db; /* each may be NULL */
+    int n, c, hw;
+    int overwrite; /* dx is assigned, not added to */
+} bcnn_hip_channel_norm_bwd_args;
+void bcnn_hip_channel_norm_forward(const bcnn_hip_channel_norm_fwd_args *args);
+void bcnn_hip_channel_norm_backward(const bcnn_hip_channel_norm_bwd_args *args);
+int bcnn_hip_channel_norm_path(int n, int c, int hw, int backward);
+
+/* ---------------------------------------------------------------------------------------------
  * Multi-head attention over the positions of a feature map (the attention node; attention.hip). No reference counterpart.
  *   q is [n][heads * d][lq], k [n][heads * d][lk], v [n][heads * c][lk], o [n][heads * c][lq]; head h of image n owns
  *   channels [h * d, (h + 1) * d) of q and k and [h * c, (h + 1) * c) of v and o. Per image and head
