@@ -23,6 +23,17 @@ class ChannelNormBwdArgs(C.Structure):  # bcnn_hip_channel_norm_bwd_args
                [("n", i), ("c", i), ("hw", i), ("overwrite", i)]
 
 
+class WindowAttnFwdArgs(C.Structure):  # BcnnWindowAttnFwdArgs
+    _fields_ = [(k, vp) for k in ("q", "k", "v", "table", "o")] + \
+               [(k, i) for k in ("n", "heads", "d", "c", "h", "w", "window", "shift")] + [("scale", f)]
+
+
+class WindowAttnBwdArgs(C.Structure):  # BcnnWindowAttnBwdArgs
+    _fields_ = [(k, vp) for k in ("q", "k", "v", "table", "dout", "dq", "dk", "dv", "dtable")] + \
+               [(k, i) for k in ("n", "heads", "d", "c", "h", "w", "window", "shift")] + [("scale", f)] + \
+               [(k, i) for k in ("overwrite_q", "overwrite_k", "overwrite_v")]
+
+
 # name -> (restype, [argtypes]); mirrors include/bcnn_hip.h one to one
 SIGNATURES = {
     "bcnn_hip_device_count": (i, []),
@@ -81,6 +92,9 @@ SIGNATURES = {
     "bcnn_hip_attention_forward": (None, [vp] * 5 + [i] * 6 + [f]),
     "bcnn_hip_attention_backward": (None, [vp] * 9 + [i] * 6 + [f, i, i, i]),
     "bcnn_hip_attention_lse_size": (sz, [i, i, i]),
+    "bcnn_hip_window_attention_forward": (None, [vp]),
+    "bcnn_hip_window_attention_backward": (None, [vp]),
+    "bcnn_hip_window_attention_check": (i, [i] * 8),
     "bcnn_hip_batchnorm_forward": (None, [vp] * 10 + [i, i, i, i, i]),
     "bcnn_hip_batchnorm_backward": (None, [vp, vp, vp, i] + [vp] * 9 + [i, i, i]),
     "bcnn_hip_conv_workspace_size": (sz, [i] * 9),

@@ -29,6 +29,7 @@ LAYER_SOFTMAX_LOSS = 22
 LAYER_DEPTHWISE_CONV2D, LAYER_DILATED_DEPTHWISE_CONV2D = 2, 23
 LAYER_ATTENTION = 24
 LAYER_CHANNEL_NORM = 25
+LAYER_WINDOW_ATTENTION = 26
 LOSS_NORM_NONE, LOSS_NORM_VALID, LOSS_NORM_VALID_PER_IMAGE = 0, 1, 2
 LOSS_NORMS = {"none": LOSS_NORM_NONE, "valid": LOSS_NORM_VALID, "valid_per_image": LOSS_NORM_VALID_PER_IMAGE}
 
@@ -158,6 +159,7 @@ def lib():
         "bcnn_add_groupnorm_layer": (i, [vp, i, f, cp, cp]),
         "bcnn_add_attention_layer": (i, [vp, i, f, cp, cp, cp, cp]),
         "bcnn_add_channel_norm_layer": (i, [vp, f, cp, cp]),
+        "bcnn_add_window_attention_layer": (i, [vp, i, i, i, i, f, cp, cp, cp, cp]),
         "bcnn_add_eltwise_layer": (i, [vp, i, cp, cp, cp]), "bcnn_add_fullc_layer": (i, [vp, i, i, i, i, cp, cp]),
         "bcnn_add_softmax_layer": (i, [vp, cp, cp]), "bcnn_add_cost_layer": (i, [vp, i, i, f, cp, cp, cp]),
         "bcnn_upload_tensor": (i, [vp, i, i]), "bcnn_download_tensor": (i, [vp, i, i]),
@@ -294,6 +296,12 @@ class Net:
         (which may be one tensor); scale 0 selects 1 / sqrt(channels of a head of q)"""
         return self._added(self.L.bcnn_add_attention_layer(self.net, heads, scale, q.encode(), k.encode(), v.encode(),
                                                            dst.encode()))
+
+    def add_window_attention(self, heads, window, q, k, v, dst, shift=0, rel_bias=True, scale=0.0):
+        """bcnn_add_window_attention_layer: attention inside the window x window windows of the map rolled by shift, per image
+        and head, with the relative position bias <dst>_relbias (rel_bias) and Swin's region mask (shift > 0)"""
+        return self._added(self.L.bcnn_add_window_attention_layer(self.net, heads, window, shift, 1 if rel_bias else 0, scale,
+                                                                  q.encode(), k.encode(), v.encode(), dst.encode()))
 
     def activation(self, act, src):
         return self._added(self.L.bcnn_add_activation_layer(self.net, act, src.encode()))

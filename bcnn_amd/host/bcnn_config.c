@@ -205,6 +205,7 @@ typedef struct {
     float loss_scale;
     int heads; /* [attention] / [self_attention]; its scale= is loss_scale's float, read only when the section wrote it */
     int has_scale;
+    int window, shift, rel_bias; /* [window_attention] / [swin_attention]; shift defaults to 0, rel_bias to 1 */
 } layer_param;
 
 static void lp_reset(layer_param *lp) {
@@ -219,6 +220,7 @@ static void lp_reset(layer_param *lp) {
     lp->k = 1.0f; /* [lrn] without a k key: the Caffe / torch default */
     lp->count_include_pad = 1; /* [pool] type=avg: the Caffe / torch default */
     lp->dilation = 1;
+    lp->rel_bias = 1;
     lp->ignore_label = -1; lp->loss_norm = (int)BCNN_LOSS_NORM_VALID_PER_IMAGE; lp->loss_scale = 1.0f;
 }
 
@@ -285,6 +287,9 @@ static void lp_set(bcnn_net *net, int section_idx, layer_param *lp, const char *
     else if (!strcmp(name, "dilation")) lp->dilation = atoi(val);
     else if (!strcmp(name, "scale")) { lp->scale = atoi(val); lp->loss_scale = (float)atof(val); lp->has_scale = 1; }
     else if (!strcmp(name, "heads") || !strcmp(name, "num_heads")) lp->heads = atoi(val);
+    else if (!strcmp(name, "window") || !strcmp(name, "window_size")) lp->window = atoi(val);
+    else if (!strcmp(name, "shift")) lp->shift = atoi(val);
+    else if (!strcmp(name, "rel_bias")) lp->rel_bias = atoi(val);
     else if (!strcmp(name, "ignore_label")) lp->ignore_label = atoi(val);
     else if (!strcmp(name, "normalize")) {
         if (!strcmp(val, "none")) lp->loss_norm = (int)BCNN_LOSS_NORM_NONE;
@@ -514,6 +519,17 @@ static bcnn_status add_layer(bcnn_net *net, const char *name, layer_param *lp) {
         const int three = lp->num_srcs == 3;
         return bcnn_add_attention_layer(net, lp->heads, lp->has_scale ? lp->loss_scale : 0.0f, src,
                                         lp->src_id[three ? 1 : 0], lp->src_id[three ? 2 : 0], dst);
+    }
+    if (is_any(name, "[window_attention]", "[swin_attention]", NULL, NULL)) {
+        /* as [attention]: src=q,k,v or one tensor; window=, shift= (0), rel_bias= (1); without scale= 1 / sqrt(d) */
+        BCNN_CHECK_AND_LOG(net->log_ctx, lp->a == BCNN_ACT_NONE, BCNN_INVALID_PARAMETER,
+                           "Window-attention layer %s: only activation=linear is supported; add an [activation] section\n", dst);
+        BCNN_CHECK_AND_LOG(net->log_ctx, lp->num_srcs == 1 || lp->num_srcs == 3, BCNN_INVALID_PARAMETER,
+                           "Window-attention layer %s: src= names q,k,v or one tensor for all three\n", dst);
+        const int three = lp->num_srcs == 3;
+        return bcnn_add_window_attention_layer(net, lp->heads, lp->window, lp->shift, lp->rel_bias,
+                                               lp->has_scale ? lp->loss_scale : 0.0f, src, lp->src_id[three ? 1 : 0],
+                                               lp->src_id[three ? 2 : 0], dst);
     }
     if (!strcmp(name, "[yolo]")) {
         /* the builder copies 2 * num values (the reference reads past a shorter list); pad a short one with zeros */

@@ -396,6 +396,12 @@ static void mark_dead_grad_fills(bcnn_net *net) {
                           ((const bcnn_cost_param *)net->nodes[i].param)->loss == BCNN_LOSS_LIFTED_STRUCT;
         if (lifted_src) continue;
         const bcnn_node *nd = &net->nodes[first];
+        if (uses == 1 && nd->type == BCNN_LAYER_WINDOW_ATTENTION && (nd->src[0] == t || nd->src[1] == t || nd->src[2] == t)) {
+            /* the window-attention node likewise: every position lies in one window, every element of dq, dk, dv has one
+             * writer (its table, src[3], accumulates and keeps its fill) */
+            hc->grad_fill_dead[t] = 2;
+            continue;
+        }
         if (uses == 1 && nd->type == BCNN_LAYER_ATTENTION) {
             /* the attention node writes every element of dq, dk and dv once, whichever of its three slots t is in; a tensor
              * in two slots counts two uses and keeps its fill: the node's launches then add up in it */
@@ -596,6 +602,8 @@ static int node_dst_shape(const bcnn_node *nd, const bcnn_tensor *s, bcnn_tensor
         if (!bcnn_interp_out_extents((const bcnn_interp_param *)nd->param, s->h, s->w, &oh, &ow)) return 0;
     } else if (nd->type == BCNN_LAYER_ATTENTION) { /* the queries' extent (s is q), the values' depth */
         oc = ((const bcnn_attention_param *)nd->param)->out_channels;
+    } else if (nd->type == BCNN_LAYER_WINDOW_ATTENTION) {
+        oc = ((const bcnn_window_attention_param *)nd->param)->out_channels;
     }
     bcnn_tensor_set_shape(d, s->n, oc, oh, ow, 1);
     return 1;
@@ -639,6 +647,13 @@ static bcnn_status resize_plan(bcnn_net *net, int w, int h, int c, int need_real
                            BCNN_INVALID_PARAMETER,
                            "bcnn_resize_net: the k and v of attention node %d would differ in their number of positions, or a "
                            "tensor reach 2^31 elements\n", i);
+        if (nd->type == BCNN_LAYER_WINDOW_ATTENTION) { /* the new extents must still be whole windows */
+            char why[256] = "";
+            BCNN_CHECK_AND_LOG(net->log_ctx,
+                               nd->num_src >= 3 && bcnn_window_attention_fits((const bcnn_window_attention_param *)nd->param, s,
+                                                                              &plan[nd->src[1]], &plan[nd->src[2]], why, sizeof(why)),
+                               BCNN_INVALID_PARAMETER, "bcnn_resize_net: window-attention node %d: %s\n", i, why);
+        }
         BCNN_CHECK_AND_LOG(net->log_ctx,
                            nd->type != BCNN_LAYER_CHANNEL_NORM || (long long)d->n * d->c * d->h * d->w < 0x7fffffffLL,
                            BCNN_INVALID_PARAMETER, "bcnn_resize_net: the tensors of channel-norm node %d would reach 2^31 elements\n",

@@ -452,6 +452,17 @@ typedef struct bcnn_channel_norm_param {
 #endif
 } bcnn_channel_norm_param;
 
+/* window attention (bcnn_add_window_attention_layer; no reference counterpart): src[0] = q, src[1] = k, src[2] = v,
+ * src[3] = the relative position bias table when rel_bias */
+typedef struct bcnn_window_attention_param {
+    int num_heads, window, shift, rel_bias;
+    float scale;
+    int out_channels; /* the depth of v */
+#ifdef BCNN_USE_HIP
+    float *adam_m_gpu, *adam_v_gpu; /* moments of the table, allocated by the first Adam step */
+#endif
+} bcnn_window_attention_param;
+
 /* multi-head attention (bcnn_add_attention_layer; no reference counterpart): src[0] = q, src[1] = k, src[2] = v */
 #define BCNN_ATTENTION_MAX_HEAD_DIM 128 /* channels of one head of q / k and of v (attention.hip) */
 typedef struct bcnn_attention_param {
@@ -682,6 +693,14 @@ void bcnn_forward_channel_norm_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_channel_norm_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_update_channel_norm_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_channel_norm_layer(bcnn_node *node);
+void bcnn_forward_window_attention_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_backward_window_attention_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_update_window_attention_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_release_param_window_attention_layer(bcnn_node *node);
+/* bcnn_layers_window_attention.c: q, k, v of these shapes pass every shape rule of the node (batch, extents, depths, heads,
+ * window, shift, head depth, 2^31); else a line for the log in `why` */
+int bcnn_window_attention_fits(const bcnn_window_attention_param *p, const bcnn_tensor *q, const bcnn_tensor *k,
+                               const bcnn_tensor *v, char *why, size_t why_size);
 void bcnn_forward_attention_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_attention_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_attention_layer(bcnn_node *node);

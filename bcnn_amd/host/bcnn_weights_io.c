@@ -68,6 +68,8 @@ bcnn_status bcnn_save_weights(bcnn_net *net, const char *filename) {
             /* biases, then scales, like a layer's biases and weights */
             const int c = net->tensors[nd->dst[0]].c;
             ok = put(fp, &net->tensors[nd->src[2]], c) && put(fp, &net->tensors[nd->src[1]], c);
+        } else if (nd->type == BCNN_LAYER_WINDOW_ATTENTION && nd->num_src > 3) { /* the relative position bias table */
+            ok = put(fp, &net->tensors[nd->src[3]], bcnn_tensor_size(&net->tensors[nd->src[3]]));
         }
     }
     fclose(fp);
@@ -154,6 +156,16 @@ static bcnn_status load_groupnorm(bcnn_net *net, bcnn_node *nd, FILE *fp, int fo
     READ_OR_FAIL(net, fp, b, c, "group-norm biases");
     READ_OR_FAIL(net, fp, s, c, "group-norm scales");
     push(s, c); push(b, c);
+    return BCNN_SUCCESS;
+}
+
+/* the window-attention node's relative position bias table, [heads][(2 ws - 1)^2] floats; Darknet files hold nothing for it */
+static bcnn_status load_relbias(bcnn_net *net, bcnn_node *nd, FILE *fp, int format) {
+    if (format != 0) return BCNN_SUCCESS;
+    bcnn_tensor *t = &net->tensors[nd->src[3]];
+    const int count = bcnn_tensor_size(t);
+    READ_OR_FAIL(net, fp, t, count, "window-attention bias table");
+    push(t, count);
     return BCNN_SUCCESS;
 }
 
@@ -251,6 +263,8 @@ bcnn_status bcnn_load_weights(bcnn_net *net, const char *filename) {
             st = load_fullc(net, nd, fp, need_transpose);
         } else if (nd->type == BCNN_LAYER_GROUPNORM || nd->type == BCNN_LAYER_CHANNEL_NORM) {
             st = load_groupnorm(net, nd, fp, format);
+        } else if (nd->type == BCNN_LAYER_WINDOW_ATTENTION && nd->num_src > 3) {
+            st = load_relbias(net, nd, fp, format);
         }
     }
     fclose(fp);

@@ -636,6 +636,43 @@ def attention_backward(q, k, v, o, lse, do, dq, dk, dv, heads, scale=0.0, overwr
                                             _f32(dv), n, heads, d, c, lq, lk, scale, *[1 if w else 0 for w in overwrite])
 
 
+WINDOW_ATTENTION_REFUSALS = ("ok", "extent", "window", "ragged_map", "shift", "head_dim", "too_large")
+
+
+def window_attention_check(n, heads, d, c, h, w, window, shift):
+    """bcnn_hip_window_attention_check: 0, or the refusal code of the shape (WINDOW_ATTENTION_REFUSALS); host only"""
+    return int(_lib.load().bcnn_hip_window_attention_check(n, heads, d, c, h, w, window, shift))
+
+
+def _window_attention_dims(q, k, v, heads, window, table):
+    n, cqk, h, w = q.shape
+    assert k.shape == q.shape and v.shape[0] == n and v.shape[2:] == q.shape[2:]
+    assert cqk % heads == 0 and v.shape[1] % heads == 0
+    assert table is None or table.numel() == heads * (2 * window - 1) ** 2
+    return n, cqk // heads, v.shape[1] // heads, h, w
+
+
+def window_attention_forward(q, k, v, table, o, heads, window, shift=0, scale=0.0):
+    """bcnn_hip_window_attention_forward: o = V softmax(scale Q^T K + B)^T inside the window x window windows of the maps
+    rolled by shift, per image and head; table ([heads][(2 window - 1)^2]) may be None; scale 0 selects 1 / sqrt(d)"""
+    n, d, c, h, w = _window_attention_dims(q, k, v, heads, window, table)
+    assert o.numel() == v.numel()
+    args = _lib.WindowAttnFwdArgs(_f32(q), _f32(k), _f32(v), _f32(table), _f32(o), n, heads, d, c, h, w, window, shift, scale)
+    _lib.load().bcnn_hip_window_attention_forward(_C.byref(args))
+
+
+def window_attention_backward(q, k, v, table, do, dq, dk, dv, dtable, heads, window, shift=0, scale=0.0,
+                              overwrite=(False, False, False)):
+    """bcnn_hip_window_attention_backward: each of dq, dk, dv is assigned (its overwrite flag) or added to, dtable is added
+    to; each of the four may be None (skipped)"""
+    n, d, c, h, w = _window_attention_dims(q, k, v, heads, window, table)
+    assert do.numel() == v.numel() and (dtable is None or (table is not None and dtable.numel() == table.numel()))
+    assert all(g is None or g.numel() == x.numel() for g, x in ((dq, q), (dk, k), (dv, v)))
+    args = _lib.WindowAttnBwdArgs(_f32(q), _f32(k), _f32(v), _f32(table), _f32(do), _f32(dq), _f32(dk), _f32(dv), _f32(dtable),
+                                  n, heads, d, c, h, w, window, shift, scale, *[1 if x else 0 for x in overwrite])
+    _lib.load().bcnn_hip_window_attention_backward(_C.byref(args))
+
+
 def activation_backward(x, dx, act, slopes=None, dslopes=None, spatial=1, channels=1):
     """bcnn_backward_activation_cpu (bcnn_activation_layer.c:165-226), dx in place"""
     _lib.load().bcnn_hip_activation_backward(_f32(x), _f32(dx), x.numel(), act, _f32(slopes), _f32(dslopes),

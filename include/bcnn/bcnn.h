@@ -80,6 +80,8 @@ typedef enum {
 #define BCNN_LAYER_ATTENTION ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 7))
 /* The layer type of bcnn_add_channel_norm_layer, likewise a constant behind the enumerator list. */
 #define BCNN_LAYER_CHANNEL_NORM ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 8))
+/* The layer type of bcnn_add_window_attention_layer, likewise a constant behind the enumerator list. */
+#define BCNN_LAYER_WINDOW_ATTENTION ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 9))
 
 typedef enum {
     BCNN_ACT_NONE, BCNN_ACT_TANH, BCNN_ACT_RELU, BCNN_ACT_RAMP, BCNN_ACT_SOFTPLUS,
@@ -341,6 +343,24 @@ BCNN_API bcnn_status bcnn_add_groupnorm_layer(bcnn_net *net, int num_groups, flo
  * Refused with BCNN_INVALID_PARAMETER and a log line, nothing added to the net: an unknown src name, a tensor of 2^31
  * elements or more. May be the first node of a net. Follows bcnn_resize_net (dst is reshaped like src). */
 BCNN_API bcnn_status bcnn_add_channel_norm_layer(bcnn_net *net, float eps, const char *src_id, const char *dst_id);
+/* New, without a reference counterpart: window attention with a relative position bias (the attention of Swin blocks), fp32.
+ * q, k [N,Cqk,H,W] and v [N,Cv,H,W] share one extent; d = Cqk / num_heads, c = Cv / num_heads, dst is [N,Cv,H,W]. The map is
+ * rolled by `shift` (torch.roll(x, (-shift, -shift))), cut into window x window windows, and every window attends to itself
+ * per image and head: S[i][j] = scale Q_i . K_j + table[head][(yi - yj + window - 1)(2 window - 1) + (xi - xj + window - 1)],
+ * dst = V softmax(S)^T written back un-rolled. With shift > 0 the pairs that the roll brought together from different
+ * sides of the map's border (Swin's three regions per axis) are excluded exactly. scale 0 selects 1 / sqrt(d).
+ *   With rel_bias != 0 the node owns the parameter <dst>_relbias, [1,1,1,num_heads (2 window - 1)^2], zero-filled, trained
+ *   like a layer's weights (SGD, Adam with the node's own moments, data parallelism) and stored in the native model file;
+ *   the Darknet reader skips it. q, k, v may be one tensor or alias in pairs; nothing is kept between forward and backward.
+ *   The backward assigns a source gradient when this node is its sole writer and adds otherwise; a source without a
+ *   gradient is skipped. Stays fp32 under bcnn_set_inference_precision(BCNN_PRECISION_BF16).
+ * Refused with BCNN_INVALID_PARAMETER and a log line, nothing added to the net: unknown sources, different batch sizes,
+ * q, k, v of different extents, q and k of different depth, heads that do not divide both depths, window < 1,
+ * window^2 > 64, H or W no multiple of window, shift outside [0, window), d or c above 64, a tensor of 2^31 elements or more.
+ * Follows bcnn_resize_net; a new extent that is no multiple of window is refused and leaves the net as it was. */
+BCNN_API bcnn_status bcnn_add_window_attention_layer(bcnn_net *net, int num_heads, int window, int shift, int rel_bias,
+                                                     float scale, const char *q_id, const char *k_id, const char *v_id,
+                                                     const char *dst_id);
 /* New, without a reference counterpart: multi-head attention over the positions of feature maps, fp32. With q [N,Cqk,Hq,Wq],
  * k [N,Cqk,Hk,Wk], v [N,Cv,Hk,Wk], d = Cqk / num_heads and c = Cv / num_heads, head h of an image owns channels
  * [h d, (h + 1) d) of q and k and [h c, (h + 1) c) of v and dst [N,Cv,Hq,Wq]:

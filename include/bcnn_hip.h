@@ -649,6 +649,56 @@ void bcnn_hip_attention_backward(const float *q_d, const float *k_d, const float
 size_t bcnn_hip_attention_lse_size(int n, int heads, int lq);
 
 /* ---------------------------------------------------------------------------------------------
+ * Window attention with a relative position bias (the window-attention node; attention_window.hip). No reference
+ * counterpart: the attention of Swin blocks, fp32.
+ *   q, k are [n][heads * d][h][w], v and o [n][heads * c][h][w]. The map is rolled by `shift` (rolled position (y', x') is
+ *   source position ((y' + shift) mod h, (x' + shift) mod w)) and cut into (h / window) * (w / window) windows of
+ *   L = window^2 positions, row-major. Inside a window, per image and head:
+ *     S[i][j] = scale * sum_t Q[t][i] K[t][j] + table[head][(yi - yj + window - 1) * (2 window - 1) + (xi - xj + window - 1)],
+ *     P = softmax_j S, O[r][i] = sum_j V[r][j] P[i][j], written to the source position of query i (the output is un-rolled).
+ *   scale == 0 selects 1 / sqrt(d). table is [heads][(2 window - 1)^2] or NULL (no bias). With shift > 0 a rolled row y' has
+ *   region 0 if y' < h - window, 1 if y' < h - shift, else 2, columns likewise with w; a pair (i, j) whose row regions or
+ *   column regions differ is excluded exactly (-inf before the maximum).
+ *   backward: recomputes S and P from q, k and the table; reads neither o nor anything the forward kept. dq, dk, dv arrive at
+ *     the source positions, each assigned (overwrite_x != 0) or added to, each may be NULL (its work is skipped, the others
+ *     keep their bits). q, k, v -- and dq, dk, dv -- may be one tensor when d == c (overwrite flags 0).
+ *     dtable[head][rel] += the sum of dS over images, windows and the pairs of that relative position: per-workgroup dense
+ *     partials, added in a fixed order in double, the start value enters as one float32 addition. dtable (or table) NULL
+ *     skips that work.
+ *   No atomics; two runs give the same bits; every access is an element access, so alignment changes nothing.
+ *   Launches (dispatch trace): window_attention_bias (the dense bias tile, only with a table), window_attention_fwd;
+ *   window_attention_bias, window_attention_bwd, window_attention_bwd:bias (only with dtable).
+ *   bcnn_hip_window_attention_check: 0, or the refusal code of the shape; host only. The entry points exit on a refused shape.
+ * ------------------------------------------------------------------------------------------- */
+enum {
+    BCNN_HIP_WINDOW_ATTN_BAD_EXTENT = 1,   /* n, heads, h or w below 1, or heads above 65535 */
+    BCNN_HIP_WINDOW_ATTN_BAD_WINDOW = 2,   /* window < 1 or window^2 > 64 */
+    BCNN_HIP_WINDOW_ATTN_RAGGED_MAP = 3,   /* h or w is no multiple of window */
+    BCNN_HIP_WINDOW_ATTN_BAD_SHIFT = 4,    /* shift outside [0, window) */
+    BCNN_HIP_WINDOW_ATTN_BAD_HEAD_DIM = 5, /* d or c outside 1 .. 64 */
+    BCNN_HIP_WINDOW_ATTN_TOO_LARGE = 6     /* a tensor of 2^31 elements or more */
+};
+typedef struct BcnnWindowAttnFwdArgs {
+    const float *q, *k, *v;
+    const float *table; /* may be NULL */
+    float *o;
+    int n, heads, d, c, h, w, window, shift;
+    float scale;
+} BcnnWindowAttnFwdArgs;
+typedef struct BcnnWindowAttnBwdArgs {
+    const float *q, *k, *v;
+    const float *table; /* may be NULL */
+    const float *dout;
+    float *dq, *dk, *dv, *dtable; /* each may be NULL */
+    int n, heads, d, c, h, w, window, shift;
+    float scale;
+    int overwrite_q, overwrite_k, overwrite_v;
+} BcnnWindowAttnBwdArgs;
+void bcnn_hip_window_attention_forward(const BcnnWindowAttnFwdArgs *args);
+void bcnn_hip_window_attention_backward(const BcnnWindowAttnBwdArgs *args);
+int bcnn_hip_window_attention_check(int n, int heads, int d, int c, int h, int w, int window, int shift);
+
+/* ---------------------------------------------------------------------------------------------
  * Depthwise convolution.  Replaces the kernels of bcnn_depthwise_conv_layer.cu:33-200; CPU semantics
  * bcnn_depthwise_conv_layer.c:165-293, 295-547: weights [c][k][k]; y = act(dwconv + bias);
  * backward: dy *= act'(y) in place, dbias += ..., and ONLY IF dx_d != NULL: dw += ..., dx += ...
