@@ -89,6 +89,9 @@ SIGNATURES = {
     "bcnn_hip_channel_norm_forward": (None, [vp]),
     "bcnn_hip_channel_norm_backward": (None, [vp]),
     "bcnn_hip_channel_norm_path": (i, [i, i, i, i]),
+    "bcnn_hip_patch_merge_forward": (None, [vp] * 6 + [i, i, i, i, f]),
+    "bcnn_hip_patch_merge_backward": (None, [vp] * 8 + [i, i, i, i, i]),
+    "bcnn_hip_patch_merge_path": (i, [i, i, i, i]),
     "bcnn_hip_attention_forward": (None, [vp] * 5 + [i] * 6 + [f]),
     "bcnn_hip_attention_backward": (None, [vp] * 9 + [i] * 6 + [f, i, i, i]),
     "bcnn_hip_attention_lse_size": (sz, [i, i, i]),

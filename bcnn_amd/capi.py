@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("BCNN_LIB", os.path.join(_HERE, "lib", "libbcnn.so")) 
 MODE_PREDICT, MODE_TRAIN, MODE_VALID = 0, 1, 2
 PRECISION_FP32, PRECISION_BF16 = 0, 1
 (ACT_NONE, ACT_TANH, ACT_RELU, ACT_RAMP, ACT_SOFTPLUS, ACT_LRELU, ACT_ABS, ACT_CLAMP, ACT_PRELU,
- ACT_LOGISTIC, ACT_RELU6, ACT_HARD_SIGMOID, ACT_HARD_SWISH, ACT_SWISH, ACT_MISH) = range(15)
+ ACT_LOGISTIC, ACT_RELU6, ACT_HARD_SIGMOID, ACT_HARD_SWISH, ACT_SWISH, ACT_MISH, ACT_GELU) = range(16)
 PADDING_SAME, PADDING_VALID, PADDING_CAFFE = 0, 1, 2
 FILLER_FIXED, FILLER_XAVIER, FILLER_MSRA = 0, 1, 2
 LOSS_EUCLIDEAN, LOSS_LIFTED_STRUCT = 0, 1
@@ -30,6 +30,7 @@ LAYER_DEPTHWISE_CONV2D, LAYER_DILATED_DEPTHWISE_CONV2D = 2, 23
 LAYER_ATTENTION = 24
 LAYER_CHANNEL_NORM = 25
 LAYER_WINDOW_ATTENTION = 26
+LAYER_PATCH_MERGING, LAYER_RESIDUAL = 27, 28
 LOSS_NORM_NONE, LOSS_NORM_VALID, LOSS_NORM_VALID_PER_IMAGE = 0, 1, 2
 LOSS_NORMS = {"none": LOSS_NORM_NONE, "valid": LOSS_NORM_VALID, "valid_per_image": LOSS_NORM_VALID_PER_IMAGE}
 
@@ -159,6 +160,8 @@ def lib():
         "bcnn_add_groupnorm_layer": (i, [vp, i, f, cp, cp]),
         "bcnn_add_attention_layer": (i, [vp, i, f, cp, cp, cp, cp]),
         "bcnn_add_channel_norm_layer": (i, [vp, f, cp, cp]),
+        "bcnn_add_patch_merging_layer": (i, [vp, i, f, cp, cp]),
+        "bcnn_add_residual_layer": (i, [vp, cp, cp, cp]),
         "bcnn_add_window_attention_layer": (i, [vp, i, i, i, i, f, cp, cp, cp, cp]),
         "bcnn_add_eltwise_layer": (i, [vp, i, cp, cp, cp]), "bcnn_add_fullc_layer": (i, [vp, i, i, i, i, cp, cp]),
         "bcnn_add_softmax_layer": (i, [vp, cp, cp]), "bcnn_add_cost_layer": (i, [vp, i, i, f, cp, cp, cp]),
@@ -308,6 +311,17 @@ class Net:
 
     def eltwise(self, act, src1, src2, dst):
         return self._added(self.L.bcnn_add_eltwise_layer(self.net, act, src1.encode(), src2.encode(), dst.encode()))
+
+    def residual(self, src1, src2, dst):
+        """bcnn_add_residual_layer: dst = src1 + src2 for two tensors of one shape, every image of the batch (eltwise keeps
+        the reference's quirk: its second operand reaches image 0 only)"""
+        return self._added(self.L.bcnn_add_residual_layer(self.net, src1.encode(), src2.encode(), dst.encode()))
+
+    def patch_merging(self, src, dst, norm=1, eps=0.0):
+        """bcnn_add_patch_merging_layer: [N,C,H,W] -> [N,4C,H/2,W/2] in Swin's order, with norm a layer norm over the 4C
+        channels of every position (parameters <src>_pm_scales, <src>_pm_b); norm=0 is space-to-depth (YOLOv5's Focus);
+        eps <= 0 selects 1e-5"""
+        return self._added(self.L.bcnn_add_patch_merging_layer(self.net, norm, eps, src.encode(), dst.encode()))
 
     def fullc(self, out, act=ACT_NONE, src="input", dst="fc"):
         return self._added(self.L.bcnn_add_fullc_layer(self.net, out, FILLER_XAVIER, act, 0, src.encode(), dst.encode()))

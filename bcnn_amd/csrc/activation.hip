@@ -66,14 +66,16 @@ __global__ void accumulate_kernel(const float* __restrict__ partials, int C, int
     out[c] += (float)s;
 }
 
-// ---- the self-gated activations: hard-swish, swish, mish (no reference counterpart) --------------------------------------------
+// ---- the self-gated activations: hard-swish, swish, mish, gelu (no reference counterpart) --------------------------------------------
 // Their derivative is a function of the INPUT, which an in-place node no longer has after its forward: the forward keeps a
 // copy (12 bytes per element instead of 8), the backward reads it (12 bytes). hard-swish is float arithmetic written as
-// torch writes it; swish and mish evaluate exp in double like LOGISTIC above and round once at the end.
+// torch writes it; swish and mish evaluate exp, gelu erf, in double like LOGISTIC above and round once at the end.
 __device__ __forceinline__ float gated_fwd(float x, int act) {
     if (act == BCNN_HIP_ACT_HARD_SWISH) return (x * fminf(fmaxf(x + 3.f, 0.f), 6.f)) / 6.0f;
     const double xd = (double)x;
     if (act == BCNN_HIP_ACT_SWISH) return (float)(xd / (1.0 + exp(-xd)));
+    // gelu, the exact form as torch writes it: x Phi(x), Phi(x) = (1 + erf(x / sqrt 2)) / 2
+    if (act == BCNN_HIP_ACT_GELU) return (float)(xd * (0.5 * (1.0 + erf(xd * 0.70710678118654752440))));
     // mish: tanh(log(1 + e)) = ((1 + e)^2 - 1) / ((1 + e)^2 + 1) = n / (n + 2), n = e (e + 2); 1 past where e^2 overflows
     const double e = exp(xd), n = e * (e + 2.0);
     return (float)(xd > 300.0 ? xd : xd * (n / (n + 2.0)));
@@ -86,6 +88,10 @@ __device__ __forceinline__ float gated_bwd(float g, float x, int act) {
     if (act == BCNN_HIP_ACT_SWISH) {
         const double s = 1.0 / (1.0 + exp(-xd));
         return (float)(gd * (s * (1.0 + xd * (1.0 - s))));
+    }
+    if (act == BCNN_HIP_ACT_GELU) {  // Phi(x) + x phi(x), phi(x) = exp(-x^2 / 2) / sqrt(2 pi)
+        const double cdf = 0.5 * (1.0 + erf(xd * 0.70710678118654752440)), pdf = 0.39894228040143267794 * exp(-0.5 * xd * xd);
+        return (float)(gd * (cdf + xd * pdf));
     }
     // mish' = t + x s (1 - t^2), t = n / (n + 2), s = e / (1 + e); 1 - t = 2 / (n + 2) without cancellation
     if (xd > 300.0) return g;
@@ -203,8 +209,8 @@ void bcnn_hip_activation_forward_keep(float* x, float* x_saved, size_t size, int
 void bcnn_hip_activation_backward_from_input(const float* x_saved, float* dx, size_t size, int act) {
     if (!size) return;
     if (!act_needs_input(act) || !x_saved) {
-        fprintf(stderr, "[bcnn_hip] bcnn_hip_activation_backward_from_input: activation %d is not hard-swish, swish or "
-                        "mish, or no saved input was given\n", act);
+        fprintf(stderr, "[bcnn_hip] bcnn_hip_activation_backward_from_input: activation %d is not hard-swish, swish, "
+                        "mish or gelu, or no saved input was given\n", act);
         exit(1);
     }
     gated_bwd_kernel<<<stream_grid(size / 4 + 1, 256), 256, 0, current_stream()>>>(x_saved, dx, size, act,

@@ -226,10 +226,10 @@ __device__ __forceinline__ float act_fwd(float x, int act, float slope) {
         default: return x;
     }
 }
-// The self-gated activations (hard-swish, swish, mish): their derivative is no function of the output, so no fused
+// The self-gated activations (hard-swish, swish, mish, gelu): their derivative is no function of the output, so no fused
 // epilogue and no `act` argument but the stand-alone activation entry points' (activation.hip) takes them.
 __host__ __device__ __forceinline__ bool act_needs_input(int act) {
-    return act == BCNN_HIP_ACT_HARD_SWISH || act == BCNN_HIP_ACT_SWISH || act == BCNN_HIP_ACT_MISH;
+    return act == BCNN_HIP_ACT_HARD_SWISH || act == BCNN_HIP_ACT_SWISH || act == BCNN_HIP_ACT_MISH || act == BCNN_HIP_ACT_GELU;
 }
 
 // Activations cheap enough to fuse into a producer's epilogue (no double-precision exp/log). The

@@ -196,7 +196,7 @@ typedef struct {
     int has_size, has_stride, pool_pad, pool_avg, ceil_mode, count_include_pad;
     int has_from; /* Darknet `from=`: src_id[0] is the previous section, src_id[1] the named one */
     int has_groups; /* [groupnorm]: the section wrote groups= (the default of num_groups, 1, belongs to convolutions) */
-    float eps;      /* [groupnorm] / [layernorm] / [instancenorm] / [channelnorm]; 0: the builder's default */
+    float eps;      /* [groupnorm] / [layernorm] / [instancenorm] / [channelnorm] / [patch_merging]; 0: the builder's default */
     int dilation;   /* [conv] / [convolutional], [depthwise-conv] / [dw-conv]: > 1 builds the dilated node; default 1 */
     int scale, zoom, out_w, out_h, align_corners; /* [interp] / [bilinear]; scale= may be written stride= (has_stride) */
     /* [softmax_loss] / [softmaxwithloss]: ignore_label (default -1), normalize (a bcnn_loss_norm, -1: a value the section
@@ -206,6 +206,7 @@ typedef struct {
     int heads; /* [attention] / [self_attention]; its scale= is loss_scale's float, read only when the section wrote it */
     int has_scale;
     int window, shift, rel_bias; /* [window_attention] / [swin_attention]; shift defaults to 0, rel_bias to 1 */
+    int norm; /* [patch_merging] / [patchmerge]: the norm over the 4C channels, default 1 */
 } layer_param;
 
 static void lp_reset(layer_param *lp) {
@@ -221,6 +222,7 @@ static void lp_reset(layer_param *lp) {
     lp->count_include_pad = 1; /* [pool] type=avg: the Caffe / torch default */
     lp->dilation = 1;
     lp->rel_bias = 1;
+    lp->norm = 1;
     lp->ignore_label = -1; lp->loss_norm = (int)BCNN_LOSS_NORM_VALID_PER_IMAGE; lp->loss_scale = 1.0f;
 }
 
@@ -290,6 +292,7 @@ static void lp_set(bcnn_net *net, int section_idx, layer_param *lp, const char *
     else if (!strcmp(name, "window") || !strcmp(name, "window_size")) lp->window = atoi(val);
     else if (!strcmp(name, "shift")) lp->shift = atoi(val);
     else if (!strcmp(name, "rel_bias")) lp->rel_bias = atoi(val);
+    else if (!strcmp(name, "norm")) lp->norm = atoi(val);
     else if (!strcmp(name, "ignore_label")) lp->ignore_label = atoi(val);
     else if (!strcmp(name, "normalize")) {
         if (!strcmp(val, "none")) lp->loss_norm = (int)BCNN_LOSS_NORM_NONE;
@@ -332,6 +335,7 @@ static void lp_set(bcnn_net *net, int section_idx, layer_param *lp, const char *
         else if (!strcmp(val, "hard_swish") || !strcmp(val, "hardswish") || !strcmp(val, "hswish")) lp->a = BCNN_ACT_HARD_SWISH;
         else if (!strcmp(val, "swish") || !strcmp(val, "silu")) lp->a = BCNN_ACT_SWISH;
         else if (!strcmp(val, "mish")) lp->a = BCNN_ACT_MISH;
+        else if (!strcmp(val, "gelu")) lp->a = BCNN_ACT_GELU;
         else {
             bcnn_log(net->log_ctx, BCNN_LOG_WARNING, "Unknown activation type %s, going with ReLU\n", val);
             lp->a = BCNN_ACT_RELU;
@@ -394,7 +398,7 @@ static int is_any(const char *name, const char *a, const char *b, const char *c,
     return !strcmp(name, a) || (b && !strcmp(name, b)) || (c && !strcmp(name, c)) || (d && !strcmp(name, d));
 }
 
-/* A section with a fused activation that asks for hard-swish, swish or mish -- whose derivative needs the layer's output
+/* A section with a fused activation that asks for hard-swish, swish, mish or gelu -- whose derivative needs the layer's output
  * BEFORE the activation, which a fused layer does not keep -- is built as the layer with no activation plus the in-place
  * activation node on its output. The section still stands for that output (Darknet's lid chain). */
 static bcnn_activation fused_act(const layer_param *lp) { return bcnn_act_needs_input(lp->a) ? BCNN_ACT_NONE : lp->a; }
@@ -509,6 +513,21 @@ static bcnn_status add_layer(bcnn_net *net, const char *name, layer_param *lp) {
         BCNN_CHECK_AND_LOG(net->log_ctx, lp->a == BCNN_ACT_NONE, BCNN_INVALID_PARAMETER,
                            "Channel-norm layer %s: only activation=linear is supported; add an [activation] section\n", dst);
         return bcnn_add_channel_norm_layer(net, lp->eps, src, dst);
+    }
+    if (is_any(name, "[patch_merging]", "[patchmerge]", "[space_to_depth]", "[focus]")) {
+        /* 2x2 neighbours to the channels; the first two names norm over the 4C channels unless norm=0, the last two never */
+        BCNN_CHECK_AND_LOG(net->log_ctx, lp->a == BCNN_ACT_NONE, BCNN_INVALID_PARAMETER,
+                           "Patch-merging layer %s: only activation=linear is supported; add an [activation] section\n", dst);
+        const int norm = is_any(name, "[patch_merging]", "[patchmerge]", NULL, NULL) && lp->norm;
+        return bcnn_add_patch_merging_layer(net, norm, lp->eps, src, dst);
+    }
+    if (is_any(name, "[residual]", "[add]", NULL, NULL)) {
+        /* a + b over the whole batch; [eltwise] / [shortcut] above keep the reference's image-0 quirk */
+        BCNN_CHECK_AND_LOG(net->log_ctx, lp->num_srcs >= 2, BCNN_INVALID_PARAMETER,
+                           "Residual layer needs two sources (src=a,b)\n");
+        BCNN_CHECK_AND_LOG(net->log_ctx, lp->a == BCNN_ACT_NONE, BCNN_INVALID_PARAMETER,
+                           "Residual layer %s: only activation=linear is supported; add an [activation] section\n", dst);
+        return bcnn_add_residual_layer(net, lp->src_id[0], lp->src_id[1], dst);
     }
     if (is_any(name, "[attention]", "[self_attention]", NULL, NULL)) {
         /* src=q,k,v; a single src=x is self-attention off one tensor. Without scale= the builder's default, 1 / sqrt(d) */

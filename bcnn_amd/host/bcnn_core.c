@@ -416,7 +416,8 @@ static void mark_dead_grad_fills(bcnn_net *net) {
         if (uses == 1 && (nd->type == BCNN_LAYER_MAXPOOL || nd->type == BCNN_LAYER_DEPTHWISE_CONV2D ||
                           nd->type == BCNN_LAYER_LRN || nd->type == BCNN_LAYER_POOL2D ||
                           nd->type == BCNN_LAYER_GROUPNORM || nd->type == BCNN_LAYER_INTERP ||
-                          nd->type == BCNN_LAYER_CHANNEL_NORM ||
+                          nd->type == BCNN_LAYER_CHANNEL_NORM || nd->type == BCNN_LAYER_PATCH_MERGING ||
+                          nd->type == BCNN_LAYER_RESIDUAL ||
                           nd->type == BCNN_LAYER_SOFTMAX_LOSS || nd->type == BCNN_LAYER_DILATED_DEPTHWISE_CONV2D)) {
             /* max-pooling's gather, the depthwise data gradient (a gather too: one thread owns a dx element,
              * bcnn_depthwise_conv_layer.c:432-547 accumulates onto the zero fill), LRN's (one lane per column), the
@@ -424,7 +425,8 @@ static void mark_dead_grad_fills(bcnn_net *net) {
              * thread owns a dx element), the bilinear interpolation's gather, whose overwrite form also writes the
              * elements a downsampling skips, and the softmax loss, whose overwrite form writes +0.0 on the pixels that are
              * not valid, and the dilated depthwise data gradient, a gather like the depthwise one whose overwrite form also
-             * writes the elements no tap reaches, and channel-norm's sweep (one thread owns a dx element) */
+             * writes the elements no tap reaches, and channel-norm's sweep (one thread owns a dx element), patch merging's (every
+             * source element has one place in dst) and the first operand of the residual add */
             hc->grad_fill_dead[t] = 2;
             continue;
         }
@@ -559,6 +561,10 @@ static bcnn_status node_reserve_buffers(const bcnn_node *nd, const bcnn_tensor *
         elems = 2 * (size_t)d->n * (size_t)d->h * (size_t)d->w;
         return RESERVE(bcnn_channel_norm_param, stats_gpu, stats_capacity);
     }
+    if (nd->type == BCNN_LAYER_PATCH_MERGING) { /* likewise, of d's positions (none without norm: the buffer is null) */
+        elems = 2 * (size_t)d->n * (size_t)d->h * (size_t)d->w;
+        return RESERVE(bcnn_patch_merging_param, stats_gpu, stats_capacity);
+    }
     if (nd->type == BCNN_LAYER_ATTENTION) { /* the log-sum-exp of d's n * heads * h * w queries */
         elems = bcnn_hip_attention_lse_size(d->n, ((const bcnn_attention_param *)nd->param)->num_heads, d->h * d->w);
         BCNN_CHECK_STATUS(RESERVE(bcnn_attention_param, lse_gpu, lse_capacity));
@@ -604,6 +610,11 @@ static int node_dst_shape(const bcnn_node *nd, const bcnn_tensor *s, bcnn_tensor
         oc = ((const bcnn_attention_param *)nd->param)->out_channels;
     } else if (nd->type == BCNN_LAYER_WINDOW_ATTENTION) {
         oc = ((const bcnn_window_attention_param *)nd->param)->out_channels;
+    } else if (nd->type == BCNN_LAYER_PATCH_MERGING) { /* whole 2x2 blocks only */
+        if (bcnn_hip_patch_merge_path(s->n, s->c, s->h, s->w) < 0) return 0;
+        oc = 4 * s->c;
+        oh = s->h / 2;
+        ow = s->w / 2;
     }
     bcnn_tensor_set_shape(d, s->n, oc, oh, ow, 1);
     return 1;
@@ -635,8 +646,8 @@ static bcnn_status resize_plan(bcnn_net *net, int w, int h, int c, int need_real
         const bcnn_tensor *s = &plan[nd->src[0]];
         bcnn_tensor *d = &plan[nd->dst[0]];
         BCNN_CHECK_AND_LOG(net->log_ctx, keeps_producer_shape(nd) || node_dst_shape(nd, s, d), BCNN_INVALID_PARAMETER,
-                           "bcnn_resize_net: node %d refuses a %d x %d source (a pooling window larger than the padded tensor, or an "
-                           "interpolation extent out of range)\n", i, s->w, s->h);
+                           "bcnn_resize_net: node %d refuses a %d x %d source (a pooling window larger than the padded tensor, an "
+                           "interpolation extent out of range, or an odd extent before a patch-merging node)\n", i, s->w, s->h);
         BCNN_CHECK_AND_LOG(net->log_ctx, need_realloc || node_reserve_buffers(nd, d, 0) == BCNN_SUCCESS,
                            BCNN_INVALID_PARAMETER,
                            "bcnn_resize_net: node %d keeps a buffer for the backward pass that is smaller than the new shape; "
@@ -658,6 +669,11 @@ static bcnn_status resize_plan(bcnn_net *net, int w, int h, int c, int need_real
                            nd->type != BCNN_LAYER_CHANNEL_NORM || (long long)d->n * d->c * d->h * d->w < 0x7fffffffLL,
                            BCNN_INVALID_PARAMETER, "bcnn_resize_net: the tensors of channel-norm node %d would reach 2^31 elements\n",
                            i);
+        if (nd->type == BCNN_LAYER_RESIDUAL) { /* both operands must still have one shape */
+            const bcnn_tensor *b = &plan[nd->src[1]];
+            BCNN_CHECK_AND_LOG(net->log_ctx, s->n == b->n && s->c == b->c && s->h == b->h && s->w == b->w, BCNN_INVALID_PARAMETER,
+                               "bcnn_resize_net: the operands of residual node %d would differ in shape\n", i);
+        }
         /* the class-index label map of a softmax-loss node follows as [n][1][h][w] */
         BCNN_CHECK_AND_LOG(net->log_ctx,
                            nd->type != BCNN_LAYER_SOFTMAX_LOSS || need_realloc ||
@@ -1222,6 +1238,8 @@ void *bcnn_get_node_state(bcnn_net *net, int node, int which) {
         return which == 0 ? (void *)((bcnn_groupnorm_param *)nd->param)->stats_gpu : NULL;
     if (nd->type == BCNN_LAYER_CHANNEL_NORM) /* mean [N * H * W] then rstd [N * H * W] of the last forward; NULL in a PREDICT-built net */
         return which == 0 ? (void *)((bcnn_channel_norm_param *)nd->param)->stats_gpu : NULL;
+    if (nd->type == BCNN_LAYER_PATCH_MERGING) /* mean then rstd, [N * H/2 * W/2] each; NULL without norm or PREDICT-built */
+        return which == 0 ? (void *)((bcnn_patch_merging_param *)nd->param)->stats_gpu : NULL;
     if (nd->type == BCNN_LAYER_ATTENTION) /* the log-sum-exp [N][heads][Lq] of the last forward; NULL in a PREDICT-built net */
         return which == 0 ? (void *)((bcnn_attention_param *)nd->param)->lse_gpu : NULL;
     if (nd->type == BCNN_LAYER_ACTIVATION) /* hard-swish / swish / mish: the input the last TRAIN forward kept */

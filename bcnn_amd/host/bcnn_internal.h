@@ -298,14 +298,15 @@ static inline const char *bcnn_act2str(bcnn_activation a) {
         case BCNN_ACT_HARD_SWISH: return "Hard-Swish";
         case BCNN_ACT_SWISH: return "Swish";
         case BCNN_ACT_MISH: return "Mish";
+        case BCNN_ACT_GELU: return "GELU";
         default: return "None";
     }
 }
 
-/* hard-swish, swish, mish: the derivative is no function of the output, so only the stand-alone activation node (which
+/* hard-swish, swish, mish, gelu: the derivative is no function of the output, so only the stand-alone activation node (which
  * keeps its input) takes them */
 static inline int bcnn_act_needs_input(bcnn_activation a) {
-    return a == BCNN_ACT_HARD_SWISH || a == BCNN_ACT_SWISH || a == BCNN_ACT_MISH;
+    return a == BCNN_ACT_HARD_SWISH || a == BCNN_ACT_SWISH || a == BCNN_ACT_MISH || a == BCNN_ACT_GELU;
 }
 /* the refusal every builder with a fused activation starts with; nothing has been added to the net at that point */
 #define BCNN_REFUSE_INPUT_ACTIVATION(net, a, layer)                                                                        \
@@ -462,6 +463,17 @@ typedef struct bcnn_window_attention_param {
     float *adam_m_gpu, *adam_v_gpu; /* moments of the table, allocated by the first Adam step */
 #endif
 } bcnn_window_attention_param;
+
+/* patch merging (bcnn_add_patch_merging_layer; no reference counterpart): with norm src[1] = scales, src[2] = b */
+typedef struct bcnn_patch_merging_param {
+    int norm;
+    float eps;
+#ifdef BCNN_USE_HIP
+    float *stats_gpu;       /* norm, nets built in TRAIN / VALID mode: mean [N * H/2 * W/2] then rstd of the last forward */
+    size_t stats_capacity;  /* floats allocated (bcnn_reserve_device) */
+    float *adam_m_gpu, *adam_v_gpu; /* moments of the scales, allocated by the first Adam step */
+#endif
+} bcnn_patch_merging_param;
 
 /* multi-head attention (bcnn_add_attention_layer; no reference counterpart): src[0] = q, src[1] = k, src[2] = v */
 #define BCNN_ATTENTION_MAX_HEAD_DIM 128 /* channels of one head of q / k and of v (attention.hip) */
@@ -701,6 +713,12 @@ void bcnn_release_param_window_attention_layer(bcnn_node *node);
  * window, shift, head depth, 2^31); else a line for the log in `why` */
 int bcnn_window_attention_fits(const bcnn_window_attention_param *p, const bcnn_tensor *q, const bcnn_tensor *k,
                                const bcnn_tensor *v, char *why, size_t why_size);
+void bcnn_forward_patch_merging_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_backward_patch_merging_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_update_patch_merging_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_release_param_patch_merging_layer(bcnn_node *node);
+void bcnn_forward_residual_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_backward_residual_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_forward_attention_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_attention_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_attention_layer(bcnn_node *node);

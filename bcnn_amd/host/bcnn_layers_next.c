@@ -113,6 +113,52 @@ void bcnn_backward_eltwise_layer(bcnn_net *net, bcnn_node *node) {
 }
 
 /* ================================================================================================
+ * residual add: dst = src1 + src2 for two tensors of one shape, every image. No reference counterpart: the eltwise
+ * node above keeps the reference's quirk 5 (the second operand reaches image 0 only), this node is what x + f(x)
+ * needs at batch sizes above 1. The operands keep the order they were named in; no activation; its own layer type,
+ * so bcnn_link_conv_eltwise never pairs it with a convolution. The kernels are the eltwise node's, with the operand
+ * count b_count the whole tensor.
+ * ============================================================================================== */
+bcnn_status bcnn_add_residual_layer(bcnn_net *net, const char *src_id1, const char *src_id2, const char *dst_id) {
+    const int i1 = src_id1 ? bcnn_net_find_tensor(net, src_id1) : -1, i2 = src_id2 ? bcnn_net_find_tensor(net, src_id2) : -1;
+    BCNN_CHECK_AND_LOG(net->log_ctx, i1 >= 0, BCNN_INVALID_PARAMETER, "Residual layer: invalid input node name %s\n",
+                       src_id1 ? src_id1 : "(null)");
+    BCNN_CHECK_AND_LOG(net->log_ctx, i2 >= 0, BCNN_INVALID_PARAMETER, "Residual layer: invalid input node name %s\n",
+                       src_id2 ? src_id2 : "(null)");
+    BCNN_CHECK_AND_LOG(net->log_ctx, i1 != i2, BCNN_INVALID_PARAMETER,
+                       "Residual layer %s: both operands are tensor %s (scale it instead)\n", dst_id, src_id1);
+    const bcnn_tensor a = net->tensors[i1], b = net->tensors[i2];
+    BCNN_CHECK_AND_LOG(net->log_ctx, a.n == b.n && a.c == b.c && a.h == b.h && a.w == b.w, BCNN_INVALID_PARAMETER,
+                       "Residual layer %s: tensor %s is %d x %d x %d x %d and tensor %s is %d x %d x %d x %d\n", dst_id, src_id1,
+                       a.n, a.c, a.h, a.w, src_id2, b.n, b.c, b.h, b.w);
+    bcnn_node node = {0};
+    BCNN_CHECK_STATUS(bcnn_node_add_input(net, &node, i1));
+    BCNN_CHECK_STATUS(bcnn_node_add_input(net, &node, i2));
+    node.type = BCNN_LAYER_RESIDUAL;
+    node.forward = bcnn_forward_residual_layer;
+    node.backward = bcnn_backward_residual_layer;
+    BCNN_CHECK_STATUS(bcnn_node_new_output(net, &node, a.n, a.c, a.h, a.w, dst_id));
+    BCNN_CHECK_STATUS(bcnn_net_add_node(net, node));
+    BCNN_INFO(net->log_ctx, "[Residual] %-8s + %-8s -> %-8s (%4d x%4d x%4d)\n", a.name, b.name, dst_id, a.w, a.h, a.c);
+    return BCNN_SUCCESS;
+}
+
+void bcnn_forward_residual_layer(bcnn_net *net, bcnn_node *node) {
+    const bcnn_tensor *a = &net->tensors[node->src[0]], *b = &net->tensors[node->src[1]];
+    bcnn_tensor *y = &net->tensors[node->dst[0]];
+    const size_t sz = (size_t)bcnn_tensor_size(y);
+    bcnn_hip_eltwise_forward(a->data_gpu, b->data_gpu, y->data_gpu, sz, sz, (int)BCNN_ACT_NONE);
+}
+
+void bcnn_backward_residual_layer(bcnn_net *net, bcnn_node *node) {
+    bcnn_tensor *a = &net->tensors[node->src[0]], *b = &net->tensors[node->src[1]], *y = &net->tensors[node->dst[0]];
+    const size_t sz = (size_t)bcnn_tensor_size(y);
+    if (!y->grad_data_gpu) return; /* PREDICT-built */
+    bcnn_hip_eltwise_backward(y->data_gpu, y->grad_data_gpu, a->grad_data_gpu, b->grad_data_gpu, sz, sz, (int)BCNN_ACT_NONE,
+                              bcnn_grad_sole_writer(net, node->src[0]));
+}
+
+/* ================================================================================================
  * full-connected (+ fused activation): y[B x P] = x[B x S] * W[P x S]^T + b
  * ============================================================================================== */
 bcnn_status bcnn_add_fullc_layer(bcnn_net *net, int output_size, bcnn_filler_type init, bcnn_activation activation,

@@ -14,8 +14,8 @@ from . import _lib
 ACT = dict(none=0, tanh=1, relu=2, ramp=3, softplus=4, lrelu=5, abs=6, clamp=7, prelu=8, logistic=9)
 # The appended activations (no reference counterpart), and every name. ACT itself stays the reference's ten: tests iterate
 # over it as "every activation the reference has". relu6 / hard_sigmoid go wherever an `act` argument is taken; hard_swish,
-# swish and mish through activation_forward[_keep] / activation_backward_from_input only.
-ACT_APPENDED = dict(relu6=10, hard_sigmoid=11, hard_swish=12, swish=13, mish=14)
+# swish, mish and gelu through activation_forward[_keep] / activation_backward_from_input only.
+ACT_APPENDED = dict(relu6=10, hard_sigmoid=11, hard_swish=12, swish=13, mish=14, gelu=15)
 ACT_ALL = dict(ACT, **ACT_APPENDED)
 MODE_PREDICT, MODE_TRAIN, MODE_VALID = 0, 1, 2
 
@@ -516,13 +516,13 @@ def activation_forward(x, act, slopes=None, spatial=1, channels=1):
 
 def activation_forward_keep(x, x_saved, act):
     """bcnn_hip_activation_forward_keep: x = act(x) in place and, unless x_saved is None, x_saved = the input. The forward
-    of hard_swish / swish / mish, whose backward (activation_backward_from_input) needs the input."""
+    of hard_swish / swish / mish / gelu, whose backward (activation_backward_from_input) needs the input."""
     assert x_saved is None or x_saved.numel() == x.numel()
     _lib.load().bcnn_hip_activation_forward_keep(_f32(x), _f32(x_saved), x.numel(), act)
 
 
 def activation_backward_from_input(x_saved, dx, act):
-    """bcnn_hip_activation_backward_from_input: dx *= act'(x_saved) in place; hard_swish / swish / mish only"""
+    """bcnn_hip_activation_backward_from_input: dx *= act'(x_saved) in place; hard_swish / swish / mish / gelu only"""
     assert x_saved.numel() == dx.numel()
     _lib.load().bcnn_hip_activation_backward_from_input(_f32(x_saved), _f32(dx), dx.numel(), act)
 
@@ -608,6 +608,46 @@ def channel_norm_backward(x, scales, mean, rstd, dy, dx, dscales, db, overwrite=
     args = _lib.ChannelNormBwdArgs(_f32(x), _f32(scales), _f32(mean), _f32(rstd), _f32(dy), _f32(dx), _f32(dscales), _f32(db),
                                    n, c, h * w, 1 if overwrite else 0)
     _lib.load().bcnn_hip_channel_norm_backward(_C.byref(args))
+
+
+PATCH_MERGE_PATHS = ("column", "split", "stream")
+
+
+def patch_merge_path(n, c, h, w):
+    """bcnn_hip_patch_merge_path: the kernel family of the source shape, 0 column, 1 split, 2 stream (PATCH_MERGE_PATHS);
+    -1 for a refused one (an odd h or w, an empty tensor, 2^31 elements or more)"""
+    return int(_lib.load().bcnn_hip_patch_merge_path(n, c, h, w))
+
+
+def patch_merge_limits():
+    """the largest C of every path but the last, read off bcnn_hip_patch_merge_path: (column limit, split limit)"""
+    paths = [patch_merge_path(1, c, 2, 2) for c in range(1, 4097)]
+    return tuple(max(c + 1 for c, p in enumerate(paths) if p == k) for k in range(len(PATCH_MERGE_PATHS) - 1))
+
+
+def patch_merge_forward(x, scales, b, y, mean, rstd, eps=1e-5):
+    """bcnn_hip_patch_merge_forward: y [N,4C,H/2,W/2] from x [N,C,H,W], output channel (2 dx + dy) C + c from
+    x[n, c, 2 oy + dy, 2 ox + dx]; with scales and b ([4C]) every output position is normalised over its 4C values in the
+    same launch, mean and rstd ([N * H/2 * W/2]) receive the statistics or are both None. scales None: the rearrangement"""
+    n, c, h, w = x.shape
+    assert y.shape == (n, 4 * c, h // 2, w // 2) and (scales is None) == (b is None)
+    assert scales is None or (scales.numel() == 4 * c and b.numel() == 4 * c)
+    rows = n * (h // 2) * (w // 2)
+    assert (mean is None) == (rstd is None) and (mean is None or (mean.numel() == rows and rstd.numel() == rows))
+    _lib.load().bcnn_hip_patch_merge_forward(_f32(x), _f32(scales), _f32(b), _f32(y), _f32(mean), _f32(rstd), n, c, h, w, eps)
+
+
+def patch_merge_backward(x, scales, mean, rstd, dy, dx, dscales, db, overwrite=False):
+    """bcnn_hip_patch_merge_backward from the stored mean and rstd: dx = (overwrite) or += the data gradient at the place
+    each value came from, dscales += sum dy * xh, db += sum dy; each of dx, dscales, db may be None. scales None (x, mean,
+    rstd may be None too): the rearrangement's backward"""
+    n, c4, oh, ow = dy.shape
+    c, h, w = c4 // 4, 2 * oh, 2 * ow
+    assert c4 == 4 * c and (x is None or x.shape == (n, c, h, w)) and (dx is None or dx.shape == (n, c, h, w))
+    assert scales is None or (x is not None and scales.numel() == c4 and mean.numel() == n * oh * ow == rstd.numel())
+    assert (dscales is None or dscales.numel() == c4) and (db is None or db.numel() == c4)
+    _lib.load().bcnn_hip_patch_merge_backward(_f32(x), _f32(scales), _f32(mean), _f32(rstd), _f32(dy), _f32(dx), _f32(dscales),
+                                              _f32(db), n, c, h, w, 1 if overwrite else 0)
 
 
 def _attention_dims(q, k, v, heads):

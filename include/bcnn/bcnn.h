@@ -82,6 +82,10 @@ typedef enum {
 #define BCNN_LAYER_CHANNEL_NORM ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 8))
 /* The layer type of bcnn_add_window_attention_layer, likewise a constant behind the enumerator list. */
 #define BCNN_LAYER_WINDOW_ATTENTION ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 9))
+/* The layer type of bcnn_add_patch_merging_layer, likewise a constant behind the enumerator list. */
+#define BCNN_LAYER_PATCH_MERGING ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 10))
+/* The layer type of bcnn_add_residual_layer, likewise a constant behind the enumerator list. */
+#define BCNN_LAYER_RESIDUAL ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 11))
 
 typedef enum {
     BCNN_ACT_NONE, BCNN_ACT_TANH, BCNN_ACT_RELU, BCNN_ACT_RAMP, BCNN_ACT_SOFTPLUS,
@@ -89,11 +93,12 @@ typedef enum {
     BCNN_ACT_ABS, BCNN_ACT_CLAMP, BCNN_ACT_PRELU, BCNN_ACT_LOGISTIC,
     /* appended, without a reference counterpart (the values above are the reference's).
      * RELU6 = min(max(x, 0), 6) and HARD_SIGMOID = min(max(x + 3, 0), 6) / 6 (torch's hardsigmoid) are accepted wherever
-     * an activation is taken. HARD_SWISH = x min(max(x + 3, 0), 6) / 6, SWISH = x sigmoid(x) and MISH = x tanh(softplus(x))
+     * an activation is taken. HARD_SWISH = x min(max(x + 3, 0), 6) / 6, SWISH = x sigmoid(x), MISH = x tanh(softplus(x))
+     * and GELU = x Phi(x) = 0.5 x (1 + erf(x / sqrt 2)) (the exact form, torch's default; the tanh approximation is not built)
      * have a derivative that is no function of the output: they exist in the stand-alone activation node
      * (bcnn_add_activation_layer) only, and every builder that takes a fused activation refuses them with
      * BCNN_INVALID_PARAMETER. */
-    BCNN_ACT_RELU6, BCNN_ACT_HARD_SIGMOID, BCNN_ACT_HARD_SWISH, BCNN_ACT_SWISH, BCNN_ACT_MISH
+    BCNN_ACT_RELU6, BCNN_ACT_HARD_SIGMOID, BCNN_ACT_HARD_SWISH, BCNN_ACT_SWISH, BCNN_ACT_MISH, BCNN_ACT_GELU
 } bcnn_activation;
 
 typedef enum { BCNN_LOSS_EUCLIDEAN, BCNN_LOSS_LIFTED_STRUCT } bcnn_loss;
@@ -382,6 +387,28 @@ BCNN_API bcnn_status bcnn_add_attention_layer(bcnn_net *net, int num_heads, floa
 BCNN_API bcnn_status bcnn_add_concat_layer(bcnn_net *net, int num_src, char *const *src_ids, const char *dst_id);
 BCNN_API bcnn_status bcnn_add_eltwise_layer(bcnn_net *net, bcnn_activation activation, const char *src_id1,
                                             const char *src_id2, const char *dst_id);
+/* New, without a reference counterpart: dst = src1 + src2 for two tensors of identical shape, EVERY image of the batch (the
+ * same-shape path of the eltwise builder above keeps the reference's quirk: its second operand reaches image 0 only, which
+ * is right for parity and wrong for x + f(x) at batch sizes above 1). No activation, no fusion with a convolution before it.
+ * The backward assigns the gradient of src1 when this node is its sole writer and adds otherwise; the gradient of src2 is
+ * added to. Refused with BCNN_INVALID_PARAMETER and a log line, nothing added to the net: an unknown name, different
+ * shapes, src_id1 == src_id2. Follows bcnn_resize_net (a resize after which the two shapes differ is refused). */
+BCNN_API bcnn_status bcnn_add_residual_layer(bcnn_net *net, const char *src_id1, const char *src_id2, const char *dst_id);
+/* New, without a reference counterpart: patch merging, the step between Swin stages (and, with norm == 0, space-to-depth:
+ * YOLOv5's Focus). src is [N,C,H,W] with H and W even, dst [N,4C,H/2,W/2]: output channel k C + c with k = 2 dx + dy takes
+ * src[n, c, 2 oy + dy, 2 ox + dx] -- Swin's cat([x[0::2,0::2], x[1::2,0::2], x[0::2,1::2], x[1::2,1::2]]) order. With
+ * norm != 0 every output position is then normalised over its 4C values (biased variance, eps <= 0 selects 1e-5) and mapped
+ * through the parameters <src>_pm_scales (filled with 1) and <src>_pm_b (0), [1,1,1,4C], trained like a layer's weights and
+ * biases, in the same launch. Swin's bias-free Linear(4C, 2C) is a 1x1 convolution node behind this one. norm == 0 is the
+ * rearrangement alone, bit-exact, without parameters. The same function in TRAIN, VALID and PREDICT mode.
+ *   Model files hold b then scales, 4C floats each (nothing with norm == 0); the Darknet reader skips the node.
+ *   A net built in TRAIN or VALID mode keeps mean and rstd of the last forward, [2][N * H/2 * W/2] floats:
+ *   bcnn_get_node_state(net, node, 0). The backward adds into the source gradient (assigns when it is its sole writer); a
+ *   source without a gradient buffer is skipped.
+ * Refused with BCNN_INVALID_PARAMETER and a log line, nothing added to the net: an unknown src name, an odd H or W (Swin's
+ * zero padding is not built), a tensor of 2^31 elements or more. May be the first node of a net. Follows bcnn_resize_net; a
+ * resize to an odd extent is refused and leaves the net as it was. */
+BCNN_API bcnn_status bcnn_add_patch_merging_layer(bcnn_net *net, int norm, float eps, const char *src_id, const char *dst_id);
 BCNN_API bcnn_status bcnn_add_dropout_layer(bcnn_net *net, float rate, const char *id);
 BCNN_API bcnn_status bcnn_add_upsample_layer(bcnn_net *net, int size, const char *src_id, const char *dst_id);
 /* New, without a reference counterpart: bilinear interpolation of every plane of src to a new extent, with a gradient --

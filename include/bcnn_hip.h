@@ -30,10 +30,11 @@ enum {
     BCNN_HIP_ACT_SOFTPLUS, BCNN_HIP_ACT_LRELU, BCNN_HIP_ACT_ABS, BCNN_HIP_ACT_CLAMP,
     BCNN_HIP_ACT_PRELU, BCNN_HIP_ACT_LOGISTIC,
     /* appended, no reference counterpart. RELU6 / HARD_SIGMOID: derivative from the output, accepted by every `act`
-     * argument (always as a separate pass, like SOFTPLUS). HARD_SWISH / SWISH / MISH: derivative from the INPUT; forward
+     * argument (always as a separate pass, like SOFTPLUS). HARD_SWISH / SWISH / MISH / GELU: derivative from the INPUT; forward
      * through bcnn_hip_activation_forward[_keep], backward through bcnn_hip_activation_backward_from_input only; every
      * other `act` argument handed one of them exits. */
-    BCNN_HIP_ACT_RELU6, BCNN_HIP_ACT_HARD_SIGMOID, BCNN_HIP_ACT_HARD_SWISH, BCNN_HIP_ACT_SWISH, BCNN_HIP_ACT_MISH
+    BCNN_HIP_ACT_RELU6, BCNN_HIP_ACT_HARD_SIGMOID, BCNN_HIP_ACT_HARD_SWISH, BCNN_HIP_ACT_SWISH, BCNN_HIP_ACT_MISH,
+    BCNN_HIP_ACT_GELU /* the exact form x Phi(x) = 0.5 x (1 + erf(x / sqrt 2)), torch's default */
 };
 /* enum bcnn_mode values (inc/bcnn/bcnn.h:105-112) -- passed as int `mode`. */
 enum { BCNN_HIP_MODE_PREDICT = 0, BCNN_HIP_MODE_TRAIN = 1, BCNN_HIP_MODE_VALID = 2 };
@@ -622,6 +623,37 @@ typedef struct bcnn_hip_channel_norm_bwd_args {
 void bcnn_hip_channel_norm_forward(const bcnn_hip_channel_norm_fwd_args *args);
 void bcnn_hip_channel_norm_backward(const bcnn_hip_channel_norm_bwd_args *args);
 int bcnn_hip_channel_norm_path(int n, int c, int hw, int backward);
+
+/* ---------------------------------------------------------------------------------------------
+ * Patch merging (the patch-merging node; patch_merge.hip). No reference counterpart: the 2x2 neighbours of x [n][c][h][w], h
+ * and w even, move to the channels, y [n][4c][h/2][w/2]: output channel k c + ch with k = 2 dx + dy takes
+ * x[n][ch][2 oy + dy][2 ox + dx] -- Swin's cat([x[0::2,0::2], x[1::2,0::2], x[0::2,1::2], x[1::2,1::2]]) and YOLOv5's Focus.
+ *   scales == NULL: the rearrangement alone, bit for bit (b, mean, rstd are not read or written). Otherwise every output
+ *   position q = n (h/2)(w/2) + oy (w/2) + ox is normalised over its m = 4c values in the same launch; scales, b are [4c],
+ *   mean, rstd [n (h/2)(w/2)] and may be NULL (nothing is stored, y has the same bits).
+ *   forward : sums of v and v^2 in double in an order that follows from the shape; mean = s / m, the biased variance
+ *     max(q / m - mean^2, 0), rstd = (float)(1 / sqrt(var + eps)); eps <= 0 selects 1e-5.
+ *     y = ((v - mean) * rstd) * scales[k c + ch] + b[k c + ch], one float32 rounding per operation on the stored float32
+ *     mean and rstd.
+ *   backward: from mean and rstd, as bcnn_hip_channel_norm_backward on the rearranged tensor; dx receives (overwrite_dx != 0)
+ *     or is added the gradient at the place each value came from; dscales[j] += sum_q dy * xh, db[j] += sum_q dy from ONE pass
+ *     over dy and x whatever 4c is: per-workgroup partial rows, added in ascending order in double, the start value one
+ *     float32 addition. Each of dx, dscales, db may be NULL. With scales == NULL (mean, rstd, x unread, dscales and db
+ *     untouched) dx (+)= dy moved back, bit for bit.
+ *   No atomics; two runs give the same bits; a base that is not 8-byte aligned changes the loads and stores, not the bits.
+ *   bcnn_hip_patch_merge_path: the kernel family, from c alone: 0 column (c <= 8, a lane holds the 4c values of a position),
+ *     1 split (c <= 256, the waves of a workgroup split the channels of a 64-position tile and hold it in registers),
+ *     2 stream (two sweeps, the second from cache); -1 for a refused shape (an extent below 1, an odd h or w, 2^31 elements
+ *     or more), on which the two entry points exit. With the dispatch trace on the launches are named
+ *     patch_merge_fwd:<path> / patch_merge_bwd:<path> (path "copy" with scales == NULL) and patch_merge_finalize: forward 1
+ *     launch, backward at most 2.
+ * ------------------------------------------------------------------------------------------- */
+void bcnn_hip_patch_merge_forward(const float *x_d, const float *scales_d, const float *b_d, float *y_d, float *mean_d,
+                                  float *rstd_d, int n, int c, int h, int w, float eps);
+void bcnn_hip_patch_merge_backward(const float *x_d, const float *scales_d, const float *mean_d, const float *rstd_d,
+                                   const float *dy_d, float *dx_d, float *dscales_d, float *db_d, int n, int c, int h, int w,
+                                   int overwrite_dx);
+int bcnn_hip_patch_merge_path(int n, int c, int h, int w);
 
 /* ---------------------------------------------------------------------------------------------
  * Multi-head attention over the positions of a feature map (the attention node; attention.hip). No reference counterpart.
