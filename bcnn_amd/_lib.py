@@ -23,6 +23,16 @@ class ChannelNormBwdArgs(C.Structure):  # bcnn_hip_channel_norm_bwd_args
                [("n", i), ("c", i), ("hw", i), ("overwrite", i)]
 
 
+class PatchExpandFwdArgs(C.Structure):  # bcnn_hip_patch_expand_fwd_args
+    _fields_ = [(k, vp) for k in ("x", "scales", "b", "y", "mean", "rstd")] + \
+               [(k, i) for k in ("n", "c_in", "h", "w", "block", "order")] + [("eps", f)]
+
+
+class PatchExpandBwdArgs(C.Structure):  # bcnn_hip_patch_expand_bwd_args
+    _fields_ = [(k, vp) for k in ("x", "scales", "mean", "rstd", "dy", "dx", "dscales", "db")] + \
+               [(k, i) for k in ("n", "c_in", "h", "w", "block", "order", "overwrite")]
+
+
 class WindowAttnFwdArgs(C.Structure):  # BcnnWindowAttnFwdArgs
     _fields_ = [(k, vp) for k in ("q", "k", "v", "table", "o")] + \
                [(k, i) for k in ("n", "heads", "d", "c", "h", "w", "window", "shift")] + [("scale", f)]
@@ -92,6 +102,9 @@ SIGNATURES = {
     "bcnn_hip_patch_merge_forward": (None, [vp] * 6 + [i, i, i, i, f]),
     "bcnn_hip_patch_merge_backward": (None, [vp] * 8 + [i, i, i, i, i]),
     "bcnn_hip_patch_merge_path": (i, [i, i, i, i]),
+    "bcnn_hip_patch_expand_forward": (None, [vp]),
+    "bcnn_hip_patch_expand_backward": (None, [vp]),
+    "bcnn_hip_patch_expand_path": (i, [i, i, i, i, i]),
     "bcnn_hip_attention_forward": (None, [vp] * 5 + [i] * 6 + [f]),
     "bcnn_hip_attention_backward": (None, [vp] * 9 + [i] * 6 + [f, i, i, i]),
     "bcnn_hip_attention_lse_size": (sz, [i, i, i]),

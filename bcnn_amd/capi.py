@@ -31,6 +31,8 @@ LAYER_ATTENTION = 24
 LAYER_CHANNEL_NORM = 25
 LAYER_WINDOW_ATTENTION = 26
 LAYER_PATCH_MERGING, LAYER_RESIDUAL = 27, 28
+LAYER_PATCH_EXPANDING = 29
+PATCH_EXPAND_BLOCKS, PATCH_EXPAND_CHANNELS = 0, 1
 LOSS_NORM_NONE, LOSS_NORM_VALID, LOSS_NORM_VALID_PER_IMAGE = 0, 1, 2
 LOSS_NORMS = {"none": LOSS_NORM_NONE, "valid": LOSS_NORM_VALID, "valid_per_image": LOSS_NORM_VALID_PER_IMAGE}
 
@@ -162,6 +164,7 @@ def lib():
         "bcnn_add_channel_norm_layer": (i, [vp, f, cp, cp]),
         "bcnn_add_patch_merging_layer": (i, [vp, i, f, cp, cp]),
         "bcnn_add_residual_layer": (i, [vp, cp, cp, cp]),
+        "bcnn_add_patch_expanding_layer": (i, [vp, i, i, i, f, cp, cp]),
         "bcnn_add_window_attention_layer": (i, [vp, i, i, i, i, f, cp, cp, cp, cp]),
         "bcnn_add_eltwise_layer": (i, [vp, i, cp, cp, cp]), "bcnn_add_fullc_layer": (i, [vp, i, i, i, i, cp, cp]),
         "bcnn_add_softmax_layer": (i, [vp, cp, cp]), "bcnn_add_cost_layer": (i, [vp, i, i, f, cp, cp, cp]),
@@ -322,6 +325,12 @@ class Net:
         channels of every position (parameters <src>_pm_scales, <src>_pm_b); norm=0 is space-to-depth (YOLOv5's Focus);
         eps <= 0 selects 1e-5"""
         return self._added(self.L.bcnn_add_patch_merging_layer(self.net, norm, eps, src.encode(), dst.encode()))
+
+    def patch_expanding(self, src, dst, block=2, order=PATCH_EXPAND_BLOCKS, norm=1, eps=0.0):
+        """bcnn_add_patch_expanding_layer: [N,p^2 c,H,W] -> [N,c,pH,pW] with block p = 2 or 4; order PATCH_EXPAND_BLOCKS is
+        Swin-UNet's / depth-to-space's, PATCH_EXPAND_CHANNELS torch's PixelShuffle; with norm a layer norm over the c channels
+        of every output position (parameters <src>_pe_scales, <src>_pe_b); eps <= 0 selects 1e-5"""
+        return self._added(self.L.bcnn_add_patch_expanding_layer(self.net, block, order, norm, eps, src.encode(), dst.encode()))
 
     def fullc(self, out, act=ACT_NONE, src="input", dst="fc"):
         return self._added(self.L.bcnn_add_fullc_layer(self.net, out, FILLER_XAVIER, act, 0, src.encode(), dst.encode()))

@@ -196,7 +196,7 @@ typedef struct {
     int has_size, has_stride, pool_pad, pool_avg, ceil_mode, count_include_pad;
     int has_from; /* Darknet `from=`: src_id[0] is the previous section, src_id[1] the named one */
     int has_groups; /* [groupnorm]: the section wrote groups= (the default of num_groups, 1, belongs to convolutions) */
-    float eps;      /* [groupnorm] / [layernorm] / [instancenorm] / [channelnorm] / [patch_merging]; 0: the builder's default */
+    float eps;      /* [groupnorm] / [layernorm] / [instancenorm] / [channelnorm] / [patch_merging] / [patch_expanding]; 0: the builder's default */
     int dilation;   /* [conv] / [convolutional], [depthwise-conv] / [dw-conv]: > 1 builds the dilated node; default 1 */
     int scale, zoom, out_w, out_h, align_corners; /* [interp] / [bilinear]; scale= may be written stride= (has_stride) */
     /* [softmax_loss] / [softmaxwithloss]: ignore_label (default -1), normalize (a bcnn_loss_norm, -1: a value the section
@@ -206,7 +206,9 @@ typedef struct {
     int heads; /* [attention] / [self_attention]; its scale= is loss_scale's float, read only when the section wrote it */
     int has_scale;
     int window, shift, rel_bias; /* [window_attention] / [swin_attention]; shift defaults to 0, rel_bias to 1 */
-    int norm; /* [patch_merging] / [patchmerge]: the norm over the 4C channels, default 1 */
+    int norm; /* [patch_merging] / [patchmerge], [patch_expanding] / [patchexpand]: the norm over the channels, default 1 */
+    int block, order; /* [patch_expanding] / [patchexpand] / [depth_to_space] / [pixel_shuffle]: block= default 2; order=
+                         blocks | channels, -1: the section's own */
 } layer_param;
 
 static void lp_reset(layer_param *lp) {
@@ -223,6 +225,8 @@ static void lp_reset(layer_param *lp) {
     lp->dilation = 1;
     lp->rel_bias = 1;
     lp->norm = 1;
+    lp->block = 2;
+    lp->order = -1;
     lp->ignore_label = -1; lp->loss_norm = (int)BCNN_LOSS_NORM_VALID_PER_IMAGE; lp->loss_scale = 1.0f;
 }
 
@@ -293,6 +297,9 @@ static void lp_set(bcnn_net *net, int section_idx, layer_param *lp, const char *
     else if (!strcmp(name, "shift")) lp->shift = atoi(val);
     else if (!strcmp(name, "rel_bias")) lp->rel_bias = atoi(val);
     else if (!strcmp(name, "norm")) lp->norm = atoi(val);
+    else if (!strcmp(name, "block")) lp->block = atoi(val);
+    else if (!strcmp(name, "order")) /* an unknown word reaches the builder, which refuses it */
+        lp->order = !strcmp(val, "blocks") ? (int)BCNN_PATCH_EXPAND_BLOCKS : (!strcmp(val, "channels") ? (int)BCNN_PATCH_EXPAND_CHANNELS : 2);
     else if (!strcmp(name, "ignore_label")) lp->ignore_label = atoi(val);
     else if (!strcmp(name, "normalize")) {
         if (!strcmp(val, "none")) lp->loss_norm = (int)BCNN_LOSS_NORM_NONE;
@@ -520,6 +527,16 @@ static bcnn_status add_layer(bcnn_net *net, const char *name, layer_param *lp) {
                            "Patch-merging layer %s: only activation=linear is supported; add an [activation] section\n", dst);
         const int norm = is_any(name, "[patch_merging]", "[patchmerge]", NULL, NULL) && lp->norm;
         return bcnn_add_patch_merging_layer(net, norm, lp->eps, src, dst);
+    }
+    if (is_any(name, "[patch_expanding]", "[patchexpand]", "[depth_to_space]", "[pixel_shuffle]")) {
+        /* channels to block x block positions; the first two names norm over the channels unless norm=0, the last two never;
+         * [pixel_shuffle] reads torch's channel order, the others the block-major one, order= overrides either */
+        BCNN_CHECK_AND_LOG(net->log_ctx, lp->a == BCNN_ACT_NONE, BCNN_INVALID_PARAMETER,
+                           "Patch-expanding layer %s: only activation=linear is supported; add an [activation] section\n", dst);
+        const int norm = is_any(name, "[patch_expanding]", "[patchexpand]", NULL, NULL) && lp->norm;
+        const int order = lp->order >= 0 ? lp->order
+                                         : (!strcmp(name, "[pixel_shuffle]") ? (int)BCNN_PATCH_EXPAND_CHANNELS : (int)BCNN_PATCH_EXPAND_BLOCKS);
+        return bcnn_add_patch_expanding_layer(net, lp->block, (bcnn_patch_expand_order)order, norm, lp->eps, src, dst);
     }
     if (is_any(name, "[residual]", "[add]", NULL, NULL)) {
         /* a + b over the whole batch; [eltwise] / [shortcut] above keep the reference's image-0 quirk */

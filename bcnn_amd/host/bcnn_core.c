@@ -417,6 +417,7 @@ static void mark_dead_grad_fills(bcnn_net *net) {
                           nd->type == BCNN_LAYER_LRN || nd->type == BCNN_LAYER_POOL2D ||
                           nd->type == BCNN_LAYER_GROUPNORM || nd->type == BCNN_LAYER_INTERP ||
                           nd->type == BCNN_LAYER_CHANNEL_NORM || nd->type == BCNN_LAYER_PATCH_MERGING ||
+                          nd->type == BCNN_LAYER_PATCH_EXPANDING ||
                           nd->type == BCNN_LAYER_RESIDUAL ||
                           nd->type == BCNN_LAYER_SOFTMAX_LOSS || nd->type == BCNN_LAYER_DILATED_DEPTHWISE_CONV2D)) {
             /* max-pooling's gather, the depthwise data gradient (a gather too: one thread owns a dx element,
@@ -425,8 +426,8 @@ static void mark_dead_grad_fills(bcnn_net *net) {
              * thread owns a dx element), the bilinear interpolation's gather, whose overwrite form also writes the
              * elements a downsampling skips, and the softmax loss, whose overwrite form writes +0.0 on the pixels that are
              * not valid, and the dilated depthwise data gradient, a gather like the depthwise one whose overwrite form also
-             * writes the elements no tap reaches, and channel-norm's sweep (one thread owns a dx element), patch merging's (every
-             * source element has one place in dst) and the first operand of the residual add */
+             * writes the elements no tap reaches, and channel-norm's sweep (one thread owns a dx element), patch merging's and
+             * patch expanding's (every source element has one place in dst) and the first operand of the residual add */
             hc->grad_fill_dead[t] = 2;
             continue;
         }
@@ -565,6 +566,10 @@ static bcnn_status node_reserve_buffers(const bcnn_node *nd, const bcnn_tensor *
         elems = 2 * (size_t)d->n * (size_t)d->h * (size_t)d->w;
         return RESERVE(bcnn_patch_merging_param, stats_gpu, stats_capacity);
     }
+    if (nd->type == BCNN_LAYER_PATCH_EXPANDING) { /* likewise */
+        elems = 2 * (size_t)d->n * (size_t)d->h * (size_t)d->w;
+        return RESERVE(bcnn_patch_expanding_param, stats_gpu, stats_capacity);
+    }
     if (nd->type == BCNN_LAYER_ATTENTION) { /* the log-sum-exp of d's n * heads * h * w queries */
         elems = bcnn_hip_attention_lse_size(d->n, ((const bcnn_attention_param *)nd->param)->num_heads, d->h * d->w);
         BCNN_CHECK_STATUS(RESERVE(bcnn_attention_param, lse_gpu, lse_capacity));
@@ -615,6 +620,12 @@ static int node_dst_shape(const bcnn_node *nd, const bcnn_tensor *s, bcnn_tensor
         oc = 4 * s->c;
         oh = s->h / 2;
         ow = s->w / 2;
+    } else if (nd->type == BCNN_LAYER_PATCH_EXPANDING) { /* any extent; the 2^31 limit can still refuse */
+        const int p = ((const bcnn_patch_expanding_param *)nd->param)->block;
+        if (bcnn_hip_patch_expand_path(s->n, s->c, s->h, s->w, p) < 0) return 0;
+        oc = s->c / (p * p);
+        oh = s->h * p;
+        ow = s->w * p;
     }
     bcnn_tensor_set_shape(d, s->n, oc, oh, ow, 1);
     return 1;
@@ -647,7 +658,8 @@ static bcnn_status resize_plan(bcnn_net *net, int w, int h, int c, int need_real
         bcnn_tensor *d = &plan[nd->dst[0]];
         BCNN_CHECK_AND_LOG(net->log_ctx, keeps_producer_shape(nd) || node_dst_shape(nd, s, d), BCNN_INVALID_PARAMETER,
                            "bcnn_resize_net: node %d refuses a %d x %d source (a pooling window larger than the padded tensor, an "
-                           "interpolation extent out of range, or an odd extent before a patch-merging node)\n", i, s->w, s->h);
+                           "interpolation extent out of range, an odd extent before a patch-merging node, or 2^31 elements at a patch-expanding "
+                           "node)\n", i, s->w, s->h);
         BCNN_CHECK_AND_LOG(net->log_ctx, need_realloc || node_reserve_buffers(nd, d, 0) == BCNN_SUCCESS,
                            BCNN_INVALID_PARAMETER,
                            "bcnn_resize_net: node %d keeps a buffer for the backward pass that is smaller than the new shape; "
@@ -1240,6 +1252,8 @@ void *bcnn_get_node_state(bcnn_net *net, int node, int which) {
         return which == 0 ? (void *)((bcnn_channel_norm_param *)nd->param)->stats_gpu : NULL;
     if (nd->type == BCNN_LAYER_PATCH_MERGING) /* mean then rstd, [N * H/2 * W/2] each; NULL without norm or PREDICT-built */
         return which == 0 ? (void *)((bcnn_patch_merging_param *)nd->param)->stats_gpu : NULL;
+    if (nd->type == BCNN_LAYER_PATCH_EXPANDING) /* mean then rstd, [N * pH * pW] each; NULL without norm or PREDICT-built */
+        return which == 0 ? (void *)((bcnn_patch_expanding_param *)nd->param)->stats_gpu : NULL;
     if (nd->type == BCNN_LAYER_ATTENTION) /* the log-sum-exp [N][heads][Lq] of the last forward; NULL in a PREDICT-built net */
         return which == 0 ? (void *)((bcnn_attention_param *)nd->param)->lse_gpu : NULL;
     if (nd->type == BCNN_LAYER_ACTIVATION) /* hard-swish / swish / mish: the input the last TRAIN forward kept */

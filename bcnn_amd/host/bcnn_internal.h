@@ -475,6 +475,19 @@ typedef struct bcnn_patch_merging_param {
 #endif
 } bcnn_patch_merging_param;
 
+/* patch expanding (bcnn_add_patch_expanding_layer; no reference counterpart): with norm src[1] = scales, src[2] = b */
+typedef struct bcnn_patch_expanding_param {
+    int block; /* 2 or 4 */
+    int order; /* a bcnn_patch_expand_order */
+    int norm;
+    float eps;
+#ifdef BCNN_USE_HIP
+    float *stats_gpu;       /* norm, nets built in TRAIN / VALID mode: mean [N * pH * pW] then rstd of the last forward */
+    size_t stats_capacity;  /* floats allocated (bcnn_reserve_device) */
+    float *adam_m_gpu, *adam_v_gpu; /* moments of the scales, allocated by the first Adam step */
+#endif
+} bcnn_patch_expanding_param;
+
 /* multi-head attention (bcnn_add_attention_layer; no reference counterpart): src[0] = q, src[1] = k, src[2] = v */
 #define BCNN_ATTENTION_MAX_HEAD_DIM 128 /* channels of one head of q / k and of v (attention.hip) */
 typedef struct bcnn_attention_param {
@@ -717,6 +730,10 @@ void bcnn_forward_patch_merging_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_patch_merging_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_update_patch_merging_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_patch_merging_layer(bcnn_node *node);
+void bcnn_forward_patch_expanding_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_backward_patch_expanding_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_update_patch_expanding_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_release_param_patch_expanding_layer(bcnn_node *node);
 void bcnn_forward_residual_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_backward_residual_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_forward_attention_layer(bcnn_net *net, bcnn_node *node);

@@ -65,8 +65,8 @@ bcnn_status bcnn_save_weights(bcnn_net *net, const char *filename) {
             const int c = net->tensors[nd->dst[0]].c;
             for (int k = 1; ok && k <= 4; ++k) ok = put(fp, &net->tensors[nd->src[k]], c);
         } else if (nd->type == BCNN_LAYER_GROUPNORM || nd->type == BCNN_LAYER_CHANNEL_NORM ||
-                   (nd->type == BCNN_LAYER_PATCH_MERGING && nd->num_src == 3)) {
-            /* biases, then scales, like a layer's biases and weights (a patch-merging node without norm has neither) */
+                   ((nd->type == BCNN_LAYER_PATCH_MERGING || nd->type == BCNN_LAYER_PATCH_EXPANDING) && nd->num_src == 3)) {
+            /* biases, then scales, like a layer's biases and weights (a patch-merging or patch-expanding node without norm has neither) */
             const int c = net->tensors[nd->dst[0]].c;
             ok = put(fp, &net->tensors[nd->src[2]], c) && put(fp, &net->tensors[nd->src[1]], c);
         } else if (nd->type == BCNN_LAYER_WINDOW_ATTENTION && nd->num_src > 3) { /* the relative position bias table */
@@ -149,7 +149,7 @@ static bcnn_status load_batchnorm(bcnn_net *net, bcnn_node *nd, FILE *fp, int fo
     return BCNN_SUCCESS;
 }
 
-/* the group-norm, channel-norm and patch-merging nodes: biases then scales, one float per channel of dst each; Darknet has no such layer and its files hold nothing for it */
+/* the group-norm, channel-norm, patch-merging and patch-expanding nodes: biases then scales, one float per channel of dst each; Darknet has no such layer and its files hold nothing for it */
 static bcnn_status load_groupnorm(bcnn_net *net, bcnn_node *nd, FILE *fp, int format) {
     if (format != 0) return BCNN_SUCCESS;
     bcnn_tensor *s = &net->tensors[nd->src[1]], *b = &net->tensors[nd->src[2]];
@@ -263,7 +263,7 @@ bcnn_status bcnn_load_weights(bcnn_net *net, const char *filename) {
         } else if (nd->type == BCNN_LAYER_FULL_CONNECTED) {
             st = load_fullc(net, nd, fp, need_transpose);
         } else if (nd->type == BCNN_LAYER_GROUPNORM || nd->type == BCNN_LAYER_CHANNEL_NORM ||
-                   (nd->type == BCNN_LAYER_PATCH_MERGING && nd->num_src == 3)) {
+                   ((nd->type == BCNN_LAYER_PATCH_MERGING || nd->type == BCNN_LAYER_PATCH_EXPANDING) && nd->num_src == 3)) {
             st = load_groupnorm(net, nd, fp, format);
         } else if (nd->type == BCNN_LAYER_WINDOW_ATTENTION && nd->num_src > 3) {
             st = load_relbias(net, nd, fp, format);

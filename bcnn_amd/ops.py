@@ -650,6 +650,59 @@ def patch_merge_backward(x, scales, mean, rstd, dy, dx, dscales, db, overwrite=F
                                               _f32(db), n, c, h, w, 1 if overwrite else 0)
 
 
+PATCH_EXPAND_PATHS = ("column", "split", "stream")
+PATCH_EXPAND_ORDERS = dict(blocks=0, channels=1)
+# what the backward of patch_expand.hip keeps per workgroup, at either block: x and dy of a unit in registers up to this c,
+# the per-channel accumulators in LDS up to that one
+PATCH_EXPAND_BWD_HOLD_MAX_C, PATCH_EXPAND_BWD_LDS_MAX_C = 32, 1024
+
+
+def patch_expand_path(n, c_in, h, w, block):
+    """bcnn_hip_patch_expand_path: the kernel family of the source shape [n, c_in, h, w], 0 column, 1 split, 2 stream
+    (PATCH_EXPAND_PATHS); -1 for a refused one (an extent below 1, a block other than 2 or 4, a c_in that is no multiple of
+    block^2, 2^31 elements or more)"""
+    return int(_lib.load().bcnn_hip_patch_expand_path(n, c_in, h, w, block))
+
+
+def patch_expand_limits(block):
+    """the largest output channel count c of every path but the last, read off bcnn_hip_patch_expand_path: (column limit,
+    split limit)"""
+    paths = [patch_expand_path(1, c * block * block, 1, 1, block) for c in range(1, 2049)]
+    return tuple(max(c + 1 for c, p in enumerate(paths) if p == k) for k in range(len(PATCH_EXPAND_PATHS) - 1))
+
+
+def patch_expand_forward(x, scales, b, y, mean, rstd, block=2, order="blocks", eps=1e-5):
+    """bcnn_hip_patch_expand_forward: y [N,c,pH,pW] from x [N,p^2 c,H,W], y[n, ch, p h + p1, p w + p2] from source plane
+    (p1 p + p2) c + ch (order "blocks": Swin-UNet, depth-to-space) or ch p^2 + p1 p + p2 ("channels": PixelShuffle); with
+    scales and b ([c]) every output position is normalised over its c values in the same launch, mean and rstd
+    ([N * pH * pW]) receive the statistics or are both None. scales None: the rearrangement. An order that is no key of
+    PATCH_EXPAND_ORDERS is handed on as it is (the entry point refuses an unknown one and does nothing)"""
+    n, c_in, h, w = x.shape
+    c = c_in // (block * block)
+    assert y.shape == (n, c, block * h, block * w) and (scales is None) == (b is None)
+    assert scales is None or (scales.numel() == c and b.numel() == c)
+    rows = n * block * h * block * w
+    assert (mean is None) == (rstd is None) and (mean is None or (mean.numel() == rows and rstd.numel() == rows))
+    args = _lib.PatchExpandFwdArgs(_f32(x), _f32(scales), _f32(b), _f32(y), _f32(mean), _f32(rstd), n, c_in, h, w, block,
+                                   PATCH_EXPAND_ORDERS.get(order, order), eps)
+    _lib.load().bcnn_hip_patch_expand_forward(_C.byref(args))
+
+
+def patch_expand_backward(x, scales, mean, rstd, dy, dx, dscales, db, block=2, order="blocks", overwrite=False):
+    """bcnn_hip_patch_expand_backward from the stored mean and rstd: dx = (overwrite) or += the data gradient at the place
+    each value came from, dscales += sum dy * xh, db += sum dy; each of dx, dscales, db may be None. scales None (x, mean,
+    rstd may be None too): the rearrangement's backward"""
+    n, c, oh, ow = dy.shape
+    c_in, h, w = c * block * block, oh // block, ow // block
+    assert (oh, ow) == (block * h, block * w)
+    assert (x is None or x.shape == (n, c_in, h, w)) and (dx is None or dx.shape == (n, c_in, h, w))
+    assert scales is None or (x is not None and scales.numel() == c and mean.numel() == n * oh * ow == rstd.numel())
+    assert (dscales is None or dscales.numel() == c) and (db is None or db.numel() == c)
+    args = _lib.PatchExpandBwdArgs(_f32(x), _f32(scales), _f32(mean), _f32(rstd), _f32(dy), _f32(dx), _f32(dscales), _f32(db),
+                                   n, c_in, h, w, block, PATCH_EXPAND_ORDERS.get(order, order), 1 if overwrite else 0)
+    _lib.load().bcnn_hip_patch_expand_backward(_C.byref(args))
+
+
 def _attention_dims(q, k, v, heads):
     n, cqk, lq = q.shape[0], q.shape[1], q.shape[2] * q.shape[3]
     cv, lk = v.shape[1], k.shape[2] * k.shape[3]

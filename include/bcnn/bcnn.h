@@ -86,6 +86,8 @@ typedef enum {
 #define BCNN_LAYER_PATCH_MERGING ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 10))
 /* The layer type of bcnn_add_residual_layer, likewise a constant behind the enumerator list. */
 #define BCNN_LAYER_RESIDUAL ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 11))
+/* The layer type of bcnn_add_patch_expanding_layer, likewise a constant behind the enumerator list. */
+#define BCNN_LAYER_PATCH_EXPANDING ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 12))
 
 typedef enum {
     BCNN_ACT_NONE, BCNN_ACT_TANH, BCNN_ACT_RELU, BCNN_ACT_RAMP, BCNN_ACT_SOFTPLUS,
@@ -409,6 +411,28 @@ BCNN_API bcnn_status bcnn_add_residual_layer(bcnn_net *net, const char *src_id1,
  * zero padding is not built), a tensor of 2^31 elements or more. May be the first node of a net. Follows bcnn_resize_net; a
  * resize to an odd extent is refused and leaves the net as it was. */
 BCNN_API bcnn_status bcnn_add_patch_merging_layer(bcnn_net *net, int norm, float eps, const char *src_id, const char *dst_id);
+/* New, without a reference counterpart: patch expanding, the upward step of Swin-UNet's decoder (and, with norm == 0,
+ * depth-to-space and torch's PixelShuffle). src is [N, p^2 c, H, W] with the block p = 2 or 4, dst [N, c, pH, pW]:
+ * dst[n, ch, p h + p1, p w + p2] takes the source channel
+ *   BCNN_PATCH_EXPAND_BLOCKS   (p1 p + p2) c + ch: einops 'b h w (p1 p2 c) -> b (h p1) (w p2) c', Swin-UNet's PatchExpand
+ *                              (block 2) and FinalPatchExpand_X4 (block 4), TensorFlow / ONNX-DCR depth-to-space;
+ *   BCNN_PATCH_EXPAND_CHANNELS ch p^2 + p1 p + p2: torch.nn.PixelShuffle, ONNX CRD.
+ * The block index is row-major (p1 p + p2) as in those models, patch merging's above is 2 dx + dy: with block 2 the BLOCKS
+ * order is not the inverse of the patch-merging rearrangement (INTEGRATION.md gives the permutation).
+ * With norm != 0 every output position is then normalised over its c values (biased variance, eps <= 0 selects 1e-5) and
+ * mapped through the parameters <src>_pe_scales (filled with 1) and <src>_pe_b (0), [1,1,1,c], trained like a layer's weights
+ * and biases, in the same launch. Swin-UNet's bias-free Linear(C, 2C) is a 1x1 convolution node in front of this one.
+ * norm == 0 is the rearrangement alone, bit-exact, without parameters. The same function in TRAIN, VALID and PREDICT mode.
+ *   Model files hold b then scales, c floats each (nothing with norm == 0); the Darknet reader skips the node.
+ *   A net built in TRAIN or VALID mode keeps mean and rstd of the last forward, [2][N * pH * pW] floats:
+ *   bcnn_get_node_state(net, node, 0). The backward adds into the source gradient (assigns when it is its sole writer); a
+ *   source without a gradient buffer is skipped.
+ * Refused with BCNN_INVALID_PARAMETER and a log line, nothing added to the net: an unknown src name, a block other than 2 or
+ * 4, an unknown order, a channel count that is no multiple of block^2, a tensor of 2^31 elements or more. May be the first
+ * node of a net. Follows bcnn_resize_net. */
+typedef enum { BCNN_PATCH_EXPAND_BLOCKS = 0, BCNN_PATCH_EXPAND_CHANNELS = 1 } bcnn_patch_expand_order;
+BCNN_API bcnn_status bcnn_add_patch_expanding_layer(bcnn_net *net, int block, bcnn_patch_expand_order order, int norm, float eps,
+                                                    const char *src_id, const char *dst_id);
 BCNN_API bcnn_status bcnn_add_dropout_layer(bcnn_net *net, float rate, const char *id);
 BCNN_API bcnn_status bcnn_add_upsample_layer(bcnn_net *net, int size, const char *src_id, const char *dst_id);
 /* New, without a reference counterpart: bilinear interpolation of every plane of src to a new extent, with a gradient --

@@ -656,6 +656,56 @@ void bcnn_hip_patch_merge_backward(const float *x_d, const float *scales_d, cons
 int bcnn_hip_patch_merge_path(int n, int c, int h, int w);
 
 /* ---------------------------------------------------------------------------------------------
+ * Patch expanding (the patch-expanding node; patch_expand.hip). No reference counterpart: the channels of x [n][c_in][h][w],
+ * c_in = block^2 c with block p = 2 or 4, move to the positions, y [n][c][p h][p w]:
+ *   y[n][ch][p h + p1][p w + p2] = x[n][src(ch, p1, p2)][h][w], 0 <= p1, p2 < p, ch < c, in one of two orders:
+ *   BCNN_HIP_PATCH_EXPAND_BLOCKS  : src = (p1 p + p2) c + ch -- einops 'b h w (p1 p2 c) -> b (h p1) (w p2) c', Swin-UNet's
+ *     PatchExpand and FinalPatchExpand_X4, TensorFlow / ONNX-DCR depth-to-space;
+ *   BCNN_HIP_PATCH_EXPAND_CHANNELS: src = ch p^2 + p1 p + p2 -- torch.nn.PixelShuffle, ONNX CRD.
+ *   The block index is row-major (p1 p + p2); patch merging's above is 2 dx + dy. Each follows the model it serves, so with
+ *   p = 2 BLOCKS is not the inverse of bcnn_hip_patch_merge_forward's rearrangement: that inverse reads block 2 p2 + p1.
+ *   scales == NULL: the rearrangement alone, bit for bit (b, mean, rstd are not read or written). Otherwise every OUTPUT
+ *   position o = n (p h)(p w) + oy (p w) + ox is normalised over its c values in the same launch; scales, b are [c], mean,
+ *   rstd [n (p h)(p w)] and may be NULL (nothing is stored, y has the same bits).
+ *   forward : sums of v and v^2 in double in an order that follows from the shape; mean = s / c, the biased variance
+ *     max(q / c - mean^2, 0), rstd = (float)(1 / sqrt(var + eps)); eps <= 0 selects 1e-5.
+ *     y = ((v - mean) * rstd) * scales[ch] + b[ch], one float32 rounding per operation on the stored float32 mean and rstd.
+ *   backward: from mean and rstd, as bcnn_hip_channel_norm_backward on the rearranged tensor; dx receives (overwrite != 0) or
+ *     is added the gradient at the place each value came from; dscales[ch] += sum_o dy * xh, db[ch] += sum_o dy from ONE pass
+ *     over dy and x whatever c is: per-workgroup partial rows, added in ascending order in double, the start value one
+ *     float32 addition. Each of dx, dscales, db may be NULL. With scales == NULL (mean, rstd, x unread, dscales and db
+ *     untouched) dx (+)= dy moved back, bit for bit.
+ *   No atomics; two runs give the same bits; a y / dy base that is not aligned to 4 p bytes changes the loads and stores,
+ *   not the bits.
+ *   bcnn_hip_patch_expand_path: the kernel family, from c = c_in / p^2 and p alone: 0 column (c <= 8, a lane holds the p c
+ *     values of its block row), 1 split (c <= 512 at p = 2, 256 at p = 4: the waves of a workgroup split the channels of a
+ *     64-position tile and hold it in registers), 2 stream (two sweeps, the second from cache); -1 for a refused shape: an
+ *     extent below 1, a block other than 2 or 4, a c_in that is no multiple of p^2, 2^31 elements or more. On those, and on
+ *     an unknown order, the two entry points write a line to stderr and return having done nothing. With the dispatch trace
+ *     on the launches are named patch_expand_fwd:<path> / patch_expand_bwd:<path> (path "copy" with scales == NULL) and
+ *     patch_expand_finalize: forward 1 launch, backward at most 2, the copy path 1 each way.
+ * ------------------------------------------------------------------------------------------- */
+enum { BCNN_HIP_PATCH_EXPAND_BLOCKS = 0, BCNN_HIP_PATCH_EXPAND_CHANNELS = 1 };
+typedef struct bcnn_hip_patch_expand_fwd_args {
+    const float *x, *scales, *b; /* scales == NULL: no norm */
+    float *y;
+    float *mean, *rstd; /* may be NULL */
+    int n, c_in, h, w;  /* the shape of x */
+    int block, order;
+    float eps;
+} bcnn_hip_patch_expand_fwd_args;
+typedef struct bcnn_hip_patch_expand_bwd_args {
+    const float *x, *scales, *mean, *rstd, *dy;
+    float *dx, *dscales, *db; /* each may be NULL */
+    int n, c_in, h, w;        /* the shape of x */
+    int block, order;
+    int overwrite; /* dx is assigned, not added to */
+} bcnn_hip_patch_expand_bwd_args;
+void bcnn_hip_patch_expand_forward(const bcnn_hip_patch_expand_fwd_args *args);
+void bcnn_hip_patch_expand_backward(const bcnn_hip_patch_expand_bwd_args *args);
+int bcnn_hip_patch_expand_path(int n, int c_in, int h, int w, int block);
+
+/* ---------------------------------------------------------------------------------------------
  * Multi-head attention over the positions of a feature map (the attention node; attention.hip). No reference counterpart.
  *   q is [n][heads * d][lq], k [n][heads * d][lk], v [n][heads * c][lk], o [n][heads * c][lq]; head h of image n owns
  *   channels [h * d, (h + 1) * d) of q and k and [h * c, (h + 1) * c) of v and o. Per image and head
