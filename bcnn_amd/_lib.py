@@ -33,6 +33,17 @@ class PatchExpandBwdArgs(C.Structure):  # bcnn_hip_patch_expand_bwd_args
                [(k, i) for k in ("n", "c_in", "h", "w", "block", "order", "overwrite")]
 
 
+class DiceLossFwdArgs(C.Structure):  # BcnnDiceLossFwdArgs
+    _fields_ = [(k, vp) for k in ("x", "label", "p", "workspace")] + \
+               [(k, i) for k in ("n", "c", "hw", "ignore_label", "squared", "reduce")] + \
+               [(k, f) for k in ("ce_weight", "dice_weight", "smooth")]
+
+
+class DiceLossBwdArgs(C.Structure):  # BcnnDiceLossBwdArgs
+    _fields_ = [(k, vp) for k in ("p", "label", "workspace", "dx")] + \
+               [(k, i) for k in ("n", "c", "hw", "ignore_label", "squared", "reduce")] + [("dice_weight", f), ("overwrite", i)]
+
+
 class WindowAttnFwdArgs(C.Structure):  # BcnnWindowAttnFwdArgs
     _fields_ = [(k, vp) for k in ("q", "k", "v", "table", "o")] + \
                [(k, i) for k in ("n", "heads", "d", "c", "h", "w", "window", "shift")] + [("scale", f)]
@@ -208,6 +219,10 @@ SIGNATURES = {
     "bcnn_hip_softmax_loss_backward": (None, [vp, vp, vp, vp, vp, i, i, i, i]),
     "bcnn_hip_softmax_loss_confusion": (None, [vp, vp, vp, vp, i, i, i]),
     "bcnn_hip_softmax_loss_c_reg": (i, []),
+    "bcnn_hip_dice_loss_forward": (None, [vp]),
+    "bcnn_hip_dice_loss_backward": (None, [vp]),
+    "bcnn_hip_dice_loss_workspace_size": (sz, [i, i, i, i]),
+    "bcnn_hip_dice_loss_path": (i, [i, i, i, i]),
     "bcnn_hip_label_map_fit": (i, [i, i, i, i, i, vp]),
     "bcnn_hip_label_maps_plan": (i, [vp, i, i, i, i, i, vp, vp, vp]),
     "bcnn_hip_label_maps_batch": (i, [vp, i, i, i, i, i, vp, i, vp, vp, vp, vp, i, vp, vp, vp]),

@@ -33,6 +33,9 @@ LAYER_WINDOW_ATTENTION = 26
 LAYER_PATCH_MERGING, LAYER_RESIDUAL = 27, 28
 LAYER_PATCH_EXPANDING = 29
 PATCH_EXPAND_BLOCKS, PATCH_EXPAND_CHANNELS = 0, 1
+LAYER_DICE_LOSS = 30
+DICE_REDUCE_BATCH, DICE_REDUCE_IMAGE = 0, 1
+DICE_REDUCES = {"batch": DICE_REDUCE_BATCH, "image": DICE_REDUCE_IMAGE}
 LOSS_NORM_NONE, LOSS_NORM_VALID, LOSS_NORM_VALID_PER_IMAGE = 0, 1, 2
 LOSS_NORMS = {"none": LOSS_NORM_NONE, "valid": LOSS_NORM_VALID, "valid_per_image": LOSS_NORM_VALID_PER_IMAGE}
 
@@ -78,6 +81,12 @@ class SoftmaxLossStats(C.Structure):
     """struct bcnn_softmax_loss_stats (include/bcnn/bcnn.h)."""
     _fields_ = [("loss", C.c_float), ("valid", C.c_int64), ("ignored", C.c_int64), ("out_of_range", C.c_int64),
                 ("correct", C.c_int64)]
+
+
+class DiceLossStats(C.Structure):
+    """struct bcnn_dice_loss_stats (include/bcnn/bcnn.h)."""
+    _fields_ = [("loss", C.c_float), ("ce", C.c_float), ("dice", C.c_float), ("valid", C.c_int64), ("ignored", C.c_int64),
+                ("out_of_range", C.c_int64), ("correct", C.c_int64)]
 
 
 _libc = C.CDLL(None)
@@ -150,6 +159,10 @@ def lib():
         "bcnn_add_softmax_loss_layer": (i, [vp, i, i, f, cp, cp, cp]),
         "bcnn_get_softmax_loss_stats": (i, [vp, i, C.POINTER(SoftmaxLossStats)]),
         "bcnn_get_confusion_matrix": (i, [vp, i, C.POINTER(C.c_int64)]),
+        "bcnn_add_dice_loss_layer": (i, [vp, i, f, f, f, i, i, cp, cp, cp]),
+        "bcnn_get_dice_loss_stats": (i, [vp, i, C.POINTER(DiceLossStats)]),
+        "bcnn_get_dice_loss_sums": (i, [vp, i, C.POINTER(C.c_double)]),
+        "bcnn_get_dice_loss_groups": (i, [vp, i]),
         "bcnn_get_label_maps_batch": (i, [vp, i, i, C.POINTER(i), C.POINTER(i), i, i, C.POINTER(vp), C.POINTER(i),
                                           C.POINTER(LabelMapEval)]),
         "bcnn_add_lrn_layer": (i, [vp, i, f, f, f, cp, cp]), "bcnn_add_dropout_layer": (i, [vp, f, cp]),
@@ -378,6 +391,35 @@ class Net:
         if st != 0:
             raise ValueError("node %d has no softmax-loss statistics (status %d)" % (node, st))
         return {name: getattr(out, name) for name, _ in SoftmaxLossStats._fields_}
+
+    def dice_loss(self, src, dst, ignore_label=-1, ce_weight=0.4, dice_weight=0.6, smooth=1e-5, squared=True, reduce="batch"):
+        """bcnn_add_dice_loss_layer: softmax over the channels of src, then ce_weight * cross-entropy + dice_weight * soft
+        Dice against the class-index label map in tensor 1; reduce: "batch", "image" or a DICE_REDUCE_* value"""
+        return self._added(self.L.bcnn_add_dice_loss_layer(self.net, ignore_label, ce_weight, dice_weight, smooth,
+                                                           1 if squared else 0, DICE_REDUCES.get(reduce, reduce),
+                                                           src.encode(), b"label", dst.encode()))
+
+    def dice_loss_stats(self, node):
+        """bcnn_get_dice_loss_stats of the node's latest TRAIN / VALID forward, as a dict (loss, ce, dice, valid, ignored,
+        out_of_range, correct); raises ValueError when the node has none (not such a node, a PREDICT forward)"""
+        out = DiceLossStats()
+        st = self.L.bcnn_get_dice_loss_stats(self.net, node, C.byref(out))
+        if st != 0:
+            raise ValueError("node %d has no dice-loss statistics (status %d)" % (node, st))
+        return {name: getattr(out, name) for name, _ in DiceLossStats._fields_}
+
+    def dice_loss_sums(self, node):
+        """bcnn_get_dice_loss_sums: the [G][C][3] float64 array {I, Z, Y} of that forward; G, from
+        bcnn_get_dice_loss_groups, is 1 for reduce="batch" and the batch size for reduce="image"""
+        groups = self.L.bcnn_get_dice_loss_groups(self.net, node)
+        if groups < 1:
+            raise ValueError("node %d is not a dice-loss node" % node)
+        c = self.shape(self.node_dst(node))[1]
+        izy = np.zeros((groups, c, 3), np.float64)
+        st = self.L.bcnn_get_dice_loss_sums(self.net, node, izy.ctypes.data_as(C.POINTER(C.c_double)))
+        if st != 0:
+            raise ValueError("node %d has no dice-loss sums (status %d)" % (node, st))
+        return izy
 
     def confusion_matrix(self, node):
         """bcnn_get_confusion_matrix: the C x C int64 matrix (row = label, column = argmax) of the node's latest forward"""

@@ -207,6 +207,10 @@ typedef struct {
     int has_scale;
     int window, shift, rel_bias; /* [window_attention] / [swin_attention]; shift defaults to 0, rel_bias to 1 */
     int norm; /* [patch_merging] / [patchmerge], [patch_expanding] / [patchexpand]: the norm over the channels, default 1 */
+    /* [dice_loss] / [softmax_dice_loss]: with ignore_label above, ce_weight (0.4), dice_weight (0.6), smooth (1e-5),
+     * squared (1) and reduce = batch | image (batch; -1: a word the section wrote that is neither) */
+    float ce_weight, dice_weight, smooth;
+    int squared, dice_reduce;
     int block, order; /* [patch_expanding] / [patchexpand] / [depth_to_space] / [pixel_shuffle]: block= default 2; order=
                          blocks | channels, -1: the section's own */
 } layer_param;
@@ -228,6 +232,7 @@ static void lp_reset(layer_param *lp) {
     lp->block = 2;
     lp->order = -1;
     lp->ignore_label = -1; lp->loss_norm = (int)BCNN_LOSS_NORM_VALID_PER_IMAGE; lp->loss_scale = 1.0f;
+    lp->ce_weight = 0.4f; lp->dice_weight = 0.6f; lp->smooth = 1e-5f; lp->squared = 1; lp->dice_reduce = (int)BCNN_DICE_REDUCE_BATCH;
 }
 
 static void lp_set_srcs(layer_param *lp, const char *list) {
@@ -301,6 +306,12 @@ static void lp_set(bcnn_net *net, int section_idx, layer_param *lp, const char *
     else if (!strcmp(name, "order")) /* an unknown word reaches the builder, which refuses it */
         lp->order = !strcmp(val, "blocks") ? (int)BCNN_PATCH_EXPAND_BLOCKS : (!strcmp(val, "channels") ? (int)BCNN_PATCH_EXPAND_CHANNELS : 2);
     else if (!strcmp(name, "ignore_label")) lp->ignore_label = atoi(val);
+    else if (!strcmp(name, "ce_weight")) lp->ce_weight = (float)atof(val);
+    else if (!strcmp(name, "dice_weight")) lp->dice_weight = (float)atof(val);
+    else if (!strcmp(name, "smooth")) lp->smooth = (float)atof(val);
+    else if (!strcmp(name, "squared")) lp->squared = atoi(val);
+    else if (!strcmp(name, "reduce")) /* refused by the section that reads it: no silent fallback */
+        lp->dice_reduce = !strcmp(val, "batch") ? (int)BCNN_DICE_REDUCE_BATCH : (!strcmp(val, "image") ? (int)BCNN_DICE_REDUCE_IMAGE : -1);
     else if (!strcmp(name, "normalize")) {
         if (!strcmp(val, "none")) lp->loss_norm = (int)BCNN_LOSS_NORM_NONE;
         else if (!strcmp(val, "valid")) lp->loss_norm = (int)BCNN_LOSS_NORM_VALID;
@@ -584,6 +595,12 @@ static bcnn_status add_layer(bcnn_net *net, const char *name, layer_param *lp) {
                            "Softmax-loss layer %s: normalize must be none, valid or valid_per_image\n", dst);
         return bcnn_add_softmax_loss_layer(net, lp->ignore_label, (bcnn_loss_norm)lp->loss_norm, lp->loss_scale, src, "label",
                                            dst);
+    }
+    if (is_any(name, "[dice_loss]", "[softmax_dice_loss]", NULL, NULL)) {
+        BCNN_CHECK_AND_LOG(net->log_ctx, lp->dice_reduce >= 0, BCNN_INVALID_PARAMETER,
+                           "Dice-loss layer %s: reduce must be batch or image\n", dst);
+        return bcnn_add_dice_loss_layer(net, lp->ignore_label, lp->ce_weight, lp->dice_weight, lp->smooth, lp->squared,
+                                        (bcnn_dice_reduce)lp->dice_reduce, src, "label", dst);
     }
     if (!strcmp(name, "[cost]")) return bcnn_add_cost_layer(net, lp->loss, lp->cost, 1.0f, src, "label", dst);
     bcnn_log(net->log_ctx, BCNN_LOG_ERROR, "Unknown Layer %s\n", name);

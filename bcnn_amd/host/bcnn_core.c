@@ -419,13 +419,14 @@ static void mark_dead_grad_fills(bcnn_net *net) {
                           nd->type == BCNN_LAYER_CHANNEL_NORM || nd->type == BCNN_LAYER_PATCH_MERGING ||
                           nd->type == BCNN_LAYER_PATCH_EXPANDING ||
                           nd->type == BCNN_LAYER_RESIDUAL ||
-                          nd->type == BCNN_LAYER_SOFTMAX_LOSS || nd->type == BCNN_LAYER_DILATED_DEPTHWISE_CONV2D)) {
+                          nd->type == BCNN_LAYER_SOFTMAX_LOSS || nd->type == BCNN_LAYER_DICE_LOSS ||
+                          nd->type == BCNN_LAYER_DILATED_DEPTHWISE_CONV2D)) {
             /* max-pooling's gather, the depthwise data gradient (a gather too: one thread owns a dx element,
              * bcnn_depthwise_conv_layer.c:432-547 accumulates onto the zero fill), LRN's (one lane per column), the
              * pool2d gather, whose overwrite form also writes the elements no window covers, group-norm's sweep (one
              * thread owns a dx element), the bilinear interpolation's gather, whose overwrite form also writes the
-             * elements a downsampling skips, and the softmax loss, whose overwrite form writes +0.0 on the pixels that are
-             * not valid, and the dilated depthwise data gradient, a gather like the depthwise one whose overwrite form also
+             * elements a downsampling skips, and the softmax loss and the dice loss, whose overwrite forms write +0.0 on the
+             * pixels that are not valid, and the dilated depthwise data gradient, a gather like the depthwise one whose overwrite form also
              * writes the elements no tap reaches, and channel-norm's sweep (one thread owns a dx element), patch merging's and
              * patch expanding's (every source element has one place in dst) and the first operand of the residual add */
             hc->grad_fill_dead[t] = 2;
@@ -626,6 +627,8 @@ static int node_dst_shape(const bcnn_node *nd, const bcnn_tensor *s, bcnn_tensor
         oc = s->c / (p * p);
         oh = s->h * p;
         ow = s->w * p;
+    } else if (nd->type == BCNN_LAYER_DICE_LOSS) { /* same shape; its kernels index with 32 bits */
+        if ((long long)s->n * s->c * s->h * s->w >= 0x80000000LL) return 0;
     }
     bcnn_tensor_set_shape(d, s->n, oc, oh, ow, 1);
     return 1;
@@ -686,13 +689,14 @@ static bcnn_status resize_plan(bcnn_net *net, int w, int h, int c, int need_real
             BCNN_CHECK_AND_LOG(net->log_ctx, s->n == b->n && s->c == b->c && s->h == b->h && s->w == b->w, BCNN_INVALID_PARAMETER,
                                "bcnn_resize_net: the operands of residual node %d would differ in shape\n", i);
         }
-        /* the class-index label map of a softmax-loss node follows as [n][1][h][w] */
+        /* the class-index label map of a softmax-loss or dice-loss node follows as [n][1][h][w] */
+        size_t *label_capacity = NULL;
         BCNN_CHECK_AND_LOG(net->log_ctx,
-                           nd->type != BCNN_LAYER_SOFTMAX_LOSS || need_realloc ||
-                               (size_t)d->n * d->h * d->w <= ((const bcnn_softmax_loss_param *)nd->param)->label_capacity,
+                           !bcnn_label_map_node(nd, NULL, &label_capacity) || need_realloc ||
+                               (size_t)d->n * d->h * d->w <= *label_capacity,
                            BCNN_INVALID_PARAMETER,
-                           "bcnn_resize_net: the label map of softmax-loss node %d would outgrow its allocation; call with "
-                           "need_realloc\n", i);
+                           "bcnn_resize_net: the label map of %s node %d would outgrow its allocation; call with "
+                           "need_realloc\n", nd->type == BCNN_LAYER_DICE_LOSS ? "dice-loss" : "softmax-loss", i);
     }
     return BCNN_SUCCESS;
 }
@@ -708,13 +712,13 @@ static bcnn_status resize_commit(bcnn_net *net, int w, int h, int c, int need_re
             node_dst_shape(nd, &net->tensors[nd->src[0]], d);
             if (need_realloc && bcnn_tensor_allocate(d, net->mode) != BCNN_SUCCESS) return BCNN_FAILED_ALLOC;
         }
-        if (nd->type == BCNN_LAYER_SOFTMAX_LOSS) { /* the label map follows the new shape */
-            bcnn_softmax_loss_param *p = (bcnn_softmax_loss_param *)nd->param;
+        size_t *label_capacity = NULL;
+        if (bcnn_label_map_node(nd, NULL, &label_capacity)) { /* the label map follows the new shape */
             bcnn_tensor *label = &net->tensors[1];
             bcnn_tensor_set_shape(label, d->n, 1, d->h, d->w, 0);
             if (need_realloc) {
                 if (bcnn_tensor_allocate(label, net->mode) != BCNN_SUCCESS) return BCNN_FAILED_ALLOC;
-                p->label_capacity = (size_t)d->n * d->h * d->w;
+                *label_capacity = (size_t)d->n * d->h * d->w;
             }
         }
         if (!need_realloc) continue; /* the plan found every buffer large enough */
@@ -1080,8 +1084,8 @@ void bcnn_node_optim_step(bcnn_net *net, bcnn_tensor *weights, bcnn_tensor *bias
 }
 
 /* reference bcnn_get_loss, bcnn_net.c:431-449. The heads' costs live on the device: with detector training on, a TRAIN
- * net reads every head's record here, once, at the end of the step. So does every softmax-loss node's loss (0 after a
- * PREDICT forward). */
+ * net reads every head's record here, once, at the end of the step. So does every softmax-loss and dice-loss node's loss (0
+ * after a PREDICT forward). */
 static float current_loss(bcnn_net *net) {
     float loss = 0.f;
     int n = 0;
@@ -1095,6 +1099,9 @@ static float current_loss(bcnn_net *net) {
             ++n;
         } else if (net->nodes[i].type == BCNN_LAYER_SOFTMAX_LOSS) { /* counted like a cost node; its record is read here */
             loss += bcnn_softmax_loss_read_loss(net, &net->nodes[i]);
+            ++n;
+        } else if (net->nodes[i].type == BCNN_LAYER_DICE_LOSS) { /* likewise */
+            loss += bcnn_dice_loss_read_loss(net, &net->nodes[i]);
             ++n;
         }
     return n ? loss / n : 0.f;

@@ -620,7 +620,7 @@ static float *label_slot(bcnn_net *net, int idx, int *label_sz) {
 
 static int has_softmax_loss(const bcnn_net *net) {
     for (int i = 0; i < net->num_nodes; ++i)
-        if (net->nodes[i].type == BCNN_LAYER_SOFTMAX_LOSS) return 1;
+        if (bcnn_label_map_node(&net->nodes[i], NULL, NULL)) return 1; /* a softmax-loss or a dice-loss node */
     return 0;
 }
 

@@ -32,8 +32,8 @@
 
 static int fill_byte(const bcnn_net *net) {
     for (int i = 0; i < net->num_nodes; ++i) {
-        if (net->nodes[i].type != BCNN_LAYER_SOFTMAX_LOSS) continue;
-        const int ignore = ((const bcnn_softmax_loss_param *)net->nodes[i].param)->ignore_label;
+        int ignore = -1;
+        if (!bcnn_label_map_node(&net->nodes[i], &ignore, NULL)) continue; /* a softmax-loss or a dice-loss node */
         return (ignore >= 0 && ignore <= 255) ? ignore : 255;
     }
     return 255;

@@ -618,6 +618,20 @@ typedef struct bcnn_softmax_loss_param {
 #endif
 } bcnn_softmax_loss_param;
 
+/* softmax + cross-entropy + soft Dice against a class-index label map (bcnn_add_dice_loss_layer; no reference counterpart) */
+typedef struct bcnn_dice_loss_param {
+    int ignore_label;
+    float ce_weight, dice_weight, smooth;
+    int squared;
+    bcnn_dice_reduce reduce;
+    int has_stats;         /* the latest forward wrote the workspace (TRAIN / VALID with a label on the device) */
+    size_t label_capacity; /* floats the label tensor was allocated with by this node */
+#ifdef BCNN_USE_HIP
+    float *workspace_gpu;  /* record, sums, coefficients: bcnn_hip_dice_loss_workspace_size floats of the shape it was built on */
+    size_t workspace_floats;
+#endif
+} bcnn_dice_loss_param;
+
 /* in-place dropout (reference src/layers/bcnn_dropout_layer.h); the mask is regenerated from (key, step) of the last
  * TRAIN forward instead of being stored (include/bcnn_hip.h) */
 typedef struct bcnn_dropout_param {
@@ -756,6 +770,28 @@ void bcnn_backward_softmax_loss_layer(bcnn_net *net, bcnn_node *node);
 void bcnn_release_param_softmax_loss_layer(bcnn_node *node);
 /* bcnn_layers_softmax_loss.c: the loss of the node's latest forward, read from its device record; 0 without statistics */
 float bcnn_softmax_loss_read_loss(bcnn_net *net, bcnn_node *node);
+void bcnn_forward_dice_loss_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_backward_dice_loss_layer(bcnn_net *net, bcnn_node *node);
+void bcnn_release_param_dice_loss_layer(bcnn_node *node);
+/* bcnn_layers_dice_loss.c: the loss of the node's latest forward, read from its device record; 0 without statistics */
+float bcnn_dice_loss_read_loss(bcnn_net *net, bcnn_node *node);
+/* A node that reads the class-index label map in tensor 1 (softmax-loss, dice-loss): 1, its ignore label in *ignore_label
+ * and where it keeps the label's capacity in *label_capacity (either may be NULL); 0 for every other node. */
+static inline int bcnn_label_map_node(const bcnn_node *nd, int *ignore_label, size_t **label_capacity) {
+    if (nd->type == BCNN_LAYER_SOFTMAX_LOSS) {
+        bcnn_softmax_loss_param *p = (bcnn_softmax_loss_param *)nd->param;
+        if (ignore_label) *ignore_label = p->ignore_label;
+        if (label_capacity) *label_capacity = &p->label_capacity;
+        return 1;
+    }
+    if (nd->type == BCNN_LAYER_DICE_LOSS) {
+        bcnn_dice_loss_param *p = (bcnn_dice_loss_param *)nd->param;
+        if (ignore_label) *ignore_label = p->ignore_label;
+        if (label_capacity) *label_capacity = &p->label_capacity;
+        return 1;
+    }
+    return 0;
+}
 
 /* SGD step on one node's parameters (bcnn_learner.c:67-104 in the reference) */
 void bcnn_link_depthwise_batchnorm(bcnn_net *net); /* bcnn_layers_hot.c; called by bcnn_compile_net */

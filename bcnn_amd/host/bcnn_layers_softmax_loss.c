@@ -148,8 +148,13 @@ bcnn_status bcnn_get_softmax_loss_stats(bcnn_net *net, int node, bcnn_softmax_lo
     return BCNN_SUCCESS;
 }
 
+/* a softmax-loss node, or a dice-loss node: it holds the same probabilities and reads the same label */
 bcnn_status bcnn_get_confusion_matrix(bcnn_net *net, int node, int64_t *counts) {
     bcnn_node *nd = loss_node(net, node);
+    int dice_ignore = -1;
+    const int dice = !nd && net && node >= 0 && node < net->num_nodes && net->nodes[node].type == BCNN_LAYER_DICE_LOSS &&
+                     bcnn_label_map_node(&net->nodes[node], &dice_ignore, NULL);
+    if (dice) nd = &net->nodes[node];
     if (!nd || !counts) return BCNN_INVALID_PARAMETER;
     const bcnn_tensor *x = &net->tensors[nd->src[0]], *y = &net->tensors[nd->dst[0]];
     const float *label = label_gpu(net, x);
@@ -162,7 +167,8 @@ bcnn_status bcnn_get_confusion_matrix(bcnn_net *net, int node, int64_t *counts) 
         free(host);
         return BCNN_FAILED_ALLOC;
     }
-    const bcnn_hip_softmax_loss_desc d = loss_desc((const bcnn_softmax_loss_param *)nd->param);
+    bcnn_hip_softmax_loss_desc d = {dice_ignore, BCNN_SL_NORM_NONE, 1.0f}; /* the kernel reads the ignore label alone */
+    if (!dice) d = loss_desc((const bcnn_softmax_loss_param *)nd->param);
     bcnn_hip_softmax_loss_confusion(&d, y->data_gpu, label, counts_gpu, x->n, x->c, x->h * x->w);
     bcnn_hip_memcpy_d2h(host, counts_gpu, cells * sizeof(unsigned));
     for (size_t i = 0; i < cells; ++i) counts[i] = (int64_t)host[i];

@@ -410,6 +410,71 @@ def softmax_loss_confusion(p, label, ignore_label=-1):
     return counts.cpu().numpy().astype("int64").reshape(c, c)
 
 
+DICE_REDUCE_BATCH, DICE_REDUCE_IMAGE = 0, 1
+DICE_REDUCES = {"batch": DICE_REDUCE_BATCH, "image": DICE_REDUCE_IMAGE}
+
+
+class DiceLossRecord(_C.Structure):
+    """struct bcnn_hip_dice_loss_record (include/bcnn_hip.h): the head of the workspace a forward with a label leaves"""
+    _fields_ = [("loss", _C.c_float), ("ce", _C.c_float), ("dice", _C.c_float), ("grad_ce", _C.c_float),
+                ("valid", _C.c_int), ("ignored", _C.c_int), ("out_of_range", _C.c_int), ("correct", _C.c_int)]
+
+
+def dice_loss_path(n, c, hw, aligned=True):
+    """bcnn_hip_dice_loss_path: 0 the register path, 1 the wide path, -1 a refused shape (host code)"""
+    return int(_lib.load().bcnn_hip_dice_loss_path(n, c, hw, 1 if aligned else 0))
+
+
+def dice_loss_workspace_size(n, c, hw, reduce="batch"):
+    """bcnn_hip_dice_loss_workspace_size in floats; 0 for a refused shape or an unknown reduce (host code)"""
+    return int(_lib.load().bcnn_hip_dice_loss_workspace_size(n, c, hw, DICE_REDUCES.get(reduce, reduce)))
+
+
+def dice_loss_workspace(n, c, hw, reduce="batch"):
+    """a zeroed device workspace (a float64 tensor: 8-byte aligned) for dice_loss_forward / dice_loss_backward"""
+    return torch.zeros((dice_loss_workspace_size(n, c, hw, reduce) + 1) // 2, dtype=torch.float64, device="cuda")
+
+
+def dice_loss_read_workspace(workspace, n, c, reduce="batch"):
+    """the workspace on the host: (record as a dict, sums [G][C][3] float64 {I, Z, Y}, coefficients [G][C][2] float32
+    {A, B}); synchronises"""
+    import numpy as np
+    raw = workspace.cpu().numpy().tobytes()
+    g = n if DICE_REDUCES.get(reduce, reduce) == DICE_REDUCE_IMAGE else 1
+    r = DiceLossRecord.from_buffer_copy(raw[:32])
+    sums = np.frombuffer(raw, np.float64, g * c * 3, 32).reshape(g, c, 3).copy()
+    coef = np.frombuffer(raw, np.float32, g * c * 2, 32 + g * c * 24).reshape(g, c, 2).copy()
+    return {name: getattr(r, name) for name, _ in DiceLossRecord._fields_}, sums, coef
+
+
+def _dice_shape(t):
+    n, c = t.shape[:2]
+    return n, c, t.numel() // max(n * c, 1)
+
+
+def dice_loss_forward(x, label, p, workspace, ignore_label=-1, ce_weight=0.4, dice_weight=0.6, smooth=1e-5, squared=True,
+                      reduce="batch"):
+    """bcnn_hip_dice_loss_forward: p = softmax over dim 1 of x ([n][C][hw] or [n][C][h][w]); with `label` ([n][1][...], class
+    indices as floats) and `workspace` also the record, the per-class sums and the gradient coefficients. None: p only."""
+    n, c, hw = _dice_shape(x)
+    assert p.numel() == x.numel() and (label is None or label.numel() == n * hw)
+    a = _lib.DiceLossFwdArgs(_f32(x), _f32(label) if label is not None else None, _f32(p),
+                             workspace.data_ptr() if workspace is not None else None, n, c, hw, int(ignore_label),
+                             1 if squared else 0, DICE_REDUCES.get(reduce, reduce), float(ce_weight), float(dice_weight),
+                             float(smooth))
+    _lib.load().bcnn_hip_dice_loss_forward(_C.byref(a))
+
+
+def dice_loss_backward(p, label, workspace, dx, ignore_label=-1, dice_weight=0.6, squared=True, reduce="batch",
+                       overwrite=False):
+    """bcnn_hip_dice_loss_backward: dx += (overwrite: dx =) the gradient of the loss the forward left in `workspace`"""
+    n, c, hw = _dice_shape(p)
+    assert dx.numel() == p.numel() and label.numel() == n * hw
+    a = _lib.DiceLossBwdArgs(_f32(p), _f32(label), workspace.data_ptr(), _f32(dx), n, c, hw, int(ignore_label),
+                             1 if squared else 0, DICE_REDUCES.get(reduce, reduce), float(dice_weight), 1 if overwrite else 0)
+    _lib.load().bcnn_hip_dice_loss_backward(_C.byref(a))
+
+
 IMAGE_FIT_STRETCH, IMAGE_FIT_LETTERBOX = 0, 1
 
 

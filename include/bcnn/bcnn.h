@@ -88,6 +88,8 @@ typedef enum {
 #define BCNN_LAYER_RESIDUAL ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 11))
 /* The layer type of bcnn_add_patch_expanding_layer, likewise a constant behind the enumerator list. */
 #define BCNN_LAYER_PATCH_EXPANDING ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 12))
+/* The layer type of bcnn_add_dice_loss_layer, likewise a constant behind the enumerator list. */
+#define BCNN_LAYER_DICE_LOSS ((bcnn_layer_type)(BCNN_LAYER_POOL2D + 13))
 
 typedef enum {
     BCNN_ACT_NONE, BCNN_ACT_TANH, BCNN_ACT_RELU, BCNN_ACT_RAMP, BCNN_ACT_SOFTPLUS,
@@ -491,6 +493,41 @@ BCNN_API bcnn_status bcnn_get_softmax_loss_stats(bcnn_net *net, int node, bcnn_s
  * the label the latest forward left on the device (one kernel, launched by this call; not on the training path). Its trace
  * is the record's `correct`, its total `valid`. BCNN_INVALID_PARAMETER: not such a node, counts NULL, no label on the device. */
 BCNN_API bcnn_status bcnn_get_confusion_matrix(bcnn_net *net, int node, int64_t *counts);
+/* New, without a reference counterpart: softmax, cross-entropy and soft Dice in one node, the objective of Swin-UNet
+ * (0.4 CE + 0.6 Dice), TransUNet (0.5 / 0.5), V-Net and the U-Net family. It stands beside the softmax-loss node: the same
+ * inputs (logits [n][C][h][w], the class-index label map [n][1][h][w] in tensor 1, shaped by the node), the same output
+ * (the probabilities, with that node's bits), the same label rule, the same place in bcnn_train_on_batch's loss, in the
+ * loaders (class-index labels, the segmentation list's fill byte) and in bcnn_resize_net; bcnn_get_confusion_matrix
+ * accepts it too.
+ *   loss = ce_weight * CE + dice_weight * Dice; CE is the mean of lse(x) - x[t] over the V valid pixels (torch's
+ *   cross_entropy default); Dice = mean over groups and classes of 1 - (2 I + smooth) / (Z + Y + smooth) with, over the
+ *   valid pixels of a group, I = sum p_c [t = c], Y = sum [t = c], Z = sum p_c^2 (squared != 0) or sum p_c. reduce BATCH:
+ *   one group, the whole batch (Swin-UNet's DiceLoss); IMAGE: one group per image (MONAI's default). A pixel that is not
+ *   valid enters no sum and receives exactly +0.0. The full mathematics and the gradient: include/bcnn_hip.h.
+ *   Unlike the softmax-loss node's default normaliser, the gradient is that of the loss as written; bcnn_update divides it
+ *   by the batch size like every other gradient.
+ *   TRAIN and VALID forwards compute probabilities, sums, loss and counts on the device without a host synchronisation; a
+ *   PREDICT forward writes the probabilities only. The node's own dst gradient is never read or written.
+ * BCNN_INVALID_PARAMETER: first node; unknown src_id; ignore_label >= 2^24; an unknown reduce; smooth negative or not
+ * finite; a weight that is not finite; a label tensor that another node already gave another shape. label_id is unused:
+ * the label is always tensor 1. */
+typedef enum { BCNN_DICE_REDUCE_BATCH = 0, BCNN_DICE_REDUCE_IMAGE = 1 } bcnn_dice_reduce;
+BCNN_API bcnn_status bcnn_add_dice_loss_layer(bcnn_net *net, int ignore_label, float ce_weight, float dice_weight, float smooth,
+                                              int squared, bcnn_dice_reduce reduce, const char *src_id, const char *label_id,
+                                              const char *dst_id);
+/* The statistics of the node's latest TRAIN / VALID forward (one synchronising read of the device record).
+ * BCNN_INVALID_PARAMETER, *out zeroed: not a dice-loss node, or no such forward yet. */
+typedef struct {
+    float loss, ce, dice;
+    int64_t valid, ignored, out_of_range, correct;
+} bcnn_dice_loss_stats;
+BCNN_API bcnn_status bcnn_get_dice_loss_stats(bcnn_net *net, int node, bcnn_dice_loss_stats *out);
+/* The sums of that forward, izy[(g * C + c) * 3 + {0, 1, 2}] = {I, Z, Y}, G * C * 3 doubles with G = 1 (BATCH) or n (IMAGE):
+ * the per-class Dice is (2 I + smooth) / (Z + Y + smooth). Same errors. */
+BCNN_API bcnn_status bcnn_get_dice_loss_sums(bcnn_net *net, int node, double *izy);
+/* G, the groups bcnn_get_dice_loss_sums copies for the node at its tensors' present shape: 1 (BATCH) or n (IMAGE); -1: not a
+ * dice-loss node. Size izy with it. */
+BCNN_API int bcnn_get_dice_loss_groups(bcnn_net *net, int node);
 /* New, without a reference counterpart: the output end of semantic segmentation. Tensor `tensor_index` -- any
  * [n][C][h][w] tensor with a device buffer, the logits or the softmax-loss node's probabilities -- becomes one class index
  * (a byte) per pixel of each of the first num_images images of the batch AT THAT IMAGE'S OWN SIZE widths[b] x heights[b],

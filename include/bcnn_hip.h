@@ -495,6 +495,71 @@ void bcnn_hip_softmax_loss_confusion(const bcnn_hip_softmax_loss_desc *desc, con
 int bcnn_hip_softmax_loss_c_reg(void);
 
 /* ---------------------------------------------------------------------------------------------
+ * Softmax + cross-entropy + soft Dice against a class-index label map in one node (the dice-loss node; dice_loss.hip).
+ * No reference counterpart: Swin-UNet's and TransUNet's 0.4 CE + 0.6 Dice (0.5 / 0.5), V-Net's Dice, MONAI's DiceCELoss.
+ *   x, p, dx are [n][c][hw]; label is [n][1][hw], class indices stored as floats, classified by csrc/softmax_loss_rule.h
+ *   exactly as for the softmax-loss node above. V = the number of valid pixels; a pixel that is not valid enters no sum
+ *   and gets no gradient.
+ *     p    = softmax over c of x per pixel, with the softmax-loss node's arithmetic: the same bits as its p.
+ *     CE   = (sum over valid pixels of l) / max(V, 1), l as in the softmax-loss node (torch's cross_entropy default).
+ *     groups g: reduce BATCH: G = 1, the sums run over all images (Swin-UNet's DiceLoss, smp's); reduce IMAGE: G = n, one
+ *       Dice per image and class (MONAI's default).
+ *     per group and class, over valid pixels: I = sum p_c [t = c], Y = sum [t = c], Z = sum p_c^2 (squared != 0; Swin-UNet,
+ *       V-Net) or sum p_c (squared == 0).
+ *     Dice = 1 / (G c) * sum_g sum_c (1 - (2 I + s) / (Z + Y + s)), s = smooth >= 0 (Swin-UNet: 1e-5). A term whose
+ *       denominator is 0 (s == 0 and nothing to sum) is 0 and has no gradient.
+ *     loss = ce_weight * CE + dice_weight * Dice.
+ *     gradient on a valid pixel of group g, with Den = Z + Y + s:
+ *       A_gc = -2 / (G c Den_gc), B_gc = (2 I_gc + s) / (G c Den_gc^2), gamma_c = A_gc [t = c] + B_gc z'(p_c), z' = 2 p_c
+ *       (squared) or 1; dx_c += dice_weight * p_c * (gamma_c - sum_k gamma_k p_k) + ce_weight / max(V, 1) * (p_c - [t = c]).
+ *   forward : writes p. With label and workspace also the workspace: the record, then the sums [G][c]{I, Z, Y} as doubles,
+ *     then the coefficients [G][c]{A, B} as floats: bcnn_hip_dice_loss_workspace_size floats (8 + 8 G c), 8-byte aligned.
+ *     label or workspace NULL: p only. Float partial sums per workgroup, added in double in a fixed order by a finalize
+ *     kernel that also forms A and B: no atomics, no host synchronisation, the same bits on every run.
+ *   backward: reads p, the label, the record and the coefficients on the device; nothing is read back on the host between
+ *     forward and backward. overwrite != 0 as for the softmax-loss node: every element is assigned, +0.0 on the pixels
+ *     that are not valid; otherwise dx is added to and the elements of those pixels keep their bits.
+ *   16-byte accesses when hw % 4 == 0 and the tensors of the call are 16-byte aligned, 4-byte accesses otherwise; that
+ *   changes the loads, not the bits of p. The dispatch is a function of (c, hw, alignment) alone:
+ *   bcnn_hip_dice_loss_path: 0 the register path (hw > 1 and c <= bcnn_hip_softmax_loss_c_reg(): one forward launch holds
+ *     a pixel's logits and the per-class sums in registers), 1 the wide path (a streaming softmax writes p, a second,
+ *     class-major launch forms the sums from p; hw == 1 goes here too, behind a one-wave-per-row softmax), -1 a refused
+ *     shape: an extent below 1 or a tensor of 2^31 elements or more. bcnn_hip_dice_loss_workspace_size is 0 for those and
+ *     for an unknown reduce. Both are host code. On those, an ignore label of 2^24 or more or a negative or non-finite
+ *     smooth the two workers exit like the other entry points handed arguments they cannot run.
+ *   With the dispatch trace on the launches are named dice_loss_fwd, dice_loss_sums (wide path only), dice_loss_finalize
+ *   and dice_loss_bwd.
+ * ------------------------------------------------------------------------------------------- */
+enum { BCNN_HIP_DICE_REDUCE_BATCH = 0, BCNN_HIP_DICE_REDUCE_IMAGE = 1 };
+typedef struct bcnn_hip_dice_loss_record {
+    float loss, ce, dice;
+    float grad_ce; /* ce_weight / max(V, 1) */
+    int valid, ignored, out_of_range, correct;
+} bcnn_hip_dice_loss_record;
+typedef struct BcnnDiceLossFwdArgs {
+    const float *x;
+    const float *label; /* NULL: p only */
+    float *p;
+    float *workspace;   /* NULL: p only */
+    int n, c, hw;
+    int ignore_label, squared, reduce;
+    float ce_weight, dice_weight, smooth;
+} BcnnDiceLossFwdArgs;
+typedef struct BcnnDiceLossBwdArgs {
+    const float *p, *label;
+    const float *workspace; /* as the forward left it */
+    float *dx;
+    int n, c, hw;
+    int ignore_label, squared, reduce;
+    float dice_weight;
+    int overwrite;
+} BcnnDiceLossBwdArgs;
+void bcnn_hip_dice_loss_forward(const BcnnDiceLossFwdArgs *args);
+void bcnn_hip_dice_loss_backward(const BcnnDiceLossBwdArgs *args);
+size_t bcnn_hip_dice_loss_workspace_size(int n, int c, int hw, int reduce);
+int bcnn_hip_dice_loss_path(int n, int c, int hw, int aligned);
+
+/* ---------------------------------------------------------------------------------------------
  * Label maps at each image's own size (label_map.hip). No reference counterpart: the output end of semantic
  * segmentation, as bcnn_hip_yolo_detect_batch is the detector's. From x_d, [n][c][h][w] on the device (logits or
  * probabilities: the call resamples what it is given), image b of the call gets one class index per pixel of ITS extent:
