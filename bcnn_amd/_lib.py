@@ -117,6 +117,7 @@ SIGNATURES = {
     "bcnn_hip_patch_expand_backward": (None, [vp]),
     "bcnn_hip_patch_expand_path": (i, [i, i, i, i, i]),
     "bcnn_hip_attention_forward": (None, [vp] * 5 + [i] * 6 + [f]),
+    "bcnn_hip_attention_forward_bf16": (None, [vp] * 5 + [i] * 6 + [f]),
     "bcnn_hip_attention_backward": (None, [vp] * 9 + [i] * 6 + [f, i, i, i]),
     "bcnn_hip_attention_lse_size": (sz, [i, i, i]),
     "bcnn_hip_window_attention_forward": (None, [vp]),

@@ -476,7 +476,8 @@ class Net:
 
     def set_inference_precision(self, precision):
         """bcnn_set_inference_precision: PRECISION_BF16 runs every convolution node of a PREDICT / VALID forward on the
-        bf16 matrix cores (fp32 accumulator; depthwise (dilated or not), deconvolution, dilated-convolution and full-connected nodes stay fp32); a TRAIN-mode
+        bf16 matrix cores (fp32 accumulator; depthwise (dilated or not), deconvolution, dilated-convolution and full-connected nodes stay fp32) and the attention node's forward
+        too (attention_bf16.hip; the window-attention node stays fp32); a TRAIN-mode
         pass is never affected. Returns the bcnn_status (1 = BCNN_INVALID_PARAMETER for an unknown value)."""
         return self.L.bcnn_set_inference_precision(self.net, precision)
 

@@ -199,7 +199,7 @@ typedef struct bcnn_hip_context {
     int in_pass;
     int no_side_stream; /* bcnn_set_weight_gradient_stream(net, 0) */
     uint64_t dropout_seed; /* bcnn_set_dropout_seed; 0 until set */
-    int inference_precision; /* bcnn_set_inference_precision (a bcnn_precision); read by the convolution node outside TRAIN mode */
+    int inference_precision; /* bcnn_set_inference_precision (a bcnn_precision); read through bcnn_bf16_inference */
     int loader_on_device; /* bcnn_set_loader_on_device: bcnn_loader_next makes the input batch with bcnn_hip_augment_batch */
     void *loader_stage;   /* its host-side gather block (bcnn_data.c: loader_stage); freed by bcnn_free_loader_stage */
     int loader_decode_on_device; /* bcnn_set_loader_decode_on_device: JPEG entries of a list batch that goes the device way
@@ -236,6 +236,13 @@ struct bcnn_net {
 #endif
     int num_threads;
 };
+
+#ifdef BCNN_USE_HIP
+/* bcnn_set_inference_precision(BCNN_PRECISION_BF16) is in force: only outside TRAIN mode (the convolution and the attention node) */
+static inline int bcnn_bf16_inference(const bcnn_net *net) {
+    return net->mode != BCNN_MODE_TRAIN && ((const bcnn_hip_context *)net->hip_ctx)->inference_precision == BCNN_PRECISION_BF16;
+}
+#endif
 
 /* ---- net / node / tensor helpers (reference: bcnn_net.h:69-76, bcnn_node.h:50-51, bcnn_tensor.h:37-63) */
 bcnn_status bcnn_net_add_node(bcnn_net *net, bcnn_node node);

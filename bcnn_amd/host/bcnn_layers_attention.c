@@ -95,8 +95,10 @@ void bcnn_forward_attention_layer(bcnn_net *net, bcnn_node *node) {
     const size_t rows = bcnn_hip_attention_lse_size(q->n, p->num_heads, q->h * q->w);
     /* PREDICT stores no log-sum-exp; nor does a net whose buffer a resize without need_realloc could not follow */
     float *lse = (net->mode != BCNN_MODE_PREDICT && p->lse_gpu && rows <= p->lse_capacity) ? p->lse_gpu : NULL;
-    bcnn_hip_attention_forward(q->data_gpu, k->data_gpu, v->data_gpu, o->data_gpu, lse, q->n, p->num_heads,
-                               q->c / p->num_heads, v->c / p->num_heads, q->h * q->w, k->h * k->w, p->scale);
+    /* bf16 inference (never a TRAIN pass): the same call on the bf16 matrix cores, whatever the shape */
+    (bcnn_bf16_inference(net) ? bcnn_hip_attention_forward_bf16 : bcnn_hip_attention_forward)(
+        q->data_gpu, k->data_gpu, v->data_gpu, o->data_gpu, lse, q->n, p->num_heads, q->c / p->num_heads,
+        v->c / p->num_heads, q->h * q->w, k->h * k->w, p->scale);
     p->out_kept = 0;
     if (lse && dst_rewritten(net, node)) { /* the backward's O, out of the in-place node's reach */
         const size_t elems = (size_t)bcnn_tensor_size(o);

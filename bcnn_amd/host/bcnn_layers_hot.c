@@ -172,11 +172,6 @@ static const float *announce_bnfold(bcnn_net *net, const bcnn_conv_param *p) {
     return net->tensors[bn->src[0]].data_gpu; /* the batch-norm's INPUT: what the convolution multiplies */
 }
 
-/* bcnn_set_inference_precision(BCNN_PRECISION_BF16) is in force: only outside TRAIN mode */
-static int bcnn_bf16_inference(const bcnn_net *net) {
-    return net->mode != BCNN_MODE_TRAIN && ((const bcnn_hip_context *)net->hip_ctx)->inference_precision == BCNN_PRECISION_BF16;
-}
-
 void bcnn_forward_conv_layer(bcnn_net *net, bcnn_node *node) {
     bcnn_conv_param *p = (bcnn_conv_param *)node->param;
     conv_io io = conv_tensors(net, node);

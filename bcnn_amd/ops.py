@@ -784,6 +784,14 @@ def attention_forward(q, k, v, o, lse, heads, scale=0.0):
     _lib.load().bcnn_hip_attention_forward(_f32(q), _f32(k), _f32(v), _f32(o), _f32(lse), n, heads, d, c, lq, lk, scale)
 
 
+def attention_forward_bf16(q, k, v, o, lse, heads, scale=0.0):
+    """bcnn_hip_attention_forward_bf16: attention_forward on the bf16 matrix cores (inference): fp32 tensors, q, k, v and
+    the exponentiated scores rounded to bf16 as operands, fp32 accumulation and softmax"""
+    n, d, c, lq, lk = _attention_dims(q, k, v, heads)
+    assert o.numel() == n * heads * c * lq and (lse is None or lse.numel() == n * heads * lq)
+    _lib.load().bcnn_hip_attention_forward_bf16(_f32(q), _f32(k), _f32(v), _f32(o), _f32(lse), n, heads, d, c, lq, lk, scale)
+
+
 def attention_backward(q, k, v, o, lse, do, dq, dk, dv, heads, scale=0.0, overwrite=(False, False, False)):
     """bcnn_hip_attention_backward from the stored o and lse: each of dq, dk, dv is assigned (its overwrite flag) or added
     to, or is None (skipped)"""

@@ -629,13 +629,16 @@ BCNN_API void bcnn_set_dropout_seed(bcnn_net *net, uint64_t seed);
  * otherwise). An 8-byte read-back; either pointer may be NULL. BCNN_INVALID_PARAMETER if the net has no such node.
  * A batch without a positive pair gives loss 0 and P 0. */
 BCNN_API bcnn_status bcnn_get_lifted_struct_loss(bcnn_net *net, float *loss, int *num_constraints);
-/* Precision of the convolution nodes in an inference forward (default BCNN_PRECISION_FP32). With BCNN_PRECISION_BF16 every
+/* Precision of the convolution and attention nodes in an inference forward (default BCNN_PRECISION_FP32). With BCNN_PRECISION_BF16 every
  * convolution node of a forward pass in BCNN_MODE_PREDICT or BCNN_MODE_VALID runs on the bf16 matrix cores: activations and
  * weights stay fp32 in memory and are rounded to bf16 (round-to-nearest-even) inside the kernel, the accumulator is fp32,
  * bias / fused batch-norm / activation are computed as before. The output of a node then differs from the fp32 one by at
  * most about 2^-8 * sum |x| |w| per element, which is outside the 1e-4 parity the default path holds:
  * hence opt-in. Every convolution node takes it, whatever its shape, so that the numerics of a net are predictable.
- * Depthwise-convolution (dilated or not), deconvolution, dilated-convolution and full-connected nodes stay fp32. The value may be set in any mode and takes
+ * The attention node (bcnn_add_attention_layer) takes it too: its two products run on the bf16 matrix cores with q, k, v and
+ * the exponentiated scores rounded to bf16 as operands, fp32 accumulators and an fp32 softmax; for q, k, v exact in bf16 its
+ * output is within 2^-9 max|v| of the exact one.
+ * Depthwise-convolution (dilated or not), deconvolution, dilated-convolution, full-connected and window-attention nodes stay fp32. The value may be set in any mode and takes
  * effect only while the net's mode is PREDICT or VALID: a BCNN_MODE_TRAIN pass never uses it (its backward needs the fp32
  * forward). An unknown value returns BCNN_INVALID_PARAMETER and changes nothing. Config files: `inference_precision=bf16`
  * (or `fp32`) in the [net] section. */

@@ -787,9 +787,16 @@ int bcnn_hip_patch_expand_path(int n, int c_in, int h, int w, int block);
  *   d and c outside 1 .. 128, a negative extent and a tensor of 2^31 elements or more exit. With the dispatch trace on the
  *   launches are named attention_fwd, attention_bwd:dl, attention_bwd:kv, attention_bwd:q.
  *   bcnn_hip_attention_lse_size: the floats behind lse_d.
+ *   bcnn_hip_attention_forward_bf16 (attention_bf16.hip): the same forward on the bf16 matrix cores, for inference. The
+ *     tensors stay fp32 in memory; q, k, v and the exponentiated scores are rounded to bf16 (round-to-nearest-even) as
+ *     operands of the two products, which accumulate in fp32; scale, maximum, sum (of the unrounded exponentials),
+ *     rescale and normalisation are fp32. For q, k, v exact in bf16, o is within 2^-9 max|v| of the exact result. The same
+ *     arguments, refusals and determinism; lse_d may be NULL. The launch is named attention_fwd_bf16. No backward.
  * ------------------------------------------------------------------------------------------- */
 void bcnn_hip_attention_forward(const float *q_d, const float *k_d, const float *v_d, float *o_d, float *lse_d, int n,
                                 int heads, int d, int c, int lq, int lk, float scale);
+void bcnn_hip_attention_forward_bf16(const float *q_d, const float *k_d, const float *v_d, float *o_d, float *lse_d, int n,
+                                     int heads, int d, int c, int lq, int lk, float scale);
 void bcnn_hip_attention_backward(const float *q_d, const float *k_d, const float *v_d, const float *o_d, const float *lse_d,
                                  const float *do_d, float *dq_d, float *dk_d, float *dv_d, int n, int heads, int d, int c,
                                  int lq, int lk, float scale, int overwrite_q, int overwrite_k, int overwrite_v);
