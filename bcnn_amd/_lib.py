@@ -121,6 +121,7 @@ SIGNATURES = {
     "bcnn_hip_attention_backward": (None, [vp] * 9 + [i] * 6 + [f, i, i, i]),
     "bcnn_hip_attention_lse_size": (sz, [i, i, i]),
     "bcnn_hip_window_attention_forward": (None, [vp]),
+    "bcnn_hip_window_attention_forward_bf16": (None, [vp]),
     "bcnn_hip_window_attention_backward": (None, [vp]),
     "bcnn_hip_window_attention_check": (i, [i] * 8),
     "bcnn_hip_batchnorm_forward": (None, [vp] * 10 + [i, i, i, i, i]),

@@ -27,21 +27,6 @@
 
 namespace bcnn_hip {
 
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-// two fp32 -> two bf16 in one dword, round-to-nearest-even (lo: the lower reduction index)
-__device__ __forceinline__ unsigned attn_pack_bf16(float lo, float hi) {
-    f32x2 v = {lo, hi};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
-}
-__device__ __forceinline__ bf16x8 attn_pack8(float a, float b, float c, float d, float e, float f, float g, float h) {
-    u32x4 p = {attn_pack_bf16(a, b), attn_pack_bf16(c, d), attn_pack_bf16(e, f), attn_pack_bf16(g, h)};
-    return __builtin_bit_cast(bf16x8, p);
-}
-
 // row[j .. j + 3] of a row of L floats; `ok` false (a row past the matrix) and columns from L on read as zero. vec: L is a
 // multiple of 4 and the row 16-byte aligned, and j is a multiple of 4: j < L then holds for all four
 __device__ __forceinline__ float4 attn_bf16_load4(const float* base, size_t row_off, int j, int L, bool ok, bool vec) {

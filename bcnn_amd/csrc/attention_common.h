@@ -1,6 +1,6 @@
 // attention_common.h -- what the attention node's fp32 kernels (attention.hip) and its bf16 inference forward
 // (attention_bf16.hip) share: the limits and refusals, the scale, the exponential, the instance ladder and the store of an
-// accumulator whose lanes hold one query each.
+// accumulator whose lanes hold one query each; and the fp32 -> bf16 packing of both bf16 forwards (attention_window_bf16.hip too).
 #pragma once
 #include "conv_common.h"
 
@@ -13,6 +13,22 @@ constexpr float kLog2e = 1.4426950408889634f;
 // exp(x) for x <= 0 (and -inf): the maximum is subtracted BEFORE the scaling to base 2, so the argument's rounding error is
 // relative to the distance from the maximum, not to the score
 __device__ __forceinline__ float attn_exp(float x) { return __builtin_amdgcn_exp2f(x * kLog2e); }
+
+// ---- the bf16 inference forwards (attention_bf16.hip, attention_window_bf16.hip) ---------------------------------------------
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// two fp32 -> two bf16 in one dword, round-to-nearest-even (lo: the lower reduction index)
+__device__ __forceinline__ unsigned attn_pack_bf16(float lo, float hi) {
+    f32x2 v = {lo, hi};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2));
+}
+__device__ __forceinline__ bf16x8 attn_pack8(float a, float b, float c, float d, float e, float f, float g, float h) {
+    u32x4 p = {attn_pack_bf16(a, b), attn_pack_bf16(c, d), attn_pack_bf16(e, f), attn_pack_bf16(g, h)};
+    return __builtin_bit_cast(bf16x8, p);
+}
 
 // acc[tile][r] (row tile * 32 + mfma_row(r, lane), column x) times f, assigned or added to dst [rows][L]
 template <int TILES>

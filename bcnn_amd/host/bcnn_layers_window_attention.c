@@ -107,7 +107,8 @@ void bcnn_forward_window_attention_layer(bcnn_net *net, bcnn_node *node) {
                                      p->rel_bias ? net->tensors[node->src[3]].data_gpu : NULL,
                                      net->tensors[node->dst[0]].data_gpu, q->n, p->num_heads, q->c / p->num_heads,
                                      v->c / p->num_heads, q->h, q->w, p->window, p->shift, p->scale};
-    bcnn_hip_window_attention_forward(&a);
+    /* bf16 inference (never a TRAIN pass): the same call on the bf16 matrix cores, whatever the shape */
+    (bcnn_bf16_inference(net) ? bcnn_hip_window_attention_forward_bf16 : bcnn_hip_window_attention_forward)(&a);
 }
 
 void bcnn_backward_window_attention_layer(bcnn_net *net, bcnn_node *node) {

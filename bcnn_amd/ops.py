@@ -827,6 +827,15 @@ def window_attention_forward(q, k, v, table, o, heads, window, shift=0, scale=0.
     _lib.load().bcnn_hip_window_attention_forward(_C.byref(args))
 
 
+def window_attention_forward_bf16(q, k, v, table, o, heads, window, shift=0, scale=0.0):
+    """bcnn_hip_window_attention_forward_bf16: window_attention_forward on the bf16 matrix cores (inference): fp32 tensors,
+    q, k, v and the exponentiated scores rounded to bf16 as operands; scale, bias, mask, softmax and accumulation fp32"""
+    n, d, c, h, w = _window_attention_dims(q, k, v, heads, window, table)
+    assert o.numel() == v.numel()
+    args = _lib.WindowAttnFwdArgs(_f32(q), _f32(k), _f32(v), _f32(table), _f32(o), n, heads, d, c, h, w, window, shift, scale)
+    _lib.load().bcnn_hip_window_attention_forward_bf16(_C.byref(args))
+
+
 def window_attention_backward(q, k, v, table, do, dq, dk, dv, dtable, heads, window, shift=0, scale=0.0,
                               overwrite=(False, False, False)):
     """bcnn_hip_window_attention_backward: each of dq, dk, dv is assigned (its overwrite flag) or added to, dtable is added

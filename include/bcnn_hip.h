@@ -823,6 +823,13 @@ size_t bcnn_hip_attention_lse_size(int n, int heads, int lq);
  *   Launches (dispatch trace): window_attention_bias (the dense bias tile, only with a table), window_attention_fwd;
  *   window_attention_bias, window_attention_bwd, window_attention_bwd:bias (only with dtable).
  *   bcnn_hip_window_attention_check: 0, or the refusal code of the shape; host only. The entry points exit on a refused shape.
+ *   bcnn_hip_window_attention_forward_bf16 (attention_window_bf16.hip): the same forward on the bf16 matrix cores, for
+ *     inference. The tensors stay fp32 in memory; q, k, v and the exponentiated scores are rounded to bf16
+ *     (round-to-nearest-even) as operands of the two products, which accumulate in fp32; scale, bias (not rounded), region
+ *     mask, maximum, sum (of the unrounded exponentials) and normalisation are fp32. For q, k, v exact in bf16, o is within
+ *     2^-9 max|v| of the exact result. The same struct, refusals and determinism. A band of up to 4 adjacent windows is
+ *     staged by one workgroup; with w % 4 == 0 and q, k, v 16-byte aligned the loads are 16-byte loads, else element
+ *     loads: the same bits. Launches: window_attention_bias (only with a table), window_attention_fwd_bf16. No backward.
  * ------------------------------------------------------------------------------------------- */
 enum {
     BCNN_HIP_WINDOW_ATTN_BAD_EXTENT = 1,   /* n, heads, h or w below 1, or heads above 65535 */
@@ -849,6 +856,7 @@ typedef struct BcnnWindowAttnBwdArgs {
     int overwrite_q, overwrite_k, overwrite_v;
 } BcnnWindowAttnBwdArgs;
 void bcnn_hip_window_attention_forward(const BcnnWindowAttnFwdArgs *args);
+void bcnn_hip_window_attention_forward_bf16(const BcnnWindowAttnFwdArgs *args);
 void bcnn_hip_window_attention_backward(const BcnnWindowAttnBwdArgs *args);
 int bcnn_hip_window_attention_check(int n, int heads, int d, int c, int h, int w, int window, int shift);
 

@@ -19,6 +19,11 @@ Every (shape, shift, leg, repeat) runs in a fresh process: a warm-up of at least
 two device events. The summary is the median over the repeats with the spread. A process that finds no device fails.
 
     python tools/window_attention_time.py [--out profiles/window_attention.json]
+
+--bf16 times the bf16 inference forward (attention_window_bf16.hip) instead: the legs ours_fwd (the
+unchanged fp32 forward, the yardstick) and ours_fwd_bf16, alternating, under the same protocol:
+
+    python tools/window_attention_time.py --bf16 [--out profiles/window_attention_bf16.json]
 """
 import argparse
 import json
@@ -32,6 +37,7 @@ MIN_WARM_S = 0.08
 N, DIM = 32, 32
 SHAPES = {"stage1": (3, 56, 56, 7), "stage3": (12, 14, 14, 7), "stage4": (24, 7, 7, 7), "ws8": (3, 64, 64, 8)}
 LEGS = ("ours_fwd", "ours_fwdbwd", "global_fwd", "global_fwdbwd", "torch_fwd", "torch_fwdbwd")
+BF16_LEGS = ("ours_fwd", "ours_fwd_bf16")
 
 
 def _leg(name, shift, leg, iters):
@@ -50,8 +56,10 @@ def _leg(name, shift, leg, iters):
     if leg.startswith("ours"):
         o, dq, dk, dv, dtable = [torch.zeros_like(x) for x in (v, q, k, v, table)]
 
+        forward = ops.window_attention_forward_bf16 if leg.endswith("bf16") else ops.window_attention_forward
+
         def fn():
-            ops.window_attention_forward(q, k, v, table, o, heads, ws, shift)
+            forward(q, k, v, table, o, heads, ws, shift)
             if backward:
                 ops.window_attention_backward(q, k, v, table, do, dq, dk, dv, dtable, heads, ws, shift, overwrite=(True,) * 3)
     elif leg.startswith("global"):
@@ -120,6 +128,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--bf16", action="store_true", help="time the bf16 forward against the fp32 forward")
     ap.add_argument("--out", default=None, help="also write the raw record as JSON here")
     ap.add_argument("--shape", default=None, help=argparse.SUPPRESS)
     ap.add_argument("--shift", type=int, default=0, help=argparse.SUPPRESS)
@@ -128,7 +137,7 @@ def main():
     if a.shape:
         _leg(a.shape, a.shift, a.leg, a.iters)
         return
-    cases = [(name, shift, leg) for name in SHAPES for shift in (0, SHAPES[name][3] // 2) for leg in LEGS
+    cases = [(name, shift, leg) for name in SHAPES for shift in (0, SHAPES[name][3] // 2) for leg in (BF16_LEGS if a.bf16 else LEGS)
              if shift == 0 or not leg.startswith("global")]
     runs = []
     for rep in range(a.repeats):   # alternating: every case once per round
